@@ -2,6 +2,7 @@
 """bench.py — variant sites/s of the pedigree BN posterior on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ped10|ped5|ped15] [--sites S]
+                  [--full] [--dump-outputs DIR]
   N > 1 either way: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
   the process is one of the ranks; started as a plain command, bench.py launches those N ranks itself
   (as child processes, before anything here has touched the GPU) and relays rank 0's line.
@@ -18,7 +19,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
                (24N+1 read + 24N post + 24N single + 1 status per site)
                / mean kernel time from HIP events on the launch stream; peak 8000 GB/s.
   fp64_valu    the roofline that actually binds: executed fp64 ops/s vs 39.3 T/s.
-  cpu_baseline the oracle (plain-C port of the reference CPU path) timed on this host.
+A plain run sets up, warms up, times the K steps, checks their outputs and prints the line.  Everything
+that takes runs of its own comes with --full only:
+  cpu_baseline the oracle (plain-C port of the reference CPU path) timed on this host;
+  elim_engine, configs_1_ped5, configs_4_ped15, elim_N32, common_pedigrees, call_path, configs_3_strong
+               (N > 1) and the stream probe (roofline.stream_probe_GBps): the side measurements.
+--dump-outputs DIR writes what the last timed step computed (rank 0's sites) as DIR/<name>.npy: post and
+single (float64 [sites][N][3]), status (float32 [sites]) and site_index (float64, the global site number of
+each row) — a fixed, evenly spaced sample of the sites where the whole would exceed 48 MiB.
 """
 import argparse
 import json
@@ -70,7 +78,34 @@ def parse():
     ap.add_argument("--warm-only", action="store_true",
                     help="compile this run's generated kernels into the cache (plan-only contexts, no GPU call) and exit: "
                          "the profiling scripts do this BEFORE rocprofv3, under which the library refuses to spawn hipcc")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: CPU baseline, other engines / configurations / sizes, strong scaling, "
+                         "stream probe (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's sites, a fixed sample beyond 48 MiB) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(dirname, post, single, status, first_site):
+    """--dump-outputs: post / single / status of the last timed step as .npy files, with the global site number of every
+    row.  Beyond the budget, a fixed sample: evenly spaced sites, the same ones for the same arguments."""
+    import numpy as np
+    import torch
+
+    S, n = post.shape[0], post.shape[1]
+    k = min(S, DUMP_BUDGET_BYTES // (2 * n * 3 * 8 + 4 + 8))
+    idx = torch.arange(k, dtype=torch.int64, device=post.device) * S // k
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in (("post", post), ("single", single), ("status", status)):
+        a = t.index_select(0, idx).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    np.save(os.path.join(dirname, "site_index.npy"), (idx.cpu().numpy() + first_site).astype(np.float64))
 
 
 def fp64_ops_per_site(plan, n):
@@ -369,7 +404,7 @@ def warm_only(a):
     """Generate + compile (or find in the cache) every kernel a run with these arguments launches."""
     import famseq_amd as fs
 
-    names = [a.workload] + (["ped5", "ped15"] if a.workload == "ped10" and not a.no_side_configs else [])
+    names = [a.workload] + (["ped5", "ped15"] if a.full and a.workload == "ped10" and not a.no_side_configs else [])
     for name in names:
         ctx = fs.Context(fs.make_model(fs.synthetic_pedigree(name), lc=a.lc), device=-1)
         for kv in a.option:
@@ -483,6 +518,8 @@ def main():
         return time.perf_counter() - t0, ev
 
     elapsed, ev = timed_steps()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, post, single, status, first_site)
     if world > 1:
         dist.barrier()
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -520,7 +557,7 @@ def main():
     # BASELINE configs[3] read literally — 10 M sites in total, sharded over the ranks (strong scaling) — measured by the same
     # ranks right after the headline's weak-scaling steps, on each rank's first share of its resident (seeded) sites
     strong_out = None
-    if world > 1 and a.scaling == "weak" and a.workload == "ped10" and a.engine == "enum":
+    if a.full and world > 1 and a.scaling == "weak" and a.workload == "ped10" and a.engine == "enum":
         total = 10_000_000
         lo_, hi_ = fs.shard.site_range(total, rank, world)
         share = min(S, hi_ - lo_)
@@ -555,7 +592,7 @@ def main():
 
     # side measurement on every rank (same barriers): the exact sum-product engine on the same batch
     elim_out = None
-    if a.engine == "enum" and not a.no_elim and plan["elim_supported"]:
+    if a.full and a.engine == "enum" and not a.no_elim and plan["elim_supported"]:
         ref_post = post.clone()
         ctx.set_option("engine", fs.ENGINE_ELIM)
         e_el, ev_el = timed_steps()
@@ -583,7 +620,9 @@ def main():
         elim_out["roofline"]["stream_probe_note"] = ("bare elementwise kernel reading one fp64 array and writing two (famseq_stream_probe), "
                                                      "same arrays, same run: what this device sustains for this traffic shape")
 
-    probe_GBps = elim_out["roofline"]["stream_probe_GBps"] if elim_out else stream_probe_GBps(fs, torch, ctx, lk, post, single, stream)
+    probe_GBps = None
+    if a.full:
+        probe_GBps = elim_out["roofline"]["stream_probe_GBps"] if elim_out else stream_probe_GBps(fs, torch, ctx, lk, post, single, stream)
     if rank == 0:
         total_sites = job_sites
         value = total_sites * a.steps / elapsed
@@ -633,7 +672,7 @@ def main():
                          "bytes_per_site": bytes_per_site,
                          "read_GBps": S * (24 * n + 1) / (kernel_ms * 1e-3) / 1e9,
                          "frac_of_measured_copy_6290GBps": achieved / 6290.0,
-                         "stream_probe_GBps": probe_GBps, "frac_of_stream_probe": achieved / probe_GBps,
+                         "stream_probe_GBps": probe_GBps, "frac_of_stream_probe": achieved / probe_GBps if probe_GBps else None,
                          "note": ("a 3^N enumeration is bound by the fp64 vector ALU for N >= 7 (arithmetic intensity 3^N/24 "
                                   "flop/B): see fp64_valu; the same marginals by sum-product are HBM-bound: see elim_engine")
                          if n >= 7 and a.engine == "enum" else None},
@@ -659,7 +698,7 @@ def main():
             out["config"]["lc"] = a.lc
         if elim_out is not None:
             out["elim_engine"] = elim_out
-        if a.workload == "ped10" and world == 1 and a.engine == "enum" and not a.no_side_configs:
+        if a.full and a.workload == "ped10" and world == 1 and a.engine == "enum" and not a.no_side_configs:
             # a 0.1 ms launch: K = 5 is too few to time it, and the extra steps cost nothing
             out["configs_1_ped5"] = side_config(fs, torch, dev, stream, "ped5", max(a.steps, 20), max(a.warmup, 5))
             # at BASELINE's 1 M sites the 120 MB of input stay in the 256 MB Infinity Cache from step to step;
@@ -678,7 +717,7 @@ def main():
                                        for w in ("trio", "quad")}
             # what the command line launches: the fused call path on packed PLs, and the text records behind it
             out["call_path"] = side_call_path(fs, torch, dev, stream, "ped10", max(a.steps, 20), max(a.warmup, 5), 1_000_000)
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(ped, cfg, a.cpu_seconds, n)
             out["speedup_vs_cpu_all_cores"] = value / out["cpu_baseline"]["value"]
         print(json.dumps(out))

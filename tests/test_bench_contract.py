@@ -23,6 +23,24 @@ def test_bench_flags_and_helpers(monkeypatch):
     assert bench.HBM_PEAK_GBPS == 8000.0
 
 
+def test_bench_full_and_dump_flags(monkeypatch):
+    """A plain run is the headline alone (--full adds the side measurements); --dump-outputs names a directory;
+    --steps is the number of timed steps, so it must be at least one."""
+    import pytest
+
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out_dir"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out_dir"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_cpu_baseline_leg_runs_on_a_tiny_budget():
     sys.path.insert(0, ROOT)
     bench = importlib.import_module("bench")

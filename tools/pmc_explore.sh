@@ -8,7 +8,7 @@ R=$PWD
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 # the library refuses to spawn hipcc under a profiler: make sure this run's kernels are in the cache first
-python3 $R/bench.py --warm-only "$@" > $O/warm.log 2>&1 || { echo "warm-up failed"; cat $O/warm.log; exit 1; }
+python3 $R/bench.py --warm-only --full "$@" > $O/warm.log 2>&1 || { echo "warm-up failed"; cat $O/warm.log; exit 1; }
 cd /tmp
 i=0
 for c in \
@@ -19,7 +19,7 @@ for c in \
   "TCC_EA0_WRREQ_STALL_sum TCC_EA0_WRREQ_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_64B_sum" \
   "GRBM_GUI_ACTIVE GRBM_COUNT"; do
   i=$((i+1))
-  timeout -k 10 170 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$i -- python3 $R/bench.py --no-cpu-baseline --no-side-configs --sites 1000000 --steps 2 --warmup 1 "$@" > $O/pmc_$i.log 2>&1
+  timeout -k 10 170 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$i -- python3 $R/bench.py --full --no-cpu-baseline --no-side-configs --sites 1000000 --steps 2 --warmup 1 "$@" > $O/pmc_$i.log 2>&1
   echo "pass $i rc=$?"
 done
 cd $R

@@ -10,16 +10,16 @@ R=$PWD
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 # the library refuses to spawn hipcc under a profiler: make sure this run's kernels are in the cache first
-python3 $R/bench.py --warm-only "$@" > $O/warm.log 2>&1 || { echo "warm-up failed"; cat $O/warm.log; exit 1; }
+python3 $R/bench.py --warm-only --full "$@" > $O/warm.log 2>&1 || { echo "warm-up failed"; cat $O/warm.log; exit 1; }
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --no-cpu-baseline "$@" > $O/kt.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --full --no-cpu-baseline "$@" > $O/kt.log 2>&1
 echo "kernel-trace rc=$?"
 for c in FETCH_SIZE WRITE_SIZE \
   "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY" \
   "SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64" \
   "GRBM_GUI_ACTIVE GRBM_COUNT"; do
   tag=$(echo $c | cut -d" " -f1)
-  timeout -k 10 170 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$tag -- python3 $R/bench.py --no-cpu-baseline --sites 1000000 --steps 2 --warmup 1 "$@" > $O/pmc_$tag.log 2>&1
+  timeout -k 10 170 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$tag -- python3 $R/bench.py --full --no-cpu-baseline --sites 1000000 --steps 2 --warmup 1 "$@" > $O/pmc_$tag.log 2>&1
   echo "$tag rc=$?"
 done
 cd $R
