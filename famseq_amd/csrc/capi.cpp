@@ -79,7 +79,8 @@ struct famseq_ctx {
   int grp_blocks_per_cu[kEnumMaxGroupDigits + 1] = {};
   int group_digits = -1, last_group_digits = 0;
   int lane_reads_rows = -1;  // does the lane call-path kernel re-read fp64 rows from global memory (unknown until asked)
-  int lane_call_variant = -1;  // the variant jit_pick_variant took for it (the answer depends on the variant)
+  int lane_call_variant = -1;  // the plain lane variant whose block shape and fencing its call-path form has (the answer depends on it)
+  int lane_call_pick = -1, elim_call_variant = -1;  // which variant of each call-path family jit_pick_variant took (famseq_plan_json)
   int64_t lane_min_sites = 256;  // below this the compiled-in team kernel answers at once (no per-pedigree compile for tiny calls) ...
   // ... unless the generated kernel for that batch is loaded or on disk already (a pre-built pedigree, or one this user has run
   // before): then nothing has to be waited for and it serves every batch size (team kernel: 0.0237 ms per 256 ten-member
@@ -406,7 +407,8 @@ bool load_call_kernel(famseq_ctx *c, bool elim) {
     const Model &mdl = c->model;
     std::string src;
     if (elim) {
-      src = jit_pick_variant([&mdl](int v) { return elim_source(mdl, v, true); }, kElimCallVariants, nullptr, elim_first_variant(mdl, true));
+      src = jit_pick_variant([&mdl](int v) { return elim_source(mdl, v, true); }, kElimCallVariants, &c->elim_call_variant,
+                             elim_first_variant(mdl, true));
     } else {
       // the same block size as the plain lane kernel runs with (variants 0-1 / 2-3: kEnumVariants), so that a batch
       // gives the same bits whether it goes through the fused kernel or through the separate stages
@@ -415,6 +417,7 @@ bool load_call_kernel(famseq_ctx *c, bool elim) {
       int pick = 0;
       // v & 1: the single posterior fenced member by member; v & 2: the leaner stage-out (see kElimCallVariants)
       src = jit_pick_variant([&mdl, base](int v) { return enumgen_source(mdl, base + (v & 1), 0, true, !(v & 2)); }, 4, &pick);
+      c->lane_call_pick = pick;
       c->lane_call_variant = base + (pick & 1);
       c->lane_reads_rows = enumgen_reads_global_rows(mdl, c->lane_call_variant) ? 1 : 0;
     }
@@ -725,7 +728,7 @@ int tune(famseq_ctx *c) {
   const bool had_lane = c->lane.fn != nullptr, had_elim = c->elim.fn != nullptr, had_lc = c->lane_call.fn != nullptr;
   jit_unload(c->lane), jit_unload(c->lane_call), jit_unload(c->elim);
   c->lane.path.clear(), c->lane_call.path.clear(), c->elim.path.clear();
-  c->lane_variant = c->lane_call_variant = c->elim_variant = -1;
+  c->lane_variant = c->lane_call_variant = c->lane_call_pick = c->elim_variant = -1;
   c->lane_reads_rows = -1;
   if (had_lane && !load_lane(c)) return fail(c, FAMSEQ_E_HIP, "lane kernel unavailable after tuning: " + c->lane_error);
   if (had_lc && !load_call_kernel(c, false)) return fail(c, FAMSEQ_E_HIP, "call-path kernel unavailable after tuning: " + c->call_error[0]);
@@ -799,7 +802,7 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
     if (lane) {  // whatever this context holds of that kernel is dropped; the next use starts from the note
       jit_unload(c->lane), jit_unload(c->lane_call);
       c->lane.path.clear(), c->lane_call.path.clear();
-      c->lane_variant = c->lane_call_variant = -1;
+      c->lane_variant = c->lane_call_variant = c->lane_call_pick = -1;
       c->lane_reads_rows = -1;
     } else {
       jit_unload(c->elim);
@@ -820,7 +823,11 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
     return 0;
   }
   else if (k == "call_kernels") {  // build (and on a device ctx load) the fused call-path forms now rather than on first use
-    if (value != 1) return fail(c, FAMSEQ_E_ARG, "call_kernels takes 1");
+    if (value != 1 && value != 2) return fail(c, FAMSEQ_E_ARG, "call_kernels takes 1 (both forms) or 2 (the form of this ctx's engine)");
+    if (value == 2) {
+      const bool elim = c->engine == FAMSEQ_ENGINE_ELIM;
+      return load_call_kernel(c, elim) ? 0 : fail(c, FAMSEQ_E_HIP, "call-path kernel unavailable: " + c->call_error[elim]);
+    }
     if (!load_call_kernel(c, false)) return fail(c, FAMSEQ_E_HIP, "call-path kernel unavailable: " + c->call_error[0]);
     if (elim_supported(c->model, nullptr) && !load_call_kernel(c, true))
       return fail(c, FAMSEQ_E_HIP, "call-path kernel unavailable: " + c->call_error[1]);
@@ -905,7 +912,9 @@ extern "C" const char *famseq_plan_json(famseq_ctx *c) {
   for (int d = 1; d <= kEnumMaxGroupDigits; ++d) c->json += std::string(d > 1 ? "," : "") + "\"" + json_str(c->grp[d].path) + "\"";
   c->json += "],\"enum_lane_call_code_object\":\"" + json_str(c->lane_call.path) + "\",\"elim_call_code_object\":\"" +
              json_str(c->elim_call.path) + "\",\"enum_lane_call_error\":\"" + json_str(c->call_error[0].substr(0, 300)) + "\",\"elim_call_error\":\"" +
-             json_str(c->call_error[1].substr(0, 300)) + "\",\"enum_lane_call_reads_rows\":" + std::to_string(c->lane_reads_rows) + ",\"tune\":\"" +
+             json_str(c->call_error[1].substr(0, 300)) + "\",\"enum_lane_call_reads_rows\":" + std::to_string(c->lane_reads_rows) +
+             ",\"enum_lane_call_variant\":" + std::to_string(c->lane_call_pick) + ",\"elim_call_variant\":" +
+             std::to_string(c->elim_call_variant) + ",\"tune\":\"" +
              json_str(c->tune_report) + "\"}";
   return c->json.c_str();
 }

@@ -11,9 +11,10 @@
 //                FGT = arg-max with strict '<' from -1 (family.cpp:636-665), gathered in VCF
 //                column order (get_postProb(true), family.cpp:584-596).
 // Both are one-element-per-lane streaming kernels (coalesced 8 B/lane).  A workgroup walks tiles of
-// kTileSites sites; inside a tile the element index is a 16-bit number, so site / member / genotype
-// come from two multiply-shift divisions (exact for n < 2^16, divisors <= 510: the launchers check
-// members <= 170) instead of the 64-bit integer divisions a flat index over n_sites * W3 costs.
+// tile_sites(w3) sites — 128, fewer where a row of w3 = 3 * members doubles is wider than 510 — so that
+// inside a tile the element index is a 16-bit number, and site / member / genotype come from two
+// multiply-high divisions (exact for n, d < 2^16: the launchers check 3 * members < 2^16) instead of the
+// 64-bit integer divisions a flat index over n_sites * W3 costs.
 // phred_call is bound by its two fp64 logarithms per element (VALU; phred_src.h), unpack_pl16 by HBM.
 // Batches served by the generated kernels do both inside the posterior kernel (elim_codegen.cpp kCallHelpers);
 // these two remain for the compiled-in team kernel and the lanes-per-site mode.
@@ -26,26 +27,28 @@ namespace famseq {
 
 namespace {
 
-constexpr int kTileSites = 128;  // 128 * 3 * kMaxIoMembers = 65280 elements per tile (must stay < 2^16)
-constexpr int kMaxIoMembers = 170;  // r / 3 as (r * 171) >> 9 is exact for r < 512
+constexpr int kTileSites = 128;
+constexpr int kMaxIoMembers = 21845;  // a row of 3 * 21845 = 65535 doubles: one site per tile still indexes below 2^16
 
-// n / d for n < 2^16, 1 <= d <= 510: the high word of n * (2^32 / d + 1) (error < n / 2^32 < 1 / d)
+// sites per tile for rows of w3 doubles: at most 128, and tile * w3 < 2^16 (128 up to 170 members, 1 at kMaxIoMembers)
+__host__ __device__ constexpr unsigned tile_sites(unsigned w3) { return 0xFFFFu / w3 < kTileSites ? 0xFFFFu / w3 : kTileSites; }
+// n / d for n < 2^16, 1 <= d < 2^16: the high word of n * (2^32 / d + 1) (error < n / 2^32 < 1 / d)
 __device__ __forceinline__ unsigned div_small(unsigned n, unsigned magic) { return __umulhi(n, magic); }
 __host__ __device__ constexpr unsigned magic_for(unsigned d) { return 0xFFFFFFFFu / d + 1; }
 
 __global__ __launch_bounds__(256) void unpack_pl16_kernel(const uint16_t *__restrict__ pl, const int32_t *__restrict__ col_of_member,
                                                           const double *__restrict__ lut, int n_members, int n_seq,
                                                           long n_sites, double *__restrict__ lk) {
-  const unsigned w3 = 3 * n_members, mw3 = magic_for(w3);
-  const long tiles = (n_sites + kTileSites - 1) / kTileSites;
+  const unsigned w3 = 3 * n_members, mw3 = magic_for(w3), m3 = magic_for(3), tile = tile_sites(w3);
+  const long tiles = (n_sites + tile - 1) / tile;
   for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
-    const long site0 = t * kTileSites;
-    const unsigned ns = n_sites - site0 < kTileSites ? (unsigned)(n_sites - site0) : kTileSites;
+    const long site0 = t * tile;
+    const unsigned ns = n_sites - site0 < tile ? (unsigned)(n_sites - site0) : tile;
     const unsigned nel = ns * w3;
     const uint16_t *plt = pl + site0 * n_seq * 3;
     double *lkt = lk + site0 * w3;
     for (unsigned e = threadIdx.x; e < nel; e += 256) {
-      const unsigned s = div_small(e, mw3), r = e - s * w3, i = (r * 171) >> 9, g = r - 3 * i;
+      const unsigned s = div_small(e, mw3), r = e - s * w3, i = div_small(r, m3), g = r - 3 * i;
       const int c = col_of_member[i];
       double v = 1.0;  // unsequenced member, or sequenced but missing at this site (all three PLs 0xFFFF)
       if (c >= 0) {
@@ -81,19 +84,19 @@ __global__ __launch_bounds__(256) void phred_call_kernel(const double *__restric
                                                          const int32_t *__restrict__ seq_members, int n_members, int n_seq,
                                                          long n_sites, double *__restrict__ gpp, double *__restrict__ fpp,
                                                          int8_t *__restrict__ fgt) {
-  const unsigned w3 = 3 * n_seq, mw3 = magic_for(w3);
+  const unsigned w3 = 3 * n_seq, mw3 = magic_for(w3), m3 = magic_for(3), tile = tile_sites(w3);
   const double nan = __builtin_nan("");
   __shared__ __attribute__((aligned(16))) double s_lt[258];  // fs_phred's table: one 16-byte LDS read per logarithm
   for (int i = threadIdx.x; i < 258; i += 256) s_lt[i] = fs_logtab[i];
   __syncthreads();
-  const long tiles = (n_sites + kTileSites - 1) / kTileSites;
+  const long tiles = (n_sites + tile - 1) / tile;
   for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
-    const long site0 = t * kTileSites;
-    const unsigned ns = n_sites - site0 < kTileSites ? (unsigned)(n_sites - site0) : kTileSites;
+    const long site0 = t * tile;
+    const unsigned ns = n_sites - site0 < tile ? (unsigned)(n_sites - site0) : tile;
     const unsigned nel = ns * w3;
     const double *postt = post + site0 * n_members * 3, *singlet = single + site0 * n_members * 3;
     for (unsigned e = threadIdx.x; e < nel; e += 256) {
-      const unsigned s = div_small(e, mw3), r = e - s * w3, k = (r * 171) >> 9, g = r - 3 * k;
+      const unsigned s = div_small(e, mw3), r = e - s * w3, k = div_small(r, m3), g = r - 3 * k;
       const unsigned src = (s * n_members + seq_members[k]) * 3;
       const int st = status[site0 + s] & 3;
       gpp[site0 * w3 + e] = st == 1 ? nan : fs_phred(singlet[src + g], s_lt);
@@ -196,8 +199,8 @@ __global__ __launch_bounds__(256) void g6_probe_kernel(const double *__restrict_
   }
 }
 
-int grid_for(long n_sites) {
-  const long tiles = (n_sites + kTileSites - 1) / kTileSites;
+int grid_for(long n_sites, unsigned w3) {
+  const long tiles = (n_sites + tile_sites(w3) - 1) / tile_sites(w3);
   return (int)(tiles < 1 ? 1 : (tiles > 16384 ? 16384 : tiles));
 }
 
@@ -207,7 +210,7 @@ hipError_t launch_unpack_pl16(const uint16_t *d_pl, const int32_t *d_col_of_memb
                               int n_seq, int64_t n_sites, double *d_lk, hipStream_t stream) {
   if (n_sites <= 0) return hipSuccess;
   if (n_members < 1 || n_members > kMaxIoMembers) return hipErrorInvalidValue;  // div_small's range
-  hipLaunchKernelGGL(unpack_pl16_kernel, dim3(grid_for(n_sites)), dim3(256), 0, stream, d_pl,
+  hipLaunchKernelGGL(unpack_pl16_kernel, dim3(grid_for(n_sites, 3u * n_members)), dim3(256), 0, stream, d_pl,
                      d_col_of_member, d_lut, n_members, n_seq, (long)n_sites, d_lk);
   return hipGetLastError();
 }
@@ -223,8 +226,8 @@ hipError_t launch_phred_call(const double *d_post, const double *d_single, const
                              const int32_t *d_seq_members, int n_members, int n_seq, int64_t n_sites, double *d_gpp,
                              double *d_fpp, int8_t *d_fgt, hipStream_t stream) {
   if (n_sites <= 0 || n_seq <= 0) return hipSuccess;
-  if (n_seq > kMaxIoMembers || n_members > kMaxIoMembers) return hipErrorInvalidValue;  // div_small's range
-  hipLaunchKernelGGL(phred_call_kernel, dim3(grid_for(n_sites)), dim3(256), 0, stream, d_post, d_single,
+  if (n_seq > kMaxIoMembers || n_members < 1 || n_members > kMaxIoMembers) return hipErrorInvalidValue;  // div_small's range
+  hipLaunchKernelGGL(phred_call_kernel, dim3(grid_for(n_sites, 3u * n_seq)), dim3(256), 0, stream, d_post, d_single,
                      d_status, d_seq_members, n_members, n_seq, (long)n_sites, d_gpp, d_fpp, d_fgt);
   return hipGetLastError();
 }

@@ -298,8 +298,16 @@ std::string jit_pick_variant(const std::function<std::string(int)> &generate, in
   int best_scratch = -1, best_i = 0;
   first = std::max(0, std::min(first, n_variants - 1));
   if (const char *e = std::getenv("FAMSEQ_VARIANT_MIN")) first = std::max(0, std::min(std::atoi(e), n_variants - 1));  // tuning aid
+  int last = n_variants - 1;
+  if (const char *e = std::getenv("FAMSEQ_VARIANT_ONLY")) {  // tuning / test aid: exactly that variant, however much it spills
+    char *end = nullptr;
+    const long v = std::strtol(e, &end, 10);
+    if (end == e || *end || v < 0 || v >= n_variants)
+      throw std::runtime_error("FAMSEQ_VARIANT_ONLY=" + std::string(e) + ": this kernel has variants 0.." + std::to_string(n_variants - 1));
+    first = last = (int)v;
+  }
   std::string best_obj;
-  for (int v = first; v < n_variants; ++v) {
+  for (int v = first; v <= last; ++v) {
     std::string src = generate(v);
     int scratch = -1;
     const std::string obj = jit_compile(src, &scratch, /*note_suffices=*/true);

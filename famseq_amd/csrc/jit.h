@@ -37,6 +37,8 @@ bool jit_cached(const std::string &source);
 // The generators can trade instruction-level parallelism against register pressure
 // (`variant` 0 = most parallel).  Compiles variants in order and returns the source of the
 // first one that does not spill (more than 16 bytes per lane), or of the one that spills least.  *picked = its index.
+// $FAMSEQ_VARIANT_MIN=v (tuning aid): start the contest at v.  $FAMSEQ_VARIANT_ONLY=v (tuning / test aid): compile exactly
+// variant v, whatever it spills; throws when v is not an index of this kernel's variants.
 std::string jit_pick_variant(const std::function<std::string(int)> &generate, int n_variants, int *picked = nullptr, int first = 0);
 // The autotuner's note (famseq_set_option "tune"): which variant of the kernel whose variant-0 source is
 // `key_source` ran fastest on this machine — "<hash>.pick" next to the code objects.  -1: none.

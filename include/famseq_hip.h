@@ -162,7 +162,7 @@ const char *famseq_last_error(famseq_ctx *ctx);
  *   "phase_clock_report"  measuring aid: with FAMSEQ_PHASE_CLOCK=1 in the environment the generated kernels carry cycle marks between
  *                   their phases; this prints the plain kernels' shares (wave cycles per phase) on stderr and clears them
  *   "call_kernels"  1 = build the generated kernels' fused call-path forms now (famseq_bn_call_batch would on
- *                   its first call)
+ *                   its first call); 2 = only the form of the engine this ctx runs (what that first call loads)
  *   "engine"        FAMSEQ_ENGINE_ENUM (default) or FAMSEQ_ENGINE_ELIM; selecting ELIM generates the
  *                   kernel for this pedigree, compiles it (libhiprtc in-process; cached on disk) and fails with
  *                   FAMSEQ_E_ARG on a pedigree whose loops need more than three conditioned members

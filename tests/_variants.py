@@ -1,0 +1,113 @@
+"""Pedigrees and batches of the variant matrices (tests/test_gpu_variants.py on the device, its host twin in
+tests/test_generated_host.py).  Every generated kernel is emitted in several variants (csrc/enum_codegen.h kEnumVariants,
+csrc/elim_codegen.h kElimVariants / kElimCallVariants); which one a pedigree gets depends on the static picker, the tuner
+and the compiler's register allocation.  These fixtures let a test force each index in turn and compare."""
+import numpy as np
+
+import famseq_amd as fs
+from famseq_amd.prebuild_sets import random_pedigree
+
+# trio .. ped15:12 (both the 7- and the 6-member block of the lane kernel exist from there on), a first-cousin loop
+# (one conditioned member) and random_pedigree(15) (nine members, three unsequenced, three conditioned)
+PEDIGREES = ("trio", "quad", "ped5", "ped10", "ped15:12", "cousins", "random15")
+MRATE = 0.0  # mu = 0: a child that contradicts its parent is impossible, which the BN-failure site needs
+
+# planted sites (indices into every batch; the PL-shaped rows fill the rest)
+SHORTCUT, SINGLE_FAIL, BN_FAIL = 3, 5, 7
+LRC_SITES = range(10, 26)    # every sequenced member sharp at PL 150..165: the -LRC vote (lc = 1) flips inside this range
+TINY_SITES = range(30, 34)   # row sums below 1e-290: the guarded plain-division path of the normalisation
+
+
+def pedigree(name):
+    if name == "cousins":
+        ids, mids, fids = [1, 2, 3, 4, 5, 6, 7, 8, 9], [0, 0, 2, 2, 0, 0, 5, 4, 8], [0, 0, 1, 1, 0, 0, 3, 6, 7]
+        ped = fs.Pedigree(ids, mids, fids, [1, 2, 1, 2, 2, 1, 1, 2, 1], ["s%d" % i for i in ids])
+    elif name.startswith("random"):
+        ped = random_pedigree(int(name[6:]))[1]
+    else:
+        ped = fs.synthetic_pedigree(name)
+    ped.relations()
+    return ped
+
+
+def variant_flags(n_sites):
+    """All four (Known, chrX) combinations inside every wave of 64 lanes, and one wave uniform in chrX (sites 64..127)."""
+    flags = (np.arange(n_sites) % 4).astype(np.uint8)
+    flags[64:128] = 2 + (np.arange(64) % 2 == 1) * 1
+    flags[BN_FAIL] = 0
+    return flags
+
+
+def variant_batch(ped, n_sites, seed=0, max_pl=100):
+    """(lk, flags, has_bn_fail): PL-shaped rows (one genotype at PL 0, the others PL 1..max_pl - 1) and the planted sites
+    above (the BN failure where a sequenced member has a sequenced mother).  Wide pedigrees want a smaller max_pl (see
+    famseq_amd.synth.random_likelihoods)."""
+    assert n_sites >= 40
+    rng = np.random.RandomState(seed)
+    n = ped.n
+    seq = np.nonzero(ped.sequenced)[0]
+    pl = rng.randint(1, max_pl, size=(n_sites, n, 3)).astype(float)
+    pl[np.arange(n_sites)[:, None], np.arange(n)[None, :], rng.randint(0, 3, size=(n_sites, n))] = 0
+    lk = 10.0 ** (-pl / 10.0)
+    lk[SHORTCUT] = 1.0
+    lk[SHORTCUT, seq] = [1.0, 1e-17, 1e-20]
+    lk[SINGLE_FAIL, seq[-1]] = 0.0
+    mo, fa = ped.relations()
+    child = [i for i in seq if mo[i] >= 0 and ped.sequenced[mo[i]]]
+    c = child[0] if child else None
+    if c is not None:  # mother hom-ref, child hom-alt: impossible at mu = 0, autosome or chrX
+        lk[BN_FAIL, mo[c]] = [1.0, 0.0, 0.0]
+        lk[BN_FAIL, c] = [0.0, 0.0, 1.0]
+    for j, s in enumerate(LRC_SITES):
+        lk[s] = 1.0
+        g = rng.randint(0, 3, size=len(seq))
+        row = np.full((len(seq), 3), 10.0 ** (-(150 + j) / 10.0))
+        row[np.arange(len(seq)), g] = 1.0
+        lk[s, seq] = row
+    for s in TINY_SITES:
+        lk[s] = 1.0
+        lk[s, seq[0]] = [1e-300, 3e-301, 2e-300]
+    lk[:, ped.sequenced == 0, :] = 1.0
+    return lk, variant_flags(n_sites), c is not None
+
+
+def packed_batch(ped, lk, seq):
+    """(pl16, lk_pl): the rows of `lk` as packed integer PLs in the column order `seq` (PL = round(-10 log10 lk); a hard
+    zero 65534, beyond the table; the first site's first column missing: 0xFFFF x 3), and the fp64 rows the library's
+    table gives for them (pow(10, -PL / 10) below 4096, 0 from there, 1 for a missing sample or an unsequenced member)."""
+    import math
+
+    with np.errstate(divide="ignore"):
+        q = np.rint(-10 * np.log10(lk[:, seq, :]))
+    pl = np.minimum(np.where(np.isfinite(q), q, 65534), 65534).astype(np.uint16)
+    pl[0, 0] = fs.PL_MISSING
+    table = np.append([math.pow(10.0, -i / 10.0) for i in range(4096)], 0.0)
+    lk_pl = np.ones_like(lk)
+    lk_pl[:, seq, :] = table[np.minimum(pl.astype(np.int64), 4096)]
+    lk_pl[0, seq[0]] = 1.0
+    return pl, lk_pl
+
+
+def reference(ped, lk, flags):
+    import oracle
+
+    return oracle.OracleModel(ped.ids, ped.mids, ped.fids, ped.genders, ped.sequenced, mrate=MRATE).bn_batch(lk, flags, threads=8)
+
+
+def check_against_reference(post, single, status, ref, has_bn_fail=True, rtol=1e-9, what=""):
+    """status bit-exact, single posterior bit-exact, BN posterior within rtol, NaN on failed rows, shortcut rows bit-exact."""
+    assert np.array_equal(status, ref[2]), what
+    assert status[SHORTCUT] == 0x80 and status[SINGLE_FAIL] == 1 and (status[BN_FAIL] == 2 or not has_bn_fail), what
+    lrc = status[list(LRC_SITES)]
+    assert (lrc == 0x80).any() and (lrc == 0).any(), what  # both sides of the -LRC boundary
+    ok, s_ok = (status & 3) == 0, (status & 3) != 1
+    assert np.array_equal(single[s_ok].view(np.uint64), ref[1][s_ok].view(np.uint64)), what
+    cut = status == 0x80
+    assert np.array_equal(post[cut].view(np.uint64), ref[0][cut].view(np.uint64)), what
+    np.testing.assert_allclose(post[ok], ref[0][ok], rtol=rtol, atol=0, err_msg=what)
+    assert np.all(np.isnan(post[~ok])) and np.all(np.isnan(single[~s_ok])), what
+
+
+def same_bits(a, b):
+    """Outputs of two variants of one kernel: bit-identical (NaN patterns included)."""
+    return all(np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8)) for x, y in zip(a, b))

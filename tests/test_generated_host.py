@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import famseq_amd as fs
+import _variants as V
 from _cases import load_cases
 
 SHIM = r"""
@@ -601,3 +602,149 @@ def test_six_member_block_form_of_wide_pedigrees(name, tmp_path, monkeypatch):
     ok = (case.status & 3) == 0
     assert np.array_equal(single[(case.status & 3) != 1], case.single[(case.status & 3) != 1])
     np.testing.assert_allclose(post[ok], case.post[ok], rtol=1e-12, atol=0)
+
+
+# ---- every variant of every generated kernel family (the host twin of tests/test_gpu_variants.py) -----------------------------
+
+VARIANT_COUNTS = dict(lane=4, elim=12, lane_call=4, elim_call=8)  # csrc/enum_codegen.h, csrc/elim_codegen.h (the lane call form: capi.cpp)
+
+
+def forced_variant_source(model, family, v, base=0, monkeypatch=None):
+    """Source of variant v of one kernel family, generated for a one-lane workgroup and forced the way a user can: the plain
+    kernels through their pick notes (pick_lane / pick_elim), the call-path forms through $FAMSEQ_VARIANT_ONLY (the lane
+    call form on top of the plain lane variant `base`).  Checks that the plan names that variant."""
+    monkeypatch.delenv("FAMSEQ_VARIANT_ONLY", raising=False)
+    ctx = fs.Context(model, device=-1)
+    try:
+        if family == "lane":
+            ctx.set_option("pick_lane", v)
+            ctx.set_option("enum_impl", 1)
+            plan = ctx.plan()
+            assert plan["enum_lane_variant"] == v
+            obj = plan["enum_lane_code_object"]
+        elif family == "elim":
+            ctx.set_option("pick_elim", v)
+            ctx.set_option("engine", fs.ENGINE_ELIM)
+            plan = ctx.plan()
+            assert plan["elim_variant"] == v
+            obj = plan["elim_code_object"]
+        elif family == "lane_call":
+            ctx.set_option("pick_lane", base)
+            monkeypatch.setenv("FAMSEQ_VARIANT_ONLY", str(v))
+            ctx.set_option("call_kernels", 2)
+            plan = ctx.plan()
+            assert plan["enum_lane_variant"] == base and plan["enum_lane_call_variant"] == v and plan["elim_call_variant"] == -1
+            obj = plan["enum_lane_call_code_object"]
+        else:
+            monkeypatch.setenv("FAMSEQ_VARIANT_ONLY", str(v))
+            ctx.set_option("engine", fs.ENGINE_ELIM)
+            ctx.set_option("call_kernels", 2)
+            plan = ctx.plan()
+            assert plan["elim_call_variant"] == v and plan["enum_lane_call_variant"] == -1
+            obj = plan["elim_call_code_object"]
+    finally:
+        ctx.close()
+        monkeypatch.delenv("FAMSEQ_VARIANT_ONLY", raising=False)
+    return open(obj[:-6] + ".hip").read()
+
+
+def compile_host(src, cache, tag, call):
+    cpp, so = str(cache / ("%s.cpp" % tag)), str(cache / ("%s.so" % tag))
+    open(cpp, "w").write(host_source(src))
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-w", "-shared", "-fPIC", "-o", so, cpp])
+    fn = getattr(C.CDLL(so), "famseq_elim" if "famseq_elim(" in src else "famseq_enum_lane")
+    fn.restype = None
+    fn.argtypes = [C.c_void_p] * 5 + [C.c_long, C.c_void_p, C.c_double] + ([C.c_void_p] if call else [])
+    return fn
+
+
+def run_host_call(fn, model, ped, lk, flags):
+    """The call-path form on fp64 rows, every sequenced member a column in reversed order -> (gpp, fpp, fgt, status)."""
+    import math
+
+    seq = np.nonzero(ped.sequenced)[0][::-1].astype(np.int32).copy()
+    k, S = len(seq), len(flags)
+    col = np.full(20, -1, np.int32)
+    col[seq] = np.arange(k)
+    slot = output_slots(col, ped.n, k)
+    lut = np.array([math.pow(10.0, -i / 10.0) for i in range(4096)])
+    tc = np.ascontiguousarray(factor_tables(model))
+    gpp, fpp = np.full((S, k, 3), -7.0), np.full((S, k, 3), -7.0)
+    fgt, st = np.full((S, k), 9, np.int8), np.full(S, 77, np.uint8)
+    a = CallArgs(None, lut.ctypes.data, col.ctypes.data, slot.ctypes.data, gpp.ctypes.data, fpp.ctypes.data, fgt.ctypes.data, k,
+                 0xFFFFFFFF // (3 * k) + 1, 0xFFFFFFFF // k + 1 if k > 1 else 0)
+    rows = misaligned(lk.shape)
+    rows[...] = lk
+    fl = np.ascontiguousarray(flags, np.uint8)
+    fn(rows.ctypes.data, fl.ctypes.data, None, None, st.ctypes.data, S, tc.ctypes.data, float(model.lc), C.addressof(a))
+    return (gpp, fpp, fgt, st), seq
+
+
+def lane_bases(model, monkeypatch):
+    """The plain lane variants whose block shapes differ (0: the 7-member block, 2: the 6-member one): one base when they agree."""
+    srcs = [forced_variant_source(model, "lane", b, monkeypatch=monkeypatch) for b in (0, 2)]
+    strip = lambda s: re.sub(r"variant \d+", "", s)
+    return [0] if strip(srcs[0]) == strip(srcs[1]) else [0, 2]
+
+
+VARIANT_HOST_SITES = 160
+
+
+@pytest.mark.parametrize("family", ["lane", "elim", "lane_call", "elim_call"])
+@pytest.mark.parametrize("name", V.PEDIGREES)
+def test_every_variant_of_every_family(name, family, tmp_path, monkeypatch):
+    """Each variant index of each generated kernel family, forced and run on the host, on one batch: all four (Known, chrX)
+    combinations, a shortcut site, a single-posterior failure, a BN failure, the -LRC boundary and row sums below 1e-290.  The
+    plain kernels against the oracle; all variants of one family bit-identical to each other (fence levels, where the
+    likelihoods live and the per-chrX passes do not change the emitted arithmetic: fp-contract is off and every FMA is
+    written out) — except the lane kernel's 7- and 6-member blocks, whose sums group differently (enum_codegen.cpp, the
+    unrolled block): 1e-12 between them.  The call forms: bit-identical across their variants, and the Phred formula and
+    genotype call of the plain kernel's posteriors."""
+    ped = V.pedigree(name)
+    model = fs.make_model(ped, mrate=V.MRATE)
+    for k, v in dict(FAMSEQ_KERNEL_CACHE=str(tmp_path), FAMSEQ_KEEP_SRC="1", FAMSEQ_LANE_BT="1", FAMSEQ_ELIM_BT="1",
+                     FAMSEQ_LANE_MINWAVES="1", FAMSEQ_JIT_SOURCE_ONLY="1").items():
+        monkeypatch.setenv(k, v)
+    probe = fs.Context(model, device=-1)
+    assert probe.plan()["elim_supported"] == 1
+    probe.close()
+    lk, flags, has_bn_fail = V.variant_batch(ped, VARIANT_HOST_SITES)
+    plain = "elim" if family.startswith("elim") else "lane"
+    bases = lane_bases(model, monkeypatch) if plain == "lane" else [0]
+    outs = {}
+    for b in bases:
+        src = forced_variant_source(model, plain, b, monkeypatch=monkeypatch)
+        outs[b] = run_host(compile_host(src, tmp_path, "plain%d" % b, False), model, lk, flags)
+    ref = V.reference(ped, lk, flags)
+    if family in ("lane", "elim"):
+        runs = {}
+        for v in range(VARIANT_COUNTS[family]):
+            src = forced_variant_source(model, family, v, monkeypatch=monkeypatch)
+            assert "#define BT 1\n" in src
+            post, single, st = runs[v] = run_host(compile_host(src, tmp_path, "v%d" % v, False), model, lk, flags)
+            V.check_against_reference(post, single, st, ref, has_bn_fail, what="%s variant %d" % (family, v))
+        for v, out in runs.items():
+            b = v & 2 if family == "lane" and len(bases) > 1 else 0  # (each lane block shape against its own first variant)
+            assert V.same_bits(out, runs[b]), "variant %d of %s differs from variant %d" % (v, family, b)
+        if len(bases) > 1:
+            a, c = runs[0], runs[2]
+            assert np.array_equal(a[2], c[2]) and np.array_equal(a[1].view(np.uint64), c[1].view(np.uint64))
+            ok = (a[2] & 3) == 0
+            np.testing.assert_allclose(a[0][ok], c[0][ok], rtol=1e-12, atol=0)
+        return
+    for b in bases:
+        post, single, st = outs[b]
+        calls = {}
+        for v in range(VARIANT_COUNTS[family]):
+            src = forced_variant_source(model, family, v, base=b, monkeypatch=monkeypatch)
+            assert "call path" in src.splitlines()[0] and "#define BT 1\n" in src
+            calls[v], seq = run_host_call(compile_host(src, tmp_path, "c%d_%d" % (b, v), True), model, ped, lk, flags)
+        for v, out in calls.items():
+            assert V.same_bits(out, calls[0]), "call variant %d (base %d) differs from call variant 0" % (v, b)
+        gpp, fpp, fgt, cst = calls[0]
+        assert np.array_equal(cst, st)
+        ok, s_ok = (st & 3) == 0, (st & 3) != 1
+        np.testing.assert_allclose(gpp[s_ok], host_phred(single[s_ok][:, seq]), rtol=1e-12, atol=0)
+        np.testing.assert_allclose(fpp[ok], host_phred(post[ok][:, seq]), rtol=1e-12, atol=0)
+        assert np.array_equal(fgt[ok], fs.call_genotypes(post[ok][:, seq]).reshape(-1, len(seq)))
+        assert np.all(np.isnan(fpp[~ok])) and np.all(fgt[~ok] == -1) and np.all(np.isnan(gpp[~s_ok]))

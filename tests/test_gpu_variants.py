@@ -1,0 +1,278 @@
+"""Every variant of every generated kernel family, forced one at a time and run on the device.
+
+Which variant a pedigree gets is decided by the static picker, the tuner and the compiler's register allocation
+(csrc/jit.cpp jit_pick_variant); the rest of the GPU suite only runs the ones its pedigrees land on.  Here each index is
+forced — the plain kernels through their pick notes (pick_lane / pick_elim), the call-path forms through
+$FAMSEQ_VARIANT_ONLY — the plan is checked to name it, and its outputs go against the reference and against the other
+variants of the same family, which must agree bit for bit (see tests/test_generated_host.py, the host twin, for why).
+
+Pick notes are written into a private kernel cache of this session: the in-tree cache and the per-user one, from which the
+rest of the suite and bench.py load, never see them."""
+import numpy as np
+import pytest
+
+import _variants as V
+import famseq_amd as fs
+
+pytestmark = pytest.mark.gpu
+
+VARIANTS = dict(lane=4, elim=12, lane_call=4, elim_call=8)
+# One launch per call (chunk_sites: the host would otherwise split a call into launches of 256 sites) on a grid of 2
+# workgroups: at 1600 sites every workgroup wraps its persistent loop at least three times, for every workgroup size the
+# generated kernels use (BT <= 256), so what carries from one iteration to the next (LDS reuse after the stage-out, the
+# loop-top barrier, the prefetch of the next chunk) runs.
+N_SITES = 1600
+GRID = 2
+WIDE = {24: range(12), 40: range(12), 64: range(8, 12)}
+
+
+@pytest.fixture(scope="session")
+def private_cache(tmp_path_factory):
+    return str(tmp_path_factory.mktemp("variant_kernels"))
+
+
+@pytest.fixture(autouse=True)
+def _private_cache(private_cache, monkeypatch):
+    monkeypatch.setenv("FAMSEQ_KERNEL_CACHE", private_cache)
+    monkeypatch.setenv("FAMSEQ_KEEP_SRC", "1")  # (to read each kernel's workgroup size: the chunk of sites)
+    monkeypatch.delenv("FAMSEQ_VARIANT_ONLY", raising=False)
+    monkeypatch.delenv("FAMSEQ_VARIANT_MIN", raising=False)
+    yield
+
+
+_REF = {}
+
+
+def batch(name):
+    if name not in _REF:
+        ped = V.pedigree(name)
+        lk, flags, has_bn_fail = V.variant_batch(ped, N_SITES, seed=len(name))
+        _REF[name] = (ped, lk, flags, has_bn_fail, V.reference(ped, lk, flags))
+    return _REF[name]
+
+
+def block_threads(code_object):
+    src = open(code_object[:-6] + ".hip").read()
+    return int(src.split("#define BT ")[1].split()[0])
+
+
+def load(ped, family, v, base=0, monkeypatch=None):
+    """A device context running variant v of `family` (grid_blocks 3), the plan checked to name it."""
+    model = fs.make_model(ped, mrate=V.MRATE)
+    ctx = fs.Context(model, device=0)
+    one_launch(ctx)
+    seq = np.nonzero(ped.sequenced)[0][::-1].astype(np.int32).copy()
+    try:
+        if family == "lane":
+            ctx.set_option("pick_lane", v)
+            ctx.set_option("enum_impl", 1)
+            ctx.set_option("group_digits", 0)
+            plan = ctx.plan()
+            assert plan["enum_lane_variant"] == v
+            obj = plan["enum_lane_code_object"]
+        elif family == "elim":
+            ctx.set_option("pick_elim", v)
+            ctx.set_option("engine", fs.ENGINE_ELIM)
+            plan = ctx.plan()
+            assert plan["elim_variant"] == v
+            obj = plan["elim_code_object"]
+        elif family == "lane_call":
+            ctx.set_option("pick_lane", base)
+            ctx.set_option("enum_impl", 1)
+            ctx.set_option("group_digits", 0)
+            monkeypatch.setenv("FAMSEQ_VARIANT_ONLY", str(v))
+            ctx.set_option("call_kernels", 2)
+            monkeypatch.delenv("FAMSEQ_VARIANT_ONLY")
+            plan = ctx.plan()
+            assert plan["enum_lane_variant"] == base and plan["enum_lane_call_variant"] == v
+            obj = plan["enum_lane_call_code_object"]
+        else:
+            monkeypatch.setenv("FAMSEQ_VARIANT_ONLY", str(v))
+            ctx.set_option("engine", fs.ENGINE_ELIM)
+            ctx.set_option("call_kernels", 2)
+            monkeypatch.delenv("FAMSEQ_VARIANT_ONLY")
+            plan = ctx.plan()
+            assert plan["elim_call_variant"] == v
+            obj = plan["elim_call_code_object"]
+    except BaseException:
+        ctx.close()
+        raise
+    print("loaded and confirmed by the plan: members %d, %s, base %d, variant %d" % (ped.n, family, base, v))
+    return ctx, seq, block_threads(obj)
+
+
+def one_launch(ctx):
+    ctx.set_option("grid_blocks", GRID)
+    ctx.set_option("chunk_sites", N_SITES)
+
+
+def wraps(n_sites, sites_per_chunk):
+    """Does every workgroup of a launch of n_sites run its persistent loop at least three times?"""
+    return -(-n_sites // sites_per_chunk) >= 3 * GRID
+
+
+def run(ctx, family, seq, lk, flags):
+    if family.endswith("_call"):
+        return ctx.bn_call_batch(seq, lk=lk, flags=flags)
+    return ctx.bn_batch(lk, flags)
+
+
+def sizes(bt):
+    return sorted({1, bt - 1, bt + 1})
+
+
+def lane_bases(ped, monkeypatch):
+    model = fs.make_model(ped, mrate=V.MRATE)
+    ctx = fs.Context(model, device=-1)
+    shapes = []
+    for b in (0, 2):
+        ctx.set_option("pick_lane", b)
+        ctx.set_option("enum_impl", 1)
+        shapes.append(ctx.plan()["enum_lane_shape"])
+    ctx.close()
+    return [0] if shapes[0] == shapes[1] else [0, 2]
+
+
+def plain_runs(name, family, variants, monkeypatch):
+    ped, lk, flags, has_bn_fail, ref = batch(name)
+    runs = {}
+    for v in variants:
+        ctx, seq, bt = load(ped, family, v, monkeypatch=monkeypatch)
+        try:
+            assert wraps(len(flags), bt), (name, family, v, bt)
+            runs[v] = run(ctx, family, seq, lk, flags)
+            V.check_against_reference(*runs[v], ref, has_bn_fail, what="%s: %s variant %d" % (name, family, v))
+            for s in sizes(bt):  # the same context again, ragged around its chunk of sites (one launch each)
+                out = run(ctx, family, seq, lk[:s], flags[:s])
+                assert V.same_bits(out, tuple(x[:s] for x in runs[v])), (name, family, v, s)
+        finally:
+            ctx.close()
+    return runs
+
+
+@pytest.mark.parametrize("family", ["lane", "elim"])
+@pytest.mark.parametrize("name", V.PEDIGREES)
+def test_every_plain_variant(name, family, monkeypatch):
+    ped = batch(name)[0]
+    runs = plain_runs(name, family, range(VARIANTS[family]), monkeypatch)
+    two_blocks = family == "lane" and lane_bases(ped, monkeypatch) == [0, 2]
+    for v, out in runs.items():
+        b = (v & 2) if two_blocks else 0
+        assert V.same_bits(out, runs[b]), "%s: %s variant %d differs from variant %d" % (name, family, v, b)
+    if two_blocks:  # the 7- and the 6-member block group the enumeration's sums differently (enum_codegen.cpp)
+        a, c = runs[0], runs[2]
+        assert np.array_equal(a[2], c[2]) and np.array_equal(a[1].view(np.uint64), c[1].view(np.uint64))
+        ok = (a[2] & 3) == 0
+        np.testing.assert_allclose(a[0][ok], c[0][ok], rtol=1e-12, atol=0)
+
+
+def phred(p):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.abs(-10 * np.log10(p))
+    return np.where(np.isinf(q), 99999.0, q)
+
+
+@pytest.mark.parametrize("family", ["lane_call", "elim_call"])
+@pytest.mark.parametrize("name", V.PEDIGREES)
+def test_every_call_variant(name, family, monkeypatch):
+    ped, lk, flags, has_bn_fail, ref = batch(name)
+    bases = lane_bases(ped, monkeypatch) if family == "lane_call" else [0]
+    pl, lk_pl = V.packed_batch(ped, lk, np.nonzero(ped.sequenced)[0][::-1])
+    for b in bases:
+        calls, packed = {}, {}
+        for v in range(VARIANTS[family]):
+            ctx, seq, bt = load(ped, family, v, base=b, monkeypatch=monkeypatch)
+            try:
+                assert wraps(len(flags), bt), (name, family, b, v, bt)
+                calls[v] = run(ctx, family, seq, lk, flags)
+                for s in sizes(bt):
+                    out = run(ctx, family, seq, lk[:s], flags[:s])
+                    assert V.same_bits(out, tuple(x[:s] for x in calls[v])), (name, family, b, v, s)
+                # packed integer PLs in (the call forms' own unpacking and staging), against fp64 rows of the table's values
+                if family == "lane_call":
+                    assert ctx.plan()["enum_lane_call_reads_rows"] == 0  # (else packed input would take the separate stages)
+                packed[v] = ctx.bn_call_batch(seq, pl16=pl, flags=flags)
+                assert V.same_bits(packed[v], ctx.bn_call_batch(seq, lk=lk_pl, flags=flags)), (name, family, b, v, "packed")
+                s = bt + 1
+                assert V.same_bits(ctx.bn_call_batch(seq, pl16=pl[:s], flags=flags[:s]), tuple(x[:s] for x in packed[v])), (name, family, b, v, s)
+            finally:
+                ctx.close()
+        for v, out in calls.items():
+            assert V.same_bits(out, calls[0]), "%s: %s variant %d (base %d) differs from variant 0" % (name, family, v, b)
+            assert V.same_bits(packed[v], packed[0]), "%s: %s variant %d (base %d), packed input, differs from variant 0" % (name, family, v, b)
+        assert ((packed[0][3] & 3) == 0).sum() > len(flags) // 2
+        # the Phred formula and the genotype call of the plain kernel's posteriors (the lane call form runs its base's block;
+        # every variant of one family gives the same bits, so one plain run stands for all)
+        gpp, fpp, fgt, st = calls[0]
+        plain, pv = ("lane", b) if family == "lane_call" else ("elim", 0)
+        post, single, pst = plain_runs(name, plain, [pv], monkeypatch)[pv]
+        seq_ = np.nonzero(ped.sequenced)[0][::-1]
+        assert np.array_equal(st, pst) and np.array_equal(st, ref[2])
+        ok, s_ok = (st & 3) == 0, (st & 3) != 1
+        np.testing.assert_allclose(gpp[s_ok], phred(single[s_ok][:, seq_]), rtol=1e-12, atol=0)
+        np.testing.assert_allclose(fpp[ok], phred(post[ok][:, seq_]), rtol=1e-12, atol=0)
+        assert np.array_equal(fgt[ok], fs.call_genotypes(post[ok][:, seq_]).reshape(-1, len(seq_)))
+        assert np.all(np.isnan(fpp[~ok])) and np.all(fgt[~ok] == -1) and np.all(np.isnan(gpp[~s_ok]))
+
+
+@pytest.mark.parametrize("name", ["ped10", "ped15:12"])
+def test_every_lanes_per_site_form(name, monkeypatch):
+    ped, lk, flags, has_bn_fail, ref = batch(name)
+    model = fs.make_model(ped, mrate=V.MRATE)
+    ctx = fs.Context(model, device=0)
+    dmax = ctx.plan()["enum_group_digits_max"]
+    ctx.close()
+    assert dmax >= 2
+    for d in range(1, dmax + 1):
+        ctx = fs.Context(model, device=0)
+        try:
+            one_launch(ctx)
+            ctx.set_option("enum_impl", 1)
+            ctx.set_option("group_digits", d)
+            out = ctx.bn_batch(lk, flags)
+            assert ctx.plan()["enum_group_digits_last"] == d
+            V.check_against_reference(*out, ref, has_bn_fail, what="%s: lanes-per-site d = %d" % (name, d))
+            for s in (1, 2, 3, 65):
+                assert V.same_bits(ctx.bn_batch(lk[:s], flags[:s]), tuple(x[:s] for x in out)), (name, d, s)
+        finally:
+            ctx.close()
+        print("loaded and confirmed by the plan: members %d, lanes-per-site d = %d" % (ped.n, d))
+
+
+@pytest.mark.parametrize("n", sorted(WIDE))
+def test_every_variant_on_wide_pedigrees(n, monkeypatch):
+    """The sum-product kernel of wide pedigrees (LDS-staged up to 39 members, rows straight from global memory from 40),
+    every variant forced, against the numpy sum-product oracle on the sites its double arithmetic is sound on."""
+    import oracle.sum_product as sp
+    from famseq_amd.prebuild_sets import wide_pedigree
+
+    ped = wide_pedigree(n)
+    ped.relations()
+    lk, flags, has_bn_fail = V.variant_batch(ped, N_SITES, seed=n, max_pl=40)
+    want = sp.pedigree_posterior(ped, lk, flags, mrate=V.MRATE)
+    true = sp.pedigree_posterior(ped, lk, flags, mrate=V.MRATE, dtype=np.longdouble)
+    sound = (want[2] == true[2]) & np.all(np.isclose(want[0], true[0].astype(np.float64), rtol=1e-10, atol=1e-35, equal_nan=True), axis=(1, 2))
+    # (the -LRC vote is a double-precision rule: in long double 1 + 1e-17 is not 1, so shortcut sites never count as sound;
+    # the kernel has to reproduce the double oracle's vote and rows there exactly)
+    cut = want[2] == 0x80
+    assert sound.mean() > 0.8 and cut[V.SHORTCUT] and sound[V.SINGLE_FAIL] and sound[list(V.TINY_SITES)].all()
+    runs = {}
+    for v in WIDE[n]:
+        ctx, seq, bt = load(ped, "elim", v, monkeypatch=monkeypatch)
+        try:
+            assert wraps(len(flags), bt), (n, v, bt)
+            post, single, st = runs[v] = ctx.bn_batch(lk, flags)
+            for s in sizes(bt):
+                assert V.same_bits(ctx.bn_batch(lk[:s], flags[:s]), tuple(x[:s] for x in runs[v])), (n, v, s)
+        finally:
+            ctx.close()
+        assert np.array_equal(st[sound | cut], want[2][sound | cut]) and st[V.SHORTCUT] == 0x80 and st[V.SINGLE_FAIL] == 1
+        assert not has_bn_fail or st[V.BN_FAIL] == 2
+        ok, s_ok = sound & ((st & 3) == 0), (want[2] & 3) != 1
+        assert np.array_equal(single[s_ok].view(np.uint64), want[1][s_ok].view(np.uint64))
+        assert np.array_equal(post[cut].view(np.uint64), want[0][cut].view(np.uint64))
+        # (atol as in `sound`: below 1e-35 the double oracle itself is only vouched for to that absolute level — a posterior of
+        # 1e-62 comes out of different orders of products a few 1e-3 apart, relatively)
+        np.testing.assert_allclose(post[ok], want[0][ok], rtol=1e-9, atol=1e-35)
+        assert np.all(np.isnan(post[(st & 3) != 0]))
+        assert V.same_bits(runs[v], runs[min(runs)]), "%d members: elim variant %d differs from variant %d" % (n, v, min(runs))

@@ -157,3 +157,76 @@ def test_cli_method2_on_wide_pedigrees(tmp_path):
 def test_cli_method1_on_a_wide_pedigree_says_what_to_do(tmp_path):
     rc, msg = run_cli(["vcf", "-vcfFile", TD + "/wide32.vcf", "-pedFile", TD + "/wide32.ped", "-method", "1", "-v"], tmp_path / "o.vcf")
     assert "Use -method 2" in msg
+
+
+@pytest.mark.parametrize("n,all_sequenced", [(170, False), (171, False), (200, True)])
+def test_call_path_beyond_170_members(n, all_sequenced, tmp_path):
+    """famseq_bn_call_batch (packed PLs) and `FamSeq vcf -method 2` at the width where the separate unpack / Phred stages
+    used to stop (170 members: a tile of 128 sites was the most their 16-bit indices held), against the numpy oracle and
+    the drivers' Phred formula and call.  The unpack stage's rows hold every member, the Phred stage's every sequenced one:
+    171 members shrink the first stage's tiles, 200 sequenced members both."""
+    import math
+
+    import oracle.sum_product as sp
+    from famseq_amd.pedigree import write_ped
+    from famseq_amd.prebuild_sets import wide_pedigree
+    from test_cli_gpu import num_close, result_fields
+
+    ped = wide_pedigree(n)
+    if all_sequenced:
+        ped = fs.Pedigree(ped.ids, ped.mids, ped.fids, ped.genders, ["s%d" % i for i in ped.ids])
+    ped.relations()
+    seq = np.nonzero(ped.sequenced)[0].astype(np.int32)
+    k = len(seq)
+    assert (k > 170) == all_sequenced
+    rng = np.random.RandomState(n)
+    s = 300  # two whole tiles of the unpack / Phred stages and a ragged one (128 sites per tile up to 170 members, 109 at 200)
+    pl = rng.randint(0, 13, size=(s, k, 3)).astype(np.uint16)  # (mild PLs: 200 sequenced members keep a site's mass far above 1e-308)
+    pl[np.arange(s)[:, None], np.arange(k)[None, :], rng.randint(0, 3, size=(s, k))] = 0
+    pl[5, 2] = fs.PL_MISSING
+    pl[9, :] = [0, 200, 250]  # a shortcut site
+    flags = np.zeros(s, np.uint8)  # (the command line's flags: autosome, no dbSNP ID)
+    table = np.array([math.pow(10.0, -v / 10.0) for v in range(256)])
+    lk = np.ones((s, ped.n, 3))
+    lk[:, seq, :] = table[pl.astype(np.int64) % 256]
+    lk[5, seq[2]] = 1.0
+    want = sp.pedigree_posterior(ped, lk, flags)
+    with np.errstate(divide="ignore"):
+        f_want = np.abs(-10 * np.log10(want[0][:, seq, :]))
+        g_want = np.abs(-10 * np.log10(want[1][:, seq, :]))
+    f_want[np.isinf(f_want)] = 99999.0
+    g_want[np.isinf(g_want)] = 99999.0
+    ctx = fs.Context(fs.make_model(ped), device=0)
+    gpp, fpp, fgt, st = ctx.bn_call_batch(seq, pl16=pl, flags=flags)
+    ctx.close()
+    assert np.array_equal(st, want[2]) and st[9] == 0x80
+    ok = (st & 3) == 0
+    assert ok.sum() > s // 2
+    np.testing.assert_allclose(fpp[ok], f_want[ok], rtol=1e-9, atol=1e-9)
+    np.testing.assert_allclose(gpp, g_want, rtol=1e-12, atol=1e-12)
+    p_sorted = np.sort(want[0][:, seq, :], axis=2)
+    clear = ok[:, None] & (p_sorted[:, :, 2] - p_sorted[:, :, 1] > 1e-9)
+    assert np.array_equal(fgt[clear], np.argmax(want[0][:, seq, :], axis=2)[clear])
+
+    # the same sites through the command line
+    vcf, pedf, out = tmp_path / "w.vcf", tmp_path / "w.ped", tmp_path / "o.vcf"
+    write_ped(ped, pedf)
+    fs.synth.write_vcf(vcf, [ped.names[i] for i in seq], np.where(pl == fs.PL_MISSING, 0, pl), np.zeros(s, bool),
+                       np.zeros((s, k), np.int64))
+    rc, msg = run_cli(["vcf", "-vcfFile", str(vcf), "-pedFile", str(pedf), "-method", "2"], out)
+    assert rc == 0, msg
+    got = result_fields(out, "vcf")
+    assert len(got) == s
+    names = {"0/0": 0, "0/1": 1, "1/1": 2}
+    for i, row in enumerate(got):
+        assert len(row) == k
+        if i == 5:
+            continue  # (a missing sample above; the text file has PLs 0,0,0 there)
+        for j, (g, f, t) in enumerate(row):
+            for u, w in zip(g.split(","), g_want[i, j]):
+                assert num_close(u, "%g" % w), (i, j, g, g_want[i, j])
+            if ok[i]:
+                for u, w in zip(f.split(","), f_want[i, j]):
+                    assert num_close(u, "%g" % w), (i, j, f, f_want[i, j])
+                if clear[i, j]:
+                    assert names[t] == fgt[i, j], (i, j, t)

@@ -120,3 +120,36 @@ print(c.plan()['elim_variant'])
         os.chmod(lib / "kernels", 0o755)
         for f in glob.glob("/tmp/famseq_kernels_%d/*" % os.getuid()):
             os.unlink(f)
+
+
+
+def test_variant_only_compiles_exactly_that_variant_and_the_plan_names_it(tmp_path):
+    """$FAMSEQ_VARIANT_ONLY=v: variant v of whichever kernel family is being picked, however much it spills; an index the
+    family does not have is an error, not a quiet fall-back.  famseq_plan_json reports both call-path forms' variants."""
+    code = r"""
+import os
+import famseq_amd as fs
+m = fs.make_model(fs.synthetic_pedigree('ped10'))
+c = fs.Context(m, device=-1)
+p = c.plan()
+assert p['enum_lane_call_variant'] == -1 and p['elim_call_variant'] == -1, p
+os.environ['FAMSEQ_VARIANT_ONLY'] = '11'        # the plain sum-product kernel has variants 0..11
+c.set_option('engine', fs.ENGINE_ELIM)
+assert c.plan()['elim_variant'] == 11
+assert 'variant 11' in open(c.plan()['elim_code_object'][:-6] + '.hip').readline()
+os.environ['FAMSEQ_VARIANT_ONLY'] = '7'         # its call-path form 0..7: built alone (call_kernels 2)
+c.set_option('call_kernels', 2)
+p = c.plan()
+assert p['elim_call_variant'] == 7 and p['enum_lane_call_variant'] == -1, p
+c.close()
+c = fs.Context(m, device=-1)
+c.set_option('pick_lane', 0)
+try:
+    c.set_option('call_kernels', 1)             # the lane call form has variants 0..3 only
+    raise SystemExit('variant 7 of a four-variant family?')
+except fs.FamseqError as e:
+    assert 'FAMSEQ_VARIANT_ONLY=7' in str(e) and '0..3' in str(e), e
+print('ok')
+"""
+    out = run_py(code, {"FAMSEQ_KERNEL_CACHE": str(tmp_path), "FAMSEQ_JIT_SOURCE_ONLY": "1", "FAMSEQ_KEEP_SRC": "1"}, tmp_path)
+    assert "ok" in out
