@@ -80,7 +80,7 @@ ABI_SYMBOLS = [
     "famseq_destroy", "famseq_last_error", "famseq_set_option", "famseq_plan_json",
     "famseq_bn_batch", "famseq_bn_batch_sharded", "famseq_bn_batch_device", "famseq_bn_batch_device_sharded",
     "famseq_bn_call_batch", "famseq_bn_call_text_batch", "famseq_bn_call_batch_device", "famseq_format_probe", "famseq_alloc_pinned", "famseq_free_pinned", "famseq_stream_probe",
-    "famseq_call_genotypes",
+    "famseq_call_genotypes", "famseq_trio_children", "famseq_trio_batch", "famseq_trio_batch_device",
 ]
 PL_MISSING = 0xFFFF
 
@@ -152,6 +152,12 @@ def lib():
     L.famseq_free_pinned.restype = None
     L.famseq_call_genotypes.argtypes = [dp, C.c_int64, C.POINTER(C.c_int8)]
     L.famseq_call_genotypes.restype = None
+    L.famseq_trio_children.argtypes = [C.c_void_p, ip]
+    L.famseq_trio_children.restype = C.c_int
+    L.famseq_trio_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, dp, dp, bp]
+    L.famseq_trio_batch.restype = C.c_int
+    L.famseq_trio_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp]
+    L.famseq_trio_batch_device.restype = C.c_int
     _lib = L
     return L
 
@@ -305,6 +311,54 @@ class Context:
                                                len(seq), d_gpp or None, d_fpp or None, d_fgt or None, d_status or None, d_text or None,
                                                stream or None)
         self._check(rc, "famseq_bn_call_batch_device")
+
+    def trio_children(self):
+        """Member indices of the children (the members with parents, PED order): child k of trio_batch is member children[k]."""
+        k = lib().famseq_trio_children(self._h, None)
+        self._check(min(k, 0), "famseq_trio_children")
+        idx = np.zeros(k, np.int32)
+        if k:
+            lib().famseq_trio_children(self._h, _p(idx, C.c_int32))
+        return idx
+
+    def trio_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_joint=True, want_dnm=True):
+        """Trio posteriors: -> (children[K], joint[S,K,27] or None, dnm[S,K] or None, status[S]).
+        joint[s, k, 9 gc + 3 gm + gf] is the posterior of child k's and its parents' genotypes; dnm[s, k] the mass of the
+        entries the mutation-free transmission table rules out.  Input is either lk [S,N,3] float64 or pl16 [S,n_seq,3]
+        uint16 in VCF column order (seq_members: their PED indices)."""
+        if (lk is None) == (pl16 is None):
+            raise ValueError("give exactly one of lk / pl16")
+        children = self.trio_children()
+        k = len(children)
+        seq, n_seq = None, 0
+        if lk is not None:
+            lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
+            s = lk.shape[0]
+        else:
+            seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+            n_seq = len(seq)
+            pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, n_seq, 3)
+            s = pl16.shape[0]
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        if fl is not None and fl.shape != (s,):
+            raise ValueError("flags must have one byte per site")
+        joint = np.empty((s, k, 27)) if want_joint else None
+        dnm = np.empty((s, k)) if want_dnm else None
+        status = np.zeros(s, np.uint8)
+        rc = lib().famseq_trio_batch(self._h, s, None if lk is None else _p(lk, C.c_double),
+                                     None if pl16 is None else _p(pl16, C.c_uint16), None if seq is None else _p(seq, C.c_int32),
+                                     n_seq, None if fl is None else _p(fl, C.c_uint8), None if joint is None else _p(joint, C.c_double),
+                                     None if dnm is None else _p(dnm, C.c_double), _p(status, C.c_uint8))
+        self._check(rc, "famseq_trio_batch")
+        return children, joint, dnm, status
+
+    def trio_batch_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_joint=0, d_dnm=0, d_status=0, stream=0):
+        """Trio posteriors on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+        rc = lib().famseq_trio_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
+                                            _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_joint or None,
+                                            d_dnm or None, d_status or None, stream or None)
+        self._check(rc, "famseq_trio_batch_device")
 
     def g6_probe(self, values):
         """The device formatter alone (famseq_format_probe): -> list of bytes, one per value."""

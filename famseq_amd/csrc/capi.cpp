@@ -119,6 +119,17 @@ struct famseq_ctx {
   int64_t dev_tmp_sites = 0;
   int dev_tmp_seq = 0;
   std::vector<int32_t> seq_members;
+  // trio posteriors (famseq_trio_batch*): the generated kernel per output form (1 dnm, 2 joint, 3 both), built on first use;
+  // the host-staged entry's own chunk buffers, and the device entry's likelihood rows for packed input
+  JitKernel trio[4]{};
+  int trio_blocks_per_cu[4] = {}, trio_variant[4] = {-1, -1, -1, -1}, trio_last = 0;
+  double *d_tj[kSlots] = {}, *d_td[kSlots] = {}, *d_tlk[kSlots] = {};
+  uint16_t *d_tpl[kSlots] = {};
+  uint8_t *d_tflags[kSlots] = {}, *d_tstatus[kSlots] = {};
+  int64_t trio_slot_sites = 0;
+  int trio_slot_seq = 0;
+  double *trio_dev_lk = nullptr;
+  int64_t trio_dev_sites = 0;
   std::string tune_report;  // what famseq_set_option "tune" measured (famseq_plan_json "tune")
   std::string err, json;
 };
@@ -191,6 +202,21 @@ void free_slots(famseq_ctx *c) {
   }
   c->slot_sites = 0;
   c->slot_seq = 0;
+}
+
+void free_trio_slots(famseq_ctx *c) {
+  for (int s = 0; s < famseq_ctx::kSlots; ++s) {
+    for (double **q : {&c->d_tj[s], &c->d_td[s], &c->d_tlk[s]}) {
+      if (*q) (void)hipFree(*q);
+      *q = nullptr;
+    }
+    if (c->d_tpl[s]) (void)hipFree(c->d_tpl[s]);
+    if (c->d_tflags[s]) (void)hipFree(c->d_tflags[s]);
+    if (c->d_tstatus[s]) (void)hipFree(c->d_tstatus[s]);
+    c->d_tpl[s] = nullptr, c->d_tflags[s] = c->d_tstatus[s] = nullptr;
+  }
+  c->trio_slot_sites = 0;
+  c->trio_slot_seq = 0;
 }
 
 // (Re)build the plan and, on a device ctx, upload its image and the factor tables.
@@ -471,6 +497,41 @@ bool launch_engine_fused(famseq_ctx *c, int64_t n_sites, const double *d_lk, con
   return true;
 }
 
+// Generate/compile (or fetch) and, on a device ctx, load the trio kernel of output form `form` (1 dnm, 2 joint, 3 both).
+// Lazily: nothing of it exists until the first trio call or the "trio_kernels" option.
+int load_trio(famseq_ctx *c, int form) {
+  JitKernel &k = c->trio[form];
+  c->trio_last = form;
+  if (k.fn || (c->device < 0 && !k.path.empty())) return 0;
+  std::string why;
+  if (!elim_supported(c->model, &why)) return fail(c, FAMSEQ_E_ARG, "trio posteriors (sum-product engine): " + why);
+  try {
+    const Model &mdl = c->model;
+    const std::string src =
+        jit_pick_variant([&mdl, form](int v) { return trio_source(mdl, v, form); }, kTrioVariants, &c->trio_variant[form], 0);
+    if (c->device < 0) {
+      k.path = jit_compile(src);
+      return 0;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    k = jit_load(src, "famseq_trio");
+  } catch (const std::exception &e) {
+    return fail(c, FAMSEQ_E_HIP, e.what());
+  }
+  int nb = 0;
+  HIP_TRY(c, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, elim_block_threads(c->model), 0));
+  c->trio_blocks_per_cu[form] = nb > 0 ? nb : 1;
+  return 0;
+}
+
+int trio_form(const void *joint, const void *dnm) { return (joint ? 2 : 0) | (dnm || !joint ? 1 : 0); }
+
+hipError_t launch_trio(famseq_ctx *c, int form, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, double *d_joint,
+                       double *d_dnm, uint8_t *d_status, hipStream_t stream) {
+  return launch_generated(c, c->trio[form].fn, elim_block_threads(c->model), c->trio_blocks_per_cu[form], n_sites, d_lk, d_flags,
+                          d_joint, d_dnm, d_status, stream);
+}
+
 }  // namespace
 
 extern "C" int famseq_device_count(void) {
@@ -580,6 +641,9 @@ extern "C" void famseq_destroy(famseq_ctx *c) {
     jit_unload(c->elim_call);
     jit_unload(c->lane_call);
     for (JitKernel &k : c->grp) jit_unload(k);
+    for (JitKernel &k : c->trio) jit_unload(k);
+    free_trio_slots(c);
+    if (c->trio_dev_lk) (void)hipFree(c->trio_dev_lk);
     if (c->d_lut) (void)hipFree(c->d_lut);
     if (c->d_seq) (void)hipFree(c->d_seq);
     if (c->d_col) (void)hipFree(c->d_col);
@@ -833,6 +897,10 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
       return fail(c, FAMSEQ_E_HIP, "call-path kernel unavailable: " + c->call_error[1]);
     return 0;
   }
+  else if (k == "trio_kernels") {  // build (and on a device ctx load) the trio kernel of that output form now
+    if (value < 1 || value > 3) return fail(c, FAMSEQ_E_ARG, "trio_kernels takes 1 (dnm), 2 (joint) or 3 (both)");
+    return load_trio(c, (int)value);
+  }
   else if (k == "group_digits") {
     if (value < -1 || value > enumgen_max_group_digits(c->model))
       return fail(c, FAMSEQ_E_ARG, "group_digits must be -1 (auto) or 0.." + std::to_string(enumgen_max_group_digits(c->model)) +
@@ -885,6 +953,14 @@ std::string json_str(const std::string &v) {  // paths may hold quotes or backsl
   }
   return o;
 }
+// the trio kernels (famseq_trio_batch): the code object of the form used last, every form's, the variant the contest took
+std::string trio_json(const famseq_ctx *c) {
+  const int f = c->trio_last;
+  std::string o = ",\"trio_code_object\":\"" + json_str(f ? c->trio[f].path : std::string()) + "\",\"trio_code_objects\":[";
+  for (int k = 1; k <= 3; ++k) o += std::string(k > 1 ? "," : "") + "\"" + json_str(c->trio[k].path) + "\"";
+  return o + "],\"trio_variant\":" + std::to_string(f ? c->trio_variant[f] : -1) + ",\"trio_children\":" +
+         std::to_string(trio_children(c->model).size());
+}
 }  // namespace
 
 extern "C" const char *famseq_plan_json(famseq_ctx *c) {
@@ -893,7 +969,7 @@ extern "C" const char *famseq_plan_json(famseq_ctx *c) {
     c->json = "{\"N\":" + std::to_string(c->model.n_members) + ",\"engine\":" + std::to_string(c->engine) + ",\"elim_supported\":1,\"elim_code_object\":\"" +
               json_str(c->elim.path) + "\",\"elim_variant\":" + std::to_string(c->elim_variant) + ",\"elim_blocks_per_cu\":" +
               std::to_string(c->elim_blocks_per_cu) + ",\"elim_conditioned_members\":" + std::to_string(elim_conditioned_members(c->model)) +
-              ",\"enum_supported\":0,\"device\":" + std::to_string(c->device) + ",\"cus\":" + std::to_string(c->n_cus) + "}";
+              ",\"enum_supported\":0,\"device\":" + std::to_string(c->device) + ",\"cus\":" + std::to_string(c->n_cus) + trio_json(c) + "}";
     return c->json.c_str();
   }
   c->json = c->plan.json();
@@ -915,7 +991,7 @@ extern "C" const char *famseq_plan_json(famseq_ctx *c) {
              json_str(c->call_error[1].substr(0, 300)) + "\",\"enum_lane_call_reads_rows\":" + std::to_string(c->lane_reads_rows) +
              ",\"enum_lane_call_variant\":" + std::to_string(c->lane_call_pick) + ",\"elim_call_variant\":" +
              std::to_string(c->elim_call_variant) + ",\"tune\":\"" +
-             json_str(c->tune_report) + "\"}";
+             json_str(c->tune_report) + "\"" + trio_json(c) + "}";
   return c->json.c_str();
 }
 
@@ -1346,5 +1422,139 @@ extern "C" int famseq_bn_call_batch_device(famseq_ctx *c, int64_t n_sites, const
   }
   if (want_text)
     HIP_TRY(c, launch_text_call(gpp ? gpp : c->dev_tmp[3], fpp ? fpp : c->dev_tmp[4], fgt ? fgt : c->dev_tmp_fgt, n_sites * n_seq, d_text, stream));
+  return 0;
+}
+
+// ---- trio posteriors -------------------------------------------------------------------------------------------------
+
+extern "C" int famseq_trio_children(famseq_ctx *c, int32_t *idx) {
+  if (!c) return FAMSEQ_E_ARG;
+  std::string why;
+  if (!elim_supported(c->model, &why)) return fail(c, FAMSEQ_E_ARG, "trio posteriors (sum-product engine): " + why);
+  const std::vector<int> kids = trio_children(c->model);
+  if (idx) std::copy(kids.begin(), kids.end(), idx);
+  return (int)kids.size();
+}
+
+namespace {
+
+int upload_lut(famseq_ctx *c) {
+  if (c->d_lut) return 0;
+  std::vector<double> lut(kPlLutSize);  // pow(10,-k/10) through the host's libm, as file.cpp:589 computes it
+  for (int k = 0; k < kPlLutSize; ++k) lut[k] = std::pow(10.0, -std::fabs(double(k)) / 10.0);
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_lut), lut.size() * sizeof(double)));
+  HIP_TRY(c, hipMemcpy(c->d_lut, lut.data(), lut.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// Arguments both trio entries check the same way; loads the kernel of the form the outputs ask for.
+int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl16, const int32_t *seq_members, int32_t n_seq,
+                  int form) {
+  if (n_sites < 0 || (n_sites > 0 && ((lk == nullptr) == (pl16 == nullptr))))
+    return fail(c, FAMSEQ_E_ARG, "exactly one of lk / pl16 must be given");
+  if (c->device < 0) return fail(c, FAMSEQ_E_NODEVICE, "context was created without a device; there is no CPU path");
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc = load_trio(c, form);
+  if (rc != 0) return rc;
+  if (pl16) {
+    if (n_seq < 1) return fail(c, FAMSEQ_E_ARG, "n_seq must be >= 1");
+    if ((rc = set_sequenced(c, seq_members, n_seq)) != 0) return rc;
+    if ((rc = upload_lut(c)) != 0) return rc;
+  }
+  return 0;
+}
+
+}  // namespace
+
+// Host buffers: chunks through the same three stages as famseq_bn_batch (copy in / unpack + trio kernel / copy out), on
+// buffers of their own.
+extern "C" int famseq_trio_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                 int32_t n_seq, const uint8_t *flags, double *joint, double *dnm, uint8_t *status) {
+  if (!c) return FAMSEQ_E_ARG;
+  const int form = trio_form(joint, dnm);
+  int rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, form);
+  if (rc != 0 || n_sites == 0) return rc;
+  const int N = c->model.n_members, K = (int)trio_children(c->model).size();
+  const size_t row = size_t(3) * N * sizeof(double), jrow = size_t(27) * K * sizeof(double), drow = size_t(K) * sizeof(double);
+  int64_t chunk = c->chunk_sites;
+  if (chunk <= 0) {
+    chunk = std::max<int64_t>(1, (int64_t(64) << 20) / int64_t(std::max(row, jrow + 1)));
+    chunk = std::min(chunk, std::max<int64_t>(c->lane_min_sites, (n_sites + 3) / 4));
+  }
+  chunk = std::min(chunk, n_sites);
+  const int want_seq = pl16 ? n_seq : 0;
+  if (c->trio_slot_sites < chunk || c->trio_slot_seq < want_seq) {
+    const int64_t cap = std::max(chunk, c->trio_slot_sites);
+    const int seqcap = std::max(want_seq, c->trio_slot_seq);
+    free_trio_slots(c);
+    for (int s = 0; s < famseq_ctx::kSlots; ++s) {
+      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_tlk[s]), cap * row));
+      if (K) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_tj[s]), cap * jrow));
+      if (K) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_td[s]), cap * drow));
+      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_tflags[s]), cap));
+      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_tstatus[s]), cap));
+      if (seqcap) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_tpl[s]), cap * seqcap * 3 * sizeof(uint16_t)));
+    }
+    c->trio_slot_sites = cap;
+    c->trio_slot_seq = seqcap;
+  }
+  hipStream_t s_in = c->stream[0], s_k = c->stream[1], s_out = c->stream[2];
+  // From here on copies into the caller's buffers may be in flight: an error must not return before the streams have drained.
+  rc = [&]() -> int {
+    int k = 0;
+    for (int64_t lo = 0; lo < n_sites; lo += chunk, ++k) {
+      const int s = k % famseq_ctx::kSlots;
+      const int64_t n = std::min(chunk, n_sites - lo);
+      if (k >= famseq_ctx::kSlots) HIP_TRY(c, hipStreamWaitEvent(s_in, c->ev_out[s], 0));
+      if (pl16)
+        HIP_TRY(c, hipMemcpyAsync(c->d_tpl[s], pl16 + lo * n_seq * 3, n * n_seq * 3 * sizeof(uint16_t), hipMemcpyHostToDevice, s_in));
+      else
+        HIP_TRY(c, hipMemcpyAsync(c->d_tlk[s], lk + lo * 3 * N, n * row, hipMemcpyHostToDevice, s_in));
+      if (flags) HIP_TRY(c, hipMemcpyAsync(c->d_tflags[s], flags + lo, n, hipMemcpyHostToDevice, s_in));
+      HIP_TRY(c, hipEventRecord(c->ev_in[s], s_in));
+      HIP_TRY(c, hipStreamWaitEvent(s_k, c->ev_in[s], 0));
+      if (pl16) HIP_TRY(c, launch_unpack_pl16(c->d_tpl[s], c->d_col, c->d_lut, N, n_seq, n, c->d_tlk[s], s_k));
+      HIP_TRY(c, launch_trio(c, form, n, c->d_tlk[s], flags ? c->d_tflags[s] : nullptr, joint ? c->d_tj[s] : nullptr,
+                             dnm ? c->d_td[s] : nullptr, status ? c->d_tstatus[s] : nullptr, s_k));
+      HIP_TRY(c, hipEventRecord(c->ev_done[s], s_k));
+      HIP_TRY(c, hipStreamWaitEvent(s_out, c->ev_done[s], 0));
+      if (joint && K) HIP_TRY(c, hipMemcpyAsync(joint + lo * 27 * K, c->d_tj[s], n * jrow, hipMemcpyDeviceToHost, s_out));
+      if (dnm && K) HIP_TRY(c, hipMemcpyAsync(dnm + lo * K, c->d_td[s], n * drow, hipMemcpyDeviceToHost, s_out));
+      if (status) HIP_TRY(c, hipMemcpyAsync(status + lo, c->d_tstatus[s], n, hipMemcpyDeviceToHost, s_out));
+      HIP_TRY(c, hipEventRecord(c->ev_out[s], s_out));
+    }
+    return 0;
+  }();
+  for (int s = 0; s < famseq_ctx::kStages; ++s) {
+    const hipError_t e = hipStreamSynchronize(c->stream[s]);
+    if (e != hipSuccess && rc == 0) return fail(c, FAMSEQ_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+  }
+  return rc;
+}
+
+// Device buffers: enqueue on the caller's stream and return.  Packed input is unpacked into likelihood rows this context keeps
+// (grown on demand).
+extern "C" int famseq_trio_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                        const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_joint,
+                                        double *d_dnm, uint8_t *d_status, void *stream_) {
+  if (!c) return FAMSEQ_E_ARG;
+  const int form = trio_form(d_joint, d_dnm);
+  const int rc = trio_prologue(c, n_sites, d_lk, d_pl16, seq_members, n_seq, form);
+  if (rc != 0 || n_sites == 0) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int N = c->model.n_members;
+  const double *lk = d_lk;
+  if (d_pl16) {
+    if (c->trio_dev_sites < n_sites) {
+      HIP_TRY(c, hipStreamSynchronize(stream));  // nothing of an earlier call may still use what is freed here
+      if (c->trio_dev_lk) (void)hipFree(c->trio_dev_lk);
+      c->trio_dev_lk = nullptr, c->trio_dev_sites = 0;
+      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->trio_dev_lk), size_t(n_sites) * 3 * N * sizeof(double)));
+      c->trio_dev_sites = n_sites;
+    }
+    HIP_TRY(c, launch_unpack_pl16(d_pl16, c->d_col, c->d_lut, N, n_seq, n_sites, c->trio_dev_lk, stream));
+    lk = c->trio_dev_lk;
+  }
+  HIP_TRY(c, launch_trio(c, form, n_sites, lk, d_flags, d_joint, d_dnm, d_status, stream));
   return 0;
 }

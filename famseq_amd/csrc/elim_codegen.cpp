@@ -216,7 +216,136 @@ class Emitter {
     return out + o_.str();
   }
 
+  // Trio posteriors (famseq_trio): for every child c (a member with parents, PED order) the clique belief of its nuclear
+  // family F restricted to (c, mother, father),
+  //   b_c(gc, gm, gf) = T_c(gc | gm, gf) * v_c->F(gc) * C(gm, gf),  C = v_mo->F(gm) * v_fa->F(gf) * prod_{other kids k} a_k(gm, gf)
+  // (C is fac2var's product for the message F -> c), normalised by its own sum, the total weight of c's component.  `mask`
+  // [2][K][27]: the entries where the mutation-free transmission table of the child is 0 (autosomes, chrX); their mass is the
+  // de novo posterior.  joint: store the 27 values too.  Loops: accumulated over the cut assignments with the weight of the
+  // rest of the network (as conditioned_body does for marginals), normalised once after the last assignment.
+  std::string trio_body(const std::vector<int> &kids, const std::vector<std::vector<double>> &mask, bool joint) {
+    const int K = (int)kids.size();
+    if (g_.cut.empty()) {
+      for (int c = 0; c < (int)g_.rep.size(); ++c)  // a component without a family (a lone founder): its weight is its local factor
+        if (g_.nb[g_.rep[c]].empty()) {
+          const std::string l = loc(g_.rep[c]);
+          o_ << "      if (((" << l << "_0 + " << l << "_1) + " << l << "_2) <= 0) bn_fail = true;\n";
+        }
+      for (int k = 0; k < K; ++k) {
+        const std::string b = trio(family_of(kids[k]), kids[k], mask, k);
+        trio_out(k, b + "s", b + "A", b + "X", joint ? b + "_" : "");
+      }
+      return o_.str();
+    }
+    const int nc = (int)g_.cut.size(), ncomp = (int)g_.rep.size();
+    int total = 1;
+    for (int k = 0; k < nc; ++k) total *= 3;
+    std::ostringstream head;
+    for (int k = 0; k < K; ++k) {
+      head << "      double tt" << k << " = 0, tA" << k << " = 0, tX" << k << " = 0;\n";
+      if (joint) {
+        head << "      double";
+        for (int i = 0; i < 27; ++i) head << (i ? ", " : " ") << "tj" << k << "_" << i << " = 0";
+        head << ";\n";
+      }
+    }
+    head << "#pragma unroll 1\n      for (int as_ = 0; as_ < " << total << "; ++as_) {\n";
+    int div = 1;
+    for (int k = 0; k < nc; ++k) {
+      head << "      const int a" << g_.cut[k] << " = (as_ / " << div << ") % 3;\n";
+      div *= 3;
+    }
+    std::string lam = "10000000.0";
+    for (int k : g_.cut) {
+      const std::string c = loc(k);
+      o_ << "      const double lam" << k << " = a" << k << " == 0 ? " << c << "_0 : (a" << k << " == 1 ? " << c << "_1 : " << c
+         << "_2);\n";
+      lam = "(" + lam + " * lam" + num(k) + ")";
+    }
+    o_ << "      const double Lam = " << lam << ";\n";
+    for (int c = 0; c < ncomp; ++c) {
+      marginal(g_.rep[c]);
+      o_ << "      const double Zc" << c << " = (m" << g_.rep[c] << "_0 + m" << g_.rep[c] << "_1) + m" << g_.rep[c] << "_2;\n";
+    }
+    for (int c = 0; c < ncomp; ++c) {
+      std::string w = "Lam";
+      for (int c2 = 0; c2 < ncomp; ++c2)
+        if (c2 != c) w = "(" + w + " * Zc" + num(c2) + ")";
+      o_ << "      const double Wc" << c << " = " << w << ";\n";
+    }
+    for (int k = 0; k < K; ++k) {
+      const int F = family_of(kids[k]);
+      const std::string b = trio(F, kids[k], mask, k), W = "Wc" + num(family_comp(F));
+      o_ << "      tt" << k << " = __builtin_fma(" << b << "s, " << W << ", tt" << k << ");\n"
+         << "      tA" << k << " = __builtin_fma(" << b << "A, " << W << ", tA" << k << ");\n"
+         << "      tX" << k << " = __builtin_fma(" << b << "X, " << W << ", tX" << k << ");\n";
+      if (joint)
+        for (int i = 0; i < 27; ++i)
+          o_ << "      tj" << k << "_" << i << " = __builtin_fma(" << b << "_" << i << ", " << W << ", tj" << k << "_" << i << ");\n";
+      fence(1);
+    }
+    std::string out = head.str() + o_.str() + "      }\n";
+    o_.str("");
+    for (int k = 0; k < K; ++k) trio_out(k, "tt" + num(k), "tA" + num(k), "tX" + num(k), joint ? "tj" + num(k) + "_" : "");
+    return out + o_.str();
+  }
+
  private:
+  int family_of(int c) const {
+    for (int F : g_.nb[c])
+      for (int k : g_.fam[F].kids)
+        if (k == c) return F;
+    throw std::logic_error("trio: member " + std::to_string(c) + " has no family");
+  }
+  // the forest component of family F (every family has a member that is not conditioned on: forest_without)
+  int family_comp(int F) const {
+    const Family &f = g_.fam[F];
+    std::vector<int> mem = {f.mo, f.fa};
+    mem.insert(mem.end(), f.kids.begin(), f.kids.end());
+    for (int p : mem)
+      if (!g_.is_cut(p)) return g_.comp[p];
+    throw std::logic_error("trio: a family of conditioned members only");
+  }
+
+  // child c's 27 clique terms b<c>_<i> (i = 9 gc + 3 gm + gf), their sum b<c>s and their masked sums b<c>A / b<c>X
+  std::string trio(int F, int c, const std::vector<std::vector<double>> &mask, int k) {
+    (void)fac2var(F, c);  // its product C of the parents' messages and the other children's summaries
+    const std::string C = "f" + num(F) + "v" + num(c) + "w", xc = var2fac(c, F), n = "b" + num(c);
+    for (int gc = 0; gc < 3; ++gc)
+      for (int gm = 0; gm < 3; ++gm)
+        for (int gf = 0; gf < 3; ++gf)
+          o_ << "      const double " << n << "_" << 9 * gc + 3 * gm + gf << " = (" << T(c, gc, gm, gf) << " * " << C << "_" << gm << gf
+             << ") * " << xc << "_" << gc << ";\n";
+    auto sum = [&](const std::string &name, const std::vector<double> *m) {
+      std::string e;
+      for (int i = 0; i < 27; ++i)
+        if (!m || (*m)[27 * k + i] == 0.0) e = e.empty() ? n + "_" + num(i) : "(" + e + " + " + n + "_" + num(i) + ")";
+      o_ << "      const double " << name << " = " << (e.empty() ? "0.0" : e) << ";\n";
+    };
+    sum(n + "s", nullptr);
+    sum(n + "A", &mask[0]);
+    sum(n + "X", &mask[1]);
+    fence(1);
+    return n;
+  }
+
+  // child k's outputs from its total s, its masked sums (the site's chromosome picks one) and, joint, the 27 terms j<i>
+  void trio_out(int k, const std::string &s, const std::string &mA, const std::string &mX, const std::string &j) {
+    auto stores = [&](const char *op, const char *by) {
+      std::string t = "if (dg) dg[" + num(k) + "] = dm_ " + op + " " + by + ";";
+      if (!j.empty()) {
+        t += " if (jg) {";
+        for (int i = 0; i < 27; ++i) t += " jg[" + num(27 * k + i) + "] = " + j + num(i) + " " + op + " " + by + ";";
+        t += " }";
+      }
+      return t;
+    };
+    o_ << "      { const double s = " << s << "; if (s <= 0) bn_fail = true;\n"
+       << "        const double dm_ = xchr_ ? " << mX << " : " << mA << ";\n"
+       << "        if (s < 1e-290) { asm volatile(\"\" ::: \"memory\"); " << stores("/", "s") << " }\n"
+       << "        else { const double r = 1.0 / s; " << stores("*", "r") << " } }\n";
+  }
+
   const Model &m_;
   const Graph &g_;
   const int fences_;  // 0 none, 1 after every family->member message, 2 also after local factors and child sums
@@ -1073,7 +1202,109 @@ std::string direct_shell(const Model &m, const std::string &comment, const std::
   return s.str();
 }
 
+// The trio kernel's shell: direct_shell's form (a lane reads its site's row straight from global memory, 3.4 KB of LDS whatever
+// the pedigree's size), no single posterior stored and no shortcut: every site that passes the single-posterior rule runs the
+// full network.  Outputs per site: joint[27 K] and dnm[K] (either may be null), status.
+std::string trio_shell(const Model &m, const std::string &comment, const std::string &body, int K, bool want_dnm, bool want_joint, int bt,
+                       bool fence_single, bool chrx_loop, bool lean) {
+  const int N = m.n_members, W3 = 3 * N;
+  std::ostringstream s;
+  s << "// generated by famseq_amd/csrc for a " << N << "-member pedigree: " << comment << "\n"
+    << "#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n#pragma clang fp contract(off)\n"
+    << "#define W3 " << W3 << "\n#define BT " << bt << "\n#define NKID " << K << "\n"
+    << "#define LDS_BARRIER() asm volatile(\"s_waitcnt lgkmcnt(0)\\n\\ts_barrier\" ::: \"memory\")\n"
+    << kDiv3Text;
+  if (lean)
+    for (int p = 0; p < N; ++p)
+      for (int gt = 0; gt < 3; ++gt) s << "#define l" << p << "_" << gt << " lgv[" << 3 * p + gt << "]\n";
+  s << "extern \"C\" __global__ __launch_bounds__(BT, 1) void famseq_trio(const double *__restrict__ lk_g,\n"
+    << "    const unsigned char *__restrict__ flags_g, double *__restrict__ joint_g, double *__restrict__ dnm_g,\n"
+    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc) {\n"
+    << "  __shared__ double s_tc[432];\n"
+    << "  const int tid = threadIdx.x;\n"
+    << "  for (int i = tid; i < 432; i += BT) s_tc[i] = tc_g[i];\n"
+    << "  LDS_BARRIER();\n"
+    << "  const long chunks = (n_sites + BT - 1) / BT;\n"
+    << "  const long q_wg = chunks / gridDim.x, r_wg = chunks - q_wg * gridDim.x;\n"
+    << "  const long c_lo = (long)blockIdx.x * q_wg + (blockIdx.x < r_wg ? blockIdx.x : r_wg), c_hi = c_lo + q_wg + (blockIdx.x < r_wg ? 1 : 0);\n"
+    << "  const double kNaN = __builtin_nan(\"\");\n"
+    << "  (void)lc;\n"
+    << "  for (long ch = c_lo; ch < c_hi; ++ch) {\n"
+    // a lane beyond the batch's end works on the last site: the same values to the same addresses as that site's own lane
+    << "    const long site = ch * BT + tid < n_sites ? ch * BT + tid : n_sites - 1;\n"
+    << "    const double *lg = lk_g + site * W3;\n"
+    // (an output this form does not write is a null constant: its stores fold away)
+    << (want_joint ? "    double *jg = joint_g ? joint_g + site * (27 * NKID) : nullptr;\n" : "    double *const jg = nullptr;\n")
+    << (want_dnm ? "    double *dg = dnm_g ? dnm_g + site * NKID : nullptr;\n" : "    double *const dg = nullptr;\n")
+    << "    (void)jg; (void)dg;\n"
+    << "    const int fl = flags_g ? (flags_g[site] & 3) : 0;\n"
+    << "    const bool xchr_ = (fl & 2) != 0;\n"
+    << "    const double *tcf = s_tc + fl * 108;\n"
+    << "    bool single_fail = false, full = false, bn_fail = false;\n"
+    << "    (void)full;\n";
+  if (lean)
+    s << "    typedef const volatile __attribute__((address_space(1))) double glb_cvd;\n    glb_cvd *lgv = (glb_cvd *)lg;\n";
+  else
+    for (int p = 0; p < N; ++p)
+      for (int gt = 0; gt < 3; ++gt) s << "    const double l" << p << "_" << gt << " = lg[" << 3 * p + gt << "];\n";
+  // the single-posterior failure rule only (a lk * prior row sum <= 0): nothing of the single posterior is stored
+  s << single_posterior_statements(m, true, false, fence_single);
+  if (chrx_loop)
+    s << "    {\n"
+      << "#pragma unroll 1\n"
+      << "      for (int x_ = 0; x_ < 2; ++x_) {\n"
+      << "        const bool mine_ = !single_fail && xchr_ == (x_ == 1);\n"
+      << "        if (__builtin_amdgcn_ballot_w64(mine_) == 0) continue;\n"
+      << "        const double *tcx = tc_g + x_ * 216;\n"
+      << "        if (mine_) {\n";
+  else
+    s << "    if (!single_fail) {\n";
+  s << body << (chrx_loop ? "        }\n      }\n    }\n" : "    }\n")
+    << "    if (single_fail || bn_fail) {\n"
+    << "      if (dg) {\n#pragma unroll 1\n        for (int k = 0; k < NKID; ++k) dg[k] = kNaN;\n      }\n"
+    << "      if (jg) {\n#pragma unroll 1\n        for (int k = 0; k < 27 * NKID; ++k) jg[k] = kNaN;\n      }\n"
+    << "    }\n"
+    << "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n"
+    << "  }\n}\n";
+  return s.str();
+}
+
 }  // namespace
+
+std::vector<int> trio_children(const Model &m) {
+  std::vector<int> kids;
+  for (int p = 0; p < m.n_members; ++p)
+    if (m.mother[p] >= 0) kids.push_back(p);
+  return kids;
+}
+
+std::string trio_source(const Model &m, int variant, int form) {
+  Graph g;
+  std::string why;
+  if (!build_graph(m, g, &why)) throw std::runtime_error("elimination engine: " + why);
+  if (form < 1 || form > 3) throw std::runtime_error("trio_source: form must be 1 (dnm), 2 (joint) or 3 (both)");
+  const std::vector<int> kids = trio_children(m);
+  // the de novo mask: where the mutation-free transmission table of the child is exactly 0 (model.cpp), [autosome, chrX][K][27]
+  double a0[27], xf0[27], xm0[27];
+  famseq_transmission_tables(0.0, a0, xf0, xm0);
+  std::vector<std::vector<double>> mask(2, std::vector<double>(27 * kids.size()));
+  for (size_t k = 0; k < kids.size(); ++k)
+    for (int i = 0; i < 27; ++i) {
+      mask[0][27 * k + i] = a0[i];
+      mask[1][27 * k + i] = m.gender[kids[k]] == 1 ? xm0[i] : xf0[i];
+    }
+  const int f = variant & 3;
+  // (from forty members on the likelihoods are read from the lane's row at each use, as variant 8+ of famseq_elim does when asked:
+  // 3 N doubles of registers are the widest pedigrees' wall)
+  const bool lean = m.n_members >= 40;
+  const bool want_dnm = form & 1, want_joint = form & 2;
+  const std::string what = "trio posteriors (" + std::string(want_dnm && want_joint ? "de novo + joint" : (want_dnm ? "de novo" : "joint")) +
+                           ") over " + std::to_string(g.fam.size()) + " nuclear families" +
+                           (g.cut.empty() ? "" : ", conditioned on " + std::to_string(g.cut.size()) + " member(s)") + ", variant " +
+                           std::to_string(f);
+  return trio_shell(m, what, Emitter(m, g, f < 2 ? f : 2, /*scalar_t=*/f >= 1, "pg", lean).trio_body(kids, mask, want_joint),
+                    (int)kids.size(), want_dnm, want_joint, elim_block_threads(m, false), f >= 3, /*chrx_loop=*/f >= 1, lean);
+}
 
 std::string elim_source(const Model &m, int variant, bool call_mode) {
   Graph g;

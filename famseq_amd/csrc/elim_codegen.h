@@ -3,6 +3,7 @@
 #define FAMSEQ_ELIM_CODEGEN_H_
 
 #include <string>
+#include <vector>
 
 #include "famseq_hip.h"
 #include "model.h"
@@ -31,6 +32,15 @@ constexpr int kElimCallVariants = 8;
 std::string elim_source(const Model &m, int variant, bool call_mode = false);
 int elim_block_threads(const Model &m, bool call_mode = false);
 int elim_first_variant(const Model &m, bool call_mode = false);  // where jit_pick_variant starts (see elim_block_threads)
+
+// Trio posteriors (famseq_trio_batch): the children are the members with parents, in PED order.
+std::vector<int> trio_children(const Model &m);
+// HIP source of `extern "C" __global__ famseq_trio(lk, flags, joint, dnm, status, n_sites, tc, lc)`: per site and child k the
+// posterior joint[27 k + 9 gc + 3 gm + gf] of the child's and its parents' genotypes in the full network, and dnm[k], its mass
+// where the mutation-free transmission table is 0.  form: 1 dnm only, 2 joint only, 3 both (what is not in the form is never
+// written).  variant 0..3: the fence levels of famseq_elim's (kTrioVariants).  Throws if the engine does not serve the pedigree.
+constexpr int kTrioVariants = 4;
+std::string trio_source(const Model &m, int variant, int form);
 
 // Shared shell of the generated kernels (see elim_codegen.cpp).
 extern const std::string kCallHelpers;  // fused call path: fs_phred, STAGE_IN_PL, STAGE_OUT_CALL, STAGE_FGT

@@ -3,7 +3,7 @@
 // Keeps the reference's CLI and file surface for the `-method 1` path:
 //   FamSeq vcf -vcfFile f -pedFile p -output o [-v] [-a] [-d] [-o] [-l loc] [-method 1]
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
-//              [-genoProbXK a c] [-LRC x]
+//              [-genoProbXK a c] [-LRC x] [-dnm]
 //   FamSeq LK  -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -16,7 +16,8 @@
 //   LK driver                            file.cpp:1640-1886
 // Differences by design: ONE pass over the input (the reference reads the file twice), sites are
 // queued and evaluated in batches on the GPU (famseq_bn_batch) with the output order preserved,
-// and only -method 1 exists here (methods 2/3 are other algorithms, out of scope).
+// -method 2 is the exact sum-product engine (the marginals of the reference's Elston-Stewart peeling), -method 3 (MCMC) is
+// not part of this build, and -dnm (vcf mode) adds each child's de novo mutation posterior (DNP) from the trio kernel.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -185,6 +186,7 @@ struct Options {
   double mrate = 1e-7, lrc = 1;
   vector<double> gN, gK, gXN, gXK;
   int num_burn = -999, num_rep = -999;
+  bool dnm = false;  // -dnm: a DNP field per sample (vcf mode)
 };
 
 // returns 0 good, 1 warnings, -1 stop (checkInput.h:345-349)
@@ -312,6 +314,8 @@ int parse_options(int argc, char **argv, Options &o) {
       } else {
         (opt == "numRep" ? o.num_rep : o.num_burn) = std::atoi(argv[i]);
       }
+    } else if (opt == "dnm") {
+      o.dnm = true;
     } else if (opt == "LRC") {
       i++;
       if (missing(i)) {
@@ -650,6 +654,20 @@ famseq_ctx *make_ctx(const Options &o, const Ped &ped, const vector<uint8_t> &se
     return nullptr;
   }
   return ctx;
+}
+
+// -dnm: does the sum-product engine, which the trio kernel is a form of, serve this pedigree?  Asked on a plan-only context
+// before any input is read.
+bool dnm_supported(const Options &o, const Ped &ped) {
+  CliModel m;
+  vector<uint8_t> all(ped.n(), 1);
+  if (m.init(ped, all, o.mrate, o.lrc) != 0) return true;  // (the driver reports a bad pedigree itself)
+  char err[512] = {0};
+  famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
+  const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;
+  if (k < 0) std::cout << "-dnm cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
+  famseq_destroy(probe);
+  return k >= 0;
 }
 
 void put_triple(std::ostream &o, const double *p) { o << p[0] << ":" << p[1] << ":" << p[2]; }
@@ -1201,6 +1219,9 @@ bool run_vcf(const Options &o, const Ped &ped) {
     fout << "##FORMAT=<ID=FPP,Number=G,Type=Integer,Description=\"Normalized, Phred-scaled for posterior probability "
             "calculated by FamSeqPro\">" << std::endl;
     fout << "##FORMAT=<ID=FGT,Number=1,Type=String,Description=\"Genotype called by FamSeqPro\">" << std::endl;
+    if (o.dnm)
+      fout << "##FORMAT=<ID=DNP,Number=1,Type=Float,Description=\"Posterior probability of a de novo mutation (genotype "
+              "Mendelian-inconsistent with the parents')\">" << std::endl;
   };
   auto fs_info = [&] {
     fout << "##FS mutation rate=" << o.mrate << " " << std::endl;
@@ -1261,6 +1282,15 @@ bool run_vcf(const Options &o, const Ped &ped) {
   for (int i = 0; i < 9; i++) fout << head[i] << '\t';
   for (int c : seq_cols) fout << head[9 + c] << '\t';
   fout << std::endl;
+  // -dnm: column j -> its member's index among the children (famseq_trio_children: the members with parents, PED order), -1 for a founder
+  vector<int> kid_of_col(seq_members.size(), -1);
+  int n_kids = 0;
+  {
+    vector<int> kid(ped.n(), -1);
+    for (int p = 0; p < ped.n(); ++p)
+      if (m.mo[p] >= 0) kid[p] = n_kids++;
+    for (size_t j = 0; j < seq_members.size(); ++j) kid_of_col[j] = kid[seq_members[j]];
+  }
 
   // ---- location filter (file.cpp:235-298)
   vector<vector<int>> loc(25);
@@ -1460,6 +1490,8 @@ bool run_vcf(const Options &o, const Ped &ped) {
     PlBatch io;          // pinned: pl + flags in, gpp / fpp / fgt / status out
     vector<double> lk;   // fp64 input, only for a block with a non-integer PL/GL field
     vector<TextBuf> text;
+    vector<double> dnm;      // -dnm: [site][child] de novo posteriors ...
+    vector<uint8_t> tstatus;  // ... and the trio kernel's status per site
   } slots[4];  // one being cut and parsed, one at the GPU, one being formatted, one being written
   bool ok = true;
   for (Slot &sl : slots) sl.parts.resize(n_threads), sl.text.resize(n_threads);
@@ -1502,12 +1534,33 @@ bool run_vcf(const Options &o, const Ped &ped) {
           std::cerr << "famseq_bn_call_batch failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
           flush_ok = false;
         }
+        if (o.dnm && flush_ok) {  // the same batch through the trio kernel (full network, whatever -LRC and -method say)
+          sl.dnm.resize(sl.n_sites * size_t(n_kids)), sl.tstatus.resize(sl.n_sites);
+          const int rt = famseq_trio_batch(ctx, (int64_t)sl.n_sites, sl.packed ? nullptr : sl.lk.data(), sl.packed ? sl.io.pl : nullptr,
+                                           seq_members.data(), (int32_t)n_seq, sl.io.flags, nullptr, n_kids ? sl.dnm.data() : nullptr,
+                                           sl.tstatus.data());
+          if (rt != 0) {
+            std::cerr << "famseq_trio_batch failed (" << rt << "): " << famseq_last_error(ctx) << std::endl;
+            flush_ok = false;
+          }
+        }
       }
       t_gpu += now_s() - t0;
       to_formatter.put(i);
     }
     to_formatter.put(-1);
   });
+  // -dnm: ":<DNP>" before the closing tab of sample j's field — "." for a founder, NA where the site or its trio posteriors failed
+  auto put_dnp = [&](TextBuf &out, const Slot &sl, size_t s, size_t j, bool failed) {
+    --out.n;
+    out.ch(':');
+    const int kid = kid_of_col[j];
+    if (failed) out.put("NA", 2);
+    else if (kid < 0) out.ch('.');
+    else if (sl.tstatus[s] != 0) out.put("NA", 2);
+    else out.num(sl.dnm[s * size_t(n_kids) + size_t(kid)]);
+    out.ch('\t');
+  };
   // ... the results are turned into text on their own thread (and its helpers) while the next block is at the GPU ...
   std::thread formatter([&] {
     for (;;) {
@@ -1528,12 +1581,14 @@ bool run_vcf(const Options &o, const Ped &ped) {
               const size_t s = size_t(it.site);
               const Record::Sample *sm = &pt.samples[it.smp];
               out.put(it.raw, it.prefix_len);  // columns 1-8 + FORMAT
-              out.put(":GPP:FPP:FGT\t", 13);
+              if (o.dnm) out.put(":GPP:FPP:FGT:DNP\t", 17);
+              else out.put(":GPP:FPP:FGT\t", 13);
               if (sl.io.status[s] & 3) {  // file.cpp:607-620
                 pt.any_failed = true;
                 for (size_t j = 0; j < k; ++j) {
                   out.put(it.raw + sm[j].off, sm[j].len);
                   out.put(":NA:NA:NA\t", 10);
+                  if (o.dnm) put_dnp(out, sl, s, j, true);
                 }
               } else {
                 for (size_t j = 0; j < k; ++j) {
@@ -1545,11 +1600,12 @@ bool run_vcf(const Options &o, const Ped &ped) {
                   }
                   if (sl.io.text) {
                     out.record(sl.io.text + (s * k + j) * FAMSEQ_TEXT_STRIDE);
-                    continue;
+                  } else {
+                    out.triples(&sl.io.gpp[(s * k + j) * 3], &sl.io.fpp[(s * k + j) * 3]);
+                    const int gt = sl.io.fgt[s * k + j];
+                    out.put(gt == 0 ? "0/0\t" : (gt == 1 ? "0/1\t" : "1/1\t"), 4);
                   }
-                  out.triples(&sl.io.gpp[(s * k + j) * 3], &sl.io.fpp[(s * k + j) * 3]);
-                  const int gt = sl.io.fgt[s * k + j];
-                  out.put(gt == 0 ? "0/0\t" : (gt == 1 ? "0/1\t" : "1/1\t"), 4);
+                  if (o.dnm) put_dnp(out, sl, s, j, false);
                 }
               }
             }
@@ -1863,6 +1919,7 @@ void help() {
             << "-genoProbXN\tPr(G) for chromosome X of males, not in dbSNP. Default 0.999 0.001." << std::endl
             << "-genoProbXK\tPr(G) for chromosome X of males, in dbSNP. Default 0.5 0.5." << std::endl
             << "-LRC\t\tLikelihood ratio criterion for the single-sample shortcut. Default 1." << std::endl
+            << "-dnm\t\t(vcf) Add DNP, each child's posterior probability of a de novo mutation, to every sample column." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl
@@ -1916,6 +1973,8 @@ int main(int argc, char **argv) {
     std::cout << "Cannot read Ped file: " << o.ped_file << "." << std::endl << "Cannot set family." << std::endl;
     return -1;
   }
+  if (o.dnm && mode != "vcf") std::cout << "-dnm applies to vcf mode only; ignored here." << std::endl;
+  if (o.dnm && mode == "vcf" && !dnm_supported(o, ped)) return 255;
   const double t0 = now_s();
   if (o.tune_mode) return run_tune(o, ped) ? 0 : -1;
   const bool ok = o.pl_mode ? run_pl(o, ped) : (o.lk_mode ? run_lk(o, ped) : run_vcf(o, ped));

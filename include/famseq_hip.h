@@ -250,6 +250,41 @@ int famseq_bn_call_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *
                                 const uint8_t *d_flags, const int32_t *seq_members, int32_t n_seq, double *d_gpp, double *d_fpp,
                                 int8_t *d_fgt, uint8_t *d_status, char *d_text, void *stream);
 
+/* ---- trio posteriors and de novo mutations ------------------------------------------------------------
+ * What the marginals cannot say: is a child's variant a de novo mutation?  That needs the JOINT posterior of the child's and
+ * both parents' genotypes, which the sum-product engine's family factors hold (the clique belief of a nuclear family, restricted
+ * to one child and the parents).  Served for every pedigree the engine serves: loop-free ones of any size, and pedigrees with
+ * loops up to three conditioned members; any other gets FAMSEQ_E_ARG with the engine's message.
+ *   children   the members that have parents, in PED order; K = their count; child k is member children[k]
+ *   joint [n_sites][K][27]  the posterior over (child k, its mother, its father) in the full pedigree network — the network
+ *              the 3^N enumeration sums, with the same priors (Known flag), chrX tables and male priors and likelihoods —
+ *              indexed 9 gc + 3 gm + gf (the transmission tables' order); the 27 values sum to 1
+ *   dnm   [n_sites][K]      the de novo posterior: the sum of joint over the entries where the mutation-free transmission table
+ *              of the child is exactly 0 (autosomes: the autosomal table at mutation rate 0; chrX: the son's or the daughter's),
+ *              i.e. the posterior probability that the child's genotype is Mendelian-inconsistent with its parents'.  Exactly 0.0
+ *              at mutation rate 0.
+ *   status [n_sites]        0 OK; 1 the single-posterior failure rule of famseq_bn_batch (a lk * prior row sum <= 0: the
+ *              drivers print such a site as NA); 2 the network's total weight is <= 0.  There is no -LRC shortcut: every site
+ *              runs the full network.  Wherever status != 0, joint and dnm are NaN.
+ * The kernel is generated per pedigree and output form (dnm only, joint only, both: chosen from which outputs are given) and
+ * compiled on the first trio call, or ahead through famseq_set_option "trio_kernels" (1 dnm, 2 joint, 3 both); nothing of it
+ * exists before.  famseq_plan_json: "trio_code_object", "trio_variant", "trio_children". */
+
+/* K, and the children's member indices in idx[K] (idx may be NULL).  FAMSEQ_E_ARG on a pedigree the engine does not serve. */
+int famseq_trio_children(famseq_ctx *ctx, int32_t *idx);
+
+/* Host buffers, blocking, chunked and pipelined like famseq_bn_call_batch.  Exactly one of lk [n_sites][N][3] / pl16
+ * [n_sites][n_seq][3] (packed PLs in VCF column order, seq_members[n_seq] their PED indices, as famseq_bn_call_batch: unpacked
+ * on the device by the same stage); seq_members / n_seq are ignored with lk.  Any of joint / dnm / status may be NULL. */
+int famseq_trio_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                      int32_t n_seq, const uint8_t *flags, double *joint, double *dnm, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
+ * NULL = the default stream) and returns without synchronising.  Packed input goes through likelihood rows this context keeps. */
+int famseq_trio_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                             const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_joint, double *d_dnm,
+                             uint8_t *d_status, void *stream);
+
 /* Diagnostic / test aid: the device formatter alone.  values[n] (host) -> out[n][16] (host): the characters of each
  * value as the text kernel prints a GPP / FPP number from byte 0, their count in byte 15; "nan" for anything outside
  * the formatter's domain, 0 and [1e-16, 999999.5). */
