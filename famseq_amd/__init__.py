@@ -81,6 +81,7 @@ ABI_SYMBOLS = [
     "famseq_bn_batch", "famseq_bn_batch_sharded", "famseq_bn_batch_device", "famseq_bn_batch_device_sharded",
     "famseq_bn_call_batch", "famseq_bn_call_text_batch", "famseq_bn_call_batch_device", "famseq_format_probe", "famseq_alloc_pinned", "famseq_free_pinned", "famseq_stream_probe",
     "famseq_call_genotypes", "famseq_trio_children", "famseq_trio_batch", "famseq_trio_batch_device",
+    "famseq_map_batch", "famseq_map_batch_device",
 ]
 PL_MISSING = 0xFFFF
 
@@ -158,6 +159,10 @@ def lib():
     L.famseq_trio_batch.restype = C.c_int
     L.famseq_trio_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp]
     L.famseq_trio_batch_device.restype = C.c_int
+    L.famseq_map_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, C.POINTER(C.c_int8), dp, bp]
+    L.famseq_map_batch.restype = C.c_int
+    L.famseq_map_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp]
+    L.famseq_map_batch_device.restype = C.c_int
     _lib = L
     return L
 
@@ -359,6 +364,45 @@ class Context:
                                             _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_joint or None,
                                             d_dnm or None, d_status or None, stream or None)
         self._check(rc, "famseq_trio_batch_device")
+
+    def map_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_gt=True, want_post=True):
+        """The joint MAP configuration: -> (map_gt[S,N] int8, map_post[S] float64, status[S] uint8).
+        map_gt[s] is the most probable genotype assignment of the whole pedigree at site s (0 / 1 / 2 per member, PED order; -1
+        where status != 0), map_post[s] its posterior probability (NaN where status != 0).  Input as trio_batch: either lk
+        [S,N,3] float64 or pl16 [S,n_seq,3] uint16 in VCF column order (seq_members: their PED indices).  want_gt / want_post
+        False: that output is not computed and returned as None."""
+        if (lk is None) == (pl16 is None):
+            raise ValueError("give exactly one of lk / pl16")
+        seq, n_seq = None, 0
+        if lk is not None:
+            lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
+            s = lk.shape[0]
+        else:
+            seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+            n_seq = len(seq)
+            pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, n_seq, 3)
+            s = pl16.shape[0]
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        if fl is not None and fl.shape != (s,):
+            raise ValueError("flags must have one byte per site")
+        gt = np.empty((s, self.n), np.int8) if want_gt else None
+        post = np.empty(s) if want_post else None
+        status = np.zeros(s, np.uint8)
+        rc = lib().famseq_map_batch(self._h, s, None if lk is None else _p(lk, C.c_double),
+                                    None if pl16 is None else _p(pl16, C.c_uint16), None if seq is None else _p(seq, C.c_int32),
+                                    n_seq, None if fl is None else _p(fl, C.c_uint8), None if gt is None else _p(gt, C.c_int8),
+                                    None if post is None else _p(post, C.c_double), _p(status, C.c_uint8))
+        self._check(rc, "famseq_map_batch")
+        return gt, post, status
+
+    def map_batch_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_map_gt=0, d_map_post=0, d_status=0, stream=0):
+        """The joint MAP configuration on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream`
+        and returns."""
+        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+        rc = lib().famseq_map_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
+                                           _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_map_gt or None,
+                                           d_map_post or None, d_status or None, stream or None)
+        self._check(rc, "famseq_map_batch_device")
 
     def g6_probe(self, values):
         """The device formatter alone (famseq_format_probe): -> list of bytes, one per value."""

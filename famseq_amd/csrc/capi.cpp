@@ -123,13 +123,21 @@ struct famseq_ctx {
   // the host-staged entry's own chunk buffers, and the device entry's likelihood rows for packed input
   JitKernel trio[4]{};
   int trio_blocks_per_cu[4] = {}, trio_variant[4] = {-1, -1, -1, -1}, trio_last = 0;
-  double *d_tj[kSlots] = {}, *d_td[kSlots] = {}, *d_tlk[kSlots] = {};
-  uint16_t *d_tpl[kSlots] = {};
-  uint8_t *d_tflags[kSlots] = {}, *d_tstatus[kSlots] = {};
-  int64_t trio_slot_sites = 0;
-  int trio_slot_seq = 0;
-  double *trio_dev_lk = nullptr;
+  // (SideSlots: likelihood rows / packed PLs / flags in, two outputs of a row size each and the status out)
+  struct SideSlots {
+    void *d_a[kSlots] = {}, *d_b[kSlots] = {};
+    double *d_lk[kSlots] = {};
+    uint16_t *d_pl[kSlots] = {};
+    uint8_t *d_flags[kSlots] = {}, *d_status[kSlots] = {};
+    int64_t sites = 0;
+    int seq = 0;
+    size_t a_row = 0, b_row = 0;
+  } trio_slots, map_slots;
+  double *trio_dev_lk = nullptr;  // shared by the trio and MAP device entries
   int64_t trio_dev_sites = 0;
+  // the joint MAP configuration (famseq_map_batch*): its generated kernel, built on first use; its host entry's chunk buffers
+  JitKernel map{};
+  int map_blocks_per_cu = 0, map_variant = -1;
   std::string tune_report;  // what famseq_set_option "tune" measured (famseq_plan_json "tune")
   std::string err, json;
 };
@@ -204,19 +212,15 @@ void free_slots(famseq_ctx *c) {
   c->slot_seq = 0;
 }
 
-void free_trio_slots(famseq_ctx *c) {
+void free_side_slots(famseq_ctx::SideSlots &t) {
   for (int s = 0; s < famseq_ctx::kSlots; ++s) {
-    for (double **q : {&c->d_tj[s], &c->d_td[s], &c->d_tlk[s]}) {
-      if (*q) (void)hipFree(*q);
-      *q = nullptr;
-    }
-    if (c->d_tpl[s]) (void)hipFree(c->d_tpl[s]);
-    if (c->d_tflags[s]) (void)hipFree(c->d_tflags[s]);
-    if (c->d_tstatus[s]) (void)hipFree(c->d_tstatus[s]);
-    c->d_tpl[s] = nullptr, c->d_tflags[s] = c->d_tstatus[s] = nullptr;
+    for (void *q : {t.d_a[s], t.d_b[s], (void *)t.d_lk[s], (void *)t.d_pl[s], (void *)t.d_flags[s], (void *)t.d_status[s]})
+      if (q) (void)hipFree(q);
+    t.d_a[s] = t.d_b[s] = nullptr, t.d_lk[s] = nullptr, t.d_pl[s] = nullptr, t.d_flags[s] = t.d_status[s] = nullptr;
   }
-  c->trio_slot_sites = 0;
-  c->trio_slot_seq = 0;
+  t.sites = 0;
+  t.seq = 0;
+  t.a_row = t.b_row = 0;
 }
 
 // (Re)build the plan and, on a device ctx, upload its image and the factor tables.
@@ -532,6 +536,37 @@ hipError_t launch_trio(famseq_ctx *c, int form, int64_t n_sites, const double *d
                           d_joint, d_dnm, d_status, stream);
 }
 
+// The same for the MAP kernel (famseq_map): nothing of it exists until the first MAP call or the "map_kernels" option.
+int load_map(famseq_ctx *c) {
+  JitKernel &k = c->map;
+  if (k.fn || (c->device < 0 && !k.path.empty())) return 0;
+  std::string why;
+  if (!elim_supported(c->model, &why)) return fail(c, FAMSEQ_E_ARG, "joint MAP call (sum-product engine): " + why);
+  try {
+    const Model &mdl = c->model;
+    const std::string src = jit_pick_variant([&mdl](int v) { return map_source(mdl, v); }, kMapVariants, &c->map_variant, 0);
+    if (c->device < 0) {
+      k.path = jit_compile(src);
+      return 0;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    k = jit_load(src, "famseq_map");
+  } catch (const std::exception &e) {
+    return fail(c, FAMSEQ_E_HIP, e.what());
+  }
+  int nb = 0;
+  HIP_TRY(c, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, elim_block_threads(c->model), 0));
+  c->map_blocks_per_cu = nb > 0 ? nb : 1;
+  return 0;
+}
+
+hipError_t launch_map(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, int8_t *d_gt, double *d_post,
+                      uint8_t *d_status, hipStream_t stream) {
+  // (famseq_map's third argument is the int8 genotype rows: launch_generated passes the pointer through untyped)
+  return launch_generated(c, c->map.fn, elim_block_threads(c->model), c->map_blocks_per_cu, n_sites, d_lk, d_flags,
+                          reinterpret_cast<double *>(d_gt), d_post, d_status, stream);
+}
+
 }  // namespace
 
 extern "C" int famseq_device_count(void) {
@@ -642,7 +677,9 @@ extern "C" void famseq_destroy(famseq_ctx *c) {
     jit_unload(c->lane_call);
     for (JitKernel &k : c->grp) jit_unload(k);
     for (JitKernel &k : c->trio) jit_unload(k);
-    free_trio_slots(c);
+    jit_unload(c->map);
+    free_side_slots(c->trio_slots);
+    free_side_slots(c->map_slots);
     if (c->trio_dev_lk) (void)hipFree(c->trio_dev_lk);
     if (c->d_lut) (void)hipFree(c->d_lut);
     if (c->d_seq) (void)hipFree(c->d_seq);
@@ -901,6 +938,10 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
     if (value < 1 || value > 3) return fail(c, FAMSEQ_E_ARG, "trio_kernels takes 1 (dnm), 2 (joint) or 3 (both)");
     return load_trio(c, (int)value);
   }
+  else if (k == "map_kernels") {  // build (and on a device ctx load) the MAP kernel now
+    if (value != 1) return fail(c, FAMSEQ_E_ARG, "map_kernels takes 1");
+    return load_map(c);
+  }
   else if (k == "group_digits") {
     if (value < -1 || value > enumgen_max_group_digits(c->model))
       return fail(c, FAMSEQ_E_ARG, "group_digits must be -1 (auto) or 0.." + std::to_string(enumgen_max_group_digits(c->model)) +
@@ -959,7 +1000,8 @@ std::string trio_json(const famseq_ctx *c) {
   std::string o = ",\"trio_code_object\":\"" + json_str(f ? c->trio[f].path : std::string()) + "\",\"trio_code_objects\":[";
   for (int k = 1; k <= 3; ++k) o += std::string(k > 1 ? "," : "") + "\"" + json_str(c->trio[k].path) + "\"";
   return o + "],\"trio_variant\":" + std::to_string(f ? c->trio_variant[f] : -1) + ",\"trio_children\":" +
-         std::to_string(trio_children(c->model).size());
+         std::to_string(trio_children(c->model).size()) + ",\"map_code_object\":\"" + json_str(c->map.path) + "\",\"map_variant\":" +
+         std::to_string(c->map_variant);
 }
 }  // namespace
 
@@ -1447,14 +1489,14 @@ int upload_lut(famseq_ctx *c) {
   return 0;
 }
 
-// Arguments both trio entries check the same way; loads the kernel of the form the outputs ask for.
+// Arguments the trio and MAP entries check the same way; loads the kernel (trio: of the form the outputs ask for; form 0: MAP).
 int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl16, const int32_t *seq_members, int32_t n_seq,
                   int form) {
   if (n_sites < 0 || (n_sites > 0 && ((lk == nullptr) == (pl16 == nullptr))))
     return fail(c, FAMSEQ_E_ARG, "exactly one of lk / pl16 must be given");
   if (c->device < 0) return fail(c, FAMSEQ_E_NODEVICE, "context was created without a device; there is no CPU path");
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = load_trio(c, form);
+  int rc = form ? load_trio(c, form) : load_map(c);
   if (rc != 0) return rc;
   if (pl16) {
     if (n_seq < 1) return fail(c, FAMSEQ_E_ARG, "n_seq must be >= 1");
@@ -1464,63 +1506,61 @@ int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl
   return 0;
 }
 
-}  // namespace
+// The host-staged entries' chunk loop (trio and MAP): chunks through the same three stages as famseq_bn_batch (copy in / unpack +
+// kernel / copy out), on the entry's own buffers `t`.  out_a / out_b: the two per-site outputs (NULL: not wanted), a_row / b_row
+// their bytes per site (0: the pedigree has none); launch(n, d_lk, d_flags, d_a, d_b, d_status, stream) enqueues the kernel.
+using SideLaunch = std::function<hipError_t(int64_t, const double *, const uint8_t *, void *, void *, uint8_t *, hipStream_t)>;
 
-// Host buffers: chunks through the same three stages as famseq_bn_batch (copy in / unpack + trio kernel / copy out), on
-// buffers of their own.
-extern "C" int famseq_trio_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
-                                 int32_t n_seq, const uint8_t *flags, double *joint, double *dnm, uint8_t *status) {
-  if (!c) return FAMSEQ_E_ARG;
-  const int form = trio_form(joint, dnm);
-  int rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, form);
-  if (rc != 0 || n_sites == 0) return rc;
-  const int N = c->model.n_members, K = (int)trio_children(c->model).size();
-  const size_t row = size_t(3) * N * sizeof(double), jrow = size_t(27) * K * sizeof(double), drow = size_t(K) * sizeof(double);
+int side_batch(famseq_ctx *c, famseq_ctx::SideSlots &t, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
+               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const SideLaunch &launch) {
+  const int N = c->model.n_members;
+  const size_t row = size_t(3) * N * sizeof(double);
   int64_t chunk = c->chunk_sites;
   if (chunk <= 0) {
-    chunk = std::max<int64_t>(1, (int64_t(64) << 20) / int64_t(std::max(row, jrow + 1)));
+    chunk = std::max<int64_t>(1, (int64_t(64) << 20) / int64_t(std::max(row, a_row + 1)));
     chunk = std::min(chunk, std::max<int64_t>(c->lane_min_sites, (n_sites + 3) / 4));
   }
   chunk = std::min(chunk, n_sites);
   const int want_seq = pl16 ? n_seq : 0;
-  if (c->trio_slot_sites < chunk || c->trio_slot_seq < want_seq) {
-    const int64_t cap = std::max(chunk, c->trio_slot_sites);
-    const int seqcap = std::max(want_seq, c->trio_slot_seq);
-    free_trio_slots(c);
+  if (t.sites < chunk || t.seq < want_seq || t.a_row != a_row || t.b_row != b_row) {
+    const int64_t cap = std::max(chunk, t.sites);
+    const int seqcap = std::max(want_seq, t.seq);
+    free_side_slots(t);
     for (int s = 0; s < famseq_ctx::kSlots; ++s) {
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_tlk[s]), cap * row));
-      if (K) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_tj[s]), cap * jrow));
-      if (K) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_td[s]), cap * drow));
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_tflags[s]), cap));
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_tstatus[s]), cap));
-      if (seqcap) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_tpl[s]), cap * seqcap * 3 * sizeof(uint16_t)));
+      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&t.d_lk[s]), cap * row));
+      if (a_row) HIP_TRY(c, hipMalloc(&t.d_a[s], cap * a_row));
+      if (b_row) HIP_TRY(c, hipMalloc(&t.d_b[s], cap * b_row));
+      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&t.d_flags[s]), cap));
+      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&t.d_status[s]), cap));
+      if (seqcap) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&t.d_pl[s]), cap * seqcap * 3 * sizeof(uint16_t)));
     }
-    c->trio_slot_sites = cap;
-    c->trio_slot_seq = seqcap;
+    t.sites = cap;
+    t.seq = seqcap;
+    t.a_row = a_row, t.b_row = b_row;
   }
   hipStream_t s_in = c->stream[0], s_k = c->stream[1], s_out = c->stream[2];
   // From here on copies into the caller's buffers may be in flight: an error must not return before the streams have drained.
-  rc = [&]() -> int {
+  int rc = [&]() -> int {
     int k = 0;
     for (int64_t lo = 0; lo < n_sites; lo += chunk, ++k) {
       const int s = k % famseq_ctx::kSlots;
       const int64_t n = std::min(chunk, n_sites - lo);
       if (k >= famseq_ctx::kSlots) HIP_TRY(c, hipStreamWaitEvent(s_in, c->ev_out[s], 0));
       if (pl16)
-        HIP_TRY(c, hipMemcpyAsync(c->d_tpl[s], pl16 + lo * n_seq * 3, n * n_seq * 3 * sizeof(uint16_t), hipMemcpyHostToDevice, s_in));
+        HIP_TRY(c, hipMemcpyAsync(t.d_pl[s], pl16 + lo * n_seq * 3, n * n_seq * 3 * sizeof(uint16_t), hipMemcpyHostToDevice, s_in));
       else
-        HIP_TRY(c, hipMemcpyAsync(c->d_tlk[s], lk + lo * 3 * N, n * row, hipMemcpyHostToDevice, s_in));
-      if (flags) HIP_TRY(c, hipMemcpyAsync(c->d_tflags[s], flags + lo, n, hipMemcpyHostToDevice, s_in));
+        HIP_TRY(c, hipMemcpyAsync(t.d_lk[s], lk + lo * 3 * N, n * row, hipMemcpyHostToDevice, s_in));
+      if (flags) HIP_TRY(c, hipMemcpyAsync(t.d_flags[s], flags + lo, n, hipMemcpyHostToDevice, s_in));
       HIP_TRY(c, hipEventRecord(c->ev_in[s], s_in));
       HIP_TRY(c, hipStreamWaitEvent(s_k, c->ev_in[s], 0));
-      if (pl16) HIP_TRY(c, launch_unpack_pl16(c->d_tpl[s], c->d_col, c->d_lut, N, n_seq, n, c->d_tlk[s], s_k));
-      HIP_TRY(c, launch_trio(c, form, n, c->d_tlk[s], flags ? c->d_tflags[s] : nullptr, joint ? c->d_tj[s] : nullptr,
-                             dnm ? c->d_td[s] : nullptr, status ? c->d_tstatus[s] : nullptr, s_k));
+      if (pl16) HIP_TRY(c, launch_unpack_pl16(t.d_pl[s], c->d_col, c->d_lut, N, n_seq, n, t.d_lk[s], s_k));
+      HIP_TRY(c, launch(n, t.d_lk[s], flags ? t.d_flags[s] : nullptr, out_a ? t.d_a[s] : nullptr, out_b ? t.d_b[s] : nullptr,
+                        status ? t.d_status[s] : nullptr, s_k));
       HIP_TRY(c, hipEventRecord(c->ev_done[s], s_k));
       HIP_TRY(c, hipStreamWaitEvent(s_out, c->ev_done[s], 0));
-      if (joint && K) HIP_TRY(c, hipMemcpyAsync(joint + lo * 27 * K, c->d_tj[s], n * jrow, hipMemcpyDeviceToHost, s_out));
-      if (dnm && K) HIP_TRY(c, hipMemcpyAsync(dnm + lo * K, c->d_td[s], n * drow, hipMemcpyDeviceToHost, s_out));
-      if (status) HIP_TRY(c, hipMemcpyAsync(status + lo, c->d_tstatus[s], n, hipMemcpyDeviceToHost, s_out));
+      if (out_a && a_row) HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(out_a) + lo * a_row, t.d_a[s], n * a_row, hipMemcpyDeviceToHost, s_out));
+      if (out_b && b_row) HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(out_b) + lo * b_row, t.d_b[s], n * b_row, hipMemcpyDeviceToHost, s_out));
+      if (status) HIP_TRY(c, hipMemcpyAsync(status + lo, t.d_status[s], n, hipMemcpyDeviceToHost, s_out));
       HIP_TRY(c, hipEventRecord(c->ev_out[s], s_out));
     }
     return 0;
@@ -1530,6 +1570,38 @@ extern "C" int famseq_trio_batch(famseq_ctx *c, int64_t n_sites, const double *l
     if (e != hipSuccess && rc == 0) return fail(c, FAMSEQ_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
   }
   return rc;
+}
+
+// The device entries' packed input: unpacked into likelihood rows this context keeps (grown on demand).
+int side_unpack(famseq_ctx *c, int64_t n_sites, const uint16_t *d_pl16, int32_t n_seq, hipStream_t stream, const double **lk) {
+  const int N = c->model.n_members;
+  if (c->trio_dev_sites < n_sites) {
+    HIP_TRY(c, hipStreamSynchronize(stream));  // nothing of an earlier call may still use what is freed here
+    if (c->trio_dev_lk) (void)hipFree(c->trio_dev_lk);
+    c->trio_dev_lk = nullptr, c->trio_dev_sites = 0;
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->trio_dev_lk), size_t(n_sites) * 3 * N * sizeof(double)));
+    c->trio_dev_sites = n_sites;
+  }
+  HIP_TRY(c, launch_unpack_pl16(d_pl16, c->d_col, c->d_lut, N, n_seq, n_sites, c->trio_dev_lk, stream));
+  *lk = c->trio_dev_lk;
+  return 0;
+}
+
+}  // namespace
+
+// Host buffers: chunked and pipelined (side_batch) on buffers of their own.
+extern "C" int famseq_trio_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                 int32_t n_seq, const uint8_t *flags, double *joint, double *dnm, uint8_t *status) {
+  if (!c) return FAMSEQ_E_ARG;
+  const int form = trio_form(joint, dnm);
+  int rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, form);
+  if (rc != 0 || n_sites == 0) return rc;
+  const size_t K = trio_children(c->model).size();
+  return side_batch(c, c->trio_slots, n_sites, lk, pl16, n_seq, flags, joint, 27 * K * sizeof(double), dnm, K * sizeof(double), status,
+                    [c, form](int64_t n, const double *d_lk, const uint8_t *d_flags, void *d_a, void *d_b, uint8_t *d_status,
+                              hipStream_t st) {
+                      return launch_trio(c, form, n, d_lk, d_flags, static_cast<double *>(d_a), static_cast<double *>(d_b), d_status, st);
+                    });
 }
 
 // Device buffers: enqueue on the caller's stream and return.  Packed input is unpacked into likelihood rows this context keeps
@@ -1542,19 +1614,40 @@ extern "C" int famseq_trio_batch_device(famseq_ctx *c, int64_t n_sites, const do
   const int rc = trio_prologue(c, n_sites, d_lk, d_pl16, seq_members, n_seq, form);
   if (rc != 0 || n_sites == 0) return rc;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const int N = c->model.n_members;
   const double *lk = d_lk;
   if (d_pl16) {
-    if (c->trio_dev_sites < n_sites) {
-      HIP_TRY(c, hipStreamSynchronize(stream));  // nothing of an earlier call may still use what is freed here
-      if (c->trio_dev_lk) (void)hipFree(c->trio_dev_lk);
-      c->trio_dev_lk = nullptr, c->trio_dev_sites = 0;
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->trio_dev_lk), size_t(n_sites) * 3 * N * sizeof(double)));
-      c->trio_dev_sites = n_sites;
-    }
-    HIP_TRY(c, launch_unpack_pl16(d_pl16, c->d_col, c->d_lut, N, n_seq, n_sites, c->trio_dev_lk, stream));
-    lk = c->trio_dev_lk;
+    const int ru = side_unpack(c, n_sites, d_pl16, n_seq, stream, &lk);
+    if (ru != 0) return ru;
   }
   HIP_TRY(c, launch_trio(c, form, n_sites, lk, d_flags, d_joint, d_dnm, d_status, stream));
+  return 0;
+}
+
+// ---- the joint MAP configuration -------------------------------------------------------------------------------------
+
+extern "C" int famseq_map_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                int32_t n_seq, const uint8_t *flags, int8_t *map_gt, double *map_post, uint8_t *status) {
+  if (!c) return FAMSEQ_E_ARG;
+  int rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, 0);
+  if (rc != 0 || n_sites == 0) return rc;
+  return side_batch(c, c->map_slots, n_sites, lk, pl16, n_seq, flags, map_gt, size_t(c->model.n_members), map_post, sizeof(double), status,
+                    [c](int64_t n, const double *d_lk, const uint8_t *d_flags, void *d_a, void *d_b, uint8_t *d_status, hipStream_t st) {
+                      return launch_map(c, n, d_lk, d_flags, static_cast<int8_t *>(d_a), static_cast<double *>(d_b), d_status, st);
+                    });
+}
+
+extern "C" int famseq_map_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                       const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, int8_t *d_map_gt,
+                                       double *d_map_post, uint8_t *d_status, void *stream_) {
+  if (!c) return FAMSEQ_E_ARG;
+  const int rc = trio_prologue(c, n_sites, d_lk, d_pl16, seq_members, n_seq, 0);
+  if (rc != 0 || n_sites == 0) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const double *lk = d_lk;
+  if (d_pl16) {
+    const int ru = side_unpack(c, n_sites, d_pl16, n_seq, stream, &lk);
+    if (ru != 0) return ru;
+  }
+  HIP_TRY(c, launch_map(c, n_sites, lk, d_flags, d_map_gt, d_map_post, d_status, stream));
   return 0;
 }

@@ -290,6 +290,102 @@ class Emitter {
     return out + o_.str();
   }
 
+  // The joint MAP configuration (famseq_map): g* = argmax_g w(g) and its posterior w(g*) / Z, by message passing under two
+  // semirings on the same graph.  One root per component (g_.rep); only the messages that point towards a root are formed.
+  //   sum pass  Z = prod_c sum_g m_root(g): marginal(root), the code every other form uses.
+  //   max pass  (mx_: the same three message kinds, their names prefixed "x", + / fma replaced by max) keeps an arg-max beside
+  //             every maximum, packed into 32-bit words: a child summary nine 2-bit entries (the child's genotype for each
+  //             (gm, gf)), a family -> parent message three 2-bit entries (the other parent's), a family -> child message three
+  //             4-bit entries (3 gm + gf).
+  //   back-track from each root outwards through the families in reverse message order (steps_): shifts of the packed words
+  //             by run-time genotypes, never an indexed array.
+  // Tie rule: every arg-max scans 0, 1, 2 (parent pairs in the order 3 gm + gf) and replaces on strictly greater only, so
+  // among values this arithmetic holds equal the lowest wins.  Loops: per assignment of the cut members (first in loop order
+  // wins ties) W = Lam * prod_c max_c against the best so far, the back-track under that branch (a few dozen integer
+  // instructions; a second run of the body for the best assignment would cost a whole pass); Z accumulates Lam * prod_c Z_c.
+  // Leaves: Z_, W_ (doubles) and the genotypes packed four members to a word in gw<k> (set only where the shell keeps them).
+  std::string map_body() {
+    const int nc = (int)g_.cut.size(), ncomp = (int)g_.rep.size(), nw = (g_.N + 3) / 4;
+    const bool loops = nc > 0;
+    std::ostringstream head;
+    if (loops) {
+      int total = 1;
+      for (int k = 0; k < nc; ++k) total *= 3;
+      head << "      double Zt_ = 0, Wb_ = 0;\n";
+      head << "#pragma unroll 1\n      for (int as_ = 0; as_ < " << total << "; ++as_) {\n";
+      int div = 1;
+      for (int k = 0; k < nc; ++k) {
+        head << "      const int a" << g_.cut[k] << " = (as_ / " << div << ") % 3;\n";
+        div *= 3;
+      }
+      std::string lam = "10000000.0";
+      for (int k : g_.cut) {
+        const std::string c = loc(k);
+        o_ << "      const double lam" << k << " = a" << k << " == 0 ? " << c << "_0 : (a" << k << " == 1 ? " << c << "_1 : " << c
+           << "_2);\n";
+        lam = "(" + lam + " * lam" + num(k) + ")";
+      }
+      o_ << "      const double Lam = " << lam << ";\n";
+    }
+    std::string z = loops ? "Lam" : "", w = z;
+    for (int c = 0; c < ncomp; ++c) {
+      marginal(g_.rep[c]);
+      o_ << "      const double Zc" << c << " = (m" << g_.rep[c] << "_0 + m" << g_.rep[c] << "_1) + m" << g_.rep[c] << "_2;\n";
+      z = z.empty() ? "Zc" + num(c) : "(" + z + " * Zc" + num(c) + ")";
+    }
+    fence(1);
+    mx_ = true;
+    for (int c = 0; c < ncomp; ++c) {
+      const int r = g_.rep[c];
+      std::vector<std::string> in = {loc(r)};
+      for (int F : g_.nb[r]) in.push_back(max_fac2var(F, r));
+      for (int g = 0; g < 3; ++g) {
+        o_ << "      const double xm" << r << "_" << g << " = ";
+        for (size_t k = 0; k < in.size(); ++k) o_ << (k ? " * " : "") << in[k] << "_" << g;
+        o_ << ";\n";
+      }
+      o_ << "      double Xc" << c << " = xm" << r << "_0; unsigned G" << r << " = 0;\n"
+         << "      if (xm" << r << "_1 > Xc" << c << ") { Xc" << c << " = xm" << r << "_1; G" << r << " = 1; }\n"
+         << "      if (xm" << r << "_2 > Xc" << c << ") { Xc" << c << " = xm" << r << "_2; G" << r << " = 2; }\n";
+      w = w.empty() ? "Xc" + num(c) : "(" + w + " * Xc" + num(c) + ")";
+    }
+    mx_ = false;
+    std::ostringstream bt;  // the back-track
+    for (int k : g_.cut) bt << "        const unsigned G" << k << " = (unsigned)a" << k << ";\n";
+    for (size_t i = steps_.size(); i-- > 0;) {
+      const Step &st = steps_[i];
+      const Family &fam = g_.fam[st.F];
+      const std::string gm = "G" + num(fam.mo), gf = "G" + num(fam.fa);
+      if (st.t == fam.mo) {
+        if (!g_.is_cut(fam.fa)) bt << "        const unsigned " << gf << " = (" << st.bp << " >> (2 * " << gm << ")) & 3u;\n";
+      } else if (st.t == fam.fa) {
+        if (!g_.is_cut(fam.mo)) bt << "        const unsigned " << gm << " = (" << st.bp << " >> (2 * " << gf << ")) & 3u;\n";
+      } else {
+        const std::string pr = "pr" + num(st.F);
+        bt << "        const unsigned " << pr << " = (" << st.bp << " >> (4 * G" << st.t << ")) & 15u;\n";
+        if (!g_.is_cut(fam.mo)) bt << "        const unsigned " << gm << " = (" << pr << " * 11u) >> 5;\n";  // pr / 3 for pr < 9
+        if (!g_.is_cut(fam.fa)) bt << "        const unsigned " << gf << " = " << pr << " - 3u * ((" << pr << " * 11u) >> 5);\n";
+      }
+      for (size_t k = 0; k < st.kids.size(); ++k)
+        if (!g_.is_cut(st.kids[k]))
+          bt << "        const unsigned G" << st.kids[k] << " = (" << st.kid_bp[k] << " >> (2 * (3 * " << gm << " + " << gf << "))) & 3u;\n";
+    }
+    for (int k = 0; k < nw; ++k) {
+      bt << "        gw" << k << " = ";
+      for (int j = 0; j < 4 && 4 * k + j < g_.N; ++j) bt << (j ? " | " : "") << "(G" << 4 * k + j << " << " << 8 * j << ")";
+      for (int j = g_.N - 4 * k; j < 4; ++j) bt << " | (255u << " << 8 * j << ")";  // (beyond the last member: never stored)
+      bt << ";\n";
+    }
+    if (!loops) {
+      o_ << "      const double Z_ = " << z << ", W_ = " << w << ";\n      {\n" << bt.str() << "      }\n";
+      return o_.str();
+    }
+    o_ << "      Zt_ = Zt_ + " << z << ";\n      const double Wa_ = " << w << ";\n"
+       << "      if (Wa_ > Wb_) {\n        Wb_ = Wa_;\n" << bt.str() << "      }\n";
+    fence(1);
+    return head.str() + o_.str() + "      }\n      const double Z_ = Zt_, W_ = Wb_;\n";
+  }
+
  private:
   int family_of(int c) const {
     for (int F : g_.nb[c])
@@ -356,6 +452,15 @@ class Emitter {
   std::ostringstream o_;
   std::map<std::string, bool> done_;
   int uid_ = 0;
+  // the max pass of map_body: messages named x..., and what the back-track needs of each family -> member message
+  bool mx_ = false;
+  struct Step {
+    int F, t;
+    std::string bp;                    // the message's packed arg-maxes
+    std::vector<int> kids;             // the family's other children ...
+    std::vector<std::string> kid_bp;   // ... and their summaries' packed arg-maxes
+  };
+  std::vector<Step> steps_;
 
   static std::string num(int x) { return std::to_string(x); }
   // Compiler fence: LDS reads (table entries, likelihoods) may not be hoisted above it.  Without
@@ -399,7 +504,7 @@ class Emitter {
 
   // member -> family message v{p}f{F}_g = local * prod of the other families' messages
   std::string var2fac(int p, int F) {
-    const std::string n = "v" + num(p) + "f" + num(F);
+    const std::string n = (mx_ ? "xv" : "v") + num(p) + "f" + num(F);
     if (g_.is_cut(p)) {  // a conditioned member: every family sees its assigned genotype, nothing flows through
       if (once(n))
         for (int g = 0; g < 3; ++g)
@@ -409,7 +514,7 @@ class Emitter {
     if (once(n)) {
       std::vector<std::string> in = {loc(p)};
       for (int F2 : g_.nb[p])
-        if (F2 != F) in.push_back(fac2var(F2, p));
+        if (F2 != F) in.push_back(mx_ ? max_fac2var(F2, p) : fac2var(F2, p));
       for (int g = 0; g < 3; ++g) {
         o_ << "      const double " << n << "_" << g << " = ";
         for (size_t k = 0; k < in.size(); ++k) o_ << (k ? " * " : "") << in[k] << "_" << g;
@@ -476,6 +581,74 @@ class Emitter {
       o_ << ";\n";
     }
     fence(1);
+    return n;
+  }
+
+  // max pass: one maximum over e[0..n) with its arg-max (first of equals) -> `v` (declared here), `b` |= arg << shift
+  void arg_max(const std::string &v, const std::vector<std::string> &e, const std::string &b, int shift) {
+    o_ << "      double " << v << " = " << e[0] << ";\n      { unsigned k_ = 0;";
+    for (size_t i = 1; i < e.size(); ++i)
+      o_ << " { const double e_ = " << e[i] << "; if (e_ > " << v << ") { " << v << " = e_; k_ = " << i << "; } }\n       ";
+    o_ << " " << b << " |= k_ << " << shift << "; }\n";
+  }
+
+  // max pass child summary xa<id>_{gm}{gf} = max_gc T_c[gc|gm,gf] * xv{c}f{F}_gc, the nine arg-maxes in xa<id>b
+  std::string max_child_sum(int F, int c) {
+    const std::string x = var2fac(c, F);
+    const std::string n = "xa" + num(uid_++);
+    o_ << "      unsigned " << n << "b = 0;\n";
+    for (int gm = 0; gm < 3; ++gm)
+      for (int gf = 0; gf < 3; ++gf) {
+        std::vector<std::string> e;
+        for (int gc = 0; gc < 3; ++gc) e.push_back(T(c, gc, gm, gf) + " * " + x + "_" + num(gc));
+        arg_max(n + "_" + num(gm) + num(gf), e, n + "b", 2 * (3 * gm + gf));
+      }
+    fence(2);
+    return n;
+  }
+
+  // max pass family -> member message xf{F}v{t}_g with its arg-maxes in xf{F}v{t}b; notes the back-track's step
+  std::string max_fac2var(int F, int t) {
+    const std::string n = "xf" + num(F) + "v" + num(t);
+    if (!once(n)) return n;
+    const Family &fam = g_.fam[F];
+    Step st{F, t, n + "b", {}, {}};
+    std::vector<std::string> sums;
+    for (int c : fam.kids)
+      if (c != t) {
+        sums.push_back(max_child_sum(F, c));
+        st.kids.push_back(c);
+        st.kid_bp.push_back(sums.back() + "b");
+      }
+    const std::string xm = t == fam.mo ? "" : var2fac(fam.mo, F);
+    const std::string xf = t == fam.fa ? "" : var2fac(fam.fa, F);
+    const std::string C = n + "w";
+    for (int gm = 0; gm < 3; ++gm)
+      for (int gf = 0; gf < 3; ++gf) {
+        std::vector<std::string> terms;
+        if (!xm.empty()) terms.push_back(xm + "_" + num(gm));
+        if (!xf.empty()) terms.push_back(xf + "_" + num(gf));
+        for (const std::string &s : sums) terms.push_back(s + "_" + num(gm) + num(gf));
+        o_ << "      const double " << C << "_" << gm << gf << " = ";
+        if (terms.empty()) o_ << "1.0";
+        for (size_t k = 0; k < terms.size(); ++k) o_ << (k ? " * " : "") << terms[k];
+        o_ << ";\n";
+      }
+    o_ << "      unsigned " << n << "b = 0;\n";
+    for (int g = 0; g < 3; ++g) {
+      std::vector<std::string> e;
+      if (t == fam.mo) {
+        for (int gf = 0; gf < 3; ++gf) e.push_back(C + "_" + num(g) + num(gf));
+      } else if (t == fam.fa) {
+        for (int gm = 0; gm < 3; ++gm) e.push_back(C + "_" + num(gm) + num(g));
+      } else {
+        for (int gm = 0; gm < 3; ++gm)
+          for (int gf = 0; gf < 3; ++gf) e.push_back(T(t, g, gm, gf) + " * " + C + "_" + num(gm) + num(gf));
+      }
+      arg_max(n + "_" + num(g), e, n + "b", (e.size() == 9 ? 4 : 2) * g);
+    }
+    fence(1);
+    steps_.push_back(st);
     return n;
   }
 
@@ -1269,6 +1442,95 @@ std::string trio_shell(const Model &m, const std::string &comment, const std::st
   return s.str();
 }
 
+// The MAP kernel's shell: trio_shell's form.  Outputs per site: map_gt[N] (int8), map_post (fp64), status; any may be null.  A
+// lane's genotype row is N bytes at a stride of N bytes, which no lane can store in aligned words on its own: the rows of a
+// workgroup's BT consecutive sites are staged in LDS (BT * N bytes) and written out together, a wave's stores contiguous —
+// in 32-bit words where the block's first byte is 4-aligned, in bytes otherwise.
+std::string map_shell(const Model &m, const std::string &comment, const std::string &body, int bt, bool fence_single, bool chrx_loop,
+                      bool lean) {
+  const int N = m.n_members, W3 = 3 * N, nw = (N + 3) / 4;
+  std::ostringstream s;
+  s << "// generated by famseq_amd/csrc for a " << N << "-member pedigree: " << comment << "\n"
+    << "#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n#pragma clang fp contract(off)\n"
+    << "#define W3 " << W3 << "\n#define BT " << bt << "\n#define NMEM " << N << "\n"
+    << "#define LDS_BARRIER() asm volatile(\"s_waitcnt lgkmcnt(0)\\n\\ts_barrier\" ::: \"memory\")\n"
+    << kDiv3Text;
+  if (lean)
+    for (int p = 0; p < N; ++p)
+      for (int gt = 0; gt < 3; ++gt) s << "#define l" << p << "_" << gt << " lgv[" << 3 * p + gt << "]\n";
+  s << "extern \"C\" __global__ __launch_bounds__(BT, 1) void famseq_map(const double *__restrict__ lk_g,\n"
+    << "    const unsigned char *__restrict__ flags_g, signed char *__restrict__ gt_g, double *__restrict__ post_g,\n"
+    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc) {\n"
+    << "  __shared__ double s_tc[432];\n"
+    << "  __shared__ unsigned s_gt[(BT * NMEM + 3) / 4];  // the workgroup's genotype rows, as they lie in map_gt\n"
+    << "  unsigned char *const s_gb = (unsigned char *)s_gt;\n"
+    << "  const int tid = threadIdx.x;\n"
+    << "  for (int i = tid; i < 432; i += BT) s_tc[i] = tc_g[i];\n"
+    << "  LDS_BARRIER();\n"
+    << "  const long chunks = (n_sites + BT - 1) / BT;\n"
+    << "  const long q_wg = chunks / gridDim.x, r_wg = chunks - q_wg * gridDim.x;\n"
+    << "  const long c_lo = (long)blockIdx.x * q_wg + (blockIdx.x < r_wg ? blockIdx.x : r_wg), c_hi = c_lo + q_wg + (blockIdx.x < r_wg ? 1 : 0);\n"
+    << "  const double kNaN = __builtin_nan(\"\");\n"
+    << "  (void)lc;\n"
+    << "  for (long ch = c_lo; ch < c_hi; ++ch) {\n"
+    // a lane beyond the batch's end works on the last site: the same values to the same addresses as that site's own lane
+    << "    const long site = ch * BT + tid < n_sites ? ch * BT + tid : n_sites - 1;\n"
+    << "    const double *lg = lk_g + site * W3;\n"
+    << "    const int fl = flags_g ? (flags_g[site] & 3) : 0;\n"
+    << "    const bool xchr_ = (fl & 2) != 0;\n"
+    << "    const double *tcf = s_tc + fl * 108;\n"
+    << "    bool single_fail = false, full = false, bn_fail = false;\n"
+    << "    (void)full;\n"
+    << "    double map_p = kNaN;\n    unsigned";
+  for (int k = 0; k < nw; ++k) s << (k ? ", " : " ") << "gw" << k << " = 0xffffffffu";
+  s << ";\n";
+  if (lean)
+    s << "    typedef const volatile __attribute__((address_space(1))) double glb_cvd;\n    glb_cvd *lgv = (glb_cvd *)lg;\n";
+  else
+    for (int p = 0; p < N; ++p)
+      for (int gt = 0; gt < 3; ++gt) s << "    const double l" << p << "_" << gt << " = lg[" << 3 * p + gt << "];\n";
+  // the single-posterior failure rule only (a lk * prior row sum <= 0): nothing of the single posterior is stored
+  s << single_posterior_statements(m, true, false, fence_single);
+  if (chrx_loop)
+    s << "    {\n"
+      << "#pragma unroll 1\n"
+      << "      for (int x_ = 0; x_ < 2; ++x_) {\n"
+      << "        const bool mine_ = !single_fail && xchr_ == (x_ == 1);\n"
+      << "        if (__builtin_amdgcn_ballot_w64(mine_) == 0) continue;\n"
+      << "        const double *tcx = tc_g + x_ * 216;\n"
+      << "        if (mine_) {\n";
+  else
+    s << "    if (!single_fail) {\n";
+  s << body
+    << "      if (Z_ <= 0 || W_ <= 0) bn_fail = true;\n"
+    << "      else map_p = W_ / Z_;\n"
+    << (chrx_loop ? "        }\n      }\n    }\n" : "    }\n")
+    << "    if (single_fail || bn_fail) {\n      map_p = kNaN;\n     ";
+  for (int k = 0; k < nw; ++k) s << " gw" << k << " = 0xffffffffu;";
+  s << "\n    }\n"
+    << "    if (post_g) __builtin_nontemporal_store(map_p, post_g + site);\n"
+    << "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n"
+    << "    if (gt_g) {\n";
+  if (N % 4 == 0)
+    for (int k = 0; k < nw; ++k) s << "      s_gt[tid * " << nw << " + " << k << "] = gw" << k << ";\n";
+  else
+    for (int p = 0; p < N; ++p) s << "      s_gb[tid * NMEM + " << p << "] = (unsigned char)(gw" << p / 4 << " >> " << 8 * (p % 4) << ");\n";
+  s << "      LDS_BARRIER();\n"
+    << "      const long left = n_sites - ch * BT;\n"
+    << "      const int nb = (int)(left < BT ? left : BT) * NMEM;  // bytes of this block's rows that lie inside the batch\n"
+    << "      signed char *dst = gt_g + ch * BT * NMEM;\n"
+    << "      int done = 0;\n"
+    << "      if (((unsigned long)dst & 3) == 0) {\n"
+    << "        done = nb & ~3;\n"
+    << "        for (int i = tid; i < (nb >> 2); i += BT) __builtin_nontemporal_store(s_gt[i], (unsigned *)dst + i);\n"
+    << "      }\n"
+    << "      for (int i = done + tid; i < nb; i += BT) dst[i] = (signed char)s_gb[i];\n"
+    << "      LDS_BARRIER();\n"
+    << "    }\n"
+    << "  }\n}\n";
+  return s.str();
+}
+
 }  // namespace
 
 std::vector<int> trio_children(const Model &m) {
@@ -1304,6 +1566,20 @@ std::string trio_source(const Model &m, int variant, int form) {
                            std::to_string(f);
   return trio_shell(m, what, Emitter(m, g, f < 2 ? f : 2, /*scalar_t=*/f >= 1, "pg", lean).trio_body(kids, mask, want_joint),
                     (int)kids.size(), want_dnm, want_joint, elim_block_threads(m, false), f >= 3, /*chrx_loop=*/f >= 1, lean);
+}
+
+std::string map_source(const Model &m, int variant) {
+  Graph g;
+  std::string why;
+  if (!build_graph(m, g, &why)) throw std::runtime_error("elimination engine: " + why);
+  if (variant < 0 || variant >= kMapVariants) throw std::runtime_error("map_source: variant must be 0.." + std::to_string(kMapVariants - 1));
+  const int f = variant;
+  const bool lean = m.n_members >= 40;  // as trio_source
+  const std::string what = "joint MAP configuration (max-product) over " + std::to_string(g.fam.size()) + " nuclear families" +
+                           (g.cut.empty() ? "" : ", conditioned on " + std::to_string(g.cut.size()) + " member(s)") + ", variant " +
+                           std::to_string(f);
+  return map_shell(m, what, Emitter(m, g, f < 2 ? f : 2, /*scalar_t=*/f >= 1, "pg", lean).map_body(), elim_block_threads(m, false),
+                   f >= 3, /*chrx_loop=*/f >= 1, lean);
 }
 
 std::string elim_source(const Model &m, int variant, bool call_mode) {

@@ -42,6 +42,14 @@ std::vector<int> trio_children(const Model &m);
 constexpr int kTrioVariants = 4;
 std::string trio_source(const Model &m, int variant, int form);
 
+// The joint MAP configuration (famseq_map_batch).  HIP source of
+// `extern "C" __global__ famseq_map(lk, flags, map_gt, map_post, status, n_sites, tc, lc)`: per site the most probable joint
+// genotype assignment of the whole pedigree, map_gt[N] (int8, PED order), and its posterior probability map_post = w(g*) / sum_g
+// w(g); the same graph as famseq_elim under the (max, x) semiring with back-pointers, Z from the sum pass.  variant 0..3: the
+// fence levels of famseq_elim's.  Throws if the engine does not serve the pedigree.
+constexpr int kMapVariants = 4;
+std::string map_source(const Model &m, int variant);
+
 // Shared shell of the generated kernels (see elim_codegen.cpp).
 extern const std::string kCallHelpers;  // fused call path: fs_phred, STAGE_IN_PL, STAGE_OUT_CALL, STAGE_FGT
 extern const char kCallArgs[];     // ... and the kernel arguments that go with them

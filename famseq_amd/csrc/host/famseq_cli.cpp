@@ -3,7 +3,7 @@
 // Keeps the reference's CLI and file surface for the `-method 1` path:
 //   FamSeq vcf -vcfFile f -pedFile p -output o [-v] [-a] [-d] [-o] [-l loc] [-method 1]
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
-//              [-genoProbXK a c] [-LRC x] [-dnm]
+//              [-genoProbXK a c] [-LRC x] [-dnm] [-map]
 //   FamSeq LK  -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -17,7 +17,8 @@
 // Differences by design: ONE pass over the input (the reference reads the file twice), sites are
 // queued and evaluated in batches on the GPU (famseq_bn_batch) with the output order preserved,
 // -method 2 is the exact sum-product engine (the marginals of the reference's Elston-Stewart peeling), -method 3 (MCMC) is
-// not part of this build, and -dnm (vcf mode) adds each child's de novo mutation posterior (DNP) from the trio kernel.
+// not part of this build, -dnm (vcf mode) adds each child's de novo mutation posterior (DNP) from the trio kernel, and -map (vcf
+// mode) each member's genotype in the most probable joint configuration of the family and that configuration's posterior (JGT, JP).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -187,6 +188,7 @@ struct Options {
   vector<double> gN, gK, gXN, gXK;
   int num_burn = -999, num_rep = -999;
   bool dnm = false;  // -dnm: a DNP field per sample (vcf mode)
+  bool map = false;  // -map: JGT and JP fields per sample (vcf mode)
 };
 
 // returns 0 good, 1 warnings, -1 stop (checkInput.h:345-349)
@@ -316,6 +318,8 @@ int parse_options(int argc, char **argv, Options &o) {
       }
     } else if (opt == "dnm") {
       o.dnm = true;
+    } else if (opt == "map") {
+      o.map = true;
     } else if (opt == "LRC") {
       i++;
       if (missing(i)) {
@@ -666,6 +670,20 @@ bool dnm_supported(const Options &o, const Ped &ped) {
   famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
   const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;
   if (k < 0) std::cout << "-dnm cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
+  famseq_destroy(probe);
+  return k >= 0;
+}
+
+// -map: the same question for the MAP kernel (another form of the same engine), answered by generating its source's graph: a
+// plan-only context refuses "map_kernels" with the engine's message before anything is compiled.
+bool map_supported(const Options &o, const Ped &ped) {
+  CliModel m;
+  vector<uint8_t> all(ped.n(), 1);
+  if (m.init(ped, all, o.mrate, o.lrc) != 0) return true;  // (the driver reports a bad pedigree itself)
+  char err[512] = {0};
+  famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
+  const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;  // (elim_supported: what load_map asks first)
+  if (k < 0) std::cout << "-map cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
   famseq_destroy(probe);
   return k >= 0;
 }
@@ -1222,6 +1240,11 @@ bool run_vcf(const Options &o, const Ped &ped) {
     if (o.dnm)
       fout << "##FORMAT=<ID=DNP,Number=1,Type=Float,Description=\"Posterior probability of a de novo mutation (genotype "
               "Mendelian-inconsistent with the parents')\">" << std::endl;
+    if (o.map) {
+      fout << "##FORMAT=<ID=JGT,Number=1,Type=String,Description=\"Genotype in the most probable joint genotype configuration of "
+              "the whole family\">" << std::endl;
+      fout << "##FORMAT=<ID=JP,Number=1,Type=Float,Description=\"Posterior probability of that joint configuration\">" << std::endl;
+    }
   };
   auto fs_info = [&] {
     fout << "##FS mutation rate=" << o.mrate << " " << std::endl;
@@ -1492,6 +1515,9 @@ bool run_vcf(const Options &o, const Ped &ped) {
     vector<TextBuf> text;
     vector<double> dnm;      // -dnm: [site][child] de novo posteriors ...
     vector<uint8_t> tstatus;  // ... and the trio kernel's status per site
+    vector<int8_t> jgt;       // -map: [site][member] the MAP configuration ...
+    vector<double> jp;        // ... its posterior ...
+    vector<uint8_t> jstatus;  // ... and the MAP kernel's status per site
   } slots[4];  // one being cut and parsed, one at the GPU, one being formatted, one being written
   bool ok = true;
   for (Slot &sl : slots) sl.parts.resize(n_threads), sl.text.resize(n_threads);
@@ -1544,6 +1570,15 @@ bool run_vcf(const Options &o, const Ped &ped) {
             flush_ok = false;
           }
         }
+        if (o.map && flush_ok) {  // and through the MAP kernel (full network as well)
+          sl.jgt.resize(sl.n_sites * size_t(ped.n())), sl.jp.resize(sl.n_sites), sl.jstatus.resize(sl.n_sites);
+          const int rm = famseq_map_batch(ctx, (int64_t)sl.n_sites, sl.packed ? nullptr : sl.lk.data(), sl.packed ? sl.io.pl : nullptr,
+                                          seq_members.data(), (int32_t)n_seq, sl.io.flags, sl.jgt.data(), sl.jp.data(), sl.jstatus.data());
+          if (rm != 0) {
+            std::cerr << "famseq_map_batch failed (" << rm << "): " << famseq_last_error(ctx) << std::endl;
+            flush_ok = false;
+          }
+        }
       }
       t_gpu += now_s() - t0;
       to_formatter.put(i);
@@ -1559,6 +1594,19 @@ bool run_vcf(const Options &o, const Ped &ped) {
     else if (kid < 0) out.ch('.');
     else if (sl.tstatus[s] != 0) out.put("NA", 2);
     else out.num(sl.dnm[s * size_t(n_kids) + size_t(kid)]);
+    out.ch('\t');
+  };
+  // -map: ":<JGT>:<JP>" before the closing tab of sample j's field — NA:NA where the site or its MAP failed
+  auto put_map = [&](TextBuf &out, const Slot &sl, size_t s, size_t j, bool failed) {
+    --out.n;
+    out.ch(':');
+    if (failed || sl.jstatus[s] != 0) {
+      out.put("NA:NA", 5);
+    } else {
+      const int gt = sl.jgt[s * size_t(ped.n()) + size_t(seq_members[j])];
+      out.put(gt == 0 ? "0/0:" : (gt == 1 ? "0/1:" : "1/1:"), 4);
+      out.num(sl.jp[s]);
+    }
     out.ch('\t');
   };
   // ... the results are turned into text on their own thread (and its helpers) while the next block is at the GPU ...
@@ -1581,14 +1629,17 @@ bool run_vcf(const Options &o, const Ped &ped) {
               const size_t s = size_t(it.site);
               const Record::Sample *sm = &pt.samples[it.smp];
               out.put(it.raw, it.prefix_len);  // columns 1-8 + FORMAT
-              if (o.dnm) out.put(":GPP:FPP:FGT:DNP\t", 17);
-              else out.put(":GPP:FPP:FGT\t", 13);
+              out.put(":GPP:FPP:FGT", 12);
+              if (o.dnm) out.put(":DNP", 4);
+              if (o.map) out.put(":JGT:JP", 7);
+              out.ch('\t');
               if (sl.io.status[s] & 3) {  // file.cpp:607-620
                 pt.any_failed = true;
                 for (size_t j = 0; j < k; ++j) {
                   out.put(it.raw + sm[j].off, sm[j].len);
                   out.put(":NA:NA:NA\t", 10);
                   if (o.dnm) put_dnp(out, sl, s, j, true);
+                  if (o.map) put_map(out, sl, s, j, true);
                 }
               } else {
                 for (size_t j = 0; j < k; ++j) {
@@ -1606,6 +1657,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
                     out.put(gt == 0 ? "0/0\t" : (gt == 1 ? "0/1\t" : "1/1\t"), 4);
                   }
                   if (o.dnm) put_dnp(out, sl, s, j, false);
+                  if (o.map) put_map(out, sl, s, j, false);
                 }
               }
             }
@@ -1920,6 +1972,8 @@ void help() {
             << "-genoProbXK\tPr(G) for chromosome X of males, in dbSNP. Default 0.5 0.5." << std::endl
             << "-LRC\t\tLikelihood ratio criterion for the single-sample shortcut. Default 1." << std::endl
             << "-dnm\t\t(vcf) Add DNP, each child's posterior probability of a de novo mutation, to every sample column." << std::endl
+            << "-map\t\t(vcf) Add JGT and JP, each member's genotype in the most probable joint configuration of the family and" << std::endl
+            << "\t\tthat configuration's posterior probability, to every sample column." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl
@@ -1975,6 +2029,8 @@ int main(int argc, char **argv) {
   }
   if (o.dnm && mode != "vcf") std::cout << "-dnm applies to vcf mode only; ignored here." << std::endl;
   if (o.dnm && mode == "vcf" && !dnm_supported(o, ped)) return 255;
+  if (o.map && mode != "vcf") std::cout << "-map applies to vcf mode only; ignored here." << std::endl;
+  if (o.map && mode == "vcf" && !map_supported(o, ped)) return 255;
   const double t0 = now_s();
   if (o.tune_mode) return run_tune(o, ped) ? 0 : -1;
   const bool ok = o.pl_mode ? run_pl(o, ped) : (o.lk_mode ? run_lk(o, ped) : run_vcf(o, ped));

@@ -285,6 +285,36 @@ int famseq_trio_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_l
                              const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_joint, double *d_dnm,
                              uint8_t *d_status, void *stream);
 
+/* ---- the joint MAP genotype configuration ---------------------------------------------------------------
+ * FGT is each member's own most probable genotype; member by member those need not form a configuration that has any
+ * probability at all (at mutation rate 0 they can be Mendelian-inconsistent).  This is the other answer: the single most probable
+ * genotype assignment of the whole pedigree and its posterior probability, by max-product message passing (with back-pointers)
+ * on the sum-product engine's graph.  Exact, O(27 N) per site, for every pedigree that engine serves: loop-free ones of any size,
+ * loops up to three conditioned members; any other gets FAMSEQ_E_ARG with the engine's message.  With w(g) = 1e7 * prod_m
+ * f_m(g_m | g_mother, g_father), the weight the 3^N enumeration gives a configuration (priors by the Known flag, chrX tables and
+ * male priors by the chrX flag):
+ *   map_gt  [n_sites][N] int8   g* = argmax_g w(g): 0 / 1 / 2 per member, PED order
+ *   map_post[n_sites]    fp64   w(g*) / sum_g w(g)
+ *   status  [n_sites]           0 OK; 1 the single-posterior failure rule of famseq_bn_batch; 2 the total or the maximum weight
+ *              is <= 0.  There is no -LRC shortcut.  Wherever status != 0, map_gt is -1 and map_post NaN.
+ * Ties: every arg-max of the kernel scans genotypes in the order 0, 1, 2 (parent pairs in the order 3 gm + gf; conditioned
+ * members' assignments in loop order) and replaces on strictly greater only, so the result is a function of the input.  Two
+ * configurations whose weights differ only by rounding may compare differently under another order of multiplication (an
+ * enumeration's): what is guaranteed against such a reference is the weight of the returned configuration, not its identity.
+ * The kernel is compiled on the first MAP call, or ahead through famseq_set_option "map_kernels" = 1 (a plan-only context
+ * generates and cross-compiles it).  famseq_plan_json: "map_code_object", "map_variant". */
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_trio_batch (exactly one of lk / pl16).  Any of map_gt /
+ * map_post / status may be NULL. */
+int famseq_map_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                     int32_t n_seq, const uint8_t *flags, int8_t *map_gt, double *map_post, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
+ * NULL = the default stream) and returns without synchronising. */
+int famseq_map_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                            const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, int8_t *d_map_gt,
+                            double *d_map_post, uint8_t *d_status, void *stream);
+
 /* Diagnostic / test aid: the device formatter alone.  values[n] (host) -> out[n][16] (host): the characters of each
  * value as the text kernel prints a GPP / FPP number from byte 0, their count in byte 15; "nan" for anything outside
  * the formatter's domain, 0 and [1e-16, 999999.5). */
