@@ -1,0 +1,209 @@
+// ctx.h — what the host translation units of libfamseq_hip.so share: the context behind the C ABI, the record of a
+// generated kernel and the device buffers a context owns.  capi.cpp is the extern "C" surface and its argument checks,
+// kernels.cpp loads, launches and tunes the generated kernels, pipeline.cpp moves host batches through the device.
+#ifndef FAMSEQ_CTX_H_
+#define FAMSEQ_CTX_H_
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "bn_kernel.h"
+#include "enum_codegen.h"
+#include "famseq_hip.h"
+#include "jit.h"
+#include "plan.h"
+
+// The fused call path's side of a generated kernel's argument list (kCallArgs): packed PLs in, GPP / FPP /
+// FGT out.  All null on the plain path.
+struct CallIO {  // = struct fs_call_args of the generated source (elim_codegen.cpp kCallHelpers)
+  const uint16_t *pl = nullptr;
+  const double *lut = nullptr;
+  const int32_t *col = nullptr, *slot = nullptr;
+  double *gpp = nullptr, *fpp = nullptr;
+  int8_t *fgt = nullptr;
+  int32_t n_seq = 0;
+  uint32_t magic_w = 0, magic_n = 0;
+  unsigned long long *phase_clk = nullptr;  // FAMSEQ_PHASE_CLOCK (measuring aid): cycles per phase of the call-path kernel, summed over waves
+};
+constexpr int kPhases = 8;
+
+namespace famseq {
+
+// Device memory with an owner: freed when the owner goes, or when it is asked for again at another size.
+struct DevBuf {
+  void *p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  }
+  hipError_t alloc(size_t bytes) {
+    release();
+    return hipMalloc(&p, bytes);
+  }
+  template <class T>
+  T *as() const { return static_cast<T *>(p); }
+  explicit operator bool() const { return p != nullptr; }
+};
+
+// A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp.
+enum KernelKind {
+  K_LANE = 0,  // K_LANE + d: the enumeration with 3^d lanes per site; d = 0 (one lane per site) serves large batches,
+               // d = 1..kEnumMaxGroupDigits batches too small to give every lane of the chip a site (compiled on first use of each d)
+  K_LANE_CALL = K_LANE + kEnumMaxGroupDigits + 1,  // the fused call-path form of the one-lane-per-site kernel (famseq_bn_call_batch)
+  K_ELIM,                                          // sum-product kernel (engine = FAMSEQ_ENGINE_ELIM)
+  K_ELIM_CALL,                                     // ... and its call-path form
+  K_TRIO,                                          // K_TRIO + form - 1: trio posteriors per output form (1 dnm, 2 joint, 3 both)
+  K_MAP = K_TRIO + 3,                              // the joint MAP configuration
+  K_COUNT
+};
+
+struct GenKernel {
+  JitKernel k;  // on a plan-only context (device < 0) only the path of the compiled code object
+  int block_threads = 0, blocks_per_cu = 0;
+  int variant = -1;  // which generator variant the tuner's note or jit_pick_variant took
+  // the lane kinds and the call-path forms remember that they could not be built (no compiler at run time, ...) and say
+  // so once; each keeps its own verdict: a call-path form that does not build must not take the plain kernels down with
+  // it, nor the other way round.  (The lanes-per-site kinds leave their message with K_LANE, which keeps its own in preference.)
+  bool failed = false;
+  std::string error;
+  void drop() {  // unloaded and forgotten: the next use generates it again
+    jit_unload(k);
+    k.path.clear();
+    variant = -1;
+  }
+};
+
+constexpr int kSlots = 2;
+constexpr int kStages = 3;
+
+// The device side of the chunked host pipeline: kSlots copies of every array a chunk passes through.  A set only grows
+// (in sites and in bytes per site), so that varying batch sizes do not thrash.
+enum SlotBuf { B_LK, B_FLAGS, B_STATUS, B_PL, B_POST, B_SINGLE, B_GPP, B_FPP, B_FGT, B_TEXT, B_COUNT,
+               B_OUT_A = B_POST, B_OUT_B = B_SINGLE };  // (the trio and MAP entries' two outputs)
+struct SlotSet {
+  DevBuf buf[kSlots][B_COUNT];
+  size_t row[B_COUNT] = {};  // bytes per site of each buffer (0: not allocated)
+  int64_t sites = 0;
+  void release() {
+    for (auto &slot : buf)
+      for (DevBuf &b : slot) b.release();
+    sites = 0;
+  }
+};
+
+}  // namespace famseq
+
+struct famseq_ctx {
+  famseq::Model model;
+  bool big = false;  // more than FAMSEQ_MAX_MEMBERS members: no enumeration plan, sum-product engine only
+  famseq::PlanOptions opt{};
+  famseq::Plan plan{};
+  famseq::KParams kp{};
+  bool plan_dirty = true;
+  int device = -1;
+  int n_cus = 0;
+  int blocks_per_cu = 0;
+  int64_t grid_override = 0;
+  int64_t chunk_sites = 0;
+  int engine = FAMSEQ_ENGINE_ENUM;
+  famseq::GenKernel kern[famseq::K_COUNT];
+  famseq::GenKernel &lanes(int d) { return kern[famseq::K_LANE + d]; }
+  const famseq::GenKernel &trio(int form) const { return kern[famseq::K_TRIO + form - 1]; }
+  bool plan_only() const { return device < 0; }
+  // enumeration engine: the team-per-site kernel is compiled into the library; the lane kernels are generated per
+  // pedigree.  enum_impl: -1 auto (lane for large batches), 0 team, 1 lane.  group_digits: -1 auto (by batch size), 0..4 forced.
+  int enum_impl = -1;
+  int group_digits = -1, last_group_digits = 0;
+  int lane_reads_rows = -1;  // does the lane call-path kernel re-read fp64 rows from global memory (unknown until it is built)
+  int trio_last = 0;         // the trio output form asked for last (famseq_plan_json)
+  int64_t lane_min_sites = 256;  // below this the compiled-in team kernel answers at once (no per-pedigree compile for tiny calls) ...
+  // ... unless the generated kernel for that batch is loaded or on disk already (a pre-built pedigree, or one this user has run
+  // before): then nothing has to be waited for and it serves every batch size (team kernel: 0.0237 ms per 256 ten-member
+  // sites, three lanes ... 81 lanes per site: 0.0159).  -1 unknown, 0 would have to be compiled, 1 ready.
+  int grp_ready[famseq::kEnumMaxGroupDigits + 1] = {-1, -1, -1, -1, -1};
+  // device constants: plan image, factor tables, pow(10, -k/10); column -> member, member -> column or -1, member -> output slot
+  famseq::DevBuf d_img, d_tc, d_lut, d_seq, d_col, d_slot;
+  std::vector<int32_t> seq_members;
+  // the host-buffer entry points: a three-stage pipeline (copy in / compute / copy out, one stream each, so both
+  // directions of the host link run at once) over two buffer slots; the posterior and call entries, the trio and the
+  // MAP entries each have their set (their outputs differ in size by an order of magnitude)
+  hipStream_t stream[famseq::kStages] = {nullptr, nullptr, nullptr};  // 0 copy in, 1 compute, 2 copy out
+  hipEvent_t ev_in[famseq::kSlots] = {}, ev_done[famseq::kSlots] = {}, ev_out[famseq::kSlots] = {};
+  famseq::SlotSet slots, trio_slots, map_slots;
+  famseq::DevBuf d_call[famseq::kSlots];  // the generated kernels' call-path arguments (CallIO), one per slot
+  famseq::DevBuf d_phase;                 // FAMSEQ_PHASE_CLOCK: kPhases counters
+  // device-resident call path (famseq_bn_call_batch_device): its own argument block, what it holds, and scratch rows for
+  // batches the fused kernels do not serve (separate unpack / posterior / Phred stages)
+  famseq::DevBuf d_call_dev;
+  CallIO call_dev_host{};
+  bool call_dev_valid = false;
+  famseq::DevBuf dev_tmp[7];  // lk, post, single, gpp, fpp, fgt, status
+  int64_t dev_tmp_sites = 0;
+  int dev_tmp_seq = 0;
+  famseq::DevBuf trio_dev_lk;  // the trio and MAP device entries' likelihood rows for packed input
+  int64_t trio_dev_sites = 0;
+  std::string tune_report;  // what famseq_set_option "tune" measured (famseq_plan_json "tune")
+  std::string err, json;
+};
+
+namespace famseq {
+
+inline int fail(famseq_ctx *c, int code, const std::string &msg) {
+  c->err = msg;
+  return code;
+}
+
+#define HIP_TRY(c, call)                                                                              \
+  do {                                                                                                \
+    hipError_t e_ = (call);                                                                           \
+    if (e_ != hipSuccess)                                                                             \
+      return famseq::fail((c), FAMSEQ_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));      \
+  } while (0)
+
+// ---- kernels.cpp ----
+// The sum-product family (K_ELIM, K_TRIO + form - 1, K_MAP): 0, or an error (FAMSEQ_E_ARG: the engine does not serve this
+// pedigree; FAMSEQ_E_HIP) that is not remembered, the next call tries again.
+int load_or_fail(famseq_ctx *c, int kind);
+// The lane kinds and both call-path forms: false when the kernel is unavailable, which is remembered and said once on
+// stderr; the caller falls back (team kernel, separate stages).
+bool load_or_remember(famseq_ctx *c, int kind);
+void drop_lane_kernels(famseq_ctx *c);  // what a new pick of the lane variant makes stale
+hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,
+                            void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk = 0, const CallIO *d_call = nullptr);
+hipError_t launch_engine(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, double *d_post, double *d_single,
+                         uint8_t *d_status, hipStream_t stream);
+bool call_fuses(famseq_ctx *c, int64_t n_sites, bool packed_in);
+bool launch_engine_fused(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, uint8_t *d_status, bool packed_in,
+                         const CallIO *d_io, hipStream_t stream, hipError_t *err);
+int tune(famseq_ctx *c);
+void report_phase_clock(famseq_ctx *c);
+
+// ---- pipeline.cpp ----
+struct HostIO {
+  const double *lk = nullptr;      // exactly one of lk / pl16
+  const uint16_t *pl16 = nullptr;  // [n_sites][n_seq][3]
+  const uint8_t *flags = nullptr;
+  double *post = nullptr, *single = nullptr;  // raw outputs [n_sites][N][3]
+  uint8_t *status = nullptr;
+  double *gpp = nullptr, *fpp = nullptr;  // called outputs [n_sites][n_seq][3]
+  int8_t *fgt = nullptr;                  // [n_sites][n_seq]
+  char *text = nullptr;                   // the same three as printed: [n_sites][n_seq][FAMSEQ_TEXT_STRIDE]
+};
+int upload_lut(famseq_ctx *c);
+CallIO make_call_io(const famseq_ctx *c, const uint16_t *d_pl, double *d_gpp, double *d_fpp, int8_t *d_fgt, int32_t n_seq,
+                    unsigned long long *d_phase_clk = nullptr);
+int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq);
+// The trio and MAP host entries: lk or packed PLs through kernel `g`, whose two outputs have a_row / b_row bytes per site.
+int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
+               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status);
+
+}  // namespace famseq
+#endif

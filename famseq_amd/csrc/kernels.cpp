@@ -1,0 +1,409 @@
+// kernels.cpp — the generated (per-pedigree) kernels of a context: how each kind is made, the one loader, the launchers,
+// which kernel serves which batch, and the tuner.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <stdexcept>
+
+#include "bn_kernel.h"
+#include "ctx.h"
+#include "elim_codegen.h"
+
+namespace famseq {
+namespace {
+
+// How a kind of generated kernel is made.
+struct KernelSpec {
+  std::function<std::string(int)> source;  // variant -> HIP source
+  int n_variants, first;                   // the variant contest (jit_pick_variant) runs first .. n_variants - 1
+  bool honours_pick;                       // a note of the tuner's, keyed by the variant-0 source, names the variant instead
+  const char *entry;
+  int block_threads;
+};
+
+bool is_lane(int kind) { return kind >= K_LANE && kind <= K_LANE + kEnumMaxGroupDigits; }
+bool is_trio(int kind) { return kind >= K_TRIO && kind < K_TRIO + 3; }
+
+KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
+  const Model &m = c->model;
+  if (is_lane(kind)) {
+    const int d = kind - K_LANE;  // (the lanes-per-site forms always use the 6-member block: no measured pick to honour)
+    return {[&m, d](int v) { return enumgen_source(m, v, d); }, kEnumVariants, 0, d == 0, "famseq_enum_lane", enumgen_block_threads(m, d)};
+  }
+  if (is_trio(kind)) {
+    const int form = kind - K_TRIO + 1;
+    return {[&m, form](int v) { return trio_source(m, v, form); }, kTrioVariants, 0, false, "famseq_trio", elim_block_threads(m)};
+  }
+  switch (kind) {
+    case K_LANE_CALL: {
+      // the same block size as the plain lane kernel runs with (variants 0-1 / 2-3: kEnumVariants), so that a batch
+      // gives the same bits whether it goes through the fused kernel or through the separate stages
+      const int base = std::max(c->kern[K_LANE].variant, 0) & ~1;
+      // v & 1: the single posterior fenced member by member; v & 2: the leaner stage-out (see kElimCallVariants)
+      return {[&m, base](int v) { return enumgen_source(m, base + (v & 1), 0, true, !(v & 2)); }, 4, 0, false, "famseq_enum_lane",
+              enumgen_block_threads(m)};
+    }
+    case K_ELIM:
+      return {[&m](int v) { return elim_source(m, v); }, kElimVariants, elim_first_variant(m), true, "famseq_elim", elim_block_threads(m)};
+    case K_ELIM_CALL:
+      return {[&m](int v) { return elim_source(m, v, true); }, kElimCallVariants, elim_first_variant(m, true), false, "famseq_elim",
+              elim_block_threads(m, true)};
+    case K_MAP:
+      return {[&m](int v) { return map_source(m, v); }, kMapVariants, 0, false, "famseq_map", elim_block_threads(m)};
+  }
+  throw std::logic_error("kernel_spec: no such kind");
+}
+
+bool have(const famseq_ctx *c, const GenKernel &g) { return g.k.fn || (c->plan_only() && !g.k.path.empty()); }
+
+// Generate, compile (or fetch) and load one kernel: 0, or FAMSEQ_E_HIP with *why.  What a failure means is the caller's.
+int load_kernel(famseq_ctx *c, int kind, std::string *why) {
+  GenKernel &g = c->kern[kind];
+  if (have(c, g)) return 0;
+  try {
+    const KernelSpec s = kernel_spec(c, kind);
+    // a measured pick (the autotuner's note, or the table build() ships) is loaded as it is: the spill contest is
+    // the static rule for pedigrees nobody has measured, and must not move off a measurement
+    const int pick = s.honours_pick ? jit_read_pick(s.source(0)) : -1;
+    std::string src;
+    if (pick >= 0 && pick < s.n_variants) {
+      src = s.source(pick);
+      g.variant = pick;
+    } else {
+      src = jit_pick_variant(s.source, s.n_variants, &g.variant, s.first);
+    }
+    if (c->plan_only()) {  // generate and compile into the cache (this is how build() pre-builds)
+      g.k.path = jit_compile(src);
+      return 0;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
+    g.k = jit_load(src, s.entry);
+    g.block_threads = s.block_threads;
+  } catch (const std::exception &e) {
+    *why = e.what();
+    return FAMSEQ_E_HIP;
+  }
+  int nb = 0;
+  if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, g.k.fn, g.block_threads, 0) != hipSuccess) nb = 1;
+  g.blocks_per_cu = std::max(nb, 1);
+  return 0;
+}
+
+}  // namespace
+
+int load_or_fail(famseq_ctx *c, int kind) {
+  if (is_trio(kind)) c->trio_last = kind - K_TRIO + 1;
+  if (have(c, c->kern[kind])) return 0;
+  std::string why;
+  if (!elim_supported(c->model, &why))
+    return fail(c, FAMSEQ_E_ARG, (kind == K_ELIM ? "elimination engine: " : kind == K_MAP ? "joint MAP call (sum-product engine): "
+                                                                                           : "trio posteriors (sum-product engine): ") + why);
+  if (load_kernel(c, kind, &why) != 0) return fail(c, FAMSEQ_E_HIP, why);
+  return 0;
+}
+
+bool load_or_remember(famseq_ctx *c, int kind) {
+  GenKernel &g = c->kern[kind];
+  if (g.k.fn) return true;
+  if (g.failed) return false;
+  if (have(c, g)) return true;
+  std::string why;
+  if (kind == K_LANE_CALL && !load_or_remember(c, K_LANE)) {  // its block shape and fencing are the plain kernel's
+    why = "the plain lane kernel is unavailable: " + c->kern[K_LANE].error;
+  } else {
+    const int rc = load_kernel(c, kind, &why);
+    if (kind == K_LANE_CALL && g.variant >= 0)  // (the answer depends on the variant taken)
+      c->lane_reads_rows = enumgen_reads_global_rows(c->model, (std::max(c->kern[K_LANE].variant, 0) & ~1) + (g.variant & 1)) ? 1 : 0;
+    if (rc == 0) return true;
+  }
+  g.failed = true;
+  const bool quiet = std::getenv("FAMSEQ_QUIET") != nullptr;  // else said once per ctx and kernel, where a user of the CLI or of the
+                                                              // library sees it (also in famseq_plan_json)
+  if (is_lane(kind)) {
+    const int d = kind - K_LANE;
+    std::string &lane_error = c->kern[K_LANE].error;
+    if (d == 0 || lane_error.empty()) lane_error = why;
+    if (!quiet)
+      std::fprintf(stderr, "famseq: the per-pedigree enumeration kernel%s is unavailable (%s); %s\n", d ? " (lanes-per-site form)" : "",
+                   why.substr(0, 300).c_str(),
+                   d ? "such batches take the one-lane-per-site or the compiled-in kernel"
+                     : "large batches fall back to the compiled-in team-per-site kernel (about 4x slower)");
+  } else {
+    g.error = why;
+    if (!quiet)
+      std::fprintf(stderr, "famseq: the fused call-path form of the %s kernel is unavailable (%s); famseq_bn_call_batch runs the "
+                           "separate unpack / posterior / Phred stages instead (same results)\n",
+                   kind == K_ELIM_CALL ? "sum-product" : "enumeration", why.substr(0, 300).c_str());
+  }
+  return false;
+}
+
+// A pick (the tuner's note, "pick_lane" / "pick_elim") is read by two loaders only — K_LANE and K_ELIM, the kinds whose
+// kernel_spec honours it — and the lane call-path form takes its block shape from K_LANE's variant.  Those three are what
+// a new pick makes stale; the lanes-per-site, sum-product call-path, trio and MAP kernels run their own contests and
+// cannot be moved by one, so they stay loaded.
+void drop_lane_kernels(famseq_ctx *c) {
+  c->kern[K_LANE].drop();
+  c->kern[K_LANE_CALL].drop();
+  c->lane_reads_rows = -1;
+}
+
+namespace {
+
+// How many of the outermost looped members' digits go on lanes for a batch of n_sites.  Cost model
+// (measured on the 10-member benchmark pedigree, tools/small_batch_rates.py): a lane's work is its
+// share of the enumeration, 3^N / 3^d configurations, plus what every lane of a group repeats (single
+// posterior, tables of the fixed levels, its columns of the reduction: about 250 N configuration
+// times); lanes run at full speed while there is at most one wave per SIMD (n_cus * 256 lanes), beyond
+// that the time grows with the lane count.  More lanes per site pay while the batch leaves SIMDs idle.
+int pick_group_digits(const famseq_ctx *c, int64_t n_sites) {
+  const int dmax = enumgen_max_group_digits(c->model);
+  if (c->group_digits >= 0) return std::min(c->group_digits, dmax);
+  if (c->enum_impl == 1) return 0;  // an explicit choice of the lane-per-site kernel is exactly that kernel
+  const double full_speed_lanes = double(std::max(1, c->n_cus)) * 256.0;
+  const double configs = std::pow(3.0, c->model.n_members), per_lane = 250.0 * c->model.n_members;
+  int best = 0;
+  double best_t = 0;
+  for (int d = 0, g = 1; d <= dmax; ++d, g *= 3) {
+    const double t = std::max(1.0, double(n_sites) * g / full_speed_lanes) * (configs / g + (d ? per_lane : 0.0));
+    if (d == 0 || t < best_t * 0.9) {
+      best = d;
+      best_t = t;
+    }
+  }
+  return best;
+}
+
+// Can the generated kernel with 3^d lanes per site run without a compilation (loaded, or its code object on disk)?
+bool generated_ready(famseq_ctx *c, int d) {
+  if (c->lanes(d).k.fn) return true;
+  if (c->lanes(d).failed) return false;
+  if (c->grp_ready[d] < 0) {
+    try {
+      const int pick = d == 0 ? jit_read_pick(enumgen_source(c->model, 0, 0)) : -1;
+      // (the variant the loader would take first; a spilling first variant sends it on to others, which may need the compiler:
+      // then this says "not ready" and the tiny batch stays on the compiled-in kernel, which is always right)
+      c->grp_ready[d] = jit_cached(enumgen_source(c->model, pick >= 0 && pick < kEnumVariants ? pick : 0, d)) ? 1 : 0;
+    } catch (const std::exception &) {
+      c->grp_ready[d] = 0;
+    }
+  }
+  return c->grp_ready[d] == 1;
+}
+
+int grid_for(const famseq_ctx *c, int64_t n_sites) {
+  const int64_t passes = (n_sites + c->plan.teams_per_block - 1) / c->plan.teams_per_block;
+  int64_t resident = c->grid_override > 0 ? c->grid_override : int64_t(c->n_cus) * c->blocks_per_cu;
+  return (int)std::max<int64_t>(1, std::min(passes, resident));
+}
+
+}  // namespace
+
+// The generated kernels share one argument list; what the third and fourth are depends on the kind (posterior and single
+// posterior rows, joint and de novo posteriors, MAP genotypes and their posterior), so they pass through untyped.
+hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,
+                            void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk, const CallIO *d_call) {
+  const int spc = sites_per_chunk > 0 ? sites_per_chunk : g.block_threads;
+  const int64_t chunks = (n_sites + spc - 1) / spc;
+  int64_t resident = c->grid_override > 0 ? c->grid_override : int64_t(c->n_cus) * g.blocks_per_cu;
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min(chunks, resident));
+  long ns = (long)n_sites;
+  double lc = c->model.lc;
+  const double *tc = c->d_tc.as<double>();
+  void *args[] = {&d_lk, &d_flags, &d_out_a, &d_out_b, &d_status, &ns, &tc, &lc, &d_call};  // the plain forms take the first eight
+  return hipModuleLaunchKernel(g.k.fn, grid, 1, 1, (unsigned)g.block_threads, 1, 1, 0, stream, args, nullptr);
+}
+
+hipError_t launch_engine(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, double *d_post, double *d_single,
+                         uint8_t *d_status, hipStream_t stream) {
+  if (c->engine == FAMSEQ_ENGINE_ELIM)
+    return launch_generated(c, c->kern[K_ELIM], n_sites, d_lk, d_flags, d_post, d_single, d_status, stream);
+  const bool want_lane = c->enum_impl == 1 || (c->enum_impl < 0 && (n_sites >= c->lane_min_sites ||
+                                                                    generated_ready(c, pick_group_digits(c, n_sites))));
+  if (want_lane) {
+    int d = pick_group_digits(c, n_sites);
+    if (d > 0 && !load_or_remember(c, K_LANE + d)) d = 0;  // that group size does not build: one lane per site before the compiled-in kernel
+    if (load_or_remember(c, K_LANE + d)) {
+      c->last_group_digits = d;
+      return launch_generated(c, c->lanes(d), n_sites, d_lk, d_flags, d_post, d_single, d_status, stream,
+                              d > 0 ? enumgen_sites_per_chunk(c->model, d) : 0);
+    }
+  }
+  return launch_bn_enum(c->plan, c->kp, grid_for(c, n_sites), c->d_img.as<uint32_t>(), c->d_tc.as<double>(), n_sites, d_lk, d_flags, d_post,
+                        d_single, d_status, stream);
+}
+
+// The fused call path: one launch does PL -> likelihood, posterior, Phred scaling and the genotype call
+// (famseq_bn_call_batch).  Served by the call-path forms of the generated kernels (one lane per site).
+// Does this batch go through one (loading it on first use), or through the separate stages instead (team kernel,
+// lanes-per-site mode, or a lane kernel that re-reads fp64 rows from global memory while the input is packed)?
+// The one place that decides.
+bool call_fuses(famseq_ctx *c, int64_t n_sites, bool packed_in) {
+  const bool elim = c->engine == FAMSEQ_ENGINE_ELIM;
+  if (c->big) return false;  // no call-path form of the wide-pedigree kernel: separate stages
+  if (!elim) {
+    const bool want_lane = c->enum_impl == 1 || (c->enum_impl < 0 && n_sites >= c->lane_min_sites);
+    if (!want_lane || pick_group_digits(c, n_sites) != 0) return false;
+  }
+  if (!load_or_remember(c, elim ? K_ELIM_CALL : K_LANE_CALL)) return false;
+  if (!elim && packed_in && c->lane_reads_rows != 0) return false;  // (set with the lane call-path kernel, for the variant it took)
+  return true;
+}
+
+bool launch_engine_fused(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, uint8_t *d_status, bool packed_in,
+                         const CallIO *d_io, hipStream_t stream, hipError_t *err) {
+  const bool elim = c->engine == FAMSEQ_ENGINE_ELIM;
+  if (!call_fuses(c, n_sites, packed_in)) return false;
+  if (!elim) c->last_group_digits = 0;
+  *err = launch_generated(c, c->kern[elim ? K_ELIM_CALL : K_LANE_CALL], n_sites, d_lk, d_flags, nullptr, nullptr, d_status, stream, 0, d_io);
+  return true;
+}
+
+// famseq_set_option(ctx, "tune", 1): where static rules pick a generated kernel's variant (the sum-product kernel's
+// fence variant by pedigree size, the enumeration kernel's 7- or 6-member block), time the candidates on THIS device
+// and pedigree — synthetic rows, a few milliseconds each — and leave the winner's index as a note in the kernel
+// cache; every later context for the pedigree starts from it.  Opt-in: it compiles every candidate.
+int tune(famseq_ctx *c) {
+  if (c->device < 0) return fail(c, FAMSEQ_E_NODEVICE, "tuning times kernels: it needs a device");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const Model &mdl = c->model;
+  const int N = mdl.n_members;
+  // about 10 ms of enumeration per launch, 64 K - 2 M sites; the sum-product kernel, whose time does not grow with
+  // 3^N, always gets 8 M (at 64 K sites its launch is most of what a timer sees)
+  // ... in whole ROUNDS of the chip: a candidate at one wave per SIMD takes 64 K sites at a time, one at two waves 128 K;
+  // a batch of 2.3 rounds times the tail, not the kernel (a thirteen-member pedigree's two blocks came out 25 % apart that
+  // way).  Up to eight rounds while a launch stays under a quarter of a second.
+  const double configs = std::pow(3.0, N), t_round = 65536.0 * configs / 2.4e13;
+  int64_t rounds = std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)(0.25 / t_round)));
+  if (rounds > 1) rounds &= ~int64_t(1);
+  const int64_t by_time = (int64_t)(0.01 * 2.4e13 / configs) / 131072 * 131072;
+  const int64_t n_enum = std::min<int64_t>(int64_t(1) << 21, std::max<int64_t>(by_time, 65536 * rounds));
+  const int64_t n_elim = int64_t(1) << 23, n_max = std::max(n_enum, n_elim);  // 8 M: it has to stream from HBM (2 M sites half fit the Infinity Cache)
+  int64_t n = n_enum;  // sites of the launches being timed
+  const size_t w = size_t(n_max) * 3 * N;
+  DevBuf lk, post, single, status;
+  if (lk.alloc(w * 8) != hipSuccess || post.alloc(w * 8) != hipSuccess || single.alloc(w * 8) != hipSuccess ||
+      status.alloc(size_t(n_max)) != hipSuccess)
+    return fail(c, FAMSEQ_E_HIP, "tune: device buffers");
+  double *d_lk = lk.as<double>();
+  {
+    // PL-shaped rows — one genotype at 1, the others 10^-(k/10) — for the first 64 K sites, doubled on the device from there
+    const size_t w0 = std::min(w, size_t(1 << 16) * 3 * N);
+    std::vector<double> h(w0);
+    uint64_t z = 0x9E3779B97F4A7C15ull;
+    for (size_t i = 0; i < w0; i += 3) {
+      z = z * 6364136223846793005ull + 1442695040888963407ull;
+      const unsigned a = unsigned(z >> 33) % 3, p1 = 3 + unsigned(z >> 40) % 88, p2 = p1 + unsigned(z >> 50) % 160;
+      h[i + a] = 1.0, h[i + (a + 1) % 3] = std::pow(10.0, -0.1 * p1), h[i + (a + 2) % 3] = std::pow(10.0, -0.1 * p2);
+    }
+    bool up = hipMemcpy(d_lk, h.data(), w0 * 8, hipMemcpyHostToDevice) == hipSuccess;
+    for (size_t have = w0; up && have < w; have *= 2)
+      up = hipMemcpy(d_lk + have, d_lk, std::min(have, w - have) * 8, hipMemcpyDeviceToDevice) == hipSuccess;
+    if (!up) return fail(c, FAMSEQ_E_HIP, "tune: upload");
+  }
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0);
+  (void)hipEventCreate(&e1);
+  std::string report;
+  // best of three launches of one candidate, ms (< 0: it could not be built)
+  auto time_one = [&](const std::string &src, const char *entry, int bt) {
+    GenKernel g;
+    try {
+      g.k = jit_load(src, entry);
+    } catch (const std::exception &) {
+      return -1.0;
+    }
+    g.block_threads = bt, g.blocks_per_cu = 1;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&g.blocks_per_cu, g.k.fn, bt, 0) != hipSuccess || g.blocks_per_cu < 1)
+      g.blocks_per_cu = 1;
+    double best = -1;
+    for (int rep = 0; rep < 4; ++rep) {
+      (void)hipEventRecord(e0, c->stream[1]);
+      const hipError_t e = launch_generated(c, g, n, d_lk, nullptr, post.p, single.p, status.as<uint8_t>(), c->stream[1]);
+      (void)hipEventRecord(e1, c->stream[1]);
+      if (e != hipSuccess || hipEventSynchronize(e1) != hipSuccess) {
+        best = -1;
+        break;
+      }
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, e0, e1);
+      if (rep > 0 && (best < 0 || ms < best)) best = ms;  // the first launch warms up
+    }
+    jit_unload(g.k);
+    return best;
+  };
+  auto race = [&](const char *what, const std::vector<int> &cands, const std::function<std::string(int)> &gen, const char *entry, int bt) {
+    int win = -1;
+    double win_ms = 0;
+    report += std::string(report.empty() ? "" : "; ") + what + ":";
+    for (int v : cands) {
+      const double ms = time_one(gen(v), entry, bt);
+      char buf[64];
+      std::snprintf(buf, sizeof buf, " v%d %.4f ms", v, ms);
+      report += buf;
+      if (ms > 0 && (win < 0 || ms < win_ms * 0.97)) win = v, win_ms = ms;  // a later candidate has to win by 3 % (two runs of one
+                                                                            // table disagreed on 17 of 78 pedigrees at 1 %: all within 2 %)
+    }
+    if (win >= 0) {
+      jit_write_pick(gen(0), win);
+      report += " -> v" + std::to_string(win);
+    }
+    return win;
+  };
+  std::string failed;
+  try {
+    if (enumgen_describe(mdl, 0) != enumgen_describe(mdl, 2))
+      (void)race("enumeration (7- / 6-member block)", {0, 2}, [&mdl](int v) { return enumgen_source(mdl, v, 0); }, "famseq_enum_lane",
+                 enumgen_block_threads(mdl, 0));
+    else
+      report += "enumeration: one block shape, nothing to choose";
+    n = n_elim;
+    if (elim_supported(mdl, nullptr))
+      (void)race("sum-product (likelihoods re-read from LDS: fence-free, fenced; in registers: fence-free, fenced)", {0, 1, 4, 5},
+                 [&mdl](int v) { return elim_source(mdl, v); }, "famseq_elim", elim_block_threads(mdl));
+  } catch (const std::exception &e) {
+    failed = e.what();
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (!failed.empty()) return fail(c, FAMSEQ_E_HIP, "tune: " + failed);
+  c->tune_report = report + " (synthetic sites per launch: " + std::to_string(n_enum) + " enumeration, " + std::to_string(n_elim) + " sum-product)";
+  // the kernels this context holds may have lost: drop them (which, and why no others: drop_lane_kernels), the next use loads the picks
+  GenKernel &lane = c->kern[K_LANE], &elim = c->kern[K_ELIM];
+  const bool had_lane = lane.k.fn != nullptr, had_elim = elim.k.fn != nullptr, had_lc = c->kern[K_LANE_CALL].k.fn != nullptr;
+  drop_lane_kernels(c);
+  elim.drop();
+  if (had_lane && !load_or_remember(c, K_LANE)) return fail(c, FAMSEQ_E_HIP, "lane kernel unavailable after tuning: " + lane.error);
+  if (had_lc && !load_or_remember(c, K_LANE_CALL))
+    return fail(c, FAMSEQ_E_HIP, "call-path kernel unavailable after tuning: " + c->kern[K_LANE_CALL].error);
+  if (had_elim || c->engine == FAMSEQ_ENGINE_ELIM) {
+    const int rc = load_or_fail(c, K_ELIM);
+    if (rc != 0) return rc;
+  }
+  if (lane.variant >= 0 || elim.variant >= 0)  // what this context runs from here on (the notes are honoured as written)
+    c->tune_report += "; loaded:" + (lane.variant >= 0 ? " enumeration v" + std::to_string(lane.variant) : std::string()) +
+                      (elim.variant >= 0 ? " sum-product v" + std::to_string(elim.variant) : std::string());
+  return 0;
+}
+
+// FAMSEQ_PHASE_CLOCK on the plain kernels: their counters sit in a module global; print and clear them.
+void report_phase_clock(famseq_ctx *c) {
+  for (int kind : {K_ELIM, K_LANE}) {
+    const JitKernel &k = c->kern[kind].k;
+    if (!k.module) continue;
+    hipDeviceptr_t p = nullptr;
+    size_t bytes = 0;
+    if (hipModuleGetGlobal(&p, &bytes, k.module, "fs_phase_clk") != hipSuccess || bytes < 8 * sizeof(unsigned long long)) continue;
+    unsigned long long ph[8] = {};
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(ph, p, sizeof ph, hipMemcpyDeviceToHost) != hipSuccess) continue;
+    unsigned long long tot = 0;
+    for (unsigned long long v : ph) tot += v;
+    std::fprintf(stderr, "famseq phase clock, %s kernel (wave cycles):", kind == K_ELIM ? "sum-product" : "enumeration");
+    for (int i = 0; i < 8; ++i) std::fprintf(stderr, " [%d] %.1f%%", i, tot ? 100.0 * double(ph[i]) / double(tot) : 0.0);
+    std::fprintf(stderr, "  total %llu\n", tot);
+    (void)hipMemset(p, 0, sizeof ph);
+  }
+}
+
+}  // namespace famseq

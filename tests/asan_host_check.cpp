@@ -4,8 +4,10 @@
 // -fsanitize=address,undefined, and drives them the way the ABI's callers do on plan-only
 // contexts: model setup and its rejections, plan options (valid and invalid), every variant of
 // both generators, the JSON description, the error paths of the compute entry points without a
-// device, and the JIT's failure path (no compiler).  Any sanitizer report aborts with a non-zero
-// exit status; the program prints one line per pedigree.
+// device, and the JIT's failure path (no compiler) of every kind of generated kernel.  Any sanitizer
+// report aborts with a non-zero exit status; the program prints one line per pedigree.
+#include <dirent.h>
+
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,6 +49,32 @@ int fails = 0;
     }                                                                    \
   } while (0)
 
+// Every failed compilation leaves its source and the compiler's log in the cache: the number of files there tells whether
+// a call went as far as the compiler.
+const char *cache_dir = nullptr;
+int cache_files() {
+  int n = 0;
+  if (DIR *d = opendir(cache_dir)) {
+    while (readdir(d)) ++n;
+    closedir(d);
+  }
+  return n;
+}
+
+// No compiler: the option fails with a message, twice in a row.  A kind that remembers its failure (sticky) answers the
+// second time without generating or compiling again; the others try again.  The plan is read in between.
+size_t fails_twice(famseq_ctx *c, const char *key, int64_t value, bool sticky) {
+  size_t bytes = 0;
+  for (int rep = 0; rep < 2; ++rep) {
+    const int before = cache_files();
+    CHECK(famseq_set_option(c, key, value) != 0);
+    CHECK(std::strlen(famseq_last_error(c)) > 0);
+    if (rep == 1) CHECK(sticky ? cache_files() == before : cache_files() > before);
+    bytes += std::strlen(famseq_plan_json(c));
+  }
+  return bytes;
+}
+
 void drive(const Ped &p) {
   famseq_model m;
   const int n = (int)p.id.size();
@@ -78,6 +106,20 @@ void drive(const Ped &p) {
   CHECK(famseq_set_option(c, "enum_impl", 1) != 0);
   if (elim) CHECK(famseq_set_option(c, "engine", FAMSEQ_ENGINE_ELIM) != 0);
   CHECK(std::strlen(famseq_last_error(c)) > 0);
+  // ... and of the other kinds: lanes-per-site and the call-path forms remember (the first enum_impl above already made
+  // the plain lane kernel's verdict), the sum-product family (plain, trio, MAP) tries again on every call
+  CHECK(famseq_set_option(c, "enum_impl", 1) != 0);
+  if (famseq::enumgen_max_group_digits(m) >= 1) bytes += fails_twice(c, "group_digits", 1, true);
+  bytes += fails_twice(c, "call_kernels", 1, true);
+  bytes += fails_twice(c, "call_kernels", 2, true);
+  if (elim) {
+    bytes += fails_twice(c, "engine", FAMSEQ_ENGINE_ELIM, false);
+    for (int form = 1; form <= 3; ++form) bytes += fails_twice(c, "trio_kernels", form, false);
+    bytes += fails_twice(c, "map_kernels", 1, false);
+  } else {  // refused for the pedigree, before anything is generated
+    CHECK(famseq_set_option(c, "trio_kernels", 1) == FAMSEQ_E_ARG && std::strstr(famseq_last_error(c), "trio posteriors (sum-product engine): "));
+    CHECK(famseq_set_option(c, "map_kernels", 1) == FAMSEQ_E_ARG && std::strstr(famseq_last_error(c), "joint MAP call (sum-product engine): "));
+  }
   // compute entry points on a ctx without a device
   std::vector<double> lk(3 * n * 4, 0.25), post(3 * n * 4);
   std::vector<uint8_t> st(4);
@@ -90,6 +132,30 @@ void drive(const Ped &p) {
   double *dp[1] = {post.data()};
   CHECK(famseq_bn_batch_device_sharded(cs, 1, ns, dl, nullptr, dp, nullptr, nullptr) == FAMSEQ_E_NODEVICE);
   CHECK(famseq_bn_batch_sharded(cs, 1, 4, lk.data(), nullptr, post.data(), nullptr, nullptr) == FAMSEQ_E_NODEVICE);
+  {  // the entries that take lk or packed PLs: exactly one of the two (checked first), then the device
+    std::vector<uint16_t> pl(3 * n * 4, 0);
+    std::vector<int32_t> seq(n);
+    for (int i = 0; i < n; ++i) seq[i] = i;
+    std::vector<double> gpp(3 * n * 4), fpp(3 * n * 4), dnm(4 * n), joint(27 * 4 * n);
+    std::vector<int8_t> fgt(n * 4);
+    std::vector<char> text(size_t(n) * 4 * FAMSEQ_TEXT_STRIDE);
+    for (int both = 0; both <= 1; ++both) {
+      const double *l = both ? lk.data() : nullptr;
+      const uint16_t *q = both ? pl.data() : nullptr;
+      CHECK(famseq_bn_call_batch(c, 4, l, q, nullptr, seq.data(), n, gpp.data(), fpp.data(), fgt.data(), st.data()) == FAMSEQ_E_ARG);
+      CHECK(famseq_bn_call_text_batch(c, 4, l, q, nullptr, seq.data(), n, text.data(), st.data()) == FAMSEQ_E_ARG);
+      CHECK(famseq_trio_batch(c, 4, l, q, seq.data(), n, nullptr, joint.data(), dnm.data(), st.data()) == FAMSEQ_E_ARG);
+      CHECK(famseq_map_batch(c, 4, l, q, seq.data(), n, nullptr, fgt.data(), post.data(), st.data()) == FAMSEQ_E_ARG);
+      CHECK(std::strstr(famseq_last_error(c), "exactly one of") != nullptr);
+    }
+    CHECK(famseq_bn_call_batch(c, 4, lk.data(), nullptr, nullptr, seq.data(), n, gpp.data(), fpp.data(), fgt.data(), st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_bn_call_batch(c, 4, nullptr, pl.data(), nullptr, seq.data(), n, gpp.data(), fpp.data(), fgt.data(), st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_bn_call_text_batch(c, 4, lk.data(), nullptr, nullptr, seq.data(), n, text.data(), st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_bn_call_text_batch(c, 4, lk.data(), nullptr, nullptr, seq.data(), n, nullptr, st.data()) == FAMSEQ_E_ARG);
+    CHECK(famseq_trio_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, joint.data(), dnm.data(), st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_map_batch(c, 4, nullptr, pl.data(), seq.data(), n, nullptr, fgt.data(), post.data(), st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(std::strstr(famseq_last_error(c), "no CPU path") != nullptr);
+  }
   std::vector<int8_t> g(n * 4);
   famseq_call_genotypes(lk.data(), n * 4, g.data());
   famseq_destroy(c);
@@ -106,6 +172,7 @@ int main() {
   const char *dir = mkdtemp(tmpl);
   if (!dir) return 2;
   setenv("FAMSEQ_KERNEL_CACHE", dir, 1);
+  cache_dir = dir;
 
   std::vector<Ped> peds;
   peds.push_back({"single", {1}, {0}, {0}, {1}, {}});

@@ -276,3 +276,43 @@ def test_every_variant_on_wide_pedigrees(n, monkeypatch):
         np.testing.assert_allclose(post[ok], want[0][ok], rtol=1e-9, atol=1e-35)
         assert np.all(np.isnan(post[(st & 3) != 0]))
         assert V.same_bits(runs[v], runs[min(runs)]), "%d members: elim variant %d differs from variant %d" % (n, v, min(runs))
+
+
+@pytest.mark.parametrize("engine", [fs.ENGINE_ENUM, fs.ENGINE_ELIM])
+def test_tune_reloads_every_kernel_it_dropped(engine, tmp_path, monkeypatch):
+    """famseq_set_option "tune" on a context that holds a plain kernel AND its call-path form: both are dropped and loaded
+    again from the picks.  A posterior batch and a call batch on that context are then bit-identical to a fresh context's
+    (which starts from the same picks), the plan names the variants loaded, and the call-path forms are back.
+    (ped5: the sum-product kernel's four candidates are all that is compiled.)"""
+    monkeypatch.setenv("FAMSEQ_KERNEL_CACHE", str(tmp_path))
+    ped = fs.synthetic_pedigree("ped5")
+    model = fs.make_model(ped)
+    mo, fa = ped.relations()
+    lk, flags = fs.synth.gen_batch(mo, fa, 600, 1)
+    seq = np.arange(ped.n, dtype=np.int32)
+
+    def results(ctx):
+        return tuple(ctx.bn_batch(lk, flags)) + tuple(ctx.bn_call_batch(seq, lk=lk, flags=flags))
+
+    ctx = fs.Context(model, enum_impl=1, engine=engine)
+    ctx.set_option("call_kernels", 1)
+    results(ctx)  # every kernel of this engine's path is loaded
+    ctx.set_option("tune", 1)
+    tuned = results(ctx)
+    plan = ctx.plan()
+    ctx.close()
+    assert ("loaded: enumeration v%d" % plan["enum_lane_variant"]) in plan["tune"], plan["tune"]
+    assert plan["enum_lane_variant"] >= 0 and plan["enum_lane_code_object"] and plan["enum_lane_call_code_object"]
+    assert plan["enum_lane_call_variant"] >= 0 and plan["enum_lane_call_reads_rows"] == 0 and plan["elim_call_code_object"]
+    if engine == fs.ENGINE_ELIM:
+        assert (" sum-product v%d" % plan["elim_variant"]) in plan["tune"].split("loaded:")[1] and plan["elim_code_object"]
+    fresh_ctx = fs.Context(model, enum_impl=1, engine=engine)
+    fresh_ctx.set_option("call_kernels", 1)
+    fresh = results(fresh_ctx)
+    fresh_plan = fresh_ctx.plan()
+    fresh_ctx.close()
+    for key in ("enum_lane_code_object", "enum_lane_call_code_object", "enum_lane_variant", "enum_lane_call_variant", "elim_call_code_object",
+                "elim_call_variant") + (("elim_code_object", "elim_variant") if engine == fs.ENGINE_ELIM else ()):
+        assert plan[key] == fresh_plan[key], key
+    for got, want in zip(tuned, fresh):
+        assert np.array_equal(got.view(np.uint8), want.view(np.uint8))
