@@ -82,6 +82,7 @@ ABI_SYMBOLS = [
     "famseq_bn_call_batch", "famseq_bn_call_text_batch", "famseq_bn_call_batch_device", "famseq_format_probe", "famseq_alloc_pinned", "famseq_free_pinned", "famseq_stream_probe",
     "famseq_call_genotypes", "famseq_trio_children", "famseq_trio_batch", "famseq_trio_batch_device",
     "famseq_map_batch", "famseq_map_batch_device",
+    "famseq_bn_prior_batch", "famseq_bn_prior_batch_device", "famseq_bn_prior_call_batch", "famseq_hwe_priors",
 ]
 PL_MISSING = 0xFFFF
 
@@ -163,6 +164,15 @@ def lib():
     L.famseq_map_batch.restype = C.c_int
     L.famseq_map_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp]
     L.famseq_map_batch_device.restype = C.c_int
+    L.famseq_bn_prior_batch.argtypes = [C.c_void_p, C.c_int64, dp, bp, dp, dp, dp, bp]
+    L.famseq_bn_prior_batch.restype = C.c_int
+    L.famseq_bn_prior_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
+    L.famseq_bn_prior_batch_device.restype = C.c_int
+    L.famseq_bn_prior_call_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), bp, dp, C.POINTER(C.c_int32), C.c_int32, dp, dp,
+                                             C.POINTER(C.c_int8), C.c_char_p, bp]
+    L.famseq_bn_prior_call_batch.restype = C.c_int
+    L.famseq_hwe_priors.argtypes = [C.c_int64, dp, dp]
+    L.famseq_hwe_priors.restype = None
     _lib = L
     return L
 
@@ -179,6 +189,15 @@ def transmission_tables(mrate):
 
 def device_count():
     return lib().famseq_device_count()
+
+
+def hwe_priors(af):
+    """Hardy-Weinberg founder priors from allele frequencies (famseq_hwe_priors): -> prior[S, 6] for bn_prior_batch.
+    Row s is ((1-q)^2, 2q(1-q), q^2) — female founders, and every founder off chrX — then (1-q, 0, q), male founders on chrX."""
+    af = np.ascontiguousarray(af, dtype=np.float64).ravel()
+    prior = np.empty((len(af), 6))
+    lib().famseq_hwe_priors(len(af), _p(af, C.c_double), _p(prior, C.c_double))
+    return prior
 
 
 def make_model(ped: Pedigree, mrate=1e-7, lc=1.0, genoProbN=None, genoProbK=None, genoProbXN=None,
@@ -262,6 +281,35 @@ class Context:
         self._check(rc, "famseq_bn_batch")
         return post, single, status
 
+    def bn_prior_batch(self, lk, prior, flags=None, want_single=True, want_status=True):
+        """bn_batch with the founders' genotype prior given per site: -> (post, single, status).
+        prior [S, 6] float64: doubles 0-2 the prior of female founders and of every founder at an autosomal site, doubles 3-5
+        the prior of male founders at a chrX site (hwe_priors makes such rows from allele frequencies).  Of the flags only
+        FLAG_CHRX is read.  Always the sum-product kernel, whatever this context's engine is."""
+        lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
+        s = lk.shape[0]
+        prior = np.ascontiguousarray(prior, dtype=np.float64)
+        if prior.shape != (s, 6):
+            raise ValueError("prior must have six doubles per site")
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        if fl is not None and fl.shape != (s,):
+            raise ValueError("flags must have one byte per site")
+        post = np.empty_like(lk)
+        single = np.empty_like(lk) if want_single else None
+        status = np.zeros(s, np.uint8) if want_status else None
+        rc = lib().famseq_bn_prior_batch(self._h, s, _p(lk, C.c_double), None if fl is None else _p(fl, C.c_uint8),
+                                         _p(prior, C.c_double), _p(post, C.c_double),
+                                         None if single is None else _p(single, C.c_double),
+                                         None if status is None else _p(status, C.c_uint8))
+        self._check(rc, "famseq_bn_prior_batch")
+        return post, single, status
+
+    def bn_prior_batch_device(self, n_sites, d_lk, d_flags, d_prior, d_post, d_single=0, d_status=0, stream=0):
+        """bn_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        rc = lib().famseq_bn_prior_batch_device(self._h, int(n_sites), d_lk or None, d_flags or None, d_prior or None, d_post or None,
+                                                d_single or None, d_status or None, stream or None)
+        self._check(rc, "famseq_bn_prior_batch_device")
+
     def bn_call_batch(self, seq_members, lk=None, pl16=None, flags=None):
         """Fused call path: -> (gpp[S,n_seq,3], fpp[S,n_seq,3], fgt[S,n_seq], status[S]).
         Input is either lk [S,N,3] float64 or pl16 [S,n_seq,3] uint16 (VCF column order)."""
@@ -283,6 +331,32 @@ class Context:
                                         None if fl is None else _p(fl, C.c_uint8), _p(seq, C.c_int32), k,
                                         _p(gpp, C.c_double), _p(fpp, C.c_double), _p(fgt, C.c_int8), _p(status, C.c_uint8))
         self._check(rc, "famseq_bn_call_batch")
+        return gpp, fpp, fgt, status
+
+    def bn_prior_call_batch(self, seq_members, prior, lk=None, pl16=None, flags=None):
+        """bn_call_batch with the founders' prior given per site (prior [S,6] as for bn_prior_batch): separate stages around the
+        site-prior kernel.  -> (gpp, fpp, fgt, status)."""
+        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+        k = len(seq)
+        if (lk is None) == (pl16 is None):
+            raise ValueError("give exactly one of lk / pl16")
+        if lk is not None:
+            lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
+            s = lk.shape[0]
+        else:
+            pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, k, 3)
+            s = pl16.shape[0]
+        prior = np.ascontiguousarray(prior, dtype=np.float64)
+        if prior.shape != (s, 6):
+            raise ValueError("prior must be [n_sites, 6]")
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        gpp, fpp = np.empty((s, k, 3)), np.empty((s, k, 3))
+        fgt, status = np.empty((s, k), np.int8), np.zeros(s, np.uint8)
+        rc = lib().famseq_bn_prior_call_batch(self._h, s, None if lk is None else _p(lk, C.c_double),
+                                              None if pl16 is None else _p(pl16, C.c_uint16),
+                                              None if fl is None else _p(fl, C.c_uint8), _p(prior, C.c_double), _p(seq, C.c_int32), k,
+                                              _p(gpp, C.c_double), _p(fpp, C.c_double), _p(fgt, C.c_int8), None, _p(status, C.c_uint8))
+        self._check(rc, "famseq_bn_prior_call_batch")
         return gpp, fpp, fgt, status
 
     def bn_call_text_batch(self, seq_members, lk=None, pl16=None, flags=None):

@@ -255,6 +255,7 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
       drop_lane_kernels(c);
     } else {
       c->kern[K_ELIM].drop();
+      c->kern[K_PRIOR].drop();  // (it runs in famseq_elim's variant: loaded again, from the note, on its next use)
       if (c->engine == FAMSEQ_ENGINE_ELIM) return load_or_fail(c, K_ELIM);
     }
     return 0;
@@ -285,6 +286,10 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
   else if (k == "map_kernels") {  // build (and on a device ctx load) the MAP kernel now
     if (value != 1) return fail(c, FAMSEQ_E_ARG, "map_kernels takes 1");
     return load_or_fail(c, K_MAP);
+  }
+  else if (k == "prior_kernels") {  // build (and on a device ctx load) the site-prior form of the sum-product kernel now
+    if (value != 1) return fail(c, FAMSEQ_E_ARG, "prior_kernels takes 1");
+    return load_or_fail(c, K_PRIOR);
   }
   else if (k == "group_digits") {
     if (value < -1 || value > enumgen_max_group_digits(c->model))
@@ -345,7 +350,8 @@ std::string trio_json(const famseq_ctx *c) {
   for (int k = 1; k <= 3; ++k) o += std::string(k > 1 ? "," : "") + "\"" + json_str(c->trio(k).k.path) + "\"";
   return o + "],\"trio_variant\":" + std::to_string(f ? c->trio(f).variant : -1) + ",\"trio_children\":" +
          std::to_string(trio_children(c->model).size()) + ",\"map_code_object\":\"" + json_str(c->kern[K_MAP].k.path) + "\",\"map_variant\":" +
-         std::to_string(c->kern[K_MAP].variant);
+         std::to_string(c->kern[K_MAP].variant) + ",\"prior_code_object\":\"" + json_str(c->kern[K_PRIOR].k.path) + "\",\"prior_variant\":" +
+         std::to_string(c->kern[K_PRIOR].variant);
 }
 }  // namespace
 
@@ -426,6 +432,55 @@ extern "C" int famseq_bn_batch(famseq_ctx *c, int64_t n_sites, const double *lk,
   HostIO io;
   io.lk = lk; io.flags = flags; io.post = post; io.single = post_single; io.status = status;
   return run_host(c, n_sites, io, 0);
+}
+
+// ---- founder priors per site -----------------------------------------------------------------------------------------
+
+extern "C" void famseq_hwe_priors(int64_t n, const double *af, double *prior) {
+  for (int64_t i = 0; i < n; ++i) {
+    const double q = af[i], p = 1 - q;
+    double *r = prior + 6 * i;
+    r[0] = p * p, r[1] = 2 * q * p, r[2] = q * q;
+    r[3] = p, r[4] = 0, r[5] = q;
+  }
+}
+
+namespace {
+// What the host entries ask of the prior rows, and the kernel they run.
+int prior_ready(famseq_ctx *c, int64_t n_sites, const uint8_t *flags, const double *prior) {
+  if (n_sites > 0 && !prior) return fail(c, FAMSEQ_E_ARG, "prior must be given (six doubles per site)");
+  if (c->device < 0) return fail(c, FAMSEQ_E_NODEVICE, kNoDevice);
+  for (int64_t s = 0; s < n_sites; ++s)  // (the male chrX row is read at chrX sites only)
+    for (int k = 0, n = flags && (flags[s] & 2) ? 6 : 3; k < n; ++k)
+      if (!(prior[6 * s + k] >= 0 && prior[6 * s + k] <= 1.79769313486231570815e308))
+        return fail(c, FAMSEQ_E_ARG, "prior entries must be finite and >= 0 (site " + std::to_string(s) + ")");
+  HIP_TRY(c, hipSetDevice(c->device));
+  return load_or_fail(c, K_PRIOR);
+}
+}  // namespace
+
+extern "C" int famseq_bn_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint8_t *flags, const double *prior,
+                                     double *post, double *post_single, uint8_t *status) {
+  if (!c) return FAMSEQ_E_ARG;
+  if (n_sites < 0 || (n_sites > 0 && (!lk || !post))) return fail(c, FAMSEQ_E_ARG, "bad batch arguments");
+  const int rc = prior_ready(c, n_sites, flags, prior);
+  if (rc != 0) return rc;
+  HostIO io;
+  io.lk = lk; io.flags = flags; io.prior = prior; io.post = post; io.single = post_single; io.status = status;
+  return run_host(c, n_sites, io, 0);
+}
+
+extern "C" int famseq_bn_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags,
+                                            const double *d_prior, double *d_post, double *d_single, uint8_t *d_status, void *stream) {
+  if (!c) return FAMSEQ_E_ARG;
+  if (n_sites < 0 || (n_sites > 0 && (!d_lk || !d_post))) return fail(c, FAMSEQ_E_ARG, "bad batch arguments");
+  if (n_sites > 0 && !d_prior) return fail(c, FAMSEQ_E_ARG, "d_prior must be given (six doubles per site)");
+  if (c->device < 0) return fail(c, FAMSEQ_E_NODEVICE, kNoDevice);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int rc = load_or_fail(c, K_PRIOR);
+  if (rc != 0 || n_sites == 0) return rc;
+  HIP_TRY(c, launch_generated(c, c->kern[K_PRIOR], n_sites, d_lk, d_flags, d_post, d_single, d_status, static_cast<hipStream_t>(stream), 0, d_prior));
+  return 0;
 }
 
 extern "C" int famseq_bn_batch_sharded(famseq_ctx *const *ctxs, int n_ctx, int64_t n_sites, const double *lk,
@@ -524,6 +579,20 @@ extern "C" int famseq_bn_call_text_batch(famseq_ctx *c, int64_t n_sites, const d
   if ((rc = set_sequenced(c, seq_members, n_seq)) != 0) return rc;
   HostIO io;
   io.lk = lk; io.pl16 = pl16; io.flags = flags; io.text = text; io.status = status;
+  return run_host(c, n_sites, io, n_seq);
+}
+
+extern "C" int famseq_bn_prior_call_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const uint8_t *flags,
+                                          const double *prior, const int32_t *seq_members, int32_t n_seq, double *gpp, double *fpp,
+                                          int8_t *fgt, char *text, uint8_t *status) {
+  if (!c) return FAMSEQ_E_ARG;
+  int rc = check_input(c, n_sites, lk, pl16, "lk / pl16", true, n_seq);
+  if (rc != 0 || (rc = prior_ready(c, n_sites, flags, prior)) != 0) return rc;
+  if ((rc = set_sequenced(c, seq_members, n_seq)) != 0) return rc;
+  HostIO io;
+  io.lk = lk; io.pl16 = pl16; io.flags = flags; io.prior = prior; io.status = status;
+  if (text) io.text = text;
+  else io.gpp = gpp, io.fpp = fpp, io.fgt = fgt;
   return run_host(c, n_sites, io, n_seq);
 }
 

@@ -62,6 +62,7 @@ enum KernelKind {
   K_ELIM_CALL,                                     // ... and its call-path form
   K_TRIO,                                          // K_TRIO + form - 1: trio posteriors per output form (1 dnm, 2 joint, 3 both)
   K_MAP = K_TRIO + 3,                              // the joint MAP configuration
+  K_PRIOR,                                         // the sum-product kernel with the founders' prior per site (famseq_bn_prior_batch)
   K_COUNT
 };
 
@@ -86,7 +87,7 @@ constexpr int kStages = 3;
 
 // The device side of the chunked host pipeline: kSlots copies of every array a chunk passes through.  A set only grows
 // (in sites and in bytes per site), so that varying batch sizes do not thrash.
-enum SlotBuf { B_LK, B_FLAGS, B_STATUS, B_PL, B_POST, B_SINGLE, B_GPP, B_FPP, B_FGT, B_TEXT, B_COUNT,
+enum SlotBuf { B_LK, B_FLAGS, B_STATUS, B_PL, B_POST, B_SINGLE, B_GPP, B_FPP, B_FGT, B_TEXT, B_PRIOR, B_COUNT,
                B_OUT_A = B_POST, B_OUT_B = B_SINGLE };  // (the trio and MAP entries' two outputs)
 struct SlotSet {
   DevBuf buf[kSlots][B_COUNT];
@@ -169,7 +170,7 @@ inline int fail(famseq_ctx *c, int code, const std::string &msg) {
   } while (0)
 
 // ---- kernels.cpp ----
-// The sum-product family (K_ELIM, K_TRIO + form - 1, K_MAP): 0, or an error (FAMSEQ_E_ARG: the engine does not serve this
+// The sum-product family (K_ELIM, K_TRIO + form - 1, K_MAP, K_PRIOR): 0, or an error (FAMSEQ_E_ARG: the engine does not serve this
 // pedigree; FAMSEQ_E_HIP) that is not remembered, the next call tries again.
 int load_or_fail(famseq_ctx *c, int kind);
 // The lane kinds and both call-path forms: false when the kernel is unavailable, which is remembered and said once on
@@ -177,7 +178,7 @@ int load_or_fail(famseq_ctx *c, int kind);
 bool load_or_remember(famseq_ctx *c, int kind);
 void drop_lane_kernels(famseq_ctx *c);  // what a new pick of the lane variant makes stale
 hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,
-                            void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk = 0, const CallIO *d_call = nullptr);
+                            void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk = 0, const void *d_ninth = nullptr);
 hipError_t launch_engine(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, double *d_post, double *d_single,
                          uint8_t *d_status, hipStream_t stream);
 bool call_fuses(famseq_ctx *c, int64_t n_sites, bool packed_in);
@@ -191,6 +192,7 @@ struct HostIO {
   const double *lk = nullptr;      // exactly one of lk / pl16
   const uint16_t *pl16 = nullptr;  // [n_sites][n_seq][3]
   const uint8_t *flags = nullptr;
+  const double *prior = nullptr;  // [n_sites][6]: the founders' prior per site (famseq_bn_prior_batch); the sum-product kernel K_PRIOR
   double *post = nullptr, *single = nullptr;  // raw outputs [n_sites][N][3]
   uint8_t *status = nullptr;
   double *gpp = nullptr, *fpp = nullptr;  // called outputs [n_sites][n_seq][3]

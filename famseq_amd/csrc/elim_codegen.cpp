@@ -145,8 +145,10 @@ class Emitter {
  public:
   // out: where the normalised marginals go — "q" (registers: the shell's compute-first flow) or "row" (the lane's LDS row,
   // free once the likelihoods sit in registers: the shell's registers-first flow)
-  Emitter(const Model &m, const Graph &g, int fences, bool scalar_t, const char *out = "q", bool lean = false, int lean_from = 1 << 30)
-      : m_(m), g_(g), fences_(fences), scalar_t_(scalar_t), out_(out), lean_(lean), lean_from_(lean_from) {}
+  // site_prior: the founders' prior is the site's own (the lane's pa_<g> / pm_<g>, see prior_source) instead of the model's rows in tcf[]
+  Emitter(const Model &m, const Graph &g, int fences, bool scalar_t, const char *out = "q", bool lean = false, int lean_from = 1 << 30,
+          bool site_prior = false)
+      : m_(m), g_(g), fences_(fences), scalar_t_(scalar_t), out_(out), lean_(lean), lean_from_(lean_from), site_prior_(site_prior) {}
 
   std::string body() {
     if (g_.cut.empty()) {
@@ -449,6 +451,7 @@ class Emitter {
   const std::string out_;
   const bool lean_;  // local factors re-formed at each use (see loc)
   const int lean_from_;  // ... for members lean_from_ and above only (their likelihoods sit in the lane's LDS row: direct_shell)
+  const bool site_prior_;  // founders' priors from the lane's variables pa_<g> (female founders; every founder off chrX) / pm_<g> (male)
   std::ostringstream o_;
   std::map<std::string, bool> done_;
   int uid_ = 0;
@@ -489,7 +492,8 @@ class Emitter {
       for (int s : g_.scaled) scale |= s == p;
       for (int g = 0; g < 3; ++g) {
         std::string e = "l" + num(p) + "_" + num(g);
-        if (m_.mother[p] < 0) e = "(tcf[" + num(kind(p) * 27 + 9 * g) + "] * " + e + ")";
+        if (m_.mother[p] < 0)
+          e = "(" + (site_prior_ ? std::string(kind(p) == 0 ? "pm_" : "pa_") + num(g) : "tcf[" + num(kind(p) * 27 + 9 * g) + "]") + " * " + e + ")";
         if (scale) e = "(10000000.0 * " + e + ")";
         // lean: not a variable but a macro — the factor is formed again at each of its two or three uses, from a fresh read of
         // the likelihood, instead of living in a register from the first use to the last (3N doubles: the widest pedigrees'
@@ -934,7 +938,7 @@ const char kDiv3Text[] = R"(
 #endif
 )";
 
-std::string single_posterior_statements(const Model &m, bool flags_pass, bool store, bool fence_single, const char *dst) {
+std::string single_posterior_statements(const Model &m, bool flags_pass, bool store, bool fence_single, const char *dst, bool site_prior) {
   std::ostringstream s;
   const int N = m.n_members;
   // members in groups of four (one at a time in the fenced variants: interleaved division sequences would spill): the products
@@ -953,9 +957,11 @@ std::string single_posterior_statements(const Model &m, bool flags_pass, bool st
     for (int p = lo; p < hi; ++p) {
       const int fk = m.gender[p] == 1 ? 0 : 1;
       const std::string k = std::to_string(p);
+      // the prior of a founder of this member's sex: the model's row, or (site_prior) the lane's own
+      auto pr = [&](int g) { return site_prior ? std::string(fk == 0 ? "pm_" : "pa_") + std::to_string(g) : "tcf[" + std::to_string(fk * 27 + 9 * g) + "]"; };
       s << "      const double a" << k << "_0 = l" << p << "_0, a" << k << "_1 = l" << p << "_1, a" << k << "_2 = l" << p << "_2;\n"
-        << "      const double p" << k << "_0 = a" << k << "_0 * tcf[" << fk * 27 << "], p" << k << "_1 = a" << k << "_1 * tcf[" << fk * 27 + 9
-        << "], p" << k << "_2 = a" << k << "_2 * tcf[" << fk * 27 + 18 << "];\n      const double s" << k << " = (p" << k << "_0 + p" << k
+        << "      const double p" << k << "_0 = a" << k << "_0 * " << pr(0) << ", p" << k << "_1 = a" << k << "_1 * " << pr(1)
+        << ", p" << k << "_2 = a" << k << "_2 * " << pr(2) << ";\n      const double s" << k << " = (p" << k << "_0 + p" << k
         << "_1) + p" << k << "_2;";
       if (flags_pass) s << " if (s" << k << " <= 0) single_fail = true;";
       s << "\n";
@@ -985,6 +991,21 @@ std::string single_posterior_statements(const Model &m, bool flags_pass, bool st
   return s.str();
 }
 
+// Site priors (prior_source): the lane's six doubles of prior_g[n_sites][6].  A site's row is 48 bytes, so a wave's sixty-four rows are
+// one contiguous block of 3 KB; each lane fetches its own in three 16-byte pieces (every line of the block is used whole, by the
+// three loads together), or — an array that is only 8-byte aligned (p16: checked once per launch) — in six doubles.  No LDS (the
+// staged shell's workgroups per CU are set by its LDS rows), no array: the pieces are named variables.
+// pa_<g>: doubles 0-2, female founders and every founder off chrX; pm_<g>: male founders — doubles 3-5 at a chrX site (a per-lane
+// select by the site's flag: the row's second half is read at chrX sites only, whatever it holds elsewhere), pa_<g> at any other.
+const char kPriorLoad[] =
+    "#define PRIOR_LOAD(S) { const double *g_ = prior_g + (S) * 6; \\\n"
+    "  if (p16) { const v2d *h_ = (const v2d *)g_; pu0 = h_[0]; pu1 = h_[1]; pu2 = h_[2]; } \\\n"
+    "  else { pu0.x = g_[0]; pu0.y = g_[1]; pu1.x = g_[2]; pu1.y = g_[3]; pu2.x = g_[4]; pu2.y = g_[5]; } }\n";
+const char kPriorNames[] =
+    "    const bool xs_ = (fl & 2) != 0;\n"
+    "    const double pa_0 = pu0.x, pa_1 = pu0.y, pa_2 = pu1.x;\n"
+    "    const double pm_0 = xs_ ? pu1.y : pa_0, pm_1 = xs_ ? pu2.x : pa_1, pm_2 = xs_ ? pu2.y : pa_2;\n";
+
 // The part every generated engine shares: I/O staging through padded LDS rows, the single
 // posterior, the shortcut vote and the status byte.  `body` runs for sites that need the full
 // computation; it reads l<p>_<g> and tcf[...], and must set bn_fail on a row sum <= 0.
@@ -995,7 +1016,8 @@ std::string single_posterior_statements(const Model &m, bool flags_pass, bool st
 //                   BEFORE the single posterior takes over the row.
 std::string kernel_shell(const Model &m, const std::string &entry, const std::string &comment,
                          const std::string &body, int bt, int min_waves, bool regs_l, bool fence_single,
-                         bool chrx_loop, int row_doubles, bool call_mode, bool lane_body, bool call_ct_out) {
+                         bool chrx_loop, int row_doubles, bool call_mode, bool lane_body, bool call_ct_out, bool site_prior) {
+  if (site_prior && call_mode) throw std::logic_error("kernel_shell: no call-path form with site priors");
   // ROW: the lane's LDS row, W3 doubles padded to an odd count (conflict-free ds_read_b64); a
   // generator may ask for more (spare slots it uses itself), odd again
   const int N = m.n_members, W3 = 3 * N, ROW = (row_doubles > 0 ? row_doubles : W3) | 1;
@@ -1126,13 +1148,15 @@ std::string kernel_shell(const Model &m, const std::string &entry, const std::st
   }
   if (flat_pl) s << "#define FS_LUT_LDS " << lut_lds << "\n" << kCallFlat;
 
+  if (site_prior) s << kPriorLoad;
   if (!regs_l)
     for (int p = 0; p < N; ++p)
       for (int gt = 0; gt < 3; ++gt) s << "#define l" << p << "_" << gt << " lrow[" << 3 * p + gt << "]\n";
   s << "extern \"C\" __global__ __launch_bounds__(BT, " << min_waves << ") void " << entry
     << "(const double *__restrict__ lk_g,\n"
     << "    const unsigned char *__restrict__ flags_g, double *__restrict__ post_g, double *__restrict__ single_g,\n"
-    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc" << (call_mode ? kCallArgs : "") << ") {\n"
+    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc" << (call_mode ? kCallArgs : "")
+    << (site_prior ? ", const double *__restrict__ prior_g" : "") << ") {\n"
     << (flat_pl ? "  __shared__ __attribute__((aligned(16))) double s_io[BT * ROW];  // one padded row per lane: conflict-free ds_read_b64\n"
                 : "  __shared__ double s_io[BT * ROW];  // one padded row per lane: conflict-free ds_read_b64\n")
     << "  __shared__ double s_tc[432];\n"
@@ -1154,6 +1178,10 @@ std::string kernel_shell(const Model &m, const std::string &entry, const std::st
     << "  v2d pre[K2];  // (prefetch) this lane's share of the NEXT chunk, loaded ahead\n"
     << "  const bool v16 = (((unsigned long)lk_g | (unsigned long)post_g | (unsigned long)single_g) & 15) == 0;\n"
     << "  bool have_pre = false;\n"
+    // (site priors) pu0..2: the lane's row of this chunk, fetched at the chunk's start: in flight with the likelihoods' stage-in.
+    // (Fetched a chunk ahead, with the prefetch of the likelihoods, the six doubles live through the output phases cost the trio
+    // kernel its third wave per SIMD: 174 VGPRs against 166; the plain kernel has 152.)
+    << (site_prior ? "  const bool p16 = ((unsigned long)prior_g & 15) == 0;\n  v2d pu0, pu1, pu2;\n" : "")
     << (call_mode ? "  const bool packed_in = call_g->pl != nullptr;  // fed with packed PLs (else fp64 rows)\n"
                     "  __shared__ int s_col[NMEM];  // member -> VCF column or -1\n"
                     // member -> slot of the output row, the same for every lane and chunk.  Small pedigrees keep them in scalar registers
@@ -1181,6 +1209,7 @@ std::string kernel_shell(const Model &m, const std::string &entry, const std::st
     << "    const bool whole = ns == BT;\n"
     << (phase_clock ? "    ph_last_ = __builtin_readcyclecounter();\n" : "")
     << "    LDS_BARRIER();\n";
+  if (site_prior) s << "    PRIOR_LOAD(site0 + (tid < ns ? tid : 0));\n";
   if (prefetch) {
     // the next chunk's rows were requested during the previous chunk's output phases
     s << "    if (have_pre) { STAGE_PRE(); } else { STAGE_IN(lk_g); }\n";
@@ -1192,11 +1221,13 @@ std::string kernel_shell(const Model &m, const std::string &entry, const std::st
                   : (call_mode ? "    STAGE_IN_ANY();\n" : "    STAGE_IN(lk_g);\n"));
   }
   s << "    LDS_BARRIER();\n" << PH(0)
-    << "    const int fl = (tid < ns && flags_g) ? (flags_g[site0 + tid] & 3) : 0;\n"
+    // (site priors: the Known bit chooses between two rows of the model that this kernel does not read)
+    << "    const int fl = (tid < ns && flags_g) ? (flags_g[site0 + tid] & " << (site_prior ? 2 : 3) << ") : 0;\n"
     << "    const double *tcf = s_tc + fl * 108;\n"
-    << "    bool single_fail = false, full = false, bn_fail = false;\n";
+    << "    bool single_fail = false, full = false, bn_fail = false;\n"
+    << (site_prior ? kPriorNames : "");
   auto single_pass = [&](bool flags_pass, bool store, const char *dst = "row") {
-    s << single_posterior_statements(m, flags_pass, store, fence_single, dst);
+    s << single_posterior_statements(m, flags_pass, store, fence_single, dst, site_prior);
   };
   if (regs_l) {
     for (int p = 0; p < N; ++p)
@@ -1303,7 +1334,7 @@ namespace {
 // the CU's LDS: 3N doubles per lane leave two waves per CU at 48 members and nothing beyond about a hundred; this form
 // needs 3.4 KB of LDS (the factor tables) whatever N is, runs four waves per CU, and has no barrier after the first.
 std::string direct_shell(const Model &m, const std::string &comment, const std::string &body, int bt, bool fence_single, bool chrx_loop,
-                         bool lean, int lds_from) {
+                         bool lean, int lds_from, bool site_prior = false) {
   // lds_from: members lds_from .. N-1 keep their likelihoods in a per-lane LDS row (3 doubles each, odd stride) and are read
   // from there at each use; the others live in registers.  The last members' local factors have the longest live ranges (the
   // upward pass of the first marginal touches every member, and member p's factor is needed again at its own marginal).
@@ -1314,6 +1345,7 @@ std::string direct_shell(const Model &m, const std::string &comment, const std::
     << "#define W3 " << W3 << "\n#define BT " << bt << "\n"
     << "#define LDS_BARRIER() asm volatile(\"s_waitcnt lgkmcnt(0)\\n\\ts_barrier\" ::: \"memory\")\n"
     << kDiv3Text;
+  if (site_prior) s << "typedef double v2d __attribute__((ext_vector_type(2)));\n" << kPriorLoad;
   if (lean)  // a likelihood is read from the lane's row in global memory at each use (volatile: never kept in a register)
     for (int p = 0; p < N; ++p)
       for (int gt = 0; gt < 3; ++gt) s << "#define l" << p << "_" << gt << " lgv[" << 3 * p + gt << "]\n";
@@ -1322,12 +1354,15 @@ std::string direct_shell(const Model &m, const std::string &comment, const std::
       for (int gt = 0; gt < 3; ++gt) s << "#define l" << p << "_" << gt << " lrow[" << 3 * (p - lds_from) + gt << "]\n";
   int min_waves = 1;
   if (const char *e = std::getenv("FAMSEQ_ELIM_MINWAVES")) min_waves = std::max(1, std::atoi(e));  // tuning aid
-  s << "extern \"C\" __global__ __launch_bounds__(BT, " << min_waves << ") void famseq_elim(const double *__restrict__ lk_g,\n"
+  s << "extern \"C\" __global__ __launch_bounds__(BT, " << min_waves << ") void " << (site_prior ? "famseq_elim_prior" : "famseq_elim")
+    << "(const double *__restrict__ lk_g,\n"
     << "    const unsigned char *__restrict__ flags_g, double *__restrict__ post_g, double *__restrict__ single_g,\n"
-    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc) {\n"
+    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc"
+    << (site_prior ? ", const double *__restrict__ prior_g" : "") << ") {\n"
     << "  __shared__ double s_tc[432];\n"
     << "  const int tid = threadIdx.x;\n"
-    << "  for (int i = tid; i < 432; i += BT) s_tc[i] = tc_g[i];\n";
+    << "  for (int i = tid; i < 432; i += BT) s_tc[i] = tc_g[i];\n"
+    << (site_prior ? "  const bool p16 = ((unsigned long)prior_g & 15) == 0;\n  v2d pu0, pu1, pu2;\n" : "");
   if (n_lds > 0)
     s << "  __shared__ double s_l[BT * " << LP << "];  // the last " << n_lds << " members' likelihoods, one padded row per lane\n"
       << "  typedef const volatile __attribute__((address_space(3))) double lds_cvd;\n"
@@ -1343,9 +1378,10 @@ std::string direct_shell(const Model &m, const std::string &comment, const std::
     << "    const double *lg = lk_g + site * W3;\n"
     << "    double *pg = post_g + site * W3;\n"
     << "    double *row = single_g ? single_g + site * W3 : pg;  // where the single posterior goes\n"
-    << "    const int fl = flags_g ? (flags_g[site] & 3) : 0;\n"
+    << "    const int fl = flags_g ? (flags_g[site] & " << (site_prior ? 2 : 3) << ") : 0;\n"
     << "    const double *tcf = s_tc + fl * 108;\n"
-    << "    bool single_fail = false, full = false, bn_fail = false;\n";
+    << "    bool single_fail = false, full = false, bn_fail = false;\n"
+    << (site_prior ? std::string("    PRIOR_LOAD(site);\n") + kPriorNames : std::string());
   if (lean)
     s << "    typedef const volatile __attribute__((address_space(1))) double glb_cvd;\n    glb_cvd *lgv = (glb_cvd *)lg;\n";
   else {
@@ -1353,7 +1389,7 @@ std::string direct_shell(const Model &m, const std::string &comment, const std::
       for (int gt = 0; gt < 3; ++gt) s << "    const double l" << p << "_" << gt << " = lg[" << 3 * p + gt << "];\n";
     for (int k = 3 * std::min(N, lds_from); k < W3; ++k) s << "    lw[" << k - 3 * lds_from << "] = lg[" << k << "];\n";
   }
-  s << single_posterior_statements(m, true, true, fence_single)
+  s << single_posterior_statements(m, true, true, fence_single, "row", site_prior)
     << "    if (single_fail) {\n#pragma unroll 1\n      for (int k = 0; k < W3; ++k) row[k] = kNaN;\n    }\n"
     // a site that does not take the full computation: its posterior IS the single posterior (family.cpp:793-878) or NaN
     << "    if (single_g && !(full && !single_fail)) {\n#pragma unroll 1\n      for (int k = 0; k < W3; ++k) pg[k] = row[k];\n    }\n";
@@ -1582,7 +1618,19 @@ std::string map_source(const Model &m, int variant) {
                    f >= 3, /*chrx_loop=*/f >= 1, lean);
 }
 
-std::string elim_source(const Model &m, int variant, bool call_mode) {
+namespace {
+std::string sum_product_source(const Model &m, int variant, bool call_mode, bool site_prior);
+}
+
+std::string elim_source(const Model &m, int variant, bool call_mode) { return sum_product_source(m, variant, call_mode, false); }
+
+// famseq_elim with the founders' prior given per site (famseq_bn_prior_batch): the same shells and the same statements in the
+// same order, every founder-prior operand the lane's own pa_<g> / pm_<g> instead of an entry of the model's table.
+std::string prior_source(const Model &m, int variant) { return sum_product_source(m, variant, false, true); }
+
+namespace {
+std::string sum_product_source(const Model &m, int variant, bool call_mode, bool site_prior) {
+  const std::string with_prior = site_prior ? ", founder priors per site" : "";
   Graph g;
   std::string why;
   if (!build_graph(m, g, &why)) throw std::runtime_error("elimination engine: " + why);
@@ -1599,9 +1647,9 @@ std::string elim_source(const Model &m, int variant, bool call_mode) {
     return direct_shell(m,
                         "exact sum-product over " + std::to_string(g.fam.size()) + " nuclear families" +
                             (g.cut.empty() ? "" : ", conditioned on " + std::to_string(g.cut.size()) + " member(s)") + ", variant " +
-                            std::to_string(variant) + " (rows straight from and to global memory)",
-                        Emitter(m, g, f < 2 ? f : 2, /*scalar_t=*/f >= 1, "pg", lean, lds_from).body(), elim_block_threads(m, false), f >= 3,
-                        /*chrx_loop=*/f >= 1, lean, lds_from);
+                            std::to_string(variant) + " (rows straight from and to global memory)" + with_prior,
+                        Emitter(m, g, f < 2 ? f : 2, /*scalar_t=*/f >= 1, "pg", lean, lds_from, site_prior).body(), elim_block_threads(m, false),
+                        f >= 3, /*chrx_loop=*/f >= 1, lean, lds_from, site_prior);
   }
   const int bt = elim_block_threads(m, call_mode);
   int min_waves = call_mode && m.n_members <= 10 ? 2 : 1;
@@ -1621,10 +1669,11 @@ std::string elim_source(const Model &m, int variant, bool call_mode) {
   const std::string what = "exact sum-product over " + std::to_string(g.fam.size()) + " nuclear families" +
                            (g.cut.empty() ? "" : ", conditioned on " + std::to_string(g.cut.size()) + " member(s)") + ", variant " +
                            std::to_string(variant + (call_mode ? (ct_out ? 0 : 4) : (regs_l ? 4 : 0))) + (regs_l ? " (likelihoods in registers)" : "") +
-                           (call_mode ? ", call path" : "");
-  return kernel_shell(m, "famseq_elim", what,
-                      Emitter(m, g, variant < 2 ? variant : 2, /*scalar_t=*/variant >= 1, regs_l ? "row" : "q").body(), bt, min_waves,
-                      regs_l, variant >= 3, /*chrx_loop=*/variant >= 1, 0, call_mode, /*lane_body=*/false, ct_out);
+                           (call_mode ? ", call path" : "") + with_prior;
+  return kernel_shell(m, site_prior ? "famseq_elim_prior" : "famseq_elim", what,
+                      Emitter(m, g, variant < 2 ? variant : 2, /*scalar_t=*/variant >= 1, regs_l ? "row" : "q", false, 1 << 30, site_prior).body(),
+                      bt, min_waves, regs_l, variant >= 3, /*chrx_loop=*/variant >= 1, 0, call_mode, /*lane_body=*/false, ct_out, site_prior);
 }
+}  // namespace
 
 }  // namespace famseq

@@ -33,6 +33,13 @@ std::string elim_source(const Model &m, int variant, bool call_mode = false);
 int elim_block_threads(const Model &m, bool call_mode = false);
 int elim_first_variant(const Model &m, bool call_mode = false);  // where jit_pick_variant starts (see elim_block_threads)
 
+// Site priors (famseq_bn_prior_batch).  HIP source of `extern "C" __global__ famseq_elim_prior(lk, flags, post, single, status,
+// n_sites, tc, lc, prior)`: famseq_elim with the founders' genotype prior read per site from prior[n_sites][6] (doubles 0-2: female
+// founders and every founder at an autosomal site; 3-5: male founders at a chrX site) instead of the model's genoProb rows; the
+// flags' Known bit is not read.  Variants and their numbering are elim_source's (the plain form only); fed the model's own rows
+// it returns famseq_elim's bits.  Throws if the engine does not serve the pedigree.
+std::string prior_source(const Model &m, int variant);
+
 // Trio posteriors (famseq_trio_batch): the children are the members with parents, in PED order.
 std::vector<int> trio_children(const Model &m);
 // HIP source of `extern "C" __global__ famseq_trio(lk, flags, joint, dnm, status, n_sites, tc, lc)`: per site and child k the
@@ -54,11 +61,13 @@ std::string map_source(const Model &m, int variant);
 extern const std::string kCallHelpers;  // fused call path: fs_phred, STAGE_IN_PL, STAGE_OUT_CALL, STAGE_FGT
 extern const char kCallArgs[];     // ... and the kernel arguments that go with them
 extern const char kDiv3Text[];     // FS_DIV_OK / FS_DIV3_FAST: what single_posterior_statements' text needs defined
-std::string single_posterior_statements(const Model &m, bool flags_pass, bool store, bool fence_single, const char *dst = "row");
+// site_prior: the founder-prior operands are the lane's variables pa_<g> / pm_<g> (see prior_source) instead of tcf[] entries
+std::string single_posterior_statements(const Model &m, bool flags_pass, bool store, bool fence_single, const char *dst = "row",
+                                        bool site_prior = false);
 std::string kernel_shell(const Model &m, const std::string &entry, const std::string &comment,
                          const std::string &body, int bt, int min_waves, bool regs_l, bool fence_single,
                          bool chrx_loop = false, int row_doubles = 0, bool call_mode = false, bool lane_body = false,
-                         bool call_ct_out = true);
+                         bool call_ct_out = true, bool site_prior = false);
 
 }  // namespace famseq
 #endif

@@ -3,7 +3,7 @@
 // Keeps the reference's CLI and file surface for the `-method 1` path:
 //   FamSeq vcf -vcfFile f -pedFile p -output o [-v] [-a] [-d] [-o] [-l loc] [-method 1]
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
-//              [-genoProbXK a c] [-LRC x] [-dnm] [-map]
+//              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-afTag KEY]
 //   FamSeq LK  -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -189,6 +189,7 @@ struct Options {
   int num_burn = -999, num_rep = -999;
   bool dnm = false;  // -dnm: a DNP field per sample (vcf mode)
   bool map = false;  // -map: JGT and JP fields per sample (vcf mode)
+  string af_tag;     // -afTag KEY: the founders' prior of a line from the allele frequency KEY= of its INFO column (vcf mode)
 };
 
 // returns 0 good, 1 warnings, -1 stop (checkInput.h:345-349)
@@ -320,6 +321,15 @@ int parse_options(int argc, char **argv, Options &o) {
       o.dnm = true;
     } else if (opt == "map") {
       o.map = true;
+    } else if (opt == "afTag") {
+      i++;
+      if (missing(i)) {
+        std::cout << "The INFO key of -afTag hasn't been set. The option is ignored." << std::endl;
+        i--;
+        rv = 1;
+      } else {
+        o.af_tag = argv[i];
+      }
     } else if (opt == "LRC") {
       i++;
       if (missing(i)) {
@@ -686,6 +696,41 @@ bool map_supported(const Options &o, const Ped &ped) {
   if (k < 0) std::cout << "-map cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
   famseq_destroy(probe);
   return k >= 0;
+}
+
+// -afTag: and for the site-prior kernel.
+bool af_supported(const Options &o, const Ped &ped) {
+  CliModel m;
+  vector<uint8_t> all(ped.n(), 1);
+  if (m.init(ped, all, o.mrate, o.lrc) != 0) return true;  // (the driver reports a bad pedigree itself)
+  char err[512] = {0};
+  famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
+  const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;  // (elim_supported, as above)
+  if (k < 0) std::cout << "-afTag cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
+  famseq_destroy(probe);
+  return k >= 0;
+}
+
+// -afTag: the allele frequency of a line, the first value of KEY= in its INFO column; < 0 where there is none to use (no such
+// key, not a number, outside (0, 1)).
+double info_af(std::string_view info, const string &key) {
+  size_t at = 0;
+  while (at < info.size()) {
+    size_t end = info.find(';', at);
+    if (end == std::string_view::npos) end = info.size();
+    const std::string_view f = info.substr(at, end - at);
+    if (f.size() > key.size() + 1 && f[key.size()] == '=' && f.compare(0, key.size(), key) == 0) {
+      std::string_view v = f.substr(key.size() + 1);
+      v = v.substr(0, v.find(','));
+      const string text(v);
+      char *stop = nullptr;
+      const double q = std::strtod(text.c_str(), &stop);
+      if (stop == text.c_str() || *stop != 0 || !(q > 0 && q < 1)) return -1;
+      return q;
+    }
+    at = end + 1;
+  }
+  return -1;
 }
 
 void put_triple(std::ostream &o, const double *p) { o << p[0] << ":" << p[1] << ":" << p[2]; }
@@ -1226,6 +1271,13 @@ bool run_vcf(const Options &o, const Ped &ped) {
     if (o.gXN.size() == 3) std::copy(o.gXN.begin(), o.gXN.end(), m.p.genoProbXN);
     if (o.gXK.size() == 3) std::copy(o.gXK.begin(), o.gXK.end(), m.p.genoProbXK);
   }
+  const bool use_af = !o.af_tag.empty() && !o.pack_mode;
+  // -afTag: the rows of a line without a usable frequency, by its Known flag: what the model itself would have used
+  double model_rows[2][6];
+  for (int k = 0; k < 3; ++k) {
+    model_rows[0][k] = m.p.genoProbN[k], model_rows[0][3 + k] = m.p.genoProbXN[k];
+    model_rows[1][k] = m.p.genoProbK[k], model_rows[1][3 + k] = m.p.genoProbXK[k];
+  }
   // pack mode writes a binary file: the text header goes nowhere
   std::ofstream fout;
   if (!o.pack_mode) fout.open(o.out_file.c_str());
@@ -1252,6 +1304,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
     fout << "##FS genotype frequency in population (Common): "; put_triple(fout, m.p.genoProbK); fout << std::endl;
     fout << "##FS genotype frequency for chromosome X of male in population (Rare): "; put_triple(fout, m.p.genoProbXN); fout << std::endl;
     fout << "##FS genotype frequency for chromosome X of male in population (Common): "; put_triple(fout, m.p.genoProbXK); fout << std::endl;
+    if (use_af) fout << "##FS genotype frequency of a site with 0 < " << o.af_tag << " < 1 in INFO: Hardy-Weinberg at that allele frequency" << std::endl;
   };
   string title;
   std::string_view line;
@@ -1394,7 +1447,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
   // the batch: a site's flag byte and packed PLs are written where the GPU call will read them (flags_q, pl16: the
   // caller has set them to "all samples missing", which is what a line that is no site stays — computed and ignored;
   // compacting the sites first cost a pass over the batch, and the GPU idles nine tenths of the loop).
-  auto parse_line = [&](std::string_view line, size_t q, Part &out, uint8_t *flags_q, uint16_t *pl16) {
+  auto parse_line = [&](std::string_view line, size_t q, Part &out, uint8_t *flags_q, uint16_t *pl16, double *prior_q) {
     if (line[0] == '#') return;
     thread_local vector<std::string_view> t, fmt, sub;
     thread_local vector<double> lkrow;
@@ -1455,6 +1508,11 @@ bool run_vcf(const Options &o, const Ped &ped) {
     out.items.push_back(Item{base, uint32_t(line.size()), uint32_t(t[8].data() + t[8].size() - base), uint32_t(fmt.size()),
                              int32_t(q), 0, 0, uint32_t(out.samples.size())});
     *flags_q = flags;
+    if (prior_q) {
+      const double af = info_af(t[7], o.af_tag);
+      if (af > 0) famseq_hwe_priors(1, &af, prior_q);
+      else std::copy(model_rows[flags & FAMSEQ_FLAG_KNOWN ? 1 : 0], model_rows[flags & FAMSEQ_FLAG_KNOWN ? 1 : 0] + 6, prior_q);
+    }
     lkrow.assign(N3, 1.0);
     bool integral = true;
     size_t col = 0;
@@ -1512,6 +1570,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
     vector<uint8_t> pk_flags;
     PlBatch io;          // pinned: pl + flags in, gpp / fpp / fgt / status out
     vector<double> lk;   // fp64 input, only for a block with a non-integer PL/GL field
+    vector<double> prior;  // -afTag: [line][6], the founders' prior rows (a line that is no site keeps the model's)
     vector<TextBuf> text;
     vector<double> dnm;      // -dnm: [site][child] de novo posteriors ...
     vector<uint8_t> tstatus;  // ... and the trio kernel's status per site
@@ -1555,9 +1614,12 @@ bool run_vcf(const Options &o, const Ped &ped) {
       }
       const double t0 = now_s();
       if (sl.n_sites > 0 && flush_ok) {
-        const int rc = sl.io.call(ctx, sl.n_sites, sl.packed ? nullptr : sl.lk.data(), seq_members.data());
+        const double *lk_in = sl.packed ? nullptr : sl.lk.data();
+        const int rc = use_af ? famseq_bn_prior_call_batch(ctx, (int64_t)sl.n_sites, lk_in, lk_in ? nullptr : sl.io.pl, sl.io.flags, sl.prior.data(),
+                                                           seq_members.data(), (int32_t)n_seq, sl.io.gpp, sl.io.fpp, sl.io.fgt, sl.io.text, sl.io.status)
+                              : sl.io.call(ctx, sl.n_sites, lk_in, seq_members.data());
         if (rc != 0) {
-          std::cerr << "famseq_bn_call_batch failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
+          std::cerr << (use_af ? "famseq_bn_prior_call_batch" : "famseq_bn_call_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
           flush_ok = false;
         }
         if (o.dnm && flush_ok) {  // the same batch through the trio kernel (full network, whatever -LRC and -method say)
@@ -1739,13 +1801,16 @@ bool run_vcf(const Options &o, const Ped &ped) {
     }
     uint16_t *const pl_arr = o.pack_mode || sl.staged ? sl.pk_pl.data() : sl.io.pl;
     uint8_t *const flags_arr = o.pack_mode || sl.staged ? sl.pk_flags.data() : sl.io.flags;
+    if (use_af) sl.prior.resize(nl * 6);
+    double *const prior_arr = use_af ? sl.prior.data() : nullptr;
     on_parts(sl.n_parts, parse_threads, [&](int t) {
       Part &pt = sl.parts[t];
       pt.clear();
       const size_t lo = nl * t / sl.n_parts, hi = nl * (t + 1) / sl.n_parts;
       std::memset(flags_arr + lo, 0, hi - lo);
+      for (size_t q = lo; prior_arr && q < hi; ++q) std::copy(model_rows[0], model_rows[0] + 6, prior_arr + 6 * q);
       std::memset(pl_arr + lo * 3 * n_seq, 0xFF, (hi - lo) * 6 * n_seq);  // 0xFFFF x3 = missing sample
-      for (size_t q = lo; q < hi; ++q) parse_line(sl.lines[q], q, pt, flags_arr + q, pl_arr + q * 3 * n_seq);
+      for (size_t q = lo; q < hi; ++q) parse_line(sl.lines[q], q, pt, flags_arr + q, pl_arr + q * 3 * n_seq, prior_arr ? prior_arr + 6 * q : nullptr);
     });
     double t3 = now_s();
     t_parse += t3 - t2;
@@ -1790,6 +1855,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
           if (d != q) {
             flags_arr[d] = flags_arr[q];
             std::memmove(pl_arr + d * 3 * n_seq, pl_arr + q * 3 * n_seq, 6 * n_seq);
+            if (prior_arr) std::memmove(prior_arr + 6 * d, prior_arr + 6 * q, 48);
           }
           if (x < pt.explicit_sites.size() && pt.explicit_sites[x] == q) pt.explicit_sites[x++] = uint32_t(d);
           it.site = int32_t(d++);
@@ -1971,6 +2037,8 @@ void help() {
             << "-genoProbXN\tPr(G) for chromosome X of males, not in dbSNP. Default 0.999 0.001." << std::endl
             << "-genoProbXK\tPr(G) for chromosome X of males, in dbSNP. Default 0.5 0.5." << std::endl
             << "-LRC\t\tLikelihood ratio criterion for the single-sample shortcut. Default 1." << std::endl
+            << "-afTag KEY\t(vcf) Founders' genotype prior per line: Hardy-Weinberg at the allele frequency KEY= of the INFO column (the first" << std::endl
+            << "\t\tvalue of a list), where it lies in (0, 1); the model's priors elsewhere. Implies -method 2; not with -dnm / -map." << std::endl
             << "-dnm\t\t(vcf) Add DNP, each child's posterior probability of a de novo mutation, to every sample column." << std::endl
             << "-map\t\t(vcf) Add JGT and JP, each member's genotype in the most probable joint configuration of the family and" << std::endl
             << "\t\tthat configuration's posterior probability, to every sample column." << std::endl
@@ -2031,6 +2099,20 @@ int main(int argc, char **argv) {
   if (o.dnm && mode == "vcf" && !dnm_supported(o, ped)) return 255;
   if (o.map && mode != "vcf") std::cout << "-map applies to vcf mode only; ignored here." << std::endl;
   if (o.map && mode == "vcf" && !map_supported(o, ped)) return 255;
+  if (!o.af_tag.empty()) {
+    if (mode != "vcf") {
+      std::cout << "-afTag applies to vcf mode only; ignored here." << std::endl;
+      o.af_tag.clear();
+    } else if (o.dnm || o.map) {
+      std::cout << "-afTag cannot be combined with -dnm or -map: their kernels use the model's priors, and one output line must not mix two models."
+                << std::endl;
+      return -1;
+    } else if (!af_supported(o, ped)) {
+      return 255;
+    } else {
+      o.method = 2;  // site priors are served by the sum-product engine
+    }
+  }
   const double t0 = now_s();
   if (o.tune_mode) return run_tune(o, ped) ? 0 : -1;
   const bool ok = o.pl_mode ? run_pl(o, ped) : (o.lk_mode ? run_lk(o, ped) : run_vcf(o, ped));

@@ -20,6 +20,9 @@ struct KernelSpec {
   bool honours_pick;                       // a note of the tuner's, keyed by the variant-0 source, names the variant instead
   const char *entry;
   int block_threads;
+  // where given: the kernel whose variant this one takes — that kernel's note, else that kernel's contest, so that a
+  // context runs both in one variant whatever the compiler's register allocation makes of either
+  std::function<std::string(int)> variant_of = nullptr;
 };
 
 bool is_lane(int kind) { return kind >= K_LANE && kind <= K_LANE + kEnumMaxGroupDigits; }
@@ -51,6 +54,9 @@ KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
               elim_block_threads(m, true)};
     case K_MAP:
       return {[&m](int v) { return map_source(m, v); }, kMapVariants, 0, false, "famseq_map", elim_block_threads(m)};
+    case K_PRIOR:  // the variant famseq_elim takes for the pedigree (its measured pick, "pick_elim", or its contest): none of its own
+      return {[&m](int v) { return prior_source(m, v); }, kElimVariants, elim_first_variant(m), true, "famseq_elim_prior", elim_block_threads(m),
+              [&m](int v) { return elim_source(m, v); }};
   }
   throw std::logic_error("kernel_spec: no such kind");
 }
@@ -65,11 +71,15 @@ int load_kernel(famseq_ctx *c, int kind, std::string *why) {
     const KernelSpec s = kernel_spec(c, kind);
     // a measured pick (the autotuner's note, or the table build() ships) is loaded as it is: the spill contest is
     // the static rule for pedigrees nobody has measured, and must not move off a measurement
-    const int pick = s.honours_pick ? jit_read_pick(s.source(0)) : -1;
+    const std::function<std::string(int)> &chooser = s.variant_of ? s.variant_of : s.source;
+    const int pick = s.honours_pick ? jit_read_pick(chooser(0)) : -1;
     std::string src;
     if (pick >= 0 && pick < s.n_variants) {
       src = s.source(pick);
       g.variant = pick;
+    } else if (s.variant_of) {
+      (void)jit_pick_variant(chooser, s.n_variants, &g.variant, s.first);
+      src = s.source(g.variant);
     } else {
       src = jit_pick_variant(s.source, s.n_variants, &g.variant, s.first);
     }
@@ -98,7 +108,7 @@ int load_or_fail(famseq_ctx *c, int kind) {
   std::string why;
   if (!elim_supported(c->model, &why))
     return fail(c, FAMSEQ_E_ARG, (kind == K_ELIM ? "elimination engine: " : kind == K_MAP ? "joint MAP call (sum-product engine): "
-                                                                                           : "trio posteriors (sum-product engine): ") + why);
+                                  : kind == K_PRIOR ? "site priors (sum-product engine): " : "trio posteriors (sum-product engine): ") + why);
   if (load_kernel(c, kind, &why) != 0) return fail(c, FAMSEQ_E_HIP, why);
   return 0;
 }
@@ -142,7 +152,8 @@ bool load_or_remember(famseq_ctx *c, int kind) {
 // A pick (the tuner's note, "pick_lane" / "pick_elim") is read by two loaders only — K_LANE and K_ELIM, the kinds whose
 // kernel_spec honours it — and the lane call-path form takes its block shape from K_LANE's variant.  Those three are what
 // a new pick makes stale; the lanes-per-site, sum-product call-path, trio and MAP kernels run their own contests and
-// cannot be moved by one, so they stay loaded.
+// cannot be moved by one, so they stay loaded.  (The site-prior kernel takes K_ELIM's variant: whoever drops K_ELIM for a
+// new pick drops K_PRIOR with it.)
 void drop_lane_kernels(famseq_ctx *c) {
   c->kern[K_LANE].drop();
   c->kern[K_LANE_CALL].drop();
@@ -201,9 +212,10 @@ int grid_for(const famseq_ctx *c, int64_t n_sites) {
 }  // namespace
 
 // The generated kernels share one argument list; what the third and fourth are depends on the kind (posterior and single
-// posterior rows, joint and de novo posteriors, MAP genotypes and their posterior), so they pass through untyped.
+// posterior rows, joint and de novo posteriors, MAP genotypes and their posterior), so they pass through untyped; so does
+// the ninth, which two kinds take: the call-path forms their CallIO, the site-prior kernel its prior rows.
 hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,
-                            void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk, const CallIO *d_call) {
+                            void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk, const void *d_ninth) {
   const int spc = sites_per_chunk > 0 ? sites_per_chunk : g.block_threads;
   const int64_t chunks = (n_sites + spc - 1) / spc;
   int64_t resident = c->grid_override > 0 ? c->grid_override : int64_t(c->n_cus) * g.blocks_per_cu;
@@ -211,7 +223,7 @@ hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, 
   long ns = (long)n_sites;
   double lc = c->model.lc;
   const double *tc = c->d_tc.as<double>();
-  void *args[] = {&d_lk, &d_flags, &d_out_a, &d_out_b, &d_status, &ns, &tc, &lc, &d_call};  // the plain forms take the first eight
+  void *args[] = {&d_lk, &d_flags, &d_out_a, &d_out_b, &d_status, &ns, &tc, &lc, &d_ninth};  // the plain forms take the first eight
   return hipModuleLaunchKernel(g.k.fn, grid, 1, 1, (unsigned)g.block_threads, 1, 1, 0, stream, args, nullptr);
 }
 
@@ -374,6 +386,7 @@ int tune(famseq_ctx *c) {
   const bool had_lane = lane.k.fn != nullptr, had_elim = elim.k.fn != nullptr, had_lc = c->kern[K_LANE_CALL].k.fn != nullptr;
   drop_lane_kernels(c);
   elim.drop();
+  c->kern[K_PRIOR].drop();  // follows famseq_elim's pick: loaded again on its next use
   if (had_lane && !load_or_remember(c, K_LANE)) return fail(c, FAMSEQ_E_HIP, "lane kernel unavailable after tuning: " + lane.error);
   if (had_lc && !load_or_remember(c, K_LANE_CALL))
     return fail(c, FAMSEQ_E_HIP, "call-path kernel unavailable after tuning: " + c->kern[K_LANE_CALL].error);

@@ -21,7 +21,7 @@ struct Staged {
 // What a call moves: the arrays copied in before a chunk's kernels and those copied out after them, in that order.
 struct ChunkJob {
   int64_t n_sites = 0, chunk = 0;
-  Staged in[2], out[7];
+  Staged in[3], out[7];
   int n_in = 0, n_out = 0;
   void copy_in(int buf, size_t row, const void *host) {
     if (host && row) in[n_in++] = {buf, row, static_cast<char *>(const_cast<void *>(host))};  // (read only)
@@ -127,7 +127,7 @@ CallIO make_call_io(const famseq_ctx *c, const uint16_t *d_pl, double *d_gpp, do
 }
 
 // The posterior and call entries: per chunk the fused call-path launch, or [unpack] -> posterior kernel -> [Phred / call]
-// -> [text].
+// -> [text].  With io.prior (famseq_bn_prior_batch, famseq_bn_prior_call_batch) the posterior kernel is the site-prior one.
 int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
   if (c->device < 0) return fail(c, FAMSEQ_E_NODEVICE, "context was created without a device; there is no CPU path");
   if (n_sites == 0) return 0;
@@ -140,7 +140,8 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
   job.n_sites = n_sites;
   job.chunk = chunk_for(c, n_sites, row);
   SlotSet &t = c->slots;
-  const size_t want[B_COUNT] = {row, 1, 1, seq * 3 * sizeof(uint16_t), row, row, call_row, call_row, seq, seq * size_t(kTextStride)};
+  const size_t prior_row = io.prior ? 6 * sizeof(double) : 0;
+  const size_t want[B_COUNT] = {row, 1, 1, seq * 3 * sizeof(uint16_t), row, row, call_row, call_row, seq, seq * size_t(kTextStride), prior_row};
   int rc = reserve(c, t, job.chunk, want);
   if (rc != 0) return rc;
   if (io.pl16 && (rc = upload_lut(c)) != 0) return rc;
@@ -164,6 +165,7 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
   job.copy_in(B_PL, size_t(n_seq) * 3 * sizeof(uint16_t), io.pl16);
   if (!io.pl16) job.copy_in(B_LK, row, io.lk);
   job.copy_in(B_FLAGS, 1, io.flags);
+  job.copy_in(B_PRIOR, prior_row, io.prior);  // a chunk's 48 n bytes travel with its likelihoods
   const size_t cr = size_t(3) * n_seq * sizeof(double);
   job.copy_out(B_GPP, cr, io.gpp);
   job.copy_out(B_FPP, cr, io.fpp);
@@ -180,7 +182,9 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
     uint8_t *d_status = io.status || called ? d[B_STATUS].as<uint8_t>() : nullptr;
     const bool need_single = io.single || io.gpp || io.text;
     bool fused = false;
-    if (called && !io.post && !io.single) {
+    // site priors: the sum-product kernel of that form, whatever the engine (the entry has loaded it), between the separate
+    // stages; there is no fused call-path form of it
+    if (called && !io.post && !io.single && !io.prior) {
       hipError_t e = hipSuccess;
       fused = launch_engine_fused(c, n, io.pl16 ? nullptr : d_lk, d_flags, d_status, io.pl16 != nullptr, c->d_call[s].as<CallIO>(), s_k, &e);
       if (fused) HIP_TRY(c, e);
@@ -188,7 +192,11 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
     if (!fused) {
       if (io.pl16)
         HIP_TRY(c, launch_unpack_pl16(d[B_PL].as<uint16_t>(), c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, n_seq, n, d_lk, s_k));
-      HIP_TRY(c, launch_engine(c, n, d_lk, d_flags, d_post, need_single ? d_single : nullptr, d_status, s_k));
+      if (io.prior)
+        HIP_TRY(c, launch_generated(c, c->kern[K_PRIOR], n, d_lk, d_flags, d_post, need_single ? d_single : nullptr, d_status, s_k, 0,
+                                    d[B_PRIOR].as<double>()));
+      else
+        HIP_TRY(c, launch_engine(c, n, d_lk, d_flags, d_post, need_single ? d_single : nullptr, d_status, s_k));
       if (called)
         HIP_TRY(c, launch_phred_call(d_post, d_single, d_status, c->d_seq.as<int32_t>(), N, n_seq, n, d_gpp, d_fpp, d[B_FGT].as<int8_t>(), s_k));
     }

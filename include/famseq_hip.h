@@ -315,6 +315,44 @@ int famseq_map_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk
                             const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, int8_t *d_map_gt,
                             double *d_map_post, uint8_t *d_status, void *stream);
 
+/* ---- founder priors per site -----------------------------------------------------------------------------------------
+ * famseq_bn_batch with the founders' genotype prior given per site — a population allele frequency, say — instead of the
+ * model's genoProbN / genoProbK (genoProbXN / genoProbXK) rows.  prior[n_sites][6], required: doubles 0-2 are the prior
+ * (genotypes 0 / 1 / 2) of female founders and of every founder at an autosomal site, doubles 3-5 the prior of male founders
+ * at a chrX site; they are read at sites with FAMSEQ_FLAG_CHRX only.  Entries must be finite and >= 0 (the host entry checks:
+ * FAMSEQ_E_ARG); a row need not sum to 1.  FAMSEQ_FLAG_KNOWN is not read; FAMSEQ_FLAG_CHRX selects the transmission tables and
+ * the male row as it does for famseq_bn_batch.  Layouts and statuses are famseq_bn_batch's: status 1 where lk * prior sums
+ * to <= 0 for any member (so an all-zero row fails its site), 2 where a network row sum is <= 0, 0x80 the -LRC shortcut;
+ * failed rows are NaN.  Given rows that equal the model's constants the outputs are, bit for bit, those of the sum-product
+ * engine's famseq_bn_batch.
+ * Served by the site-prior form of the sum-product kernel whatever "engine" says, for every pedigree that engine serves
+ * (FAMSEQ_E_ARG with its message otherwise).  The kernel is compiled on the first call, or ahead through famseq_set_option
+ * "prior_kernels" = 1 (a plan-only context generates and cross-compiles it); it takes the variant the sum-product kernel
+ * takes for the pedigree (its measured one, "pick_elim" / "tune", where there is one; else the winner of that
+ * kernel's spill contest, which the first call on an unmeasured pedigree compiles too where the cache does not hold it).  famseq_plan_json: "prior_code_object", "prior_variant". */
+
+/* Host buffers, blocking, chunked and pipelined (a chunk's prior rows travel with its likelihoods).  post_single and status
+ * may be NULL. */
+int famseq_bn_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint8_t *flags, const double *prior,
+                          double *post, double *post_single, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device: enqueues on `stream` (a hipStream_t; NULL = the default stream) and
+ * returns without synchronising.  Nothing is checked of d_prior's contents. */
+int famseq_bn_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint8_t *d_flags,
+                                 const double *d_prior, double *d_post, double *d_single, uint8_t *d_status, void *stream);
+
+/* The call path under site priors (`FamSeq vcf -afTag`): famseq_bn_call_batch's inputs and called outputs (or, with `text`
+ * given, famseq_bn_call_text_batch's records instead of gpp / fpp / fgt) with one prior row per site as above.  Per chunk the
+ * separate stages on the device: PL unpack, the site-prior kernel, Phred scaling and genotype call, text; there is no fused
+ * call-path form of the site-prior kernel. */
+int famseq_bn_prior_call_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const uint8_t *flags,
+                               const double *prior, const int32_t *seq_members, int32_t n_seq, double *gpp, double *fpp, int8_t *fgt,
+                               char *text, uint8_t *status);
+
+/* Hardy-Weinberg rows for the two entries above, on the host: prior[i] = ((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
+ * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
+void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);
+
 /* Diagnostic / test aid: the device formatter alone.  values[n] (host) -> out[n][16] (host): the characters of each
  * value as the text kernel prints a GPP / FPP number from byte 0, their count in byte 15; "nan" for anything outside
  * the formatter's domain, 0 and [1e-16, 999999.5). */
