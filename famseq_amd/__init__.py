@@ -83,6 +83,7 @@ ABI_SYMBOLS = [
     "famseq_call_genotypes", "famseq_trio_children", "famseq_trio_batch", "famseq_trio_batch_device",
     "famseq_map_batch", "famseq_map_batch_device",
     "famseq_bn_prior_batch", "famseq_bn_prior_batch_device", "famseq_bn_prior_call_batch", "famseq_hwe_priors",
+    "famseq_trio_prior_batch", "famseq_trio_prior_batch_device", "famseq_map_prior_batch", "famseq_map_prior_batch_device",
 ]
 PL_MISSING = 0xFFFF
 
@@ -173,6 +174,14 @@ def lib():
     L.famseq_bn_prior_call_batch.restype = C.c_int
     L.famseq_hwe_priors.argtypes = [C.c_int64, dp, dp]
     L.famseq_hwe_priors.restype = None
+    L.famseq_trio_prior_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, dp, dp, dp, bp]
+    L.famseq_trio_prior_batch.restype = C.c_int
+    L.famseq_trio_prior_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp, vp]
+    L.famseq_trio_prior_batch_device.restype = C.c_int
+    L.famseq_map_prior_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, dp, C.POINTER(C.c_int8), dp, bp]
+    L.famseq_map_prior_batch.restype = C.c_int
+    L.famseq_map_prior_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp, vp]
+    L.famseq_map_prior_batch_device.restype = C.c_int
     _lib = L
     return L
 
@@ -189,6 +198,13 @@ def transmission_tables(mrate):
 
 def device_count():
     return lib().famseq_device_count()
+
+
+def _prior_rows(prior, s):
+    prior = np.ascontiguousarray(prior, dtype=np.float64)
+    if prior.shape != (s, 6):
+        raise ValueError("prior must be [n_sites, 6]")
+    return prior
 
 
 def hwe_priors(af):
@@ -405,6 +421,14 @@ class Context:
         joint[s, k, 9 gc + 3 gm + gf] is the posterior of child k's and its parents' genotypes; dnm[s, k] the mass of the
         entries the mutation-free transmission table rules out.  Input is either lk [S,N,3] float64 or pl16 [S,n_seq,3]
         uint16 in VCF column order (seq_members: their PED indices)."""
+        return self._trio(lk, pl16, seq_members, flags, want_joint, want_dnm, None)
+
+    def trio_prior_batch(self, prior, lk=None, pl16=None, seq_members=None, flags=None, want_joint=True, want_dnm=True):
+        """trio_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give trio_batch's bits."""
+        return self._trio(lk, pl16, seq_members, flags, want_joint, want_dnm, prior)
+
+    def _trio(self, lk, pl16, seq_members, flags, want_joint, want_dnm, prior):
         if (lk is None) == (pl16 is None):
             raise ValueError("give exactly one of lk / pl16")
         children = self.trio_children()
@@ -424,11 +448,13 @@ class Context:
         joint = np.empty((s, k, 27)) if want_joint else None
         dnm = np.empty((s, k)) if want_dnm else None
         status = np.zeros(s, np.uint8)
-        rc = lib().famseq_trio_batch(self._h, s, None if lk is None else _p(lk, C.c_double),
-                                     None if pl16 is None else _p(pl16, C.c_uint16), None if seq is None else _p(seq, C.c_int32),
-                                     n_seq, None if fl is None else _p(fl, C.c_uint8), None if joint is None else _p(joint, C.c_double),
-                                     None if dnm is None else _p(dnm, C.c_double), _p(status, C.c_uint8))
-        self._check(rc, "famseq_trio_batch")
+        head = (self._h, s, None if lk is None else _p(lk, C.c_double), None if pl16 is None else _p(pl16, C.c_uint16),
+                None if seq is None else _p(seq, C.c_int32), n_seq, None if fl is None else _p(fl, C.c_uint8))
+        out = (None if joint is None else _p(joint, C.c_double), None if dnm is None else _p(dnm, C.c_double), _p(status, C.c_uint8))
+        if prior is None:
+            self._check(lib().famseq_trio_batch(*head, *out), "famseq_trio_batch")
+        else:
+            self._check(lib().famseq_trio_prior_batch(*head, _p(_prior_rows(prior, s), C.c_double), *out), "famseq_trio_prior_batch")
         return children, joint, dnm, status
 
     def trio_batch_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_joint=0, d_dnm=0, d_status=0, stream=0):
@@ -439,12 +465,28 @@ class Context:
                                             d_dnm or None, d_status or None, stream or None)
         self._check(rc, "famseq_trio_batch_device")
 
+    def trio_prior_batch_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_joint=0, d_dnm=0, d_status=0, stream=0):
+        """trio_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+        rc = lib().famseq_trio_prior_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
+                                                  _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_prior or None,
+                                                  d_joint or None, d_dnm or None, d_status or None, stream or None)
+        self._check(rc, "famseq_trio_prior_batch_device")
+
     def map_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_gt=True, want_post=True):
         """The joint MAP configuration: -> (map_gt[S,N] int8, map_post[S] float64, status[S] uint8).
         map_gt[s] is the most probable genotype assignment of the whole pedigree at site s (0 / 1 / 2 per member, PED order; -1
         where status != 0), map_post[s] its posterior probability (NaN where status != 0).  Input as trio_batch: either lk
         [S,N,3] float64 or pl16 [S,n_seq,3] uint16 in VCF column order (seq_members: their PED indices).  want_gt / want_post
         False: that output is not computed and returned as None."""
+        return self._map(lk, pl16, seq_members, flags, want_gt, want_post, None)
+
+    def map_prior_batch(self, prior, lk=None, pl16=None, seq_members=None, flags=None, want_gt=True, want_post=True):
+        """map_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give map_batch's bits."""
+        return self._map(lk, pl16, seq_members, flags, want_gt, want_post, prior)
+
+    def _map(self, lk, pl16, seq_members, flags, want_gt, want_post, prior):
         if (lk is None) == (pl16 is None):
             raise ValueError("give exactly one of lk / pl16")
         seq, n_seq = None, 0
@@ -462,11 +504,13 @@ class Context:
         gt = np.empty((s, self.n), np.int8) if want_gt else None
         post = np.empty(s) if want_post else None
         status = np.zeros(s, np.uint8)
-        rc = lib().famseq_map_batch(self._h, s, None if lk is None else _p(lk, C.c_double),
-                                    None if pl16 is None else _p(pl16, C.c_uint16), None if seq is None else _p(seq, C.c_int32),
-                                    n_seq, None if fl is None else _p(fl, C.c_uint8), None if gt is None else _p(gt, C.c_int8),
-                                    None if post is None else _p(post, C.c_double), _p(status, C.c_uint8))
-        self._check(rc, "famseq_map_batch")
+        head = (self._h, s, None if lk is None else _p(lk, C.c_double), None if pl16 is None else _p(pl16, C.c_uint16),
+                None if seq is None else _p(seq, C.c_int32), n_seq, None if fl is None else _p(fl, C.c_uint8))
+        out = (None if gt is None else _p(gt, C.c_int8), None if post is None else _p(post, C.c_double), _p(status, C.c_uint8))
+        if prior is None:
+            self._check(lib().famseq_map_batch(*head, *out), "famseq_map_batch")
+        else:
+            self._check(lib().famseq_map_prior_batch(*head, _p(_prior_rows(prior, s), C.c_double), *out), "famseq_map_prior_batch")
         return gt, post, status
 
     def map_batch_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_map_gt=0, d_map_post=0, d_status=0, stream=0):
@@ -477,6 +521,15 @@ class Context:
                                            _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_map_gt or None,
                                            d_map_post or None, d_status or None, stream or None)
         self._check(rc, "famseq_map_batch_device")
+
+    def map_prior_batch_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_map_gt=0, d_map_post=0, d_status=0,
+                               stream=0):
+        """map_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+        rc = lib().famseq_map_prior_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
+                                                 _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_prior or None,
+                                                 d_map_gt or None, d_map_post or None, d_status or None, stream or None)
+        self._check(rc, "famseq_map_prior_batch_device")
 
     def g6_probe(self, values):
         """The device formatter alone (famseq_format_probe): -> list of bytes, one per value."""

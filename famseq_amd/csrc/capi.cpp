@@ -291,6 +291,14 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
     if (value != 1) return fail(c, FAMSEQ_E_ARG, "prior_kernels takes 1");
     return load_or_fail(c, K_PRIOR);
   }
+  else if (k == "trio_prior_kernels") {  // ... and of the trio and MAP kernels' site-prior forms
+    if (value < 1 || value > 3) return fail(c, FAMSEQ_E_ARG, "trio_prior_kernels takes 1 (dnm), 2 (joint) or 3 (both)");
+    return load_or_fail(c, K_TRIO_PRIOR + (int)value - 1);
+  }
+  else if (k == "map_prior_kernels") {
+    if (value != 1) return fail(c, FAMSEQ_E_ARG, "map_prior_kernels takes 1");
+    return load_or_fail(c, K_MAP_PRIOR);
+  }
   else if (k == "group_digits") {
     if (value < -1 || value > enumgen_max_group_digits(c->model))
       return fail(c, FAMSEQ_E_ARG, "group_digits must be -1 (auto) or 0.." + std::to_string(enumgen_max_group_digits(c->model)) +
@@ -345,13 +353,16 @@ std::string json_str(const std::string &v) {  // paths may hold quotes or backsl
 }
 // the trio kernels (famseq_trio_batch): the code object of the form used last, every form's, the variant the contest took
 std::string trio_json(const famseq_ctx *c) {
-  const int f = c->trio_last;
+  const int f = c->trio_last, fp = c->trio_prior_last;
   std::string o = ",\"trio_code_object\":\"" + json_str(f ? c->trio(f).k.path : std::string()) + "\",\"trio_code_objects\":[";
   for (int k = 1; k <= 3; ++k) o += std::string(k > 1 ? "," : "") + "\"" + json_str(c->trio(k).k.path) + "\"";
   return o + "],\"trio_variant\":" + std::to_string(f ? c->trio(f).variant : -1) + ",\"trio_children\":" +
          std::to_string(trio_children(c->model).size()) + ",\"map_code_object\":\"" + json_str(c->kern[K_MAP].k.path) + "\",\"map_variant\":" +
          std::to_string(c->kern[K_MAP].variant) + ",\"prior_code_object\":\"" + json_str(c->kern[K_PRIOR].k.path) + "\",\"prior_variant\":" +
-         std::to_string(c->kern[K_PRIOR].variant);
+         std::to_string(c->kern[K_PRIOR].variant) + ",\"trio_prior_code_object\":\"" +
+         json_str(fp ? c->kern[K_TRIO_PRIOR + fp - 1].k.path : std::string()) + "\",\"trio_prior_variant\":" +
+         std::to_string(fp ? c->kern[K_TRIO_PRIOR + fp - 1].variant : -1) + ",\"map_prior_code_object\":\"" +
+         json_str(c->kern[K_MAP_PRIOR].k.path) + "\",\"map_prior_variant\":" + std::to_string(c->kern[K_MAP_PRIOR].variant);
 }
 }  // namespace
 
@@ -447,7 +458,7 @@ extern "C" void famseq_hwe_priors(int64_t n, const double *af, double *prior) {
 
 namespace {
 // What the host entries ask of the prior rows, and the kernel they run.
-int prior_ready(famseq_ctx *c, int64_t n_sites, const uint8_t *flags, const double *prior) {
+int prior_ready(famseq_ctx *c, int64_t n_sites, const uint8_t *flags, const double *prior, int kind = K_PRIOR) {
   if (n_sites > 0 && !prior) return fail(c, FAMSEQ_E_ARG, "prior must be given (six doubles per site)");
   if (c->device < 0) return fail(c, FAMSEQ_E_NODEVICE, kNoDevice);
   for (int64_t s = 0; s < n_sites; ++s)  // (the male chrX row is read at chrX sites only)
@@ -455,7 +466,7 @@ int prior_ready(famseq_ctx *c, int64_t n_sites, const uint8_t *flags, const doub
       if (!(prior[6 * s + k] >= 0 && prior[6 * s + k] <= 1.79769313486231570815e308))
         return fail(c, FAMSEQ_E_ARG, "prior entries must be finite and >= 0 (site " + std::to_string(s) + ")");
   HIP_TRY(c, hipSetDevice(c->device));
-  return load_or_fail(c, K_PRIOR);
+  return load_or_fail(c, kind);
 }
 }  // namespace
 
@@ -716,10 +727,11 @@ int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl
   return 0;
 }
 
-// The device entries of both: enqueue kernel `kind` on the caller's stream and return.  Packed input is unpacked into likelihood
+// The device entries of both, plain and site-prior (d_prior): enqueue kernel `kind` on the caller's stream and return.  Packed input is unpacked into likelihood
 // rows this context keeps (grown on demand).
 int side_batch_device(famseq_ctx *c, int kind, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16, const int32_t *seq_members,
-                      int32_t n_seq, const uint8_t *d_flags, void *d_out_a, void *d_out_b, uint8_t *d_status, hipStream_t stream) {
+                      int32_t n_seq, const uint8_t *d_flags, void *d_out_a, void *d_out_b, uint8_t *d_status, hipStream_t stream,
+                      const double *d_prior = nullptr) {
   const int rc = trio_prologue(c, n_sites, d_lk, d_pl16, seq_members, n_seq, kind);
   if (rc != 0 || n_sites == 0) return rc;
   if (d_pl16) {
@@ -733,7 +745,7 @@ int side_batch_device(famseq_ctx *c, int kind, int64_t n_sites, const double *d_
     d_lk = c->trio_dev_lk.as<double>();
     HIP_TRY(c, launch_unpack_pl16(d_pl16, c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, n_seq, n_sites, c->trio_dev_lk.as<double>(), stream));
   }
-  HIP_TRY(c, launch_generated(c, c->kern[kind], n_sites, d_lk, d_flags, d_out_a, d_out_b, d_status, stream));
+  HIP_TRY(c, launch_generated(c, c->kern[kind], n_sites, d_lk, d_flags, d_out_a, d_out_b, d_status, stream, 0, d_prior));
   return 0;
 }
 
@@ -775,4 +787,48 @@ extern "C" int famseq_map_batch_device(famseq_ctx *c, int64_t n_sites, const dou
   if (!c) return FAMSEQ_E_ARG;
   return side_batch_device(c, K_MAP, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_map_gt, d_map_post, d_status,
                            static_cast<hipStream_t>(stream));
+}
+
+// ---- founder priors per site for both ---------------------------------------------------------------------------------
+
+extern "C" int famseq_trio_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                       int32_t n_seq, const uint8_t *flags, const double *prior, double *joint, double *dnm,
+                                       uint8_t *status) {
+  if (!c) return FAMSEQ_E_ARG;
+  const int kind = K_TRIO_PRIOR + trio_form(joint, dnm) - 1;
+  int rc = check_input(c, n_sites, lk, pl16, "lk / pl16", false, n_seq);
+  if (rc != 0 || (rc = prior_ready(c, n_sites, flags, prior, kind)) != 0) return rc;
+  if ((rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, kind)) != 0 || n_sites == 0) return rc;
+  const size_t K = trio_children(c->model).size();
+  return side_batch(c, c->trio_slots, c->kern[kind], n_sites, lk, pl16, n_seq, flags, joint, 27 * K * sizeof(double), dnm, K * sizeof(double), status,
+                    prior);
+}
+
+extern "C" int famseq_trio_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                              const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                              double *d_joint, double *d_dnm, uint8_t *d_status, void *stream) {
+  if (!c) return FAMSEQ_E_ARG;
+  if (n_sites > 0 && !d_prior) return fail(c, FAMSEQ_E_ARG, "d_prior must be given (six doubles per site)");
+  return side_batch_device(c, K_TRIO_PRIOR + trio_form(d_joint, d_dnm) - 1, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_joint, d_dnm,
+                           d_status, static_cast<hipStream_t>(stream), d_prior);
+}
+
+extern "C" int famseq_map_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                      int32_t n_seq, const uint8_t *flags, const double *prior, int8_t *map_gt, double *map_post,
+                                      uint8_t *status) {
+  if (!c) return FAMSEQ_E_ARG;
+  int rc = check_input(c, n_sites, lk, pl16, "lk / pl16", false, n_seq);
+  if (rc != 0 || (rc = prior_ready(c, n_sites, flags, prior, K_MAP_PRIOR)) != 0) return rc;
+  if ((rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, K_MAP_PRIOR)) != 0 || n_sites == 0) return rc;
+  return side_batch(c, c->map_slots, c->kern[K_MAP_PRIOR], n_sites, lk, pl16, n_seq, flags, map_gt, size_t(c->model.n_members), map_post,
+                    sizeof(double), status, prior);
+}
+
+extern "C" int famseq_map_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                             const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                             int8_t *d_map_gt, double *d_map_post, uint8_t *d_status, void *stream) {
+  if (!c) return FAMSEQ_E_ARG;
+  if (n_sites > 0 && !d_prior) return fail(c, FAMSEQ_E_ARG, "d_prior must be given (six doubles per site)");
+  return side_batch_device(c, K_MAP_PRIOR, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_map_gt, d_map_post, d_status,
+                           static_cast<hipStream_t>(stream), d_prior);
 }

@@ -63,6 +63,8 @@ enum KernelKind {
   K_TRIO,                                          // K_TRIO + form - 1: trio posteriors per output form (1 dnm, 2 joint, 3 both)
   K_MAP = K_TRIO + 3,                              // the joint MAP configuration
   K_PRIOR,                                         // the sum-product kernel with the founders' prior per site (famseq_bn_prior_batch)
+  K_TRIO_PRIOR,                                    // K_TRIO_PRIOR + form - 1: the trio kernels with the founders' prior per site
+  K_MAP_PRIOR = K_TRIO_PRIOR + 3,                  // ... and the MAP kernel
   K_COUNT
 };
 
@@ -125,6 +127,7 @@ struct famseq_ctx {
   int group_digits = -1, last_group_digits = 0;
   int lane_reads_rows = -1;  // does the lane call-path kernel re-read fp64 rows from global memory (unknown until it is built)
   int trio_last = 0;         // the trio output form asked for last (famseq_plan_json)
+  int trio_prior_last = 0;   // ... and of the site-prior trio kernels
   int64_t lane_min_sites = 256;  // below this the compiled-in team kernel answers at once (no per-pedigree compile for tiny calls) ...
   // ... unless the generated kernel for that batch is loaded or on disk already (a pre-built pedigree, or one this user has run
   // before): then nothing has to be waited for and it serves every batch size (team kernel: 0.0237 ms per 256 ten-member
@@ -170,7 +173,7 @@ inline int fail(famseq_ctx *c, int code, const std::string &msg) {
   } while (0)
 
 // ---- kernels.cpp ----
-// The sum-product family (K_ELIM, K_TRIO + form - 1, K_MAP, K_PRIOR): 0, or an error (FAMSEQ_E_ARG: the engine does not serve this
+// The sum-product family (K_ELIM, K_TRIO + form - 1, K_MAP, K_PRIOR, K_TRIO_PRIOR + form - 1, K_MAP_PRIOR): 0, or an error (FAMSEQ_E_ARG: the engine does not serve this
 // pedigree; FAMSEQ_E_HIP) that is not remembered, the next call tries again.
 int load_or_fail(famseq_ctx *c, int kind);
 // The lane kinds and both call-path forms: false when the kernel is unavailable, which is remembered and said once on
@@ -204,8 +207,9 @@ CallIO make_call_io(const famseq_ctx *c, const uint16_t *d_pl, double *d_gpp, do
                     unsigned long long *d_phase_clk = nullptr);
 int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq);
 // The trio and MAP host entries: lk or packed PLs through kernel `g`, whose two outputs have a_row / b_row bytes per site.
+// prior: the site-prior forms' rows [n_sites][6], staged chunk by chunk alongside the likelihoods (NULL: the plain forms).
 int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
-               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status);
+               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior = nullptr);
 
 }  // namespace famseq
 #endif

@@ -1414,24 +1414,33 @@ std::string direct_shell(const Model &m, const std::string &comment, const std::
 // The trio kernel's shell: direct_shell's form (a lane reads its site's row straight from global memory, 3.4 KB of LDS whatever
 // the pedigree's size), no single posterior stored and no shortcut: every site that passes the single-posterior rule runs the
 // full network.  Outputs per site: joint[27 K] and dnm[K] (either may be null), status.
+// site_prior (famseq_trio_prior): direct_shell's form of it — the lane's row of prior_g in three 16-byte loads issued beside the
+// likelihood loads, the Known bit not read.
 std::string trio_shell(const Model &m, const std::string &comment, const std::string &body, int K, bool want_dnm, bool want_joint, int bt,
-                       bool fence_single, bool chrx_loop, bool lean) {
+                       bool fence_single, bool chrx_loop, bool lean, bool site_prior = false) {
   const int N = m.n_members, W3 = 3 * N;
+  // the lane's prior row is asked for before its likelihoods; FAMSEQ_PRIOR_LATE=1 (tuning aid): after them
+  bool prior_late = false;
+  if (const char *e = std::getenv("FAMSEQ_PRIOR_LATE")) prior_late = std::atoi(e) != 0;
   std::ostringstream s;
   s << "// generated by famseq_amd/csrc for a " << N << "-member pedigree: " << comment << "\n"
     << "#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n#pragma clang fp contract(off)\n"
     << "#define W3 " << W3 << "\n#define BT " << bt << "\n#define NKID " << K << "\n"
     << "#define LDS_BARRIER() asm volatile(\"s_waitcnt lgkmcnt(0)\\n\\ts_barrier\" ::: \"memory\")\n"
     << kDiv3Text;
+  if (site_prior) s << "typedef double v2d __attribute__((ext_vector_type(2)));\n" << kPriorLoad;
   if (lean)
     for (int p = 0; p < N; ++p)
       for (int gt = 0; gt < 3; ++gt) s << "#define l" << p << "_" << gt << " lgv[" << 3 * p + gt << "]\n";
-  s << "extern \"C\" __global__ __launch_bounds__(BT, 1) void famseq_trio(const double *__restrict__ lk_g,\n"
+  s << "extern \"C\" __global__ __launch_bounds__(BT, 1) void " << (site_prior ? "famseq_trio_prior" : "famseq_trio")
+    << "(const double *__restrict__ lk_g,\n"
     << "    const unsigned char *__restrict__ flags_g, double *__restrict__ joint_g, double *__restrict__ dnm_g,\n"
-    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc) {\n"
+    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc"
+    << (site_prior ? ", const double *__restrict__ prior_g" : "") << ") {\n"
     << "  __shared__ double s_tc[432];\n"
     << "  const int tid = threadIdx.x;\n"
     << "  for (int i = tid; i < 432; i += BT) s_tc[i] = tc_g[i];\n"
+    << (site_prior ? "  const bool p16 = ((unsigned long)prior_g & 15) == 0;\n  v2d pu0, pu1, pu2;\n" : "")
     << "  LDS_BARRIER();\n"
     << "  const long chunks = (n_sites + BT - 1) / BT;\n"
     << "  const long q_wg = chunks / gridDim.x, r_wg = chunks - q_wg * gridDim.x;\n"
@@ -1446,18 +1455,21 @@ std::string trio_shell(const Model &m, const std::string &comment, const std::st
     << (want_joint ? "    double *jg = joint_g ? joint_g + site * (27 * NKID) : nullptr;\n" : "    double *const jg = nullptr;\n")
     << (want_dnm ? "    double *dg = dnm_g ? dnm_g + site * NKID : nullptr;\n" : "    double *const dg = nullptr;\n")
     << "    (void)jg; (void)dg;\n"
-    << "    const int fl = flags_g ? (flags_g[site] & 3) : 0;\n"
+    // (site priors: the Known bit chooses between two rows of the model that this kernel does not read)
+    << "    const int fl = flags_g ? (flags_g[site] & " << (site_prior ? 2 : 3) << ") : 0;\n"
     << "    const bool xchr_ = (fl & 2) != 0;\n"
     << "    const double *tcf = s_tc + fl * 108;\n"
     << "    bool single_fail = false, full = false, bn_fail = false;\n"
-    << "    (void)full;\n";
+    << "    (void)full;\n"
+    << (site_prior && !prior_late ? "    PRIOR_LOAD(site);\n" : "");
   if (lean)
     s << "    typedef const volatile __attribute__((address_space(1))) double glb_cvd;\n    glb_cvd *lgv = (glb_cvd *)lg;\n";
   else
     for (int p = 0; p < N; ++p)
       for (int gt = 0; gt < 3; ++gt) s << "    const double l" << p << "_" << gt << " = lg[" << 3 * p + gt << "];\n";
+  if (site_prior) s << (prior_late ? "    PRIOR_LOAD(site);\n" : "") << kPriorNames;
   // the single-posterior failure rule only (a lk * prior row sum <= 0): nothing of the single posterior is stored
-  s << single_posterior_statements(m, true, false, fence_single);
+  s << single_posterior_statements(m, true, false, fence_single, "row", site_prior);
   if (chrx_loop)
     s << "    {\n"
       << "#pragma unroll 1\n"
@@ -1482,26 +1494,34 @@ std::string trio_shell(const Model &m, const std::string &comment, const std::st
 // lane's genotype row is N bytes at a stride of N bytes, which no lane can store in aligned words on its own: the rows of a
 // workgroup's BT consecutive sites are staged in LDS (BT * N bytes) and written out together, a wave's stores contiguous —
 // in 32-bit words where the block's first byte is 4-aligned, in bytes otherwise.
+// site_prior (famseq_map_prior): as trio_shell's.
 std::string map_shell(const Model &m, const std::string &comment, const std::string &body, int bt, bool fence_single, bool chrx_loop,
-                      bool lean) {
+                      bool lean, bool site_prior = false) {
   const int N = m.n_members, W3 = 3 * N, nw = (N + 3) / 4;
+  // the lane's prior row is asked for before its likelihoods; FAMSEQ_PRIOR_LATE=1 (tuning aid): after them
+  bool prior_late = false;
+  if (const char *e = std::getenv("FAMSEQ_PRIOR_LATE")) prior_late = std::atoi(e) != 0;
   std::ostringstream s;
   s << "// generated by famseq_amd/csrc for a " << N << "-member pedigree: " << comment << "\n"
     << "#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n#pragma clang fp contract(off)\n"
     << "#define W3 " << W3 << "\n#define BT " << bt << "\n#define NMEM " << N << "\n"
     << "#define LDS_BARRIER() asm volatile(\"s_waitcnt lgkmcnt(0)\\n\\ts_barrier\" ::: \"memory\")\n"
     << kDiv3Text;
+  if (site_prior) s << "typedef double v2d __attribute__((ext_vector_type(2)));\n" << kPriorLoad;
   if (lean)
     for (int p = 0; p < N; ++p)
       for (int gt = 0; gt < 3; ++gt) s << "#define l" << p << "_" << gt << " lgv[" << 3 * p + gt << "]\n";
-  s << "extern \"C\" __global__ __launch_bounds__(BT, 1) void famseq_map(const double *__restrict__ lk_g,\n"
+  s << "extern \"C\" __global__ __launch_bounds__(BT, 1) void " << (site_prior ? "famseq_map_prior" : "famseq_map")
+    << "(const double *__restrict__ lk_g,\n"
     << "    const unsigned char *__restrict__ flags_g, signed char *__restrict__ gt_g, double *__restrict__ post_g,\n"
-    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc) {\n"
+    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc"
+    << (site_prior ? ", const double *__restrict__ prior_g" : "") << ") {\n"
     << "  __shared__ double s_tc[432];\n"
     << "  __shared__ unsigned s_gt[(BT * NMEM + 3) / 4];  // the workgroup's genotype rows, as they lie in map_gt\n"
     << "  unsigned char *const s_gb = (unsigned char *)s_gt;\n"
     << "  const int tid = threadIdx.x;\n"
     << "  for (int i = tid; i < 432; i += BT) s_tc[i] = tc_g[i];\n"
+    << (site_prior ? "  const bool p16 = ((unsigned long)prior_g & 15) == 0;\n  v2d pu0, pu1, pu2;\n" : "")
     << "  LDS_BARRIER();\n"
     << "  const long chunks = (n_sites + BT - 1) / BT;\n"
     << "  const long q_wg = chunks / gridDim.x, r_wg = chunks - q_wg * gridDim.x;\n"
@@ -1512,21 +1532,22 @@ std::string map_shell(const Model &m, const std::string &comment, const std::str
     // a lane beyond the batch's end works on the last site: the same values to the same addresses as that site's own lane
     << "    const long site = ch * BT + tid < n_sites ? ch * BT + tid : n_sites - 1;\n"
     << "    const double *lg = lk_g + site * W3;\n"
-    << "    const int fl = flags_g ? (flags_g[site] & 3) : 0;\n"
+    << "    const int fl = flags_g ? (flags_g[site] & " << (site_prior ? 2 : 3) << ") : 0;\n"
     << "    const bool xchr_ = (fl & 2) != 0;\n"
     << "    const double *tcf = s_tc + fl * 108;\n"
     << "    bool single_fail = false, full = false, bn_fail = false;\n"
     << "    (void)full;\n"
     << "    double map_p = kNaN;\n    unsigned";
   for (int k = 0; k < nw; ++k) s << (k ? ", " : " ") << "gw" << k << " = 0xffffffffu";
-  s << ";\n";
+  s << ";\n" << (site_prior && !prior_late ? "    PRIOR_LOAD(site);\n" : "");
   if (lean)
     s << "    typedef const volatile __attribute__((address_space(1))) double glb_cvd;\n    glb_cvd *lgv = (glb_cvd *)lg;\n";
   else
     for (int p = 0; p < N; ++p)
       for (int gt = 0; gt < 3; ++gt) s << "    const double l" << p << "_" << gt << " = lg[" << 3 * p + gt << "];\n";
+  if (site_prior) s << (prior_late ? "    PRIOR_LOAD(site);\n" : "") << kPriorNames;
   // the single-posterior failure rule only (a lk * prior row sum <= 0): nothing of the single posterior is stored
-  s << single_posterior_statements(m, true, false, fence_single);
+  s << single_posterior_statements(m, true, false, fence_single, "row", site_prior);
   if (chrx_loop)
     s << "    {\n"
       << "#pragma unroll 1\n"
@@ -1576,7 +1597,7 @@ std::vector<int> trio_children(const Model &m) {
   return kids;
 }
 
-std::string trio_source(const Model &m, int variant, int form) {
+std::string trio_source(const Model &m, int variant, int form, bool site_prior) {
   Graph g;
   std::string why;
   if (!build_graph(m, g, &why)) throw std::runtime_error("elimination engine: " + why);
@@ -1599,12 +1620,12 @@ std::string trio_source(const Model &m, int variant, int form) {
   const std::string what = "trio posteriors (" + std::string(want_dnm && want_joint ? "de novo + joint" : (want_dnm ? "de novo" : "joint")) +
                            ") over " + std::to_string(g.fam.size()) + " nuclear families" +
                            (g.cut.empty() ? "" : ", conditioned on " + std::to_string(g.cut.size()) + " member(s)") + ", variant " +
-                           std::to_string(f);
-  return trio_shell(m, what, Emitter(m, g, f < 2 ? f : 2, /*scalar_t=*/f >= 1, "pg", lean).trio_body(kids, mask, want_joint),
-                    (int)kids.size(), want_dnm, want_joint, elim_block_threads(m, false), f >= 3, /*chrx_loop=*/f >= 1, lean);
+                           std::to_string(f) + (site_prior ? ", founder priors per site" : "");
+  return trio_shell(m, what, Emitter(m, g, f < 2 ? f : 2, /*scalar_t=*/f >= 1, "pg", lean, 1 << 30, site_prior).trio_body(kids, mask, want_joint),
+                    (int)kids.size(), want_dnm, want_joint, elim_block_threads(m, false), f >= 3, /*chrx_loop=*/f >= 1, lean, site_prior);
 }
 
-std::string map_source(const Model &m, int variant) {
+std::string map_source(const Model &m, int variant, bool site_prior) {
   Graph g;
   std::string why;
   if (!build_graph(m, g, &why)) throw std::runtime_error("elimination engine: " + why);
@@ -1613,9 +1634,9 @@ std::string map_source(const Model &m, int variant) {
   const bool lean = m.n_members >= 40;  // as trio_source
   const std::string what = "joint MAP configuration (max-product) over " + std::to_string(g.fam.size()) + " nuclear families" +
                            (g.cut.empty() ? "" : ", conditioned on " + std::to_string(g.cut.size()) + " member(s)") + ", variant " +
-                           std::to_string(f);
-  return map_shell(m, what, Emitter(m, g, f < 2 ? f : 2, /*scalar_t=*/f >= 1, "pg", lean).map_body(), elim_block_threads(m, false),
-                   f >= 3, /*chrx_loop=*/f >= 1, lean);
+                           std::to_string(f) + (site_prior ? ", founder priors per site" : "");
+  return map_shell(m, what, Emitter(m, g, f < 2 ? f : 2, /*scalar_t=*/f >= 1, "pg", lean, 1 << 30, site_prior).map_body(), elim_block_threads(m, false),
+                   f >= 3, /*chrx_loop=*/f >= 1, lean, site_prior);
 }
 
 namespace {

@@ -47,7 +47,9 @@ std::vector<int> trio_children(const Model &m);
 // where the mutation-free transmission table is 0.  form: 1 dnm only, 2 joint only, 3 both (what is not in the form is never
 // written).  variant 0..3: the fence levels of famseq_elim's (kTrioVariants).  Throws if the engine does not serve the pedigree.
 constexpr int kTrioVariants = 4;
-std::string trio_source(const Model &m, int variant, int form);
+// site_prior: the entry point is famseq_trio_prior, with a trailing `prior` [n_sites][6] as famseq_elim_prior takes it (see
+// prior_source): the founders' prior is the site's row, the Known bit is not read; every other statement is famseq_trio's.
+std::string trio_source(const Model &m, int variant, int form, bool site_prior = false);
 
 // The joint MAP configuration (famseq_map_batch).  HIP source of
 // `extern "C" __global__ famseq_map(lk, flags, map_gt, map_post, status, n_sites, tc, lc)`: per site the most probable joint
@@ -55,7 +57,8 @@ std::string trio_source(const Model &m, int variant, int form);
 // w(g); the same graph as famseq_elim under the (max, x) semiring with back-pointers, Z from the sum pass.  variant 0..3: the
 // fence levels of famseq_elim's.  Throws if the engine does not serve the pedigree.
 constexpr int kMapVariants = 4;
-std::string map_source(const Model &m, int variant);
+// site_prior: famseq_map_prior, with a trailing `prior` [n_sites][6] (as trio_source's).
+std::string map_source(const Model &m, int variant, bool site_prior = false);
 
 // Shared shell of the generated kernels (see elim_codegen.cpp).
 extern const std::string kCallHelpers;  // fused call path: fs_phred, STAGE_IN_PL, STAGE_OUT_CALL, STAGE_FGT

@@ -3,7 +3,7 @@
 // Keeps the reference's CLI and file surface for the `-method 1` path:
 //   FamSeq vcf -vcfFile f -pedFile p -output o [-v] [-a] [-d] [-o] [-l loc] [-method 1]
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
-//              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-afTag KEY]
+//              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-afTag KEY | -afTagAll KEY]
 //   FamSeq LK  -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -190,6 +190,8 @@ struct Options {
   bool dnm = false;  // -dnm: a DNP field per sample (vcf mode)
   bool map = false;  // -map: JGT and JP fields per sample (vcf mode)
   string af_tag;     // -afTag KEY: the founders' prior of a line from the allele frequency KEY= of its INFO column (vcf mode)
+  bool af_conflict = false;  // both -afTag and -afTagAll were given
+  bool af_all = false;  // -afTagAll KEY: -afTag KEY, applied to every field a line prints (DNP, JGT and JP too: may go with -dnm / -map)
 };
 
 // returns 0 good, 1 warnings, -1 stop (checkInput.h:345-349)
@@ -321,14 +323,17 @@ int parse_options(int argc, char **argv, Options &o) {
       o.dnm = true;
     } else if (opt == "map") {
       o.map = true;
-    } else if (opt == "afTag") {
+    } else if (opt == "afTag" || opt == "afTagAll") {
       i++;
       if (missing(i)) {
-        std::cout << "The INFO key of -afTag hasn't been set. The option is ignored." << std::endl;
+        std::cout << "The INFO key of -" << opt << " hasn't been set. The option is ignored." << std::endl;
         i--;
         rv = 1;
+      } else if (!o.af_tag.empty() && o.af_all != (opt == "afTagAll")) {
+        o.af_conflict = true;
       } else {
         o.af_tag = argv[i];
+        o.af_all = opt == "afTagAll";
       }
     } else if (opt == "LRC") {
       i++;
@@ -698,7 +703,7 @@ bool map_supported(const Options &o, const Ped &ped) {
   return k >= 0;
 }
 
-// -afTag: and for the site-prior kernel.
+// -afTag / -afTagAll: and for the site-prior kernels.
 bool af_supported(const Options &o, const Ped &ped) {
   CliModel m;
   vector<uint8_t> all(ped.n(), 1);
@@ -706,7 +711,7 @@ bool af_supported(const Options &o, const Ped &ped) {
   char err[512] = {0};
   famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
   const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;  // (elim_supported, as above)
-  if (k < 0) std::cout << "-afTag cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
+  if (k < 0) std::cout << (o.af_all ? "-afTagAll" : "-afTag") << " cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
   famseq_destroy(probe);
   return k >= 0;
 }
@@ -1304,7 +1309,9 @@ bool run_vcf(const Options &o, const Ped &ped) {
     fout << "##FS genotype frequency in population (Common): "; put_triple(fout, m.p.genoProbK); fout << std::endl;
     fout << "##FS genotype frequency for chromosome X of male in population (Rare): "; put_triple(fout, m.p.genoProbXN); fout << std::endl;
     fout << "##FS genotype frequency for chromosome X of male in population (Common): "; put_triple(fout, m.p.genoProbXK); fout << std::endl;
-    if (use_af) fout << "##FS genotype frequency of a site with 0 < " << o.af_tag << " < 1 in INFO: Hardy-Weinberg at that allele frequency" << std::endl;
+    if (use_af)
+      fout << "##FS genotype frequency of a site with 0 < " << o.af_tag << " < 1 in INFO: Hardy-Weinberg at that allele frequency"
+           << (o.af_all ? " (-afTagAll: for every field of the line)" : "") << std::endl;
   };
   string title;
   std::string_view line;
@@ -1624,20 +1631,29 @@ bool run_vcf(const Options &o, const Ped &ped) {
         }
         if (o.dnm && flush_ok) {  // the same batch through the trio kernel (full network, whatever -LRC and -method say)
           sl.dnm.resize(sl.n_sites * size_t(n_kids)), sl.tstatus.resize(sl.n_sites);
-          const int rt = famseq_trio_batch(ctx, (int64_t)sl.n_sites, sl.packed ? nullptr : sl.lk.data(), sl.packed ? sl.io.pl : nullptr,
-                                           seq_members.data(), (int32_t)n_seq, sl.io.flags, nullptr, n_kids ? sl.dnm.data() : nullptr,
-                                           sl.tstatus.data());
+          // (-afTagAll: under the rows FPP and FGT were computed with)
+          const double *tlk = sl.packed ? nullptr : sl.lk.data();
+          const uint16_t *tpl = sl.packed ? sl.io.pl : nullptr;
+          double *dnm_out = n_kids ? sl.dnm.data() : nullptr;
+          const int rt = use_af ? famseq_trio_prior_batch(ctx, (int64_t)sl.n_sites, tlk, tpl, seq_members.data(), (int32_t)n_seq, sl.io.flags,
+                                                          sl.prior.data(), nullptr, dnm_out, sl.tstatus.data())
+                                : famseq_trio_batch(ctx, (int64_t)sl.n_sites, tlk, tpl, seq_members.data(), (int32_t)n_seq, sl.io.flags, nullptr,
+                                                    dnm_out, sl.tstatus.data());
           if (rt != 0) {
-            std::cerr << "famseq_trio_batch failed (" << rt << "): " << famseq_last_error(ctx) << std::endl;
+            std::cerr << (use_af ? "famseq_trio_prior_batch" : "famseq_trio_batch") << " failed (" << rt << "): " << famseq_last_error(ctx) << std::endl;
             flush_ok = false;
           }
         }
         if (o.map && flush_ok) {  // and through the MAP kernel (full network as well)
           sl.jgt.resize(sl.n_sites * size_t(ped.n())), sl.jp.resize(sl.n_sites), sl.jstatus.resize(sl.n_sites);
-          const int rm = famseq_map_batch(ctx, (int64_t)sl.n_sites, sl.packed ? nullptr : sl.lk.data(), sl.packed ? sl.io.pl : nullptr,
-                                          seq_members.data(), (int32_t)n_seq, sl.io.flags, sl.jgt.data(), sl.jp.data(), sl.jstatus.data());
+          const double *mlk = sl.packed ? nullptr : sl.lk.data();
+          const uint16_t *mpl = sl.packed ? sl.io.pl : nullptr;
+          const int rm = use_af ? famseq_map_prior_batch(ctx, (int64_t)sl.n_sites, mlk, mpl, seq_members.data(), (int32_t)n_seq, sl.io.flags,
+                                                         sl.prior.data(), sl.jgt.data(), sl.jp.data(), sl.jstatus.data())
+                                : famseq_map_batch(ctx, (int64_t)sl.n_sites, mlk, mpl, seq_members.data(), (int32_t)n_seq, sl.io.flags,
+                                                   sl.jgt.data(), sl.jp.data(), sl.jstatus.data());
           if (rm != 0) {
-            std::cerr << "famseq_map_batch failed (" << rm << "): " << famseq_last_error(ctx) << std::endl;
+            std::cerr << (use_af ? "famseq_map_prior_batch" : "famseq_map_batch") << " failed (" << rm << "): " << famseq_last_error(ctx) << std::endl;
             flush_ok = false;
           }
         }
@@ -2039,6 +2055,8 @@ void help() {
             << "-LRC\t\tLikelihood ratio criterion for the single-sample shortcut. Default 1." << std::endl
             << "-afTag KEY\t(vcf) Founders' genotype prior per line: Hardy-Weinberg at the allele frequency KEY= of the INFO column (the first" << std::endl
             << "\t\tvalue of a list), where it lies in (0, 1); the model's priors elsewhere. Implies -method 2; not with -dnm / -map." << std::endl
+            << "-afTagAll KEY\t(vcf) -afTag KEY for every field the line prints: DNP, JGT and JP are computed under the line's prior too." << std::endl
+            << "\t\tMay be combined with -dnm and -map; not with -afTag. Implies -method 2." << std::endl
             << "-dnm\t\t(vcf) Add DNP, each child's posterior probability of a de novo mutation, to every sample column." << std::endl
             << "-map\t\t(vcf) Add JGT and JP, each member's genotype in the most probable joint configuration of the family and" << std::endl
             << "\t\tthat configuration's posterior probability, to every sample column." << std::endl
@@ -2099,11 +2117,15 @@ int main(int argc, char **argv) {
   if (o.dnm && mode == "vcf" && !dnm_supported(o, ped)) return 255;
   if (o.map && mode != "vcf") std::cout << "-map applies to vcf mode only; ignored here." << std::endl;
   if (o.map && mode == "vcf" && !map_supported(o, ped)) return 255;
+  if (o.af_conflict) {
+    std::cout << "-afTag and -afTagAll cannot be combined: give the INFO key once." << std::endl;
+    return -1;
+  }
   if (!o.af_tag.empty()) {
     if (mode != "vcf") {
-      std::cout << "-afTag applies to vcf mode only; ignored here." << std::endl;
+      std::cout << (o.af_all ? "-afTagAll" : "-afTag") << " applies to vcf mode only; ignored here." << std::endl;
       o.af_tag.clear();
-    } else if (o.dnm || o.map) {
+    } else if (!o.af_all && (o.dnm || o.map)) {
       std::cout << "-afTag cannot be combined with -dnm or -map: their kernels use the model's priors, and one output line must not mix two models."
                 << std::endl;
       return -1;

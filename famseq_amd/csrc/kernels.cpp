@@ -27,6 +27,7 @@ struct KernelSpec {
 
 bool is_lane(int kind) { return kind >= K_LANE && kind <= K_LANE + kEnumMaxGroupDigits; }
 bool is_trio(int kind) { return kind >= K_TRIO && kind < K_TRIO + 3; }
+bool is_trio_prior(int kind) { return kind >= K_TRIO_PRIOR && kind < K_TRIO_PRIOR + 3; }
 
 KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
   const Model &m = c->model;
@@ -37,6 +38,11 @@ KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
   if (is_trio(kind)) {
     const int form = kind - K_TRIO + 1;
     return {[&m, form](int v) { return trio_source(m, v, form); }, kTrioVariants, 0, false, "famseq_trio", elim_block_threads(m)};
+  }
+  if (is_trio_prior(kind)) {  // the variant famseq_trio of that form takes for the pedigree (its contest): none of its own, as K_PRIOR
+    const int form = kind - K_TRIO_PRIOR + 1;
+    return {[&m, form](int v) { return trio_source(m, v, form, true); }, kTrioVariants, 0, false, "famseq_trio_prior", elim_block_threads(m),
+            [&m, form](int v) { return trio_source(m, v, form); }};
   }
   switch (kind) {
     case K_LANE_CALL: {
@@ -57,6 +63,9 @@ KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
     case K_PRIOR:  // the variant famseq_elim takes for the pedigree (its measured pick, "pick_elim", or its contest): none of its own
       return {[&m](int v) { return prior_source(m, v); }, kElimVariants, elim_first_variant(m), true, "famseq_elim_prior", elim_block_threads(m),
               [&m](int v) { return elim_source(m, v); }};
+    case K_MAP_PRIOR:  // ... and famseq_map's
+      return {[&m](int v) { return map_source(m, v, true); }, kMapVariants, 0, false, "famseq_map_prior", elim_block_threads(m),
+              [&m](int v) { return map_source(m, v); }};
   }
   throw std::logic_error("kernel_spec: no such kind");
 }
@@ -104,11 +113,15 @@ int load_kernel(famseq_ctx *c, int kind, std::string *why) {
 
 int load_or_fail(famseq_ctx *c, int kind) {
   if (is_trio(kind)) c->trio_last = kind - K_TRIO + 1;
+  if (is_trio_prior(kind)) c->trio_prior_last = kind - K_TRIO_PRIOR + 1;
   if (have(c, c->kern[kind])) return 0;
   std::string why;
   if (!elim_supported(c->model, &why))
     return fail(c, FAMSEQ_E_ARG, (kind == K_ELIM ? "elimination engine: " : kind == K_MAP ? "joint MAP call (sum-product engine): "
-                                  : kind == K_PRIOR ? "site priors (sum-product engine): " : "trio posteriors (sum-product engine): ") + why);
+                                  : kind == K_PRIOR ? "site priors (sum-product engine): "
+                                  : kind == K_MAP_PRIOR ? "site priors, joint MAP call (sum-product engine): "
+                                  : is_trio_prior(kind) ? "site priors, trio posteriors (sum-product engine): "
+                                                        : "trio posteriors (sum-product engine): ") + why);
   if (load_kernel(c, kind, &why) != 0) return fail(c, FAMSEQ_E_HIP, why);
   return 0;
 }
@@ -153,7 +166,8 @@ bool load_or_remember(famseq_ctx *c, int kind) {
 // kernel_spec honours it — and the lane call-path form takes its block shape from K_LANE's variant.  Those three are what
 // a new pick makes stale; the lanes-per-site, sum-product call-path, trio and MAP kernels run their own contests and
 // cannot be moved by one, so they stay loaded.  (The site-prior kernel takes K_ELIM's variant: whoever drops K_ELIM for a
-// new pick drops K_PRIOR with it.)
+// new pick drops K_PRIOR with it.  The site-prior trio and MAP kernels take their plain siblings' contests' variants; no pick
+// moves those, and nothing drops a trio or MAP kernel: whoever comes to drop one drops its site-prior form with it.)
 void drop_lane_kernels(famseq_ctx *c) {
   c->kern[K_LANE].drop();
   c->kern[K_LANE_CALL].drop();

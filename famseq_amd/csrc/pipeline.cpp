@@ -216,22 +216,25 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
   return rc;
 }
 
-// ... and the trio and MAP entries: per chunk [unpack] -> kernel, on the entry's own set of slots.  out_a / out_b: the two
+// ... and the trio and MAP entries (plain and site-prior): per chunk [unpack] -> kernel, on the entry's own set of slots.  out_a / out_b: the two
 // per-site outputs (NULL: not wanted), a_row / b_row their bytes per site (0: the pedigree has none).
 int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
-               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status) {
+               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior) {
   const int N = c->model.n_members;
   const size_t row = size_t(3) * N * sizeof(double), pl_row = pl16 ? size_t(n_seq) * 3 * sizeof(uint16_t) : 0;
+  const size_t prior_row = prior ? 6 * sizeof(double) : 0;
   ChunkJob job;
   job.n_sites = n_sites;
   job.chunk = chunk_for(c, n_sites, std::max(row, a_row + 1));
   size_t want[B_COUNT] = {};
   want[B_LK] = row, want[B_FLAGS] = want[B_STATUS] = 1, want[B_PL] = pl_row, want[B_OUT_A] = a_row, want[B_OUT_B] = b_row;
+  want[B_PRIOR] = prior_row;
   const int rc = reserve(c, t, job.chunk, want);
   if (rc != 0) return rc;
   job.copy_in(B_PL, pl_row, pl16);
   if (!pl16) job.copy_in(B_LK, row, lk);
   job.copy_in(B_FLAGS, 1, flags);
+  job.copy_in(B_PRIOR, prior_row, prior);
   job.copy_out(B_OUT_A, a_row, out_a);
   job.copy_out(B_OUT_B, b_row, out_b);
   job.copy_out(B_STATUS, 1, status);
@@ -240,7 +243,8 @@ int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, c
     if (pl16)
       HIP_TRY(c, launch_unpack_pl16(d[B_PL].as<uint16_t>(), c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, n_seq, n, d[B_LK].as<double>(), s_k));
     HIP_TRY(c, launch_generated(c, g, n, d[B_LK].as<double>(), flags ? d[B_FLAGS].as<uint8_t>() : nullptr, out_a ? d[B_OUT_A].p : nullptr,
-                                out_b ? d[B_OUT_B].p : nullptr, status ? d[B_STATUS].as<uint8_t>() : nullptr, s_k));
+                                out_b ? d[B_OUT_B].p : nullptr, status ? d[B_STATUS].as<uint8_t>() : nullptr, s_k, 0,
+                                prior ? d[B_PRIOR].p : nullptr));
     return 0;
   });
 }

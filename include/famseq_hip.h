@@ -349,7 +349,38 @@ int famseq_bn_prior_call_batch(famseq_ctx *ctx, int64_t n_sites, const double *l
                                const double *prior, const int32_t *seq_members, int32_t n_seq, double *gpp, double *fpp, int8_t *fgt,
                                char *text, uint8_t *status);
 
-/* Hardy-Weinberg rows for the two entries above, on the host: prior[i] = ((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
+/* ---- founder priors per site for the trio posteriors and the joint MAP call -------------------------------------------
+ * famseq_trio_batch and famseq_map_batch with the founders' genotype prior given per site: prior[n_sites][6], required, laid
+ * out, read (the male half at chrX sites only; FAMSEQ_FLAG_KNOWN not read) and checked by the host entries (finite, >= 0, else
+ * FAMSEQ_E_ARG naming the site) exactly as for famseq_bn_prior_batch.  The de novo posterior is the output that depends most
+ * on that prior: the evidence that makes a de novo call at a singleton is, at a common variant, a missed parental heterozygote.
+ * Outputs, layouts and statuses are the plain entries' with the prior row in the place of genoProb*: status 1 where lk * prior
+ * sums to <= 0 for any member (an all-zero row fails its site), 2 where the network's total weight (MAP: or the maximum) is <= 0,
+ * no shortcut; joint / dnm / map_post NaN and map_gt -1 wherever status != 0.  The de novo mask depends on the transmission
+ * tables only and is unchanged.  Given rows that equal the model's constants the outputs are, bit for bit, famseq_trio_batch's
+ * and famseq_map_batch's.
+ * The kernels (famseq_trio_prior per output form, famseq_map_prior) are compiled on the first call, or ahead through
+ * famseq_set_option "trio_prior_kernels" (1 dnm, 2 joint, 3 both) / "map_prior_kernels" = 1 (a plan-only context generates and
+ * cross-compiles them); each takes the variant its plain sibling's contest takes for the pedigree.  famseq_plan_json:
+ * "trio_prior_code_object", "trio_prior_variant" (the form asked for last), "map_prior_code_object", "map_prior_variant". */
+
+/* Host buffers, blocking, chunked and pipelined (a chunk's prior rows travel with its likelihoods); the other arguments as
+ * famseq_trio_batch / famseq_map_batch. */
+int famseq_trio_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                            int32_t n_seq, const uint8_t *flags, const double *prior, double *joint, double *dnm, uint8_t *status);
+int famseq_map_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                           int32_t n_seq, const uint8_t *flags, const double *prior, int8_t *map_gt, double *map_post, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array): enqueue on `stream` (a hipStream_t;
+ * NULL = the default stream) and return without synchronising.  Nothing is checked of d_prior's contents. */
+int famseq_trio_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                   const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                   double *d_joint, double *d_dnm, uint8_t *d_status, void *stream);
+int famseq_map_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                  const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                  int8_t *d_map_gt, double *d_map_post, uint8_t *d_status, void *stream);
+
+/* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] = ((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);
 
