@@ -7,7 +7,7 @@ CSRC := famseq_amd/csrc
 LIB := famseq_amd/lib/libfamseq_hip.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Iinclude -I$(CSRC) -Wall -Wno-unused-result
 
-SRCS := $(CSRC)/bn_kernel.hip $(CSRC)/io_kernels.hip $(CSRC)/capi.cpp $(CSRC)/kernels.cpp $(CSRC)/pipeline.cpp $(CSRC)/plan.cpp $(CSRC)/model.cpp $(CSRC)/jit.cpp $(CSRC)/elim_codegen.cpp $(CSRC)/enum_codegen.cpp
+SRCS := $(CSRC)/bn_kernel.hip $(CSRC)/io_kernels.hip $(CSRC)/capi.cpp $(CSRC)/kernels.cpp $(CSRC)/pipeline.cpp $(CSRC)/plan.cpp $(CSRC)/model.cpp $(CSRC)/jit.cpp $(CSRC)/elim_codegen.cpp $(CSRC)/enum_codegen.cpp $(CSRC)/kernel_shell.cpp
 OBJS := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 
 CLI := bin/FamSeq
@@ -51,7 +51,7 @@ tools: $(TOOLS)
 # tests/asan_host_check.cpp.  CPU only (GPU AddressSanitizer is not available on the pool); the two
 # kernel translation units are linked as they are (their host side is launch glue).  `make asan` builds
 # and runs it; tests/test_abi.py runs it as part of the CPU suite.
-ASAN_SRCS := capi.cpp kernels.cpp pipeline.cpp plan.cpp model.cpp jit.cpp elim_codegen.cpp enum_codegen.cpp
+ASAN_SRCS := capi.cpp kernels.cpp pipeline.cpp plan.cpp model.cpp jit.cpp elim_codegen.cpp enum_codegen.cpp kernel_shell.cpp
 ASAN_OBJS := $(patsubst %,build/asan/%.o,$(ASAN_SRCS))
 ASAN_FLAGS := -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
               -ffp-contract=off -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -I$(CSRC) -Wall -Wno-unused-result

@@ -19,7 +19,7 @@
 
 // The fused call path's side of a generated kernel's argument list (kCallArgs): packed PLs in, GPP / FPP /
 // FGT out.  All null on the plain path.
-struct CallIO {  // = struct fs_call_args of the generated source (elim_codegen.cpp kCallHelpers)
+struct CallIO {  // = struct fs_call_args of the generated source (kernel_shell.cpp kCallHelpers)
   const uint16_t *pl = nullptr;
   const double *lut = nullptr;
   const int32_t *col = nullptr, *slot = nullptr;

@@ -60,17 +60,5 @@ constexpr int kMapVariants = 4;
 // site_prior: famseq_map_prior, with a trailing `prior` [n_sites][6] (as trio_source's).
 std::string map_source(const Model &m, int variant, bool site_prior = false);
 
-// Shared shell of the generated kernels (see elim_codegen.cpp).
-extern const std::string kCallHelpers;  // fused call path: fs_phred, STAGE_IN_PL, STAGE_OUT_CALL, STAGE_FGT
-extern const char kCallArgs[];     // ... and the kernel arguments that go with them
-extern const char kDiv3Text[];     // FS_DIV_OK / FS_DIV3_FAST: what single_posterior_statements' text needs defined
-// site_prior: the founder-prior operands are the lane's variables pa_<g> / pm_<g> (see prior_source) instead of tcf[] entries
-std::string single_posterior_statements(const Model &m, bool flags_pass, bool store, bool fence_single, const char *dst = "row",
-                                        bool site_prior = false);
-std::string kernel_shell(const Model &m, const std::string &entry, const std::string &comment,
-                         const std::string &body, int bt, int min_waves, bool regs_l, bool fence_single,
-                         bool chrx_loop = false, int row_doubles = 0, bool call_mode = false, bool lane_body = false,
-                         bool call_ct_out = true, bool site_prior = false);
-
 }  // namespace famseq
 #endif

@@ -28,7 +28,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "elim_codegen.h"
+#include "kernel_shell.h"
 
 namespace famseq {
 
@@ -68,8 +68,7 @@ Shape choose_shape(const Model &m, int cap) {
   // (four members at most: 60 — two founders and two children of both are 3 + 3 + 27 + 27 — so that a quad is ONE unrolled block of
   // 81 configurations instead of a three-step loop over 27: 0.556 -> 0.512 ms per 8 M sites; five members all unrolled need 120 and
   // run at half the waves, 0.70 -> 0.88)
-  int table_budget = N <= 4 ? 60 : 48;
-  if (const char *e = std::getenv("FAMSEQ_LANE_TABLE_BUDGET")) table_budget = std::atoi(e);  // tuning aid
+  const int table_budget = env_int("FAMSEQ_LANE_TABLE_BUDGET", N <= 4 ? 60 : 48);  // (the variable: a tuning aid)
   auto table_doubles = [&]() {
     int t = 0;
     for (int i = 0; i < N; ++i)
@@ -178,7 +177,7 @@ class Gen {
   }
 
   std::string body() {
-    if (const char *e = std::getenv("FAMSEQ_LANE_PIN")) pin_style_ = std::atoi(e);  // tuning aid
+    pin_style_ = env_int("FAMSEQ_LANE_PIN", pin_style_);  // tuning aid
     compute_deps();
     choose_superleaf();
     order_outer_loops();
@@ -228,7 +227,7 @@ class Gen {
       o_ << "      const int fx" << k << " = (sub / " << div << ") % 3;\n";
     }
     joint_ = sl_ >= 2;
-    if (const char *e = std::getenv("FAMSEQ_LANE_JOINT")) joint_ = joint_ && std::atoi(e) != 0;  // tuning aid
+    joint_ = joint_ && env_int("FAMSEQ_LANE_JOINT", 1) != 0;  // tuning aid
     for (int k = 0; k < nu_; ++k) {
       if (joint_ && k >= nu_ - sl_) continue;
       const int p = s_.unrolled[k];
@@ -271,8 +270,7 @@ class Gen {
     // One division per row and three products (the sums differ from the reference's in their last bits already, by
     // summation order; 35 -> 25 divisions per five-member site, each ten instructions).  A row sum in the subnormal
     // range, whose reciprocal overflows, keeps the three divisions behind a real branch.
-    bool div_rows = false;
-    if (const char *e = std::getenv("FAMSEQ_LANE_DIVROWS")) div_rows = std::atoi(e) != 0;  // tuning aid: three divisions per row
+    const bool div_rows = env_int("FAMSEQ_LANE_DIVROWS", 0) != 0;  // tuning aid: three divisions per row
     for (int p = 0; p < s_.N; ++p) {
       auto out = [&](int g) { return O_ + "[" + std::to_string(3 * p + g) + "]"; };
       const std::string b = "b" + std::to_string(p);
@@ -764,7 +762,7 @@ class Gen {
 
 std::string enumgen_describe(const Model &m, int variant) {
   int cap = (variant >= 0 && variant < 2) ? 7 : 6;  // kEnumVariants; unknown yet (-1): the 6-member form
-  if (const char *e = std::getenv("FAMSEQ_LANE_CAP")) cap = std::atoi(e);
+  cap = env_int("FAMSEQ_LANE_CAP", cap);
   const Shape s = choose_shape(m, cap);
   std::string d = "looped members [";
   for (size_t k = 0; k < s.outer.size(); ++k) d += (k ? " " : "") + num(s.outer[k]);
@@ -783,9 +781,7 @@ std::string enumgen_describe(const Model &m, int variant) {
 // (a quarter of the lanes per CU: no likelihood is re-read from global memory any more), 10.21 -> 9.78 ms per 4 M sites
 // (profiles/r02c/exp_block_sizes_*.txt).  The lanes-per-site forms keep wide workgroups: a site's 81 lanes span waves.
 int enumgen_block_threads(const Model &m, int group_digits) {
-  if (const char *e = std::getenv("FAMSEQ_LANE_BT")) return std::atoi(e);  // tuning aid
-  if (group_digits == 0) return 64;
-  return m.n_members <= 10 ? 256 : 128;
+  return env_int("FAMSEQ_LANE_BT", group_digits == 0 ? 64 : (m.n_members <= 10 ? 256 : 128));  // (the variable: a tuning aid)
 }
 
 // (asked of the call-path form: its LDS row has less room than the plain form's, so it may re-read members
@@ -796,7 +792,7 @@ bool enumgen_reads_global_rows(const Model &m, int variant) {
 
 int enumgen_max_group_digits(const Model &m) {
   int cap = 6;
-  if (const char *e = std::getenv("FAMSEQ_LANE_CAP")) cap = std::atoi(e);
+  cap = env_int("FAMSEQ_LANE_CAP", cap);
   return std::min<int>(kEnumMaxGroupDigits, (int)choose_shape(m, cap).outer.size());
 }
 
@@ -819,26 +815,18 @@ std::string grouped_shell(const Model &m, const std::string &comment, const std:
                           int bt, int min_waves, bool fence_single, int row_doubles, int group) {
   const int N = m.n_members, W3 = 3 * N, ROW = (row_doubles > 0 ? row_doubles : W3) | 1;
   std::ostringstream s;
-  s << "// generated by famseq_amd/csrc for a " << N << "-member pedigree: " << comment << "\n"
-    // (the in-process compiler, hiprtc, brings the device built-ins itself and has no include path for the header)
-    << "#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n#pragma clang fp contract(off)\n"
-    << "#define W3 " << W3 << "\n#define ROW " << ROW << "\n#define BT " << bt << "\n#define G " << group << "\n#define SPC (BT / G)\n"
-    << "#define LDS_BARRIER() asm volatile(\"s_waitcnt lgkmcnt(0)\\n\\ts_barrier\" ::: \"memory\")\n"
-    << kDiv3Text
+  s << source_head(m, comment, bt, ROW, "#define G " + std::to_string(group) + "\n#define SPC (BT / G)\n")
     // rows of the groups' first lanes -> global, coalesced
     << "#define STAGE_OUT(Gp) { double *g_ = (Gp) + site0 * W3; \\\n"
     << "  for (int e = tid; e < ns * W3; e += BT) { const int s_ = e / W3; g_[e] = s_io[s_ * G * ROW + (e - s_ * W3)]; } }\n"
-    << "extern \"C\" __global__ __launch_bounds__(BT, " << min_waves << ") void famseq_enum_lane(const double *__restrict__ lk_g,\n"
-    << "    const unsigned char *__restrict__ flags_g, double *__restrict__ post_g, double *__restrict__ single_g,\n"
-    << "    unsigned char *__restrict__ status_g, long n_sites, const double *__restrict__ tc_g, double lc) {\n"
+    << kernel_signature("famseq_enum_lane", min_waves, "double *__restrict__ post_g, double *__restrict__ single_g")
     << "  __shared__ double s_io[BT * ROW];  // one padded row per lane\n"
     << "  __shared__ double s_tc[432];\n"
     << "  const int tid = threadIdx.x;\n"
     << "  for (int i = tid; i < 432; i += BT) s_tc[i] = tc_g[i];\n"
     << "  const int sidx = tid / G, sub = tid - sidx * G;  // site within the chunk, lane within the group\n"
     << "  const long chunks = (n_sites + SPC - 1) / SPC;\n"
-    << "  const long q_wg = chunks / gridDim.x, r_wg = chunks - q_wg * gridDim.x;  // q or q + 1 chunks each: no idle workgroup\n"
-    << "  const long c_lo = (long)blockIdx.x * q_wg + (blockIdx.x < r_wg ? blockIdx.x : r_wg), c_hi = c_lo + q_wg + (blockIdx.x < r_wg ? 1 : 0);\n"
+    << chunk_range("  // q or q + 1 chunks each: no idle workgroup")
     << "  const double kNaN = __builtin_nan(\"\");\n"
     << "  double *row = s_io + tid * ROW;\n"
     << "  for (long ch = c_lo; ch < c_hi; ++ch) {\n"
@@ -853,7 +841,9 @@ std::string grouped_shell(const Model &m, const std::string &comment, const std:
     << "    bool single_fail = false, full = false, bn_fail = false;\n";
   for (int p = 0; p < N; ++p)
     for (int gt = 0; gt < 3; ++gt) s << "    const double l" << p << "_" << gt << " = lg[" << 3 * p + gt << "];\n";
-  s << single_posterior_statements(m, true, true, fence_single)
+  SingleOptions so;
+  so.fence = fence_single;
+  s << single_posterior_statements(m, so)
     << "    if (!act) full = false;\n"
     << "    if (single_fail) for (int k = 0; k < W3; ++k) row[k] = kNaN;\n"
     << "    LDS_BARRIER();\n"
@@ -889,7 +879,7 @@ std::string grouped_shell(const Model &m, const std::string &comment, const std:
 
 std::string enumgen_source(const Model &m, int variant, int group_digits, bool call_mode, bool call_ct_out) {
   int cap = (group_digits == 0 && variant < 2) ? 7 : 6;  // see kEnumVariants
-  if (const char *e = std::getenv("FAMSEQ_LANE_CAP")) cap = std::atoi(e);  // tuning aid
+  cap = env_int("FAMSEQ_LANE_CAP", cap);  // tuning aid
   const Shape s = choose_shape(m, cap);
   if (s.unrolled.empty()) throw std::runtime_error("enumeration codegen: empty unrolled set");
   if (group_digits < 0 || group_digits > std::min<int>(kEnumMaxGroupDigits, (int)s.outer.size()))
@@ -916,8 +906,7 @@ std::string enumgen_source(const Model &m, int variant, int group_digits, bool c
   // slots follow them.  Measured slower (8 M sites, tools/kernel_bench, two runs): trio 0.368-0.374 -> 0.385-0.392 ms,
   // quad 0.604-0.613 -> 0.640-0.655, 5 members 0.805-0.816 -> 0.827-0.829 (identical binaries differ by +-4 %
   // between runs on these boxes).
-  bool late = false;
-  if (const char *e = std::getenv("FAMSEQ_LANE_LATE")) late = std::atoi(e) != 0 && group_digits == 0;  // tuning aid
+  bool late = env_int("FAMSEQ_LANE_LATE", 0) != 0 && group_digits == 0;  // tuning aid
   int scratch_len = 0;
   if (late) {
     int looped_tables = 0;
@@ -943,34 +932,33 @@ std::string enumgen_source(const Model &m, int variant, int group_digits, bool c
   // (the call-path form of a small pedigree's kernel: two waves per SIMD at least — with 512 registers to fill, its output stages'
   // batched loads took the five-member kernel from two waves to one, 0.156 -> 0.203 ms per 1 M sites; bounded, the variant
   // contest sees the spill and takes the leaner stage-out)
-  int min_waves = group_digits == 0 ? (call_mode && m.n_members <= 6 ? 2 : 1) : bt / 128;
-  if (const char *e = std::getenv("FAMSEQ_LANE_MINWAVES")) min_waves = std::atoi(e);  // tuning aid
+  const int min_waves = env_int("FAMSEQ_LANE_MINWAVES", group_digits == 0 ? (call_mode && m.n_members <= 6 ? 2 : 1) : bt / 128);  // tuning aid
   // Transmission entries through scalar loads, and the innermost loop's loads one step ahead (see Gen): the one-lane-per-site
   // forms of pedigrees that have looped members; the lanes-per-site forms keep the per-lane LDS table.  Round 3, measured
   // with tools/kernel_bench on one box (profiles/r03a/exp_scalar_tables.txt): ten members 10.40 -> 10.13-10.20 ms per 4 M sites,
   // fifteen 139.2 -> 138.4 ms per 262 k; the innermost loop loses 36 of its 39 LDS reads and 10 of its 11 waits (885 -> 881
   // instructions per 729 configurations) — the waits were a small part of what one wave per SIMD loses: at 1.21 instructions
   // per configuration in that loop and 1.33 overall the kernel runs at the issue rate a single wave sustains.
-  bool scalar_t = true;
-  int prefetch = 2;
-  if (const char *e = std::getenv("FAMSEQ_LANE_ST")) scalar_t = std::atoi(e) != 0;  // tuning aid
-  if (const char *e = std::getenv("FAMSEQ_LANE_PRE")) prefetch = std::atoi(e);     // tuning aid: 0 none, 1 table entries, 2 and LDS reads
-  scalar_t = scalar_t && group_digits == 0 && !late && !s.outer.empty();
+  const bool scalar_t = env_int("FAMSEQ_LANE_ST", 1) != 0 && group_digits == 0 && !late && !s.outer.empty();  // (the variable: a tuning aid)
+  const int prefetch = env_int("FAMSEQ_LANE_PRE", 2);  // tuning aid: 0 none, 1 table entries, 2 and LDS reads
   Gen gen(m, s, late ? std::max(scratch_len, 1) : row_len, group_digits, late, scalar_t, prefetch);
   if (call_mode) what += ", call path";
-  if (late)  // regs_l = false: the shell's compute-first flow; variant 0 / 1 as below
-    return kernel_shell(m, "famseq_enum_lane", what + ", compute-first shell", gen.body(), bt, min_waves, /*regs_l=*/false, (variant & 1) != 0,
-                        /*chrx_loop=*/false, row_len, call_mode, /*lane_body=*/true, call_ct_out);
+  // variant 0: the members of the single posterior overlap, 1: fenced one from the other (fewer registers)
   const bool fence_single = variant & 1;
   if (group > 1) {
     if (call_mode) throw std::runtime_error("enumeration codegen: the lanes-per-site form has no call path");
     const std::string body = gen.body();
     return grouped_shell(m, what, body, gen.reduce_body(), bt, min_waves, fence_single, row_len, group);
   }
-  // regs_l: LDS-resident likelihoods measured 17% slower.  variant 0: the members of the single
-  // posterior overlap, 1: fenced one from the other (fewer registers)
-  return kernel_shell(m, "famseq_enum_lane", what, gen.body(), bt, min_waves, /*regs_l=*/true, fence_single,
-                      /*chrx_loop=*/scalar_t, row_len, call_mode, /*lane_body=*/false, call_ct_out);
+  ShellOptions o;
+  o.entry = "famseq_enum_lane";
+  o.comment = late ? what + ", compute-first shell" : what;
+  o.body = gen.body();
+  o.bt = bt, o.min_waves = min_waves, o.row_doubles = row_len;
+  // registers-first (LDS-resident likelihoods measured 17 % slower) unless the late experiment asks for the shell's compute-first flow
+  o.regs_l = !late, o.lane_body = late;
+  o.fence_single = fence_single, o.chrx_loop = !late && scalar_t, o.call_mode = call_mode, o.call_ct_out = call_ct_out;
+  return kernel_shell(m, o);
 }
 
 }  // namespace famseq

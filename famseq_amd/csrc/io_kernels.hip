@@ -16,7 +16,7 @@
 // multiply-high divisions (exact for n, d < 2^16: the launchers check 3 * members < 2^16) instead of the
 // 64-bit integer divisions a flat index over n_sites * W3 costs.
 // phred_call is bound by its two fp64 logarithms per element (VALU; phred_src.h), unpack_pl16 by HBM.
-// Batches served by the generated kernels do both inside the posterior kernel (elim_codegen.cpp kCallHelpers);
+// Batches served by the generated kernels do both inside the posterior kernel (kernel_shell.cpp kCallHelpers);
 // these two remain for the compiled-in team kernel and the lanes-per-site mode.
 #include <hip/hip_runtime.h>
 

@@ -2,8 +2,8 @@
 // (`make asan`; CPU only, never on the GPU box).  Links the library's own host translation units
 // (model, plan, both kernel generators, jit, the C ABI), compiled by g++ with
 // -fsanitize=address,undefined, and drives them the way the ABI's callers do on plan-only
-// contexts: model setup and its rejections, plan options (valid and invalid), every variant of
-// both generators, the JSON description, the error paths of the compute entry points without a
+// contexts: model setup and its rejections, plan options (valid and invalid), every variant and form of
+// both generators (the sum-product family's site-prior, trio and MAP kernels among them), the JSON description, the error paths of the compute entry points without a
 // device, and the JIT's failure path (no compiler) of every kind of generated kernel.  Any sanitizer
 // report aborts with a non-zero exit status; the program prints one line per pedigree.
 #include <dirent.h>
@@ -100,8 +100,15 @@ void drive(const Ped &p) {
   bytes += famseq::enumgen_describe(m).size();
   std::string why;
   const bool elim = famseq::elim_supported(m, &why);
-  if (elim)
-    for (int v = 0; v < famseq::kElimVariants; ++v) bytes += famseq::elim_source(m, v).size();
+  if (elim) {  // every form of the sum-product family: plain, call path, site priors, trio and MAP (with and without site priors)
+    for (int v = 0; v < famseq::kElimVariants; ++v) bytes += famseq::elim_source(m, v).size() + famseq::prior_source(m, v).size();
+    for (int v = 0; v < famseq::kElimCallVariants; ++v) bytes += famseq::elim_source(m, v, true).size();
+    for (int prior = 0; prior <= 1; ++prior) {
+      for (int v = 0; v < famseq::kTrioVariants; ++v)
+        for (int form = 1; form <= 3; ++form) bytes += famseq::trio_source(m, v, form, prior != 0).size();
+      for (int v = 0; v < famseq::kMapVariants; ++v) bytes += famseq::map_source(m, v, prior != 0).size();
+    }
+  }
   // no compiler: the JIT's failure path (message, no leak, the ctx stays usable)
   CHECK(famseq_set_option(c, "enum_impl", 1) != 0);
   if (elim) CHECK(famseq_set_option(c, "engine", FAMSEQ_ENGINE_ELIM) != 0);

@@ -1,6 +1,6 @@
 // io_ceiling.hip — what does MI355X give a kernel with the posterior kernels' traffic shape
 // (read one fp64 row per site, write two)?  Times bare I/O skeletons with HIP events so that the
-// generated kernels' staging (elim_codegen.cpp kernel_shell) can be compared against a ceiling
+// generated kernels' staging (kernel_shell.cpp kernel_shell) can be compared against a ceiling
 // measured in the same access pattern rather than against a copy.
 //   ew8 / ew16 / ew16nt   elementwise streaming, no LDS: 8 or 16 B per lane, non-temporal or not
 //   ew8c                  elementwise, one contiguous range per workgroup
