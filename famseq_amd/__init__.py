@@ -84,6 +84,7 @@ ABI_SYMBOLS = [
     "famseq_map_batch", "famseq_map_batch_device",
     "famseq_bn_prior_batch", "famseq_bn_prior_batch_device", "famseq_bn_prior_call_batch", "famseq_hwe_priors",
     "famseq_trio_prior_batch", "famseq_trio_prior_batch_device", "famseq_map_prior_batch", "famseq_map_prior_batch_device",
+    "famseq_evidence_batch", "famseq_evidence_batch_device", "famseq_evidence_prior_batch", "famseq_evidence_prior_batch_device",
 ]
 PL_MISSING = 0xFFFF
 
@@ -182,6 +183,14 @@ def lib():
     L.famseq_map_prior_batch.restype = C.c_int
     L.famseq_map_prior_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.famseq_map_prior_batch_device.restype = C.c_int
+    L.famseq_evidence_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, dp, dp, bp]
+    L.famseq_evidence_batch.restype = C.c_int
+    L.famseq_evidence_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp]
+    L.famseq_evidence_batch_device.restype = C.c_int
+    L.famseq_evidence_prior_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, dp, dp, dp, bp]
+    L.famseq_evidence_prior_batch.restype = C.c_int
+    L.famseq_evidence_prior_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp, vp]
+    L.famseq_evidence_prior_batch_device.restype = C.c_int
     _lib = L
     return L
 
@@ -530,6 +539,63 @@ class Context:
                                                  _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_prior or None,
                                                  d_map_gt or None, d_map_post or None, d_status or None, stream or None)
         self._check(rc, "famseq_map_prior_batch_device")
+
+    def evidence_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_loglik=True, want_pref=True):
+        """The evidence: -> (loglik[S] float64, pref[S] float64, status[S] uint8).
+        loglik[s] is log10 of the data's likelihood under the pedigree at site s, pref[s] the posterior probability that every
+        member is hom-ref (both NaN where status != 0).  Input as map_batch: either lk [S,N,3] float64 or pl16 [S,n_seq,3]
+        uint16 in VCF column order (seq_members: their PED indices).  want_loglik / want_pref False: that output is not
+        computed and returned as None."""
+        return self._evidence(lk, pl16, seq_members, flags, want_loglik, want_pref, None)
+
+    def evidence_prior_batch(self, prior, lk=None, pl16=None, seq_members=None, flags=None, want_loglik=True, want_pref=True):
+        """evidence_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags
+        only FLAG_CHRX is read).  Rows equal to the model's constants give evidence_batch's bits."""
+        return self._evidence(lk, pl16, seq_members, flags, want_loglik, want_pref, prior)
+
+    def _evidence(self, lk, pl16, seq_members, flags, want_loglik, want_pref, prior):
+        if (lk is None) == (pl16 is None):
+            raise ValueError("give exactly one of lk / pl16")
+        seq, n_seq = None, 0
+        if lk is not None:
+            lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
+            s = lk.shape[0]
+        else:
+            seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+            n_seq = len(seq)
+            pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, n_seq, 3)
+            s = pl16.shape[0]
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        if fl is not None and fl.shape != (s,):
+            raise ValueError("flags must have one byte per site")
+        loglik = np.empty(s) if want_loglik else None
+        pref = np.empty(s) if want_pref else None
+        status = np.zeros(s, np.uint8)
+        head = (self._h, s, None if lk is None else _p(lk, C.c_double), None if pl16 is None else _p(pl16, C.c_uint16),
+                None if seq is None else _p(seq, C.c_int32), n_seq, None if fl is None else _p(fl, C.c_uint8))
+        out = (None if loglik is None else _p(loglik, C.c_double), None if pref is None else _p(pref, C.c_double), _p(status, C.c_uint8))
+        if prior is None:
+            self._check(lib().famseq_evidence_batch(*head, *out), "famseq_evidence_batch")
+        else:
+            self._check(lib().famseq_evidence_prior_batch(*head, _p(_prior_rows(prior, s), C.c_double), *out), "famseq_evidence_prior_batch")
+        return loglik, pref, status
+
+    def evidence_batch_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_loglik=0, d_pref=0, d_status=0, stream=0):
+        """The evidence on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+        rc = lib().famseq_evidence_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
+                                                _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_loglik or None,
+                                                d_pref or None, d_status or None, stream or None)
+        self._check(rc, "famseq_evidence_batch_device")
+
+    def evidence_prior_batch_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_loglik=0, d_pref=0, d_status=0,
+                                    stream=0):
+        """evidence_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+        rc = lib().famseq_evidence_prior_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
+                                                      _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_prior or None,
+                                                      d_loglik or None, d_pref or None, d_status or None, stream or None)
+        self._check(rc, "famseq_evidence_prior_batch_device")
 
     def g6_probe(self, values):
         """The device formatter alone (famseq_format_probe): -> list of bytes, one per value."""

@@ -299,6 +299,14 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
     if (value != 1) return fail(c, FAMSEQ_E_ARG, "map_prior_kernels takes 1");
     return load_or_fail(c, K_MAP_PRIOR);
   }
+  else if (k == "evidence_kernels") {  // build (and on a device ctx load) the evidence kernel now
+    if (value != 1) return fail(c, FAMSEQ_E_ARG, "evidence_kernels takes 1");
+    return load_or_fail(c, K_EVID);
+  }
+  else if (k == "evidence_prior_kernels") {  // ... and its site-prior form
+    if (value != 1) return fail(c, FAMSEQ_E_ARG, "evidence_prior_kernels takes 1");
+    return load_or_fail(c, K_EVID_PRIOR);
+  }
   else if (k == "group_digits") {
     if (value < -1 || value > enumgen_max_group_digits(c->model))
       return fail(c, FAMSEQ_E_ARG, "group_digits must be -1 (auto) or 0.." + std::to_string(enumgen_max_group_digits(c->model)) +
@@ -362,7 +370,10 @@ std::string trio_json(const famseq_ctx *c) {
          std::to_string(c->kern[K_PRIOR].variant) + ",\"trio_prior_code_object\":\"" +
          json_str(fp ? c->kern[K_TRIO_PRIOR + fp - 1].k.path : std::string()) + "\",\"trio_prior_variant\":" +
          std::to_string(fp ? c->kern[K_TRIO_PRIOR + fp - 1].variant : -1) + ",\"map_prior_code_object\":\"" +
-         json_str(c->kern[K_MAP_PRIOR].k.path) + "\",\"map_prior_variant\":" + std::to_string(c->kern[K_MAP_PRIOR].variant);
+         json_str(c->kern[K_MAP_PRIOR].k.path) + "\",\"map_prior_variant\":" + std::to_string(c->kern[K_MAP_PRIOR].variant) +
+         ",\"evidence_code_object\":\"" + json_str(c->kern[K_EVID].k.path) + "\",\"evidence_variant\":" + std::to_string(c->kern[K_EVID].variant) +
+         ",\"evidence_prior_code_object\":\"" + json_str(c->kern[K_EVID_PRIOR].k.path) + "\",\"evidence_prior_variant\":" +
+         std::to_string(c->kern[K_EVID_PRIOR].variant) + ",\"evidence_block_threads\":" + std::to_string(elim_block_threads(c->model));
 }
 }  // namespace
 
@@ -830,5 +841,43 @@ extern "C" int famseq_map_prior_batch_device(famseq_ctx *c, int64_t n_sites, con
   if (!c) return FAMSEQ_E_ARG;
   if (n_sites > 0 && !d_prior) return fail(c, FAMSEQ_E_ARG, "d_prior must be given (six doubles per site)");
   return side_batch_device(c, K_MAP_PRIOR, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_map_gt, d_map_post, d_status,
+                           static_cast<hipStream_t>(stream), d_prior);
+}
+
+// ---- the evidence: the site's log10 likelihood and the hom-ref posterior ------------------------------------------------
+
+extern "C" int famseq_evidence_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                     int32_t n_seq, const uint8_t *flags, double *loglik, double *pref, uint8_t *status) {
+  if (!c) return FAMSEQ_E_ARG;
+  const int rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, K_EVID);
+  if (rc != 0 || n_sites == 0) return rc;
+  return side_batch(c, c->evid_slots, c->kern[K_EVID], n_sites, lk, pl16, n_seq, flags, loglik, sizeof(double), pref, sizeof(double), status);
+}
+
+extern "C" int famseq_evidence_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                            const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_loglik,
+                                            double *d_pref, uint8_t *d_status, void *stream) {
+  if (!c) return FAMSEQ_E_ARG;
+  return side_batch_device(c, K_EVID, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_loglik, d_pref, d_status,
+                           static_cast<hipStream_t>(stream));
+}
+
+extern "C" int famseq_evidence_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
+                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
+                                           double *loglik, double *pref, uint8_t *status) {
+  if (!c) return FAMSEQ_E_ARG;
+  int rc = check_input(c, n_sites, lk, pl16, "lk / pl16", false, n_seq);
+  if (rc != 0 || (rc = prior_ready(c, n_sites, flags, prior, K_EVID_PRIOR)) != 0) return rc;
+  if ((rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, K_EVID_PRIOR)) != 0 || n_sites == 0) return rc;
+  return side_batch(c, c->evid_slots, c->kern[K_EVID_PRIOR], n_sites, lk, pl16, n_seq, flags, loglik, sizeof(double), pref, sizeof(double),
+                    status, prior);
+}
+
+extern "C" int famseq_evidence_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                                  const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                                  double *d_loglik, double *d_pref, uint8_t *d_status, void *stream) {
+  if (!c) return FAMSEQ_E_ARG;
+  if (n_sites > 0 && !d_prior) return fail(c, FAMSEQ_E_ARG, "d_prior must be given (six doubles per site)");
+  return side_batch_device(c, K_EVID_PRIOR, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_loglik, d_pref, d_status,
                            static_cast<hipStream_t>(stream), d_prior);
 }

@@ -65,6 +65,8 @@ enum KernelKind {
   K_PRIOR,                                         // the sum-product kernel with the founders' prior per site (famseq_bn_prior_batch)
   K_TRIO_PRIOR,                                    // K_TRIO_PRIOR + form - 1: the trio kernels with the founders' prior per site
   K_MAP_PRIOR = K_TRIO_PRIOR + 3,                  // ... and the MAP kernel
+  K_EVID,                                          // the evidence: log10 likelihood of the site and the hom-ref posterior
+  K_EVID_PRIOR,                                    // ... with the founders' prior per site
   K_COUNT
 };
 
@@ -90,7 +92,7 @@ constexpr int kStages = 3;
 // The device side of the chunked host pipeline: kSlots copies of every array a chunk passes through.  A set only grows
 // (in sites and in bytes per site), so that varying batch sizes do not thrash.
 enum SlotBuf { B_LK, B_FLAGS, B_STATUS, B_PL, B_POST, B_SINGLE, B_GPP, B_FPP, B_FGT, B_TEXT, B_PRIOR, B_COUNT,
-               B_OUT_A = B_POST, B_OUT_B = B_SINGLE };  // (the trio and MAP entries' two outputs)
+               B_OUT_A = B_POST, B_OUT_B = B_SINGLE };  // (the trio, MAP and evidence entries' two outputs)
 struct SlotSet {
   DevBuf buf[kSlots][B_COUNT];
   size_t row[B_COUNT] = {};  // bytes per site of each buffer (0: not allocated)
@@ -137,11 +139,11 @@ struct famseq_ctx {
   famseq::DevBuf d_img, d_tc, d_lut, d_seq, d_col, d_slot;
   std::vector<int32_t> seq_members;
   // the host-buffer entry points: a three-stage pipeline (copy in / compute / copy out, one stream each, so both
-  // directions of the host link run at once) over two buffer slots; the posterior and call entries, the trio and the
-  // MAP entries each have their set (their outputs differ in size by an order of magnitude)
+  // directions of the host link run at once) over two buffer slots; the posterior and call entries, the trio, the MAP
+  // and the evidence entries each have their set (their outputs differ in size by an order of magnitude)
   hipStream_t stream[famseq::kStages] = {nullptr, nullptr, nullptr};  // 0 copy in, 1 compute, 2 copy out
   hipEvent_t ev_in[famseq::kSlots] = {}, ev_done[famseq::kSlots] = {}, ev_out[famseq::kSlots] = {};
-  famseq::SlotSet slots, trio_slots, map_slots;
+  famseq::SlotSet slots, trio_slots, map_slots, evid_slots;
   famseq::DevBuf d_call[famseq::kSlots];  // the generated kernels' call-path arguments (CallIO), one per slot
   famseq::DevBuf d_phase;                 // FAMSEQ_PHASE_CLOCK: kPhases counters
   // device-resident call path (famseq_bn_call_batch_device): its own argument block, what it holds, and scratch rows for
@@ -173,7 +175,7 @@ inline int fail(famseq_ctx *c, int code, const std::string &msg) {
   } while (0)
 
 // ---- kernels.cpp ----
-// The sum-product family (K_ELIM, K_TRIO + form - 1, K_MAP, K_PRIOR, K_TRIO_PRIOR + form - 1, K_MAP_PRIOR): 0, or an error (FAMSEQ_E_ARG: the engine does not serve this
+// The sum-product family (K_ELIM, K_TRIO + form - 1, K_MAP, K_PRIOR, K_TRIO_PRIOR + form - 1, K_MAP_PRIOR, K_EVID, K_EVID_PRIOR): 0, or an error (FAMSEQ_E_ARG: the engine does not serve this
 // pedigree; FAMSEQ_E_HIP) that is not remembered, the next call tries again.
 int load_or_fail(famseq_ctx *c, int kind);
 // The lane kinds and both call-path forms: false when the kernel is unavailable, which is remembered and said once on

@@ -280,6 +280,35 @@ class Emitter {
            "      const double Z_ = Zt_, W_ = Wb_;\n";
   }
 
+  // The evidence (famseq_evidence): Z = sum_g w(g), the sum pass of map_body alone, and W0 = w(0, ..., 0), the weight of the
+  // configuration in which every member is hom-ref: one product of the members' factors in PED order, formed once per site,
+  // outside the cut loop.  Where the likelihoods sit in registers it stands in front of the message passing, where every one
+  // of them has just been read (two registers from there on); where they are read from the lane's row at each use (lean) it
+  // stands behind it, where nothing else is alive while its N loads are in flight (in front, the 64-member kernel spilled
+  // 200 B per lane).  Both carry the scale Z carries: 1e7 per connected component of a loop-free pedigree (the members of
+  // g_.scaled), one 1e7 under conditioning (Lam); evidence_scale_digits() says how many decimal digits that is.
+  // Leaves: Z_, W0_.
+  std::string evidence_body() {
+    std::string w0;
+    for (int c = 0; c < evidence_scale_digits() / 7; ++c) w0 = w0.empty() ? "10000000.0" : "(" + w0 + " * 10000000.0)";
+    for (int p = 0; p < g_.N; ++p)
+      w0 = "(" + w0 + " * " + (m_.mother[p] < 0 ? unscaled_loc(p, 0) : "(" + T(p, 0, 0, 0) + " * " + unscaled_loc(p, 0) + ")") + ")";
+    w0 = "      const double W0_ = " + w0 + ";\n";
+    const std::string front = lean_ ? "" : w0, back = lean_ ? w0 : "";
+    if (g_.cut.empty()) {
+      o_ << front;
+      fence(1);
+      component_sums();
+      o_ << "      const double Z_ = " << times_sums("") << ";\n";
+      fence(1);
+      return o_.str() + back;
+    }
+    return front + cut_loop("      double Zt_ = 0;\n", /*wc=*/false, /*wall=*/true, [&] { o_ << "      Zt_ = Zt_ + Wall;\n"; fence(1); }) +
+           "      const double Z_ = Zt_;\n" + back;
+  }
+  // the decimal digits of scale in evidence_body's Z_ and W0_
+  int evidence_scale_digits() const { return 7 * (g_.cut.empty() ? (int)g_.scaled.size() : 1); }
+
  private:
   // The cut-assignment loop of a pedigree with loops: `decls` (the accumulators) in front, then per assignment as_ of the cut
   // members their genotypes a<k>, their local factors lam<k> and Lam = 1e7 * prod lam<k>, every component's total weight Zc<c>
@@ -475,6 +504,15 @@ class Emitter {
     return std::string(scalar_t_ ? "tcx[" : "tcf[") + num(kind(child) * 27 + 9 * gc + 3 * gm + gf) + "]";
   }
 
+  // member p's local factor at genotype g without the component's scale: lk for a child, prior * lk for a founder (the prior
+  // the model's row, or with site priors the lane's own)
+  std::string unscaled_loc(int p, int g) const {
+    std::string e = "l" + num(p) + "_" + num(g);
+    if (m_.mother[p] < 0)
+      e = "(" + (site_prior_ ? std::string(kind(p) == 0 ? "pm_" : "pa_") + num(g) : "tcf[" + num(kind(p) * 27 + 9 * g) + "]") + " * " + e + ")";
+    return e;
+  }
+
   // member-local factor c{p}_g
   std::string loc(int p) {
     const std::string n = "c" + num(p);
@@ -482,9 +520,7 @@ class Emitter {
       bool scale = false;
       for (int s : g_.scaled) scale |= s == p;
       for (int g = 0; g < 3; ++g) {
-        std::string e = "l" + num(p) + "_" + num(g);
-        if (m_.mother[p] < 0)
-          e = "(" + (site_prior_ ? std::string(kind(p) == 0 ? "pm_" : "pa_") + num(g) : "tcf[" + num(kind(p) * 27 + 9 * g) + "]") + " * " + e + ")";
+        std::string e = unscaled_loc(p, g);
         if (scale) e = "(10000000.0 * " + e + ")";
         // lean: not a variable but a macro — the factor is formed again at each of its two or three uses, from a fresh read of
         // the likelihood, instead of living in a register from the first use to the last (3N doubles: the widest pedigrees'
@@ -914,6 +950,33 @@ std::string map_source(const Model &m, int variant, bool site_prior) {
       << "      LDS_BARRIER();\n"
       << "    }\n";
   d.epilogue = end.str();
+  d.bt = elim_block_threads(m, false);
+  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  return lane_shell(m, d);
+}
+
+// The evidence kernel: the trio kernel's rules.  Outputs per site: loglik = log10 of the data's likelihood under the pedigree
+// (the total weight without the reference's 1e7), pref = the posterior probability that every member is hom-ref, status; any
+// may be null.  A total weight that is not a positive finite number fails the site (status 2); a hom-ref weight of 0 does not.
+std::string evidence_source(const Model &m, int variant, bool site_prior) {
+  const Graph g = graph_or_throw(m);
+  if (variant < 0 || variant >= kEvidenceVariants)
+    throw std::runtime_error("evidence_source: variant must be 0.." + std::to_string(kEvidenceVariants - 1));
+  const int f = variant;
+  EmitOptions eo = emit_options(f, "pg", site_prior);
+  LaneShell d;
+  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
+  d.entry = "famseq_evidence";
+  d.comment = describe("evidence and hom-ref posterior (sum pass)", g, std::to_string(f), site_prior);
+  d.outputs = "double *__restrict__ loglik_g, double *__restrict__ pref_g";
+  d.site_vars = "    double ev_ll = kNaN, ev_p0 = kNaN;\n";
+  Emitter e(m, g, eo);
+  d.body = e.evidence_body() +
+           "      if (!(Z_ > 0 && Z_ <= 1.79769313486231570815e308)) bn_fail = true;\n"
+           "      else { ev_ll = log10(Z_) - " + std::to_string(e.evidence_scale_digits()) + ".0; ev_p0 = W0_ / Z_; }\n";
+  d.epilogue = "    if (loglik_g) __builtin_nontemporal_store(ev_ll, loglik_g + site);\n"
+               "    if (pref_g) __builtin_nontemporal_store(ev_p0, pref_g + site);\n"
+               "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.bt = elim_block_threads(m, false);
   d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
   return lane_shell(m, d);

@@ -60,5 +60,14 @@ constexpr int kMapVariants = 4;
 // site_prior: famseq_map_prior, with a trailing `prior` [n_sites][6] (as trio_source's).
 std::string map_source(const Model &m, int variant, bool site_prior = false);
 
+// The evidence (famseq_evidence_batch).  HIP source of
+// `extern "C" __global__ famseq_evidence(lk, flags, loglik, pref, status, n_sites, tc, lc)`: per site loglik = log10 sum_g prod_m
+// f_m(g_m | g_mother, g_father), the data's likelihood under the pedigree (the sum pass of famseq_map, the reference's 1e7 taken
+// out), and pref = w(0, ..., 0) / sum_g w(g), the posterior probability that every member is hom-ref.  variant 0..3: the fence
+// levels of famseq_elim's.  Throws if the engine does not serve the pedigree.
+constexpr int kEvidenceVariants = 4;
+// site_prior: famseq_evidence_prior, with a trailing `prior` [n_sites][6] (as trio_source's).
+std::string evidence_source(const Model &m, int variant, bool site_prior = false);
+
 }  // namespace famseq
 #endif

@@ -3,7 +3,7 @@
 // Keeps the reference's CLI and file surface for the `-method 1` path:
 //   FamSeq vcf -vcfFile f -pedFile p -output o [-v] [-a] [-d] [-o] [-l loc] [-method 1]
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
-//              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-afTag KEY | -afTagAll KEY]
+//              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-afTag KEY | -afTagAll KEY]
 //   FamSeq LK  -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -18,7 +18,8 @@
 // queued and evaluated in batches on the GPU (famseq_bn_batch) with the output order preserved,
 // -method 2 is the exact sum-product engine (the marginals of the reference's Elston-Stewart peeling), -method 3 (MCMC) is
 // not part of this build, -dnm (vcf mode) adds each child's de novo mutation posterior (DNP) from the trio kernel, and -map (vcf
-// mode) each member's genotype in the most probable joint configuration of the family and that configuration's posterior (JGT, JP).
+// mode) each member's genotype in the most probable joint configuration of the family and that configuration's posterior (JGT, JP),
+// and -siteQ (vcf mode) the family's variant quality and the site's log10 likelihood under the pedigree to the INFO column (FQ, FLL).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -189,6 +190,7 @@ struct Options {
   int num_burn = -999, num_rep = -999;
   bool dnm = false;  // -dnm: a DNP field per sample (vcf mode)
   bool map = false;  // -map: JGT and JP fields per sample (vcf mode)
+  bool siteq = false;  // -siteQ: FQ and FLL keys in the INFO column (vcf mode)
   string af_tag;     // -afTag KEY: the founders' prior of a line from the allele frequency KEY= of its INFO column (vcf mode)
   bool af_conflict = false;  // both -afTag and -afTagAll were given
   bool af_all = false;  // -afTagAll KEY: -afTag KEY, applied to every field a line prints (DNP, JGT and JP too: may go with -dnm / -map)
@@ -323,6 +325,8 @@ int parse_options(int argc, char **argv, Options &o) {
       o.dnm = true;
     } else if (opt == "map") {
       o.map = true;
+    } else if (opt == "siteQ") {
+      o.siteq = true;
     } else if (opt == "afTag" || opt == "afTagAll") {
       i++;
       if (missing(i)) {
@@ -699,6 +703,19 @@ bool map_supported(const Options &o, const Ped &ped) {
   famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
   const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;  // (elim_supported: what load_map asks first)
   if (k < 0) std::cout << "-map cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
+  famseq_destroy(probe);
+  return k >= 0;
+}
+
+// -siteQ: and for the evidence kernel.
+bool siteq_supported(const Options &o, const Ped &ped) {
+  CliModel m;
+  vector<uint8_t> all(ped.n(), 1);
+  if (m.init(ped, all, o.mrate, o.lrc) != 0) return true;  // (the driver reports a bad pedigree itself)
+  char err[512] = {0};
+  famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
+  const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;  // (elim_supported, as above)
+  if (k < 0) std::cout << "-siteQ cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
   famseq_destroy(probe);
   return k >= 0;
 }
@@ -1302,6 +1319,11 @@ bool run_vcf(const Options &o, const Ped &ped) {
               "the whole family\">" << std::endl;
       fout << "##FORMAT=<ID=JP,Number=1,Type=Float,Description=\"Posterior probability of that joint configuration\">" << std::endl;
     }
+    if (o.siteq) {
+      fout << "##INFO=<ID=FQ,Number=1,Type=Float,Description=\"Family variant quality: Phred-scaled posterior probability that every "
+              "member of the family is homozygous reference\">" << std::endl;
+      fout << "##INFO=<ID=FLL,Number=1,Type=Float,Description=\"log10 likelihood of the site's data under the pedigree\">" << std::endl;
+    }
   };
   auto fs_info = [&] {
     fout << "##FS mutation rate=" << o.mrate << " " << std::endl;
@@ -1584,6 +1606,8 @@ bool run_vcf(const Options &o, const Ped &ped) {
     vector<int8_t> jgt;       // -map: [site][member] the MAP configuration ...
     vector<double> jp;        // ... its posterior ...
     vector<uint8_t> jstatus;  // ... and the MAP kernel's status per site
+    vector<double> fll, pref;  // -siteQ: [site] the log10 likelihood and the hom-ref posterior ...
+    vector<uint8_t> estatus;   // ... and the evidence kernel's status per site
   } slots[4];  // one being cut and parsed, one at the GPU, one being formatted, one being written
   bool ok = true;
   for (Slot &sl : slots) sl.parts.resize(n_threads), sl.text.resize(n_threads);
@@ -1657,6 +1681,19 @@ bool run_vcf(const Options &o, const Ped &ped) {
             flush_ok = false;
           }
         }
+        if (o.siteq && flush_ok) {  // and through the evidence kernel (full network as well)
+          sl.fll.resize(sl.n_sites), sl.pref.resize(sl.n_sites), sl.estatus.resize(sl.n_sites);
+          const double *elk = sl.packed ? nullptr : sl.lk.data();
+          const uint16_t *epl = sl.packed ? sl.io.pl : nullptr;
+          const int re = use_af ? famseq_evidence_prior_batch(ctx, (int64_t)sl.n_sites, elk, epl, seq_members.data(), (int32_t)n_seq, sl.io.flags,
+                                                              sl.prior.data(), sl.fll.data(), sl.pref.data(), sl.estatus.data())
+                                : famseq_evidence_batch(ctx, (int64_t)sl.n_sites, elk, epl, seq_members.data(), (int32_t)n_seq, sl.io.flags,
+                                                        sl.fll.data(), sl.pref.data(), sl.estatus.data());
+          if (re != 0) {
+            std::cerr << (use_af ? "famseq_evidence_prior_batch" : "famseq_evidence_batch") << " failed (" << re << "): " << famseq_last_error(ctx) << std::endl;
+            flush_ok = false;
+          }
+        }
       }
       t_gpu += now_s() - t0;
       to_formatter.put(i);
@@ -1687,6 +1724,32 @@ bool run_vcf(const Options &o, const Ped &ped) {
     }
     out.ch('\t');
   };
+  // -siteQ: columns 1-8 + FORMAT of a site with "FQ=<x>;FLL=<y>" joined to its INFO column (an INFO of "." is replaced); a site
+  // whose evidence failed keeps its INFO.  FQ by the drivers' rule for FPP: fabs(-10 log10 p), 99999 for 0 (file.cpp:696-745).
+  auto put_prefix_siteq = [&](TextBuf &out, const Slot &sl, size_t s, const char *raw, size_t len) {
+    size_t info = 0, end = 0;  // the INFO column is raw[info, end): between the seventh and the eighth tab
+    int tabs = 0;
+    for (size_t q = 0; q < len && tabs < 8; ++q)
+      if (raw[q] == '\t') {
+        if (++tabs == 7) info = q + 1;
+        if (tabs == 8) end = q;
+      }
+    if (tabs < 8 || sl.estatus[s] != 0) {
+      out.put(raw, len);
+      return;
+    }
+    out.put(raw, info);
+    if (!(end - info == 1 && raw[info] == '.')) {
+      out.put(raw + info, end - info);
+      if (end > info) out.ch(';');
+    }
+    const double p = sl.pref[s];
+    out.put("FQ=", 3);
+    out.num(p == 0 ? 99999.0 : std::fabs(-10.0 * std::log10(p)));
+    out.put(";FLL=", 5);
+    out.num(sl.fll[s]);
+    out.put(raw + end, len - end);
+  };
   // ... the results are turned into text on their own thread (and its helpers) while the next block is at the GPU ...
   std::thread formatter([&] {
     for (;;) {
@@ -1706,7 +1769,8 @@ bool run_vcf(const Options &o, const Ped &ped) {
             } else {
               const size_t s = size_t(it.site);
               const Record::Sample *sm = &pt.samples[it.smp];
-              out.put(it.raw, it.prefix_len);  // columns 1-8 + FORMAT
+              if (o.siteq) put_prefix_siteq(out, sl, s, it.raw, it.prefix_len);
+              else out.put(it.raw, it.prefix_len);  // columns 1-8 + FORMAT
               out.put(":GPP:FPP:FGT", 12);
               if (o.dnm) out.put(":DNP", 4);
               if (o.map) out.put(":JGT:JP", 7);
@@ -2060,6 +2124,9 @@ void help() {
             << "-dnm\t\t(vcf) Add DNP, each child's posterior probability of a de novo mutation, to every sample column." << std::endl
             << "-map\t\t(vcf) Add JGT and JP, each member's genotype in the most probable joint configuration of the family and" << std::endl
             << "\t\tthat configuration's posterior probability, to every sample column." << std::endl
+            << "-siteQ\t\t(vcf) Add FQ, the Phred-scaled posterior probability that no member of the family carries a variant, and FLL," << std::endl
+            << "\t\tthe log10 likelihood of the site under the pedigree, to the INFO column. Implies -method 2; may be combined with" << std::endl
+            << "\t\t-dnm, -map and -afTagAll; not with -afTag." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl
@@ -2117,6 +2184,11 @@ int main(int argc, char **argv) {
   if (o.dnm && mode == "vcf" && !dnm_supported(o, ped)) return 255;
   if (o.map && mode != "vcf") std::cout << "-map applies to vcf mode only; ignored here." << std::endl;
   if (o.map && mode == "vcf" && !map_supported(o, ped)) return 255;
+  if (o.siteq && mode != "vcf") {
+    std::cout << "-siteQ applies to vcf mode only; ignored here." << std::endl;
+    o.siteq = false;
+  }
+  if (o.siteq && !siteq_supported(o, ped)) return 255;
   if (o.af_conflict) {
     std::cout << "-afTag and -afTagAll cannot be combined: give the INFO key once." << std::endl;
     return -1;
@@ -2125,7 +2197,7 @@ int main(int argc, char **argv) {
     if (mode != "vcf") {
       std::cout << (o.af_all ? "-afTagAll" : "-afTag") << " applies to vcf mode only; ignored here." << std::endl;
       o.af_tag.clear();
-    } else if (!o.af_all && (o.dnm || o.map)) {
+    } else if (!o.af_all && (o.dnm || o.map || o.siteq)) {
       std::cout << "-afTag cannot be combined with -dnm or -map: their kernels use the model's priors, and one output line must not mix two models."
                 << std::endl;
       return -1;
@@ -2135,6 +2207,7 @@ int main(int argc, char **argv) {
       o.method = 2;  // site priors are served by the sum-product engine
     }
   }
+  if (o.siteq) o.method = 2;  // the evidence is the sum-product engine's
   const double t0 = now_s();
   if (o.tune_mode) return run_tune(o, ped) ? 0 : -1;
   const bool ok = o.pl_mode ? run_pl(o, ped) : (o.lk_mode ? run_lk(o, ped) : run_vcf(o, ped));

@@ -66,6 +66,11 @@ KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
     case K_MAP_PRIOR:  // ... and famseq_map's
       return {[&m](int v) { return map_source(m, v, true); }, kMapVariants, 0, false, "famseq_map_prior", elim_block_threads(m),
               [&m](int v) { return map_source(m, v); }};
+    case K_EVID:
+      return {[&m](int v) { return evidence_source(m, v); }, kEvidenceVariants, 0, false, "famseq_evidence", elim_block_threads(m)};
+    case K_EVID_PRIOR:  // ... and famseq_evidence's
+      return {[&m](int v) { return evidence_source(m, v, true); }, kEvidenceVariants, 0, false, "famseq_evidence_prior", elim_block_threads(m),
+              [&m](int v) { return evidence_source(m, v); }};
   }
   throw std::logic_error("kernel_spec: no such kind");
 }
@@ -120,6 +125,8 @@ int load_or_fail(famseq_ctx *c, int kind) {
     return fail(c, FAMSEQ_E_ARG, (kind == K_ELIM ? "elimination engine: " : kind == K_MAP ? "joint MAP call (sum-product engine): "
                                   : kind == K_PRIOR ? "site priors (sum-product engine): "
                                   : kind == K_MAP_PRIOR ? "site priors, joint MAP call (sum-product engine): "
+                                  : kind == K_EVID ? "site evidence (sum-product engine): "
+                                  : kind == K_EVID_PRIOR ? "site priors, site evidence (sum-product engine): "
                                   : is_trio_prior(kind) ? "site priors, trio posteriors (sum-product engine): "
                                                         : "trio posteriors (sum-product engine): ") + why);
   if (load_kernel(c, kind, &why) != 0) return fail(c, FAMSEQ_E_HIP, why);
@@ -167,7 +174,7 @@ bool load_or_remember(famseq_ctx *c, int kind) {
 // a new pick makes stale; the lanes-per-site, sum-product call-path, trio and MAP kernels run their own contests and
 // cannot be moved by one, so they stay loaded.  (The site-prior kernel takes K_ELIM's variant: whoever drops K_ELIM for a
 // new pick drops K_PRIOR with it.  The site-prior trio and MAP kernels take their plain siblings' contests' variants; no pick
-// moves those, and nothing drops a trio or MAP kernel: whoever comes to drop one drops its site-prior form with it.)
+// moves those, and nothing drops a trio, MAP or evidence kernel: whoever comes to drop one drops its site-prior form with it.)
 void drop_lane_kernels(famseq_ctx *c) {
   c->kern[K_LANE].drop();
   c->kern[K_LANE_CALL].drop();
@@ -226,7 +233,8 @@ int grid_for(const famseq_ctx *c, int64_t n_sites) {
 }  // namespace
 
 // The generated kernels share one argument list; what the third and fourth are depends on the kind (posterior and single
-// posterior rows, joint and de novo posteriors, MAP genotypes and their posterior), so they pass through untyped; so does
+// posterior rows, joint and de novo posteriors, MAP genotypes and their posterior, log10 likelihood and hom-ref posterior), so
+// they pass through untyped; so does
 // the ninth, which two kinds take: the call-path forms their CallIO, the site-prior kernel its prior rows.
 hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,
                             void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk, const void *d_ninth) {

@@ -380,6 +380,49 @@ int famseq_map_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double
                                   const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                   int8_t *d_map_gt, double *d_map_post, uint8_t *d_status, void *stream);
 
+/* ---- the evidence: the site's likelihood under the pedigree, and the family's variant quality ---------------------------
+ * The third standard query on the pedigree network, beside the marginals (famseq_bn_batch, famseq_trio_batch) and the most
+ * probable assignment (famseq_map_batch): the total weight itself, which every other kernel forms, divides by and drops.  With
+ * w(g) = prod_m f_m(g_m | g_mother, g_father), f = prior * lk for a founder and T[g | gm, gf] * lk for a child (priors by the
+ * Known flag, chrX tables and male priors by the chrX flag; no 1e7):
+ *   loglik [n_sites] fp64   log10 sum_g w(g): the data's likelihood under the pedigree and the model.  Summed over sites it
+ *              compares mutation rates, founder priors and pedigree hypotheses (a sample swap, non-paternity).  It may be
+ *              positive: likelihood rows and priors need not sum to 1.
+ *   pref   [n_sites] fp64   w(0, ..., 0) / sum_g w(g): the posterior probability that every member is hom-ref, i.e. that the
+ *              site is not variant in this family at all.  Not a product of the members' marginals, which are not independent.
+ *              0.0 where the hom-ref configuration has no weight.
+ *   status [n_sites]        0 OK; 1 the single-posterior failure rule of famseq_bn_batch; 2 the total weight is <= 0 or not
+ *              finite.  There is no -LRC shortcut.  Wherever status != 0, loglik and pref are NaN.
+ * The sum pass of famseq_map_batch on the sum-product engine's graph, O(27 N) per site, for every pedigree that engine serves:
+ * loop-free ones of any size, loops up to three conditioned members; any other gets FAMSEQ_E_ARG with the engine's message.
+ * The kernel is compiled on the first call, or ahead through famseq_set_option "evidence_kernels" = 1 (a plan-only context
+ * generates and cross-compiles it).  famseq_plan_json: "evidence_code_object", "evidence_variant", "evidence_block_threads" (the
+ * sites a workgroup takes per loop trip: one per lane). */
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_map_batch (exactly one of lk / pl16, seq_members / n_seq for
+ * packed input).  Any of loglik / pref / status may be NULL. */
+int famseq_evidence_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                          int32_t n_seq, const uint8_t *flags, double *loglik, double *pref, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
+ * NULL = the default stream) and returns without synchronising. */
+int famseq_evidence_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                 const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_loglik, double *d_pref,
+                                 uint8_t *d_status, void *stream);
+
+/* With the founders' genotype prior given per site: prior[n_sites][6], required, laid out, read (the male half at chrX sites
+ * only; FAMSEQ_FLAG_KNOWN not read) and checked by the host entry (finite, >= 0, else FAMSEQ_E_ARG naming the site) exactly as
+ * for famseq_map_prior_batch.  Given rows that equal the model's constants the outputs are, bit for bit, famseq_evidence_batch's.
+ * The kernel (famseq_evidence_prior) is compiled on the first call or ahead through "evidence_prior_kernels" = 1 and takes the
+ * variant its plain sibling's contest takes.  famseq_plan_json: "evidence_prior_code_object", "evidence_prior_variant".
+ * Nothing is checked of d_prior's contents. */
+int famseq_evidence_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                int32_t n_seq, const uint8_t *flags, const double *prior, double *loglik, double *pref,
+                                uint8_t *status);
+int famseq_evidence_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                       const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                       double *d_loglik, double *d_pref, uint8_t *d_status, void *stream);
+
 /* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] = ((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);
