@@ -158,14 +158,6 @@ def lib():
     L.famseq_call_genotypes.restype = None
     L.famseq_trio_children.argtypes = [C.c_void_p, ip]
     L.famseq_trio_children.restype = C.c_int
-    L.famseq_trio_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, dp, dp, bp]
-    L.famseq_trio_batch.restype = C.c_int
-    L.famseq_trio_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp]
-    L.famseq_trio_batch_device.restype = C.c_int
-    L.famseq_map_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, C.POINTER(C.c_int8), dp, bp]
-    L.famseq_map_batch.restype = C.c_int
-    L.famseq_map_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp]
-    L.famseq_map_batch_device.restype = C.c_int
     L.famseq_bn_prior_batch.argtypes = [C.c_void_p, C.c_int64, dp, bp, dp, dp, dp, bp]
     L.famseq_bn_prior_batch.restype = C.c_int
     L.famseq_bn_prior_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
@@ -175,28 +167,56 @@ def lib():
     L.famseq_bn_prior_call_batch.restype = C.c_int
     L.famseq_hwe_priors.argtypes = [C.c_int64, dp, dp]
     L.famseq_hwe_priors.restype = None
-    L.famseq_trio_prior_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, dp, dp, dp, bp]
-    L.famseq_trio_prior_batch.restype = C.c_int
-    L.famseq_trio_prior_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp, vp]
-    L.famseq_trio_prior_batch_device.restype = C.c_int
-    L.famseq_map_prior_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, dp, C.POINTER(C.c_int8), dp, bp]
-    L.famseq_map_prior_batch.restype = C.c_int
-    L.famseq_map_prior_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp, vp]
-    L.famseq_map_prior_batch_device.restype = C.c_int
-    L.famseq_evidence_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, dp, dp, bp]
-    L.famseq_evidence_batch.restype = C.c_int
-    L.famseq_evidence_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp]
-    L.famseq_evidence_batch_device.restype = C.c_int
-    L.famseq_evidence_prior_batch.argtypes = [C.c_void_p, C.c_int64, dp, C.POINTER(C.c_uint16), ip, C.c_int32, bp, dp, dp, dp, bp]
-    L.famseq_evidence_prior_batch.restype = C.c_int
-    L.famseq_evidence_prior_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, vp, vp, vp, vp]
-    L.famseq_evidence_prior_batch_device.restype = C.c_int
+    # the side products' entries: famseq_<name>[_prior]_batch[_device]
+    u16p = C.POINTER(C.c_uint16)
+    for name, out_a in (("trio", dp), ("map", C.POINTER(C.c_int8)), ("evidence", dp)):
+        for prior in (0, 1):
+            host = getattr(L, "famseq_%s%s_batch" % (name, "_prior" * prior))
+            dev = getattr(L, "famseq_%s%s_batch_device" % (name, "_prior" * prior))
+            host.argtypes = [C.c_void_p, C.c_int64, dp, u16p, ip, C.c_int32, bp] + [dp] * prior + [out_a, dp, bp]
+            dev.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp] + [vp] * prior + [vp, vp, vp, vp]
+            host.restype = dev.restype = C.c_int
     _lib = L
     return L
 
 
 def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
+
+
+_POINTER = {np.dtype(t): C.POINTER(c) for t, c in ((np.float64, C.c_double), (np.uint16, C.c_uint16), (np.int32, C.c_int32),
+                                                  (np.uint8, C.c_uint8), (np.int8, C.c_int8))}
+
+
+def _opt(a):
+    """An optional array as the pointer to its element type (None: NULL)."""
+    return None if a is None else a.ctypes.data_as(_POINTER[a.dtype])
+
+
+def _inputs(n, lk, pl16, seq_members, flags, n_seq_required):
+    """What the entries that take likelihood rows or packed PLs are given: exactly one of lk [S,n,3] and pl16 [S,n_seq,3], the
+    sequenced members and the flags, as contiguous arrays.  -> (lk, pl16, S, seq, n_seq, flags).  n_seq_required: the call
+    path, which takes seq_members with either input (and leaves the flags' shape to the library); otherwise they are read with
+    pl16 only, and the flags must have one byte per site."""
+    seq, n_seq = None, 0
+    if n_seq_required:
+        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+        n_seq = len(seq)
+    if (lk is None) == (pl16 is None):
+        raise ValueError("give exactly one of lk / pl16")
+    if lk is not None:
+        lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, n, 3)
+        s = lk.shape[0]
+    else:
+        if seq is None:
+            seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+            n_seq = len(seq)
+        pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, n_seq, 3)
+        s = pl16.shape[0]
+    fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+    if not n_seq_required and fl is not None and fl.shape != (s,):
+        raise ValueError("flags must have one byte per site")
+    return lk, pl16, s, seq, n_seq, fl
 
 
 def transmission_tables(mrate):
@@ -338,22 +358,10 @@ class Context:
     def bn_call_batch(self, seq_members, lk=None, pl16=None, flags=None):
         """Fused call path: -> (gpp[S,n_seq,3], fpp[S,n_seq,3], fgt[S,n_seq], status[S]).
         Input is either lk [S,N,3] float64 or pl16 [S,n_seq,3] uint16 (VCF column order)."""
-        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-        k = len(seq)
-        if (lk is None) == (pl16 is None):
-            raise ValueError("give exactly one of lk / pl16")
-        if lk is not None:
-            lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
-            s = lk.shape[0]
-        else:
-            pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, k, 3)
-            s = pl16.shape[0]
-        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        lk, pl16, s, seq, k, fl = _inputs(self.n, lk, pl16, seq_members, flags, True)
         gpp, fpp = np.empty((s, k, 3)), np.empty((s, k, 3))
         fgt, status = np.empty((s, k), np.int8), np.zeros(s, np.uint8)
-        rc = lib().famseq_bn_call_batch(self._h, s, None if lk is None else _p(lk, C.c_double),
-                                        None if pl16 is None else _p(pl16, C.c_uint16),
-                                        None if fl is None else _p(fl, C.c_uint8), _p(seq, C.c_int32), k,
+        rc = lib().famseq_bn_call_batch(self._h, s, _opt(lk), _opt(pl16), _opt(fl), _p(seq, C.c_int32), k,
                                         _p(gpp, C.c_double), _p(fpp, C.c_double), _p(fgt, C.c_int8), _p(status, C.c_uint8))
         self._check(rc, "famseq_bn_call_batch")
         return gpp, fpp, fgt, status
@@ -361,25 +369,13 @@ class Context:
     def bn_prior_call_batch(self, seq_members, prior, lk=None, pl16=None, flags=None):
         """bn_call_batch with the founders' prior given per site (prior [S,6] as for bn_prior_batch): separate stages around the
         site-prior kernel.  -> (gpp, fpp, fgt, status)."""
-        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-        k = len(seq)
-        if (lk is None) == (pl16 is None):
-            raise ValueError("give exactly one of lk / pl16")
-        if lk is not None:
-            lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
-            s = lk.shape[0]
-        else:
-            pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, k, 3)
-            s = pl16.shape[0]
+        lk, pl16, s, seq, k, fl = _inputs(self.n, lk, pl16, seq_members, flags, True)
         prior = np.ascontiguousarray(prior, dtype=np.float64)
         if prior.shape != (s, 6):
             raise ValueError("prior must be [n_sites, 6]")
-        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
         gpp, fpp = np.empty((s, k, 3)), np.empty((s, k, 3))
         fgt, status = np.empty((s, k), np.int8), np.zeros(s, np.uint8)
-        rc = lib().famseq_bn_prior_call_batch(self._h, s, None if lk is None else _p(lk, C.c_double),
-                                              None if pl16 is None else _p(pl16, C.c_uint16),
-                                              None if fl is None else _p(fl, C.c_uint8), _p(prior, C.c_double), _p(seq, C.c_int32), k,
+        rc = lib().famseq_bn_prior_call_batch(self._h, s, _opt(lk), _opt(pl16), _opt(fl), _p(prior, C.c_double), _p(seq, C.c_int32), k,
                                               _p(gpp, C.c_double), _p(fpp, C.c_double), _p(fgt, C.c_int8), None, _p(status, C.c_uint8))
         self._check(rc, "famseq_bn_prior_call_batch")
         return gpp, fpp, fgt, status
@@ -387,22 +383,10 @@ class Context:
     def bn_call_text_batch(self, seq_members, lk=None, pl16=None, flags=None):
         """The call path with its outputs as text: -> (records, status).  records[s][j] is the bytes the reference's drivers
         append to sample column j of site s, b"g0,g1,g2:f0,f1,f2:0/1\\t" (file.cpp:696-745), formatted on the device."""
-        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-        k = len(seq)
-        if (lk is None) == (pl16 is None):
-            raise ValueError("give exactly one of lk / pl16")
-        if lk is not None:
-            lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
-            s = lk.shape[0]
-        else:
-            pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, k, 3)
-            s = pl16.shape[0]
-        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        lk, pl16, s, seq, k, fl = _inputs(self.n, lk, pl16, seq_members, flags, True)
         text = np.zeros((s, k, TEXT_STRIDE), np.uint8)
         status = np.zeros(s, np.uint8)
-        rc = lib().famseq_bn_call_text_batch(self._h, s, None if lk is None else _p(lk, C.c_double),
-                                             None if pl16 is None else _p(pl16, C.c_uint16),
-                                             None if fl is None else _p(fl, C.c_uint8), _p(seq, C.c_int32), k,
+        rc = lib().famseq_bn_call_text_batch(self._h, s, _opt(lk), _opt(pl16), _opt(fl), _p(seq, C.c_int32), k,
                                              text.ctypes.data_as(C.c_char_p), _p(status, C.c_uint8))
         self._check(rc, "famseq_bn_call_text_batch")
         return text, status
@@ -425,62 +409,52 @@ class Context:
             lib().famseq_trio_children(self._h, _p(idx, C.c_int32))
         return idx
 
+    def _side_host(self, name, prior, lk, pl16, seq_members, flags, outs):
+        """The host entry of a side product, famseq_<name>_batch or (prior given) famseq_<name>_prior_batch.  outs(S) makes its two
+        output arrays (None: not wanted).  -> (out_a, out_b, status)."""
+        lk, pl16, s, seq, n_seq, fl = _inputs(self.n, lk, pl16, seq_members, flags, False)
+        out_a, out_b = outs(s)
+        status = np.zeros(s, np.uint8)
+        fn = "famseq_%s%s_batch" % (name, "" if prior is None else "_prior")
+        rows = () if prior is None else (_p(_prior_rows(prior, s), C.c_double),)
+        self._check(getattr(lib(), fn)(self._h, s, _opt(lk), _opt(pl16), _opt(seq), n_seq, _opt(fl), *rows, _opt(out_a), _opt(out_b),
+                                       _opt(status)), fn)
+        return out_a, out_b, status
+
+    def _side_device(self, name, n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior, d_a, d_b, d_status, stream):
+        """The device entry of a side product on raw device pointers, famseq_<name>_batch_device or (d_prior not None: an int, 0
+        = not given) famseq_<name>_prior_batch_device."""
+        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
+        fn = "famseq_%s%s_batch_device" % (name, "" if d_prior is None else "_prior")
+        rows = () if d_prior is None else (d_prior or None,)
+        self._check(getattr(lib(), fn)(self._h, int(n_sites), d_lk or None, d_pl16 or None, _p(seq, C.c_int32) if len(seq) else None, len(seq),
+                                       d_flags or None, *rows, d_a or None, d_b or None, d_status or None, stream or None), fn)
+
     def trio_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_joint=True, want_dnm=True):
         """Trio posteriors: -> (children[K], joint[S,K,27] or None, dnm[S,K] or None, status[S]).
         joint[s, k, 9 gc + 3 gm + gf] is the posterior of child k's and its parents' genotypes; dnm[s, k] the mass of the
         entries the mutation-free transmission table rules out.  Input is either lk [S,N,3] float64 or pl16 [S,n_seq,3]
         uint16 in VCF column order (seq_members: their PED indices)."""
-        return self._trio(lk, pl16, seq_members, flags, want_joint, want_dnm, None)
+        return self._trio(None, lk, pl16, seq_members, flags, want_joint, want_dnm)
 
     def trio_prior_batch(self, prior, lk=None, pl16=None, seq_members=None, flags=None, want_joint=True, want_dnm=True):
         """trio_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
         FLAG_CHRX is read).  Rows equal to the model's constants give trio_batch's bits."""
-        return self._trio(lk, pl16, seq_members, flags, want_joint, want_dnm, prior)
+        return self._trio(prior, lk, pl16, seq_members, flags, want_joint, want_dnm)
 
-    def _trio(self, lk, pl16, seq_members, flags, want_joint, want_dnm, prior):
-        if (lk is None) == (pl16 is None):
-            raise ValueError("give exactly one of lk / pl16")
-        children = self.trio_children()
+    def _trio(self, prior, lk, pl16, seq_members, flags, want_joint, want_dnm):
+        children = self.trio_children() if (lk is None) != (pl16 is None) else ()  # (else _inputs says what is wrong)
         k = len(children)
-        seq, n_seq = None, 0
-        if lk is not None:
-            lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
-            s = lk.shape[0]
-        else:
-            seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-            n_seq = len(seq)
-            pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, n_seq, 3)
-            s = pl16.shape[0]
-        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
-        if fl is not None and fl.shape != (s,):
-            raise ValueError("flags must have one byte per site")
-        joint = np.empty((s, k, 27)) if want_joint else None
-        dnm = np.empty((s, k)) if want_dnm else None
-        status = np.zeros(s, np.uint8)
-        head = (self._h, s, None if lk is None else _p(lk, C.c_double), None if pl16 is None else _p(pl16, C.c_uint16),
-                None if seq is None else _p(seq, C.c_int32), n_seq, None if fl is None else _p(fl, C.c_uint8))
-        out = (None if joint is None else _p(joint, C.c_double), None if dnm is None else _p(dnm, C.c_double), _p(status, C.c_uint8))
-        if prior is None:
-            self._check(lib().famseq_trio_batch(*head, *out), "famseq_trio_batch")
-        else:
-            self._check(lib().famseq_trio_prior_batch(*head, _p(_prior_rows(prior, s), C.c_double), *out), "famseq_trio_prior_batch")
-        return children, joint, dnm, status
+        outs = lambda s: (np.empty((s, k, 27)) if want_joint else None, np.empty((s, k)) if want_dnm else None)
+        return (children,) + self._side_host("trio", prior, lk, pl16, seq_members, flags, outs)
 
     def trio_batch_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_joint=0, d_dnm=0, d_status=0, stream=0):
         """Trio posteriors on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
-        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-        rc = lib().famseq_trio_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
-                                            _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_joint or None,
-                                            d_dnm or None, d_status or None, stream or None)
-        self._check(rc, "famseq_trio_batch_device")
+        self._side_device("trio", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_joint, d_dnm, d_status, stream)
 
     def trio_prior_batch_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_joint=0, d_dnm=0, d_status=0, stream=0):
         """trio_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
-        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-        rc = lib().famseq_trio_prior_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
-                                                  _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_prior or None,
-                                                  d_joint or None, d_dnm or None, d_status or None, stream or None)
-        self._check(rc, "famseq_trio_prior_batch_device")
+        self._side_device("trio", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_joint, d_dnm, d_status, stream)
 
     def map_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_gt=True, want_post=True):
         """The joint MAP configuration: -> (map_gt[S,N] int8, map_post[S] float64, status[S] uint8).
@@ -488,57 +462,24 @@ class Context:
         where status != 0), map_post[s] its posterior probability (NaN where status != 0).  Input as trio_batch: either lk
         [S,N,3] float64 or pl16 [S,n_seq,3] uint16 in VCF column order (seq_members: their PED indices).  want_gt / want_post
         False: that output is not computed and returned as None."""
-        return self._map(lk, pl16, seq_members, flags, want_gt, want_post, None)
+        outs = lambda s: (np.empty((s, self.n), np.int8) if want_gt else None, np.empty(s) if want_post else None)
+        return self._side_host("map", None, lk, pl16, seq_members, flags, outs)
 
     def map_prior_batch(self, prior, lk=None, pl16=None, seq_members=None, flags=None, want_gt=True, want_post=True):
         """map_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
         FLAG_CHRX is read).  Rows equal to the model's constants give map_batch's bits."""
-        return self._map(lk, pl16, seq_members, flags, want_gt, want_post, prior)
-
-    def _map(self, lk, pl16, seq_members, flags, want_gt, want_post, prior):
-        if (lk is None) == (pl16 is None):
-            raise ValueError("give exactly one of lk / pl16")
-        seq, n_seq = None, 0
-        if lk is not None:
-            lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
-            s = lk.shape[0]
-        else:
-            seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-            n_seq = len(seq)
-            pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, n_seq, 3)
-            s = pl16.shape[0]
-        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
-        if fl is not None and fl.shape != (s,):
-            raise ValueError("flags must have one byte per site")
-        gt = np.empty((s, self.n), np.int8) if want_gt else None
-        post = np.empty(s) if want_post else None
-        status = np.zeros(s, np.uint8)
-        head = (self._h, s, None if lk is None else _p(lk, C.c_double), None if pl16 is None else _p(pl16, C.c_uint16),
-                None if seq is None else _p(seq, C.c_int32), n_seq, None if fl is None else _p(fl, C.c_uint8))
-        out = (None if gt is None else _p(gt, C.c_int8), None if post is None else _p(post, C.c_double), _p(status, C.c_uint8))
-        if prior is None:
-            self._check(lib().famseq_map_batch(*head, *out), "famseq_map_batch")
-        else:
-            self._check(lib().famseq_map_prior_batch(*head, _p(_prior_rows(prior, s), C.c_double), *out), "famseq_map_prior_batch")
-        return gt, post, status
+        outs = lambda s: (np.empty((s, self.n), np.int8) if want_gt else None, np.empty(s) if want_post else None)
+        return self._side_host("map", prior, lk, pl16, seq_members, flags, outs)
 
     def map_batch_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_map_gt=0, d_map_post=0, d_status=0, stream=0):
         """The joint MAP configuration on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream`
         and returns."""
-        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-        rc = lib().famseq_map_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
-                                           _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_map_gt or None,
-                                           d_map_post or None, d_status or None, stream or None)
-        self._check(rc, "famseq_map_batch_device")
+        self._side_device("map", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_map_gt, d_map_post, d_status, stream)
 
     def map_prior_batch_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_map_gt=0, d_map_post=0, d_status=0,
                                stream=0):
         """map_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
-        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-        rc = lib().famseq_map_prior_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
-                                                 _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_prior or None,
-                                                 d_map_gt or None, d_map_post or None, d_status or None, stream or None)
-        self._check(rc, "famseq_map_prior_batch_device")
+        self._side_device("map", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_map_gt, d_map_post, d_status, stream)
 
     def evidence_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_loglik=True, want_pref=True):
         """The evidence: -> (loglik[S] float64, pref[S] float64, status[S] uint8).
@@ -546,56 +487,23 @@ class Context:
         member is hom-ref (both NaN where status != 0).  Input as map_batch: either lk [S,N,3] float64 or pl16 [S,n_seq,3]
         uint16 in VCF column order (seq_members: their PED indices).  want_loglik / want_pref False: that output is not
         computed and returned as None."""
-        return self._evidence(lk, pl16, seq_members, flags, want_loglik, want_pref, None)
+        outs = lambda s: (np.empty(s) if want_loglik else None, np.empty(s) if want_pref else None)
+        return self._side_host("evidence", None, lk, pl16, seq_members, flags, outs)
 
     def evidence_prior_batch(self, prior, lk=None, pl16=None, seq_members=None, flags=None, want_loglik=True, want_pref=True):
         """evidence_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags
         only FLAG_CHRX is read).  Rows equal to the model's constants give evidence_batch's bits."""
-        return self._evidence(lk, pl16, seq_members, flags, want_loglik, want_pref, prior)
-
-    def _evidence(self, lk, pl16, seq_members, flags, want_loglik, want_pref, prior):
-        if (lk is None) == (pl16 is None):
-            raise ValueError("give exactly one of lk / pl16")
-        seq, n_seq = None, 0
-        if lk is not None:
-            lk = np.ascontiguousarray(lk, dtype=np.float64).reshape(-1, self.n, 3)
-            s = lk.shape[0]
-        else:
-            seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-            n_seq = len(seq)
-            pl16 = np.ascontiguousarray(pl16, dtype=np.uint16).reshape(-1, n_seq, 3)
-            s = pl16.shape[0]
-        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
-        if fl is not None and fl.shape != (s,):
-            raise ValueError("flags must have one byte per site")
-        loglik = np.empty(s) if want_loglik else None
-        pref = np.empty(s) if want_pref else None
-        status = np.zeros(s, np.uint8)
-        head = (self._h, s, None if lk is None else _p(lk, C.c_double), None if pl16 is None else _p(pl16, C.c_uint16),
-                None if seq is None else _p(seq, C.c_int32), n_seq, None if fl is None else _p(fl, C.c_uint8))
-        out = (None if loglik is None else _p(loglik, C.c_double), None if pref is None else _p(pref, C.c_double), _p(status, C.c_uint8))
-        if prior is None:
-            self._check(lib().famseq_evidence_batch(*head, *out), "famseq_evidence_batch")
-        else:
-            self._check(lib().famseq_evidence_prior_batch(*head, _p(_prior_rows(prior, s), C.c_double), *out), "famseq_evidence_prior_batch")
-        return loglik, pref, status
+        outs = lambda s: (np.empty(s) if want_loglik else None, np.empty(s) if want_pref else None)
+        return self._side_host("evidence", prior, lk, pl16, seq_members, flags, outs)
 
     def evidence_batch_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_loglik=0, d_pref=0, d_status=0, stream=0):
         """The evidence on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
-        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-        rc = lib().famseq_evidence_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
-                                                _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_loglik or None,
-                                                d_pref or None, d_status or None, stream or None)
-        self._check(rc, "famseq_evidence_batch_device")
+        self._side_device("evidence", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_loglik, d_pref, d_status, stream)
 
     def evidence_prior_batch_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_loglik=0, d_pref=0, d_status=0,
                                     stream=0):
         """evidence_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
-        seq = np.ascontiguousarray(seq_members, dtype=np.int32)
-        rc = lib().famseq_evidence_prior_batch_device(self._h, int(n_sites), d_lk or None, d_pl16 or None,
-                                                      _p(seq, C.c_int32) if len(seq) else None, len(seq), d_flags or None, d_prior or None,
-                                                      d_loglik or None, d_pref or None, d_status or None, stream or None)
-        self._check(rc, "famseq_evidence_prior_batch_device")
+        self._side_device("evidence", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_loglik, d_pref, d_status, stream)
 
     def g6_probe(self, values):
         """The device formatter alone (famseq_format_probe): -> list of bytes, one per value."""

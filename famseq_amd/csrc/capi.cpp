@@ -226,6 +226,13 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
       return fail(c, FAMSEQ_E_ARG, "the 3^N enumeration serves up to 20 members; this pedigree has " + std::to_string(c->model.n_members));
     if (k == "call_kernels") return 0;  // (the call path of such a pedigree runs as separate stages)
   }
+  // "<stem>_kernels", "<stem>_prior_kernels" of a side product: build (and on a device ctx load) the kernel of that output form now
+  for (const SideProduct &p : side_table())
+    for (bool site_prior : {false, true})
+      if (k == std::string(p.stem) + (site_prior ? "_prior_kernels" : "_kernels")) {
+        if (value < 1 || value > p.n_forms) return fail(c, FAMSEQ_E_ARG, k + " takes " + p.takes);
+        return load_or_fail(c, p.kind_of((int)value, site_prior));
+      }
   PlanOptions saved = c->opt;
   if (k == "fixed_digits") c->opt.fixed_digits = (int)value;
   else if (k == "low_members") c->opt.low_members = (int)value;
@@ -279,33 +286,9 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
     }
     return 0;
   }
-  else if (k == "trio_kernels") {  // build (and on a device ctx load) the trio kernel of that output form now
-    if (value < 1 || value > 3) return fail(c, FAMSEQ_E_ARG, "trio_kernels takes 1 (dnm), 2 (joint) or 3 (both)");
-    return load_or_fail(c, K_TRIO + (int)value - 1);
-  }
-  else if (k == "map_kernels") {  // build (and on a device ctx load) the MAP kernel now
-    if (value != 1) return fail(c, FAMSEQ_E_ARG, "map_kernels takes 1");
-    return load_or_fail(c, K_MAP);
-  }
   else if (k == "prior_kernels") {  // build (and on a device ctx load) the site-prior form of the sum-product kernel now
     if (value != 1) return fail(c, FAMSEQ_E_ARG, "prior_kernels takes 1");
     return load_or_fail(c, K_PRIOR);
-  }
-  else if (k == "trio_prior_kernels") {  // ... and of the trio and MAP kernels' site-prior forms
-    if (value < 1 || value > 3) return fail(c, FAMSEQ_E_ARG, "trio_prior_kernels takes 1 (dnm), 2 (joint) or 3 (both)");
-    return load_or_fail(c, K_TRIO_PRIOR + (int)value - 1);
-  }
-  else if (k == "map_prior_kernels") {
-    if (value != 1) return fail(c, FAMSEQ_E_ARG, "map_prior_kernels takes 1");
-    return load_or_fail(c, K_MAP_PRIOR);
-  }
-  else if (k == "evidence_kernels") {  // build (and on a device ctx load) the evidence kernel now
-    if (value != 1) return fail(c, FAMSEQ_E_ARG, "evidence_kernels takes 1");
-    return load_or_fail(c, K_EVID);
-  }
-  else if (k == "evidence_prior_kernels") {  // ... and its site-prior form
-    if (value != 1) return fail(c, FAMSEQ_E_ARG, "evidence_prior_kernels takes 1");
-    return load_or_fail(c, K_EVID_PRIOR);
   }
   else if (k == "group_digits") {
     if (value < -1 || value > enumgen_max_group_digits(c->model))
@@ -359,21 +342,32 @@ std::string json_str(const std::string &v) {  // paths may hold quotes or backsl
   }
   return o;
 }
-// the trio kernels (famseq_trio_batch): the code object of the form used last, every form's, the variant the contest took
+// One form of a side product: "<stem>[_prior]_code_object" and "..._variant" (trio: of the output form asked for last, with every
+// form's code object and the number of children beside the plain form's).
+std::string side_json(const famseq_ctx *c, const SideProduct &p, bool site_prior) {
+  const int form = p.n_forms == 1 ? 1 : site_prior ? c->trio_prior_last : c->trio_last;
+  const GenKernel *g = form ? &c->kern[p.kind_of(form, site_prior)] : nullptr;
+  const std::string key = std::string(",\"") + p.stem + (site_prior ? "_prior" : "");
+  std::string o = key + "_code_object\":\"" + json_str(g ? g->k.path : std::string()) + "\"";
+  if (p.n_forms > 1 && !site_prior) {
+    o += key + "_code_objects\":[";
+    for (int f = 1; f <= p.n_forms; ++f) o += std::string(f > 1 ? "," : "") + "\"" + json_str(c->kern[p.kind_of(f, false)].k.path) + "\"";
+    o += "]";
+  }
+  o += key + "_variant\":" + std::to_string(g ? g->variant : -1);
+  if (p.n_forms > 1 && !site_prior) o += key + "_children\":" + std::to_string(trio_children(c->model).size());
+  return o;
+}
+// The side products and K_PRIOR.  The key order is the order they came in: trio and MAP, the site-prior forms of the posterior
+// kernel and of those two, then every later product with its site-prior form behind it.
 std::string trio_json(const famseq_ctx *c) {
-  const int f = c->trio_last, fp = c->trio_prior_last;
-  std::string o = ",\"trio_code_object\":\"" + json_str(f ? c->trio(f).k.path : std::string()) + "\",\"trio_code_objects\":[";
-  for (int k = 1; k <= 3; ++k) o += std::string(k > 1 ? "," : "") + "\"" + json_str(c->trio(k).k.path) + "\"";
-  return o + "],\"trio_variant\":" + std::to_string(f ? c->trio(f).variant : -1) + ",\"trio_children\":" +
-         std::to_string(trio_children(c->model).size()) + ",\"map_code_object\":\"" + json_str(c->kern[K_MAP].k.path) + "\",\"map_variant\":" +
-         std::to_string(c->kern[K_MAP].variant) + ",\"prior_code_object\":\"" + json_str(c->kern[K_PRIOR].k.path) + "\",\"prior_variant\":" +
-         std::to_string(c->kern[K_PRIOR].variant) + ",\"trio_prior_code_object\":\"" +
-         json_str(fp ? c->kern[K_TRIO_PRIOR + fp - 1].k.path : std::string()) + "\",\"trio_prior_variant\":" +
-         std::to_string(fp ? c->kern[K_TRIO_PRIOR + fp - 1].variant : -1) + ",\"map_prior_code_object\":\"" +
-         json_str(c->kern[K_MAP_PRIOR].k.path) + "\",\"map_prior_variant\":" + std::to_string(c->kern[K_MAP_PRIOR].variant) +
-         ",\"evidence_code_object\":\"" + json_str(c->kern[K_EVID].k.path) + "\",\"evidence_variant\":" + std::to_string(c->kern[K_EVID].variant) +
-         ",\"evidence_prior_code_object\":\"" + json_str(c->kern[K_EVID_PRIOR].k.path) + "\",\"evidence_prior_variant\":" +
-         std::to_string(c->kern[K_EVID_PRIOR].variant) + ",\"evidence_block_threads\":" + std::to_string(elim_block_threads(c->model));
+  constexpr int n_first = SIDE_MAP + 1;
+  std::string o;
+  for (int i = 0; i < n_first; ++i) o += side_json(c, side_table()[i], false);
+  o += ",\"prior_code_object\":\"" + json_str(c->kern[K_PRIOR].k.path) + "\",\"prior_variant\":" + std::to_string(c->kern[K_PRIOR].variant);
+  for (int i = 0; i < n_first; ++i) o += side_json(c, side_table()[i], true);
+  for (int i = n_first; i < SIDE_COUNT; ++i) o += side_json(c, side_table()[i], false) + side_json(c, side_table()[i], true);
+  return o + ",\"evidence_block_threads\":" + std::to_string(elim_block_threads(c->model));
 }
 }  // namespace
 
@@ -723,7 +717,7 @@ namespace {
 
 int trio_form(const void *joint, const void *dnm) { return (joint ? 2 : 0) | (dnm || !joint ? 1 : 0); }
 
-// Arguments the trio and MAP entries check the same way; loads the kernel of that kind (trio: of the form the outputs ask for).
+// Arguments the side products' entries check the same way; loads the kernel of that kind (trio: of the form the outputs ask for).
 int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl16, const int32_t *seq_members, int32_t n_seq,
                   int kind) {
   int rc = check_input(c, n_sites, lk, pl16, "lk / pl16", false, n_seq);
@@ -738,14 +732,40 @@ int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl
   return 0;
 }
 
-// The device entries of both, plain and site-prior (d_prior): enqueue kernel `kind` on the caller's stream and return.  Packed input is unpacked into likelihood
-// rows this context keeps (grown on demand).
-int side_batch_device(famseq_ctx *c, int kind, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16, const int32_t *seq_members,
-                      int32_t n_seq, const uint8_t *d_flags, void *d_out_a, void *d_out_b, uint8_t *d_status, hipStream_t stream,
-                      const double *d_prior = nullptr) {
-  const int rc = trio_prologue(c, n_sites, d_lk, d_pl16, seq_members, n_seq, kind);
-  if (rc != 0 || n_sites == 0) return rc;
-  if (d_pl16) {
+// What the twelve entries below share.  On the device path (`device`) the arrays are the caller's resident buffers and the
+// kernel is enqueued on `stream`; on the host path they are chunked and pipelined (side_batch) on the product's own buffers.
+// The order of the checks is what callers have come to rely on: a site-prior device entry asks for d_prior before anything
+// else, a site-prior host entry checks its input and its prior rows (prior_ready) first, then every entry trio_prologue.
+struct SideIn {
+  int64_t n_sites;
+  const double *lk;
+  const uint16_t *pl16;
+  const int32_t *seq_members;
+  int32_t n_seq;
+  const uint8_t *flags;
+};
+int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device, const SideIn &in, const double *prior, void *out_a,
+               void *out_b, uint8_t *status, void *stream_ = nullptr) {
+  if (!c) return FAMSEQ_E_ARG;
+  const SideProduct &p = side_table()[id];
+  const int kind = p.kind_of(form, site_prior);
+  const int64_t n_sites = in.n_sites;
+  int rc;
+  if (site_prior && device) {
+    if (n_sites > 0 && !prior) return fail(c, FAMSEQ_E_ARG, "d_prior must be given (six doubles per site)");
+  } else if (site_prior) {
+    if ((rc = check_input(c, n_sites, in.lk, in.pl16, "lk / pl16", false, in.n_seq)) != 0 || (rc = prior_ready(c, n_sites, in.flags, prior, kind)) != 0)
+      return rc;
+  }
+  if ((rc = trio_prologue(c, n_sites, in.lk, in.pl16, in.seq_members, in.n_seq, kind)) != 0 || n_sites == 0) return rc;
+  if (!device) {
+    size_t row[2];
+    p.rows(c->model, row);
+    return side_batch(c, c->side_slots[id], c->kern[kind], n_sites, in.lk, in.pl16, in.n_seq, in.flags, out_a, row[0], out_b, row[1], status, prior);
+  }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const double *d_lk = in.lk;
+  if (in.pl16) {  // packed input is unpacked into likelihood rows this context keeps (grown on demand)
     const int N = c->model.n_members;
     if (c->trio_dev_sites < n_sites) {
       HIP_TRY(c, hipStreamSynchronize(stream));  // nothing of an earlier call may still use what is freed here
@@ -754,130 +774,88 @@ int side_batch_device(famseq_ctx *c, int kind, int64_t n_sites, const double *d_
       c->trio_dev_sites = n_sites;
     }
     d_lk = c->trio_dev_lk.as<double>();
-    HIP_TRY(c, launch_unpack_pl16(d_pl16, c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, n_seq, n_sites, c->trio_dev_lk.as<double>(), stream));
+    HIP_TRY(c, launch_unpack_pl16(in.pl16, c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, in.n_seq, n_sites, c->trio_dev_lk.as<double>(), stream));
   }
-  HIP_TRY(c, launch_generated(c, c->kern[kind], n_sites, d_lk, d_flags, d_out_a, d_out_b, d_status, stream, 0, d_prior));
+  HIP_TRY(c, launch_generated(c, c->kern[kind], n_sites, d_lk, in.flags, out_a, out_b, status, stream, 0, prior));
   return 0;
 }
 
 }  // namespace
 
-// Host buffers: chunked and pipelined (side_batch) on buffers of their own.
+// ---- trio posteriors, the joint MAP configuration, the evidence (the site's log10 likelihood and the hom-ref posterior), each
+// ---- plain and with the founders' prior per site, on host and on resident buffers: side_entry --------------------------------
+
 extern "C" int famseq_trio_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                  int32_t n_seq, const uint8_t *flags, double *joint, double *dnm, uint8_t *status) {
-  if (!c) return FAMSEQ_E_ARG;
-  const int kind = K_TRIO + trio_form(joint, dnm) - 1;
-  const int rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, kind);
-  if (rc != 0 || n_sites == 0) return rc;
-  const size_t K = trio_children(c->model).size();
-  return side_batch(c, c->trio_slots, c->kern[kind], n_sites, lk, pl16, n_seq, flags, joint, 27 * K * sizeof(double), dnm, K * sizeof(double), status);
+  return side_entry(c, SIDE_TRIO, trio_form(joint, dnm), false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, joint, dnm, status);
 }
 
 extern "C" int famseq_trio_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                         const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_joint,
                                         double *d_dnm, uint8_t *d_status, void *stream) {
-  if (!c) return FAMSEQ_E_ARG;
-  return side_batch_device(c, K_TRIO + trio_form(d_joint, d_dnm) - 1, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_joint, d_dnm, d_status,
-                           static_cast<hipStream_t>(stream));
+  return side_entry(c, SIDE_TRIO, trio_form(d_joint, d_dnm), false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_joint,
+                    d_dnm, d_status, stream);
 }
-
-// ---- the joint MAP configuration -------------------------------------------------------------------------------------
-
-extern "C" int famseq_map_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
-                                int32_t n_seq, const uint8_t *flags, int8_t *map_gt, double *map_post, uint8_t *status) {
-  if (!c) return FAMSEQ_E_ARG;
-  const int rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, K_MAP);
-  if (rc != 0 || n_sites == 0) return rc;
-  return side_batch(c, c->map_slots, c->kern[K_MAP], n_sites, lk, pl16, n_seq, flags, map_gt, size_t(c->model.n_members), map_post, sizeof(double),
-                    status);
-}
-
-extern "C" int famseq_map_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
-                                       const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, int8_t *d_map_gt,
-                                       double *d_map_post, uint8_t *d_status, void *stream) {
-  if (!c) return FAMSEQ_E_ARG;
-  return side_batch_device(c, K_MAP, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_map_gt, d_map_post, d_status,
-                           static_cast<hipStream_t>(stream));
-}
-
-// ---- founder priors per site for both ---------------------------------------------------------------------------------
 
 extern "C" int famseq_trio_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                        int32_t n_seq, const uint8_t *flags, const double *prior, double *joint, double *dnm,
                                        uint8_t *status) {
-  if (!c) return FAMSEQ_E_ARG;
-  const int kind = K_TRIO_PRIOR + trio_form(joint, dnm) - 1;
-  int rc = check_input(c, n_sites, lk, pl16, "lk / pl16", false, n_seq);
-  if (rc != 0 || (rc = prior_ready(c, n_sites, flags, prior, kind)) != 0) return rc;
-  if ((rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, kind)) != 0 || n_sites == 0) return rc;
-  const size_t K = trio_children(c->model).size();
-  return side_batch(c, c->trio_slots, c->kern[kind], n_sites, lk, pl16, n_seq, flags, joint, 27 * K * sizeof(double), dnm, K * sizeof(double), status,
-                    prior);
+  return side_entry(c, SIDE_TRIO, trio_form(joint, dnm), true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, joint, dnm, status);
 }
 
 extern "C" int famseq_trio_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                               const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                               double *d_joint, double *d_dnm, uint8_t *d_status, void *stream) {
-  if (!c) return FAMSEQ_E_ARG;
-  if (n_sites > 0 && !d_prior) return fail(c, FAMSEQ_E_ARG, "d_prior must be given (six doubles per site)");
-  return side_batch_device(c, K_TRIO_PRIOR + trio_form(d_joint, d_dnm) - 1, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_joint, d_dnm,
-                           d_status, static_cast<hipStream_t>(stream), d_prior);
+  return side_entry(c, SIDE_TRIO, trio_form(d_joint, d_dnm), true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_joint,
+                    d_dnm, d_status, stream);
+}
+
+extern "C" int famseq_map_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                int32_t n_seq, const uint8_t *flags, int8_t *map_gt, double *map_post, uint8_t *status) {
+  return side_entry(c, SIDE_MAP, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, map_gt, map_post, status);
+}
+
+extern "C" int famseq_map_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                       const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, int8_t *d_map_gt,
+                                       double *d_map_post, uint8_t *d_status, void *stream) {
+  return side_entry(c, SIDE_MAP, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_map_gt, d_map_post, d_status,
+                    stream);
 }
 
 extern "C" int famseq_map_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                       int32_t n_seq, const uint8_t *flags, const double *prior, int8_t *map_gt, double *map_post,
                                       uint8_t *status) {
-  if (!c) return FAMSEQ_E_ARG;
-  int rc = check_input(c, n_sites, lk, pl16, "lk / pl16", false, n_seq);
-  if (rc != 0 || (rc = prior_ready(c, n_sites, flags, prior, K_MAP_PRIOR)) != 0) return rc;
-  if ((rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, K_MAP_PRIOR)) != 0 || n_sites == 0) return rc;
-  return side_batch(c, c->map_slots, c->kern[K_MAP_PRIOR], n_sites, lk, pl16, n_seq, flags, map_gt, size_t(c->model.n_members), map_post,
-                    sizeof(double), status, prior);
+  return side_entry(c, SIDE_MAP, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, map_gt, map_post, status);
 }
 
 extern "C" int famseq_map_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                              const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                              int8_t *d_map_gt, double *d_map_post, uint8_t *d_status, void *stream) {
-  if (!c) return FAMSEQ_E_ARG;
-  if (n_sites > 0 && !d_prior) return fail(c, FAMSEQ_E_ARG, "d_prior must be given (six doubles per site)");
-  return side_batch_device(c, K_MAP_PRIOR, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_map_gt, d_map_post, d_status,
-                           static_cast<hipStream_t>(stream), d_prior);
+  return side_entry(c, SIDE_MAP, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_map_gt, d_map_post, d_status,
+                    stream);
 }
-
-// ---- the evidence: the site's log10 likelihood and the hom-ref posterior ------------------------------------------------
 
 extern "C" int famseq_evidence_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                      int32_t n_seq, const uint8_t *flags, double *loglik, double *pref, uint8_t *status) {
-  if (!c) return FAMSEQ_E_ARG;
-  const int rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, K_EVID);
-  if (rc != 0 || n_sites == 0) return rc;
-  return side_batch(c, c->evid_slots, c->kern[K_EVID], n_sites, lk, pl16, n_seq, flags, loglik, sizeof(double), pref, sizeof(double), status);
+  return side_entry(c, SIDE_EVID, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, loglik, pref, status);
 }
 
 extern "C" int famseq_evidence_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                             const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_loglik,
                                             double *d_pref, uint8_t *d_status, void *stream) {
-  if (!c) return FAMSEQ_E_ARG;
-  return side_batch_device(c, K_EVID, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_loglik, d_pref, d_status,
-                           static_cast<hipStream_t>(stream));
+  return side_entry(c, SIDE_EVID, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_loglik, d_pref, d_status,
+                    stream);
 }
 
 extern "C" int famseq_evidence_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
                                            const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
                                            double *loglik, double *pref, uint8_t *status) {
-  if (!c) return FAMSEQ_E_ARG;
-  int rc = check_input(c, n_sites, lk, pl16, "lk / pl16", false, n_seq);
-  if (rc != 0 || (rc = prior_ready(c, n_sites, flags, prior, K_EVID_PRIOR)) != 0) return rc;
-  if ((rc = trio_prologue(c, n_sites, lk, pl16, seq_members, n_seq, K_EVID_PRIOR)) != 0 || n_sites == 0) return rc;
-  return side_batch(c, c->evid_slots, c->kern[K_EVID_PRIOR], n_sites, lk, pl16, n_seq, flags, loglik, sizeof(double), pref, sizeof(double),
-                    status, prior);
+  return side_entry(c, SIDE_EVID, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, loglik, pref, status);
 }
 
 extern "C" int famseq_evidence_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                                   const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                                   double *d_loglik, double *d_pref, uint8_t *d_status, void *stream) {
-  if (!c) return FAMSEQ_E_ARG;
-  if (n_sites > 0 && !d_prior) return fail(c, FAMSEQ_E_ARG, "d_prior must be given (six doubles per site)");
-  return side_batch_device(c, K_EVID_PRIOR, n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_loglik, d_pref, d_status,
-                           static_cast<hipStream_t>(stream), d_prior);
+  return side_entry(c, SIDE_EVID, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_loglik, d_pref, d_status,
+                    stream);
 }

@@ -53,7 +53,8 @@ struct DevBuf {
   explicit operator bool() const { return p != nullptr; }
 };
 
-// A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp.
+// A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp; the trio,
+// MAP and evidence kinds are the rows of side_table() below.
 enum KernelKind {
   K_LANE = 0,  // K_LANE + d: the enumeration with 3^d lanes per site; d = 0 (one lane per site) serves large batches,
                // d = 1..kEnumMaxGroupDigits batches too small to give every lane of the chip a site (compiled on first use of each d)
@@ -104,6 +105,23 @@ struct SlotSet {
   }
 };
 
+// A side product of the sum-product engine: a generated kernel that takes the common argument list and writes two outputs per
+// site and a status byte, in a plain form and in one that reads the founders' prior per site.  Everything its ABI entries, its
+// prebuild options, its plan keys and its loader differ in is one row of side_table() (kernels.cpp).
+enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
+struct SideProduct {
+  const char *stem;   // "trio": the entry points famseq_trio[_prior], the options trio[_prior]_kernels, the plan keys trio[_prior]_*
+  const char *what;   // load_or_fail's message starts "[site priors, ]<what> (sum-product engine): "
+  const char *takes;  // the values of its prebuild options, as their refusal names them
+  int kind, prior_kind, n_forms;  // output form f = 1 .. n_forms is kind + f - 1, its site-prior form prior_kind + f - 1
+  int n_variants;
+  std::string (*source)(const Model &, int variant, int form, bool site_prior);
+  void (*rows)(const Model &, size_t row[2]);  // bytes per site of the two outputs
+  int kind_of(int form, bool site_prior) const { return (site_prior ? prior_kind : kind) + form - 1; }
+};
+using SideTable = const SideProduct[SIDE_COUNT];
+SideTable &side_table();
+
 }  // namespace famseq
 
 struct famseq_ctx {
@@ -121,7 +139,6 @@ struct famseq_ctx {
   int engine = FAMSEQ_ENGINE_ENUM;
   famseq::GenKernel kern[famseq::K_COUNT];
   famseq::GenKernel &lanes(int d) { return kern[famseq::K_LANE + d]; }
-  const famseq::GenKernel &trio(int form) const { return kern[famseq::K_TRIO + form - 1]; }
   bool plan_only() const { return device < 0; }
   // enumeration engine: the team-per-site kernel is compiled into the library; the lane kernels are generated per
   // pedigree.  enum_impl: -1 auto (lane for large batches), 0 team, 1 lane.  group_digits: -1 auto (by batch size), 0..4 forced.
@@ -139,11 +156,11 @@ struct famseq_ctx {
   famseq::DevBuf d_img, d_tc, d_lut, d_seq, d_col, d_slot;
   std::vector<int32_t> seq_members;
   // the host-buffer entry points: a three-stage pipeline (copy in / compute / copy out, one stream each, so both
-  // directions of the host link run at once) over two buffer slots; the posterior and call entries, the trio, the MAP
-  // and the evidence entries each have their set (their outputs differ in size by an order of magnitude)
+  // directions of the host link run at once) over two buffer slots; the posterior and call entries and every side
+  // product have their set (their outputs differ in size by an order of magnitude)
   hipStream_t stream[famseq::kStages] = {nullptr, nullptr, nullptr};  // 0 copy in, 1 compute, 2 copy out
   hipEvent_t ev_in[famseq::kSlots] = {}, ev_done[famseq::kSlots] = {}, ev_out[famseq::kSlots] = {};
-  famseq::SlotSet slots, trio_slots, map_slots, evid_slots;
+  famseq::SlotSet slots, side_slots[famseq::SIDE_COUNT];
   famseq::DevBuf d_call[famseq::kSlots];  // the generated kernels' call-path arguments (CallIO), one per slot
   famseq::DevBuf d_phase;                 // FAMSEQ_PHASE_CLOCK: kPhases counters
   // device-resident call path (famseq_bn_call_batch_device): its own argument block, what it holds, and scratch rows for
@@ -154,7 +171,7 @@ struct famseq_ctx {
   famseq::DevBuf dev_tmp[7];  // lk, post, single, gpp, fpp, fgt, status
   int64_t dev_tmp_sites = 0;
   int dev_tmp_seq = 0;
-  famseq::DevBuf trio_dev_lk;  // the trio and MAP device entries' likelihood rows for packed input
+  famseq::DevBuf trio_dev_lk;  // the side products' device entries' likelihood rows for packed input
   int64_t trio_dev_sites = 0;
   std::string tune_report;  // what famseq_set_option "tune" measured (famseq_plan_json "tune")
   std::string err, json;
@@ -175,8 +192,8 @@ inline int fail(famseq_ctx *c, int code, const std::string &msg) {
   } while (0)
 
 // ---- kernels.cpp ----
-// The sum-product family (K_ELIM, K_TRIO + form - 1, K_MAP, K_PRIOR, K_TRIO_PRIOR + form - 1, K_MAP_PRIOR, K_EVID, K_EVID_PRIOR): 0, or an error (FAMSEQ_E_ARG: the engine does not serve this
-// pedigree; FAMSEQ_E_HIP) that is not remembered, the next call tries again.
+// The sum-product family (K_ELIM, K_PRIOR and every kind of side_table()): 0, or an error (FAMSEQ_E_ARG: the engine does not serve
+// this pedigree; FAMSEQ_E_HIP) that is not remembered, the next call tries again.
 int load_or_fail(famseq_ctx *c, int kind);
 // The lane kinds and both call-path forms: false when the kernel is unavailable, which is remembered and said once on
 // stderr; the caller falls back (team kernel, separate stages).
@@ -208,7 +225,7 @@ int upload_lut(famseq_ctx *c);
 CallIO make_call_io(const famseq_ctx *c, const uint16_t *d_pl, double *d_gpp, double *d_fpp, int8_t *d_fgt, int32_t n_seq,
                     unsigned long long *d_phase_clk = nullptr);
 int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq);
-// The trio and MAP host entries: lk or packed PLs through kernel `g`, whose two outputs have a_row / b_row bytes per site.
+// The side products' host entries: lk or packed PLs through kernel `g`, whose two outputs have a_row / b_row bytes per site.
 // prior: the site-prior forms' rows [n_sites][6], staged chunk by chunk alongside the likelihoods (NULL: the plain forms).
 int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
                const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior = nullptr);

@@ -679,56 +679,16 @@ famseq_ctx *make_ctx(const Options &o, const Ped &ped, const vector<uint8_t> &se
   return ctx;
 }
 
-// -dnm: does the sum-product engine, which the trio kernel is a form of, serve this pedigree?  Asked on a plan-only context
-// before any input is read.
-bool dnm_supported(const Options &o, const Ped &ped) {
+// -dnm, -map, -siteQ, -afTag / -afTagAll (flag_text: the one to name): does the sum-product engine, which their kernels are forms
+// of, serve this pedigree?  Asked on a plan-only context before any input is read.
+bool sum_product_serves(const Options &o, const Ped &ped, const char *flag_text) {
   CliModel m;
   vector<uint8_t> all(ped.n(), 1);
   if (m.init(ped, all, o.mrate, o.lrc) != 0) return true;  // (the driver reports a bad pedigree itself)
   char err[512] = {0};
   famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
-  const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;
-  if (k < 0) std::cout << "-dnm cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
-  famseq_destroy(probe);
-  return k >= 0;
-}
-
-// -map: the same question for the MAP kernel (another form of the same engine), answered by generating its source's graph: a
-// plan-only context refuses "map_kernels" with the engine's message before anything is compiled.
-bool map_supported(const Options &o, const Ped &ped) {
-  CliModel m;
-  vector<uint8_t> all(ped.n(), 1);
-  if (m.init(ped, all, o.mrate, o.lrc) != 0) return true;  // (the driver reports a bad pedigree itself)
-  char err[512] = {0};
-  famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
-  const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;  // (elim_supported: what load_map asks first)
-  if (k < 0) std::cout << "-map cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
-  famseq_destroy(probe);
-  return k >= 0;
-}
-
-// -siteQ: and for the evidence kernel.
-bool siteq_supported(const Options &o, const Ped &ped) {
-  CliModel m;
-  vector<uint8_t> all(ped.n(), 1);
-  if (m.init(ped, all, o.mrate, o.lrc) != 0) return true;  // (the driver reports a bad pedigree itself)
-  char err[512] = {0};
-  famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
-  const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;  // (elim_supported, as above)
-  if (k < 0) std::cout << "-siteQ cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
-  famseq_destroy(probe);
-  return k >= 0;
-}
-
-// -afTag / -afTagAll: and for the site-prior kernels.
-bool af_supported(const Options &o, const Ped &ped) {
-  CliModel m;
-  vector<uint8_t> all(ped.n(), 1);
-  if (m.init(ped, all, o.mrate, o.lrc) != 0) return true;  // (the driver reports a bad pedigree itself)
-  char err[512] = {0};
-  famseq_ctx *probe = famseq_create_pedigree(&m.p, -1, err, sizeof err);
-  const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;  // (elim_supported, as above)
-  if (k < 0) std::cout << (o.af_all ? "-afTagAll" : "-afTag") << " cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
+  const int k = probe ? famseq_trio_children(probe, nullptr) : FAMSEQ_E_ARG;  // (elim_supported: what every loader asks first)
+  if (k < 0) std::cout << flag_text << " cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
   famseq_destroy(probe);
   return k >= 0;
 }
@@ -1653,46 +1613,31 @@ bool run_vcf(const Options &o, const Ped &ped) {
           std::cerr << (use_af ? "famseq_bn_prior_call_batch" : "famseq_bn_call_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
           flush_ok = false;
         }
-        if (o.dnm && flush_ok) {  // the same batch through the trio kernel (full network, whatever -LRC and -method say)
-          sl.dnm.resize(sl.n_sites * size_t(n_kids)), sl.tstatus.resize(sl.n_sites);
-          // (-afTagAll: under the rows FPP and FGT were computed with)
-          const double *tlk = sl.packed ? nullptr : sl.lk.data();
-          const uint16_t *tpl = sl.packed ? sl.io.pl : nullptr;
-          double *dnm_out = n_kids ? sl.dnm.data() : nullptr;
-          const int rt = use_af ? famseq_trio_prior_batch(ctx, (int64_t)sl.n_sites, tlk, tpl, seq_members.data(), (int32_t)n_seq, sl.io.flags,
-                                                          sl.prior.data(), nullptr, dnm_out, sl.tstatus.data())
-                                : famseq_trio_batch(ctx, (int64_t)sl.n_sites, tlk, tpl, seq_members.data(), (int32_t)n_seq, sl.io.flags, nullptr,
-                                                    dnm_out, sl.tstatus.data());
-          if (rt != 0) {
-            std::cerr << (use_af ? "famseq_trio_prior_batch" : "famseq_trio_batch") << " failed (" << rt << "): " << famseq_last_error(ctx) << std::endl;
+        // the same batch through a side product's kernel (full network, whatever -LRC and -method say; -afTagAll: under the rows FPP
+        // and FGT were computed with): its plain or its site-prior entry, `name` the plain one's
+        auto side = [&](auto plain, auto with_prior, auto *out_a, double *out_b, vector<uint8_t> &status, const char *name) {
+          status.resize(sl.n_sites);
+          const double *lk = sl.packed ? nullptr : sl.lk.data();
+          const uint16_t *pl = sl.packed ? sl.io.pl : nullptr;
+          const int rc = use_af ? with_prior(ctx, (int64_t)sl.n_sites, lk, pl, seq_members.data(), (int32_t)n_seq, sl.io.flags, sl.prior.data(), out_a,
+                                             out_b, status.data())
+                                : plain(ctx, (int64_t)sl.n_sites, lk, pl, seq_members.data(), (int32_t)n_seq, sl.io.flags, out_a, out_b, status.data());
+          if (rc != 0) {
+            std::cerr << name << (use_af ? "_prior_batch" : "_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
             flush_ok = false;
           }
+        };
+        if (o.dnm && flush_ok) {
+          sl.dnm.resize(sl.n_sites * size_t(n_kids));
+          side(famseq_trio_batch, famseq_trio_prior_batch, (double *)nullptr, n_kids ? sl.dnm.data() : nullptr, sl.tstatus, "famseq_trio");
         }
-        if (o.map && flush_ok) {  // and through the MAP kernel (full network as well)
-          sl.jgt.resize(sl.n_sites * size_t(ped.n())), sl.jp.resize(sl.n_sites), sl.jstatus.resize(sl.n_sites);
-          const double *mlk = sl.packed ? nullptr : sl.lk.data();
-          const uint16_t *mpl = sl.packed ? sl.io.pl : nullptr;
-          const int rm = use_af ? famseq_map_prior_batch(ctx, (int64_t)sl.n_sites, mlk, mpl, seq_members.data(), (int32_t)n_seq, sl.io.flags,
-                                                         sl.prior.data(), sl.jgt.data(), sl.jp.data(), sl.jstatus.data())
-                                : famseq_map_batch(ctx, (int64_t)sl.n_sites, mlk, mpl, seq_members.data(), (int32_t)n_seq, sl.io.flags,
-                                                   sl.jgt.data(), sl.jp.data(), sl.jstatus.data());
-          if (rm != 0) {
-            std::cerr << (use_af ? "famseq_map_prior_batch" : "famseq_map_batch") << " failed (" << rm << "): " << famseq_last_error(ctx) << std::endl;
-            flush_ok = false;
-          }
+        if (o.map && flush_ok) {
+          sl.jgt.resize(sl.n_sites * size_t(ped.n())), sl.jp.resize(sl.n_sites);
+          side(famseq_map_batch, famseq_map_prior_batch, sl.jgt.data(), sl.jp.data(), sl.jstatus, "famseq_map");
         }
-        if (o.siteq && flush_ok) {  // and through the evidence kernel (full network as well)
-          sl.fll.resize(sl.n_sites), sl.pref.resize(sl.n_sites), sl.estatus.resize(sl.n_sites);
-          const double *elk = sl.packed ? nullptr : sl.lk.data();
-          const uint16_t *epl = sl.packed ? sl.io.pl : nullptr;
-          const int re = use_af ? famseq_evidence_prior_batch(ctx, (int64_t)sl.n_sites, elk, epl, seq_members.data(), (int32_t)n_seq, sl.io.flags,
-                                                              sl.prior.data(), sl.fll.data(), sl.pref.data(), sl.estatus.data())
-                                : famseq_evidence_batch(ctx, (int64_t)sl.n_sites, elk, epl, seq_members.data(), (int32_t)n_seq, sl.io.flags,
-                                                        sl.fll.data(), sl.pref.data(), sl.estatus.data());
-          if (re != 0) {
-            std::cerr << (use_af ? "famseq_evidence_prior_batch" : "famseq_evidence_batch") << " failed (" << re << "): " << famseq_last_error(ctx) << std::endl;
-            flush_ok = false;
-          }
+        if (o.siteq && flush_ok) {
+          sl.fll.resize(sl.n_sites), sl.pref.resize(sl.n_sites);
+          side(famseq_evidence_batch, famseq_evidence_prior_batch, sl.fll.data(), sl.pref.data(), sl.estatus, "famseq_evidence");
         }
       }
       t_gpu += now_s() - t0;
@@ -2181,14 +2126,14 @@ int main(int argc, char **argv) {
     return -1;
   }
   if (o.dnm && mode != "vcf") std::cout << "-dnm applies to vcf mode only; ignored here." << std::endl;
-  if (o.dnm && mode == "vcf" && !dnm_supported(o, ped)) return 255;
+  if (o.dnm && mode == "vcf" && !sum_product_serves(o, ped, "-dnm")) return 255;
   if (o.map && mode != "vcf") std::cout << "-map applies to vcf mode only; ignored here." << std::endl;
-  if (o.map && mode == "vcf" && !map_supported(o, ped)) return 255;
+  if (o.map && mode == "vcf" && !sum_product_serves(o, ped, "-map")) return 255;
   if (o.siteq && mode != "vcf") {
     std::cout << "-siteQ applies to vcf mode only; ignored here." << std::endl;
     o.siteq = false;
   }
-  if (o.siteq && !siteq_supported(o, ped)) return 255;
+  if (o.siteq && !sum_product_serves(o, ped, "-siteQ")) return 255;
   if (o.af_conflict) {
     std::cout << "-afTag and -afTagAll cannot be combined: give the INFO key once." << std::endl;
     return -1;
@@ -2201,7 +2146,7 @@ int main(int argc, char **argv) {
       std::cout << "-afTag cannot be combined with -dnm or -map: their kernels use the model's priors, and one output line must not mix two models."
                 << std::endl;
       return -1;
-    } else if (!af_supported(o, ped)) {
+    } else if (!sum_product_serves(o, ped, o.af_all ? "-afTagAll" : "-afTag")) {
       return 255;
     } else {
       o.method = 2;  // site priors are served by the sum-product engine

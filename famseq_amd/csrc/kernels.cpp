@@ -11,6 +11,24 @@
 #include "elim_codegen.h"
 
 namespace famseq {
+
+SideTable &side_table() {
+  static SideTable table = {
+      {"trio", "trio posteriors", "1 (dnm), 2 (joint) or 3 (both)", K_TRIO, K_TRIO_PRIOR, 3, kTrioVariants, trio_source,
+       [](const Model &m, size_t row[2]) {  // joint[K][27], dnm[K]
+         const size_t K = trio_children(m).size();
+         row[0] = 27 * K * sizeof(double), row[1] = K * sizeof(double);
+       }},
+      {"map", "joint MAP call", "1", K_MAP, K_MAP_PRIOR, 1, kMapVariants,
+       [](const Model &m, int v, int, bool site_prior) { return map_source(m, v, site_prior); },
+       [](const Model &m, size_t row[2]) { row[0] = size_t(m.n_members), row[1] = sizeof(double); }},  // map_gt[N], map_post
+      {"evidence", "site evidence", "1", K_EVID, K_EVID_PRIOR, 1, kEvidenceVariants,
+       [](const Model &m, int v, int, bool site_prior) { return evidence_source(m, v, site_prior); },
+       [](const Model &, size_t row[2]) { row[0] = row[1] = sizeof(double); }},  // loglik, pref
+  };
+  return table;
+}
+
 namespace {
 
 // How a kind of generated kernel is made.
@@ -18,7 +36,7 @@ struct KernelSpec {
   std::function<std::string(int)> source;  // variant -> HIP source
   int n_variants, first;                   // the variant contest (jit_pick_variant) runs first .. n_variants - 1
   bool honours_pick;                       // a note of the tuner's, keyed by the variant-0 source, names the variant instead
-  const char *entry;
+  std::string entry;
   int block_threads;
   // where given: the kernel whose variant this one takes — that kernel's note, else that kernel's contest, so that a
   // context runs both in one variant whatever the compiler's register allocation makes of either
@@ -26,8 +44,19 @@ struct KernelSpec {
 };
 
 bool is_lane(int kind) { return kind >= K_LANE && kind <= K_LANE + kEnumMaxGroupDigits; }
-bool is_trio(int kind) { return kind >= K_TRIO && kind < K_TRIO + 3; }
-bool is_trio_prior(int kind) { return kind >= K_TRIO_PRIOR && kind < K_TRIO_PRIOR + 3; }
+
+// Which side product a kind belongs to (p == nullptr: none), in which form.
+struct SideKind {
+  const SideProduct *p;
+  bool site_prior;
+  int form;
+};
+SideKind side_of(int kind) {
+  for (const SideProduct &p : side_table())
+    for (bool site_prior : {false, true})
+      if (kind >= p.kind_of(1, site_prior) && kind <= p.kind_of(p.n_forms, site_prior)) return {&p, site_prior, kind - p.kind_of(1, site_prior) + 1};
+  return {nullptr, false, 0};
+}
 
 KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
   const Model &m = c->model;
@@ -35,14 +64,13 @@ KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
     const int d = kind - K_LANE;  // (the lanes-per-site forms always use the 6-member block: no measured pick to honour)
     return {[&m, d](int v) { return enumgen_source(m, v, d); }, kEnumVariants, 0, d == 0, "famseq_enum_lane", enumgen_block_threads(m, d)};
   }
-  if (is_trio(kind)) {
-    const int form = kind - K_TRIO + 1;
-    return {[&m, form](int v) { return trio_source(m, v, form); }, kTrioVariants, 0, false, "famseq_trio", elim_block_threads(m)};
-  }
-  if (is_trio_prior(kind)) {  // the variant famseq_trio of that form takes for the pedigree (its contest): none of its own, as K_PRIOR
-    const int form = kind - K_TRIO_PRIOR + 1;
-    return {[&m, form](int v) { return trio_source(m, v, form, true); }, kTrioVariants, 0, false, "famseq_trio_prior", elim_block_threads(m),
-            [&m, form](int v) { return trio_source(m, v, form); }};
+  if (const SideKind k = side_of(kind); k.p) {
+    const auto source = [&m, k](bool site_prior) { return [&m, k, site_prior](int v) { return k.p->source(m, v, k.form, site_prior); }; };
+    KernelSpec spec{source(k.site_prior), k.p->n_variants, 0, false, std::string("famseq_") + k.p->stem + (k.site_prior ? "_prior" : ""),
+                    elim_block_threads(m)};
+    // a site-prior form takes the variant its plain sibling takes for the pedigree (its contest): none of its own, as K_PRIOR
+    if (k.site_prior) spec.variant_of = source(false);
+    return spec;
   }
   switch (kind) {
     case K_LANE_CALL: {
@@ -58,19 +86,9 @@ KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
     case K_ELIM_CALL:
       return {[&m](int v) { return elim_source(m, v, true); }, kElimCallVariants, elim_first_variant(m, true), false, "famseq_elim",
               elim_block_threads(m, true)};
-    case K_MAP:
-      return {[&m](int v) { return map_source(m, v); }, kMapVariants, 0, false, "famseq_map", elim_block_threads(m)};
     case K_PRIOR:  // the variant famseq_elim takes for the pedigree (its measured pick, "pick_elim", or its contest): none of its own
       return {[&m](int v) { return prior_source(m, v); }, kElimVariants, elim_first_variant(m), true, "famseq_elim_prior", elim_block_threads(m),
               [&m](int v) { return elim_source(m, v); }};
-    case K_MAP_PRIOR:  // ... and famseq_map's
-      return {[&m](int v) { return map_source(m, v, true); }, kMapVariants, 0, false, "famseq_map_prior", elim_block_threads(m),
-              [&m](int v) { return map_source(m, v); }};
-    case K_EVID:
-      return {[&m](int v) { return evidence_source(m, v); }, kEvidenceVariants, 0, false, "famseq_evidence", elim_block_threads(m)};
-    case K_EVID_PRIOR:  // ... and famseq_evidence's
-      return {[&m](int v) { return evidence_source(m, v, true); }, kEvidenceVariants, 0, false, "famseq_evidence_prior", elim_block_threads(m),
-              [&m](int v) { return evidence_source(m, v); }};
   }
   throw std::logic_error("kernel_spec: no such kind");
 }
@@ -117,18 +135,15 @@ int load_kernel(famseq_ctx *c, int kind, std::string *why) {
 }  // namespace
 
 int load_or_fail(famseq_ctx *c, int kind) {
-  if (is_trio(kind)) c->trio_last = kind - K_TRIO + 1;
-  if (is_trio_prior(kind)) c->trio_prior_last = kind - K_TRIO_PRIOR + 1;
+  const SideKind k = side_of(kind);
+  if (k.p && k.p->n_forms > 1) (k.site_prior ? c->trio_prior_last : c->trio_last) = k.form;  // (the trio kernels: famseq_plan_json)
   if (have(c, c->kern[kind])) return 0;
   std::string why;
-  if (!elim_supported(c->model, &why))
-    return fail(c, FAMSEQ_E_ARG, (kind == K_ELIM ? "elimination engine: " : kind == K_MAP ? "joint MAP call (sum-product engine): "
-                                  : kind == K_PRIOR ? "site priors (sum-product engine): "
-                                  : kind == K_MAP_PRIOR ? "site priors, joint MAP call (sum-product engine): "
-                                  : kind == K_EVID ? "site evidence (sum-product engine): "
-                                  : kind == K_EVID_PRIOR ? "site priors, site evidence (sum-product engine): "
-                                  : is_trio_prior(kind) ? "site priors, trio posteriors (sum-product engine): "
-                                                        : "trio posteriors (sum-product engine): ") + why);
+  if (!elim_supported(c->model, &why)) {
+    const std::string what = k.p ? std::string(k.site_prior ? "site priors, " : "") + k.p->what + " (sum-product engine): "
+                                 : kind == K_PRIOR ? "site priors (sum-product engine): " : "elimination engine: ";
+    return fail(c, FAMSEQ_E_ARG, what + why);
+  }
   if (load_kernel(c, kind, &why) != 0) return fail(c, FAMSEQ_E_HIP, why);
   return 0;
 }
@@ -171,10 +186,10 @@ bool load_or_remember(famseq_ctx *c, int kind) {
 
 // A pick (the tuner's note, "pick_lane" / "pick_elim") is read by two loaders only — K_LANE and K_ELIM, the kinds whose
 // kernel_spec honours it — and the lane call-path form takes its block shape from K_LANE's variant.  Those three are what
-// a new pick makes stale; the lanes-per-site, sum-product call-path, trio and MAP kernels run their own contests and
-// cannot be moved by one, so they stay loaded.  (The site-prior kernel takes K_ELIM's variant: whoever drops K_ELIM for a
-// new pick drops K_PRIOR with it.  The site-prior trio and MAP kernels take their plain siblings' contests' variants; no pick
-// moves those, and nothing drops a trio, MAP or evidence kernel: whoever comes to drop one drops its site-prior form with it.)
+// a new pick makes stale; the lanes-per-site and sum-product call-path kernels and the side products (side_table()) run their own
+// contests and cannot be moved by one, so they stay loaded.  (The site-prior kernel takes K_ELIM's variant: whoever drops
+// K_ELIM for a new pick drops K_PRIOR with it.  A side product's site-prior form takes its plain sibling's contest's variant; no
+// pick moves those, and nothing drops a side product's kernel: whoever comes to drop one drops its site-prior form with it.)
 void drop_lane_kernels(famseq_ctx *c) {
   c->kern[K_LANE].drop();
   c->kern[K_LANE_CALL].drop();

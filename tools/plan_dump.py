@@ -9,7 +9,8 @@ of the (fresh) kernel cache.  Run it on both commits and compare the files byte 
     python tools/plan_dump.py OUT.json [--compile] [--root CHECKOUT]
 
 Default: FAMSEQ_JIT_SOURCE_ONLY (nothing is compiled; the variant contest takes its first candidate) over trio, ped5,
-ped10, ped15, random_pedigree(0..5) and a 32-member wide pedigree.  --compile: compile for real, so that the spill
+ped10, ped15, random_pedigree(0..5), a 32-member wide pedigree and four disjoint sib matings (four loops: one more than
+the sum-product engine conditions on, so every kernel of its family is refused).  --compile: compile for real, so that the spill
 contest and the shipped picks decide, over ped10, ped15, random_pedigree(3) (a loop) and a 48-member wide pedigree.
 --root: the checkout whose library is loaded (default: this one)."""
 import argparse
@@ -40,6 +41,10 @@ if args.compile:
 else:
     peds = [(n, fs.synthetic_pedigree(n)) for n in ("trio", "ped5", "ped10", "ped15")]
     peds += [("random%d" % s, random_pedigree(s)[1]) for s in range(6)] + [("wide32", wide_pedigree(32))]
+    o = [10 * b for b in range(4) for _ in range(5)]  # 1 x 2 -> 3, 4; 3 x 4 -> 5, four times over
+    ids = [x + k for x, k in zip(o, [1, 2, 3, 4, 5] * 4)]
+    peds.append(("loops4", fs.Pedigree(ids, [x + k if k else 0 for x, k in zip(o, [0, 0, 2, 2, 4] * 4)],
+                                       [x + k if k else 0 for x, k in zip(o, [0, 0, 1, 1, 3] * 4)], [1, 2, 1, 2, 1] * 4, ["s%d" % i for i in ids])))
 
 
 def kept(key):
@@ -50,7 +55,8 @@ out = {}
 for name, ped in peds:
     ctx = fs.Context(fs.make_model(ped), device=-1)
     steps = [("enum_impl", 1), ("group_digits", 1), ("group_digits", 2), ("engine", fs.ENGINE_ELIM), ("trio_kernels", 1),
-             ("trio_kernels", 3), ("map_kernels", 1), ("call_kernels", 1)]
+             ("trio_kernels", 3), ("map_kernels", 1), ("call_kernels", 1), ("prior_kernels", 1), ("trio_prior_kernels", 3),
+             ("map_prior_kernels", 1), ("evidence_kernels", 1), ("evidence_prior_kernels", 1)]
     refused = []
     for k, v in steps:  # (a pedigree without that many looped members, or one the sum-product engine does not serve, says so)
         try:
