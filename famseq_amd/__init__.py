@@ -85,6 +85,7 @@ ABI_SYMBOLS = [
     "famseq_bn_prior_batch", "famseq_bn_prior_batch_device", "famseq_bn_prior_call_batch", "famseq_hwe_priors",
     "famseq_trio_prior_batch", "famseq_trio_prior_batch_device", "famseq_map_prior_batch", "famseq_map_prior_batch_device",
     "famseq_evidence_batch", "famseq_evidence_batch_device", "famseq_evidence_prior_batch", "famseq_evidence_prior_batch_device",
+    "famseq_loo_batch", "famseq_loo_batch_device", "famseq_loo_prior_batch", "famseq_loo_prior_batch_device",
 ]
 PL_MISSING = 0xFFFF
 
@@ -169,7 +170,7 @@ def lib():
     L.famseq_hwe_priors.restype = None
     # the side products' entries: famseq_<name>[_prior]_batch[_device]
     u16p = C.POINTER(C.c_uint16)
-    for name, out_a in (("trio", dp), ("map", C.POINTER(C.c_int8)), ("evidence", dp)):
+    for name, out_a in (("trio", dp), ("map", C.POINTER(C.c_int8)), ("evidence", dp), ("loo", dp)):
         for prior in (0, 1):
             host = getattr(L, "famseq_%s%s_batch" % (name, "_prior" * prior))
             dev = getattr(L, "famseq_%s%s_batch_device" % (name, "_prior" * prior))
@@ -504,6 +505,31 @@ class Context:
                                     stream=0):
         """evidence_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
         self._side_device("evidence", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_loglik, d_pref, d_status, stream)
+
+    def loo_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_loo=True, want_fit=True):
+        """Leave-one-out posteriors and per-member fit: -> (loo[S,N,3] float64, fit[S,N] float64, status[S] uint8).
+        loo[s, i] is member i's genotype distribution given the likelihood rows of every member but i (for a member whose row
+        is all ones, its posterior); fit[s, i] = sum_a loo[s, i, a] * lk[s, i, a], the predictive likelihood of i's row given
+        its relatives, linear and in the row's own units (0.0: the row is impossible given the relatives).  Both NaN where
+        status != 0.  Input as map_batch: either lk [S,N,3] float64 or pl16 [S,n_seq,3] uint16 in VCF column order
+        (seq_members: their PED indices).  want_loo / want_fit False: that output is not computed and returned as None."""
+        outs = lambda s: (np.empty((s, self.n, 3)) if want_loo else None, np.empty((s, self.n)) if want_fit else None)
+        return self._side_host("loo", None, lk, pl16, seq_members, flags, outs)
+
+    def loo_prior_batch(self, prior, lk=None, pl16=None, seq_members=None, flags=None, want_loo=True, want_fit=True):
+        """loo_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give loo_batch's bits."""
+        outs = lambda s: (np.empty((s, self.n, 3)) if want_loo else None, np.empty((s, self.n)) if want_fit else None)
+        return self._side_host("loo", prior, lk, pl16, seq_members, flags, outs)
+
+    def loo_batch_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_loo=0, d_fit=0, d_status=0, stream=0):
+        """Leave-one-out posteriors and fit on resident buffers (raw device pointers as ints; 0 = not given); enqueues on
+        `stream` and returns."""
+        self._side_device("loo", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_loo, d_fit, d_status, stream)
+
+    def loo_prior_batch_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_loo=0, d_fit=0, d_status=0, stream=0):
+        """loo_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("loo", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_loo, d_fit, d_status, stream)
 
     def g6_probe(self, values):
         """The device formatter alone (famseq_format_probe): -> list of bytes, one per value."""

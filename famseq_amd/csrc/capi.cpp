@@ -367,7 +367,8 @@ std::string trio_json(const famseq_ctx *c) {
   o += ",\"prior_code_object\":\"" + json_str(c->kern[K_PRIOR].k.path) + "\",\"prior_variant\":" + std::to_string(c->kern[K_PRIOR].variant);
   for (int i = 0; i < n_first; ++i) o += side_json(c, side_table()[i], true);
   for (int i = n_first; i < SIDE_COUNT; ++i) o += side_json(c, side_table()[i], false) + side_json(c, side_table()[i], true);
-  return o + ",\"evidence_block_threads\":" + std::to_string(elim_block_threads(c->model));
+  const std::string bt = std::to_string(elim_block_threads(c->model));  // (every side product's kernel runs in these workgroups)
+  return o + ",\"evidence_block_threads\":" + bt + ",\"loo_block_threads\":" + bt;
 }
 }  // namespace
 
@@ -732,7 +733,7 @@ int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl
   return 0;
 }
 
-// What the twelve entries below share.  On the device path (`device`) the arrays are the caller's resident buffers and the
+// What the sixteen entries below share.  On the device path (`device`) the arrays are the caller's resident buffers and the
 // kernel is enqueued on `stream`; on the host path they are chunked and pipelined (side_batch) on the product's own buffers.
 // The order of the checks is what callers have come to rely on: a site-prior device entry asks for d_prior before anything
 // else, a site-prior host entry checks its input and its prior rows (prior_ready) first, then every entry trio_prologue.
@@ -782,7 +783,8 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
 
 }  // namespace
 
-// ---- trio posteriors, the joint MAP configuration, the evidence (the site's log10 likelihood and the hom-ref posterior), each
+// ---- trio posteriors, the joint MAP configuration, the evidence (the site's log10 likelihood and the hom-ref posterior), the
+// ---- leave-one-out posteriors and fit, each
 // ---- plain and with the founders' prior per site, on host and on resident buffers: side_entry --------------------------------
 
 extern "C" int famseq_trio_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
@@ -857,5 +859,28 @@ extern "C" int famseq_evidence_prior_batch_device(famseq_ctx *c, int64_t n_sites
                                                   const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                                   double *d_loglik, double *d_pref, uint8_t *d_status, void *stream) {
   return side_entry(c, SIDE_EVID, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_loglik, d_pref, d_status,
+                    stream);
+}
+
+extern "C" int famseq_loo_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                int32_t n_seq, const uint8_t *flags, double *loo, double *fit, uint8_t *status) {
+  return side_entry(c, SIDE_LOO, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, loo, fit, status);
+}
+
+extern "C" int famseq_loo_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                       const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_loo, double *d_fit,
+                                       uint8_t *d_status, void *stream) {
+  return side_entry(c, SIDE_LOO, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_loo, d_fit, d_status, stream);
+}
+
+extern "C" int famseq_loo_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                      int32_t n_seq, const uint8_t *flags, const double *prior, double *loo, double *fit, uint8_t *status) {
+  return side_entry(c, SIDE_LOO, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, loo, fit, status);
+}
+
+extern "C" int famseq_loo_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                             const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                             double *d_loo, double *d_fit, uint8_t *d_status, void *stream) {
+  return side_entry(c, SIDE_LOO, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_loo, d_fit, d_status,
                     stream);
 }

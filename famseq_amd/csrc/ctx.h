@@ -54,7 +54,7 @@ struct DevBuf {
 };
 
 // A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp; the trio,
-// MAP and evidence kinds are the rows of side_table() below.
+// MAP, evidence and leave-one-out kinds are the rows of side_table() below.
 enum KernelKind {
   K_LANE = 0,  // K_LANE + d: the enumeration with 3^d lanes per site; d = 0 (one lane per site) serves large batches,
                // d = 1..kEnumMaxGroupDigits batches too small to give every lane of the chip a site (compiled on first use of each d)
@@ -68,6 +68,8 @@ enum KernelKind {
   K_MAP_PRIOR = K_TRIO_PRIOR + 3,                  // ... and the MAP kernel
   K_EVID,                                          // the evidence: log10 likelihood of the site and the hom-ref posterior
   K_EVID_PRIOR,                                    // ... with the founders' prior per site
+  K_LOO,                                           // leave-one-out posteriors and the per-member fit
+  K_LOO_PRIOR,                                     // ... with the founders' prior per site
   K_COUNT
 };
 
@@ -93,7 +95,7 @@ constexpr int kStages = 3;
 // The device side of the chunked host pipeline: kSlots copies of every array a chunk passes through.  A set only grows
 // (in sites and in bytes per site), so that varying batch sizes do not thrash.
 enum SlotBuf { B_LK, B_FLAGS, B_STATUS, B_PL, B_POST, B_SINGLE, B_GPP, B_FPP, B_FGT, B_TEXT, B_PRIOR, B_COUNT,
-               B_OUT_A = B_POST, B_OUT_B = B_SINGLE };  // (the trio, MAP and evidence entries' two outputs)
+               B_OUT_A = B_POST, B_OUT_B = B_SINGLE };  // (the side products' two outputs)
 struct SlotSet {
   DevBuf buf[kSlots][B_COUNT];
   size_t row[B_COUNT] = {};  // bytes per site of each buffer (0: not allocated)
@@ -108,7 +110,7 @@ struct SlotSet {
 // A side product of the sum-product engine: a generated kernel that takes the common argument list and writes two outputs per
 // site and a status byte, in a plain form and in one that reads the founders' prior per site.  Everything its ABI entries, its
 // prebuild options, its plan keys and its loader differ in is one row of side_table() (kernels.cpp).
-enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
+enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
 struct SideProduct {
   const char *stem;   // "trio": the entry points famseq_trio[_prior], the options trio[_prior]_kernels, the plan keys trio[_prior]_*
   const char *what;   // load_or_fail's message starts "[site priors, ]<what> (sum-product engine): "

@@ -309,6 +309,51 @@ class Emitter {
   // the decimal digits of scale in evidence_body's Z_ and W0_
   int evidence_scale_digits() const { return 7 * (g_.cut.empty() ? (int)g_.scaled.size() : 1); }
 
+  // Leave-one-out (famseq_loo): for every member p its cavity row k<p>_g, the product of everything the network says of g_p but
+  // p's own likelihood: the founder's prior (a child has none) times the message of every adjacent family.  Member p's
+  // marginal is c<p>_g * prod of the same messages; here the likelihood is left out of the product, never divided out of it
+  // (rows hold exact zeros, where the cavity is finite and positive).  Outputs: loo = k / sum_g k and fit = sum_g k_g l_g /
+  // sum_g k_g = Z / Z_-p.  The reference's 1e7: the prior of a g_.scaled member is taken without it, the messages that reach
+  // the component's other members carry it (through c<scaled>), under conditioning Lam carries it: it stays where the
+  // messages have it and cancels in both outputs, each being a ratio of two sums of one row.
+  // Loops: accumulated over the assignments of the cut members, with the weight of the rest of the network, as
+  // conditioned_body does for marginals.  A cut member k adds, at its assigned genotype, the weight of the assignment
+  // without its own likelihood: Wall's product formed with lam<k> replaced by its prior part (1 for a child).
+  std::string loo_body() {
+    if (g_.cut.empty()) {
+      for (int p = 0; p < g_.N; ++p) loo_out(p, cavity(p));
+      return o_.str();
+    }
+    std::ostringstream decls;
+    for (int p = 0; p < g_.N; ++p) decls << "      double acc" << p << "_0 = 0, acc" << p << "_1 = 0, acc" << p << "_2 = 0;\n";
+    const std::string loop = cut_loop(decls.str(), /*wc=*/true, /*wall=*/false, [&] {
+      for (int p = 0; p < g_.N; ++p) {
+        if (g_.is_cut(p)) {
+          std::string w = "10000000.0";
+          for (int k : g_.cut) {
+            if (k != p) {
+              w = "(" + w + " * lam" + num(k) + ")";
+            } else if (m_.mother[p] < 0) {
+              o_ << "      const double pri" << p << " = a" << p << " == 0 ? " << founder_prior(p, 0) << " : (a" << p << " == 1 ? "
+                 << founder_prior(p, 1) << " : " << founder_prior(p, 2) << ");\n";
+              w = "(" + w + " * pri" + num(p) + ")";
+            }
+          }
+          o_ << "      const double wx" << p << " = " << times_sums(w) << ";\n";
+          for (int g = 0; g < 3; ++g) o_ << "      acc" << p << "_" << g << " += a" << p << " == " << g << " ? wx" << p << " : 0.0;\n";
+          continue;
+        }
+        const std::string k = cavity(p);
+        for (int g = 0; g < 3; ++g)
+          o_ << "      acc" << p << "_" << g << " = __builtin_fma(" << k << "_" << g << ", Wc" << g_.comp[p] << ", acc" << p << "_" << g
+             << ");\n";
+        fence(1);
+      }
+    });
+    for (int p = 0; p < g_.N; ++p) loo_out(p, "acc" + num(p));
+    return loop + o_.str();
+  }
+
  private:
   // The cut-assignment loop of a pedigree with loops: `decls` (the accumulators) in front, then per assignment as_ of the cut
   // members their genotypes a<k>, their local factors lam<k> and Lam = 1e7 * prod lam<k>, every component's total weight Zc<c>
@@ -508,9 +553,12 @@ class Emitter {
   // the model's row, or with site priors the lane's own)
   std::string unscaled_loc(int p, int g) const {
     std::string e = "l" + num(p) + "_" + num(g);
-    if (m_.mother[p] < 0)
-      e = "(" + (site_prior_ ? std::string(kind(p) == 0 ? "pm_" : "pa_") + num(g) : "tcf[" + num(kind(p) * 27 + 9 * g) + "]") + " * " + e + ")";
+    if (m_.mother[p] < 0) e = "(" + founder_prior(p, g) + " * " + e + ")";
     return e;
+  }
+  // founder p's prior at genotype g: the model's row (by the flags, a male's chrX row among them) or the site's own
+  std::string founder_prior(int p, int g) const {
+    return site_prior_ ? std::string(kind(p) == 0 ? "pm_" : "pa_") + num(g) : "tcf[" + num(kind(p) * 27 + 9 * g) + "]";
   }
 
   // member-local factor c{p}_g
@@ -688,6 +736,38 @@ class Emitter {
     std::vector<std::string> in = {loc(p)};
     for (int F : g_.nb[p]) in.push_back(fac2var(F, p));
     products("m" + num(p), in);
+  }
+
+  // member p's cavity row (loo_body): k{p}_g = the founder's prior * prod of the messages of the adjacent families.  A child of
+  // one family and no other: that family's message itself; a founder without a family: its prior.  -> the row's name
+  std::string cavity(int p) {
+    std::vector<std::string> in;
+    for (int F : g_.nb[p]) in.push_back(fac2var(F, p));
+    if (m_.mother[p] >= 0 && in.size() == 1) return in[0];
+    const std::string n = "k" + num(p);
+    for (int g = 0; g < 3; ++g) {
+      o_ << "      const double " << n << "_" << g << " = ";
+      if (m_.mother[p] < 0) o_ << founder_prior(p, g);
+      for (size_t k = 0; k < in.size(); ++k) o_ << (k || m_.mother[p] < 0 ? " * " : "") << in[k] << "_" << g;
+      o_ << ";\n";
+    }
+    return n;
+  }
+
+  // member p's leave-one-out outputs from its unnormalised cavity row `from`: og[3 p + g] = from_g / s and fg[p] = the row's
+  // product with p's likelihood (read again from the row in the lean form) / s, in normalise()'s arithmetic: one reciprocal,
+  // the three (four) divisions behind a real branch for a sum in the subnormal range.  A sum that is not a positive finite
+  // number fails the site.
+  void loo_out(int p, const std::string &from) {
+    auto o3 = [&](int g) { return "og[" + num(3 * p + g) + "]"; };
+    const std::string l = "l" + num(p);
+    o_ << "      { const double s = (" << from << "_0 + " << from << "_1) + " << from << "_2; if (!(s > 0 && s <= 1.79769313486231570815e308)) bn_fail = true;\n"
+       << "        const double t = ((" << from << "_0 * " << l << "_0 + " << from << "_1 * " << l << "_1) + " << from << "_2 * " << l << "_2);\n"
+       << "        if (s < 1e-290) { asm volatile(\"\" ::: \"memory\"); if (og) { " << o3(0) << " = " << from << "_0 / s; " << o3(1) << " = " << from
+       << "_1 / s; " << o3(2) << " = " << from << "_2 / s; } if (fg) fg[" << p << "] = t / s; }\n"
+       << "        else { const double r = 1.0 / s; if (og) { " << o3(0) << " = " << from << "_0 * r; " << o3(1) << " = " << from << "_1 * r; " << o3(2)
+       << " = " << from << "_2 * r; } if (fg) fg[" << p << "] = t * r; } }\n";
+    fence(1);
   }
 
   // row p of the output: `from`_g / sum, with the reference's failure rule (family.cpp:943-954)
@@ -977,6 +1057,36 @@ std::string evidence_source(const Model &m, int variant, bool site_prior) {
   d.epilogue = "    if (loglik_g) __builtin_nontemporal_store(ev_ll, loglik_g + site);\n"
                "    if (pref_g) __builtin_nontemporal_store(ev_p0, pref_g + site);\n"
                "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
+  d.bt = elim_block_threads(m, false);
+  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  return lane_shell(m, d);
+}
+
+// The leave-one-out kernel: the trio kernel's rules.  Outputs per site: loo[3 N] (member p's genotype distribution given every
+// row but its own) and fit[N] (the predictive likelihood of p's row given the others, Z / Z_-p), status; any may be null (a
+// null output's stores fold away).  Stored straight from the lane, as famseq_elim's variants 8..11 store post.  A cavity row
+// whose sum is not a positive finite number fails the site (status 2); a total weight of 0 does not: every fit is 0.0 then.
+std::string loo_source(const Model &m, int variant, bool site_prior) {
+  const Graph g = graph_or_throw(m);
+  if (variant < 0 || variant >= kLooVariants) throw std::runtime_error("loo_source: variant must be 0.." + std::to_string(kLooVariants - 1));
+  const int f = variant;
+  EmitOptions eo = emit_options(f, "pg", site_prior);
+  LaneShell d;
+  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
+  d.entry = "famseq_loo";
+  d.comment = describe("leave-one-out posteriors and fit", g, std::to_string(f), site_prior);
+  d.outputs = "double *__restrict__ loo_g, double *__restrict__ fit_g";
+  d.defines = "#define NMEM " + std::to_string(m.n_members) + "\n";
+  d.site_decls = "    double *og = loo_g ? loo_g + site * W3 : nullptr;\n"
+                 "    double *fg = fit_g ? fit_g + site * NMEM : nullptr;\n"
+                 "    (void)og; (void)fg;\n";
+  d.body = Emitter(m, g, eo).loo_body();
+  d.epilogue =
+      "    if (single_fail || bn_fail) {\n"
+      "      if (og) {\n#pragma unroll 1\n        for (int k = 0; k < W3; ++k) og[k] = kNaN;\n      }\n"
+      "      if (fg) {\n#pragma unroll 1\n        for (int k = 0; k < NMEM; ++k) fg[k] = kNaN;\n      }\n"
+      "    }\n"
+      "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.bt = elim_block_threads(m, false);
   d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
   return lane_shell(m, d);

@@ -69,5 +69,14 @@ constexpr int kEvidenceVariants = 4;
 // site_prior: famseq_evidence_prior, with a trailing `prior` [n_sites][6] (as trio_source's).
 std::string evidence_source(const Model &m, int variant, bool site_prior = false);
 
+// Leave-one-out posteriors and per-member fit (famseq_loo_batch).  HIP source of
+// `extern "C" __global__ famseq_loo(lk, flags, loo, fit, status, n_sites, tc, lc)`: per site and member p (PED order)
+// loo[3 p + g] = P(g_p = g | the likelihood rows of every member but p), from the messages famseq_elim forms with p's own row
+// left out of the product (never divided out), and fit[p] = sum_g loo[3 p + g] lk[3 p + g] = Z / Z_-p, the predictive likelihood
+// of p's row given its relatives.  variant 0..3: the fence levels of famseq_elim's.  Throws if the engine does not serve the pedigree.
+constexpr int kLooVariants = 4;
+// site_prior: famseq_loo_prior, with a trailing `prior` [n_sites][6] (as trio_source's).
+std::string loo_source(const Model &m, int variant, bool site_prior = false);
+
 }  // namespace famseq
 #endif

@@ -3,7 +3,7 @@
 // Keeps the reference's CLI and file surface for the `-method 1` path:
 //   FamSeq vcf -vcfFile f -pedFile p -output o [-v] [-a] [-d] [-o] [-l loc] [-method 1]
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
-//              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-afTag KEY | -afTagAll KEY]
+//              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-loo] [-afTag KEY | -afTagAll KEY]
 //   FamSeq LK  -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -191,6 +191,7 @@ struct Options {
   bool dnm = false;  // -dnm: a DNP field per sample (vcf mode)
   bool map = false;  // -map: JGT and JP fields per sample (vcf mode)
   bool siteq = false;  // -siteQ: FQ and FLL keys in the INFO column (vcf mode)
+  bool loo = false;    // -loo: LOP and LOF fields per sample, the leave-one-out posteriors and the member's fit (vcf mode)
   string af_tag;     // -afTag KEY: the founders' prior of a line from the allele frequency KEY= of its INFO column (vcf mode)
   bool af_conflict = false;  // both -afTag and -afTagAll were given
   bool af_all = false;  // -afTagAll KEY: -afTag KEY, applied to every field a line prints (DNP, JGT and JP too: may go with -dnm / -map)
@@ -327,6 +328,8 @@ int parse_options(int argc, char **argv, Options &o) {
       o.map = true;
     } else if (opt == "siteQ") {
       o.siteq = true;
+    } else if (opt == "loo") {
+      o.loo = true;
     } else if (opt == "afTag" || opt == "afTagAll") {
       i++;
       if (missing(i)) {
@@ -679,7 +682,7 @@ famseq_ctx *make_ctx(const Options &o, const Ped &ped, const vector<uint8_t> &se
   return ctx;
 }
 
-// -dnm, -map, -siteQ, -afTag / -afTagAll (flag_text: the one to name): does the sum-product engine, which their kernels are forms
+// -dnm, -map, -siteQ, -loo, -afTag / -afTagAll (flag_text: the one to name): does the sum-product engine, which their kernels are forms
 // of, serve this pedigree?  Asked on a plan-only context before any input is read.
 bool sum_product_serves(const Options &o, const Ped &ped, const char *flag_text) {
   CliModel m;
@@ -1279,6 +1282,12 @@ bool run_vcf(const Options &o, const Ped &ped) {
               "the whole family\">" << std::endl;
       fout << "##FORMAT=<ID=JP,Number=1,Type=Float,Description=\"Posterior probability of that joint configuration\">" << std::endl;
     }
+    if (o.loo) {
+      fout << "##FORMAT=<ID=LOP,Number=G,Type=Float,Description=\"Phred-scaled genotype probabilities given the data of every other "
+              "member of the family, the sample's own left out\">" << std::endl;
+      fout << "##FORMAT=<ID=LOF,Number=1,Type=Float,Description=\"Phred-scaled predictive likelihood of the sample's data given the "
+              "other members' (99999: impossible given the relatives)\">" << std::endl;
+    }
     if (o.siteq) {
       fout << "##INFO=<ID=FQ,Number=1,Type=Float,Description=\"Family variant quality: Phred-scaled posterior probability that every "
               "member of the family is homozygous reference\">" << std::endl;
@@ -1568,6 +1577,8 @@ bool run_vcf(const Options &o, const Ped &ped) {
     vector<uint8_t> jstatus;  // ... and the MAP kernel's status per site
     vector<double> fll, pref;  // -siteQ: [site] the log10 likelihood and the hom-ref posterior ...
     vector<uint8_t> estatus;   // ... and the evidence kernel's status per site
+    vector<double> loo, fit;   // -loo: [site][member][3] leave-one-out posteriors, [site][member] the members' fit ...
+    vector<uint8_t> lstatus;   // ... and the leave-one-out kernel's status per site
   } slots[4];  // one being cut and parsed, one at the GPU, one being formatted, one being written
   bool ok = true;
   for (Slot &sl : slots) sl.parts.resize(n_threads), sl.text.resize(n_threads);
@@ -1639,6 +1650,10 @@ bool run_vcf(const Options &o, const Ped &ped) {
           sl.fll.resize(sl.n_sites), sl.pref.resize(sl.n_sites);
           side(famseq_evidence_batch, famseq_evidence_prior_batch, sl.fll.data(), sl.pref.data(), sl.estatus, "famseq_evidence");
         }
+        if (o.loo && flush_ok) {
+          sl.loo.resize(sl.n_sites * size_t(ped.n()) * 3), sl.fit.resize(sl.n_sites * size_t(ped.n()));
+          side(famseq_loo_batch, famseq_loo_prior_batch, sl.loo.data(), sl.fit.data(), sl.lstatus, "famseq_loo");
+        }
       }
       t_gpu += now_s() - t0;
       to_formatter.put(i);
@@ -1666,6 +1681,24 @@ bool run_vcf(const Options &o, const Ped &ped) {
       const int gt = sl.jgt[s * size_t(ped.n()) + size_t(seq_members[j])];
       out.put(gt == 0 ? "0/0:" : (gt == 1 ? "0/1:" : "1/1:"), 4);
       out.num(sl.jp[s]);
+    }
+    out.ch('\t');
+  };
+  // -loo: ":<LOP>:<LOF>" before the closing tab of sample j's field — NA:NA where the site or its leave-one-out kernel failed.
+  // Both by the drivers' rule for FPP: fabs(-10 log10 p), 99999 for 0 (file.cpp:696-745).
+  auto put_loo = [&](TextBuf &out, const Slot &sl, size_t s, size_t j, bool failed) {
+    --out.n;
+    out.ch(':');
+    if (failed || sl.lstatus[s] != 0) {
+      out.put("NA:NA", 5);
+    } else {
+      auto phred = [](double p) { return p == 0 ? 99999.0 : std::fabs(-10.0 * std::log10(p)); };
+      const size_t mem = s * size_t(ped.n()) + size_t(seq_members[j]);
+      for (int g = 0; g < 3; ++g) {
+        out.num(phred(sl.loo[3 * mem + size_t(g)]));
+        out.ch(g < 2 ? ',' : ':');
+      }
+      out.num(phred(sl.fit[mem]));
     }
     out.ch('\t');
   };
@@ -1719,6 +1752,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
               out.put(":GPP:FPP:FGT", 12);
               if (o.dnm) out.put(":DNP", 4);
               if (o.map) out.put(":JGT:JP", 7);
+              if (o.loo) out.put(":LOP:LOF", 8);
               out.ch('\t');
               if (sl.io.status[s] & 3) {  // file.cpp:607-620
                 pt.any_failed = true;
@@ -1727,6 +1761,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
                   out.put(":NA:NA:NA\t", 10);
                   if (o.dnm) put_dnp(out, sl, s, j, true);
                   if (o.map) put_map(out, sl, s, j, true);
+                  if (o.loo) put_loo(out, sl, s, j, true);
                 }
               } else {
                 for (size_t j = 0; j < k; ++j) {
@@ -1745,6 +1780,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
                   }
                   if (o.dnm) put_dnp(out, sl, s, j, false);
                   if (o.map) put_map(out, sl, s, j, false);
+                  if (o.loo) put_loo(out, sl, s, j, false);
                 }
               }
             }
@@ -2072,6 +2108,9 @@ void help() {
             << "-siteQ\t\t(vcf) Add FQ, the Phred-scaled posterior probability that no member of the family carries a variant, and FLL," << std::endl
             << "\t\tthe log10 likelihood of the site under the pedigree, to the INFO column. Implies -method 2; may be combined with" << std::endl
             << "\t\t-dnm, -map and -afTagAll; not with -afTag." << std::endl
+            << "-loo\t\t(vcf) Add LOP, the sample's Phred-scaled genotype probabilities given every other member's data with its own" << std::endl
+            << "\t\tleft out, and LOF, the Phred-scaled likelihood of its own data given theirs (99999: impossible given the relatives)," << std::endl
+            << "\t\tto every sample column. Implies -method 2; may be combined with -dnm, -map, -siteQ and -afTagAll; not with -afTag." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl
@@ -2134,6 +2173,11 @@ int main(int argc, char **argv) {
     o.siteq = false;
   }
   if (o.siteq && !sum_product_serves(o, ped, "-siteQ")) return 255;
+  if (o.loo && mode != "vcf") {
+    std::cout << "-loo applies to vcf mode only; ignored here." << std::endl;
+    o.loo = false;
+  }
+  if (o.loo && !sum_product_serves(o, ped, "-loo")) return 255;
   if (o.af_conflict) {
     std::cout << "-afTag and -afTagAll cannot be combined: give the INFO key once." << std::endl;
     return -1;
@@ -2142,7 +2186,7 @@ int main(int argc, char **argv) {
     if (mode != "vcf") {
       std::cout << (o.af_all ? "-afTagAll" : "-afTag") << " applies to vcf mode only; ignored here." << std::endl;
       o.af_tag.clear();
-    } else if (!o.af_all && (o.dnm || o.map || o.siteq)) {
+    } else if (!o.af_all && (o.dnm || o.map || o.siteq || o.loo)) {
       std::cout << "-afTag cannot be combined with -dnm or -map: their kernels use the model's priors, and one output line must not mix two models."
                 << std::endl;
       return -1;
@@ -2152,7 +2196,7 @@ int main(int argc, char **argv) {
       o.method = 2;  // site priors are served by the sum-product engine
     }
   }
-  if (o.siteq) o.method = 2;  // the evidence is the sum-product engine's
+  if (o.siteq || o.loo) o.method = 2;  // the evidence and the leave-one-out kernel are the sum-product engine's
   const double t0 = now_s();
   if (o.tune_mode) return run_tune(o, ped) ? 0 : -1;
   const bool ok = o.pl_mode ? run_pl(o, ped) : (o.lk_mode ? run_lk(o, ped) : run_vcf(o, ped));

@@ -25,6 +25,9 @@ SideTable &side_table() {
       {"evidence", "site evidence", "1", K_EVID, K_EVID_PRIOR, 1, kEvidenceVariants,
        [](const Model &m, int v, int, bool site_prior) { return evidence_source(m, v, site_prior); },
        [](const Model &, size_t row[2]) { row[0] = row[1] = sizeof(double); }},  // loglik, pref
+      {"loo", "leave-one-out posteriors", "1", K_LOO, K_LOO_PRIOR, 1, kLooVariants,
+       [](const Model &m, int v, int, bool site_prior) { return loo_source(m, v, site_prior); },
+       [](const Model &m, size_t row[2]) { row[0] = 3 * size_t(m.n_members) * sizeof(double), row[1] = size_t(m.n_members) * sizeof(double); }},  // loo[N][3], fit[N]
   };
   return table;
 }
@@ -248,7 +251,7 @@ int grid_for(const famseq_ctx *c, int64_t n_sites) {
 }  // namespace
 
 // The generated kernels share one argument list; what the third and fourth are depends on the kind (posterior and single
-// posterior rows, joint and de novo posteriors, MAP genotypes and their posterior, log10 likelihood and hom-ref posterior), so
+// posterior rows, joint and de novo posteriors, MAP genotypes and their posterior, log10 likelihood and hom-ref posterior, leave-one-out rows and fit), so
 // they pass through untyped; so does
 // the ninth, which two kinds take: the call-path forms their CallIO, the site-prior kernel its prior rows.
 hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,

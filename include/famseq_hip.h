@@ -423,6 +423,48 @@ int famseq_evidence_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const d
                                        const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                        double *d_loglik, double *d_pref, uint8_t *d_status, void *stream);
 
+/* ---- leave-one-out posteriors and per-member fit: what the relatives alone say of a member ----------------------------------
+ * Every other entry folds a member's own reads into that member's answer.  This one leaves them out, for every member at once,
+ * from the messages of one pass over the network (with w as for the evidence):
+ *   loo  [n_sites][N][3] fp64   loo[i][a] = P(g_i = a | the likelihood rows of every member but i), normalised over a: member
+ *              i's marginal had its row been (1, 1, 1).  For a member whose row is all ones (not sequenced) its posterior.
+ *              The own row is left out of the product, never divided out: an exact 0 in a row costs nothing.
+ *   fit  [n_sites][N] fp64      sum_a loo[i][a] * lk[i][a] = Z / Z_-i, Z_-i the total weight with row i set to ones: the
+ *              predictive likelihood of member i's row given its relatives, linear (no logarithm), in the units of the row as
+ *              given.  Summed in logs over the sites of a file it is the per-sample statistic for sample swaps, contamination
+ *              and Mendelian errors.  0.0 where the row is impossible given the relatives: a result, not a failure.  Where
+ *              Z > 0, famseq_bn_batch's post[i][a] = loo[i][a] * lk[i][a] / fit[i].
+ *   status [n_sites]        0 OK; 1 the single-posterior failure rule of famseq_bn_batch; 2 some member's unnormalised cavity
+ *              row sums to <= 0 or is not finite.  There is no -LRC shortcut.  Wherever status != 0, loo and fit of the whole
+ *              site are NaN.
+ * O(27 N) per site on the sum-product engine's graph, for every pedigree that engine serves: loop-free ones of any size, loops
+ * up to three conditioned members; any other gets FAMSEQ_E_ARG with the engine's message.  The kernel is compiled on the first
+ * call, or ahead through famseq_set_option "loo_kernels" = 1 (a plan-only context generates and cross-compiles it).
+ * famseq_plan_json: "loo_code_object", "loo_variant", "loo_block_threads" (the sites a workgroup takes per loop trip: one per
+ * lane). */
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_map_batch (exactly one of lk / pl16, seq_members / n_seq for
+ * packed input).  Any of loo / fit / status may be NULL. */
+int famseq_loo_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                     int32_t n_seq, const uint8_t *flags, double *loo, double *fit, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
+ * NULL = the default stream) and returns without synchronising. */
+int famseq_loo_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16, const int32_t *seq_members,
+                            int32_t n_seq, const uint8_t *d_flags, double *d_loo, double *d_fit, uint8_t *d_status, void *stream);
+
+/* With the founders' genotype prior given per site: prior[n_sites][6], required, laid out, read (the male half at chrX sites
+ * only; FAMSEQ_FLAG_KNOWN not read) and checked by the host entry (finite, >= 0, else FAMSEQ_E_ARG naming the site) exactly as
+ * for famseq_map_prior_batch.  Given rows that equal the model's constants the outputs are, bit for bit, famseq_loo_batch's.
+ * The kernel (famseq_loo_prior) is compiled on the first call or ahead through "loo_prior_kernels" = 1 and takes the variant
+ * its plain sibling's contest takes.  famseq_plan_json: "loo_prior_code_object", "loo_prior_variant".  Nothing is checked of
+ * d_prior's contents. */
+int famseq_loo_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                           int32_t n_seq, const uint8_t *flags, const double *prior, double *loo, double *fit, uint8_t *status);
+int famseq_loo_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                  const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior, double *d_loo,
+                                  double *d_fit, uint8_t *d_status, void *stream);
+
 /* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] = ((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);

@@ -56,7 +56,8 @@ for name, ped in peds:
     ctx = fs.Context(fs.make_model(ped), device=-1)
     steps = [("enum_impl", 1), ("group_digits", 1), ("group_digits", 2), ("engine", fs.ENGINE_ELIM), ("trio_kernels", 1),
              ("trio_kernels", 3), ("map_kernels", 1), ("call_kernels", 1), ("prior_kernels", 1), ("trio_prior_kernels", 3),
-             ("map_prior_kernels", 1), ("evidence_kernels", 1), ("evidence_prior_kernels", 1)]
+             ("map_prior_kernels", 1), ("evidence_kernels", 1), ("evidence_prior_kernels", 1), ("loo_kernels", 1),
+             ("loo_prior_kernels", 1)]
     refused = []
     for k, v in steps:  # (a pedigree without that many looped members, or one the sum-product engine does not serve, says so)
         try:
