@@ -392,7 +392,7 @@ extern "C" const char *famseq_plan_json(famseq_ctx *c) {
              ",\"elim_conditioned_members\":" + std::to_string(elim_conditioned_members(c->model)) +
              ",\"elim_blocks_per_cu\":" + std::to_string(elim.blocks_per_cu) + ",\"enum_lane_variant\":" +
              std::to_string(lane.variant) + ",\"enum_lane_blocks_per_cu\":" + std::to_string(lane.blocks_per_cu) +
-             ",\"enum_group_digits\":" + std::to_string(c->group_digits) + ",\"enum_group_digits_max\":" +
+             ",\"enum_lane_first_variant\":" + std::to_string(lane_first_variant(c)) + ",\"enum_group_digits\":" + std::to_string(c->group_digits) + ",\"enum_group_digits_max\":" +
              std::to_string(enumgen_max_group_digits(c->model)) + ",\"enum_group_digits_last\":" +
              std::to_string(c->last_group_digits) + ",\"enum_group_code_objects\":[";
   for (int d = 1; d <= kEnumMaxGroupDigits; ++d) c->json += std::string(d > 1 ? "," : "") + "\"" + json_str(c->lanes(d).k.path) + "\"";

@@ -146,6 +146,7 @@ struct famseq_ctx {
   // pedigree.  enum_impl: -1 auto (lane for large batches), 0 team, 1 lane.  group_digits: -1 auto (by batch size), 0..4 forced.
   int enum_impl = -1;
   int group_digits = -1, last_group_digits = 0;
+  int lane_first = -1;  // where the lane kernel's variant contest starts (lane_first_variant(): worked out once per context)
   int lane_reads_rows = -1;  // does the lane call-path kernel re-read fp64 rows from global memory (unknown until it is built)
   int trio_last = 0;         // the trio output form asked for last (famseq_plan_json)
   int trio_prior_last = 0;   // ... and of the site-prior trio kernels
@@ -201,6 +202,7 @@ int load_or_fail(famseq_ctx *c, int kind);
 // stderr; the caller falls back (team kernel, separate stages).
 bool load_or_remember(famseq_ctx *c, int kind);
 void drop_lane_kernels(famseq_ctx *c);  // what a new pick of the lane variant makes stale
+int lane_first_variant(const famseq_ctx *c);  // 4 where the lane kernel has the once-per-site form (variants 4-7), else 0
 hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,
                             void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk = 0, const void *d_ninth = nullptr);
 hipError_t launch_engine(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, double *d_post, double *d_single,

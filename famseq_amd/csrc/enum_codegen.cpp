@@ -16,10 +16,15 @@
 //     3^sl accumulators run over the whole site and are summed into the super-leaf members'
 //     marginals at the end; the other unrolled members receive block sums (Q) per prefix, the
 //     looped ones block totals kept in the lane's LDS row.
+//   * where the super-leaf table depends on no prefix digit and a cost model agrees (lane_form), the same step is taken one
+//     level further out: the innermost looped member joins the block, prefix tables that mention no loop digit are built once
+//     per site into the lane's LDS row, and the prefix members' marginals are formed after the loops (Gen, "The once-per-site
+//     form"): lane variants 4-7 (enum_codegen.h); FAMSEQ_LANE_HOIST=0 keeps the per-prefix text there too.
 // The generic team-per-site kernel remains the fallback (small batches, no compiler at run time).
 #include "enum_codegen.h"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <functional>
 #include <map>
@@ -123,10 +128,37 @@ class Gen {
   // instruction, no VGPR) and the founders' priors are folded into their likelihood slots once per site;
   // prefetch 1: the entries the innermost loop's tables need are loaded one step ahead (loop-carried SGPRs), 2: so are
   // that loop's LDS reads — everything the next step's table statements wait for is in flight during this step's block
-  Gen(const Model &m, const Shape &s, int row_len, int fixed = 0, bool late = false, bool scalar_t = false, int prefetch = 0)
+  // once: the form whose prefix tables are built once per site (see plan_once())
+  Gen(const Model &m, const Shape &s, int row_len, int fixed = 0, bool late = false, bool scalar_t = false, int prefetch = 0,
+      bool once = false)
       : m_(m), s_(s), nu_((int)s.unrolled.size()), row_len_(row_len), fixed_(fixed), S_(late ? "srow" : "row"),
         O_(late ? "q" : "row"), outer_(s.outer), st_(scalar_t && !s.outer.empty()),
-        pre_(scalar_t && fixed < (int)s.outer.size() ? prefetch : 0) {}
+        pre_(scalar_t && fixed < (int)s.outer.size() && !once ? prefetch : 0), once_(once) {}
+
+  // The innermost looped member, if it may join the unrolled block as its outermost prefix level: its digit feeds
+  // only factor tables of prefix levels (none of the super-leaf's), another loop remains outside it, and the block
+  // stays at seven members.  -1: none.  `ordered` receives the looped members in loop order.
+  int joinable_member(std::vector<int> *ordered) {
+    prepare();
+    *ordered = outer_;
+    // (an explicit FAMSEQ_LANE_CAP bounds the block whichever way it grows)
+    if ((int)outer_.size() - fixed_ < 2 || nu_ + 1 > std::min(7, env_int("FAMSEQ_LANE_CAP", 7)) || sl_ < 2) return -1;
+    const int c = outer_.back();
+    for (int k = 0; k < nu_; ++k) {
+      const int p = s_.unrolled[k];
+      if (m_.mother[p] >= 0 && (m_.mother[p] == c || m_.father[p] == c) && k >= nu_ - sl_) return -1;
+    }
+    return c;
+  }
+
+  // Can this shape take the once-per-site form, with `row_len_` doubles of LDS per lane?
+  bool once_feasible() {
+    if (!once_ || !st_ || fixed_ != 0 || std::getenv("FAMSEQ_LANE_LAZY")) return false;
+    prepare();
+    if (sl_ < 2 || env_int("FAMSEQ_LANE_JOINT", 1) == 0) return false;
+    if (!dep_[nu_ - sl_].empty() || nu_ - sl_ < 1) return false;
+    return plan_once();
+  }
 
   // Lanes-per-site mode, last step (the group's first lane, after the column sums): normalise,
   // failure rule (family.cpp:943-954).
@@ -176,13 +208,19 @@ class Gen {
     });
   }
 
-  std::string body() {
-    pin_style_ = env_int("FAMSEQ_LANE_PIN", pin_style_);  // tuning aid
+  void prepare() {
     compute_deps();
     choose_superleaf();
     order_outer_loops();
+  }
+
+  std::string body() {
+    pin_style_ = env_int("FAMSEQ_LANE_PIN", pin_style_);  // tuning aid
+    prepare();
     const int no = (int)outer_.size(), row_len = row_len_;
     l_in_lds_ = 6 * no <= row_len;
+    lik_base_ = 3 * no;
+    if (once_ && !plan_once()) throw std::logic_error("enumeration codegen: the once-per-site form does not fit this shape");
     o_ << "      // outer (looped) members:";
     for (int p : outer_) o_ << " " << p;
     o_ << " | unrolled block:";
@@ -199,14 +237,17 @@ class Gen {
     for (int k = 0; k < no; ++k)
       for (int g = 0; g < 3; ++g) {
         o_ << "      " << S_ << "[" << 3 * k + g << "] = 0;\n";
-        if (l_in_lds_) o_ << "      " << S_ << "[" << 3 * no + 3 * k + g << "] = " << l_name(outer_[k], g) << ";\n";
+        if (l_in_lds_) o_ << "      " << S_ << "[" << lik_base_ + 3 * k + g << "] = " << l_name(outer_[k], g) << ";\n";
       }
     // The unrolled members' likelihoods are needed only where their tables are rebuilt (outer loop
     // levels).  What is left of the LDS row holds them for the members whose tables sit in the
     // deepest loops (read 3^depth times per site: +3 % on ped10); the others are re-read from the
     // site's own row in global memory there (L2 hits).  Either way 6 registers per member stay free
     // for the block.
-    {
+    if (once_) {
+      for (const auto &kv : lds_slot_)
+        for (int g = 0; g < 3; ++g) o_ << "      " << S_ << "[" << kv.second + g << "] = l" << kv.first << "_" << g << ";\n";
+    } else {
       const std::vector<int> wb = table_buckets();
       std::vector<int> order;
       for (int k = 0; k < nu_; ++k)
@@ -230,6 +271,7 @@ class Gen {
     joint_ = joint_ && env_int("FAMSEQ_LANE_JOINT", 1) != 0;  // tuning aid
     for (int k = 0; k < nu_; ++k) {
       if (joint_ && k >= nu_ - sl_) continue;
+      if (once_ && k < np_) continue;  // formed after the loops (site_walk)
       const int p = s_.unrolled[k];
       o_ << "      double b" << p << "_0 = 0, b" << p << "_1 = 0, b" << p << "_2 = 0;\n";
     }
@@ -240,7 +282,9 @@ class Gen {
     o_ << "      const double P_root = 10000000.0;\n";  // family.cpp:911
     tables();
     o_ << bucket_[0];
+    if (once_) once_before_loops();
     outer_level(0, "P_root", "");
+    if (once_) once_after_loops();
     for (int k = 0; k < no; ++k)
       o_ << "      const double b" << outer_[k] << "_0 = " << S_ << "[" << 3 * k << "], b" << outer_[k] << "_1 = " << S_ << "[" << 3 * k + 1
          << "], b" << outer_[k] << "_2 = " << S_ << "[" << 3 * k + 2 << "];\n";
@@ -298,6 +342,7 @@ class Gen {
   std::vector<int> outer_;  // looped members, outermost first
   const bool st_;           // see the constructor
   const int pre_;
+  const bool once_;
   std::string prologue_, prefetch_;  // (pre_) before the innermost loop / inside it, between its table statements and the block
   std::map<std::string, std::string> tq_;  // (pre_) table entry (index text with the innermost digit as '@') -> its loop-carried variable
   std::ostringstream o_;
@@ -358,7 +403,7 @@ class Gen {
     const int p = outer_[k];
     const int no = (int)outer_.size();
     const std::string g = "g" + num(p), ind(6 + 2 * k, ' ');
-    const std::string lk_g = l_in_lds_ ? S_ + "[" + num(3 * no + 3 * (int)k) + " + " + g + "]"
+    const std::string lk_g = l_in_lds_ ? S_ + "[" + num(lik_base_ + 3 * (int)k) + " + " + g + "]"
                                        : "(" + g + " == 0 ? " + l_name(p, 0) + " : (" + g + " == 1 ? " + l_name(p, 1) + " : " + l_name(p, 2) + "))";
     const bool inner = pre_ > 0 && (int)k == inner_pos();
     const bool carried_l = inner && pre_ >= 2 && l_in_lds_;
@@ -489,6 +534,7 @@ class Gen {
     const auto it = lds_slot_.find(p);
     if (it != lds_slot_.end()) return S_ + "[" + num(it->second + g) + "]";
     if (before_loops_.count(p)) return "l" + num(p) + "_" + num(g);  // used once, ahead of all loops: still in registers
+    if (once_) return "l" + num(p) + "_" + num(g);  // (the once-per-site form has the registers: nothing is re-read from global memory)
     return "lg[" + num(3 * p + g) + "]";
   }
 
@@ -548,6 +594,11 @@ class Gen {
           if (mu) suffix += "m" + num(gm);
           if (fu) suffix += "f" + num(gf);
           for (int g = 0; g < 3; ++g) {
+            if (once_ && k < np_ && const_lvl_[k]) {  // built once per site, kept in the lane's LDS row
+              o << "      " << S_ << "[" << tslot_[k] + ((gm * (fu ? 3 : 1) + gf) * 3 + g) << "] = " << t_tab(p) << "["
+                << t_index(p, num(g), mu ? gm : -1, fu ? gf : -1) << "] * " << lk_src(p, g) << ";\n";
+              continue;
+            }
             o << ind << "const double w" << p << "_" << g << suffix << " = ";
             if (pre_ > 0 && has && wb[k] == innermost) {
               // rebuilt in the innermost loop: the entry comes from the variable loaded a step ahead, the likelihood — the
@@ -585,6 +636,7 @@ class Gen {
     }
     // block sums, deepest level first
     for (int k = nu_ - 1; k >= 0; --k) {
+      if (once_ && k < np_) break;  // no block sums per prefix in this form
       std::ostringstream o;
       const int nd = (int)dep_[k].size();
       std::vector<int> dig(nu_, 0);
@@ -638,6 +690,222 @@ class Gen {
       walk(k0, "");
     }
     bucket_[qb[k0] + 1] += o.str();
+  }
+
+  // ---- The once-per-site form (once_) -------------------------------------------------------------------------------
+  // Every weight of an outer step is P x (product of the prefix levels' table entries) x W[c].  Where the
+  // super-leaf table W depends on no prefix digit (dep_[nu_ - sl_] empty), everything but the 3^N configuration
+  // FMAs factors:
+  //   * a prefix level whose table mentions no loop digit ("constant": a founder, or a child of unrolled
+  //     members only) has the same entries in every step: they are formed once per site and chrX pass, kept in
+  //     the lane's LDS row and read where a prefix product is formed (one group of reads ahead of their use);
+  //   * the block total of a step is P Q sum_c v_c C_c: Q the sum of W, v_c the product of the tables that ARE
+  //     rebuilt per step (c: the digits they mention, D_), C_c the sum of the constant tables' products over the
+  //     other prefix digits — taken once per site, ahead of the loops;
+  //   * the prefix members' marginals need no per-step work beyond U_c += P Q v_c: after the loops one walk of
+  //     the prefix tree with U_c in the place of the per-step tables yields all of them (site_walk).
+  // Sums of non-negative terms in the order written here: results differ from the per-prefix form's in their
+  // last bits and are bit-reproducible.
+  int np_ = 0;                    // prefix levels: unrolled levels above the super-leaf
+  int lik_base_ = 0;              // first LDS slot of the looped members' likelihoods
+  std::vector<char> const_lvl_;   // prefix level -> its table mentions no loop digit
+  std::vector<int> tslot_;        // ... and the first slot of that table in the lane's LDS row
+  std::vector<int> D_;            // prefix levels whose digits the per-step tables mention, ascending
+  std::vector<std::vector<std::pair<int, int>>> groups_;  // table entries (level, offset) read together, in walk order
+  std::map<std::string, int> consumer_;                   // tree node (its digits; "" = root) below which a group is first used
+
+  int t_entries(int k) const {
+    const int p = s_.unrolled[k];
+    int e = 3;
+    if (m_.mother[p] >= 0) e *= (s_.upos[m_.mother[p]] >= 0 ? 3 : 1) * (s_.upos[m_.father[p]] >= 0 ? 3 : 1);
+    return e;
+  }
+  int t_off(int k, int g, const std::vector<int> &dig) const {  // the order tables() writes a level's entries in
+    const int p = s_.unrolled[k];
+    int o = 0;
+    if (m_.mother[p] >= 0) {
+      if (s_.upos[m_.mother[p]] >= 0) o = dig[s_.upos[m_.mother[p]]];
+      if (s_.upos[m_.father[p]] >= 0) o = 3 * o + dig[s_.upos[m_.father[p]]];
+    }
+    return 3 * o + g;
+  }
+  std::string t_var(int k, int off) const { return "t" + num(s_.unrolled[k]) + "_" + num(off); }
+  static std::string node_key(int k, const std::vector<int> &dig) {
+    std::string n;
+    for (int j = 0; j <= k; ++j) n += char('0' + dig[j]);
+    return n;
+  }
+  int dcode(const std::vector<int> &dig) const {
+    int c = 0;
+    for (size_t i = D_.size(); i-- > 0;) c = 3 * c + dig[D_[i]];
+    return c;
+  }
+  int max_prefix_parent(int k) const {  // deepest prefix level whose digit level k's table mentions, -1: none
+    const int p = s_.unrolled[k];
+    int j = -1;
+    if (m_.mother[p] >= 0)
+      for (int par : {m_.mother[p], m_.father[p]}) j = std::max(j, s_.upos[par]);
+    return j;
+  }
+
+  // Slots of the lane's LDS row, the digits the per-step tables mention and the read groups.  false: no room, or more
+  // than two such digits (3^|D| values per step).
+  bool plan_once() {
+    const int no = (int)outer_.size();
+    np_ = nu_ - sl_;
+    const std::vector<int> wb = table_buckets();
+    const_lvl_.assign(nu_, 0);
+    tslot_.assign(nu_, -1);
+    D_.clear();
+    lds_slot_.clear();
+    before_loops_.clear();
+    int next = 3 * no;
+    std::set<int> d;
+    for (int k = 0; k < np_; ++k) {
+      if (wb[k] < 0) {
+        const_lvl_[k] = 1;
+        tslot_[k] = next;
+        next += t_entries(k);
+        continue;
+      }
+      d.insert(k);
+      const int p = s_.unrolled[k];
+      for (int par : {m_.mother[p], m_.father[p]})
+        if (s_.upos[par] >= 0) d.insert(s_.upos[par]);
+    }
+    if (next > row_len_ || d.size() > 2) return false;
+    D_.assign(d.begin(), d.end());
+    // likelihoods the table statements inside the loops read: deepest loop first, while there is room (tables());
+    // the looped members' own behind them, all or none
+    std::vector<int> order;
+    for (int k = 0; k < nu_; ++k)
+      if (wb[k] >= 0) order.push_back(k);
+      else before_loops_.insert(s_.unrolled[k]);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return wb[a] > wb[b]; });
+    for (int k : order) {
+      if (next + 3 > row_len_) break;
+      lds_slot_[s_.unrolled[k]] = next;
+      next += 3;
+    }
+    l_in_lds_ = next + 3 * no <= row_len_;
+    lik_base_ = next;
+    // read groups: the entries that become known at a node of the prefix tree, in walk order; a group opens only once
+    // configuration FMAs lie between it and the one before (the root's entries and the first subtree's are one group)
+    groups_.clear();
+    consumer_.clear();
+    std::vector<int> dig(nu_, 0);
+    bool work_since = true;
+    std::function<void(int)> node = [&](int j) {  // node at level j (-1: the root), its digits in dig
+      std::vector<std::pair<int, int>> here;
+      for (int k = j + 1; k < np_; ++k)
+        if (const_lvl_[k] && max_prefix_parent(k) == j)
+          for (int g = 0; g < 3; ++g) here.push_back({k, t_off(k, g, dig)});
+      if (!here.empty()) {
+        if (work_since) {
+          consumer_[node_key(j, dig)] = (int)groups_.size();
+          groups_.push_back({});
+          work_since = false;
+        }
+        groups_.back().insert(groups_.back().end(), here.begin(), here.end());
+      }
+      if (j == np_ - 1) {
+        work_since = true;
+        return;
+      }
+      for (int g = 0; g < 3; ++g) {
+        dig[j + 1] = g;
+        node(j + 1);
+      }
+    };
+    node(-1);
+    return true;
+  }
+
+  void fetch_group(int i, const std::string &ind) {
+    // (the clobber: these reads are repeated in every step on purpose — left to itself the compiler may keep the
+    // tables in registers across the block instead)
+    o_ << ind << "asm volatile(\"\" ::: \"memory\");\n";
+    for (const auto &e : groups_[i]) o_ << ind << t_var(e.first, e.second) << " = " << S_ << "[" << tslot_[e.first] + e.second << "];\n";
+  }
+
+  // product of the per-step tables' entries for combination c of the digits in D_ (a table entry, or a new variable)
+  std::string step_value(int c, const std::string &ind) {
+    std::vector<int> dig(nu_, 0);
+    for (int l : D_) {
+      dig[l] = c % 3;
+      c /= 3;
+    }
+    std::string v;
+    for (int k = 0; k < np_; ++k) {
+      if (const_lvl_[k]) continue;
+      const std::string w = w_name(k, dig[k], dig);
+      if (v.empty()) {
+        v = w;
+        continue;
+      }
+      const std::string n = "v" + num(uid_++);
+      o_ << ind << "const double " << n << " = " << v << " * " << w << ";\n";
+      v = n;
+    }
+    return v.empty() ? "1.0" : v;
+  }
+
+  // One walk of the prefix tree over the constant tables (read from the LDS row), outside the loops.
+  // final = false: C_c += the product, per combination c of the digits in D_.
+  // final = true : U_c joins the product at the deepest level of D_; every prefix member's marginal receives the sum
+  //                of the weights below each of its digits (sums of three, level by level).
+  void site_walk(bool final) {
+    const std::string ind = "      ";
+    const int at = D_.empty() ? 0 : D_.back();
+    std::vector<int> dig(nu_, 0);
+    std::function<std::string(int, const std::string &)> walk = [&](int k, const std::string &P) -> std::string {
+      const int p = s_.unrolled[k];
+      std::string sub[3];
+      for (int g = 0; g < 3; ++g) {
+        dig[k] = g;
+        std::string cur = P;
+        auto times = [&](const std::string &f) {
+          if (cur.empty()) {
+            cur = f;
+            return;
+          }
+          const std::string n = "h" + num(uid_++);
+          o_ << ind << "const double " << n << " = " << cur << " * " << f << ";\n";
+          cur = n;
+        };
+        if (final && k == at) times("U_" + num(dcode(dig)));
+        if (const_lvl_[k]) times(S_ + "[" + num(tslot_[k] + t_off(k, g, dig)) + "]");
+        if (k < np_ - 1) sub[g] = walk(k + 1, cur);
+        else {
+          sub[g] = cur.empty() ? "1.0" : cur;
+          if (!final) o_ << ind << "C_" << dcode(dig) << " = C_" << dcode(dig) << " + " << sub[g] << ";\n";
+        }
+        if (final) o_ << ind << "b" << p << "_" << g << " = b" << p << "_" << g << " + " << sub[g] << ";\n";
+      }
+      if (!final) return "";
+      const std::string n = "h" + num(uid_++);
+      o_ << ind << "const double " << n << " = (" << sub[0] << " + " << sub[1] << ") + " << sub[2] << ";\n";
+      return n;
+    };
+    walk(0, "");
+  }
+
+  void once_before_loops() {
+    for (int c = 0; c < pow3((int)D_.size()); ++c) o_ << "      double C_" << c << " = 0, U_" << c << " = 0;\n";
+    site_walk(false);
+    std::set<std::string> declared;  // (an entry belongs to several groups where its table skips a level's digit)
+    for (const auto &grp : groups_)
+      for (const auto &e : grp)
+        if (declared.insert(t_var(e.first, e.second)).second) o_ << "      double " << t_var(e.first, e.second) << ";\n";
+    if (!groups_.empty()) fetch_group(0, "      ");
+  }
+
+  void once_after_loops() {
+    for (int k = 0; k < np_; ++k) {
+      const int p = s_.unrolled[k];
+      o_ << "      double b" << p << "_0 = 0, b" << p << "_1 = 0, b" << p << "_2 = 0;\n";
+    }
+    site_walk(true);
   }
 
   void superleaf(const std::string &P, std::vector<int> &dig, const std::string &ind) {
@@ -710,6 +978,20 @@ class Gen {
       superleaf(P, dig, ind);
       return;
     }
+    if (once_) {
+      // a prefix level of the once-per-site form: the product, nothing else — the members' marginals are formed after the loops
+      for (int g = 0; g < 3; ++g) {
+        dig[k] = g;
+        const std::string pg = "p" + num(uid_++);
+        o_ << ind << "double " << pg << " = " << P << " * " << (const_lvl_[k] ? t_var(k, t_off(k, g, dig)) : w_name(k, g, dig)) << ";\n"
+           << pin("\"+v\"(" + pg + ")", ind);
+        const auto it = consumer_.find(node_key(k, dig));
+        if (it != consumer_.end()) fetch_group((it->second + 1) % (int)groups_.size(), ind);
+        level(k + 1, pg, dig, ind);
+        o_ << pin("\"+v\"(" + P + ")", ind);
+      }
+      return;
+    }
     if (k == nu_ - 1) {
       for (int g = 0; g < 3; ++g)
         o_ << ind << "b" << p << "_" << g << " = __builtin_fma(" << P << ", " << w_name(k, g, dig) << ", b" << p << "_" << g
@@ -750,6 +1032,25 @@ class Gen {
     o_ << ind << "{\n";
     const std::string in2 = ind + "  ";
     std::vector<int> dig(nu_, 0);
+    if (once_) {
+      // The block's total and the prefix members' marginals, once per step: every weight of the step is
+      // (P Q) x (product of the prefix tables), Q the sum of the super-leaf table.  The tables built per step
+      // enter through v_c (one value per combination c of the digits they mention); the others are the same in
+      // every step of the site, so the sums of P Q v_c over the steps (U_c) are all the prefix members need.
+      o_ << in2 << "const double PQ = " << P << " * " << q_name(nu_ - sl_, dig) << ";\n";
+      std::string z;
+      for (int c = 0; c < pow3((int)D_.size()); ++c) {
+        const std::string v = step_value(c, in2);
+        o_ << in2 << "U_" << c << " = __builtin_fma(PQ, " << v << ", U_" << c << ");\n";
+        z = z.empty() ? "(" + v + " * C_" + num(c) + ")" : "__builtin_fma(" + v + ", C_" + num(c) + ", " + z + ")";
+      }
+      if (!acc_parent.empty()) o_ << in2 << acc_parent << " += PQ * " << z << ";\n";
+      o_ << in2 << "double Pb = " << P << ";\n" << pin("\"+v\"(Pb)", in2);
+      if (consumer_.count("")) fetch_group((consumer_[""] + 1) % (int)groups_.size(), in2);
+      level(0, "Pb", dig, in2);
+      o_ << ind << "}\n";
+      return;
+    }
     o_ << in2 << "double Pb = " << P << ";\n";
     if (!acc_parent.empty() && !q0_incremental_) o_ << in2 << acc_parent << " += Pb * " << q_name(0, dig) << ";\n";
     level(0, "Pb", dig, in2);
@@ -760,17 +1061,137 @@ class Gen {
 
 }  // namespace
 
+namespace {
+
+// fp64 statements of a generated body per site, each weighted by 3^(digit loops around it): what the kernel's time follows
+// (DESIGN.md 2.1).  Counted from the text: index expressions (in brackets) and integer statements are left out.
+double fp64_statements(const std::string &body) {
+  double total = 0, weight = 1;
+  int depth = 0;
+  std::vector<int> loop_depth;
+  std::istringstream in(body);
+  for (std::string line; std::getline(in, line);) {
+    const bool loop = line.find("for (int g") != std::string::npos;
+    if (!loop && line.find("int ") == std::string::npos && line.find("asm") == std::string::npos && line.find("//") == std::string::npos) {
+      int in_index = 0, ops = 0;
+      for (size_t i = 0; i < line.size(); ++i) {
+        const char ch = line[i];
+        if (ch == '[') ++in_index;
+        else if (ch == ']') --in_index;
+        else if (in_index == 0 && (ch == '*' || ch == '/' || (ch == '+' && line[i + 1 < line.size() ? i + 1 : i] != '+' && (i == 0 || line[i - 1] != '+')))) ++ops;
+        else if (in_index == 0 && line.compare(i, 14, "__builtin_fma(") == 0) ++ops;
+      }
+      total += ops * weight;
+    }
+    for (char ch : line) {
+      if (ch == '{') {
+        ++depth;
+      } else if (ch == '}') {
+        if (!loop_depth.empty() && loop_depth.back() == depth) {
+          loop_depth.pop_back();
+          weight /= 3;
+        }
+        --depth;
+      }
+    }
+    if (loop && line.find('{') != std::string::npos) {  // the loop's own brace was counted just above
+      loop_depth.push_back(depth);
+      weight *= 3;
+    }
+  }
+  return total;
+}
+
+// LDS row of the once-per-site form (Gen::plan_once): what it would like, cut to what four one-wave workgroups per CU leave
+// (each also holds the 432-double transmission table); 0: not even the output row fits.
+int once_row_len(const Model &m, const Shape &s, int bt) {
+  int want = 6 * (int)s.outer.size();
+  for (int p : s.unrolled) {
+    const bool has = m.mother[p] >= 0;
+    const bool looped = has && (s.upos[m.mother[p]] < 0 || s.upos[m.father[p]] < 0);
+    want += looped ? 3 : 3 * (has ? (s.upos[m.mother[p]] >= 0 ? 3 : 1) * (s.upos[m.father[p]] >= 0 ? 3 : 1) : 1);
+  }
+  want = std::max(want, 3 * m.n_members) | 1;
+  int fit = (160 * 1024 / 4 - 432 * 8) / (bt * 8);
+  if (fit % 2 == 0) --fit;
+  return fit < ((3 * m.n_members) | 1) ? 0 : std::min(want, fit);
+}
+
+struct LaneForm {
+  bool once = false;
+  Shape shape;       // of the form taken
+  int row_len = 0;
+  std::string body;
+  double fp64_parent = 0, fp64_once = 0;  // the cost model's counts (once: 0 where the form does not apply)
+};
+
+// The body of the one-lane-per-site kernel (group_digits = 0, not the call path: that form keeps the per-prefix text, and its
+// posteriors differ from the once-per-site form's in their last bits), in the form the cost model takes:
+// the once-per-site form (Gen, "The once-per-site form") where it applies, fits four workgroups per CU and executes
+// fewer fp64 statements per site than the per-prefix form (may_once: variants 4-7 ask for it); FAMSEQ_LANE_HOIST=0 (tuning aid)
+// keeps the latter.
+LaneForm lane_form(const Model &m, const Shape &s, int row_len, int bt, bool scalar_t, int prefetch, bool may_once) {
+  LaneForm f;
+  f.shape = s, f.row_len = row_len;
+  {
+    Gen gen(m, s, row_len, 0, false, scalar_t, prefetch);
+    f.body = gen.body();
+  }
+  if (!may_once || !scalar_t || env_int("FAMSEQ_LANE_HOIST", 1) == 0) return f;
+  f.fp64_parent = fp64_statements(f.body);
+  Shape h = s;
+  {
+    std::vector<int> ordered;
+    Gen probe(m, s, row_len, 0, false, scalar_t, prefetch);
+    const int join = probe.joinable_member(&ordered);
+    if (join >= 0) {  // part 1: the innermost looped member becomes the block's outermost prefix level
+      h.outer.clear();
+      for (int p : ordered)
+        if (p != join) h.outer.push_back(p);
+      h.unrolled.insert(h.unrolled.begin(), join);
+      for (size_t k = 0; k < h.unrolled.size(); ++k) h.upos[h.unrolled[k]] = (int)k;
+    }
+  }
+  const int hrow = once_row_len(m, h, bt);
+  if (hrow == 0) return f;
+  Gen gen(m, h, hrow, 0, false, scalar_t, 0, /*once=*/true);
+  if (!gen.once_feasible()) return f;
+  std::string body = gen.body();
+  f.fp64_once = fp64_statements(body);
+  if (f.fp64_once >= f.fp64_parent) return f;
+  f.once = true, f.shape = h, f.row_len = hrow, f.body = std::move(body);
+  return f;
+}
+
+int lane_row_len(const Model &m, const Shape &s, int bt, bool call_mode);
+
+}  // namespace
+
 std::string enumgen_describe(const Model &m, int variant) {
+  const bool want_once = variant >= 4;  // kEnumVariants: 4-7 are 0-3 in the once-per-site form
+  if (variant >= 4) variant -= 4;
   int cap = (variant >= 0 && variant < 2) ? 7 : 6;  // kEnumVariants; unknown yet (-1): the 6-member form
   cap = env_int("FAMSEQ_LANE_CAP", cap);
-  const Shape s = choose_shape(m, cap);
+  Shape s = choose_shape(m, cap);
+  std::string form;
+  if (want_once && !s.unrolled.empty() && !s.outer.empty() && env_int("FAMSEQ_LANE_LATE", 0) == 0 && env_int("FAMSEQ_LANE_ST", 1) != 0) {
+    const int bt = enumgen_block_threads(m, 0);
+    const LaneForm f = lane_form(m, s, lane_row_len(m, s, bt, false), bt, true, env_int("FAMSEQ_LANE_PRE", 2), true);
+    if (f.once) {
+      s = f.shape;
+      char buf[160];
+      std::snprintf(buf, sizeof buf, ", prefix tables and marginals once per site (%.0f fp64 statements per site against %.0f)", f.fp64_once,
+                    f.fp64_parent);
+      form = buf;
+    }
+  }
   std::string d = "looped members [";
   for (size_t k = 0; k < s.outer.size(); ++k) d += (k ? " " : "") + num(s.outer[k]);
   d += "], unrolled block [";
   for (size_t k = 0; k < s.unrolled.size(); ++k) d += (k ? " " : "") + num(s.unrolled[k]);
   int n = 1;
   for (size_t k = 0; k < s.unrolled.size(); ++k) n *= 3;
-  return d + "] = " + num(n) + " configurations per step";
+  return d + "] = " + num(n) + " configurations per step" + form;
 }
 
 // One lane per site: workgroups of ONE wave, and no register cap (`__launch_bounds__(64, 1)`).  A wave that
@@ -803,6 +1224,22 @@ int enumgen_sites_per_chunk(const Model &m, int group_digits) {
 }
 
 namespace {
+
+// The lane's LDS row: 3N doubles padded to an odd count, plus — while two workgroups per CU still
+// fit in the 160 KB — room for the likelihoods of unrolled members whose tables are rebuilt inside
+// the loops (otherwise re-read from global memory there: L2 misses that show up as HBM traffic).
+int lane_row_len(const Model &m, const Shape &s, int bt, bool call_mode) {
+  int row_len = (3 * m.n_members) | 1;
+  int looped_tables = 0;  // unrolled members with a looped parent
+  for (int p : s.unrolled)
+    if (m.mother[p] >= 0 && (s.upos[m.mother[p]] < 0 || s.upos[m.father[p]] < 0)) ++looped_tables;
+  const int used = 6 * (int)s.outer.size() <= row_len ? 6 * (int)s.outer.size() : 3 * (int)s.outer.size();
+  const int want = (used + 3 * looped_tables) | 1;
+  // odd, two workgroups per CU (the call-path form also keeps a byte per member and lane, and two small tables)
+  const int fit = ((160 * 1024 / 2 - 432 * 8 - (call_mode ? bt * m.n_members + 256 + 2064 : 0)) / (bt * 8) - 1) | 1;
+  if (want > row_len) row_len = std::min(want, std::max(row_len, fit));
+  return row_len;
+}
 
 // Shell of the lanes-per-site mode (small batches): G = 3^d consecutive lanes share a site, each
 // walks the digits (fx0, fx1, ...) of the d outermost looped members given by its position in the
@@ -877,7 +1314,17 @@ std::string grouped_shell(const Model &m, const std::string &comment, const std:
 
 }  // namespace
 
-std::string enumgen_source(const Model &m, int variant, int group_digits, bool call_mode, bool call_ct_out) {
+bool enumgen_has_once_form(const Model &m) {
+  for (int v : {0, 2})
+    if (enumgen_source(m, v) != enumgen_source(m, v + 4)) return true;
+  return false;
+}
+
+std::string enumgen_source(const Model &m, int variant_asked, int group_digits, bool call_mode, bool call_ct_out) {
+  // variants 4-7: variants 0-3 with the block's prefix levels in the once-per-site form, where the cost model takes it (lane_form);
+  // where it does not — and in the lanes-per-site forms — they are the text of 0-3
+  const bool want_once = variant_asked >= 4 && group_digits == 0;
+  const int variant = variant_asked & 3;
   int cap = (group_digits == 0 && variant < 2) ? 7 : 6;  // see kEnumVariants
   cap = env_int("FAMSEQ_LANE_CAP", cap);  // tuning aid
   const Shape s = choose_shape(m, cap);
@@ -885,20 +1332,7 @@ std::string enumgen_source(const Model &m, int variant, int group_digits, bool c
   if (group_digits < 0 || group_digits > std::min<int>(kEnumMaxGroupDigits, (int)s.outer.size()))
     throw std::runtime_error("enumeration codegen: more group digits than looped members");
   const int bt = enumgen_block_threads(m, group_digits);
-  // The lane's LDS row: 3N doubles padded to an odd count, plus — while two workgroups per CU still
-  // fit in the 160 KB — room for the likelihoods of unrolled members whose tables are rebuilt inside
-  // the loops (otherwise re-read from global memory there: L2 misses that show up as HBM traffic).
-  int row_len = (3 * m.n_members) | 1;
-  {
-    int looped_tables = 0;  // unrolled members with a looped parent
-    for (int p : s.unrolled)
-      if (m.mother[p] >= 0 && (s.upos[m.mother[p]] < 0 || s.upos[m.father[p]] < 0)) ++looped_tables;
-    const int used = 6 * (int)s.outer.size() <= row_len ? 6 * (int)s.outer.size() : 3 * (int)s.outer.size();
-    const int want = (used + 3 * looped_tables) | 1;
-    // odd, two workgroups per CU (the call-path form also keeps a byte per member and lane, and two small tables)
-    const int fit = ((160 * 1024 / 2 - 432 * 8 - (call_mode ? bt * m.n_members + 256 + 2064 : 0)) / (bt * 8) - 1) | 1;
-    if (want > row_len) row_len = std::min(want, std::max(row_len, fit));
-  }
+  int row_len = lane_row_len(m, s, bt, call_mode);
   // An experiment that is OFF (FAMSEQ_LANE_LATE=1 turns it on): the sum-product kernel's order of phases for
   // the enumeration too — the whole computation first (marginals to registers), the next chunk requested,
   // then the two outputs — instead of single posterior / store / enumeration / store: one barrier fewer and
@@ -941,19 +1375,32 @@ std::string enumgen_source(const Model &m, int variant, int group_digits, bool c
   // per configuration in that loop and 1.33 overall the kernel runs at the issue rate a single wave sustains.
   const bool scalar_t = env_int("FAMSEQ_LANE_ST", 1) != 0 && group_digits == 0 && !late && !s.outer.empty();  // (the variable: a tuning aid)
   const int prefetch = env_int("FAMSEQ_LANE_PRE", 2);  // tuning aid: 0 none, 1 table entries, 2 and LDS reads
-  Gen gen(m, s, late ? std::max(scratch_len, 1) : row_len, group_digits, late, scalar_t, prefetch);
   if (call_mode) what += ", call path";
   // variant 0: the members of the single posterior overlap, 1: fenced one from the other (fewer registers)
   const bool fence_single = variant & 1;
   if (group > 1) {
     if (call_mode) throw std::runtime_error("enumeration codegen: the lanes-per-site form has no call path");
+    Gen gen(m, s, row_len, group_digits, late, scalar_t, prefetch);
     const std::string body = gen.body();
     return grouped_shell(m, what, body, gen.reduce_body(), bt, min_waves, fence_single, row_len, group);
   }
   ShellOptions o;
   o.entry = "famseq_enum_lane";
   o.comment = late ? what + ", compute-first shell" : what;
-  o.body = gen.body();
+  if (late) {
+    Gen gen(m, s, std::max(scratch_len, 1), group_digits, late, scalar_t, prefetch);
+    o.body = gen.body();
+  } else {
+    LaneForm f = lane_form(m, s, row_len, bt, scalar_t, prefetch, want_once && !call_mode);
+    if (f.once) {
+      o.comment = "3^N enumeration, lane per site, " + std::to_string(f.shape.outer.size()) + " looped + " +
+                  std::to_string(f.shape.unrolled.size()) + " unrolled members, variant " + std::to_string(variant_asked) +
+                  ", prefix tables and marginals once per site";
+      if (f.shape.unrolled.size() > s.unrolled.size())
+        o.comment += " (looped member " + std::to_string(f.shape.unrolled[0]) + " unrolled ahead of the block)";
+    }
+    o.body = std::move(f.body), row_len = f.row_len;
+  }
   o.bt = bt, o.min_waves = min_waves, o.row_doubles = row_len;
   // registers-first (LDS-resident likelihoods measured 17 % slower) unless the late experiment asks for the shell's compute-first flow
   o.regs_l = !late, o.lane_body = late;

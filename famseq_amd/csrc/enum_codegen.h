@@ -15,12 +15,17 @@ namespace famseq {
 // step: fewer table rebuilds; measured +1.9 % at 15 members, where it does not spill; at 10 members it spills
 // more than the 6-member block and loses the pick), 2, 3 = a 6-member block; odd = the members of the single
 // posterior fenced one from the other (fewer registers).  The lanes-per-site forms always use the 6-member block.
-constexpr int kEnumVariants = 4;
+// 4-7 = 0-3 with the block's prefix tables and marginals formed once per site (enum_codegen.cpp, "The once-per-site form"),
+// for the pedigrees on which the generator's cost model takes that form; for every other pedigree they are the text of 0-3.
+// Where the form exists the contest starts at 4 (enumgen_first_variant).
+constexpr int kEnumVariants = 8;
 // group_digits = d > 0: lanes-per-site mode for small batches — 3^d consecutive lanes share a site, each
 // taking one combination of the d outermost looped members' digits (d <= enumgen_max_group_digits)
 constexpr int kEnumMaxGroupDigits = 4;
 // call_ct_out (call path only): the stage-out walk with the row width as a constant (see kElimCallVariants)
 std::string enumgen_source(const Model &m, int variant, int group_digits = 0, bool call_mode = false, bool call_ct_out = true);
+bool enumgen_has_once_form(const Model &m);  // does any of variants 4-7 differ from 0-3 for this pedigree?
+inline int enumgen_first_variant(const Model &m) { return enumgen_has_once_form(m) ? 4 : 0; }
 int enumgen_max_group_digits(const Model &m);
 // true when the call-path form of the one-lane-per-site kernel re-reads some members' likelihoods from the
 // fp64 rows in global memory inside its loops (wide pedigrees whose LDS row cannot hold them): such a kernel

@@ -46,6 +46,24 @@ struct KernelSpec {
   std::function<std::string(int)> variant_of = nullptr;
 };
 
+}  // namespace
+
+// 4 where the pedigree's lane kernel has the once-per-site form (variants 4-7 differ from 0-3), else 0.  Generating the
+// candidates to find out costs milliseconds, so it is done once per context; a generator that throws means "no such form".
+int lane_first_variant(const famseq_ctx *c) {
+  famseq_ctx *w = const_cast<famseq_ctx *>(c);
+  if (w->lane_first < 0) {
+    try {
+      w->lane_first = enumgen_first_variant(c->model);
+    } catch (const std::exception &) {
+      w->lane_first = 0;
+    }
+  }
+  return w->lane_first;
+}
+
+namespace {
+
 bool is_lane(int kind) { return kind >= K_LANE && kind <= K_LANE + kEnumMaxGroupDigits; }
 
 // Which side product a kind belongs to (p == nullptr: none), in which form.
@@ -65,7 +83,11 @@ KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
   const Model &m = c->model;
   if (is_lane(kind)) {
     const int d = kind - K_LANE;  // (the lanes-per-site forms always use the 6-member block: no measured pick to honour)
-    return {[&m, d](int v) { return enumgen_source(m, v, d); }, kEnumVariants, 0, d == 0, "famseq_enum_lane", enumgen_block_threads(m, d)};
+    // (one lane per site: the contest starts at the once-per-site variants where the pedigree has that form; elsewhere 4-7 are
+    // the texts of 0-3 again, reached only when all of those spill, and then cache hits)
+    const bool once = d == 0 && lane_first_variant(c) == 4;
+    return {[&m, d](int v) { return enumgen_source(m, v, d); }, kEnumVariants, once ? 4 : 0, d == 0, "famseq_enum_lane",
+            enumgen_block_threads(m, d)};
   }
   if (const SideKind k = side_of(kind); k.p) {
     const auto source = [&m, k](bool site_prior) { return [&m, k, site_prior](int v) { return k.p->source(m, v, k.form, site_prior); }; };
@@ -79,7 +101,8 @@ KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
     case K_LANE_CALL: {
       // the same block size as the plain lane kernel runs with (variants 0-1 / 2-3: kEnumVariants), so that a batch
       // gives the same bits whether it goes through the fused kernel or through the separate stages
-      const int base = std::max(c->kern[K_LANE].variant, 0) & ~1;
+      // (variants 4-7 are 0-3 in the once-per-site form: the call path keeps the per-prefix text of the same block shape)
+      const int base = std::max(c->kern[K_LANE].variant, 0) & 2;
       // v & 1: the single posterior fenced member by member; v & 2: the leaner stage-out (see kElimCallVariants)
       return {[&m, base](int v) { return enumgen_source(m, base + (v & 1), 0, true, !(v & 2)); }, 4, 0, false, "famseq_enum_lane",
               enumgen_block_threads(m)};
@@ -234,7 +257,7 @@ bool generated_ready(famseq_ctx *c, int d) {
       const int pick = d == 0 ? jit_read_pick(enumgen_source(c->model, 0, 0)) : -1;
       // (the variant the loader would take first; a spilling first variant sends it on to others, which may need the compiler:
       // then this says "not ready" and the tiny batch stays on the compiled-in kernel, which is always right)
-      c->grp_ready[d] = jit_cached(enumgen_source(c->model, pick >= 0 && pick < kEnumVariants ? pick : 0, d)) ? 1 : 0;
+      c->grp_ready[d] = jit_cached(enumgen_source(c->model, pick >= 0 && pick < kEnumVariants ? pick : (d == 0 ? lane_first_variant(c) : 0), d)) ? 1 : 0;
     } catch (const std::exception &) {
       c->grp_ready[d] = 0;
     }
@@ -405,9 +428,11 @@ int tune(famseq_ctx *c) {
   };
   std::string failed;
   try {
-    if (enumgen_describe(mdl, 0) != enumgen_describe(mdl, 2))
-      (void)race("enumeration (7- / 6-member block)", {0, 2}, [&mdl](int v) { return enumgen_source(mdl, v, 0); }, "famseq_enum_lane",
-                 enumgen_block_threads(mdl, 0));
+    // (the two block shapes, in the form the pedigree's contest starts from: variants 0 / 2, or 4 / 6 where the once-per-site form exists)
+    const int f0 = lane_first_variant(c);
+    if (enumgen_describe(mdl, f0) != enumgen_describe(mdl, f0 + 2))
+      (void)race(f0 ? "enumeration (7- / 6-member block, once-per-site form)" : "enumeration (7- / 6-member block)", {f0, f0 + 2},
+                 [&mdl](int v) { return enumgen_source(mdl, v, 0); }, "famseq_enum_lane", enumgen_block_threads(mdl, 0));
     else
       report += "enumeration: one block shape, nothing to choose";
     n = n_elim;

@@ -24,7 +24,9 @@ for k, ped in enumerate(peds):
     ctx = fs.Context(fs.make_model(ped), enum_impl=1)
     ctx.set_option("tune", 1)
     plan = ctx.plan()
-    entry = {"lane": plan["enum_lane_variant"], "elim": -1, "report": plan["tune"]}
+    # (the table holds the block shape, 0 or 2: build() ships it in the form the pedigree's contest starts from — variants 4-7
+    # are 0-3 in the once-per-site form — so a tuner that raced 4 against 6 is recorded as 0 or 2)
+    entry = {"lane": plan["enum_lane_variant"] & 3, "elim": -1, "report": plan["tune"]}
     if plan["elim_supported"]:
         ctx.set_option("engine", fs.ENGINE_ELIM)
         entry["elim"] = ctx.plan()["elim_variant"]
