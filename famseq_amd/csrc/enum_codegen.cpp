@@ -128,12 +128,15 @@ class Gen {
   // instruction, no VGPR) and the founders' priors are folded into their likelihood slots once per site;
   // prefetch 1: the entries the innermost loop's tables need are loaded one step ahead (loop-carried SGPRs), 2: so are
   // that loop's LDS reads — everything the next step's table statements wait for is in flight during this step's block
-  // once: the form whose prefix tables are built once per site (see plan_once())
+  // once: the form whose prefix tables are built once per site (see plan_once()); it honours prefetch too: 1 the same carried
+  // entries, 2 the likelihoods those entries multiply are read ahead of the innermost loop and every loop level reads its
+  // marginal slot where its step begins (one wave per SIMD: a wait right behind its load is time nobody else fills); 0 is
+  // the text without any of it
   Gen(const Model &m, const Shape &s, int row_len, int fixed = 0, bool late = false, bool scalar_t = false, int prefetch = 0,
       bool once = false)
       : m_(m), s_(s), nu_((int)s.unrolled.size()), row_len_(row_len), fixed_(fixed), S_(late ? "srow" : "row"),
         O_(late ? "q" : "row"), outer_(s.outer), st_(scalar_t && !s.outer.empty()),
-        pre_(scalar_t && fixed < (int)s.outer.size() && !once ? prefetch : 0), once_(once) {}
+        pre_(scalar_t && fixed < (int)s.outer.size() ? prefetch : 0), once_(once) {}
 
   // The innermost looped member, if it may join the unrolled block as its outermost prefix level: its digit feeds
   // only factor tables of prefix levels (none of the super-leaf's), another loop remains outside it, and the block
@@ -401,18 +404,19 @@ class Gen {
       return;
     }
     const int p = outer_[k];
-    const int no = (int)outer_.size();
     const std::string g = "g" + num(p), ind(6 + 2 * k, ' ');
     const std::string lk_g = l_in_lds_ ? S_ + "[" + num(lik_base_ + 3 * (int)k) + " + " + g + "]"
                                        : "(" + g + " == 0 ? " + l_name(p, 0) + " : (" + g + " == 1 ? " + l_name(p, 1) + " : " + l_name(p, 2) + "))";
     const bool inner = pre_ > 0 && (int)k == inner_pos();
     const bool carried_l = inner && pre_ >= 2 && l_in_lds_;
+    // the once-per-site form reads a level's marginal slot where the step begins: the sum at its end waits for nothing
+    const bool early_acc = once_ && pre_ >= 2 && !carried_l;
     std::string f_expr = carried_l ? "lq_" : lk_g;
     if (!folded(p))
       f_expr = (inner && m_.mother[p] >= 0 ? carried_entry("tcx", t_index(p, "@", -1, -1, p, "@")) : t_tab(p) + "[" + t_index(p, g, -1, -1) + "]") + " * " + f_expr;
     if (inner) o_ << prologue_;
     if (carried_l)  // this loop's own LDS reads, one step ahead: the member's likelihood, its marginal slot
-      o_ << ind << "double lq_ = " << S_ << "[" << 3 * no + 3 * (int)k << "], aq_ = " << S_ << "[" << 3 * (int)k << "];\n";
+      o_ << ind << "double lq_ = " << S_ << "[" << lik_base_ + 3 * (int)k << "], aq_ = " << S_ << "[" << 3 * (int)k << "];\n";
     if ((int)k < fixed_)
       o_ << ind << "{ const int " << g << " = fx" << k << ";  // one digit per lane of the group\n";
     else
@@ -424,13 +428,29 @@ class Gen {
        << bucket_[k + 1];
     if (inner) {
       o_ << ind << "  const int " << g << "n = " << g << " < 2 ? " << g << " + 1 : 2;\n" << prefetch_;
-      if (carried_l) o_ << ind << "  const double lq_n = " << S_ << "[" << 3 * no + 3 * (int)k << " + " << g << "n];\n";
-      o_ << ind << "  __builtin_amdgcn_sched_barrier(0);\n";
+      if (carried_l) o_ << ind << "  const double lq_n = " << S_ << "[" << lik_base_ + 3 * (int)k << " + " << g << "n];\n";
     }
+    if (early_acc) o_ << ind << "  const double aq" << p << " = " << S_ << "[" << 3 * (int)k << " + " << g << "];\n";
+    // (once-per-site form: the entries loaded above are claimed here, a table's worth of statements after their issue, by an
+    // empty statement that names them — scalar loads return out of order, so while one is in flight every wait inside the block,
+    // the counted ones of its read groups too, is for all that is outstanding, the group just requested included)
+    if (inner && once_ && !tq_.empty()) {
+      std::vector<std::string> v;
+      for (const auto &kv : tq_) v.push_back(kv.second);
+      std::sort(v.begin(), v.end(), [](const std::string &a, const std::string &b) { return a.size() != b.size() ? a.size() < b.size() : a < b; });
+      for (size_t i = 0; i < v.size(); i += 24) {  // (an asm statement takes thirty operands)
+        o_ << ind << "  asm volatile(\"\" ::";
+        for (size_t j = i; j < std::min(v.size(), i + 24); ++j) o_ << (j > i ? ", " : " ") << "\"s\"(" << v[j] << ")";
+        o_ << ");\n";
+      }
+    }
+    if (inner) o_ << ind << "  __builtin_amdgcn_sched_barrier(0);\n";
     outer_level(k + 1, "P" + num(p), "acc" + num(p));
     if (carried_l)
       o_ << ind << "  " << S_ << "[" << 3 * (int)k << " + " << g << "] = aq_ + acc" << p << ";\n"
          << ind << "  lq_ = lq_n; aq_ = " << S_ << "[" << 3 * (int)k << " + " << g << "n];\n";
+    else if (early_acc)
+      o_ << ind << "  " << S_ << "[" << 3 * (int)k << " + " << g << "] = aq" << p << " + acc" << p << ";\n";
     else
       o_ << ind << "  " << S_ << "[" << 3 * (int)k << " + " << g << "] += acc" << p << ";\n";
     if (!acc_parent.empty()) o_ << ind << "  " << acc_parent << " += acc" << p << ";\n";
@@ -1154,7 +1174,7 @@ LaneForm lane_form(const Model &m, const Shape &s, int row_len, int bt, bool sca
   }
   const int hrow = once_row_len(m, h, bt);
   if (hrow == 0) return f;
-  Gen gen(m, h, hrow, 0, false, scalar_t, 0, /*once=*/true);
+  Gen gen(m, h, hrow, 0, false, scalar_t, prefetch, /*once=*/true);
   if (!gen.once_feasible()) return f;
   std::string body = gen.body();
   f.fp64_once = fp64_statements(body);
@@ -1374,7 +1394,7 @@ std::string enumgen_source(const Model &m, int variant_asked, int group_digits, 
   // instructions per 729 configurations) — the waits were a small part of what one wave per SIMD loses: at 1.21 instructions
   // per configuration in that loop and 1.33 overall the kernel runs at the issue rate a single wave sustains.
   const bool scalar_t = env_int("FAMSEQ_LANE_ST", 1) != 0 && group_digits == 0 && !late && !s.outer.empty();  // (the variable: a tuning aid)
-  const int prefetch = env_int("FAMSEQ_LANE_PRE", 2);  // tuning aid: 0 none, 1 table entries, 2 and LDS reads
+  const int prefetch = env_int("FAMSEQ_LANE_PRE", 2);  // tuning aid: 0 none, 1 table entries, 2 and LDS reads (both forms: see Gen)
   if (call_mode) what += ", call path";
   // variant 0: the members of the single posterior overlap, 1: fenced one from the other (fewer registers)
   const bool fence_single = variant & 1;
