@@ -18,14 +18,15 @@
 //     looped ones block totals kept in the lane's LDS row.
 //   * where the super-leaf table depends on no prefix digit and a cost model agrees (lane_form), the same step is taken one
 //     level further out: the innermost looped member joins the block, prefix tables that mention no loop digit are built once
-//     per site into the lane's LDS row, and the prefix members' marginals are formed after the loops (Gen, "The once-per-site
-//     form"): lane variants 4-7 (enum_codegen.h); FAMSEQ_LANE_HOIST=0 keeps the per-prefix text there too.
+//     per site into the lane's LDS row, and the prefix members' marginals are formed after the loops (OnceEmitter, "The
+//     once-per-site form"): lane variants 4-7 (enum_codegen.h); FAMSEQ_LANE_HOIST=0 keeps the per-prefix text there too.
+// BlockPlan holds what is decided about a block shape, row_layout the lane's LDS row per form, Emitter the text both forms
+// share; lane_form chooses between PrefixEmitter and OnceEmitter.
 // The generic team-per-site kernel remains the fallback (small batches, no compiler at run time).
 #include "enum_codegen.h"
 
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <functional>
 #include <map>
 #include <set>
@@ -117,113 +118,218 @@ Shape choose_shape(const Model &m, int cap) {
   return s;
 }
 
-class Gen {
+int pow3(int e) {
+  int r = 1;
+  while (e-- > 0) r *= 3;
+  return r;
+}
+
+// What a generator of the block has to know about (Model, Shape, fixed), computed once and never changed: the digits the
+// block sums depend on, the super-leaf depth, the looped members in loop order and where each level's statements go.
+// fixed: the `fixed` outermost looped members do not loop — their digits come from the lane's position in its group
+// (fx0, fx1, ...: lanes-per-site mode, 3^fixed lanes share a site).
+struct BlockPlan {
+  const Model &m;
+  const Shape s;
+  const int fixed, nu;
+  std::vector<std::vector<int>> dep;  // dep[k]: unrolled levels < k whose digits the block sums of levels >= k depend on
+  // Super-leaf: the deepest sl levels are walked together.  Their factors are multiplied once per outer step into a
+  // combined table W (3^sl entries per combination of the upper digits they depend on), so each of the 3^sl
+  // configurations below a prefix costs exactly one FMA and no products are formed inside the block for these levels.
+  int sl = 1;
+  std::vector<int> outer;    // looped members, outermost first
+  std::vector<int> entries;  // doubles in level k's factor table
+  // Loop level (index into outer, -1 = before all loops) at which level k's factor table has to be rebuilt — that of its
+  // innermost looped parent — and at which its block sums have to be
+  std::vector<int> wb, qb;
+
+  BlockPlan(const Model &model, const Shape &shape, int fixed_digits = 0)
+      : m(model), s(shape), fixed(fixed_digits), nu((int)shape.unrolled.size()), outer(shape.outer) {
+    dep.assign(nu + 1, {});
+    for (int k = nu - 1; k >= 0; --k) {
+      std::vector<char> in(nu, 0);
+      for (int j = k; j < nu; ++j) {
+        const int p = s.unrolled[j];
+        if (m.mother[p] < 0) continue;
+        for (int par : {m.mother[p], m.father[p]})
+          if (s.upos[par] >= 0 && s.upos[par] < k) in[s.upos[par]] = 1;
+      }
+      for (int l = 0; l < k; ++l)
+        if (in[l]) dep[k].push_back(l);
+    }
+    for (int t = std::min(3, nu); t >= 2 && sl == 1; --t) {
+      const int d = (int)dep[nu - t].size();
+      int doubles = pow3(t + d);
+      for (int j = 0; j + 1 < t; ++j) doubles += pow3(j + 1 + d);
+      if (doubles <= 45) sl = t;
+    }
+    for (int k = 0; k < nu; ++k) {
+      const int p = s.unrolled[k];
+      entries.push_back(m.mother[p] < 0 ? 3 : 3 * (s.upos[m.mother[p]] >= 0 ? 3 : 1) * (s.upos[m.father[p]] >= 0 ? 3 : 1));
+    }
+    order_outer_loops();
+    wb.assign(nu, -1);
+    qb.assign(nu + 1, -1);
+    for (int k = nu - 1; k >= 0; --k) {
+      const int p = s.unrolled[k];
+      if (m.mother[p] >= 0)
+        for (int par : {m.mother[p], m.father[p]})
+          if (s.upos[par] < 0) wb[k] = std::max(wb[k], outer_pos(par));
+      qb[k] = std::max(qb[k + 1], wb[k]);
+    }
+  }
+
+  int np() const { return nu - sl; }  // prefix levels: unrolled levels above the super-leaf
+  int outer_pos(int member) const {
+    for (size_t k = 0; k < outer.size(); ++k)
+      if (outer[k] == member) return (int)k;
+    return -1;
+  }
+  int looped_tables() const {  // unrolled members with a looped parent
+    return (int)std::count_if(wb.begin(), wb.end(), [](int b) { return b >= 0; });
+  }
+
+  // The innermost looped member, if it may join the unrolled block as its outermost prefix level: its digit feeds
+  // only factor tables of prefix levels (none of the super-leaf's), another loop remains outside it, and the block
+  // stays at seven members.  -1: none.
+  int joinable_member() const {
+    // (an explicit FAMSEQ_LANE_CAP bounds the block whichever way it grows)
+    if ((int)outer.size() - fixed < 2 || nu + 1 > std::min(7, env_int("FAMSEQ_LANE_CAP", 7)) || sl < 2) return -1;
+    const int c = outer.back();
+    for (int k = np(); k < nu; ++k) {
+      const int p = s.unrolled[k];
+      if (m.mother[p] >= 0 && (m.mother[p] == c || m.father[p] == c)) return -1;
+    }
+    return c;
+  }
+
+  // The once-per-site form (OnceEmitter) applies where the super-leaf table depends on no prefix digit.
+  bool once_applies() const { return fixed == 0 && sl >= 2 && np() >= 1 && dep[np()].empty(); }
+
+ private:
+  // The per-step tables are plain expressions of the loop digits, so the compiler hoists each one
+  // to the outermost loop whose digit it mentions.  Put the member whose digit feeds the most
+  // table entries outermost (among members of equal depth, parents still enclose children).
+  void order_outer_loops() {
+    const int N = s.N;
+    std::vector<int> depth(N, 0), cost(N, 0);
+    for (int pass = 0; pass < N; ++pass)
+      for (int i = 0; i < N; ++i)
+        if (m.mother[i] >= 0) depth[i] = std::max(depth[i], 1 + std::max(depth[m.mother[i]], depth[m.father[i]]));
+    for (int o : outer) {
+      bool below = false;  // does any level >= k depend on o?
+      for (int k = nu - 1; k >= 0; --k) {
+        const int p = s.unrolled[k];
+        if (m.mother[p] >= 0 && (m.mother[p] == o || m.father[p] == o)) {
+          cost[o] += entries[k];
+          below = true;
+        }
+        if (below) cost[o] += pow3((int)dep[k].size());                                       // Q<k>
+        if (below && sl >= 2 && k == nu - sl) cost[o] += pow3(sl + (int)dep[k].size()) * 3 / 2;  // W, X
+      }
+    }
+    std::stable_sort(outer.begin(), outer.end(), [&](int a, int b) {
+      if (depth[a] != depth[b]) return depth[a] < depth[b];
+      return cost[a] > cost[b];
+    });
+  }
+};
+
+// The lane's LDS row, as the body uses it between the single-posterior store and the final write-back: slots 3k.. hold looped
+// member k's marginal accumulators; then come, in the per-prefix form, the looped members' likelihoods (all or none) and the
+// likelihoods of unrolled members whose tables are rebuilt inside the loops; in the once-per-site form the constant prefix
+// tables, those unrolled members' likelihoods and the looped members' own behind them (all or none).
+struct RowLayout {
+  bool fits = true;  // (once-per-site form) false: no room, or more than two digits in the tables rebuilt per step
+  bool l_in_lds = false;
+  int lik_base = 0;                            // first slot of the looped members' likelihoods
+  std::vector<std::pair<int, int>> lik_slots;  // unrolled member, first of its 3 slots: in the order the body fills them
+  std::set<int> before_loops;                  // unrolled members whose tables are built once per site, ahead of all loops
+  std::vector<int> tslot;  // prefix level -> first slot of its table, where the table mentions no loop digit ("constant"); else -1
+  std::vector<int> D;      // prefix levels whose digits the tables rebuilt per step mention, ascending
+};
+
+RowLayout row_layout(const BlockPlan &p, int row_len, bool once) {
+  RowLayout L;
+  const int no = (int)p.outer.size();
+  L.tslot.assign(p.nu, -1);
+  int next = 3 * no;
+  if (once) {
+    std::set<int> d;
+    for (int k = 0; k < p.np(); ++k) {
+      if (p.wb[k] < 0) {
+        L.tslot[k] = next;
+        next += p.entries[k];
+        continue;
+      }
+      d.insert(k);
+      const int mem = p.s.unrolled[k];
+      for (int par : {p.m.mother[mem], p.m.father[mem]})
+        if (p.s.upos[par] >= 0) d.insert(p.s.upos[par]);
+    }
+    if (next > row_len || d.size() > 2) {  // (3^|D| values per step)
+      L.fits = false;
+      return L;
+    }
+    L.D.assign(d.begin(), d.end());
+  } else {
+    L.l_in_lds = 6 * no <= row_len;
+    L.lik_base = next;
+    next = (L.l_in_lds ? 6 : 3) * no;
+  }
+  // The unrolled members' likelihoods are needed only where their tables are rebuilt (outer loop levels).  What is left
+  // of the row holds them for the members whose tables sit in the deepest loops (read 3^depth times per site: +3 % on
+  // ped10), deepest loop first, while there is room.  Either way 6 registers per member stay free for the block.
+  std::vector<int> order;
+  for (int k = 0; k < p.nu; ++k)
+    if (p.wb[k] >= 0) order.push_back(k);
+    else L.before_loops.insert(p.s.unrolled[k]);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p.wb[a] > p.wb[b]; });
+  for (int k : order) {
+    if (next + 3 > row_len) break;
+    L.lik_slots.push_back({p.s.unrolled[k], next});
+    next += 3;
+  }
+  if (once) {
+    L.l_in_lds = next + 3 * no <= row_len;
+    L.lik_base = next;
+    std::sort(L.lik_slots.begin(), L.lik_slots.end());  // (this form fills them in member order)
+  }
+  return L;
+}
+
+// Lanes-per-site mode, last step (the group's first lane, after the column sums): normalise,
+// failure rule (family.cpp:943-954).
+std::string reduce_body() {
+  std::ostringstream o;
+  o << "#pragma unroll 1\n      for (int k = 0; k < W3; k += 3) {\n"
+    << "        const double t0 = row[k], t1 = row[k + 1], t2 = row[k + 2];\n"
+    << "        const double s = (t0 + t1) + t2; if (s <= 0) bn_fail = true;\n"
+    << "        if (s < 1e-290) { asm volatile(\"\" ::: \"memory\"); row[k] = t0 / s; row[k + 1] = t1 / s; row[k + 2] = t2 / s; }\n"
+    << "        else { const double r = 1.0 / s; row[k] = t0 * r; row[k + 1] = t1 * r; row[k + 2] = t2 * r; }\n      }\n";
+  return o.str();
+}
+
+// What both forms of the body are made of: the outer loops with their prefetch, the factor-table statements, the super-leaf
+// table and its FMAs, the marginals from the joint accumulators and the row normalisation.  A form supplies the block.
+class Emitter {
  public:
-  // fixed: the `fixed` outermost looped members do not loop — their digits come from the lane's
-  // position in its group (fx0, fx1, ...: lanes-per-site mode, 3^fixed lanes share a site)
   // late: the small-pedigree form — the lane's row keeps the input likelihoods (the shell reads them from
   // LDS and turns them into the single posterior only after this body), so the body's scratch slots live
   // behind them (srow = row + W3) and the normalised marginals go to registers q[] instead of the row
   // scalar_t: the children's transmission entries come from tcx[] (wave-uniform pointer: scalar loads, no LDS
   // instruction, no VGPR) and the founders' priors are folded into their likelihood slots once per site;
   // prefetch 1: the entries the innermost loop's tables need are loaded one step ahead (loop-carried SGPRs), 2: so are
-  // that loop's LDS reads — everything the next step's table statements wait for is in flight during this step's block
-  // once: the form whose prefix tables are built once per site (see plan_once()); it honours prefetch too: 1 the same carried
-  // entries, 2 the likelihoods those entries multiply are read ahead of the innermost loop and every loop level reads its
-  // marginal slot where its step begins (one wave per SIMD: a wait right behind its load is time nobody else fills); 0 is
-  // the text without any of it
-  Gen(const Model &m, const Shape &s, int row_len, int fixed = 0, bool late = false, bool scalar_t = false, int prefetch = 0,
-      bool once = false)
-      : m_(m), s_(s), nu_((int)s.unrolled.size()), row_len_(row_len), fixed_(fixed), S_(late ? "srow" : "row"),
-        O_(late ? "q" : "row"), outer_(s.outer), st_(scalar_t && !s.outer.empty()),
-        pre_(scalar_t && fixed < (int)s.outer.size() ? prefetch : 0), once_(once) {}
-
-  // The innermost looped member, if it may join the unrolled block as its outermost prefix level: its digit feeds
-  // only factor tables of prefix levels (none of the super-leaf's), another loop remains outside it, and the block
-  // stays at seven members.  -1: none.  `ordered` receives the looped members in loop order.
-  int joinable_member(std::vector<int> *ordered) {
-    prepare();
-    *ordered = outer_;
-    // (an explicit FAMSEQ_LANE_CAP bounds the block whichever way it grows)
-    if ((int)outer_.size() - fixed_ < 2 || nu_ + 1 > std::min(7, env_int("FAMSEQ_LANE_CAP", 7)) || sl_ < 2) return -1;
-    const int c = outer_.back();
-    for (int k = 0; k < nu_; ++k) {
-      const int p = s_.unrolled[k];
-      if (m_.mother[p] >= 0 && (m_.mother[p] == c || m_.father[p] == c) && k >= nu_ - sl_) return -1;
-    }
-    return c;
-  }
-
-  // Can this shape take the once-per-site form, with `row_len_` doubles of LDS per lane?
-  bool once_feasible() {
-    if (!once_ || !st_ || fixed_ != 0 || std::getenv("FAMSEQ_LANE_LAZY")) return false;
-    prepare();
-    if (sl_ < 2 || env_int("FAMSEQ_LANE_JOINT", 1) == 0) return false;
-    if (!dep_[nu_ - sl_].empty() || nu_ - sl_ < 1) return false;
-    return plan_once();
-  }
-
-  // Lanes-per-site mode, last step (the group's first lane, after the column sums): normalise,
-  // failure rule (family.cpp:943-954).
-  std::string reduce_body() const {
-    std::ostringstream o;
-    o << "#pragma unroll 1\n      for (int k = 0; k < W3; k += 3) {\n"
-      << "        const double t0 = row[k], t1 = row[k + 1], t2 = row[k + 2];\n"
-      << "        const double s = (t0 + t1) + t2; if (s <= 0) bn_fail = true;\n"
-      << "        if (s < 1e-290) { asm volatile(\"\" ::: \"memory\"); row[k] = t0 / s; row[k + 1] = t1 / s; row[k + 2] = t2 / s; }\n"
-      << "        else { const double r = 1.0 / s; row[k] = t0 * r; row[k + 1] = t1 * r; row[k + 2] = t2 * r; }\n      }\n";
-    return o.str();
-  }
-
-  // The per-step tables are plain expressions of the loop digits, so the compiler hoists each one
-  // to the outermost loop whose digit it mentions.  Put the member whose digit feeds the most
-  // table entries outermost (among members of equal depth, parents still enclose children).
-  void order_outer_loops() {
-    const int N = s_.N;
-    std::vector<int> depth(N, 0), cost(N, 0);
-    for (int pass = 0; pass < N; ++pass)
-      for (int i = 0; i < N; ++i)
-        if (m_.mother[i] >= 0) depth[i] = std::max(depth[i], 1 + std::max(depth[m_.mother[i]], depth[m_.father[i]]));
-    std::vector<std::vector<char>> feeds(nu_, std::vector<char>(N, 0));  // outer parents of level k
-    for (int k = 0; k < nu_; ++k) {
-      const int p = s_.unrolled[k];
-      if (m_.mother[p] < 0) continue;
-      for (int par : {m_.mother[p], m_.father[p]})
-        if (s_.upos[par] < 0) feeds[k][par] = 1;
-    }
-    for (int o : outer_) {
-      bool below = false;  // does any level >= k depend on o?
-      for (int k = nu_ - 1; k >= 0; --k) {
-        const int p = s_.unrolled[k];
-        if (feeds[k][o]) {
-          int e = 3;
-          if (m_.mother[p] >= 0) e *= (s_.upos[m_.mother[p]] >= 0 ? 3 : 1) * (s_.upos[m_.father[p]] >= 0 ? 3 : 1);
-          cost[o] += e;
-          below = true;
-        }
-        if (below) cost[o] += pow3((int)dep_[k].size());                                   // Q<k>
-        if (below && sl_ >= 2 && k == nu_ - sl_) cost[o] += pow3(sl_ + (int)dep_[k].size()) * 3 / 2;  // W, WQ, X
-      }
-    }
-    std::stable_sort(outer_.begin(), outer_.end(), [&](int a, int b) {
-      if (depth[a] != depth[b]) return depth[a] < depth[b];
-      return cost[a] > cost[b];
-    });
-  }
-
-  void prepare() {
-    compute_deps();
-    choose_superleaf();
-    order_outer_loops();
-  }
+  // that loop's LDS reads — everything the next step's table statements wait for is in flight during this step's block;
+  // 0 is the text without any of it
+  Emitter(const BlockPlan &plan, const RowLayout &layout, bool late, bool scalar_t, int prefetch)
+      : p_(plan), L_(layout), m_(plan.m), s_(plan.s), nu_(plan.nu), sl_(plan.sl), joint_(plan.sl >= 2), fixed_(plan.fixed),
+        S_(late ? "srow" : "row"), O_(late ? "q" : "row"), outer_(plan.outer), st_(scalar_t && !plan.outer.empty()),
+        pre_(scalar_t && plan.fixed < (int)plan.outer.size() ? prefetch : 0) {}
+  virtual ~Emitter() = default;
 
   std::string body() {
-    pin_style_ = env_int("FAMSEQ_LANE_PIN", pin_style_);  // tuning aid
-    prepare();
-    const int no = (int)outer_.size(), row_len = row_len_;
-    l_in_lds_ = 6 * no <= row_len;
-    lik_base_ = 3 * no;
-    if (once_ && !plan_once()) throw std::logic_error("enumeration codegen: the once-per-site form does not fit this shape");
+    const int no = (int)outer_.size();
     o_ << "      // outer (looped) members:";
     for (int p : outer_) o_ << " " << p;
     o_ << " | unrolled block:";
@@ -232,7 +338,7 @@ class Gen {
     // The lane's LDS row is idle between the single-posterior store and the final write-back:
     // the looped members' marginal accumulators (touched once per iteration of their own loop)
     // and, when they fit, their likelihoods live there instead of in registers, which keeps the
-    // unrolled block free of scratch traffic.
+    // unrolled block free of scratch traffic (RowLayout).
     for (int k = 0; k < no; ++k)
       if (folded(outer_[k]))  // the founder's prior goes into its likelihood once per site (the product the loop would form each time)
         for (int g = 0; g < 3; ++g)
@@ -240,59 +346,29 @@ class Gen {
     for (int k = 0; k < no; ++k)
       for (int g = 0; g < 3; ++g) {
         o_ << "      " << S_ << "[" << 3 * k + g << "] = 0;\n";
-        if (l_in_lds_) o_ << "      " << S_ << "[" << lik_base_ + 3 * k + g << "] = " << l_name(outer_[k], g) << ";\n";
+        if (L_.l_in_lds) o_ << "      " << S_ << "[" << L_.lik_base + 3 * k + g << "] = " << l_name(outer_[k], g) << ";\n";
       }
-    // The unrolled members' likelihoods are needed only where their tables are rebuilt (outer loop
-    // levels).  What is left of the LDS row holds them for the members whose tables sit in the
-    // deepest loops (read 3^depth times per site: +3 % on ped10); the others are re-read from the
-    // site's own row in global memory there (L2 hits).  Either way 6 registers per member stay free
-    // for the block.
-    if (once_) {
-      for (const auto &kv : lds_slot_)
-        for (int g = 0; g < 3; ++g) o_ << "      " << S_ << "[" << kv.second + g << "] = l" << kv.first << "_" << g << ";\n";
-    } else {
-      const std::vector<int> wb = table_buckets();
-      std::vector<int> order;
-      for (int k = 0; k < nu_; ++k)
-        if (wb[k] >= 0) order.push_back(k);
-        else before_loops_.insert(s_.unrolled[k]);
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return wb[a] > wb[b]; });
-      int next = (l_in_lds_ ? 6 : 3) * no;
-      for (int k : order) {
-        if (next + 3 > row_len) break;
-        lds_slot_[s_.unrolled[k]] = next;
-        for (int g = 0; g < 3; ++g) o_ << "      " << S_ << "[" << next + g << "] = l" << s_.unrolled[k] << "_" << g << ";\n";
-        next += 3;
-      }
-    }
-    for (int k = 0; k < fixed_; ++k) {  // this lane's digits of the members that do not loop
-      int div = 1;
-      for (int j = 0; j < k; ++j) div *= 3;
-      o_ << "      const int fx" << k << " = (sub / " << div << ") % 3;\n";
-    }
-    joint_ = sl_ >= 2;
-    joint_ = joint_ && env_int("FAMSEQ_LANE_JOINT", 1) != 0;  // tuning aid
-    for (int k = 0; k < nu_; ++k) {
-      if (joint_ && k >= nu_ - sl_) continue;
-      if (once_ && k < np_) continue;  // formed after the loops (site_walk)
+    for (const auto &ms : L_.lik_slots)
+      for (int g = 0; g < 3; ++g) o_ << "      " << S_ << "[" << ms.second + g << "] = l" << ms.first << "_" << g << ";\n";
+    for (int k = 0; k < fixed_; ++k)  // this lane's digits of the members that do not loop
+      o_ << "      const int fx" << k << " = (sub / " << pow3(k) << ") % 3;\n";
+    for (int k = site_levels_; k < (joint_ ? nu_ - sl_ : nu_); ++k) {
       const int p = s_.unrolled[k];
       o_ << "      double b" << p << "_0 = 0, b" << p << "_1 = 0, b" << p << "_2 = 0;\n";
     }
-    if (joint_) {
-      std::vector<int> dig(nu_, 0);
+    std::vector<int> dig(nu_, 0);
+    if (joint_)
       for (int c = 0; c < pow3(sl_); ++c) o_ << "      double " << s_name(c, dig) << " = 0;\n";
-    }
     o_ << "      const double P_root = 10000000.0;\n";  // family.cpp:911
     tables();
     o_ << bucket_[0];
-    if (once_) once_before_loops();
+    before_loops();
     outer_level(0, "P_root", "");
-    if (once_) once_after_loops();
+    after_loops();
     for (int k = 0; k < no; ++k)
       o_ << "      const double b" << outer_[k] << "_0 = " << S_ << "[" << 3 * k << "], b" << outer_[k] << "_1 = " << S_ << "[" << 3 * k + 1
          << "], b" << outer_[k] << "_2 = " << S_ << "[" << 3 * k + 2 << "];\n";
-    if (joint_) {  // the super-leaf members' marginals: sums of the joint accumulators over the other digits
-      std::vector<int> dig(nu_, 0);
+    if (joint_)  // the super-leaf members' marginals: sums of the joint accumulators over the other digits
       for (int j = 0; j < sl_; ++j)
         for (int g = 0; g < 3; ++g) {
           std::string e;
@@ -308,24 +384,17 @@ class Gen {
           }
           o_ << "      const double b" << s_.unrolled[nu_ - sl_ + j] << "_" << g << " = " << e << ";\n";
         }
-    }
     if (fixed_ > 0) {  // this lane's share of the marginals, unnormalised: reduce_body() sums the group's
       for (int p = 0; p < s_.N; ++p)
         for (int g = 0; g < 3; ++g) o_ << "      row[" << 3 * p + g << "] = b" << p << "_" << g << ";\n";
       return o_.str();
     }
     // One division per row and three products (the sums differ from the reference's in their last bits already, by
-    // summation order; 35 -> 25 divisions per five-member site, each ten instructions).  A row sum in the subnormal
-    // range, whose reciprocal overflows, keeps the three divisions behind a real branch.
-    const bool div_rows = env_int("FAMSEQ_LANE_DIVROWS", 0) != 0;  // tuning aid: three divisions per row
+    // summation order).  A row sum in the subnormal range, whose reciprocal overflows, keeps the three divisions behind
+    // a real branch.
     for (int p = 0; p < s_.N; ++p) {
       auto out = [&](int g) { return O_ + "[" + std::to_string(3 * p + g) + "]"; };
       const std::string b = "b" + std::to_string(p);
-      if (div_rows) {
-        o_ << "      { const double s = (" << b << "_0 + " << b << "_1) + " << b << "_2; if (s <= 0) bn_fail = true;\n        " << out(0) << " = "
-           << b << "_0 / s; " << out(1) << " = " << b << "_1 / s; " << out(2) << " = " << b << "_2 / s; }\n";
-        continue;
-      }
       o_ << "      { const double s = (" << b << "_0 + " << b << "_1) + " << b << "_2; if (s <= 0) bn_fail = true;\n"
          << "        if (s < 1e-290) { asm volatile(\"\" ::: \"memory\"); " << out(0) << " = " << b << "_0 / s; " << out(1) << " = " << b
          << "_1 / s; " << out(2) << " = " << b << "_2 / s; }\n"
@@ -335,31 +404,33 @@ class Gen {
     return o_.str();
   }
 
- private:
+ protected:
+  const BlockPlan &p_;
+  const RowLayout &L_;
   const Model &m_;
   const Shape &s_;
-  const int nu_;
-  const int row_len_;  // doubles in the lane's LDS row (>= 3N, odd)
-  const int fixed_;    // outermost looped members whose digit is the lane's (lanes-per-site mode)
+  const int nu_, sl_;
+  const bool joint_;  // super-leaf marginals from 3^sl joint accumulators (see superleaf())
+  const int fixed_;
   const std::string S_, O_;  // the body's scratch array and where the normalised marginals go
-  std::vector<int> outer_;  // looped members, outermost first
-  const bool st_;           // see the constructor
+  const std::vector<int> &outer_;
+  const bool st_;  // see the constructor
   const int pre_;
-  const bool once_;
+  int site_levels_ = 0;  // prefix levels that get no accumulators and no block sums per prefix: the form sums them once per site
   std::string prologue_, prefetch_;  // (pre_) before the innermost loop / inside it, between its table statements and the block
   std::map<std::string, std::string> tq_;  // (pre_) table entry (index text with the innermost digit as '@') -> its loop-carried variable
   std::ostringstream o_;
   int uid_ = 0;
-  bool l_in_lds_ = false;
-  bool joint_ = false;  // super-leaf marginals from 3^sl joint accumulators (see superleaf())
-  std::map<int, int> lds_slot_;  // unrolled member -> first of its 3 slots in the lane's LDS row
-  std::set<int> before_loops_;   // unrolled members whose tables are built once per site
 
-  static int pow3(int e) {
-    int r = 1;
-    while (e-- > 0) r *= 3;
-    return r;
-  }
+  // The unrolled block of one outer step: P the prefix product of the looped members, acc_parent the innermost loop's total.
+  virtual void block(const std::string &P, const std::string &acc_parent) = 0;
+  virtual void before_loops() {}
+  virtual void after_loops() {}
+  // an unrolled member's likelihood, where the row has no slot for it and its table is rebuilt inside the loops
+  virtual std::string unplaced_likelihood(int p, int g) const = 0;
+  // does a loop level read its marginal slot where its step begins (and not where it adds to it)?
+  virtual bool slot_read_ahead() const { return false; }
+  virtual void claim_carried(const std::string &) {}  // the innermost loop, after the next step's loads have been issued
 
   // table offset of member p's factor for child genotype expression `gc` ("2" or "g7"): literal
   // part + digits of outer parents (runtime, uniform) — unrolled parents are added by the caller
@@ -378,7 +449,7 @@ class Gen {
   std::string t_tab(int p) const { return st_ && m_.mother[p] >= 0 ? "tcx" : "tcf"; }
   // founder with its prior folded into the likelihood (scalar_t): pl<p>_<g>, formed once per site
   bool folded(int p) const { return st_ && m_.mother[p] < 0; }
-  std::string l_name(int p, int g) const { return (folded(p) && outer_pos(p) >= 0 ? "pl" : "l") + num(p) + "_" + num(g); }
+  std::string l_name(int p, int g) const { return (folded(p) && p_.outer_pos(p) >= 0 ? "pl" : "l") + num(p) + "_" + num(g); }
   int inner_pos() const { return (int)outer_.size() - 1; }
   // (pre_) the loop-carried variable holding table entry `idx` ('@' = the innermost looped member's digit): loaded for
   // digit 0 ahead of the innermost loop, for the next digit inside it once this digit's table statements are done
@@ -405,18 +476,17 @@ class Gen {
     }
     const int p = outer_[k];
     const std::string g = "g" + num(p), ind(6 + 2 * k, ' ');
-    const std::string lk_g = l_in_lds_ ? S_ + "[" + num(lik_base_ + 3 * (int)k) + " + " + g + "]"
-                                       : "(" + g + " == 0 ? " + l_name(p, 0) + " : (" + g + " == 1 ? " + l_name(p, 1) + " : " + l_name(p, 2) + "))";
+    const std::string lk_g = L_.l_in_lds ? S_ + "[" + num(L_.lik_base + 3 * (int)k) + " + " + g + "]"
+                                         : "(" + g + " == 0 ? " + l_name(p, 0) + " : (" + g + " == 1 ? " + l_name(p, 1) + " : " + l_name(p, 2) + "))";
     const bool inner = pre_ > 0 && (int)k == inner_pos();
-    const bool carried_l = inner && pre_ >= 2 && l_in_lds_;
-    // the once-per-site form reads a level's marginal slot where the step begins: the sum at its end waits for nothing
-    const bool early_acc = once_ && pre_ >= 2 && !carried_l;
+    const bool carried_l = inner && pre_ >= 2 && L_.l_in_lds;
+    const bool early_acc = slot_read_ahead() && !carried_l;
     std::string f_expr = carried_l ? "lq_" : lk_g;
     if (!folded(p))
       f_expr = (inner && m_.mother[p] >= 0 ? carried_entry("tcx", t_index(p, "@", -1, -1, p, "@")) : t_tab(p) + "[" + t_index(p, g, -1, -1) + "]") + " * " + f_expr;
     if (inner) o_ << prologue_;
     if (carried_l)  // this loop's own LDS reads, one step ahead: the member's likelihood, its marginal slot
-      o_ << ind << "double lq_ = " << S_ << "[" << lik_base_ + 3 * (int)k << "], aq_ = " << S_ << "[" << 3 * (int)k << "];\n";
+      o_ << ind << "double lq_ = " << S_ << "[" << L_.lik_base + 3 * (int)k << "], aq_ = " << S_ << "[" << 3 * (int)k << "];\n";
     if ((int)k < fixed_)
       o_ << ind << "{ const int " << g << " = fx" << k << ";  // one digit per lane of the group\n";
     else
@@ -428,23 +498,13 @@ class Gen {
        << bucket_[k + 1];
     if (inner) {
       o_ << ind << "  const int " << g << "n = " << g << " < 2 ? " << g << " + 1 : 2;\n" << prefetch_;
-      if (carried_l) o_ << ind << "  const double lq_n = " << S_ << "[" << lik_base_ + 3 * (int)k << " + " << g << "n];\n";
+      if (carried_l) o_ << ind << "  const double lq_n = " << S_ << "[" << L_.lik_base + 3 * (int)k << " + " << g << "n];\n";
     }
     if (early_acc) o_ << ind << "  const double aq" << p << " = " << S_ << "[" << 3 * (int)k << " + " << g << "];\n";
-    // (once-per-site form: the entries loaded above are claimed here, a table's worth of statements after their issue, by an
-    // empty statement that names them — scalar loads return out of order, so while one is in flight every wait inside the block,
-    // the counted ones of its read groups too, is for all that is outstanding, the group just requested included)
-    if (inner && once_ && !tq_.empty()) {
-      std::vector<std::string> v;
-      for (const auto &kv : tq_) v.push_back(kv.second);
-      std::sort(v.begin(), v.end(), [](const std::string &a, const std::string &b) { return a.size() != b.size() ? a.size() < b.size() : a < b; });
-      for (size_t i = 0; i < v.size(); i += 24) {  // (an asm statement takes thirty operands)
-        o_ << ind << "  asm volatile(\"\" ::";
-        for (size_t j = i; j < std::min(v.size(), i + 24); ++j) o_ << (j > i ? ", " : " ") << "\"s\"(" << v[j] << ")";
-        o_ << ");\n";
-      }
+    if (inner) {
+      claim_carried(ind);
+      o_ << ind << "  __builtin_amdgcn_sched_barrier(0);\n";
     }
-    if (inner) o_ << ind << "  __builtin_amdgcn_sched_barrier(0);\n";
     outer_level(k + 1, "P" + num(p), "acc" + num(p));
     if (carried_l)
       o_ << ind << "  " << S_ << "[" << 3 * (int)k << " + " << g << "] = aq_ + acc" << p << ";\n"
@@ -467,50 +527,13 @@ class Gen {
     }
     return n;
   }
-  // dep_[k]: unrolled levels < k whose digits the block sums of levels >= k depend on
-  std::vector<std::vector<int>> dep_;
-
-  void compute_deps() {
-    dep_.assign(nu_ + 1, {});
-    for (int k = nu_ - 1; k >= 0; --k) {
-      std::vector<char> in(nu_, 0);
-      for (int j = k; j < nu_; ++j) {
-        const int p = s_.unrolled[j];
-        if (m_.mother[p] < 0) continue;
-        for (int par : {m_.mother[p], m_.father[p]})
-          if (s_.upos[par] >= 0 && s_.upos[par] < k) in[s_.upos[par]] = 1;
-      }
-      for (int l = 0; l < k; ++l)
-        if (in[l]) dep_[k].push_back(l);
-    }
-  }
-  // Super-leaf: the deepest t levels are walked together.  Their factors are multiplied once per
-  // outer step into a combined table W (3^t entries per combination of the upper digits they
-  // depend on), so each of the 3^t configurations below a prefix costs exactly one FMA
-  // (prefix * W into the deepest member's marginal) and the other t-1 members take one FMA per
-  // combination of their own and the shallower super-leaf digits (prefix * WQ).  No products are
-  // formed inside the block for these levels.
-  int sl_ = 1;  // t
-  void choose_superleaf() {
-    sl_ = 1;
-    for (int t = std::min(3, nu_); t >= 2; --t) {
-      const int d = (int)dep_[nu_ - t].size();
-      int doubles = pow3(t + d);
-      for (int j = 0; j + 1 < t; ++j) doubles += pow3(j + 1 + d);
-      if (doubles <= 45) {
-        sl_ = t;
-        break;
-      }
-    }
-  }
-  std::string sl_name(const char *prefix, int upto, const std::vector<int> &dig) const {  // W / WQ<j> entry
+  std::string sl_name(const char *prefix, int upto, const std::vector<int> &dig) const {  // W / X entry
     const int k0 = nu_ - sl_;
     std::string n = prefix;
     for (int k = k0; k <= upto; ++k) n += "_" + num(dig[k]);
-    for (int l : dep_[k0]) n += "_" + num(l) + "d" + num(dig[l]);
+    for (int l : p_.dep[k0]) n += "_" + num(l) + "d" + num(dig[l]);
     return n;
   }
-
   // joint accumulator of super-leaf configuration c (most significant digit = shallowest member)
   std::string s_name(int c, std::vector<int> &dig) const {
     const int k0 = nu_ - sl_;
@@ -522,87 +545,33 @@ class Gen {
     for (int k = k0; k < nu_; ++k) n += "_" + num(dig[k]);
     return n;
   }
-
-  // Q<k>[digits of dep_[k]] = sum over the configurations of levels k.. of prod w: the total
+  // Q<k>[digits of dep[k]] = sum over the configurations of levels k.. of prod w: the total
   // weight below a node, per unit of prefix.  Q<nu> = 1.
   std::string q_name(int k, const std::vector<int> &dig) const {
     if (k >= nu_) return "1.0";
     std::string n = "Q" + num(k);
-    for (int l : dep_[k]) n += "_" + num(l) + "d" + num(dig[l]);
+    for (int l : p_.dep[k]) n += "_" + num(l) + "d" + num(dig[l]);
     return n;
+  }
+
+  // where the block's table statements read unrolled member p's likelihood from
+  std::string lk_src(int p, int g) const {
+    for (const auto &ms : L_.lik_slots)
+      if (ms.first == p) return S_ + "[" + num(ms.second + g) + "]";
+    if (L_.before_loops.count(p)) return "l" + num(p) + "_" + num(g);  // used once, ahead of all loops: still in registers
+    return unplaced_likelihood(p, g);
   }
 
   // Table statements, bucketed by the innermost outer loop whose digit they mention
   // (index into outer_, -1 = none): each bucket is emitted at the top of that loop's body, so a
   // table is rebuilt only when a digit it depends on changes.
   std::vector<std::string> bucket_;  // [outer position + 1]
-  // Lazy tables (FAMSEQ_LANE_LAZY, an experiment that is OFF: measured slower): entries (factor tables of
-  // prefix levels, block sums) that depend on the FIRST unrolled member's digit only, and are rebuilt in the
-  // innermost loop anyway, are not built at the top of the block for all three digits but inside that
-  // digit's part of the unrolled tree: a third of them is live at a time.  At ten members that is 14
-  // doubles = 28 VGPRs — the whole of the spill, which the eager form reloads from scratch inside the
-  // block (10 scratch loads per outer step): scratch goes from 108 B to 0.  But the LDS reads behind the
-  // table statements then sit in the middle of the block: 11.1 ms per 4 M sites against 10.3 (built one
-  // digit ahead: 10.6, scratch back at 100 B).  The block total Q0 is summed as the parts go by (same FMA
-  // order), so the results are bit-identical either way.
-  bool lazy0_ = false, lazy_ahead_ = false;
-  std::string lazy0_stmt_[3];
-  bool q0_incremental_ = false;
-
-  // where the block's table statements read unrolled member p's likelihood from
-  std::string lk_src(int p, int g) const {
-    const auto it = lds_slot_.find(p);
-    if (it != lds_slot_.end()) return S_ + "[" + num(it->second + g) + "]";
-    if (before_loops_.count(p)) return "l" + num(p) + "_" + num(g);  // used once, ahead of all loops: still in registers
-    if (once_) return "l" + num(p) + "_" + num(g);  // (the once-per-site form has the registers: nothing is re-read from global memory)
-    return "lg[" + num(3 * p + g) + "]";
-  }
-
-  int outer_pos(int member) const {
-    for (size_t k = 0; k < outer_.size(); ++k)
-      if (outer_[k] == member) return (int)k;
-    return -1;
-  }
-
-  // Loop level (index into outer_, -1 = before all loops) at which unrolled level k's factor table
-  // has to be rebuilt: that of its innermost looped parent.
-  std::vector<int> table_buckets() const {
-    std::vector<int> wb(nu_, -1);
-    for (int k = 0; k < nu_; ++k) {
-      const int p = s_.unrolled[k];
-      if (m_.mother[p] >= 0)
-        for (int par : {m_.mother[p], m_.father[p]})
-          if (s_.upos[par] < 0) wb[k] = std::max(wb[k], outer_pos(par));
-    }
-    return wb;
-  }
 
   void tables() {
     const std::string ind = "        ";
     bucket_.assign(outer_.size() + 1, "");
-    const std::vector<int> wb = table_buckets();  // bucket of level k's factor table
-    std::vector<int> qb(nu_ + 1, -1);             // ... and of its block sums
-    for (int k = nu_ - 1; k >= 0; --k) qb[k] = std::max(qb[k + 1], wb[k]);
-    // which levels' tables / block sums are lazy (see lazy0_): a prefix level k >= 1 whose block sums depend on
-    // level 0's digit only and sit in the innermost loop; the chain must be unbroken from level 1 on, because
-    // the (eager) sums of a level use those of the next
+    const std::vector<int> &wb = p_.wb, &qb = p_.qb;
     const int innermost = (int)outer_.size() - 1;
-    const int n_prefix = nu_ - (sl_ >= 2 ? sl_ : 1);  // levels above the (super-)leaf
-    std::vector<char> lazy_q(nu_ + 1, 0), lazy_w(nu_ + 1, 0);
-    if (const char *e = std::getenv("FAMSEQ_LANE_LAZY")) {  // tuning aid: 0 eager, 1 lazy, 2 lazy one digit ahead
-      lazy0_ = std::atoi(e) != 0;
-      lazy_ahead_ = std::atoi(e) == 2;
-    }
-    if (lazy0_ && innermost >= 0 && n_prefix >= 2)
-      for (int k = 1; k < n_prefix; ++k) {
-        if (!(dep_[k].size() == 1 && dep_[k][0] == 0 && qb[k] == innermost)) break;
-        lazy_q[k] = 1;
-        const int p = s_.unrolled[k];
-        const bool mu = m_.mother[p] >= 0 && s_.upos[m_.mother[p]] >= 0, fu = m_.mother[p] >= 0 && s_.upos[m_.father[p]] >= 0;
-        const bool m0 = mu && s_.upos[m_.mother[p]] == 0, f0 = fu && s_.upos[m_.father[p]] == 0;
-        lazy_w[k] = wb[k] == innermost && (mu + fu) == 1 && (m0 || f0);
-      }
-    q0_incremental_ = lazy_q[1];
     for (int k = 0; k < nu_; ++k) {
       std::ostringstream o;
       const int p = s_.unrolled[k];
@@ -614,8 +583,8 @@ class Gen {
           if (mu) suffix += "m" + num(gm);
           if (fu) suffix += "f" + num(gf);
           for (int g = 0; g < 3; ++g) {
-            if (once_ && k < np_ && const_lvl_[k]) {  // built once per site, kept in the lane's LDS row
-              o << "      " << S_ << "[" << tslot_[k] + ((gm * (fu ? 3 : 1) + gf) * 3 + g) << "] = " << t_tab(p) << "["
+            if (L_.tslot[k] >= 0) {  // built once per site, kept in the lane's LDS row
+              o << "      " << S_ << "[" << L_.tslot[k] + ((gm * (fu ? 3 : 1) + gf) * 3 + g) << "] = " << t_tab(p) << "["
                 << t_index(p, num(g), mu ? gm : -1, fu ? gf : -1) << "] * " << lk_src(p, g) << ";\n";
               continue;
             }
@@ -638,31 +607,16 @@ class Gen {
             }
           }
         }
-      if (lazy_w[k]) continue;  // emitted per digit of the first unrolled member (below)
       bucket_[wb[k] + 1] += o.str();
     }
-    for (int k = 1; k < nu_; ++k) {
-      if (!lazy_w[k]) continue;
-      const int p = s_.unrolled[k];
-      const bool mu = s_.upos[m_.mother[p]] == 0, fu = s_.upos[m_.father[p]] == 0;  // exactly one of them is level 0
-      for (int d = 0; d < 3; ++d) {
-        std::ostringstream o;
-        const std::string suffix = (mu ? "m" : "f") + num(d);
-        for (int g = 0; g < 3; ++g)
-          o << ind << "const double w" << p << "_" << g << suffix << " = " << t_tab(p) << "[" << t_index(p, num(g), mu ? d : -1, fu ? d : -1)
-            << "] * " << lk_src(p, g) << ";\n";
-        lazy0_stmt_[d] += o.str();
-      }
-    }
     // block sums, deepest level first
-    for (int k = nu_ - 1; k >= 0; --k) {
-      if (once_ && k < np_) break;  // no block sums per prefix in this form
+    for (int k = nu_ - 1; k >= site_levels_; --k) {
       std::ostringstream o;
-      const int nd = (int)dep_[k].size();
+      const int nd = (int)p_.dep[k].size();
       std::vector<int> dig(nu_, 0);
       for (int code = 0; code < pow3(nd); ++code) {
         int c = code;
-        for (int l : dep_[k]) {
+        for (int l : p_.dep[k]) {
           dig[l] = c % 3;
           c /= 3;
         }
@@ -673,20 +627,18 @@ class Gen {
           if (q == "1.0") e = e.empty() ? w : "(" + e + " + " + w + ")";
           else e = e.empty() ? "(" + w + " * " + q + ")" : "__builtin_fma(" + w + ", " + q + ", " + e + ")";
         }
-        if (k == 0 && q0_incremental_) continue;  // summed inside the block as level 0's digits go by
-        if (lazy_q[k]) lazy0_stmt_[dig[0]] += ind + "const double " + q_name(k, dig) + " = " + e + ";\n";
-        else o << ind << "const double " << q_name(k, dig) << " = " << e << ";\n";
+        o << ind << "const double " << q_name(k, dig) << " = " << e << ";\n";
       }
       bucket_[qb[k] + 1] += o.str();
     }
     if (sl_ < 2) return;
-    // super-leaf tables: running products over the t levels, per combination of the upper digits
+    // super-leaf tables: running products over the sl levels, per combination of the upper digits
     std::ostringstream o;
-    const int k0 = nu_ - sl_, nd = (int)dep_[k0].size();
+    const int k0 = nu_ - sl_, nd = (int)p_.dep[k0].size();
     std::vector<int> dig(nu_, 0);
     for (int code = 0; code < pow3(nd); ++code) {
       int c = code;
-      for (int l : dep_[k0]) {
+      for (int l : p_.dep[k0]) {
         dig[l] = c % 3;
         c /= 3;
       }
@@ -699,12 +651,7 @@ class Gen {
             here = sl_name(k == nu_ - 1 ? "W" : "X", k, dig);
             o << ind << "const double " << here << " = " << prod << " * " << w << ";\n";
           }
-          if (k < nu_ - 1) {
-            if (!joint_)
-              o << ind << "const double " << sl_name(("WQ" + num(k - k0)).c_str(), k, dig) << " = " << here << " * "
-                << q_name(k + 1, dig) << ";\n";
-            walk(k + 1, here);
-          }
+          if (k < nu_ - 1) walk(k + 1, here);
         }
       };
       walk(k0, "");
@@ -712,34 +659,148 @@ class Gen {
     bucket_[qb[k0] + 1] += o.str();
   }
 
-  // ---- The once-per-site form (once_) -------------------------------------------------------------------------------
-  // Every weight of an outer step is P x (product of the prefix levels' table entries) x W[c].  Where the
-  // super-leaf table W depends on no prefix digit (dep_[nu_ - sl_] empty), everything but the 3^N configuration
-  // FMAs factors:
-  //   * a prefix level whose table mentions no loop digit ("constant": a founder, or a child of unrolled
-  //     members only) has the same entries in every step: they are formed once per site and chrX pass, kept in
-  //     the lane's LDS row and read where a prefix product is formed (one group of reads ahead of their use);
-  //   * the block total of a step is P Q sum_c v_c C_c: Q the sum of W, v_c the product of the tables that ARE
-  //     rebuilt per step (c: the digits they mention, D_), C_c the sum of the constant tables' products over the
-  //     other prefix digits — taken once per site, ahead of the loops;
-  //   * the prefix members' marginals need no per-step work beyond U_c += P Q v_c: after the loops one walk of
-  //     the prefix tree with U_c in the place of the per-step tables yields all of them (site_walk).
-  // Sums of non-negative terms in the order written here: results differ from the per-prefix form's in their
-  // last bits and are bit-reproducible.
-  int np_ = 0;                    // prefix levels: unrolled levels above the super-leaf
-  int lik_base_ = 0;              // first LDS slot of the looped members' likelihoods
-  std::vector<char> const_lvl_;   // prefix level -> its table mentions no loop digit
-  std::vector<int> tslot_;        // ... and the first slot of that table in the lane's LDS row
-  std::vector<int> D_;            // prefix levels whose digits the per-step tables mention, ascending
+  // Every configuration: ONE FMA — its joint weight prefix * W is formed and added to the
+  // accumulator of its super-leaf digits.  The 3^sl accumulators run over the whole site; the
+  // marginals of all sl members are sums of them, taken once at the end (body()), and
+  // the accumulators form 3^sl independent dependency chains.
+  // (No pins here: the prefix products are pinned where they are formed, which is what keeps
+  // hipcc from forming all of them up front; a pin per three FMAs cost an s_nop each, -5 %.)
+  void superleaf(const std::string &P, std::vector<int> &dig, const std::string &ind) {
+    for (int c = 0; c < pow3(sl_); ++c) {
+      const std::string a = s_name(c, dig);  // sets dig[k0..]
+      o_ << ind << a << " = __builtin_fma(" << P << ", " << sl_name("W", nu_ - 1, dig) << ", " << a << ");\n";
+    }
+  }
+
+  // Where prefix products are formed the instruction order is pinned (left alone, hipcc forms the
+  // products of the whole unrolled tree ahead of their uses and spills) by a scheduling barrier:
+  // nothing is moved across, and no instruction is emitted.
+  static std::string pin(const std::string &ind) { return ind + "__builtin_amdgcn_sched_barrier(0);\n"; }
+};
+
+// The per-prefix form: every prefix level adds prefix * (block sum below) to its member's marginal where the prefix
+// product is formed, in every outer step.
+class PrefixEmitter : public Emitter {
+ public:
+  using Emitter::Emitter;
+
+ private:
+  // (re-read from the site's own row in global memory: L2 hits)
+  std::string unplaced_likelihood(int p, int g) const override { return "lg[" + num(3 * p + g) + "]"; }
+
+  void level(int k, const std::string &P, std::vector<int> &dig, const std::string &ind) {
+    const int p = s_.unrolled[k];
+    if (sl_ >= 2 && k == nu_ - sl_) {
+      superleaf(P, dig, ind);
+      return;
+    }
+    if (k == nu_ - 1) {
+      for (int g = 0; g < 3; ++g)
+        o_ << ind << "b" << p << "_" << g << " = __builtin_fma(" << P << ", " << w_name(k, g, dig) << ", b" << p << "_" << g
+           << ");\n";
+      o_ << ind << "asm volatile(\"\" : \"+v\"(b" << p << "_0), \"+v\"(b" << p << "_1), \"+v\"(b" << p << "_2), \"+v\"(" << P
+         << "));\n";
+      return;
+    }
+    for (int g = 0; g < 3; ++g) {
+      dig[k] = g;
+      const std::string pg = "p" + num(uid_++);
+      o_ << ind << "double " << pg << " = " << P << " * " << w_name(k, g, dig) << ";\n"
+         << ind << "b" << p << "_" << g << " = __builtin_fma(" << pg << ", " << q_name(k + 1, dig) << ", b" << p << "_" << g
+         << ");\n"
+         << pin(ind);
+      level(k + 1, pg, dig, ind);
+      o_ << pin(ind);
+    }
+  }
+
+  void block(const std::string &P, const std::string &acc_parent) override {
+    const std::string ind(6 + 2 * outer_.size(), ' '), in2 = ind + "  ";
+    std::vector<int> dig(nu_, 0);
+    o_ << ind << "{\n" << in2 << "double Pb = " << P << ";\n";
+    if (!acc_parent.empty()) o_ << in2 << acc_parent << " += Pb * " << q_name(0, dig) << ";\n";
+    level(0, "Pb", dig, in2);
+    o_ << ind << "}\n";
+  }
+};
+
+// The once-per-site form.
+// Every weight of an outer step is P x (product of the prefix levels' table entries) x W[c].  Where the
+// super-leaf table W depends on no prefix digit (BlockPlan::once_applies), everything but the 3^N configuration
+// FMAs factors:
+//   * a prefix level whose table mentions no loop digit ("constant": a founder, or a child of unrolled
+//     members only) has the same entries in every step: they are formed once per site and chrX pass, kept in
+//     the lane's LDS row and read where a prefix product is formed (one group of reads ahead of their use);
+//   * the block total of a step is P Q sum_c v_c C_c: Q the sum of W, v_c the product of the tables that ARE
+//     rebuilt per step (c: the digits they mention, D), C_c the sum of the constant tables' products over the
+//     other prefix digits — taken once per site, ahead of the loops;
+//   * the prefix members' marginals need no per-step work beyond U_c += P Q v_c: after the loops one walk of
+//     the prefix tree with U_c in the place of the per-step tables yields all of them (site_walk).
+// Sums of non-negative terms in the order written here: results differ from the per-prefix form's in their
+// last bits and are bit-reproducible.
+// It honours prefetch too: 1 the same carried entries, 2 the likelihoods those entries multiply are read ahead of the
+// innermost loop and every loop level reads its marginal slot where its step begins (one wave per SIMD: a wait right
+// behind its load is time nobody else fills).
+class OnceEmitter : public Emitter {
+ public:
+  OnceEmitter(const BlockPlan &plan, const RowLayout &layout, bool scalar_t, int prefetch)
+      : Emitter(plan, layout, false, scalar_t, prefetch), np_(plan.np()), D_(layout.D) {
+    if (!layout.fits || !plan.once_applies()) throw std::logic_error("enumeration codegen: the once-per-site form does not fit this shape");
+    site_levels_ = np_;
+    // read groups: the entries that become known at a node of the prefix tree, in walk order; a group opens only once
+    // configuration FMAs lie between it and the one before (the root's entries and the first subtree's are one group)
+    std::vector<int> dig(nu_, 0);
+    bool work_since = true;
+    std::function<void(int)> node = [&](int j) {  // node at level j (-1: the root), its digits in dig
+      std::vector<std::pair<int, int>> here;
+      for (int k = j + 1; k < np_; ++k)
+        if (constant(k) && max_prefix_parent(k) == j)
+          for (int g = 0; g < 3; ++g) here.push_back({k, t_off(k, g, dig)});
+      if (!here.empty()) {
+        if (work_since) {
+          consumer_[node_key(j, dig)] = (int)groups_.size();
+          groups_.push_back({});
+          work_since = false;
+        }
+        groups_.back().insert(groups_.back().end(), here.begin(), here.end());
+      }
+      if (j == np_ - 1) {
+        work_since = true;
+        return;
+      }
+      for (int g = 0; g < 3; ++g) {
+        dig[j + 1] = g;
+        node(j + 1);
+      }
+    };
+    node(-1);
+  }
+
+ private:
+  const int np_;              // prefix levels
+  const std::vector<int> &D_;  // prefix levels whose digits the per-step tables mention, ascending
   std::vector<std::vector<std::pair<int, int>>> groups_;  // table entries (level, offset) read together, in walk order
   std::map<std::string, int> consumer_;                   // tree node (its digits; "" = root) below which a group is first used
 
-  int t_entries(int k) const {
-    const int p = s_.unrolled[k];
-    int e = 3;
-    if (m_.mother[p] >= 0) e *= (s_.upos[m_.mother[p]] >= 0 ? 3 : 1) * (s_.upos[m_.father[p]] >= 0 ? 3 : 1);
-    return e;
+  bool constant(int k) const { return L_.tslot[k] >= 0; }
+  // (this form has the registers: nothing is re-read from global memory)
+  std::string unplaced_likelihood(int p, int g) const override { return "l" + num(p) + "_" + num(g); }
+  // a level's marginal slot is read where the step begins: the sum at its end waits for nothing
+  bool slot_read_ahead() const override { return pre_ >= 2; }
+  // The entries loaded a step ahead are claimed here, a table's worth of statements after their issue, by an empty statement
+  // that names them — scalar loads return out of order, so while one is in flight every wait inside the block, the counted
+  // ones of its read groups too, is for all that is outstanding, the group just requested included.
+  void claim_carried(const std::string &ind) override {
+    std::vector<std::string> v;
+    for (const auto &kv : tq_) v.push_back(kv.second);
+    std::sort(v.begin(), v.end(), [](const std::string &a, const std::string &b) { return a.size() != b.size() ? a.size() < b.size() : a < b; });
+    for (size_t i = 0; i < v.size(); i += 24) {  // (an asm statement takes thirty operands)
+      o_ << ind << "  asm volatile(\"\" ::";
+      for (size_t j = i; j < std::min(v.size(), i + 24); ++j) o_ << (j > i ? ", " : " ") << "\"s\"(" << v[j] << ")";
+      o_ << ");\n";
+    }
   }
+
   int t_off(int k, int g, const std::vector<int> &dig) const {  // the order tables() writes a level's entries in
     const int p = s_.unrolled[k];
     int o = 0;
@@ -768,84 +829,11 @@ class Gen {
     return j;
   }
 
-  // Slots of the lane's LDS row, the digits the per-step tables mention and the read groups.  false: no room, or more
-  // than two such digits (3^|D| values per step).
-  bool plan_once() {
-    const int no = (int)outer_.size();
-    np_ = nu_ - sl_;
-    const std::vector<int> wb = table_buckets();
-    const_lvl_.assign(nu_, 0);
-    tslot_.assign(nu_, -1);
-    D_.clear();
-    lds_slot_.clear();
-    before_loops_.clear();
-    int next = 3 * no;
-    std::set<int> d;
-    for (int k = 0; k < np_; ++k) {
-      if (wb[k] < 0) {
-        const_lvl_[k] = 1;
-        tslot_[k] = next;
-        next += t_entries(k);
-        continue;
-      }
-      d.insert(k);
-      const int p = s_.unrolled[k];
-      for (int par : {m_.mother[p], m_.father[p]})
-        if (s_.upos[par] >= 0) d.insert(s_.upos[par]);
-    }
-    if (next > row_len_ || d.size() > 2) return false;
-    D_.assign(d.begin(), d.end());
-    // likelihoods the table statements inside the loops read: deepest loop first, while there is room (tables());
-    // the looped members' own behind them, all or none
-    std::vector<int> order;
-    for (int k = 0; k < nu_; ++k)
-      if (wb[k] >= 0) order.push_back(k);
-      else before_loops_.insert(s_.unrolled[k]);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return wb[a] > wb[b]; });
-    for (int k : order) {
-      if (next + 3 > row_len_) break;
-      lds_slot_[s_.unrolled[k]] = next;
-      next += 3;
-    }
-    l_in_lds_ = next + 3 * no <= row_len_;
-    lik_base_ = next;
-    // read groups: the entries that become known at a node of the prefix tree, in walk order; a group opens only once
-    // configuration FMAs lie between it and the one before (the root's entries and the first subtree's are one group)
-    groups_.clear();
-    consumer_.clear();
-    std::vector<int> dig(nu_, 0);
-    bool work_since = true;
-    std::function<void(int)> node = [&](int j) {  // node at level j (-1: the root), its digits in dig
-      std::vector<std::pair<int, int>> here;
-      for (int k = j + 1; k < np_; ++k)
-        if (const_lvl_[k] && max_prefix_parent(k) == j)
-          for (int g = 0; g < 3; ++g) here.push_back({k, t_off(k, g, dig)});
-      if (!here.empty()) {
-        if (work_since) {
-          consumer_[node_key(j, dig)] = (int)groups_.size();
-          groups_.push_back({});
-          work_since = false;
-        }
-        groups_.back().insert(groups_.back().end(), here.begin(), here.end());
-      }
-      if (j == np_ - 1) {
-        work_since = true;
-        return;
-      }
-      for (int g = 0; g < 3; ++g) {
-        dig[j + 1] = g;
-        node(j + 1);
-      }
-    };
-    node(-1);
-    return true;
-  }
-
   void fetch_group(int i, const std::string &ind) {
     // (the clobber: these reads are repeated in every step on purpose — left to itself the compiler may keep the
     // tables in registers across the block instead)
     o_ << ind << "asm volatile(\"\" ::: \"memory\");\n";
-    for (const auto &e : groups_[i]) o_ << ind << t_var(e.first, e.second) << " = " << S_ << "[" << tslot_[e.first] + e.second << "];\n";
+    for (const auto &e : groups_[i]) o_ << ind << t_var(e.first, e.second) << " = " << S_ << "[" << L_.tslot[e.first] + e.second << "];\n";
   }
 
   // product of the per-step tables' entries for combination c of the digits in D_ (a table entry, or a new variable)
@@ -857,7 +845,7 @@ class Gen {
     }
     std::string v;
     for (int k = 0; k < np_; ++k) {
-      if (const_lvl_[k]) continue;
+      if (constant(k)) continue;
       const std::string w = w_name(k, dig[k], dig);
       if (v.empty()) {
         v = w;
@@ -894,7 +882,7 @@ class Gen {
           cur = n;
         };
         if (final && k == at) times("U_" + num(dcode(dig)));
-        if (const_lvl_[k]) times(S_ + "[" + num(tslot_[k] + t_off(k, g, dig)) + "]");
+        if (constant(k)) times(S_ + "[" + num(L_.tslot[k] + t_off(k, g, dig)) + "]");
         if (k < np_ - 1) sub[g] = walk(k + 1, cur);
         else {
           sub[g] = cur.empty() ? "1.0" : cur;
@@ -910,7 +898,7 @@ class Gen {
     walk(0, "");
   }
 
-  void once_before_loops() {
+  void before_loops() override {
     for (int c = 0; c < pow3((int)D_.size()); ++c) o_ << "      double C_" << c << " = 0, U_" << c << " = 0;\n";
     site_walk(false);
     std::set<std::string> declared;  // (an entry belongs to several groups where its table skips a level's digit)
@@ -920,7 +908,7 @@ class Gen {
     if (!groups_.empty()) fetch_group(0, "      ");
   }
 
-  void once_after_loops() {
+  void after_loops() override {
     for (int k = 0; k < np_; ++k) {
       const int p = s_.unrolled[k];
       o_ << "      double b" << p << "_0 = 0, b" << p << "_1 = 0, b" << p << "_2 = 0;\n";
@@ -928,159 +916,46 @@ class Gen {
     site_walk(true);
   }
 
-  void superleaf(const std::string &P, std::vector<int> &dig, const std::string &ind) {
-    const int k0 = nu_ - sl_, last = s_.unrolled[nu_ - 1];
-    if (joint_) {
-      // Every configuration: ONE FMA — its joint weight prefix * W is formed and added to the
-      // accumulator of its super-leaf digits.  The 3^sl accumulators run over the whole site; the
-      // marginals of all sl members are sums of them, taken once at the end (body()).  Against one
-      // set of bins per member (39 FMAs per 27 configurations at sl = 3) this is 27 per 27, and
-      // the accumulators form 3^sl independent dependency chains.
-      // (No pins here: the prefix products are pinned where they are formed, which is what keeps
-      // hipcc from forming all of them up front; a pin per three FMAs cost an s_nop each, -5 %.)
-      for (int c = 0; c < pow3(sl_); ++c) {
-        const std::string a = s_name(c, dig);  // sets dig[k0..]
-        o_ << ind << a << " = __builtin_fma(" << P << ", " << sl_name("W", nu_ - 1, dig) << ", " << a << ");\n";
-      }
-      return;
-    }
-    // every configuration: one FMA, its joint weight formed as prefix * W
-    std::function<void(int)> leaves = [&](int k) {
-      for (int g = 0; g < 3; ++g) {
-        dig[k] = g;
-        if (k < nu_ - 1) {
-          leaves(k + 1);
-          continue;
-        }
-        o_ << ind << "b" << last << "_" << g << " = __builtin_fma(" << P << ", " << sl_name("W", nu_ - 1, dig) << ", b"
-           << last << "_" << g << ");\n";
-      }
-      if (k == nu_ - 1)
-        o_ << ind << "asm volatile(\"\" : \"+v\"(b" << last << "_0), \"+v\"(b" << last << "_1), \"+v\"(b" << last
-           << "_2), \"+v\"(" << P << "));\n";
-    };
-    leaves(k0);
-    // the shallower super-leaf members: one FMA per combination of their digits
-    for (int j = 0; j + 1 < sl_; ++j) {
-      const int p = s_.unrolled[k0 + j];
-      std::function<void(int)> bins = [&](int k) {
-        for (int g = 0; g < 3; ++g) {
-          dig[k] = g;
-          if (k < k0 + j) {
-            bins(k + 1);
-            continue;
-          }
-          o_ << ind << "b" << p << "_" << g << " = __builtin_fma(" << P << ", " << sl_name(("WQ" + num(j)).c_str(), k0 + j, dig)
-             << ", b" << p << "_" << g << ");\n";
-        }
-      };
-      bins(k0);
-      o_ << ind << "asm volatile(\"\" : \"+v\"(b" << p << "_0), \"+v\"(b" << p << "_1), \"+v\"(b" << p << "_2), \"+v\"("
-         << P << "));\n";
-    }
-  }
-
-  // Where prefix products are formed the instruction order is pinned (left alone, hipcc forms the
-  // products of the whole unrolled tree ahead of their uses and spills).  pin_style_ 1: an empty asm
-  // statement tying the values to registers at that point; 2: a scheduling barrier
-  // (__builtin_amdgcn_sched_barrier: nothing is moved across, and no instruction is emitted — the asm
-  // form costs an s_nop each); 0: none.
-  int pin_style_ = 2;  // measured on MI355X: 10.59 ms (asm) -> 10.20 ms (barrier) per 4 M 10-member sites, 139.4 -> 136.8 ms at 15 members
-  std::string pin(const std::string &operands, const std::string &ind) const {
-    if (pin_style_ == 2) return ind + "__builtin_amdgcn_sched_barrier(0);\n";
-    if (pin_style_ == 0) return "";
-    return ind + "asm volatile(\"\" : " + operands + ");\n";
-  }
-
+  // a prefix level: the product, nothing else — the members' marginals are formed after the loops
   void level(int k, const std::string &P, std::vector<int> &dig, const std::string &ind) {
-    const int p = s_.unrolled[k];
-    if (sl_ >= 2 && k == nu_ - sl_) {
+    if (k == np_) {
       superleaf(P, dig, ind);
-      return;
-    }
-    if (once_) {
-      // a prefix level of the once-per-site form: the product, nothing else — the members' marginals are formed after the loops
-      for (int g = 0; g < 3; ++g) {
-        dig[k] = g;
-        const std::string pg = "p" + num(uid_++);
-        o_ << ind << "double " << pg << " = " << P << " * " << (const_lvl_[k] ? t_var(k, t_off(k, g, dig)) : w_name(k, g, dig)) << ";\n"
-           << pin("\"+v\"(" + pg + ")", ind);
-        const auto it = consumer_.find(node_key(k, dig));
-        if (it != consumer_.end()) fetch_group((it->second + 1) % (int)groups_.size(), ind);
-        level(k + 1, pg, dig, ind);
-        o_ << pin("\"+v\"(" + P + ")", ind);
-      }
-      return;
-    }
-    if (k == nu_ - 1) {
-      for (int g = 0; g < 3; ++g)
-        o_ << ind << "b" << p << "_" << g << " = __builtin_fma(" << P << ", " << w_name(k, g, dig) << ", b" << p << "_" << g
-           << ");\n";
-      o_ << ind << "asm volatile(\"\" : \"+v\"(b" << p << "_0), \"+v\"(b" << p << "_1), \"+v\"(b" << p << "_2), \"+v\"(" << P
-         << "));\n";
       return;
     }
     for (int g = 0; g < 3; ++g) {
       dig[k] = g;
-      if (k == 0) {
-        // one digit ahead: the LDS reads behind these statements return while the previous digit's part of the
-        // tree is computed (built at the head of their own part they stalled it: 11.1 vs 10.3 ms per 4 M sites)
-        if (lazy_ahead_) {
-          if (g == 0) o_ << lazy0_stmt_[0];
-          if (g < 2) o_ << lazy0_stmt_[g + 1];
-        } else {
-          o_ << lazy0_stmt_[g];
-        }
-        if (q0_incremental_) {  // the block total, in the order the eager form adds it
-          const std::string w = w_name(0, g, dig), q = q_name(1, dig);
-          if (g == 0) o_ << ind << "double Q0i = " << w << " * " << q << ";\n";
-          else o_ << ind << "Q0i = __builtin_fma(" << w << ", " << q << ", Q0i);\n";
-        }
-      }
       const std::string pg = "p" + num(uid_++);
-      o_ << ind << "double " << pg << " = " << P << " * " << w_name(k, g, dig) << ";\n"
-         << ind << "b" << p << "_" << g << " = __builtin_fma(" << pg << ", " << q_name(k + 1, dig) << ", b" << p << "_" << g
-         << ");\n"
-         << pin("\"+v\"(" + pg + "), \"+v\"(b" + num(p) + "_" + num(g) + ")", ind);
+      o_ << ind << "double " << pg << " = " << P << " * " << (constant(k) ? t_var(k, t_off(k, g, dig)) : w_name(k, g, dig)) << ";\n" << pin(ind);
+      const auto it = consumer_.find(node_key(k, dig));
+      if (it != consumer_.end()) fetch_group((it->second + 1) % (int)groups_.size(), ind);
       level(k + 1, pg, dig, ind);
-      o_ << pin("\"+v\"(" + P + "), \"+v\"(b" + num(p) + "_" + num(g) + ")", ind);
+      o_ << pin(ind);
     }
   }
 
-  void block(const std::string &P, const std::string &acc_parent) {
-    const std::string ind(6 + 2 * outer_.size(), ' ');
-    o_ << ind << "{\n";
-    const std::string in2 = ind + "  ";
+  // The block's total and the prefix members' marginals, once per step: every weight of the step is
+  // (P Q) x (product of the prefix tables), Q the sum of the super-leaf table.  The tables built per step
+  // enter through v_c (one value per combination c of the digits they mention); the others are the same in
+  // every step of the site, so the sums of P Q v_c over the steps (U_c) are all the prefix members need.
+  void block(const std::string &P, const std::string &acc_parent) override {
+    const std::string ind(6 + 2 * outer_.size(), ' '), in2 = ind + "  ";
     std::vector<int> dig(nu_, 0);
-    if (once_) {
-      // The block's total and the prefix members' marginals, once per step: every weight of the step is
-      // (P Q) x (product of the prefix tables), Q the sum of the super-leaf table.  The tables built per step
-      // enter through v_c (one value per combination c of the digits they mention); the others are the same in
-      // every step of the site, so the sums of P Q v_c over the steps (U_c) are all the prefix members need.
-      o_ << in2 << "const double PQ = " << P << " * " << q_name(nu_ - sl_, dig) << ";\n";
-      std::string z;
-      for (int c = 0; c < pow3((int)D_.size()); ++c) {
-        const std::string v = step_value(c, in2);
-        o_ << in2 << "U_" << c << " = __builtin_fma(PQ, " << v << ", U_" << c << ");\n";
-        z = z.empty() ? "(" + v + " * C_" + num(c) + ")" : "__builtin_fma(" + v + ", C_" + num(c) + ", " + z + ")";
-      }
-      if (!acc_parent.empty()) o_ << in2 << acc_parent << " += PQ * " << z << ";\n";
-      o_ << in2 << "double Pb = " << P << ";\n" << pin("\"+v\"(Pb)", in2);
-      if (consumer_.count("")) fetch_group((consumer_[""] + 1) % (int)groups_.size(), in2);
-      level(0, "Pb", dig, in2);
-      o_ << ind << "}\n";
-      return;
+    o_ << ind << "{\n" << in2 << "const double PQ = " << P << " * " << q_name(np_, dig) << ";\n";
+    std::string z;
+    for (int c = 0; c < pow3((int)D_.size()); ++c) {
+      const std::string v = step_value(c, in2);
+      o_ << in2 << "U_" << c << " = __builtin_fma(PQ, " << v << ", U_" << c << ");\n";
+      z = z.empty() ? "(" + v + " * C_" + num(c) + ")" : "__builtin_fma(" + v + ", C_" + num(c) + ", " + z + ")";
     }
-    o_ << in2 << "double Pb = " << P << ";\n";
-    if (!acc_parent.empty() && !q0_incremental_) o_ << in2 << acc_parent << " += Pb * " << q_name(0, dig) << ";\n";
+    if (!acc_parent.empty()) o_ << in2 << acc_parent << " += PQ * " << z << ";\n";
+    o_ << in2 << "double Pb = " << P << ";\n" << pin(in2);
+    if (consumer_.count("")) fetch_group((consumer_[""] + 1) % (int)groups_.size(), in2);
     level(0, "Pb", dig, in2);
-    if (!acc_parent.empty() && q0_incremental_) o_ << in2 << acc_parent << " += Pb * Q0i;\n";
     o_ << ind << "}\n";
   }
 };
 
 }  // namespace
-
 namespace {
 
 // fp64 statements of a generated body per site, each weighted by 3^(digit loops around it): what the kernel's time follows
@@ -1122,96 +997,137 @@ double fp64_statements(const std::string &body) {
   return total;
 }
 
-// LDS row of the once-per-site form (Gen::plan_once): what it would like, cut to what four one-wave workgroups per CU leave
-// (each also holds the 432-double transmission table); 0: not even the output row fits.
-int once_row_len(const Model &m, const Shape &s, int bt) {
-  int want = 6 * (int)s.outer.size();
-  for (int p : s.unrolled) {
-    const bool has = m.mother[p] >= 0;
-    const bool looped = has && (s.upos[m.mother[p]] < 0 || s.upos[m.father[p]] < 0);
-    want += looped ? 3 : 3 * (has ? (s.upos[m.mother[p]] >= 0 ? 3 : 1) * (s.upos[m.father[p]] >= 0 ? 3 : 1) : 1);
-  }
-  want = std::max(want, 3 * m.n_members) | 1;
-  int fit = (160 * 1024 / 4 - 432 * 8) / (bt * 8);
-  if (fit % 2 == 0) --fit;
-  return fit < ((3 * m.n_members) | 1) ? 0 : std::min(want, fit);
+// Doubles per lane (an odd count) that fit in the 160 KB of LDS with `bt` lanes per workgroup and `w` workgroups per CU,
+// each workgroup also holding the 432-double transmission table (the call-path form: a byte per member and lane and two
+// small tables as well) — and the unrolled members with a looped parent, whose likelihoods want a place there.
+struct LdsRoom {
+  int fit, looped_tables;
+};
+LdsRoom lds_room(const BlockPlan &p, int bt, int w, bool call_mode) {
+  const int x = (160 * 1024 / w - 432 * 8 - (call_mode ? bt * p.m.n_members + 256 + 2064 : 0)) / (bt * 8);
+  return {(x - 1) | 1, p.looped_tables()};
+}
+
+// The lane's LDS row: 3N doubles padded to an odd count, plus — while two workgroups per CU still
+// fit — room for the likelihoods of unrolled members whose tables are rebuilt inside
+// the loops (otherwise re-read from global memory there: L2 misses that show up as HBM traffic).
+int lane_row_len(const BlockPlan &p, int bt, bool call_mode) {
+  const LdsRoom room = lds_room(p, bt, 2, call_mode);
+  const int row_len = (3 * p.m.n_members) | 1, no = (int)p.outer.size();
+  const int want = ((6 * no <= row_len ? 6 : 3) * no + 3 * room.looped_tables) | 1;
+  return want > row_len ? std::min(want, std::max(row_len, room.fit)) : row_len;
+}
+
+// LDS row of the once-per-site form (row_layout): what it would like, cut to what four one-wave workgroups per CU leave;
+// 0: not even the output row fits.
+int once_row_len(const BlockPlan &p, int bt) {
+  int want = 6 * (int)p.outer.size();
+  for (int k = 0; k < p.nu; ++k) want += p.wb[k] >= 0 ? 3 : p.entries[k];
+  const int w3 = 3 * p.m.n_members, fit = lds_room(p, bt, 4, false).fit;
+  return fit < (w3 | 1) ? 0 : std::min(std::max(want, w3) | 1, fit);
 }
 
 struct LaneForm {
-  bool once = false;
-  Shape shape;       // of the form taken
+  bool once = false, late = false;
+  Shape shape;  // of the form taken
   int row_len = 0;
-  std::string body;
+  bool scalar_t = false;
+  std::string body;                       // (empty where it was not asked for and the cost model did not need it)
   double fp64_parent = 0, fp64_once = 0;  // the cost model's counts (once: 0 where the form does not apply)
 };
 
-// The body of the one-lane-per-site kernel (group_digits = 0, not the call path: that form keeps the per-prefix text, and its
-// posteriors differ from the once-per-site form's in their last bits), in the form the cost model takes:
-// the once-per-site form (Gen, "The once-per-site form") where it applies, fits four workgroups per CU and executes
-// fewer fp64 statements per site than the per-prefix form (may_once: variants 4-7 ask for it); FAMSEQ_LANE_HOIST=0 (tuning aid)
-// keeps the latter.
-LaneForm lane_form(const Model &m, const Shape &s, int row_len, int bt, bool scalar_t, int prefetch, bool may_once) {
+// Shape, form, row length and body of the one-lane-per-site kernel (group_digits = 0) for the block shape `s`.
+// may_once (variants 4-7, not the call path: that form keeps the per-prefix text, and its posteriors differ from the
+// once-per-site form's in their last bits): the once-per-site form (OnceEmitter) where it applies, fits four workgroups
+// per CU and executes fewer fp64 statements per site than the per-prefix form; FAMSEQ_LANE_HOIST=0 (tuning aid) keeps the latter.
+LaneForm lane_form(const Model &m, const Shape &s, bool call_mode, bool may_once, bool need_body = true) {
   LaneForm f;
-  f.shape = s, f.row_len = row_len;
-  {
-    Gen gen(m, s, row_len, 0, false, scalar_t, prefetch);
-    f.body = gen.body();
-  }
-  if (!may_once || !scalar_t || env_int("FAMSEQ_LANE_HOIST", 1) == 0) return f;
-  f.fp64_parent = fp64_statements(f.body);
-  Shape h = s;
-  {
-    std::vector<int> ordered;
-    Gen probe(m, s, row_len, 0, false, scalar_t, prefetch);
-    const int join = probe.joinable_member(&ordered);
-    if (join >= 0) {  // part 1: the innermost looped member becomes the block's outermost prefix level
-      h.outer.clear();
-      for (int p : ordered)
-        if (p != join) h.outer.push_back(p);
-      h.unrolled.insert(h.unrolled.begin(), join);
-      for (size_t k = 0; k < h.unrolled.size(); ++k) h.upos[h.unrolled[k]] = (int)k;
+  f.shape = s;
+  if (s.unrolled.empty()) return f;
+  const int bt = enumgen_block_threads(m, 0), no = (int)s.outer.size();
+  const BlockPlan plan(m, s);
+  f.row_len = lane_row_len(plan, bt, call_mode);
+  const int prefetch = env_int("FAMSEQ_LANE_PRE", 2);  // tuning aid: 0 none, 1 table entries, 2 and LDS reads (both forms: see Emitter)
+  // An experiment that is OFF (FAMSEQ_LANE_LATE=1 turns it on): the sum-product kernel's order of phases for
+  // the enumeration too — the whole computation first (marginals to registers), the next chunk requested,
+  // then the two outputs — instead of single posterior / store / enumeration / store: one barrier fewer and
+  // the prefetch in flight through both output phases; the row keeps the likelihoods until the end, scratch
+  // slots follow them.  Measured slower (8 M sites, tools/kernel_bench, two runs): trio 0.368-0.374 -> 0.385-0.392 ms,
+  // quad 0.604-0.613 -> 0.640-0.655, 5 members 0.805-0.816 -> 0.827-0.829 (identical binaries differ by +-4 %
+  // between runs on these boxes).
+  if (env_int("FAMSEQ_LANE_LATE", 0) != 0) {  // tuning aid
+    const LdsRoom room = lds_room(plan, bt, 2, call_mode);
+    const int w3 = 3 * m.n_members, behind = room.fit - w3;
+    if (behind >= 3 * no) {  // (else not even the looped members' accumulators fit behind the row)
+      const int scratch_len = std::min(behind, (6 * no <= behind ? 6 : 3) * no + 3 * room.looped_tables);
+      f.late = true, f.row_len = (w3 + scratch_len) | 1;
+      const RowLayout layout = row_layout(plan, std::max(scratch_len, 1), false);
+      f.body = PrefixEmitter(plan, layout, true, false, prefetch).body();
+      return f;
     }
   }
-  const int hrow = once_row_len(m, h, bt);
+  // Transmission entries through scalar loads, and the innermost loop's loads one step ahead (see Emitter): the one-lane-per-site
+  // forms of pedigrees that have looped members; the lanes-per-site forms keep the per-lane LDS table.  Round 3, measured
+  // with tools/kernel_bench on one box (profiles/r03a/exp_scalar_tables.txt): ten members 10.40 -> 10.13-10.20 ms per 4 M sites,
+  // fifteen 139.2 -> 138.4 ms per 262 k; the innermost loop loses 36 of its 39 LDS reads and 10 of its 11 waits (885 -> 881
+  // instructions per 729 configurations) — the waits were a small part of what one wave per SIMD loses: at 1.21 instructions
+  // per configuration in that loop and 1.33 overall the kernel runs at the issue rate a single wave sustains (DESIGN.md 2.1).
+  f.scalar_t = env_int("FAMSEQ_LANE_ST", 1) != 0 && no > 0;  // (the variable: a tuning aid)
+  may_once = may_once && f.scalar_t && env_int("FAMSEQ_LANE_HOIST", 1) != 0;
+  if (need_body || may_once) {
+    const RowLayout layout = row_layout(plan, f.row_len, false);
+    f.body = PrefixEmitter(plan, layout, false, f.scalar_t, prefetch).body();
+  }
+  if (!may_once) return f;
+  f.fp64_parent = fp64_statements(f.body);
+  Shape h = s;
+  if (const int join = plan.joinable_member(); join >= 0) {  // part 1: the innermost looped member becomes the block's outermost prefix level
+    h.outer.clear();
+    for (int p : plan.outer)
+      if (p != join) h.outer.push_back(p);
+    h.unrolled.insert(h.unrolled.begin(), join);
+    for (size_t k = 0; k < h.unrolled.size(); ++k) h.upos[h.unrolled[k]] = (int)k;
+  }
+  const BlockPlan hplan(m, h);
+  const int hrow = hplan.once_applies() ? once_row_len(hplan, bt) : 0;
   if (hrow == 0) return f;
-  Gen gen(m, h, hrow, 0, false, scalar_t, prefetch, /*once=*/true);
-  if (!gen.once_feasible()) return f;
-  std::string body = gen.body();
+  const RowLayout hlayout = row_layout(hplan, hrow, true);
+  if (!hlayout.fits) return f;
+  std::string body = OnceEmitter(hplan, hlayout, f.scalar_t, prefetch).body();
   f.fp64_once = fp64_statements(body);
   if (f.fp64_once >= f.fp64_parent) return f;
   f.once = true, f.shape = h, f.row_len = hrow, f.body = std::move(body);
   return f;
 }
 
-int lane_row_len(const Model &m, const Shape &s, int bt, bool call_mode);
+Shape variant_shape(const Model &m, const LaneVariant &v) { return choose_shape(m, env_int("FAMSEQ_LANE_CAP", v.cap)); }  // (the variable: a tuning aid)
 
 }  // namespace
 
+LaneVariant enumgen_variant(int variant, int group_digits) {
+  LaneVariant v;
+  v.once = variant >= 4 && group_digits == 0;
+  v.plain = variant < 0 ? variant : variant & 3;
+  v.cap = group_digits == 0 && (v.plain == 0 || v.plain == 1) ? 7 : 6;
+  v.fence_single = v.plain > 0 && (v.plain & 1);
+  return v;
+}
+
 std::string enumgen_describe(const Model &m, int variant) {
-  const bool want_once = variant >= 4;  // kEnumVariants: 4-7 are 0-3 in the once-per-site form
-  if (variant >= 4) variant -= 4;
-  int cap = (variant >= 0 && variant < 2) ? 7 : 6;  // kEnumVariants; unknown yet (-1): the 6-member form
-  cap = env_int("FAMSEQ_LANE_CAP", cap);
-  Shape s = choose_shape(m, cap);
-  std::string form;
-  if (want_once && !s.unrolled.empty() && !s.outer.empty() && env_int("FAMSEQ_LANE_LATE", 0) == 0 && env_int("FAMSEQ_LANE_ST", 1) != 0) {
-    const int bt = enumgen_block_threads(m, 0);
-    const LaneForm f = lane_form(m, s, lane_row_len(m, s, bt, false), bt, true, env_int("FAMSEQ_LANE_PRE", 2), true);
-    if (f.once) {
-      s = f.shape;
-      char buf[160];
-      std::snprintf(buf, sizeof buf, ", prefix tables and marginals once per site (%.0f fp64 statements per site against %.0f)", f.fp64_once,
-                    f.fp64_parent);
-      form = buf;
-    }
-  }
+  const LaneVariant v = enumgen_variant(variant);
+  const LaneForm f = lane_form(m, variant_shape(m, v), false, v.once, /*need_body=*/false);
   std::string d = "looped members [";
-  for (size_t k = 0; k < s.outer.size(); ++k) d += (k ? " " : "") + num(s.outer[k]);
+  for (size_t k = 0; k < f.shape.outer.size(); ++k) d += (k ? " " : "") + num(f.shape.outer[k]);
   d += "], unrolled block [";
-  for (size_t k = 0; k < s.unrolled.size(); ++k) d += (k ? " " : "") + num(s.unrolled[k]);
-  int n = 1;
-  for (size_t k = 0; k < s.unrolled.size(); ++k) n *= 3;
-  return d + "] = " + num(n) + " configurations per step" + form;
+  for (size_t k = 0; k < f.shape.unrolled.size(); ++k) d += (k ? " " : "") + num(f.shape.unrolled[k]);
+  d += "] = " + num(pow3((int)f.shape.unrolled.size())) + " configurations per step";
+  if (f.once) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, ", prefix tables and marginals once per site (%.0f fp64 statements per site against %.0f)", f.fp64_once,
+                  f.fp64_parent);
+    d += buf;
+  }
+  return d;
 }
 
 // One lane per site: workgroups of ONE wave, and no register cap (`__launch_bounds__(64, 1)`).  A wave that
@@ -1232,34 +1148,12 @@ bool enumgen_reads_global_rows(const Model &m, int variant) {
 }
 
 int enumgen_max_group_digits(const Model &m) {
-  int cap = 6;
-  cap = env_int("FAMSEQ_LANE_CAP", cap);
-  return std::min<int>(kEnumMaxGroupDigits, (int)choose_shape(m, cap).outer.size());
+  return std::min<int>(kEnumMaxGroupDigits, (int)variant_shape(m, enumgen_variant(0, 1)).outer.size());
 }
 
-int enumgen_sites_per_chunk(const Model &m, int group_digits) {
-  int g = 1;
-  for (int k = 0; k < group_digits; ++k) g *= 3;
-  return enumgen_block_threads(m, group_digits) / g;
-}
+int enumgen_sites_per_chunk(const Model &m, int group_digits) { return enumgen_block_threads(m, group_digits) / pow3(group_digits); }
 
 namespace {
-
-// The lane's LDS row: 3N doubles padded to an odd count, plus — while two workgroups per CU still
-// fit in the 160 KB — room for the likelihoods of unrolled members whose tables are rebuilt inside
-// the loops (otherwise re-read from global memory there: L2 misses that show up as HBM traffic).
-int lane_row_len(const Model &m, const Shape &s, int bt, bool call_mode) {
-  int row_len = (3 * m.n_members) | 1;
-  int looped_tables = 0;  // unrolled members with a looped parent
-  for (int p : s.unrolled)
-    if (m.mother[p] >= 0 && (s.upos[m.mother[p]] < 0 || s.upos[m.father[p]] < 0)) ++looped_tables;
-  const int used = 6 * (int)s.outer.size() <= row_len ? 6 * (int)s.outer.size() : 3 * (int)s.outer.size();
-  const int want = (used + 3 * looped_tables) | 1;
-  // odd, two workgroups per CU (the call-path form also keeps a byte per member and lane, and two small tables)
-  const int fit = ((160 * 1024 / 2 - 432 * 8 - (call_mode ? bt * m.n_members + 256 + 2064 : 0)) / (bt * 8) - 1) | 1;
-  if (want > row_len) row_len = std::min(want, std::max(row_len, fit));
-  return row_len;
-}
 
 // Shell of the lanes-per-site mode (small batches): G = 3^d consecutive lanes share a site, each
 // walks the digits (fx0, fx1, ...) of the d outermost looped members given by its position in the
@@ -1335,96 +1229,50 @@ std::string grouped_shell(const Model &m, const std::string &comment, const std:
 }  // namespace
 
 bool enumgen_has_once_form(const Model &m) {
-  for (int v : {0, 2})
-    if (enumgen_source(m, v) != enumgen_source(m, v + 4)) return true;
+  for (int v : {4, 6})  // the 7-member cap and the 6-member cap
+    if (lane_form(m, variant_shape(m, enumgen_variant(v)), false, true, /*need_body=*/false).once) return true;
   return false;
 }
 
 std::string enumgen_source(const Model &m, int variant_asked, int group_digits, bool call_mode, bool call_ct_out) {
   // variants 4-7: variants 0-3 with the block's prefix levels in the once-per-site form, where the cost model takes it (lane_form);
   // where it does not — and in the lanes-per-site forms — they are the text of 0-3
-  const bool want_once = variant_asked >= 4 && group_digits == 0;
-  const int variant = variant_asked & 3;
-  int cap = (group_digits == 0 && variant < 2) ? 7 : 6;  // see kEnumVariants
-  cap = env_int("FAMSEQ_LANE_CAP", cap);  // tuning aid
-  const Shape s = choose_shape(m, cap);
+  const LaneVariant v = enumgen_variant(variant_asked, group_digits);
+  const Shape s = variant_shape(m, v);
   if (s.unrolled.empty()) throw std::runtime_error("enumeration codegen: empty unrolled set");
   if (group_digits < 0 || group_digits > std::min<int>(kEnumMaxGroupDigits, (int)s.outer.size()))
     throw std::runtime_error("enumeration codegen: more group digits than looped members");
-  const int bt = enumgen_block_threads(m, group_digits);
-  int row_len = lane_row_len(m, s, bt, call_mode);
-  // An experiment that is OFF (FAMSEQ_LANE_LATE=1 turns it on): the sum-product kernel's order of phases for
-  // the enumeration too — the whole computation first (marginals to registers), the next chunk requested,
-  // then the two outputs — instead of single posterior / store / enumeration / store: one barrier fewer and
-  // the prefetch in flight through both output phases; the row keeps the likelihoods until the end, scratch
-  // slots follow them.  Measured slower (8 M sites, tools/kernel_bench, two runs): trio 0.368-0.374 -> 0.385-0.392 ms,
-  // quad 0.604-0.613 -> 0.640-0.655, 5 members 0.805-0.816 -> 0.827-0.829 (identical binaries differ by +-4 %
-  // between runs on these boxes).
-  bool late = env_int("FAMSEQ_LANE_LATE", 0) != 0 && group_digits == 0;  // tuning aid
-  int scratch_len = 0;
-  if (late) {
-    int looped_tables = 0;
-    for (int p : s.unrolled)
-      if (m.mother[p] >= 0 && (s.upos[m.mother[p]] < 0 || s.upos[m.father[p]] < 0)) ++looped_tables;
-    const int fit = ((160 * 1024 / 2 - 432 * 8 - (call_mode ? bt * m.n_members + 256 + 2064 : 0)) / (bt * 8) - 1) | 1;
-    const int w3 = 3 * m.n_members, room = fit - w3;
-    if (room < 3 * (int)s.outer.size()) late = false;  // not even the looped members' accumulators fit behind the row
-    else {
-      const int used = 6 * (int)s.outer.size() <= room ? 6 * (int)s.outer.size() : 3 * (int)s.outer.size();
-      scratch_len = std::min(room, used + 3 * looped_tables);
-      row_len = (w3 + scratch_len) | 1;
-    }
-  }
-  int group = 1;
-  for (int k = 0; k < group_digits; ++k) group *= 3;
-  std::string what = "3^N enumeration, lane per site, " + std::to_string(s.outer.size()) + " looped + " +
-                     std::to_string(s.unrolled.size()) + " unrolled members, variant " + std::to_string(variant);
-  if (group > 1)
-    what = "3^N enumeration, " + std::to_string(group) + " lanes per site (" + std::to_string(group_digits) + " of " +
-           std::to_string(s.outer.size()) + " looped members' digits on lanes), " + std::to_string(s.unrolled.size()) +
-           " unrolled members, variant " + std::to_string(variant);
+  const int bt = enumgen_block_threads(m, group_digits), group = pow3(group_digits);
   // (the call-path form of a small pedigree's kernel: two waves per SIMD at least — with 512 registers to fill, its output stages'
   // batched loads took the five-member kernel from two waves to one, 0.156 -> 0.203 ms per 1 M sites; bounded, the variant
   // contest sees the spill and takes the leaner stage-out)
   const int min_waves = env_int("FAMSEQ_LANE_MINWAVES", group_digits == 0 ? (call_mode && m.n_members <= 6 ? 2 : 1) : bt / 128);  // tuning aid
-  // Transmission entries through scalar loads, and the innermost loop's loads one step ahead (see Gen): the one-lane-per-site
-  // forms of pedigrees that have looped members; the lanes-per-site forms keep the per-lane LDS table.  Round 3, measured
-  // with tools/kernel_bench on one box (profiles/r03a/exp_scalar_tables.txt): ten members 10.40 -> 10.13-10.20 ms per 4 M sites,
-  // fifteen 139.2 -> 138.4 ms per 262 k; the innermost loop loses 36 of its 39 LDS reads and 10 of its 11 waits (885 -> 881
-  // instructions per 729 configurations) — the waits were a small part of what one wave per SIMD loses: at 1.21 instructions
-  // per configuration in that loop and 1.33 overall the kernel runs at the issue rate a single wave sustains (DESIGN.md 2.1).
-  const bool scalar_t = env_int("FAMSEQ_LANE_ST", 1) != 0 && group_digits == 0 && !late && !s.outer.empty();  // (the variable: a tuning aid)
-  const int prefetch = env_int("FAMSEQ_LANE_PRE", 2);  // tuning aid: 0 none, 1 table entries, 2 and LDS reads (both forms: see Gen)
-  if (call_mode) what += ", call path";
-  // variant 0: the members of the single posterior overlap, 1: fenced one from the other (fewer registers)
-  const bool fence_single = variant & 1;
   if (group > 1) {
     if (call_mode) throw std::runtime_error("enumeration codegen: the lanes-per-site form has no call path");
-    Gen gen(m, s, row_len, group_digits, late, scalar_t, prefetch);
-    const std::string body = gen.body();
-    return grouped_shell(m, what, body, gen.reduce_body(), bt, min_waves, fence_single, row_len, group);
+    const std::string what = "3^N enumeration, " + std::to_string(group) + " lanes per site (" + std::to_string(group_digits) + " of " +
+                             std::to_string(s.outer.size()) + " looped members' digits on lanes), " + std::to_string(s.unrolled.size()) +
+                             " unrolled members, variant " + std::to_string(v.plain);
+    const BlockPlan plan(m, s, group_digits);
+    const int row_len = lane_row_len(plan, bt, false);
+    const RowLayout layout = row_layout(plan, row_len, false);
+    const std::string body = PrefixEmitter(plan, layout, false, false, 0).body();
+    return grouped_shell(m, what, body, reduce_body(), bt, min_waves, v.fence_single, row_len, group);
   }
+  LaneForm f = lane_form(m, s, call_mode, v.once && !call_mode);
   ShellOptions o;
   o.entry = "famseq_enum_lane";
-  o.comment = late ? what + ", compute-first shell" : what;
-  if (late) {
-    Gen gen(m, s, std::max(scratch_len, 1), group_digits, late, scalar_t, prefetch);
-    o.body = gen.body();
-  } else {
-    LaneForm f = lane_form(m, s, row_len, bt, scalar_t, prefetch, want_once && !call_mode);
-    if (f.once) {
-      o.comment = "3^N enumeration, lane per site, " + std::to_string(f.shape.outer.size()) + " looped + " +
-                  std::to_string(f.shape.unrolled.size()) + " unrolled members, variant " + std::to_string(variant_asked) +
-                  ", prefix tables and marginals once per site";
-      if (f.shape.unrolled.size() > s.unrolled.size())
-        o.comment += " (looped member " + std::to_string(f.shape.unrolled[0]) + " unrolled ahead of the block)";
-    }
-    o.body = std::move(f.body), row_len = f.row_len;
-  }
-  o.bt = bt, o.min_waves = min_waves, o.row_doubles = row_len;
+  o.comment = "3^N enumeration, lane per site, " + std::to_string(f.shape.outer.size()) + " looped + " + std::to_string(f.shape.unrolled.size()) +
+              " unrolled members, variant " + std::to_string(f.once ? variant_asked : v.plain);
+  if (f.once) o.comment += ", prefix tables and marginals once per site";
+  if (f.shape.unrolled.size() > s.unrolled.size()) o.comment += " (looped member " + std::to_string(f.shape.unrolled[0]) + " unrolled ahead of the block)";
+  if (call_mode) o.comment += ", call path";
+  if (f.late) o.comment += ", compute-first shell";
+  o.body = std::move(f.body);
+  o.bt = bt, o.min_waves = min_waves, o.row_doubles = f.row_len;
   // registers-first (LDS-resident likelihoods measured 17 % slower) unless the late experiment asks for the shell's compute-first flow
-  o.regs_l = !late, o.lane_body = late;
-  o.fence_single = fence_single, o.chrx_loop = !late && scalar_t, o.call_mode = call_mode, o.call_ct_out = call_ct_out;
+  o.regs_l = !f.late, o.lane_body = f.late;
+  // variant 0: the members of the single posterior overlap, 1: fenced one from the other (fewer registers)
+  o.fence_single = v.fence_single, o.chrx_loop = f.scalar_t, o.call_mode = call_mode, o.call_ct_out = call_ct_out;
   return kernel_shell(m, o);
 }
 

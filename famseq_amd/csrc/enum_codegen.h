@@ -19,6 +19,15 @@ namespace famseq {
 // for the pedigrees on which the generator's cost model takes that form; for every other pedigree they are the text of 0-3.
 // Where the form exists the contest starts at 4 (enumgen_first_variant).
 constexpr int kEnumVariants = 8;
+// What a variant index means (the one decoder): the block's member cap, whether the single posterior is fenced, whether the
+// once-per-site form is asked for, and the index without that request (0-3; -1, no variant chosen yet: the 6-member form).
+struct LaneVariant {
+  int plain, cap;
+  bool fence_single, once;
+};
+LaneVariant enumgen_variant(int variant, int group_digits = 0);
+// The call-path kernel has variants 0-3 only (it keeps the per-prefix text): the one with plain variant `lane`'s block shape.
+inline int enumgen_call_variant(int lane, bool fence_single) { return (enumgen_variant(lane < 0 ? 0 : lane).plain & 2) + (fence_single ? 1 : 0); }
 // group_digits = d > 0: lanes-per-site mode for small batches — 3^d consecutive lanes share a site, each
 // taking one combination of the d outermost looped members' digits (d <= enumgen_max_group_digits)
 constexpr int kEnumMaxGroupDigits = 4;

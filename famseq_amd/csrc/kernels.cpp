@@ -102,9 +102,9 @@ KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
       // the same block size as the plain lane kernel runs with (variants 0-1 / 2-3: kEnumVariants), so that a batch
       // gives the same bits whether it goes through the fused kernel or through the separate stages
       // (variants 4-7 are 0-3 in the once-per-site form: the call path keeps the per-prefix text of the same block shape)
-      const int base = std::max(c->kern[K_LANE].variant, 0) & 2;
+      const int lane = c->kern[K_LANE].variant;
       // v & 1: the single posterior fenced member by member; v & 2: the leaner stage-out (see kElimCallVariants)
-      return {[&m, base](int v) { return enumgen_source(m, base + (v & 1), 0, true, !(v & 2)); }, 4, 0, false, "famseq_enum_lane",
+      return {[&m, lane](int v) { return enumgen_source(m, enumgen_call_variant(lane, v & 1), 0, true, !(v & 2)); }, 4, 0, false, "famseq_enum_lane",
               enumgen_block_threads(m)};
     }
     case K_ELIM:
@@ -185,7 +185,7 @@ bool load_or_remember(famseq_ctx *c, int kind) {
   } else {
     const int rc = load_kernel(c, kind, &why);
     if (kind == K_LANE_CALL && g.variant >= 0)  // (the answer depends on the variant taken)
-      c->lane_reads_rows = enumgen_reads_global_rows(c->model, (std::max(c->kern[K_LANE].variant, 0) & ~1) + (g.variant & 1)) ? 1 : 0;
+      c->lane_reads_rows = enumgen_reads_global_rows(c->model, enumgen_call_variant(c->kern[K_LANE].variant, g.variant & 1)) ? 1 : 0;
     if (rc == 0) return true;
   }
   g.failed = true;

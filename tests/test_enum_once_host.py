@@ -177,3 +177,38 @@ def test_the_plan_names_the_form(tmp_path, monkeypatch):
         ctx.close()
     assert ONCE not in shapes["ped5"]
     assert shapes["ped10"].startswith("looped members [5 0 1], unrolled block [4 2 6 7 3 8 9] = 2187 configurations per step, " + ONCE)
+
+
+def test_the_plan_names_the_form_where_the_manifest_has_a_second_text(tmp_path, monkeypatch):
+    """A context that is free to choose starts its variant contest at the once-per-site variants, and its plan says so, exactly
+    for the pedigrees whose lane/4 differs from lane/0 in the manifest of generated sources (the generator answers the question
+    from its decision function, the manifest from the texts)."""
+    import json
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import source_digests as D
+
+    with open(os.path.join(root, "tests", "golden", "generated_sources.json")) as f:
+        golden = json.load(f)
+    for k, v in dict(FAMSEQ_KERNEL_CACHE=str(tmp_path), FAMSEQ_JIT_SOURCE_ONLY="1", FAMSEQ_QUIET="1").items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.delenv("FAMSEQ_VARIANT_ONLY", raising=False)
+    second_text, named = set(), set()
+    for name in D.PEDIGREES:
+        ped = D._named(name)
+        if ped.n > fs.MAXN:
+            continue
+        ped.relations()
+        if golden["%s lane/4" % name] != golden["%s lane/0" % name]:
+            second_text.add(name)
+        ctx = fs.Context(fs.make_model(ped), device=-1)
+        ctx.set_option("enum_impl", 1)
+        plan = ctx.plan()
+        ctx.close()
+        assert (plan["enum_lane_first_variant"] == 4) == (ONCE in plan["enum_lane_shape"]), name
+        if ONCE in plan["enum_lane_shape"]:
+            named.add(name)
+    assert second_text == named
+    assert {"ped10", "random99"} <= named

@@ -48,9 +48,12 @@ def _named(name):
 
 # trio .. ped15:12, cousins (one conditioned member) and random15 (three): the variant matrices' pedigrees (tests/_variants.py);
 # random0 / random3: the MAP host tests'; random99: two conditioned members; wide24 / 48 / 64: the staged form, the lean forms
-# (from forty members) and the LDS-row members (from fifty-six); lone: a component without a family
+# (from forty members) and the LDS-row members (from fifty-six); lone: a component without a family.
+# The lane kernel's once-per-site form (lane/4..7 differ from lane/0..3) is taken by ped10 (a looped member unrolled ahead of
+# the block, one prefix digit in the tables rebuilt per step), random99 (two such digits) and random34 (every prefix table
+# constant: none); for every other pedigree lane/4..7 are recorded as the text of lane/0..3.
 PEDIGREES = ("trio", "quad", "ped5", "ped10", "ped15:12", "cousins", "random15", "random0", "random3", "random%d" % TWO_CUT_SEED,
-             "wide24", "wide48", "wide64", "lone")
+             "wide24", "wide48", "wide64", "lone", "random34")
 
 # One case per tuning switch at a value that is not its default, in a kernel family that reads it: (switch, value, pedigree,
 # cases).  ped10, and wide48 for the form without LDS staging.  A case is "<family>/<variant>" as _one_variant names it.
@@ -80,6 +83,12 @@ SWITCHES = (
     ("FAMSEQ_LANE_MINWAVES", "2", "ped10", ("lane/1",)),
     ("FAMSEQ_LANE_ST", "0", "ped10", ("lane/1",)),
     ("FAMSEQ_LANE_PRE", "0", "ped10", ("lane/1",)),
+    # ... and what the once-per-site form (lane/4..7) reads
+    ("FAMSEQ_LANE_HOIST", "0", "ped10", ("lane/5",)),
+    ("FAMSEQ_LANE_PRE", "0", "ped10", ("lane/5",)),
+    ("FAMSEQ_LANE_PRE", "1", "ped10", ("lane/1", "lane/5")),
+    ("FAMSEQ_LANE_CAP", "5", "ped10", ("lane/5",)),
+    ("FAMSEQ_LANE_TABLE_BUDGET", "40", "ped10", ("lane/1",)),
 )
 
 
@@ -105,15 +114,18 @@ def _one_variant(ped, v, env):
     try:
         with mock.patch.dict(os.environ, dict(base, **env)):
             model = fs.make_model(ped)
-            if ped.n <= fs.MAXN and v < 4:  # the enumeration's lane kernel, its lanes-per-site forms and its call form
+            if ped.n <= fs.MAXN and v < 8:  # the enumeration's lane kernel, its lanes-per-site forms and its call form
                 ctx = fs.Context(model, device=-1)
                 ctx.set_option("enum_impl", 1)
                 out["lane/%d" % v] = _digest(ctx.plan(), "enum_lane_code_object")
-                for d in range(1, ctx.plan()["enum_group_digits_max"] + 1):
+                # (variants 4-7, the once-per-site form: the plain kernel only — their lanes-per-site forms are the text of
+                # 0-3 and the call path has variants 0-3)
+                for d in range(1, ctx.plan()["enum_group_digits_max"] + 1 if v < 4 else 0):
                     ctx.set_option("group_digits", d)
                     out["lane_group%d/%d" % (d, v)] = _digest(ctx.plan(), "enum_group_code_objects", d - 1)
-                ctx.set_option("call_kernels", 2)
-                out["lane_call/%d" % v] = _digest(ctx.plan(), "enum_lane_call_code_object")
+                if v < 4:
+                    ctx.set_option("call_kernels", 2)
+                    out["lane_call/%d" % v] = _digest(ctx.plan(), "enum_lane_call_code_object")
                 ctx.close()
             ctx = fs.Context(model, device=-1)
             ctx.set_option("engine", fs.ENGINE_ELIM)
