@@ -86,6 +86,7 @@ ABI_SYMBOLS = [
     "famseq_trio_prior_batch", "famseq_trio_prior_batch_device", "famseq_map_prior_batch", "famseq_map_prior_batch_device",
     "famseq_evidence_batch", "famseq_evidence_batch_device", "famseq_evidence_prior_batch", "famseq_evidence_prior_batch_device",
     "famseq_loo_batch", "famseq_loo_batch_device", "famseq_loo_prior_batch", "famseq_loo_prior_batch_device",
+    "famseq_pattern_batch", "famseq_pattern_batch_device", "famseq_pattern_prior_batch", "famseq_pattern_prior_batch_device",
 ]
 PL_MISSING = 0xFFFF
 
@@ -170,12 +171,15 @@ def lib():
     L.famseq_hwe_priors.restype = None
     # the side products' entries: famseq_<name>[_prior]_batch[_device]
     u16p = C.POINTER(C.c_uint16)
-    for name, out_a in (("trio", dp), ("map", C.POINTER(C.c_int8)), ("evidence", dp), ("loo", dp)):
+    # (more: what an entry takes between the prior rows and its outputs, as the host and the device entry declare it)
+    masks = ([bp, C.c_int32], [vp, C.c_int32])
+    for name, out_a, more in (("trio", dp, ([], [])), ("map", C.POINTER(C.c_int8), ([], [])), ("evidence", dp, ([], [])), ("loo", dp, ([], [])),
+                              ("pattern", dp, masks)):
         for prior in (0, 1):
             host = getattr(L, "famseq_%s%s_batch" % (name, "_prior" * prior))
             dev = getattr(L, "famseq_%s%s_batch_device" % (name, "_prior" * prior))
-            host.argtypes = [C.c_void_p, C.c_int64, dp, u16p, ip, C.c_int32, bp] + [dp] * prior + [out_a, dp, bp]
-            dev.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp] + [vp] * prior + [vp, vp, vp, vp]
+            host.argtypes = [C.c_void_p, C.c_int64, dp, u16p, ip, C.c_int32, bp] + [dp] * prior + more[0] + [out_a, dp, bp]
+            dev.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp] + [vp] * prior + more[1] + [vp, vp, vp, vp]
             host.restype = dev.restype = C.c_int
     _lib = L
     return L
@@ -244,6 +248,26 @@ def hwe_priors(af):
     prior = np.empty((len(af), 6))
     lib().famseq_hwe_priors(len(af), _p(af, C.c_double), _p(prior, C.c_double))
     return prior
+
+
+SEGREGATION_MASKS = {"dominant": (6, 1), "recessive": (4, 3)}  # model -> (affected, unaffected); anyone else 7
+
+
+def segregation_masks(n, affected, unaffected=(), model="dominant"):
+    """The mask row [n] uint8 of a segregation pattern for Context.pattern_batch; affected / unaffected: member indices (PED
+    order).  dominant: the affected carry the variant (genotypes 1, 2: mask 6), the unaffected are hom-ref (1).  recessive: the
+    affected are hom-alt (4), the unaffected are not (3).  A member in neither list is unconstrained (7)."""
+    if model not in SEGREGATION_MASKS:
+        raise ValueError("model must be 'dominant' or 'recessive', got %r" % (model,))
+    aff, unaff = [int(i) for i in affected], [int(i) for i in unaffected]
+    for i in aff + unaff:
+        if not 0 <= i < n:
+            raise ValueError("member index %d is outside 0..%d" % (i, n - 1))
+    if set(aff) & set(unaff):
+        raise ValueError("members %s are listed as affected and as unaffected" % sorted(set(aff) & set(unaff)))
+    row = np.full(n, 7, np.uint8)
+    row[aff], row[unaff] = SEGREGATION_MASKS[model]
+    return row
 
 
 def make_model(ped: Pedigree, mrate=1e-7, lc=1.0, genoProbN=None, genoProbK=None, genoProbXN=None,
@@ -410,26 +434,27 @@ class Context:
             lib().famseq_trio_children(self._h, _p(idx, C.c_int32))
         return idx
 
-    def _side_host(self, name, prior, lk, pl16, seq_members, flags, outs):
+    def _side_host(self, name, prior, lk, pl16, seq_members, flags, outs, more=()):
         """The host entry of a side product, famseq_<name>_batch or (prior given) famseq_<name>_prior_batch.  outs(S) makes its two
-        output arrays (None: not wanted).  -> (out_a, out_b, status)."""
+        output arrays (None: not wanted); more: the arguments the entry takes between the prior rows and its outputs.
+        -> (out_a, out_b, status)."""
         lk, pl16, s, seq, n_seq, fl = _inputs(self.n, lk, pl16, seq_members, flags, False)
         out_a, out_b = outs(s)
         status = np.zeros(s, np.uint8)
         fn = "famseq_%s%s_batch" % (name, "" if prior is None else "_prior")
         rows = () if prior is None else (_p(_prior_rows(prior, s), C.c_double),)
-        self._check(getattr(lib(), fn)(self._h, s, _opt(lk), _opt(pl16), _opt(seq), n_seq, _opt(fl), *rows, _opt(out_a), _opt(out_b),
+        self._check(getattr(lib(), fn)(self._h, s, _opt(lk), _opt(pl16), _opt(seq), n_seq, _opt(fl), *rows, *more, _opt(out_a), _opt(out_b),
                                        _opt(status)), fn)
         return out_a, out_b, status
 
-    def _side_device(self, name, n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior, d_a, d_b, d_status, stream):
+    def _side_device(self, name, n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior, d_a, d_b, d_status, stream, more=()):
         """The device entry of a side product on raw device pointers, famseq_<name>_batch_device or (d_prior not None: an int, 0
-        = not given) famseq_<name>_prior_batch_device."""
+        = not given) famseq_<name>_prior_batch_device.  more: as _side_host's."""
         seq = np.ascontiguousarray(seq_members, dtype=np.int32)
         fn = "famseq_%s%s_batch_device" % (name, "" if d_prior is None else "_prior")
         rows = () if d_prior is None else (d_prior or None,)
         self._check(getattr(lib(), fn)(self._h, int(n_sites), d_lk or None, d_pl16 or None, _p(seq, C.c_int32) if len(seq) else None, len(seq),
-                                       d_flags or None, *rows, d_a or None, d_b or None, d_status or None, stream or None), fn)
+                                       d_flags or None, *rows, *more, d_a or None, d_b or None, d_status or None, stream or None), fn)
 
     def trio_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_joint=True, want_dnm=True):
         """Trio posteriors: -> (children[K], joint[S,K,27] or None, dnm[S,K] or None, status[S]).
@@ -526,6 +551,46 @@ class Context:
         """Leave-one-out posteriors and fit on resident buffers (raw device pointers as ints; 0 = not given); enqueues on
         `stream` and returns."""
         self._side_device("loo", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_loo, d_fit, d_status, stream)
+
+    @staticmethod
+    def _masks(masks, n):
+        """masks [M, N] (or one row [N]) as a contiguous uint8 array."""
+        m = np.ascontiguousarray(masks, dtype=np.uint8)
+        if m.ndim == 1:
+            m = m[None, :]
+        if m.ndim != 2 or m.shape[1] != n:
+            raise ValueError("masks must have shape [n_patterns, %d]" % n)
+        return m
+
+    def pattern_batch(self, masks, lk=None, pl16=None, seq_members=None, flags=None, want_post=True, want_loglik=True):
+        """Genotype-pattern posteriors: -> (pat_post[S,M] float64, loglik[S] float64, status[S] uint8).
+        masks [M, N] uint8 (PED order): bit g of masks[m, i] set = pattern m allows member i genotype g (7: unconstrained).
+        pat_post[s, m] = P(every member's genotype is allowed by pattern m | data) in the full network; loglik is
+        evidence_batch's.  segregation_masks() makes the dominant and recessive rows.  Input is either lk [S,N,3] float64 or
+        pl16 [S,n_seq,3] uint16 in VCF column order (seq_members: their PED indices).  want_* False: not computed, None."""
+        m = self._masks(masks, self.n)
+        outs = lambda s: (np.empty((s, m.shape[0])) if want_post else None, np.empty(s) if want_loglik else None)
+        return self._side_host("pattern", None, lk, pl16, seq_members, flags, outs, (_p(m, C.c_uint8), m.shape[0]))
+
+    def pattern_prior_batch(self, prior, masks, lk=None, pl16=None, seq_members=None, flags=None, want_post=True, want_loglik=True):
+        """pattern_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give pattern_batch's bits."""
+        m = self._masks(masks, self.n)
+        outs = lambda s: (np.empty((s, m.shape[0])) if want_post else None, np.empty(s) if want_loglik else None)
+        return self._side_host("pattern", prior, lk, pl16, seq_members, flags, outs, (_p(m, C.c_uint8), m.shape[0]))
+
+    def pattern_batch_device(self, n_sites, d_masks, n_patterns, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_pat_post=0, d_loglik=0,
+                             d_status=0, stream=0):
+        """pattern_batch on resident buffers (raw device pointers as ints; 0 = not given), d_masks [n_patterns, N] uint8 among
+        them; enqueues on `stream` and returns."""
+        self._side_device("pattern", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_pat_post, d_loglik, d_status, stream,
+                          (d_masks or None, int(n_patterns)))
+
+    def pattern_prior_batch_device(self, n_sites, d_prior, d_masks, n_patterns, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_pat_post=0,
+                                   d_loglik=0, d_status=0, stream=0):
+        """pattern_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("pattern", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_pat_post, d_loglik, d_status, stream,
+                          (d_masks or None, int(n_patterns)))
 
     def loo_prior_batch_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_loo=0, d_fit=0, d_status=0, stream=0):
         """loo_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""

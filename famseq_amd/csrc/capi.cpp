@@ -496,7 +496,7 @@ extern "C" int famseq_bn_prior_batch_device(famseq_ctx *c, int64_t n_sites, cons
   HIP_TRY(c, hipSetDevice(c->device));
   const int rc = load_or_fail(c, K_PRIOR);
   if (rc != 0 || n_sites == 0) return rc;
-  HIP_TRY(c, launch_generated(c, c->kern[K_PRIOR], n_sites, d_lk, d_flags, d_post, d_single, d_status, static_cast<hipStream_t>(stream), 0, d_prior));
+  HIP_TRY(c, launch_generated(c, c->kern[K_PRIOR], n_sites, d_lk, d_flags, d_post, d_single, d_status, static_cast<hipStream_t>(stream), 0, {&d_prior}));
   return 0;
 }
 
@@ -733,7 +733,7 @@ int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl
   return 0;
 }
 
-// What the sixteen entries below share.  On the device path (`device`) the arrays are the caller's resident buffers and the
+// What the twenty entries below share.  On the device path (`device`) the arrays are the caller's resident buffers and the
 // kernel is enqueued on `stream`; on the host path they are chunked and pipelined (side_batch) on the product's own buffers.
 // The order of the checks is what callers have come to rely on: a site-prior device entry asks for d_prior before anything
 // else, a site-prior host entry checks its input and its prior rows (prior_ready) first, then every entry trio_prologue.
@@ -745,9 +745,27 @@ struct SideIn {
   int32_t n_seq;
   const uint8_t *flags;
 };
+// What the pattern entries take beside: the masks [n_patterns][N] (host entry: the caller's host array; device entry: resident).
+struct PatternIn {
+  const uint8_t *masks;
+  int32_t n_patterns;
+};
+// Said before anything else, so that a context without a device says it too.
+int check_patterns(famseq_ctx *c, const PatternIn &pat, bool device) {
+  if (pat.n_patterns < 1 || pat.n_patterns > FAMSEQ_MAX_PATTERNS)
+    return fail(c, FAMSEQ_E_ARG, "n_patterns must be 1.." + std::to_string(FAMSEQ_MAX_PATTERNS) + ", got " + std::to_string(pat.n_patterns));
+  if (!pat.masks) return fail(c, FAMSEQ_E_ARG, "masks must be given (n_patterns rows of one byte per member)");
+  if (!device)
+    for (size_t i = 0, n = size_t(pat.n_patterns) * c->model.n_members; i < n; ++i)
+      if (pat.masks[i] > 7)
+        return fail(c, FAMSEQ_E_ARG, "masks: pattern " + std::to_string(i / c->model.n_members) + ", member " + std::to_string(i % c->model.n_members) +
+                                         " is " + std::to_string(pat.masks[i]) + "; a mask is 0..7 (bit g: genotype g allowed)");
+  return 0;
+}
 int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device, const SideIn &in, const double *prior, void *out_a,
-               void *out_b, uint8_t *status, void *stream_ = nullptr) {
+               void *out_b, uint8_t *status, void *stream_ = nullptr, const PatternIn *pat = nullptr) {
   if (!c) return FAMSEQ_E_ARG;
+  if (pat && check_patterns(c, *pat, device) != 0) return FAMSEQ_E_ARG;
   const SideProduct &p = side_table()[id];
   const int kind = p.kind_of(form, site_prior);
   const int64_t n_sites = in.n_sites;
@@ -759,10 +777,23 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
       return rc;
   }
   if ((rc = trio_prologue(c, n_sites, in.lk, in.pl16, in.seq_members, in.n_seq, kind)) != 0 || n_sites == 0) return rc;
+  // the arguments in front of the prior rows (the pattern kernels' masks and their number)
+  const uint8_t *d_masks = pat ? pat->masks : nullptr;
+  const int32_t n_patterns = pat ? pat->n_patterns : 1;
   if (!device) {
     size_t row[2];
-    p.rows(c->model, row);
-    return side_batch(c, c->side_slots[id], c->kern[kind], n_sites, in.lk, in.pl16, in.n_seq, in.flags, out_a, row[0], out_b, row[1], status, prior);
+    p.rows(c->model, n_patterns, row);
+    if (pat) {
+      // The masks go through a copy the context keeps into a buffer it owns, on the stream the chunks' kernels run on: ordered
+      // with them by the stream itself.  (A host entry returns with its streams drained, so neither is in use by an earlier call.)
+      const size_t bytes = size_t(n_patterns) * c->model.n_members;
+      if (!c->d_masks) HIP_TRY(c, c->d_masks.alloc(size_t(FAMSEQ_MAX_PATTERNS) * c->model.n_members));
+      c->masks_host.assign(pat->masks, pat->masks + bytes);
+      HIP_TRY(c, hipMemcpyAsync(c->d_masks.p, c->masks_host.data(), bytes, hipMemcpyHostToDevice, c->stream[1]));
+      d_masks = c->d_masks.as<uint8_t>();
+    }
+    return side_batch(c, c->side_slots[id], c->kern[kind], n_sites, in.lk, in.pl16, in.n_seq, in.flags, out_a, row[0], out_b, row[1], status, prior,
+                      pat ? MoreArgs{&d_masks, &n_patterns} : MoreArgs{});
   }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const double *d_lk = in.lk;
@@ -777,14 +808,16 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
     d_lk = c->trio_dev_lk.as<double>();
     HIP_TRY(c, launch_unpack_pl16(in.pl16, c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, in.n_seq, n_sites, c->trio_dev_lk.as<double>(), stream));
   }
-  HIP_TRY(c, launch_generated(c, c->kern[kind], n_sites, d_lk, in.flags, out_a, out_b, status, stream, 0, prior));
+  MoreArgs more = pat ? MoreArgs{&d_masks, &n_patterns} : MoreArgs{};
+  more.at[more.n++] = &prior;  // (behind the last parameter of a plain form: not read)
+  HIP_TRY(c, launch_generated(c, c->kern[kind], n_sites, d_lk, in.flags, out_a, out_b, status, stream, 0, more));
   return 0;
 }
 
 }  // namespace
 
 // ---- trio posteriors, the joint MAP configuration, the evidence (the site's log10 likelihood and the hom-ref posterior), the
-// ---- leave-one-out posteriors and fit, each
+// ---- leave-one-out posteriors and fit, the genotype-pattern posteriors, each
 // ---- plain and with the founders' prior per site, on host and on resident buffers: side_entry --------------------------------
 
 extern "C" int famseq_trio_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
@@ -883,4 +916,35 @@ extern "C" int famseq_loo_prior_batch_device(famseq_ctx *c, int64_t n_sites, con
                                              double *d_loo, double *d_fit, uint8_t *d_status, void *stream) {
   return side_entry(c, SIDE_LOO, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_loo, d_fit, d_status,
                     stream);
+}
+
+extern "C" int famseq_pattern_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                    int32_t n_seq, const uint8_t *flags, const uint8_t *masks, int32_t n_patterns, double *pat_post,
+                                    double *loglik, uint8_t *status) {
+  const PatternIn pat{masks, n_patterns};
+  return side_entry(c, SIDE_PATTERN, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, pat_post, loglik, status, nullptr, &pat);
+}
+
+extern "C" int famseq_pattern_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const uint8_t *d_masks,
+                                           int32_t n_patterns, double *d_pat_post, double *d_loglik, uint8_t *d_status, void *stream) {
+  const PatternIn pat{d_masks, n_patterns};
+  return side_entry(c, SIDE_PATTERN, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_pat_post, d_loglik, d_status,
+                    stream, &pat);
+}
+
+extern "C" int famseq_pattern_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
+                                          const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
+                                          const uint8_t *masks, int32_t n_patterns, double *pat_post, double *loglik, uint8_t *status) {
+  const PatternIn pat{masks, n_patterns};
+  return side_entry(c, SIDE_PATTERN, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, pat_post, loglik, status, nullptr, &pat);
+}
+
+extern "C" int famseq_pattern_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                                 const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                                 const uint8_t *d_masks, int32_t n_patterns, double *d_pat_post, double *d_loglik,
+                                                 uint8_t *d_status, void *stream) {
+  const PatternIn pat{d_masks, n_patterns};
+  return side_entry(c, SIDE_PATTERN, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_pat_post, d_loglik, d_status,
+                    stream, &pat);
 }

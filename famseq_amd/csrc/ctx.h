@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -54,7 +55,7 @@ struct DevBuf {
 };
 
 // A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp; the trio,
-// MAP, evidence and leave-one-out kinds are the rows of side_table() below.
+// MAP, evidence, leave-one-out and pattern kinds are the rows of side_table() below.
 enum KernelKind {
   K_LANE = 0,  // K_LANE + d: the enumeration with 3^d lanes per site; d = 0 (one lane per site) serves large batches,
                // d = 1..kEnumMaxGroupDigits batches too small to give every lane of the chip a site (compiled on first use of each d)
@@ -70,6 +71,8 @@ enum KernelKind {
   K_EVID_PRIOR,                                    // ... with the founders' prior per site
   K_LOO,                                           // leave-one-out posteriors and the per-member fit
   K_LOO_PRIOR,                                     // ... with the founders' prior per site
+  K_PATTERN,                                       // genotype-pattern posteriors: the sum pass once per pattern
+  K_PATTERN_PRIOR,                                 // ... with the founders' prior per site
   K_COUNT
 };
 
@@ -110,7 +113,7 @@ struct SlotSet {
 // A side product of the sum-product engine: a generated kernel that takes the common argument list and writes two outputs per
 // site and a status byte, in a plain form and in one that reads the founders' prior per site.  Everything its ABI entries, its
 // prebuild options, its plan keys and its loader differ in is one row of side_table() (kernels.cpp).
-enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
+enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
 struct SideProduct {
   const char *stem;   // "trio": the entry points famseq_trio[_prior], the options trio[_prior]_kernels, the plan keys trio[_prior]_*
   const char *what;   // load_or_fail's message starts "[site priors, ]<what> (sum-product engine): "
@@ -118,7 +121,8 @@ struct SideProduct {
   int kind, prior_kind, n_forms;  // output form f = 1 .. n_forms is kind + f - 1, its site-prior form prior_kind + f - 1
   int n_variants;
   std::string (*source)(const Model &, int variant, int form, bool site_prior);
-  void (*rows)(const Model &, size_t row[2]);  // bytes per site of the two outputs
+  // bytes per site of the two outputs; per_call: what the call itself says of them (the pattern entries' n_patterns; 1 elsewhere)
+  void (*rows)(const Model &, int per_call, size_t row[2]);
   int kind_of(int form, bool site_prior) const { return (site_prior ? prior_kind : kind) + form - 1; }
 };
 using SideTable = const SideProduct[SIDE_COUNT];
@@ -175,6 +179,9 @@ struct famseq_ctx {
   int64_t dev_tmp_sites = 0;
   int dev_tmp_seq = 0;
   famseq::DevBuf trio_dev_lk;  // the side products' device entries' likelihood rows for packed input
+  // the pattern host entries' masks: FAMSEQ_MAX_PATTERNS rows, staged per call from a copy the context keeps, on the compute stream
+  famseq::DevBuf d_masks;
+  std::vector<uint8_t> masks_host;
   int64_t trio_dev_sites = 0;
   std::string tune_report;  // what famseq_set_option "tune" measured (famseq_plan_json "tune")
   std::string err, json;
@@ -194,6 +201,19 @@ inline int fail(famseq_ctx *c, int code, const std::string &msg) {
       return famseq::fail((c), FAMSEQ_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));      \
   } while (0)
 
+// What a generated kernel takes behind the common eight arguments, in the order of its parameter list: the address of each
+// argument's value (hipModuleLaunchKernel's form).  The call-path forms take their CallIO, the site-prior kernels their prior
+// rows, the pattern kernels their masks and n_patterns in front of those; the plain forms nothing.
+struct MoreArgs {
+  static constexpr int kMax = 3;
+  void *at[kMax] = {};
+  int n = 0;
+  MoreArgs() = default;
+  MoreArgs(std::initializer_list<const void *> list) {
+    for (const void *a : list) at[n++] = const_cast<void *>(a);
+  }
+};
+
 // ---- kernels.cpp ----
 // The sum-product family (K_ELIM, K_PRIOR and every kind of side_table()): 0, or an error (FAMSEQ_E_ARG: the engine does not serve
 // this pedigree; FAMSEQ_E_HIP) that is not remembered, the next call tries again.
@@ -204,7 +224,7 @@ bool load_or_remember(famseq_ctx *c, int kind);
 void drop_lane_kernels(famseq_ctx *c);  // what a new pick of the lane variant makes stale
 int lane_first_variant(const famseq_ctx *c);  // 4 where the lane kernel has the once-per-site form (variants 4-7), else 0
 hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,
-                            void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk = 0, const void *d_ninth = nullptr);
+                            void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk = 0, const MoreArgs &more = {});
 hipError_t launch_engine(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, double *d_post, double *d_single,
                          uint8_t *d_status, hipStream_t stream);
 bool call_fuses(famseq_ctx *c, int64_t n_sites, bool packed_in);
@@ -231,8 +251,10 @@ CallIO make_call_io(const famseq_ctx *c, const uint16_t *d_pl, double *d_gpp, do
 int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq);
 // The side products' host entries: lk or packed PLs through kernel `g`, whose two outputs have a_row / b_row bytes per site.
 // prior: the site-prior forms' rows [n_sites][6], staged chunk by chunk alongside the likelihoods (NULL: the plain forms).
+// lead: what the kernel takes between the common arguments and the prior rows (the same for every chunk).
 int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
-               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior = nullptr);
+               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior = nullptr,
+               const MoreArgs &lead = {});
 
 }  // namespace famseq
 #endif

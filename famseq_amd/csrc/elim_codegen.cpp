@@ -309,6 +309,50 @@ class Emitter {
   // the decimal digits of scale in evidence_body's Z_ and W0_
   int evidence_scale_digits() const { return 7 * (g_.cut.empty() ? (int)g_.scaled.size() : 1); }
 
+  // Genotype-pattern posteriors (famseq_pattern): the sum pass of evidence_body, run n_patterns + 1 times on one read of the
+  // site's rows.  Pass 0 takes the rows as they are; pass m = 1 .. n_patterns takes member p's entry g as
+  // (mask[m - 1][p] >> g) & 1 ? l_g : 0.0 — a select, no multiplication, no rounding — formed before loc() sees it, so the
+  // founders' priors, the site's own prior rows, the male chrX row and a cut member's lam all follow unchanged.  The masks are
+  // wave-uniform: the shell packs them into LDS words once per workgroup (s_mw: four bits per member, eight members per word,
+  // row 0 all ones), and a pass reads its NMW words into scalar registers.  The loop is `#pragma unroll 1`: the pass's text
+  // stands once whatever n_patterns is.  Where the likelihoods sit in registers (r<p>_<g>: the shell's l<p>_<g> under another
+  // name) a pass's masked values shadow the shell's names; in the lean form the names are macros and are defined again, the
+  // row read afresh at each use and the select applied to what was read.
+  // Per pass: Zp_, the pass's total weight (scaled as evidence_body's Z_: evidence_scale_digits()), then `per_pass`.
+  std::string pattern_body(const std::string &per_pass) {
+    const int nmw = (g_.N + 7) / 8;
+    std::ostringstream head;
+    auto bit = [&](int p, int g) { return "(mw" + num(p / 8) + " >> " + num(4 * (p % 8) + g) + ") & 1u"; };
+    if (!lean_) {
+      for (int p = 0; p < g_.N; ++p)
+        head << "      const double r" << p << "_0 = l" << p << "_0, r" << p << "_1 = l" << p << "_1, r" << p << "_2 = l" << p << "_2;\n";
+    } else {
+      for (int p = 0; p < g_.N; ++p)
+        for (int g = 0; g < 3; ++g)
+          head << "#undef l" << p << "_" << g << "\n#define l" << p << "_" << g << " __extension__ ({ const double v_ = lgv[" << 3 * p + g
+               << "]; " << bit(p, g) << " ? v_ : 0.0; })\n";
+    }
+    head << "#pragma unroll 1\n      for (int pt_ = 0; pt_ <= last_; ++pt_) {\n";
+    for (int k = 0; k < nmw; ++k)
+      head << "      const unsigned mw" << k << " = __builtin_amdgcn_readfirstlane(s_mw[pt_ * " << nmw << " + " << k << "]);\n";
+    if (!lean_)
+      for (int p = 0; p < g_.N; ++p)
+        for (int g = 0; g < 3; ++g)
+          head << "      const double l" << p << "_" << g << " = " << bit(p, g) << " ? r" << p << "_" << g << " : 0.0;\n";
+    std::string pass;
+    if (g_.cut.empty()) {
+      fence(1);
+      component_sums();
+      o_ << "      const double Zp_ = " << times_sums("") << ";\n";
+      fence(1);
+      pass = o_.str();
+    } else {
+      pass = cut_loop("      double Zt_ = 0;\n", /*wc=*/false, /*wall=*/true, [&] { o_ << "      Zt_ = Zt_ + Wall;\n"; fence(1); }) +
+             "      const double Zp_ = Zt_;\n";
+    }
+    return head.str() + pass + per_pass + "      }\n";
+  }
+
   // Leave-one-out (famseq_loo): for every member p its cavity row k<p>_g, the product of everything the network says of g_p but
   // p's own likelihood: the founder's prior (a child has none) times the message of every adjacent family.  Member p's
   // marginal is c<p>_g * prod of the same messages; here the likelihood is left out of the product, never divided out of it
@@ -841,6 +885,8 @@ struct LaneShell {
   std::string outputs;     // the declarations of the third and fourth parameters
   std::string defines;     // behind W3 and BT
   std::string shared;      // __shared__ declarations behind the factor tables'
+  std::string more_args;   // parameters behind the common eight (in front of prior_g)
+  std::string prologue;    // per workgroup: behind the factor tables' staging, in front of the first barrier
   std::string site_decls;  // per site: in front of the flags
   std::string site_vars;   // ... and behind the failure flags
   std::string after_single;  // behind the single posterior's statements
@@ -870,11 +916,12 @@ std::string lane_shell(const Model &m, const LaneShell &d) {
   for (int p = d.lean ? 0 : first_lds; p < N; ++p)
     for (int gt = 0; gt < 3; ++gt)
       s << "#define l" << p << "_" << gt << (d.lean ? " lgv[" : " lrow[") << 3 * (d.lean ? p : p - first_lds) + gt << "]\n";
-  s << kernel_signature(d.entry + (d.site_prior ? "_prior" : ""), d.min_waves, d.outputs, d.site_prior ? ", const double *__restrict__ prior_g" : "")
+  s << kernel_signature(d.entry + (d.site_prior ? "_prior" : ""), d.min_waves, d.outputs, d.more_args + (d.site_prior ? ", const double *__restrict__ prior_g" : ""))
     << "  __shared__ double s_tc[432];\n"
     << d.shared
     << "  const int tid = threadIdx.x;\n"
     << "  for (int i = tid; i < 432; i += BT) s_tc[i] = tc_g[i];\n"
+    << d.prologue
     << (d.site_prior ? "  const bool p16 = ((unsigned long)prior_g & 15) == 0;\n  v2d pu0, pu1, pu2;\n" : "");
   if (n_lds > 0)
     s << "  __shared__ double s_l[BT * " << LP << "];  // the last " << n_lds << " members' likelihoods, one padded row per lane\n"
@@ -1087,6 +1134,59 @@ std::string loo_source(const Model &m, int variant, bool site_prior) {
       "      if (fg) {\n#pragma unroll 1\n        for (int k = 0; k < NMEM; ++k) fg[k] = kNaN;\n      }\n"
       "    }\n"
       "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
+  d.bt = elim_block_threads(m, false);
+  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  return lane_shell(m, d);
+}
+
+// The pattern kernel: the evidence kernel's rules and shell.  Beyond the common arguments: mask_g[n_patterns][N] (bit g of an entry
+// set: genotype g is allowed to that member) and n_patterns (1 .. FAMSEQ_MAX_PATTERNS; the host checks, the kernel clamps).
+// Outputs per site: ppost[n_patterns], pattern m's posterior Z_m / Z — a true division, so that a pattern that allows everything
+// gives exactly 1.0 — and loglik, famseq_evidence's, from the unmasked pass; either may be null (without ppost only the unmasked
+// pass runs).  No clamp: every term of the sum is non-negative and a masked pass runs the unmasked pass's statements on operands
+// that are the same or zero, and rounding is monotonic, so Z_m <= Z holds in floating point as it does in exact arithmetic.
+// Z_m = 0 gives 0.0, which is a result; only an unmasked Z that is not a positive finite number fails the site (status 2).
+// Where the likelihoods live: in registers twice under forty members (the real rows and the pass's masked copy, which the
+// compiler is free to form at its use instead), from forty on read from the lane's row at each use, as the evidence kernel does.
+std::string pattern_source(const Model &m, int variant, bool site_prior) {
+  const Graph g = graph_or_throw(m);
+  if (variant < 0 || variant >= kPatternVariants)
+    throw std::runtime_error("pattern_source: variant must be 0.." + std::to_string(kPatternVariants - 1));
+  const int f = variant, N = m.n_members, nmw = (N + 7) / 8;
+  EmitOptions eo = emit_options(f, "pg", site_prior);
+  LaneShell d;
+  d.lean = eo.lean = N >= 40;  // as trio_source
+  d.entry = "famseq_pattern";
+  d.comment = describe("genotype-pattern posteriors (sum pass per pattern)", g, std::to_string(f), site_prior);
+  d.outputs = "double *__restrict__ ppost_g, double *__restrict__ loglik_g";
+  d.more_args = ", const unsigned char *__restrict__ mask_g, int n_patterns";
+  d.defines = "#define NMEM " + std::to_string(N) + "\n#define NMW " + std::to_string(nmw) + "\n#define MAXPAT " +
+              std::to_string(FAMSEQ_MAX_PATTERNS) + "\n";
+  d.shared = "  __shared__ unsigned s_mw[(MAXPAT + 1) * NMW];  // the passes' masks: four bits per member, row 0 (the unmasked pass) all ones\n";
+  d.prologue =
+      "  const int np_ = n_patterns < 0 ? 0 : (n_patterns > MAXPAT ? MAXPAT : n_patterns);\n"
+      "  for (int i = tid; i < (np_ + 1) * NMW; i += BT) {\n"
+      "    const int pt = i / NMW, w = i - pt * NMW;\n"
+      "    unsigned v = 0;\n"
+      "    for (int j = 0; j < 8 && 8 * w + j < NMEM; ++j) v |= (pt ? (unsigned)mask_g[(pt - 1) * NMEM + 8 * w + j] & 7u : 7u) << (4 * j);\n"
+      "    s_mw[i] = v;\n"
+      "  }\n";
+  d.site_decls = "    double *pp = ppost_g ? ppost_g + site * np_ : nullptr;\n"
+                 "    const int last_ = pp ? np_ : 0;\n";
+  d.site_vars = "    double pt_ll = kNaN, Z0_ = 0;\n";
+  Emitter e(m, g, eo);
+  d.body = e.pattern_body(
+      "      if (pt_ == 0) {\n"
+      "        if (!(Zp_ > 0 && Zp_ <= 1.79769313486231570815e308)) { bn_fail = true; break; }\n"
+      "        Z0_ = Zp_; pt_ll = log10(Zp_) - " + std::to_string(e.evidence_scale_digits()) + ".0;\n"
+      "      } else {\n"
+      "        __builtin_nontemporal_store(Zp_ / Z0_, pp + (pt_ - 1));\n"
+      "      }\n");
+  d.epilogue = "    if (single_fail || bn_fail) {\n      pt_ll = kNaN;\n"
+               "      if (pp) {\n#pragma unroll 1\n        for (int k = 0; k < np_; ++k) pp[k] = kNaN;\n      }\n"
+               "    }\n"
+               "    if (loglik_g) __builtin_nontemporal_store(pt_ll, loglik_g + site);\n"
+               "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.bt = elim_block_threads(m, false);
   d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
   return lane_shell(m, d);

@@ -78,5 +78,15 @@ constexpr int kLooVariants = 4;
 // site_prior: famseq_loo_prior, with a trailing `prior` [n_sites][6] (as trio_source's).
 std::string loo_source(const Model &m, int variant, bool site_prior = false);
 
+// Genotype-pattern posteriors (famseq_pattern_batch).  HIP source of
+// `extern "C" __global__ famseq_pattern(lk, flags, ppost, loglik, status, n_sites, tc, lc, mask, n_patterns)`: per site and pattern
+// m — mask[m][p] holds in bit g whether member p (PED order) may have genotype g — ppost[m] = Z_m / Z, the posterior probability
+// that every member's genotype is one its mask allows, Z_m being the network's total weight with the disallowed entries of every
+// likelihood row set to zero; and loglik, famseq_evidence's.  The sum pass of famseq_evidence, n_patterns + 1 times on one read of
+// the site's rows.  variant 0..3: the fence levels of famseq_elim's.  Throws if the engine does not serve the pedigree.
+constexpr int kPatternVariants = 4;
+// site_prior: famseq_pattern_prior, with a trailing `prior` [n_sites][6] behind n_patterns (as trio_source's).
+std::string pattern_source(const Model &m, int variant, bool site_prior = false);
+
 }  // namespace famseq
 #endif

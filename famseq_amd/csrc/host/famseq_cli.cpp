@@ -4,6 +4,7 @@
 //   FamSeq vcf -vcfFile f -pedFile p -output o [-v] [-a] [-d] [-o] [-l loc] [-method 1]
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
 //              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-loo] [-afTag KEY | -afTagAll KEY]
+//              [-seg dominant|recessive|both -affected ID[,ID...] [-unaffected ID[,ID...]]]
 //   FamSeq LK  -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -19,7 +20,10 @@
 // -method 2 is the exact sum-product engine (the marginals of the reference's Elston-Stewart peeling), -method 3 (MCMC) is
 // not part of this build, -dnm (vcf mode) adds each child's de novo mutation posterior (DNP) from the trio kernel, and -map (vcf
 // mode) each member's genotype in the most probable joint configuration of the family and that configuration's posterior (JGT, JP),
-// and -siteQ (vcf mode) the family's variant quality and the site's log10 likelihood under the pedigree to the INFO column (FQ, FLL).
+// -siteQ (vcf mode) the family's variant quality and the site's log10 likelihood under the pedigree to the INFO column (FQ, FLL),
+// -loo (vcf mode) each sample's leave-one-out genotype probabilities and fit (LOP, LOF), and -seg (vcf mode) the posterior probability
+// that the variant segregates with the phenotype of the members named by -affected / -unaffected, under a dominant and / or a
+// recessive model, to the INFO column (PSD, PSR).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -192,6 +196,9 @@ struct Options {
   bool map = false;  // -map: JGT and JP fields per sample (vcf mode)
   bool siteq = false;  // -siteQ: FQ and FLL keys in the INFO column (vcf mode)
   bool loo = false;    // -loo: LOP and LOF fields per sample, the leave-one-out posteriors and the member's fit (vcf mode)
+  // -seg dominant|recessive|both: PSD and / or PSR keys in the INFO column (vcf mode), the posterior probability of the genotype
+  // pattern that model gives the members of -affected and -unaffected (PED IDs, comma-separated)
+  string seg, affected, unaffected;
   string af_tag;     // -afTag KEY: the founders' prior of a line from the allele frequency KEY= of its INFO column (vcf mode)
   bool af_conflict = false;  // both -afTag and -afTagAll were given
   bool af_all = false;  // -afTagAll KEY: -afTag KEY, applied to every field a line prints (DNP, JGT and JP too: may go with -dnm / -map)
@@ -330,6 +337,15 @@ int parse_options(int argc, char **argv, Options &o) {
       o.siteq = true;
     } else if (opt == "loo") {
       o.loo = true;
+    } else if (opt == "seg" || opt == "affected" || opt == "unaffected") {
+      i++;
+      if (missing(i)) {
+        std::cout << "The value of -" << opt << " hasn't been set. The option is ignored." << std::endl;
+        i--;
+        rv = 1;
+      } else {
+        (opt == "seg" ? o.seg : (opt == "affected" ? o.affected : o.unaffected)) = argv[i];
+      }
     } else if (opt == "afTag" || opt == "afTagAll") {
       i++;
       if (missing(i)) {
@@ -694,6 +710,47 @@ bool sum_product_serves(const Options &o, const Ped &ped, const char *flag_text)
   if (k < 0) std::cout << flag_text << " cannot serve this pedigree: " << (probe ? famseq_last_error(probe) : err) << std::endl;
   famseq_destroy(probe);
   return k >= 0;
+}
+
+// -seg: the mask rows of its patterns in the order they are printed (PSD, PSR), [n_patterns][N] in PED order, from the PED IDs of
+// -affected and -unaffected.  false with a message: an unknown model, no -affected, an ID the PED file does not hold, an ID in both.
+bool segregation_masks(const Options &o, const Ped &ped, vector<uint8_t> &masks, vector<const char *> &keys) {
+  if (o.seg != "dominant" && o.seg != "recessive" && o.seg != "both") {
+    std::cout << "-seg takes dominant, recessive or both, not \"" << o.seg << "\"." << std::endl;
+    return false;
+  }
+  if (o.affected.empty()) {
+    std::cout << "-seg needs the affected members: -affected ID[,ID...] (PED IDs)." << std::endl;
+    return false;
+  }
+  vector<int> role(ped.n(), 0);  // 1 affected, 2 unaffected
+  for (int r = 1; r <= 2; ++r) {
+    std::istringstream in(r == 1 ? o.affected : o.unaffected);
+    string tok;
+    while (std::getline(in, tok, ',')) {
+      char *end = nullptr;
+      const long id = std::strtol(tok.c_str(), &end, 10);
+      int at = -1;
+      for (int i = 0; i < ped.n() && !tok.empty() && *end == 0; ++i)
+        if (ped.id[i] == id) at = i;
+      if (at < 0) {
+        std::cout << (r == 1 ? "-affected" : "-unaffected") << ": \"" << tok << "\" is not an individual ID of the PED file." << std::endl;
+        return false;
+      }
+      if (role[at] != 0 && role[at] != r) {
+        std::cout << "Individual " << tok << " is listed both as affected and as unaffected." << std::endl;
+        return false;
+      }
+      role[at] = r;
+    }
+  }
+  masks.clear(), keys.clear();
+  for (int model = 0; model < 2; ++model) {  // dominant: affected 6, unaffected 1; recessive: 4, 3; anyone else 7
+    if (o.seg != "both" && o.seg != (model ? "recessive" : "dominant")) continue;
+    keys.push_back(model ? "PSR=" : "PSD=");
+    for (int i = 0; i < ped.n(); ++i) masks.push_back(role[i] == 1 ? (model ? 4 : 6) : (role[i] == 2 ? (model ? 3 : 1) : 7));
+  }
+  return true;
 }
 
 // -afTag: the allele frequency of a line, the first value of KEY= in its INFO column; < 0 where there is none to use (no such
@@ -1257,6 +1314,11 @@ bool run_vcf(const Options &o, const Ped &ped) {
     if (o.gXK.size() == 3) std::copy(o.gXK.begin(), o.gXK.end(), m.p.genoProbXK);
   }
   const bool use_af = !o.af_tag.empty() && !o.pack_mode;
+  // -seg: the patterns' mask rows and INFO keys (main has checked the options: this cannot fail here)
+  vector<uint8_t> seg_masks;
+  vector<const char *> seg_keys;
+  if (!o.seg.empty() && !o.pack_mode && !segregation_masks(o, ped, seg_masks, seg_keys)) return false;
+  const size_t n_seg = seg_keys.size();
   // -afTag: the rows of a line without a usable frequency, by its Known flag: what the model itself would have used
   double model_rows[2][6];
   for (int k = 0; k < 3; ++k) {
@@ -1287,6 +1349,14 @@ bool run_vcf(const Options &o, const Ped &ped) {
               "member of the family, the sample's own left out\">" << std::endl;
       fout << "##FORMAT=<ID=LOF,Number=1,Type=Float,Description=\"Phred-scaled predictive likelihood of the sample's data given the "
               "other members' (99999: impossible given the relatives)\">" << std::endl;
+    }
+    if (!o.seg.empty()) {
+      if (o.seg != "recessive")
+        fout << "##INFO=<ID=PSD,Number=1,Type=Float,Description=\"Posterior probability that the affected members, and no unaffected one, "
+                "carry the variant (dominant segregation pattern)\">" << std::endl;
+      if (o.seg != "dominant")
+        fout << "##INFO=<ID=PSR,Number=1,Type=Float,Description=\"Posterior probability that the affected members, and no unaffected one, "
+                "are homozygous for the variant (recessive segregation pattern)\">" << std::endl;
     }
     if (o.siteq) {
       fout << "##INFO=<ID=FQ,Number=1,Type=Float,Description=\"Family variant quality: Phred-scaled posterior probability that every "
@@ -1579,6 +1649,8 @@ bool run_vcf(const Options &o, const Ped &ped) {
     vector<uint8_t> estatus;   // ... and the evidence kernel's status per site
     vector<double> loo, fit;   // -loo: [site][member][3] leave-one-out posteriors, [site][member] the members' fit ...
     vector<uint8_t> lstatus;   // ... and the leave-one-out kernel's status per site
+    vector<double> ppat;       // -seg: [site][pattern] the patterns' posteriors ...
+    vector<uint8_t> pstatus;   // ... and the pattern kernel's status per site
   } slots[4];  // one being cut and parsed, one at the GPU, one being formatted, one being written
   bool ok = true;
   for (Slot &sl : slots) sl.parts.resize(n_threads), sl.text.resize(n_threads);
@@ -1654,6 +1726,18 @@ bool run_vcf(const Options &o, const Ped &ped) {
           sl.loo.resize(sl.n_sites * size_t(ped.n()) * 3), sl.fit.resize(sl.n_sites * size_t(ped.n()));
           side(famseq_loo_batch, famseq_loo_prior_batch, sl.loo.data(), sl.fit.data(), sl.lstatus, "famseq_loo");
         }
+        if (n_seg && flush_ok) {  // (the masks ride between the input and the outputs of both entries)
+          sl.ppat.resize(sl.n_sites * n_seg);
+          const uint8_t *mk = seg_masks.data();
+          const int32_t np = (int32_t)n_seg;
+          side([=](famseq_ctx *c, int64_t n, const double *lk, const uint16_t *pl, const int32_t *seq, int32_t ns, const uint8_t *fl, double *a,
+                   double *b, uint8_t *st) { return famseq_pattern_batch(c, n, lk, pl, seq, ns, fl, mk, np, a, b, st); },
+               [=](famseq_ctx *c, int64_t n, const double *lk, const uint16_t *pl, const int32_t *seq, int32_t ns, const uint8_t *fl,
+                   const double *prior, double *a, double *b, uint8_t *st) {
+                 return famseq_pattern_prior_batch(c, n, lk, pl, seq, ns, fl, prior, mk, np, a, b, st);
+               },
+               sl.ppat.data(), (double *)nullptr, sl.pstatus, "famseq_pattern");
+        }
       }
       t_gpu += now_s() - t0;
       to_formatter.put(i);
@@ -1702,9 +1786,11 @@ bool run_vcf(const Options &o, const Ped &ped) {
     }
     out.ch('\t');
   };
-  // -siteQ: columns 1-8 + FORMAT of a site with "FQ=<x>;FLL=<y>" joined to its INFO column (an INFO of "." is replaced); a site
-  // whose evidence failed keeps its INFO.  FQ by the drivers' rule for FPP: fabs(-10 log10 p), 99999 for 0 (file.cpp:696-745).
-  auto put_prefix_siteq = [&](TextBuf &out, const Slot &sl, size_t s, const char *raw, size_t len) {
+  // -siteQ, -seg: columns 1-8 + FORMAT of a site with "FQ=<x>;FLL=<y>" and / or "PSD=<p>;PSR=<q>" joined to its INFO column (an
+  // INFO of "." is replaced); a site whose evidence (pattern kernel) failed does without those keys, and keeps its INFO where none
+  // is left to add.  FQ by the drivers' rule for FPP: fabs(-10 log10 p), 99999 for 0 (file.cpp:696-745); PSD and PSR are plain
+  // probabilities — the value of interest is near 1, where Phred has no resolution.
+  auto put_prefix_info = [&](TextBuf &out, const Slot &sl, size_t s, const char *raw, size_t len) {
     size_t info = 0, end = 0;  // the INFO column is raw[info, end): between the seventh and the eighth tab
     int tabs = 0;
     for (size_t q = 0; q < len && tabs < 8; ++q)
@@ -1712,7 +1798,8 @@ bool run_vcf(const Options &o, const Ped &ped) {
         if (++tabs == 7) info = q + 1;
         if (tabs == 8) end = q;
       }
-    if (tabs < 8 || sl.estatus[s] != 0) {
+    const bool add_q = o.siteq && sl.estatus[s] == 0, add_seg = n_seg && sl.pstatus[s] == 0;
+    if (tabs < 8 || !(add_q || add_seg)) {
       out.put(raw, len);
       return;
     }
@@ -1721,11 +1808,18 @@ bool run_vcf(const Options &o, const Ped &ped) {
       out.put(raw + info, end - info);
       if (end > info) out.ch(';');
     }
-    const double p = sl.pref[s];
-    out.put("FQ=", 3);
-    out.num(p == 0 ? 99999.0 : std::fabs(-10.0 * std::log10(p)));
-    out.put(";FLL=", 5);
-    out.num(sl.fll[s]);
+    if (add_q) {
+      const double p = sl.pref[s];
+      out.put("FQ=", 3);
+      out.num(p == 0 ? 99999.0 : std::fabs(-10.0 * std::log10(p)));
+      out.put(";FLL=", 5);
+      out.num(sl.fll[s]);
+    }
+    for (size_t m = 0; add_seg && m < n_seg; ++m) {
+      if (add_q || m) out.ch(';');
+      out.put(seg_keys[m], 4);
+      out.num(sl.ppat[s * n_seg + m]);
+    }
     out.put(raw + end, len - end);
   };
   // ... the results are turned into text on their own thread (and its helpers) while the next block is at the GPU ...
@@ -1747,7 +1841,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
             } else {
               const size_t s = size_t(it.site);
               const Record::Sample *sm = &pt.samples[it.smp];
-              if (o.siteq) put_prefix_siteq(out, sl, s, it.raw, it.prefix_len);
+              if (o.siteq || n_seg) put_prefix_info(out, sl, s, it.raw, it.prefix_len);
               else out.put(it.raw, it.prefix_len);  // columns 1-8 + FORMAT
               out.put(":GPP:FPP:FGT", 12);
               if (o.dnm) out.put(":DNP", 4);
@@ -2111,6 +2205,10 @@ void help() {
             << "-loo\t\t(vcf) Add LOP, the sample's Phred-scaled genotype probabilities given every other member's data with its own" << std::endl
             << "\t\tleft out, and LOF, the Phred-scaled likelihood of its own data given theirs (99999: impossible given the relatives)," << std::endl
             << "\t\tto every sample column. Implies -method 2; may be combined with -dnm, -map, -siteQ and -afTagAll; not with -afTag." << std::endl
+            << "-seg MODEL\t(vcf) MODEL dominant, recessive or both, with -affected ID[,ID...] and optionally -unaffected ID[,ID...] (PED IDs):" << std::endl
+            << "\t\tadd PSD (dominant: the affected carry the variant, the unaffected do not) and / or PSR (recessive: the affected are" << std::endl
+            << "\t\thomozygous for it, the unaffected are not), the posterior probability of that pattern given the whole family's data," << std::endl
+            << "\t\tto the INFO column. Implies -method 2; may be combined with -dnm, -map, -siteQ, -loo and -afTagAll; not with -afTag." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl
@@ -2178,6 +2276,20 @@ int main(int argc, char **argv) {
     o.loo = false;
   }
   if (o.loo && !sum_product_serves(o, ped, "-loo")) return 255;
+  if ((!o.seg.empty() || !o.affected.empty() || !o.unaffected.empty()) && mode != "vcf") {
+    std::cout << "-seg applies to vcf mode only; ignored here." << std::endl;
+    o.seg.clear(), o.affected.clear(), o.unaffected.clear();
+  }
+  if (o.seg.empty() && !(o.affected.empty() && o.unaffected.empty())) {
+    std::cout << "-affected and -unaffected belong to -seg dominant|recessive|both, which was not given." << std::endl;
+    return -1;
+  }
+  if (!o.seg.empty()) {
+    vector<uint8_t> masks;
+    vector<const char *> keys;
+    if (!segregation_masks(o, ped, masks, keys)) return -1;
+    if (!sum_product_serves(o, ped, "-seg")) return 255;
+  }
   if (o.af_conflict) {
     std::cout << "-afTag and -afTagAll cannot be combined: give the INFO key once." << std::endl;
     return -1;
@@ -2186,7 +2298,7 @@ int main(int argc, char **argv) {
     if (mode != "vcf") {
       std::cout << (o.af_all ? "-afTagAll" : "-afTag") << " applies to vcf mode only; ignored here." << std::endl;
       o.af_tag.clear();
-    } else if (!o.af_all && (o.dnm || o.map || o.siteq || o.loo)) {
+    } else if (!o.af_all && (o.dnm || o.map || o.siteq || o.loo || !o.seg.empty())) {
       std::cout << "-afTag cannot be combined with -dnm or -map: their kernels use the model's priors, and one output line must not mix two models."
                 << std::endl;
       return -1;
@@ -2196,7 +2308,7 @@ int main(int argc, char **argv) {
       o.method = 2;  // site priors are served by the sum-product engine
     }
   }
-  if (o.siteq || o.loo) o.method = 2;  // the evidence and the leave-one-out kernel are the sum-product engine's
+  if (o.siteq || o.loo || !o.seg.empty()) o.method = 2;  // the evidence, leave-one-out and pattern kernels are the sum-product engine's
   const double t0 = now_s();
   if (o.tune_mode) return run_tune(o, ped) ? 0 : -1;
   const bool ok = o.pl_mode ? run_pl(o, ped) : (o.lk_mode ? run_lk(o, ped) : run_vcf(o, ped));

@@ -15,19 +15,22 @@ namespace famseq {
 SideTable &side_table() {
   static SideTable table = {
       {"trio", "trio posteriors", "1 (dnm), 2 (joint) or 3 (both)", K_TRIO, K_TRIO_PRIOR, 3, kTrioVariants, trio_source,
-       [](const Model &m, size_t row[2]) {  // joint[K][27], dnm[K]
+       [](const Model &m, int, size_t row[2]) {  // joint[K][27], dnm[K]
          const size_t K = trio_children(m).size();
          row[0] = 27 * K * sizeof(double), row[1] = K * sizeof(double);
        }},
       {"map", "joint MAP call", "1", K_MAP, K_MAP_PRIOR, 1, kMapVariants,
        [](const Model &m, int v, int, bool site_prior) { return map_source(m, v, site_prior); },
-       [](const Model &m, size_t row[2]) { row[0] = size_t(m.n_members), row[1] = sizeof(double); }},  // map_gt[N], map_post
+       [](const Model &m, int, size_t row[2]) { row[0] = size_t(m.n_members), row[1] = sizeof(double); }},  // map_gt[N], map_post
       {"evidence", "site evidence", "1", K_EVID, K_EVID_PRIOR, 1, kEvidenceVariants,
        [](const Model &m, int v, int, bool site_prior) { return evidence_source(m, v, site_prior); },
-       [](const Model &, size_t row[2]) { row[0] = row[1] = sizeof(double); }},  // loglik, pref
+       [](const Model &, int, size_t row[2]) { row[0] = row[1] = sizeof(double); }},  // loglik, pref
       {"loo", "leave-one-out posteriors", "1", K_LOO, K_LOO_PRIOR, 1, kLooVariants,
        [](const Model &m, int v, int, bool site_prior) { return loo_source(m, v, site_prior); },
-       [](const Model &m, size_t row[2]) { row[0] = 3 * size_t(m.n_members) * sizeof(double), row[1] = size_t(m.n_members) * sizeof(double); }},  // loo[N][3], fit[N]
+       [](const Model &m, int, size_t row[2]) { row[0] = 3 * size_t(m.n_members) * sizeof(double), row[1] = size_t(m.n_members) * sizeof(double); }},  // loo[N][3], fit[N]
+      {"pattern", "genotype-pattern posteriors", "1", K_PATTERN, K_PATTERN_PRIOR, 1, kPatternVariants,
+       [](const Model &m, int v, int, bool site_prior) { return pattern_source(m, v, site_prior); },
+       [](const Model &, int n_patterns, size_t row[2]) { row[0] = size_t(n_patterns) * sizeof(double), row[1] = sizeof(double); }},  // pat_post[M], loglik
   };
   return table;
 }
@@ -274,11 +277,10 @@ int grid_for(const famseq_ctx *c, int64_t n_sites) {
 }  // namespace
 
 // The generated kernels share one argument list; what the third and fourth are depends on the kind (posterior and single
-// posterior rows, joint and de novo posteriors, MAP genotypes and their posterior, log10 likelihood and hom-ref posterior, leave-one-out rows and fit), so
-// they pass through untyped; so does
-// the ninth, which two kinds take: the call-path forms their CallIO, the site-prior kernel its prior rows.
+// posterior rows, joint and de novo posteriors, MAP genotypes and their posterior, log10 likelihood and hom-ref posterior, leave-one-out rows and fit, pattern
+// posteriors and log10 likelihood), so they pass through untyped; so does what some kinds take behind the eighth (MoreArgs).
 hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,
-                            void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk, const void *d_ninth) {
+                            void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk, const MoreArgs &more) {
   const int spc = sites_per_chunk > 0 ? sites_per_chunk : g.block_threads;
   const int64_t chunks = (n_sites + spc - 1) / spc;
   int64_t resident = c->grid_override > 0 ? c->grid_override : int64_t(c->n_cus) * g.blocks_per_cu;
@@ -286,7 +288,8 @@ hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, 
   long ns = (long)n_sites;
   double lc = c->model.lc;
   const double *tc = c->d_tc.as<double>();
-  void *args[] = {&d_lk, &d_flags, &d_out_a, &d_out_b, &d_status, &ns, &tc, &lc, &d_ninth};  // the plain forms take the first eight
+  void *args[8 + MoreArgs::kMax] = {&d_lk, &d_flags, &d_out_a, &d_out_b, &d_status, &ns, &tc, &lc};  // the plain forms take these eight
+  for (int i = 0; i < more.n; ++i) args[8 + i] = more.at[i];
   return hipModuleLaunchKernel(g.k.fn, grid, 1, 1, (unsigned)g.block_threads, 1, 1, 0, stream, args, nullptr);
 }
 
@@ -331,7 +334,7 @@ bool launch_engine_fused(famseq_ctx *c, int64_t n_sites, const double *d_lk, con
   const bool elim = c->engine == FAMSEQ_ENGINE_ELIM;
   if (!call_fuses(c, n_sites, packed_in)) return false;
   if (!elim) c->last_group_digits = 0;
-  *err = launch_generated(c, c->kern[elim ? K_ELIM_CALL : K_LANE_CALL], n_sites, d_lk, d_flags, nullptr, nullptr, d_status, stream, 0, d_io);
+  *err = launch_generated(c, c->kern[elim ? K_ELIM_CALL : K_LANE_CALL], n_sites, d_lk, d_flags, nullptr, nullptr, d_status, stream, 0, {&d_io});
   return true;
 }
 

@@ -176,6 +176,7 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
   job.copy_out(B_STATUS, 1, io.status);
   rc = run_pipeline(c, t, job, [&](int s, int64_t n, hipStream_t s_k) -> int {
     DevBuf *d = t.buf[s];
+    const double *d_prior = d[B_PRIOR].as<double>();
     double *d_lk = d[B_LK].as<double>(), *d_post = d[B_POST].as<double>(), *d_single = d[B_SINGLE].as<double>();
     double *d_gpp = d[B_GPP].as<double>(), *d_fpp = d[B_FPP].as<double>();
     const uint8_t *d_flags = io.flags ? d[B_FLAGS].as<uint8_t>() : nullptr;
@@ -194,7 +195,7 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
         HIP_TRY(c, launch_unpack_pl16(d[B_PL].as<uint16_t>(), c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, n_seq, n, d_lk, s_k));
       if (io.prior)
         HIP_TRY(c, launch_generated(c, c->kern[K_PRIOR], n, d_lk, d_flags, d_post, need_single ? d_single : nullptr, d_status, s_k, 0,
-                                    d[B_PRIOR].as<double>()));
+                                    {&d_prior}));
       else
         HIP_TRY(c, launch_engine(c, n, d_lk, d_flags, d_post, need_single ? d_single : nullptr, d_status, s_k));
       if (called)
@@ -219,7 +220,7 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
 // ... and the trio and MAP entries (plain and site-prior): per chunk [unpack] -> kernel, on the entry's own set of slots.  out_a / out_b: the two
 // per-site outputs (NULL: not wanted), a_row / b_row their bytes per site (0: the pedigree has none).
 int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
-               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior) {
+               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior, const MoreArgs &lead) {
   const int N = c->model.n_members;
   const size_t row = size_t(3) * N * sizeof(double), pl_row = pl16 ? size_t(n_seq) * 3 * sizeof(uint16_t) : 0;
   const size_t prior_row = prior ? 6 * sizeof(double) : 0;
@@ -242,9 +243,11 @@ int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, c
     DevBuf *d = t.buf[s];
     if (pl16)
       HIP_TRY(c, launch_unpack_pl16(d[B_PL].as<uint16_t>(), c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, n_seq, n, d[B_LK].as<double>(), s_k));
+    const void *d_prior = prior ? d[B_PRIOR].p : nullptr;
+    MoreArgs more = lead;
+    more.at[more.n++] = &d_prior;  // (behind the last parameter of a plain form: not read)
     HIP_TRY(c, launch_generated(c, g, n, d[B_LK].as<double>(), flags ? d[B_FLAGS].as<uint8_t>() : nullptr, out_a ? d[B_OUT_A].p : nullptr,
-                                out_b ? d[B_OUT_B].p : nullptr, status ? d[B_STATUS].as<uint8_t>() : nullptr, s_k, 0,
-                                prior ? d[B_PRIOR].p : nullptr));
+                                out_b ? d[B_OUT_B].p : nullptr, status ? d[B_STATUS].as<uint8_t>() : nullptr, s_k, 0, more));
     return 0;
   });
 }

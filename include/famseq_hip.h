@@ -465,6 +465,50 @@ int famseq_loo_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double
                                   const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior, double *d_loo,
                                   double *d_fit, uint8_t *d_status, void *stream);
 
+/* ---- genotype-pattern posteriors ---------------------------------------------------------------------------------------
+ * A pattern gives every member a set of allowed genotypes; its posterior is the probability, given everybody's data, that
+ * every member's genotype lies in its set:  P(g_i in A_i for every i | data) = Z_A / Z,  Z_A being the network's total weight
+ * with the disallowed entries of every likelihood row set to zero.  (Members' marginals are not independent: the product of
+ * their P(g_i in A_i) is not this number.)  Segregation with a phenotype is two such patterns: "dominant", the affected carry
+ * the variant (mask 6) and the unaffected do not (1); "recessive", the affected are hom-alt (4) and nobody else named is (3).
+ *   masks [n_patterns][N]   one byte per member in PED order: bit g set = genotype g allowed.  7 leaves the member
+ *              unconstrained; 0 is legal and makes the pattern impossible.  The same for every site of the call.
+ *   n_patterns              1 .. FAMSEQ_MAX_PATTERNS.
+ *   pat_post [n_sites][n_patterns]   Z_m / Z, in [0, 1]: exactly 1.0 for a pattern of 7s, exactly 0.0 for a pattern without
+ *              weight (a result, not a failure).
+ *   loglik [n_sites]        famseq_evidence_batch's: log10 of the site's likelihood under the pedigree.
+ *   status [n_sites]        0 OK; 1 the single-posterior failure rule of famseq_bn_batch, applied to the rows as given; 2 the
+ *              total weight Z is <= 0 or not finite.  Wherever status != 0, pat_post and loglik of the site are NaN.
+ * One kernel launch reads a site's rows once and runs the sum pass n_patterns + 1 times on them.  Served by the sum-product
+ * engine's graph as famseq_evidence_batch is, whatever the context's engine; compiled on the first call or ahead through
+ * famseq_set_option "pattern_kernels" = 1.  famseq_plan_json: "pattern_code_object", "pattern_variant".
+ * FAMSEQ_E_ARG, with a message: n_patterns outside 1 .. FAMSEQ_MAX_PATTERNS, masks NULL, (host entries) a mask byte > 7. */
+#define FAMSEQ_MAX_PATTERNS 32
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_evidence_batch.  masks is a host array, staged by the library.
+ * Any of pat_post / loglik / status may be NULL. */
+int famseq_pattern_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                         int32_t n_seq, const uint8_t *flags, const uint8_t *masks, int32_t n_patterns, double *pat_post,
+                         double *loglik, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array), d_masks among them — it must stay valid
+ * and unchanged until the kernel has run, and only its low three bits per byte are read: enqueues on `stream` (a hipStream_t;
+ * NULL = the default stream) and returns without synchronising. */
+int famseq_pattern_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const uint8_t *d_masks,
+                                int32_t n_patterns, double *d_pat_post, double *d_loglik, uint8_t *d_status, void *stream);
+
+/* With the founders' genotype prior given per site: prior[n_sites][6], as for famseq_evidence_prior_batch.  Given rows that equal
+ * the model's constants the outputs are, bit for bit, famseq_pattern_batch's.  "pattern_prior_kernels" = 1 builds the kernel
+ * (famseq_pattern_prior) ahead; famseq_plan_json: "pattern_prior_code_object", "pattern_prior_variant". */
+int famseq_pattern_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                               int32_t n_seq, const uint8_t *flags, const double *prior, const uint8_t *masks, int32_t n_patterns,
+                               double *pat_post, double *loglik, uint8_t *status);
+int famseq_pattern_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                      const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                      const uint8_t *d_masks, int32_t n_patterns, double *d_pat_post, double *d_loglik,
+                                      uint8_t *d_status, void *stream);
+
 /* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] = ((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);
