@@ -87,7 +87,9 @@ ABI_SYMBOLS = [
     "famseq_evidence_batch", "famseq_evidence_batch_device", "famseq_evidence_prior_batch", "famseq_evidence_prior_batch_device",
     "famseq_loo_batch", "famseq_loo_batch_device", "famseq_loo_prior_batch", "famseq_loo_prior_batch_device",
     "famseq_pattern_batch", "famseq_pattern_batch_device", "famseq_pattern_prior_batch", "famseq_pattern_prior_batch_device",
+    "famseq_sample_batch", "famseq_sample_batch_device", "famseq_sample_prior_batch", "famseq_sample_prior_batch_device",
 ]
+# (and famseq_philox4x32_10, the one name with digits in it: philox4x32 below)
 PL_MISSING = 0xFFFF
 
 _lib = None
@@ -173,14 +175,18 @@ def lib():
     u16p = C.POINTER(C.c_uint16)
     # (more: what an entry takes between the prior rows and its outputs, as the host and the device entry declare it)
     masks = ([bp, C.c_int32], [vp, C.c_int32])
+    draws = ([C.c_uint64, C.c_int64, C.c_int32],) * 2  # seed, site_base, n_draws
     for name, out_a, more in (("trio", dp, ([], [])), ("map", C.POINTER(C.c_int8), ([], [])), ("evidence", dp, ([], [])), ("loo", dp, ([], [])),
-                              ("pattern", dp, masks)):
+                              ("pattern", dp, masks), ("sample", C.POINTER(C.c_int8), draws)):
         for prior in (0, 1):
             host = getattr(L, "famseq_%s%s_batch" % (name, "_prior" * prior))
             dev = getattr(L, "famseq_%s%s_batch_device" % (name, "_prior" * prior))
             host.argtypes = [C.c_void_p, C.c_int64, dp, u16p, ip, C.c_int32, bp] + [dp] * prior + more[0] + [out_a, dp, bp]
             dev.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp] + [vp] * prior + more[1] + [vp, vp, vp, vp]
             host.restype = dev.restype = C.c_int
+    u32p = C.POINTER(C.c_uint32)
+    L.famseq_philox4x32_10.argtypes = [u32p, u32p, u32p]
+    L.famseq_philox4x32_10.restype = None
     _lib = L
     return L
 
@@ -248,6 +254,19 @@ def hwe_priors(af):
     prior = np.empty((len(af), 6))
     lib().famseq_hwe_priors(len(af), _p(af, C.c_double), _p(prior, C.c_double))
     return prior
+
+
+def philox4x32(counter, key):
+    """One block of Philox4x32-10, the generator of Context.sample_batch (famseq_philox4x32_10): counter (4 words), key (2 words)
+    -> uint32[4].  Word w of the stream of site i's draw k under `seed` is element w % 4 of
+    philox4x32((i & 0xffffffff, i >> 32, k, w // 4), (seed & 0xffffffff, seed >> 32))."""
+    c = np.ascontiguousarray(counter, dtype=np.uint32)
+    k = np.ascontiguousarray(key, dtype=np.uint32)
+    if c.shape != (4,) or k.shape != (2,):
+        raise ValueError("counter must have 4 words and key 2")
+    out = np.empty(4, np.uint32)
+    lib().famseq_philox4x32_10(_p(c, C.c_uint32), _p(k, C.c_uint32), _p(out, C.c_uint32))
+    return out
 
 
 SEGREGATION_MASKS = {"dominant": (6, 1), "recessive": (4, 3)}  # model -> (affected, unaffected); anyone else 7
@@ -578,6 +597,41 @@ class Context:
         m = self._masks(masks, self.n)
         outs = lambda s: (np.empty((s, m.shape[0])) if want_post else None, np.empty(s) if want_loglik else None)
         return self._side_host("pattern", prior, lk, pl16, seq_members, flags, outs, (_p(m, C.c_uint8), m.shape[0]))
+
+    def _draw_args(self, n_draws, seed, site_base):
+        return (int(seed) & 0xFFFFFFFFFFFFFFFF, int(site_base), int(n_draws))
+
+    def _draw_outs(self, n_draws, want_gt, want_post):
+        k = max(int(n_draws), 0)  # (what the library refuses must reach it: no array is made too small)
+        return lambda s: (np.empty((s, k, self.n), np.int8) if want_gt else None, np.empty((s, k)) if want_post else None)
+
+    def sample_batch(self, n_draws, seed=0, site_base=0, lk=None, pl16=None, seq_members=None, flags=None, want_gt=True, want_post=True):
+        """Exact joint posterior draws: -> (gt[S,K,N] int8, post[S,K] float64, status[S] uint8), K = n_draws (1 .. 256).
+        gt[s, k] is a genotype configuration of the whole pedigree (PED order) drawn with probability w(g) / Z, post[s, k] that
+        probability; -1 / NaN where status != 0.  Distinct (site, draw) pairs are independent.  A draw depends on the pedigree, the
+        site's rows, seed, the site's absolute index site_base + s and k only: a batch cut into parts, each sampled with its
+        first site's index as site_base, gives the rows of the whole batch.  Input as map_batch."""
+        return self._side_host("sample", None, lk, pl16, seq_members, flags, self._draw_outs(n_draws, want_gt, want_post),
+                               self._draw_args(n_draws, seed, site_base))
+
+    def sample_prior_batch(self, prior, n_draws, seed=0, site_base=0, lk=None, pl16=None, seq_members=None, flags=None, want_gt=True,
+                           want_post=True):
+        """sample_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give sample_batch's bits."""
+        return self._side_host("sample", prior, lk, pl16, seq_members, flags, self._draw_outs(n_draws, want_gt, want_post),
+                               self._draw_args(n_draws, seed, site_base))
+
+    def sample_batch_device(self, n_sites, n_draws, seed=0, site_base=0, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_samp_gt=0,
+                            d_samp_post=0, d_status=0, stream=0):
+        """sample_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("sample", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_samp_gt, d_samp_post, d_status, stream,
+                          self._draw_args(n_draws, seed, site_base))
+
+    def sample_prior_batch_device(self, n_sites, d_prior, n_draws, seed=0, site_base=0, d_lk=0, d_pl16=0, seq_members=(), d_flags=0,
+                                  d_samp_gt=0, d_samp_post=0, d_status=0, stream=0):
+        """sample_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("sample", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_samp_gt, d_samp_post, d_status, stream,
+                          self._draw_args(n_draws, seed, site_base))
 
     def pattern_batch_device(self, n_sites, d_masks, n_patterns, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_pat_post=0, d_loglik=0,
                              d_status=0, stream=0):

@@ -762,10 +762,23 @@ int check_patterns(famseq_ctx *c, const PatternIn &pat, bool device) {
                                          " is " + std::to_string(pat.masks[i]) + "; a mask is 0..7 (bit g: genotype g allowed)");
   return 0;
 }
+// What the sampling entries take beside: the seed, the absolute index of the call's first site and the draws per site.
+struct SampleIn {
+  uint64_t seed;
+  int64_t site_base;
+  int32_t n_draws;
+};
+int check_sample(famseq_ctx *c, const SampleIn &smp) {
+  if (smp.n_draws < 1 || smp.n_draws > FAMSEQ_MAX_DRAWS)
+    return fail(c, FAMSEQ_E_ARG, "n_draws must be 1.." + std::to_string(FAMSEQ_MAX_DRAWS) + ", got " + std::to_string(smp.n_draws));
+  if (smp.site_base < 0) return fail(c, FAMSEQ_E_ARG, "site_base must be >= 0, got " + std::to_string(smp.site_base));
+  return 0;
+}
 int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device, const SideIn &in, const double *prior, void *out_a,
-               void *out_b, uint8_t *status, void *stream_ = nullptr, const PatternIn *pat = nullptr) {
+               void *out_b, uint8_t *status, void *stream_ = nullptr, const PatternIn *pat = nullptr, const SampleIn *smp = nullptr) {
   if (!c) return FAMSEQ_E_ARG;
   if (pat && check_patterns(c, *pat, device) != 0) return FAMSEQ_E_ARG;
+  if (smp && check_sample(c, *smp) != 0) return FAMSEQ_E_ARG;
   const SideProduct &p = side_table()[id];
   const int kind = p.kind_of(form, site_prior);
   const int64_t n_sites = in.n_sites;
@@ -780,9 +793,14 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
   // the arguments in front of the prior rows (the pattern kernels' masks and their number)
   const uint8_t *d_masks = pat ? pat->masks : nullptr;
   const int32_t n_patterns = pat ? pat->n_patterns : 1;
+  // ... or the sampling kernels' seed, site_base (the host path: per chunk, side_batch) and n_draws
+  const unsigned long seed = smp ? (unsigned long)smp->seed : 0;
+  const long site_base = smp ? long(smp->site_base) : 0;
+  const int32_t n_draws = smp ? smp->n_draws : 1;
+  const MoreArgs lead = pat ? MoreArgs{&d_masks, &n_patterns} : smp ? MoreArgs{&seed, &site_base, &n_draws} : MoreArgs{};
   if (!device) {
     size_t row[2];
-    p.rows(c->model, n_patterns, row);
+    p.rows(c->model, smp ? n_draws : n_patterns, row);
     if (pat) {
       // The masks go through a copy the context keeps into a buffer it owns, on the stream the chunks' kernels run on: ordered
       // with them by the stream itself.  (A host entry returns with its streams drained, so neither is in use by an earlier call.)
@@ -793,7 +811,7 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
       d_masks = c->d_masks.as<uint8_t>();
     }
     return side_batch(c, c->side_slots[id], c->kern[kind], n_sites, in.lk, in.pl16, in.n_seq, in.flags, out_a, row[0], out_b, row[1], status, prior,
-                      pat ? MoreArgs{&d_masks, &n_patterns} : MoreArgs{});
+                      lead, smp ? 1 : -1, site_base);
   }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const double *d_lk = in.lk;
@@ -808,7 +826,7 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
     d_lk = c->trio_dev_lk.as<double>();
     HIP_TRY(c, launch_unpack_pl16(in.pl16, c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, in.n_seq, n_sites, c->trio_dev_lk.as<double>(), stream));
   }
-  MoreArgs more = pat ? MoreArgs{&d_masks, &n_patterns} : MoreArgs{};
+  MoreArgs more = lead;
   more.at[more.n++] = &prior;  // (behind the last parameter of a plain form: not read)
   HIP_TRY(c, launch_generated(c, c->kern[kind], n_sites, d_lk, in.flags, out_a, out_b, status, stream, 0, more));
   return 0;
@@ -947,4 +965,54 @@ extern "C" int famseq_pattern_prior_batch_device(famseq_ctx *c, int64_t n_sites,
   const PatternIn pat{d_masks, n_patterns};
   return side_entry(c, SIDE_PATTERN, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_pat_post, d_loglik, d_status,
                     stream, &pat);
+}
+
+// ---- exact joint posterior draws: the MAP entries with the seed, the first site's absolute index and the draws per site -------
+
+extern "C" int famseq_sample_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                   int32_t n_seq, const uint8_t *flags, uint64_t seed, int64_t site_base, int32_t n_draws, int8_t *samp_gt,
+                                   double *samp_post, uint8_t *status) {
+  const SampleIn smp{seed, site_base, n_draws};
+  return side_entry(c, SIDE_SAMPLE, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, samp_gt, samp_post, status, nullptr,
+                    nullptr, &smp);
+}
+
+extern "C" int famseq_sample_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                          const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, uint64_t seed, int64_t site_base,
+                                          int32_t n_draws, int8_t *d_samp_gt, double *d_samp_post, uint8_t *d_status, void *stream) {
+  const SampleIn smp{seed, site_base, n_draws};
+  return side_entry(c, SIDE_SAMPLE, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_samp_gt, d_samp_post, d_status,
+                    stream, nullptr, &smp);
+}
+
+extern "C" int famseq_sample_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                         int32_t n_seq, const uint8_t *flags, const double *prior, uint64_t seed, int64_t site_base,
+                                         int32_t n_draws, int8_t *samp_gt, double *samp_post, uint8_t *status) {
+  const SampleIn smp{seed, site_base, n_draws};
+  return side_entry(c, SIDE_SAMPLE, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, samp_gt, samp_post, status, nullptr,
+                    nullptr, &smp);
+}
+
+extern "C" int famseq_sample_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                                const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                                uint64_t seed, int64_t site_base, int32_t n_draws, int8_t *d_samp_gt, double *d_samp_post,
+                                                uint8_t *d_status, void *stream) {
+  const SampleIn smp{seed, site_base, n_draws};
+  return side_entry(c, SIDE_SAMPLE, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_samp_gt, d_samp_post, d_status,
+                    stream, nullptr, &smp);
+}
+
+// The sampling kernels' generator on the host: the text they carry (philox_src.h), compiled here.
+namespace {
+#define FS_PHILOX_FN inline
+#define FS_PHILOX_DEF(...) __VA_ARGS__
+#include "philox_src.h"
+#undef FS_PHILOX_DEF
+#undef FS_PHILOX_FN
+}  // namespace
+
+extern "C" void famseq_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  unsigned o[4];
+  fs_philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], o);
+  for (int i = 0; i < 4; ++i) out[i] = o[i];
 }

@@ -398,7 +398,181 @@ class Emitter {
     return loop + o_.str();
   }
 
+  // Exact joint posterior draws (famseq_sample): nd_ configurations per site, each drawn with probability w(g) / Z, by the walk
+  // map_body's back-track takes with a weighted random choice in the place of every arg-max (forward filtering, backward sampling).
+  //   collect   map_body's sum pass: component_sums(), one root per component, only the messages that point towards a root.
+  //   rows      the member -> family messages of that pass (three doubles per member that is not a root) go to the lane's LDS row
+  //             sv[], where a run-time genotype indexes them (what the compiler makes of the row: sample_source).
+  //   walk      per draw: each root from its marginal, then the families in reverse message order (sum_steps_).  Given a parent the
+  //             other parent from v_other(g') prod_k a_k(g, g'); given a child the parent pair from the nine terms
+  //             T(g | gm, gf) v_mo(gm) v_fa(gf) prod_k a_k(gm, gf) in the order 3 gm + gf; each remaining child from
+  //             T(gc | gm, gf) v_c(gc).  The child summaries a_k at the genotypes at hand are formed again (three FMAs, the operands
+  //             read from LDS), never kept.
+  //   decision  fs_pick3 / fs_pick9: s the terms' sum left to right, t = u s, the first i with t < e_0 + ... + e_i, else the last
+  //             i with e_i > 0: products, sums and compares only.  A term of exactly 0 is never taken.
+  //   words     decision d of a draw, in emitted order, takes word d of the draw's Philox stream: element d % 4 of block d / 4
+  //             (counter (site, site >> 32, draw, block), key the seed's halves); u = (word + 0.5) 2^-32.
+  //   weight    the drawn configuration's w(g): the product of the members' factors at the drawn genotypes, scaled as Z is.
+  // Loops: inside the cut loop.  Assignment as_ of weight Wall: Zt_ += Wall, then draw k takes it where u(k, as_) Zt_ < Wall (the
+  // first of positive weight always, one of weight 0 never: streaming weighted selection; u(k, as_) is word D + as_ of the draw's
+  // stream, D the decisions of a draw) and runs the walk under that branch with the cut members at their assigned genotypes,
+  // overwriting its row and its weight in the outputs; the weights are divided by the final Zt_ behind the loop.
+  // Reads nd_, sp_ (the site's samp_post row or null), gg (its samp_gt rows or null), ilo_ / ihi_ / key0_ / key1_; sets bn_fail.
+  std::string sample_body() {
+    const bool loops = !g_.cut.empty();
+    if (!loops) {
+      component_sums();
+      o_ << "      const double Z_ = " << times_sums("") << ";\n";
+      fence(1);
+      o_ << "      if (!(Z_ > 0 && Z_ <= 1.79769313486231570815e308)) bn_fail = true;\n      else {\n";
+      sample_draws(false);
+      o_ << "      }\n";
+      return o_.str();
+    }
+    return cut_loop("      double Zt_ = 0;\n", /*wc=*/false, /*wall=*/true, [&] {
+             o_ << "      Zt_ = Zt_ + Wall;\n";
+             fence(1);
+             o_ << "      if (Wall > 0 && Wall <= 1.79769313486231570815e308) {\n";
+             sample_draws(true);
+             o_ << "      }\n";
+           }) +
+           "      if (!(Zt_ > 0 && Zt_ <= 1.79769313486231570815e308)) bn_fail = true;\n"
+           "      else if (sp_) {\n#pragma unroll 1\n        for (int k_ = 0; k_ < nd_; ++k_) sp_[k_] = sp_[k_] / Zt_;\n      }\n";
+  }
+  int sample_row_doubles() const { return 3 * (int)sv_at_.size(); }  // of the lane's LDS row (sample_body)
+  int sample_decisions() const { return n_dec_; }                    // D: the decision words of a draw
+
  private:
+  // member p's message to family F at the run-time genotype `g`: from the lane's row, or a cut member's indicator
+  std::string sv(int p, int F, const std::string &g) {
+    if (g_.is_cut(p)) return "(a" + num(p) + " == (int)(" + g + ") ? 1.0 : 0.0)";
+    const std::string key = "v" + num(p) + "f" + num(F);
+    if (!sv_at_.count(key)) {
+      const int at = 3 * (int)sv_at_.size();
+      sv_at_[key] = at;
+    }
+    return "sv[" + num(sv_at_[key]) + " + " + g + "]";
+  }
+  // transmission entry of child c at run-time genotypes (the lane's table in LDS)
+  std::string Tr(int c, const std::string &gc, const std::string &gm, const std::string &gf) const {
+    return "tcf[" + num(kind(c) * 27) + " + 9 * " + gc + " + 3 * " + gm + " + " + gf + "]";
+  }
+  // member p's likelihood and founder p's prior at the run-time genotype G<p>
+  std::string lk_at(int p) const {
+    const std::string G = "G" + num(p);
+    if (lean_ || p >= lean_from_) return "lgv[" + num(3 * p) + " + " + G + "]";
+    return "(" + G + " == 0 ? l" + num(p) + "_0 : (" + G + " == 1 ? l" + num(p) + "_1 : l" + num(p) + "_2))";
+  }
+  std::string prior_at(int p) const {
+    const std::string G = "G" + num(p);
+    if (!site_prior_) return "tcf[" + num(kind(p) * 27) + " + 9 * " + G + "]";
+    const std::string r = kind(p) == 0 ? "pm_" : "pa_";
+    return "(" + G + " == 0 ? " + r + "0 : (" + G + " == 1 ? " + r + "1 : " + r + "2))";
+  }
+
+  // sample_body's draw loop for the pedigree as it is, or (loops) for one assignment of the cut members
+  void sample_draws(bool loops) {
+    std::ostringstream w;  // one draw's walk
+    int D = 0;
+    auto next_u = [&]() {
+      const int d = D++;
+      if (d % 4 == 0) w << "          fs_philox4x32_10(ilo_, ihi_, (unsigned)k_, " << d / 4 << "u, key0_, key1_, rw_);\n";
+      return "FS_U01(rw_[" + num(d % 4) + "])";
+    };
+    w << "          unsigned rw_[4];\n          unsigned";
+    for (int p = 0; p < g_.N; ++p) w << (p ? ", " : " ") << "G" << p << " = " << (g_.is_cut(p) ? "(unsigned)a" + num(p) : std::string("0"));
+    w << ";\n";
+    for (size_t c = 0; c < g_.rep.size(); ++c) {
+      const int r = g_.rep[c];
+      const std::string u = next_u();
+      w << "          G" << r << " = fs_pick3(" << u << ", m" << r << "_0, m" << r << "_1, m" << r << "_2);\n";
+    }
+    for (size_t i = sum_steps_.size(); i-- > 0;) {
+      const int F = sum_steps_[i].F, t = sum_steps_[i].t;
+      const Family &fam = g_.fam[F];
+      const std::string gm = "G" + num(fam.mo), gf = "G" + num(fam.fa);
+      std::vector<int> kids;
+      for (int c : fam.kids)
+        if (c != t) kids.push_back(c);
+      w << "          {\n";
+      for (int c : kids)
+        w << "            const double x" << c << "_0 = " << sv(c, F, "0") << ", x" << c << "_1 = " << sv(c, F, "1") << ", x" << c
+          << "_2 = " << sv(c, F, "2") << ";\n";
+      // the other children's summaries at (a, b), multiplied on to `e` left to right
+      auto with_sums = [&](std::string e, const std::string &a, const std::string &b) {
+        for (int c : kids)
+          e = "(" + e + " * __builtin_fma(" + Tr(c, "2", a, b) + ", x" + num(c) + "_2, __builtin_fma(" + Tr(c, "1", a, b) + ", x" + num(c) +
+              "_1, " + Tr(c, "0", a, b) + " * x" + num(c) + "_0)))";
+        return e;
+      };
+      if (t == fam.mo || t == fam.fa) {
+        const int other = t == fam.mo ? fam.fa : fam.mo;
+        if (!g_.is_cut(other)) {
+          const std::string u = next_u();
+          for (int g = 0; g < 3; ++g)
+            w << "            const double e" << g << "_ = " << with_sums(sv(other, F, num(g)), t == fam.mo ? gm : num(g), t == fam.mo ? num(g) : gf)
+              << ";\n";
+          w << "            G" << other << " = fs_pick3(" << u << ", e0_, e1_, e2_);\n";
+        }
+      } else if (!(g_.is_cut(fam.mo) && g_.is_cut(fam.fa))) {
+        const std::string u = next_u();
+        w << "            double e_[9];\n";
+        for (int a = 0; a < 3; ++a)
+          for (int b = 0; b < 3; ++b)
+            w << "            e_[" << 3 * a + b << "] = "
+              << with_sums("((" + Tr(t, "G" + num(t), num(a), num(b)) + " * " + sv(fam.mo, F, num(a)) + ") * " + sv(fam.fa, F, num(b)) + ")", num(a), num(b))
+              << ";\n";
+        w << "            const unsigned pr_ = fs_pick9(" << u << ", e_);\n";
+        if (!g_.is_cut(fam.mo)) w << "            " << gm << " = (pr_ * 11u) >> 5;\n";  // pr_ / 3 for pr_ < 9
+        if (!g_.is_cut(fam.fa)) w << "            " << gf << " = pr_ - 3u * ((pr_ * 11u) >> 5);\n";
+      }
+      for (int c : kids)
+        if (!g_.is_cut(c)) {
+          const std::string u = next_u();
+          w << "            G" << c << " = fs_pick3(" << u << ", " << Tr(c, "0", gm, gf) << " * x" << c << "_0, " << Tr(c, "1", gm, gf) << " * x" << c
+            << "_1, " << Tr(c, "2", gm, gf) << " * x" << c << "_2);\n";
+        }
+      w << "          }\n";
+    }
+    n_dec_ = D;
+    // the configuration's weight, scaled as Z is (evidence_body's W0_ at run-time genotypes)
+    w << "          double w_ = 1.0;\n";
+    for (int c = 0; c < evidence_scale_digits() / 7; ++c) w << "          w_ = w_ * 10000000.0;\n";
+    for (int p = 0; p < g_.N; ++p)
+      w << "          w_ = w_ * (" << (m_.mother[p] < 0 ? prior_at(p) : Tr(p, "G" + num(p), "G" + num(m_.mother[p]), "G" + num(m_.father[p]))) << " * "
+        << lk_at(p) << ");\n";
+    w << "          if (sp_) sp_[k_] = " << (loops ? "w_" : "w_ / Z_") << ";\n";
+    // the row: from the lane, in 32-bit words where the row's first byte is 4-aligned, in bytes otherwise
+    const int nw = g_.N / 4;
+    w << "          if (gg) {\n            signed char *const d_ = gg + (long)k_ * " << g_.N << ";\n            int b_ = 0;\n";
+    if (nw > 0) {
+      w << "            if (((unsigned long)d_ & 3) == 0) {\n";
+      for (int k = 0; k < nw; ++k) {
+        w << "              ((unsigned *)d_)[" << k << "] = ";
+        for (int j = 0; j < 4; ++j) w << (j ? " | " : "") << "(G" << 4 * k + j << " << " << 8 * j << ")";
+        w << ";\n";
+      }
+      w << "              b_ = " << 4 * nw << ";\n            }\n";
+    }
+    for (int p = 0; p < g_.N; ++p) w << "            if (b_ <= " << p << ") d_[" << p << "] = (signed char)G" << p << ";\n";
+    w << "          }\n";
+    // the messages the walk reads, into the lane's row
+    for (const auto &kv : sv_at_)
+      for (int g = 0; g < 3; ++g) o_ << "        sw[" << kv.second + g << "] = " << kv.first << "_" << g << ";\n";
+    o_ << "#pragma unroll 1\n        for (int k_ = 0; k_ < nd_; ++k_) {\n";
+    if (loops) {
+      // (word D + as_ of the draw's stream)
+      o_ << "          unsigned rs_[4];\n"
+         << "          fs_philox4x32_10(ilo_, ihi_, (unsigned)k_, (unsigned)(" << D << " + as_) >> 2, key0_, key1_, rs_);\n"
+         << "          const unsigned el_ = (unsigned)(" << D << " + as_) & 3u;\n"
+         << "          const double us_ = FS_U01(el_ == 0 ? rs_[0] : (el_ == 1 ? rs_[1] : (el_ == 2 ? rs_[2] : rs_[3])));\n"
+         << "          if (!(Zt_ == Wall || us_ * Zt_ < Wall)) continue;\n";
+    }
+    o_ << w.str() << "        }\n";
+  }
+  std::map<std::string, int> sv_at_;  // sample_body: message name -> its first double in the lane's row
+  int n_dec_ = 0;
+
   // The cut-assignment loop of a pedigree with loops: `decls` (the accumulators) in front, then per assignment as_ of the cut
   // members their genotypes a<k>, their local factors lam<k> and Lam = 1e7 * prod lam<k>, every component's total weight Zc<c>
   // (component_sums), and where the caller uses them Wc<c> = Lam * prod_{c' != c} Zc<c'> (the weight of everything outside
@@ -573,6 +747,11 @@ class Emitter {
     std::vector<std::string> kid_bp;   // ... and their summaries' packed arg-maxes
   };
   std::vector<Step> steps_;
+  // the sum pass's family -> member messages in the order they were formed (sample_body walks them backwards)
+  struct SumStep {
+    int F, t;
+  };
+  std::vector<SumStep> sum_steps_;
 
   static std::string num(int x) { return std::to_string(x); }
   // Compiler fence: LDS reads (table entries, likelihoods) may not be hoisted above it.  Without
@@ -716,6 +895,7 @@ class Emitter {
       o_ << ";\n";
     }
     fence(1);
+    sum_steps_.push_back({F, t});
     return n;
   }
 
@@ -1188,6 +1368,101 @@ std::string pattern_source(const Model &m, int variant, bool site_prior) {
                "    if (loglik_g) __builtin_nontemporal_store(pt_ll, loglik_g + site);\n"
                "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.bt = elim_block_threads(m, false);
+  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  return lane_shell(m, d);
+}
+
+namespace {
+
+// What a sampling kernel carries in front of its entry: the Philox text (philox_src.h, the one the host exports), a word as a
+// uniform in (0, 1), and the decision among three and among nine non-negative terms (Emitter::sample_body).
+#define FS_PHILOX_DEF(...) #__VA_ARGS__
+const char kPhiloxText[] =
+#include "philox_src.h"
+    ;
+#undef FS_PHILOX_DEF
+const char kSampleHelpers[] = R"(
+#define FS_U01(x) (((double)(x) + 0.5) * (1.0 / 4294967296.0))
+static __device__ __forceinline__ unsigned fs_pick3(double u, double e0, double e1, double e2) {
+  const double p1 = e0 + e1, s = p1 + e2, t = u * s;
+  const unsigned last = e2 > 0.0 ? 2u : (e1 > 0.0 ? 1u : 0u);
+  return t < e0 ? 0u : (t < p1 ? 1u : (t < s ? 2u : last));
+}
+static __device__ __forceinline__ unsigned fs_pick9(double u, const double *e) {
+  double p[9];
+  p[0] = e[0];
+#pragma unroll
+  for (int i = 1; i < 9; ++i) p[i] = p[i - 1] + e[i];
+  const double t = u * p[8];
+  unsigned pick = 0;
+#pragma unroll
+  for (int i = 1; i < 9; ++i) pick = e[i] > 0.0 ? (unsigned)i : pick;
+#pragma unroll
+  for (int i = 8; i >= 0; --i) pick = t < p[i] ? (unsigned)i : pick;  /* the partial sums do not decrease: the first such i */
+  return pick;
+}
+)";
+
+}  // namespace
+
+// The sampling kernel: the MAP kernel's rules.  Beyond the common arguments: seed, site_base (the absolute index of the call's
+// first site) and n_draws (1 .. FAMSEQ_MAX_DRAWS; the host checks, the kernel clamps).  Outputs per site: samp_gt[n_draws][N]
+// (int8) and samp_post[n_draws] (fp64), status; any may be null.  A total weight that is not a positive finite number fails the
+// site (status 2): every genotype -1, every samp_post NaN.
+// The rows are stored from the lane as each draw ends — a loop pedigree's draw may be replaced by a later assignment, and K rows
+// per lane do not fit a stage in LDS beside the messages — in 32-bit words where a row starts 4-aligned, in bytes otherwise:
+// every store lies inside the site's n_draws * N bytes whatever the alignment of samp_gt.
+std::string sample_source(const Model &m, int variant, bool site_prior) {
+  const Graph g = graph_or_throw(m);
+  if (variant < 0 || variant >= kSampleVariants)
+    throw std::runtime_error("sample_source: variant must be 0.." + std::to_string(kSampleVariants - 1));
+  const int f = variant, N = m.n_members;
+  EmitOptions eo = emit_options(f, "pg", site_prior);
+  LaneShell d;
+  d.lean = eo.lean = N >= 40;  // as trio_source
+  d.bt = elim_block_threads(m, false);
+  Emitter e(m, g, eo);
+  d.body = e.sample_body();
+  const int vp = e.sample_row_doubles() | 1, D = e.sample_decisions();
+  // (the factor tables, the rows and what the compiler keeps for itself within the CU's 160 KB)
+  if (size_t(d.bt) * vp * sizeof(double) > size_t(150) << 10)
+    throw std::runtime_error("sample_source: the messages of " + std::to_string(N) + " members do not fit the lanes' LDS rows");
+  d.entry = "famseq_sample";
+  d.comment = describe("exact joint posterior draws (forward filtering, backward sampling)", g, std::to_string(f), site_prior) +
+              "\n// Random numbers: Philox4x32-10, key (seed, seed >> 32), counter (i, i >> 32, draw, block), i the site's absolute index."
+              "\n// Word w of a draw is element w % 4 of block w / 4; u = (word + 0.5) 2^-32 (one decision resolves 2^-32 of probability)."
+              "\n// Decision d of a draw takes word d, d counting in the order the walk is written below: the root of every component, then the"
+              "\n// families in reverse message order, in each the other parent or the parent pair, then its remaining children: D = " +
+              std::to_string(D) + " words." +
+              (g.cut.empty() ? "" : "\n// Assignment as_ of the conditioned members takes word D + as_ for its selection.");
+  d.outputs = "signed char *__restrict__ gt_g, double *__restrict__ post_g";
+  d.more_args = ", unsigned long seed, long site_base, int n_draws";
+  d.defines = "#define NMEM " + std::to_string(N) + "\n#define MAXDRAW " + std::to_string(FAMSEQ_MAX_DRAWS) + "\n#define VP " + std::to_string(vp) +
+              "\n#define FS_PHILOX_FN static __device__ __forceinline__\n" + kPhiloxText + "\n" + kSampleHelpers;
+  d.shared = "  __shared__ double s_v[BT * VP];  // the member -> family messages of the collect pass, one padded row per lane\n";
+  d.prologue = std::string() +
+               "  const unsigned key0_ = (unsigned)seed, key1_ = (unsigned)(seed >> 32);\n"
+               "  const int nd_ = n_draws < 0 ? 0 : (n_draws > MAXDRAW ? MAXDRAW : n_draws);\n"
+               "  double *const sw = s_v + tid * VP;\n" +
+               // Read through a plain pointer.  Under forty members hipcc then turns a read at a genotype of 0..2 into three reads and
+               // a select, forwards the stores, and keeps the messages in registers (the row takes no LDS at all); from forty on,
+               // where the likelihoods are volatile reads, it leaves them in the row.  Measured against reads forced to LDS through
+               // a volatile pointer, as lane_shell reads s_l (FAMSEQ_SAMPLE_ROWS=1, a tuning aid): the compiler's form is faster at
+               // every size tried — K = 8 draws of 2 M 32-member sites 1.92 ms against 2.97 (K = 1: 0.44 against 0.66), 10 M
+               // ten-member sites 2.35 against 2.46, 8 M trios 0.65 against 0.70 (profiles/sample/rate.txt).
+               (env_int("FAMSEQ_SAMPLE_ROWS", 0) != 0
+                    ? "  typedef const volatile __attribute__((address_space(3))) double smp_cvd;\n  smp_cvd *const sv = (smp_cvd *)sw;\n"
+                    : "  const double *const sv = sw;\n");
+  d.site_decls = "    signed char *gg = gt_g ? gt_g + site * nd_ * NMEM : nullptr;\n"
+                 "    double *sp_ = post_g ? post_g + site * nd_ : nullptr;\n"
+                 "    const unsigned long ai_ = (unsigned long)(site_base + site);\n"
+                 "    const unsigned ilo_ = (unsigned)ai_, ihi_ = (unsigned)(ai_ >> 32);\n";
+  d.epilogue =
+      "    if (single_fail || bn_fail) {\n"
+      "      if (gg) {\n#pragma unroll 1\n        for (int k = 0; k < nd_ * NMEM; ++k) gg[k] = (signed char)-1;\n      }\n"
+      "      if (sp_) {\n#pragma unroll 1\n        for (int k = 0; k < nd_; ++k) sp_[k] = kNaN;\n      }\n"
+      "    }\n"
+      "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
   return lane_shell(m, d);
 }

@@ -88,5 +88,15 @@ constexpr int kPatternVariants = 4;
 // site_prior: famseq_pattern_prior, with a trailing `prior` [n_sites][6] behind n_patterns (as trio_source's).
 std::string pattern_source(const Model &m, int variant, bool site_prior = false);
 
+// Exact joint posterior draws (famseq_sample_batch).  HIP source of
+// `extern "C" __global__ famseq_sample(lk, flags, samp_gt, samp_post, status, n_sites, tc, lc, seed, site_base, n_draws)`: per site
+// and draw k a joint configuration samp_gt[k][N] (int8, PED order) drawn with probability w(g) / Z and samp_post[k], that
+// probability: the sum pass of famseq_map, then per draw the walk of its back-track with a weighted random choice (Philox4x32-10,
+// counter (site_base + site, draw, block)) where that takes an arg-max.  variant 0..3: the fence levels of famseq_elim's; every
+// variant draws the same bits.  Throws if the engine does not serve the pedigree, or if its messages do not fit the lanes' LDS rows.
+constexpr int kSampleVariants = 4;
+// site_prior: famseq_sample_prior, with a trailing `prior` [n_sites][6] behind n_draws (as trio_source's).
+std::string sample_source(const Model &m, int variant, bool site_prior = false);
+
 }  // namespace famseq
 #endif

@@ -4,7 +4,7 @@
 //   FamSeq vcf -vcfFile f -pedFile p -output o [-v] [-a] [-d] [-o] [-l loc] [-method 1]
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
 //              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-loo] [-afTag KEY | -afTagAll KEY]
-//              [-seg dominant|recessive|both -affected ID[,ID...] [-unaffected ID[,ID...]]]
+//              [-seg dominant|recessive|both -affected ID[,ID...] [-unaffected ID[,ID...]]] [-sample K [-seed S]]
 //   FamSeq LK  -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -23,7 +23,8 @@
 // -siteQ (vcf mode) the family's variant quality and the site's log10 likelihood under the pedigree to the INFO column (FQ, FLL),
 // -loo (vcf mode) each sample's leave-one-out genotype probabilities and fit (LOP, LOF), and -seg (vcf mode) the posterior probability
 // that the variant segregates with the phenotype of the members named by -affected / -unaffected, under a dominant and / or a
-// recessive model, to the INFO column (PSD, PSR).
+// recessive model, to the INFO column (PSD, PSR), and -sample K (vcf mode) each sample's alt-allele counts in K joint configurations
+// of the family drawn from their posterior (SGT).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -196,6 +197,8 @@ struct Options {
   bool map = false;  // -map: JGT and JP fields per sample (vcf mode)
   bool siteq = false;  // -siteQ: FQ and FLL keys in the INFO column (vcf mode)
   bool loo = false;    // -loo: LOP and LOF fields per sample, the leave-one-out posteriors and the member's fit (vcf mode)
+  int sample = 0;      // -sample K: an SGT field per sample, its alt-allele counts in K joint posterior draws of the family (vcf mode)
+  uint64_t seed = 0;   // -seed S: the draws' seed
   // -seg dominant|recessive|both: PSD and / or PSR keys in the INFO column (vcf mode), the posterior probability of the genotype
   // pattern that model gives the members of -affected and -unaffected (PED IDs, comma-separated)
   string seg, affected, unaffected;
@@ -337,6 +340,23 @@ int parse_options(int argc, char **argv, Options &o) {
       o.siteq = true;
     } else if (opt == "loo") {
       o.loo = true;
+    } else if (opt == "sample" || opt == "seed") {
+      i++;
+      if (missing(i)) {
+        std::cout << "The value of -" << opt << " hasn't been set. The option is ignored." << std::endl;
+        i--;
+        rv = 1;
+      } else if (opt == "seed") {
+        o.seed = std::strtoull(argv[i], nullptr, 10);
+      } else {
+        o.sample = std::atoi(argv[i]);
+        if (o.sample < 1 || o.sample > FAMSEQ_MAX_DRAWS) {
+          std::cout << "-sample takes the number of draws per site, 1.." << FAMSEQ_MAX_DRAWS << ", not \"" << argv[i] << "\". The option is ignored."
+                    << std::endl;
+          o.sample = 0;
+          rv = 1;
+        }
+      }
     } else if (opt == "seg" || opt == "affected" || opt == "unaffected") {
       i++;
       if (missing(i)) {
@@ -1350,6 +1370,9 @@ bool run_vcf(const Options &o, const Ped &ped) {
       fout << "##FORMAT=<ID=LOF,Number=1,Type=Float,Description=\"Phred-scaled predictive likelihood of the sample's data given the "
               "other members' (99999: impossible given the relatives)\">" << std::endl;
     }
+    if (o.sample)
+      fout << "##FORMAT=<ID=SGT,Number=.,Type=Integer,Description=\"Alternate allele counts of the sample in " << o.sample
+           << " joint genotype configurations of the whole family drawn from their posterior (seed " << o.seed << ")\">" << std::endl;
     if (!o.seg.empty()) {
       if (o.seg != "recessive")
         fout << "##INFO=<ID=PSD,Number=1,Type=Float,Description=\"Posterior probability that the affected members, and no unaffected one, "
@@ -1649,6 +1672,9 @@ bool run_vcf(const Options &o, const Ped &ped) {
     vector<uint8_t> estatus;   // ... and the evidence kernel's status per site
     vector<double> loo, fit;   // -loo: [site][member][3] leave-one-out posteriors, [site][member] the members' fit ...
     vector<uint8_t> lstatus;   // ... and the leave-one-out kernel's status per site
+    vector<int8_t> sgt;        // -sample: [site][draw][member] the drawn configurations ...
+    vector<uint8_t> sstatus;   // ... and the sampling kernel's status per site
+    int64_t site_base = 0;     // ... the block's first site among the sites of the file
     vector<double> ppat;       // -seg: [site][pattern] the patterns' posteriors ...
     vector<uint8_t> pstatus;   // ... and the pattern kernel's status per site
   } slots[4];  // one being cut and parsed, one at the GPU, one being formatted, one being written
@@ -1726,6 +1752,19 @@ bool run_vcf(const Options &o, const Ped &ped) {
           sl.loo.resize(sl.n_sites * size_t(ped.n()) * 3), sl.fit.resize(sl.n_sites * size_t(ped.n()));
           side(famseq_loo_batch, famseq_loo_prior_batch, sl.loo.data(), sl.fit.data(), sl.lstatus, "famseq_loo");
         }
+        if (o.sample && flush_ok) {  // (seed, the block's first site and the draws ride between the input and the outputs)
+          sl.sgt.resize(sl.n_sites * size_t(o.sample) * size_t(ped.n()));
+          const uint64_t seed = o.seed;
+          const int64_t base = sl.site_base;
+          const int32_t nd = o.sample;
+          side([=](famseq_ctx *c, int64_t n, const double *lk, const uint16_t *pl, const int32_t *seq, int32_t ns, const uint8_t *fl, int8_t *a,
+                   double *b, uint8_t *st) { return famseq_sample_batch(c, n, lk, pl, seq, ns, fl, seed, base, nd, a, b, st); },
+               [=](famseq_ctx *c, int64_t n, const double *lk, const uint16_t *pl, const int32_t *seq, int32_t ns, const uint8_t *fl,
+                   const double *prior, int8_t *a, double *b, uint8_t *st) {
+                 return famseq_sample_prior_batch(c, n, lk, pl, seq, ns, fl, prior, seed, base, nd, a, b, st);
+               },
+               sl.sgt.data(), (double *)nullptr, sl.sstatus, "famseq_sample");
+        }
         if (n_seg && flush_ok) {  // (the masks ride between the input and the outputs of both entries)
           sl.ppat.resize(sl.n_sites * n_seg);
           const uint8_t *mk = seg_masks.data();
@@ -1783,6 +1822,22 @@ bool run_vcf(const Options &o, const Ped &ped) {
         out.ch(g < 2 ? ',' : ':');
       }
       out.num(phred(sl.fit[mem]));
+    }
+    out.ch('\t');
+  };
+  // -sample: ":<SGT>" before the closing tab of sample j's field, the draws' alt-allele counts comma-separated, draw 0 first — NA
+  // where the site or its sampling kernel failed
+  auto put_sgt = [&](TextBuf &out, const Slot &sl, size_t s, size_t j, bool failed) {
+    --out.n;
+    out.ch(':');
+    if (failed || sl.sstatus[s] != 0) {
+      out.put("NA", 2);
+    } else {
+      const int8_t *g = &sl.sgt[s * size_t(o.sample) * size_t(ped.n()) + size_t(seq_members[j])];
+      for (int k = 0; k < o.sample; ++k) {
+        if (k) out.ch(',');
+        out.ch(char('0' + g[size_t(k) * size_t(ped.n())]));
+      }
     }
     out.ch('\t');
   };
@@ -1847,6 +1902,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
               if (o.dnm) out.put(":DNP", 4);
               if (o.map) out.put(":JGT:JP", 7);
               if (o.loo) out.put(":LOP:LOF", 8);
+              if (o.sample) out.put(":SGT", 4);
               out.ch('\t');
               if (sl.io.status[s] & 3) {  // file.cpp:607-620
                 pt.any_failed = true;
@@ -1856,6 +1912,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
                   if (o.dnm) put_dnp(out, sl, s, j, true);
                   if (o.map) put_map(out, sl, s, j, true);
                   if (o.loo) put_loo(out, sl, s, j, true);
+                  if (o.sample) put_sgt(out, sl, s, j, true);
                 }
               } else {
                 for (size_t j = 0; j < k; ++j) {
@@ -1875,6 +1932,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
                   if (o.dnm) put_dnp(out, sl, s, j, false);
                   if (o.map) put_map(out, sl, s, j, false);
                   if (o.loo) put_loo(out, sl, s, j, false);
+                  if (o.sample) put_sgt(out, sl, s, j, false);
                 }
               }
             }
@@ -1918,6 +1976,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
   const double t_begin = now_s();
   to_driver.put(0), to_driver.put(1), to_driver.put(2), to_driver.put(3);
   bool more = have_line;
+  uint64_t sites_before = 0;  // sites of the blocks cut so far
   while (more && ok && flush_ok) {
     double t0 = now_s();
     const int i = to_driver.take();  // a slot whose previous block is written
@@ -1999,7 +2058,8 @@ bool run_vcf(const Options &o, const Ped &ped) {
     size_t n_real = 0;
     for (int t = 0; t < sl.n_parts; ++t)
       for (const Item &it : sl.parts[t].items) n_real += it.site >= 0;
-    if (n_real > 0 && n_real < nl && ped.n() >= compact_from) {
+    // (-sample: always, so that a site's position in the batch is its position among the block's sites)
+    if (n_real > 0 && n_real < nl && (ped.n() >= compact_from || o.sample)) {
       size_t d = 0;
       for (int t = 0; t < sl.n_parts; ++t) {
         Part &pt = sl.parts[t];
@@ -2018,6 +2078,8 @@ bool run_vcf(const Options &o, const Ped &ped) {
       }
       sl.n_sites = d;
     }
+    sl.site_base = (int64_t)sites_before;  // -sample: a site's index is its ordinal among the file's sites, whatever the blocks
+    sites_before += n_real;
     if (!packed) {
       // fp64 rows: the table's value for every integer field (what the parser computed for it), the parsed rows of the others
       const size_t n = sl.n_sites;
@@ -2205,6 +2267,10 @@ void help() {
             << "-loo\t\t(vcf) Add LOP, the sample's Phred-scaled genotype probabilities given every other member's data with its own" << std::endl
             << "\t\tleft out, and LOF, the Phred-scaled likelihood of its own data given theirs (99999: impossible given the relatives)," << std::endl
             << "\t\tto every sample column. Implies -method 2; may be combined with -dnm, -map, -siteQ and -afTagAll; not with -afTag." << std::endl
+            << "-sample K\t(vcf) Add SGT, the sample's alt-allele counts in K (1.." << FAMSEQ_MAX_DRAWS << ") joint genotype configurations of the whole" << std::endl
+            << "\t\tfamily drawn from their posterior, draw 0 first; -seed S (default 0) seeds them. A line's draws depend on the seed" << std::endl
+            << "\t\tand on its ordinal among the file's sites, not on FAMSEQ_BATCH. May be combined with -dnm, -map, -siteQ, -loo, -seg" << std::endl
+            << "\t\tand -afTagAll; not with -afTag." << std::endl
             << "-seg MODEL\t(vcf) MODEL dominant, recessive or both, with -affected ID[,ID...] and optionally -unaffected ID[,ID...] (PED IDs):" << std::endl
             << "\t\tadd PSD (dominant: the affected carry the variant, the unaffected do not) and / or PSR (recessive: the affected are" << std::endl
             << "\t\thomozygous for it, the unaffected are not), the posterior probability of that pattern given the whole family's data," << std::endl
@@ -2276,6 +2342,11 @@ int main(int argc, char **argv) {
     o.loo = false;
   }
   if (o.loo && !sum_product_serves(o, ped, "-loo")) return 255;
+  if (o.sample && mode != "vcf") {
+    std::cout << "-sample applies to vcf mode only; ignored here." << std::endl;
+    o.sample = 0;
+  }
+  if (o.sample && !sum_product_serves(o, ped, "-sample")) return 255;
   if ((!o.seg.empty() || !o.affected.empty() || !o.unaffected.empty()) && mode != "vcf") {
     std::cout << "-seg applies to vcf mode only; ignored here." << std::endl;
     o.seg.clear(), o.affected.clear(), o.unaffected.clear();
@@ -2298,7 +2369,7 @@ int main(int argc, char **argv) {
     if (mode != "vcf") {
       std::cout << (o.af_all ? "-afTagAll" : "-afTag") << " applies to vcf mode only; ignored here." << std::endl;
       o.af_tag.clear();
-    } else if (!o.af_all && (o.dnm || o.map || o.siteq || o.loo || !o.seg.empty())) {
+    } else if (!o.af_all && (o.dnm || o.map || o.siteq || o.loo || o.sample || !o.seg.empty())) {
       std::cout << "-afTag cannot be combined with -dnm or -map: their kernels use the model's priors, and one output line must not mix two models."
                 << std::endl;
       return -1;

@@ -31,7 +31,8 @@ struct ChunkJob {
   }
 };
 // Enqueues a chunk's kernels — n sites in slot s — on the compute stream; 0 or the error code (message set).
-using Stage = std::function<int(int s, int64_t n, hipStream_t stream)>;
+// (lo: the chunk's first site in the call)
+using Stage = std::function<int(int s, int64_t n, hipStream_t stream, int64_t lo)>;
 
 // Default chunk: at most 64 MiB per array of `row` bytes per site, at least four chunks per call so that the stages
 // overlap, but not below the batch size the lane-per-site kernel needs to fill the chip.
@@ -74,7 +75,7 @@ int run_chunks(famseq_ctx *c, SlotSet &t, const ChunkJob &job, const Stage &stag
     HIP_TRY(c, hipEventRecord(c->ev_in[s], s_in));
     // compute
     HIP_TRY(c, hipStreamWaitEvent(s_k, c->ev_in[s], 0));
-    const int rc = stage(s, n, s_k);
+    const int rc = stage(s, n, s_k, lo);
     if (rc != 0) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_done[s], s_k));
     // copy out
@@ -174,7 +175,7 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
   job.copy_out(B_POST, row, io.post);
   job.copy_out(B_SINGLE, row, io.single);
   job.copy_out(B_STATUS, 1, io.status);
-  rc = run_pipeline(c, t, job, [&](int s, int64_t n, hipStream_t s_k) -> int {
+  rc = run_pipeline(c, t, job, [&](int s, int64_t n, hipStream_t s_k, int64_t) -> int {
     DevBuf *d = t.buf[s];
     const double *d_prior = d[B_PRIOR].as<double>();
     double *d_lk = d[B_LK].as<double>(), *d_post = d[B_POST].as<double>(), *d_single = d[B_SINGLE].as<double>();
@@ -220,7 +221,8 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
 // ... and the trio and MAP entries (plain and site-prior): per chunk [unpack] -> kernel, on the entry's own set of slots.  out_a / out_b: the two
 // per-site outputs (NULL: not wanted), a_row / b_row their bytes per site (0: the pedigree has none).
 int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
-               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior, const MoreArgs &lead) {
+               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior, const MoreArgs &lead,
+               int base_at, int64_t site_base) {
   const int N = c->model.n_members;
   const size_t row = size_t(3) * N * sizeof(double), pl_row = pl16 ? size_t(n_seq) * 3 * sizeof(uint16_t) : 0;
   const size_t prior_row = prior ? 6 * sizeof(double) : 0;
@@ -239,12 +241,14 @@ int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, c
   job.copy_out(B_OUT_A, a_row, out_a);
   job.copy_out(B_OUT_B, b_row, out_b);
   job.copy_out(B_STATUS, 1, status);
-  return run_pipeline(c, t, job, [&](int s, int64_t n, hipStream_t s_k) -> int {
+  return run_pipeline(c, t, job, [&](int s, int64_t n, hipStream_t s_k, int64_t lo) -> int {
     DevBuf *d = t.buf[s];
     if (pl16)
       HIP_TRY(c, launch_unpack_pl16(d[B_PL].as<uint16_t>(), c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, n_seq, n, d[B_LK].as<double>(), s_k));
     const void *d_prior = prior ? d[B_PRIOR].p : nullptr;
     MoreArgs more = lead;
+    const long chunk_base = long(site_base + lo);  // (read when the launch is enqueued)
+    if (base_at >= 0) more.at[base_at] = const_cast<long *>(&chunk_base);
     more.at[more.n++] = &d_prior;  // (behind the last parameter of a plain form: not read)
     HIP_TRY(c, launch_generated(c, g, n, d[B_LK].as<double>(), flags ? d[B_FLAGS].as<uint8_t>() : nullptr, out_a ? d[B_OUT_A].p : nullptr,
                                 out_b ? d[B_OUT_B].p : nullptr, status ? d[B_STATUS].as<uint8_t>() : nullptr, s_k, 0, more));

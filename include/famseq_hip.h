@@ -509,6 +509,53 @@ int famseq_pattern_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const do
                                       const uint8_t *d_masks, int32_t n_patterns, double *d_pat_post, double *d_loglik,
                                       uint8_t *d_status, void *stream);
 
+/* ---- exact joint posterior draws -----------------------------------------------------------------------------------------
+ * n_draws joint genotype configurations per site, each drawn from the posterior of the whole pedigree: for any statistic of the
+ * family that is not one of the closed forms above (carrier counts, transmitted alleles, burden over sites), with the family's
+ * dependence intact.  One collect pass of the sum-product messages, then per draw a backward pass that chooses where the MAP
+ * kernel maximises: exact, independent draws, no burn-in, for every pedigree the sum-product engine serves.
+ *   samp_gt  [n_sites][n_draws][N] int8   configuration g drawn with probability w(g) / Z (w as for the evidence), PED order.
+ *   samp_post[n_sites][n_draws] fp64      w(g) / Z of the configuration drawn.
+ *   status   [n_sites]      0 OK; 1 the single-posterior failure rule of famseq_bn_batch; 2 the total weight Z is <= 0 or not
+ *              finite.  Wherever status != 0 every genotype of the site is -1 and every samp_post NaN.  No -LRC shortcut.
+ *   seed, site_base, n_draws   Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (i & 0xffffffff, i >> 32, k, j):
+ *              i = site_base + the site's position in the call, k the draw, j the block; word w of the stream of (site, draw)
+ *              is element w % 4 of block w / 4 and becomes u = (word + 0.5) 2^-32.  A draw is a function of the pedigree, the
+ *              site's inputs, seed, i and k alone: not of the batch, the chunking, the launch or n_draws (draw 3 of 4 is draw 3
+ *              of 32).  A caller that splits a batch passes each part its first site's index as site_base and gets the whole
+ *              batch's rows.  One decision resolves 2^-32 of probability; a term of exactly 0 is never drawn (at mutation rate
+ *              0 every draw is Mendelian-consistent).  n_draws: 1 .. FAMSEQ_MAX_DRAWS; site_base >= 0.
+ * The kernel (famseq_sample) is compiled on the first call or ahead through famseq_set_option "sample_kernels" = 1;
+ * famseq_plan_json: "sample_code_object", "sample_variant".  FAMSEQ_E_ARG, with a message and before the device is asked for:
+ * n_draws outside 1 .. FAMSEQ_MAX_DRAWS, site_base < 0.  Pedigrees beyond about a hundred members, whose messages do not fit
+ * the lanes' LDS rows, get FAMSEQ_E_HIP with the generator's message. */
+#define FAMSEQ_MAX_DRAWS 256
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_map_batch.  Any of samp_gt / samp_post / status may be NULL. */
+int famseq_sample_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                        int32_t n_seq, const uint8_t *flags, uint64_t seed, int64_t site_base, int32_t n_draws, int8_t *samp_gt,
+                        double *samp_post, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
+ * NULL = the default stream) and returns without synchronising. */
+int famseq_sample_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                               const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, uint64_t seed, int64_t site_base,
+                               int32_t n_draws, int8_t *d_samp_gt, double *d_samp_post, uint8_t *d_status, void *stream);
+
+/* With the founders' genotype prior given per site: prior[n_sites][6], as for famseq_map_prior_batch.  Given rows that equal the
+ * model's constants the outputs are, bit for bit, famseq_sample_batch's.  "sample_prior_kernels" = 1 builds the kernel
+ * (famseq_sample_prior) ahead; famseq_plan_json: "sample_prior_code_object", "sample_prior_variant". */
+int famseq_sample_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                              int32_t n_seq, const uint8_t *flags, const double *prior, uint64_t seed, int64_t site_base,
+                              int32_t n_draws, int8_t *samp_gt, double *samp_post, uint8_t *status);
+int famseq_sample_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                     const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                     uint64_t seed, int64_t site_base, int32_t n_draws, int8_t *d_samp_gt, double *d_samp_post,
+                                     uint8_t *d_status, void *stream);
+
+/* The generator of the entries above, one block: Philox4x32-10 of counter ctr under key -> out (Random123's known answers). */
+void famseq_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+
 /* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] = ((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);
