@@ -32,7 +32,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
-#include <functional>
 #include <future>
 #include <iostream>
 #include <charconv>
@@ -122,6 +121,17 @@ struct TextBuf {
     std::memcpy(p, r, FAMSEQ_TEXT_STRIDE);
     n += size_t((unsigned char)r[FAMSEQ_TEXT_STRIDE - 1]);
   }
+  // Called sample `at` (site * samples + column) of a batch, from the device's records or, where text is null, from its numbers.
+  // tab = false leaves the closing tab to the caller, who has more fields to put in front of it.
+  void called(const char *text, const double *gpp, const double *fpp, const int8_t *fgt, size_t at, bool tab = true) {
+    if (text) {
+      record(text + at * FAMSEQ_TEXT_STRIDE);
+      n -= !tab;
+    } else {
+      triples(gpp + 3 * at, fpp + 3 * at);
+      put(fgt[at] == 0 ? "0/0\t" : (fgt[at] == 1 ? "0/1\t" : "1/1\t"), tab ? 4 : 3);
+    }
+  }
 };
 
 // Where the numbers become text: on the device (default — one more streaming kernel behind the call kernel, a record per
@@ -156,25 +166,6 @@ struct PlTable {
     return std::pow(10.0, -std::fabs(x) / 10.0);
   }
 };
-
-// Text formatting is the slowest part of the pipeline (printf-style %g per number); the records
-// of a flushed batch are independent, so they are formatted on all host cores and written in order.
-template <class F>
-void parallel_for(size_t n, F f) {
-  unsigned t = std::thread::hardware_concurrency();
-  if (const char *e = std::getenv("FAMSEQ_THREADS")) t = (unsigned)std::atoi(e);
-  t = std::max(1u, std::min(t, 32u));
-  if (n < 2048 || t == 1) {
-    for (size_t i = 0; i < n; ++i) f(i);
-    return;
-  }
-  vector<std::thread> pool;
-  for (unsigned k = 0; k < t; ++k)
-    pool.emplace_back([=] {
-      for (size_t i = n * k / t, e = n * (k + 1) / t; i < e; ++i) f(i);
-    });
-  for (std::thread &th : pool) th.join();
-}
 
 // ---- options -----------------------------------------------------------------------------
 
@@ -474,6 +465,40 @@ bool read_ped(const string &path, Ped &p) {  // file.cpp:24-62
   return true;
 }
 
+// The sample columns of an input matched to PED members by name (file.cpp:200-232, :1671-1689: a column takes the first member
+// of its name); columns that are not in the PED are ignored.
+struct ColumnMap {
+  vector<int> member;         // [column] its PED index, -1: not in the PED
+  vector<uint8_t> sequenced;  // [PED index] some column is this member's
+  vector<int> cols;           // the matched columns in input order ...
+  vector<int32_t> members;    // ... and their PED indices
+};
+
+ColumnMap map_columns(const string *names, size_t n, const Ped &ped) {
+  ColumnMap cm;
+  cm.member.assign(n, -1);
+  cm.sequenced.assign(ped.n(), 0);
+  for (size_t i = 0; i < n; i++)
+    for (int j = 0; j < ped.n(); j++)
+      if (names[i] == ped.name[j]) {
+        cm.member[i] = j;
+        cm.sequenced[j] = 1;
+        cm.cols.push_back((int)i);
+        cm.members.push_back(j);
+        break;
+      }
+  return cm;
+}
+
+// The header lines of the three fields every driver adds; GPP's description names the method in the spelling of its driver.
+void put_format_header(std::ostream &out, const char *gpp_by) {
+  out << "##FORMAT=<ID=GPP,Number=G,Type=Integer,Description=\"Normalized, Phred-scaled for posterior probability " << gpp_by << "\">"
+      << std::endl;
+  out << "##FORMAT=<ID=FPP,Number=G,Type=Integer,Description=\"Normalized, Phred-scaled for posterior probability "
+         "calculated by FamSeqPro\">" << std::endl;
+  out << "##FORMAT=<ID=FGT,Number=1,Type=String,Description=\"Genotype called by FamSeqPro\">" << std::endl;
+}
+
 // ---- batched caller: queue of output records, flushed through the GPU in order -------------
 
 struct Record {
@@ -505,6 +530,12 @@ int parallel_ranges(size_t n, F f) {
   for (std::thread &th : pool) th.join();
   return (int)t;
 }
+template <class F>
+void parallel_for(size_t n, F f) {
+  parallel_ranges(n, [&](size_t lo, size_t hi, int) {
+    for (size_t i = lo; i < hi; ++i) f(i);
+  });
+}
 
 // Queue of output records between the LK driver's line loop and the GPU (the vcf driver has its own block
 // pipeline, run_vcf).  Records are kept in input order; a full batch is handed to a flusher thread — GPU call
@@ -513,7 +544,7 @@ int parallel_ranges(size_t n, F f) {
 class BatchCaller {
  public:
   double t_gpu = 0, t_format = 0, t_write = 0, t_stall = 0;  // FAMSEQ_TIMING: where the flusher spends its time; driver waiting for it
-  BatchCaller(famseq_ctx *ctx, int n_members, const vector<int> &seq_members, std::ostream &out, size_t cap)
+  BatchCaller(famseq_ctx *ctx, int n_members, const vector<int32_t> &seq_members, std::ostream &out, size_t cap)
       : ctx_(ctx), n_(n_members), seq_(seq_members.begin(), seq_members.end()), out_(out), cap_(cap) {}
   ~BatchCaller() { wait(); }
 
@@ -616,7 +647,6 @@ class BatchCaller {
             }
           } else {
             for (size_t j = 0; j < k; ++j) {
-              const int gt = fgt_[size_t(r.site) * k + j];
               const Record::Sample &sm = r.samples[j];
               if (sm.missing) {
                 for (uint32_t q = 0; q < r.n_fmt; ++q) line.put("NA:", 3);
@@ -624,8 +654,7 @@ class BatchCaller {
                 line.put(r.raw.data() + sm.off, sm.len);
                 line.ch(':');
               }
-              line.triples(&gpp_[(size_t(r.site) * k + j) * 3], &fpp_[(size_t(r.site) * k + j) * 3]);
-              line.put(gt == 0 ? "0/0\t" : (gt == 1 ? "0/1\t" : "1/1\t"), 4);
+              line.called(nullptr, gpp_.data(), fpp_.data(), fgt_.data(), size_t(r.site) * k + j);
             }
           }
         }
@@ -677,6 +706,12 @@ struct CliModel {
     return famseq_pedigree_init(&p, ped.n(), ped.id.data(), ped.mid.data(), ped.fid.data(), ped.gender.data(), seq.data(), mrate,
                                 lrc, mo.data(), fa.data());
   }
+  void set_priors(const Options &o) {  // -genoProbN ...: the ones that were given
+    const vector<double> *src[4] = {&o.gN, &o.gK, &o.gXN, &o.gXK};
+    double *dst[4] = {p.genoProbN, p.genoProbK, p.genoProbXN, p.genoProbXK};
+    for (int k = 0; k < 4; ++k)
+      if (src[k]->size() == 3) std::copy(src[k]->begin(), src[k]->end(), dst[k]);
+  }
 };
 
 famseq_ctx *make_ctx(const Options &o, const Ped &ped, const vector<uint8_t> &sequenced, CliModel &m) {
@@ -687,13 +722,7 @@ famseq_ctx *make_ctx(const Options &o, const Ped &ped, const vector<uint8_t> &se
     std::cout << "Cannot initiate family. Please check ped file." << std::endl;
     return nullptr;
   }
-  auto put = [](double *dst, const vector<double> &src) {
-    if (src.size() == 3) std::copy(src.begin(), src.end(), dst);
-  };
-  put(m.p.genoProbN, o.gN);
-  put(m.p.genoProbK, o.gK);
-  put(m.p.genoProbXN, o.gXN);
-  put(m.p.genoProbXK, o.gXK);
+  m.set_priors(o);
   const char *dev = std::getenv("FAMSEQ_DEVICE");
   char err[512] = {0};
   if (ped.n() > FAMSEQ_MAX_MEMBERS && o.method != 2) {  // the reference's own advice for -method 1 is "family size less than seven"
@@ -796,6 +825,16 @@ double info_af(std::string_view info, const string &key) {
 }
 
 void put_triple(std::ostream &o, const double *p) { o << p[0] << ":" << p[1] << ":" << p[2]; }
+
+// the header of the LK and PL drivers' text: the columns `cols` of `names` are the samples'
+void put_lk_header(std::ostream &out, const Options &o, const CliModel &m, const vector<string> &names, const vector<int> &cols) {
+  put_format_header(out, "calculated by individual-base Method");
+  out << "##FS mutation rate=" << o.mrate << " " << std::endl;
+  out << "##FS genotype frequency in pupulation: "; put_triple(out, m.p.genoProbN); out << std::endl;
+  out << "#FORMAT\t";
+  for (int c : cols) out << names[c] << '\t';
+  out << std::endl;
+}
 
 // ---- packed PL file (row N4 of SURVEY.md 8(f)): the text-free feed for the GPU ---------------
 //   bytes 0-7   "FSPL0001"
@@ -958,28 +997,12 @@ bool run_pl(const Options &o, const Ped &ped) {
     fin.read(buf, 32);
     names[i] = buf;
   }
-  // columns -> PED members (file.cpp:1671-1689); columns that are not in the PED are ignored
-  vector<int> col_member(n_seq, -1);
-  vector<uint8_t> sequenced(ped.n(), 0);
-  for (uint32_t i = 0; i < n_seq; i++)
-    for (int j = 0; j < ped.n(); j++)
-      if (names[i] == ped.name[j]) {
-        col_member[i] = j;
-        sequenced[j] = 1;
-        break;
-      }
-  vector<int32_t> seq_members;
-  vector<uint32_t> seq_cols;
-  for (uint32_t i = 0; i < n_seq; i++)
-    if (col_member[i] >= 0) {
-      seq_cols.push_back(i);
-      seq_members.push_back(col_member[i]);
-    }
-  if (seq_members.empty()) {
+  const ColumnMap cm = map_columns(names.data(), n_seq, ped);
+  if (cm.members.empty()) {
     std::cout << "No sample of " << o.pl_file << " is in the ped file." << std::endl;
     return false;
   }
-  const size_t k = seq_members.size();
+  const size_t k = cm.members.size();
 
   // unpack mode: the results come from a packed result file instead of the GPU
   std::ifstream fpo;
@@ -999,7 +1022,7 @@ bool run_pl(const Options &o, const Ped &ped) {
     for (size_t j = 0; j < k; j++) {
       char buf[33] = {0};
       fpo.read(buf, 32);
-      if (names[seq_cols[j]] != buf) {
+      if (names[cm.cols[j]] != buf) {
         std::cout << o.po_file << " was written for other samples than " << o.pl_file << " holds." << std::endl;
         return false;
       }
@@ -1009,14 +1032,14 @@ bool run_pl(const Options &o, const Ped &ped) {
   CliModel m;
   famseq_ctx *ctx = nullptr;
   if (o.unpack_mode) {  // only the header needs the model's priors
-    if (m.init(ped, sequenced, o.mrate, o.lrc) != 0) {
+    if (m.init(ped, cm.sequenced, o.mrate, o.lrc) != 0) {
       std::cout << "Cannot initiate family. Please check ped file." << std::endl;
       return false;
     }
     if (o.gN.size() == 3) std::copy(o.gN.begin(), o.gN.end(), m.p.genoProbN);
   } else {
     const double t0 = now_s();
-    ctx = make_ctx(o, ped, sequenced, m);
+    ctx = make_ctx(o, ped, cm.sequenced, m);
     if (!ctx) return false;
     if (std::getenv("FAMSEQ_TIMING")) std::cerr << "FamSeq PL: context (HIP start-up, plan, kernels) " << now_s() - t0 << " s" << std::endl;
   }
@@ -1028,22 +1051,13 @@ bool run_pl(const Options &o, const Ped &ped) {
     fout.write(reinterpret_cast<const char *>(&k32), 4);
     fout.write(reinterpret_cast<const char *>(&reserved), 4);
     fout.write(reinterpret_cast<const char *>(&written), 8);
-    for (uint32_t c : seq_cols) {
+    for (int c : cm.cols) {
       char buf[32] = {0};
       std::strncpy(buf, names[c].c_str(), 31);
       fout.write(buf, 32);
     }
   } else {
-    fout << "##FORMAT=<ID=GPP,Number=G,Type=Integer,Description=\"Normalized, Phred-scaled for posterior probability "
-            "calculated by individual-base Method\">" << std::endl;
-    fout << "##FORMAT=<ID=FPP,Number=G,Type=Integer,Description=\"Normalized, Phred-scaled for posterior probability "
-            "calculated by FamSeqPro\">" << std::endl;
-    fout << "##FORMAT=<ID=FGT,Number=1,Type=String,Description=\"Genotype called by FamSeqPro\">" << std::endl;
-    fout << "##FS mutation rate=" << o.mrate << " " << std::endl;
-    fout << "##FS genotype frequency in pupulation: "; put_triple(fout, m.p.genoProbN); fout << std::endl;
-    fout << "#FORMAT\t";
-    for (uint32_t c : seq_cols) fout << names[c] << '\t';
-    fout << std::endl;
+    put_lk_header(fout, o, m, names, cm.cols);
   }
 
   // Text of one batch (what `FamSeq PL` prints per site), formatted on all cores: one buffer per thread, written in order.
@@ -1073,13 +1087,7 @@ bool run_pl(const Options &o, const Ped &ped) {
             continue;
           }
           line.ch(':');
-          if (rec) {
-            line.record(rec + (s * k + j) * FAMSEQ_TEXT_STRIDE);
-            continue;
-          }
-          line.triples(&gpp[(s * k + j) * 3], &fpp[(s * k + j) * 3]);
-          const int gt = fgt[s * k + j];
-          line.put(gt == 0 ? "0/0\t" : (gt == 1 ? "0/1\t" : "1/1\t"), 4);
+          line.called(rec, gpp, fpp, fgt, s * k + j);
         }
         line.ch('\n');
       }
@@ -1135,7 +1143,7 @@ bool run_pl(const Options &o, const Ped &ped) {
         parallel_for(b.n, [&](size_t s) {  // de-interleave: flags[] and the PED-matched columns of pl[]
           const char *r = raw + s * rec;
           b.flags[s] = uint8_t(r[0]);
-          for (size_t j = 0; j < k; j++) std::memcpy(&b.pl[(s * k + j) * 3], r + 1 + 6 * seq_cols[j], 6);
+          for (size_t j = 0; j < k; j++) std::memcpy(&b.pl[(s * k + j) * 3], r + 1 + 6 * cm.cols[j], 6);
         });
         at += b.n;
         t_read += now_s() - t0;
@@ -1184,7 +1192,7 @@ bool run_pl(const Options &o, const Ped &ped) {
       PlBatch &b = bt[i];
       if (ok) {
         const double t0 = now_s();
-        const int rc = b.call(ctx, b.n, nullptr, seq_members.data());
+        const int rc = b.call(ctx, b.n, nullptr, cm.members.data());
         t_gpu += now_s() - t0;
         if (rc != 0) {
           std::cerr << "famseq_bn_call_batch failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
@@ -1244,7 +1252,7 @@ bool run_pl(const Options &o, const Ped &ped) {
     }
     parallel_for(n, [&](size_t s) {  // the PED-matched columns of pl[]
       const char *r = raw.data() + s * rec;
-      for (size_t j = 0; j < k; j++) std::memcpy(&pl[(s * k + j) * 3], r + 1 + 6 * seq_cols[j], 6);
+      for (size_t j = 0; j < k; j++) std::memcpy(&pl[(s * k + j) * 3], r + 1 + 6 * cm.cols[j], 6);
     });
     format_and_write(n, pl.data(), status.data(), gpp.data(), fpp.data(), fgt.data(), nullptr);
   }
@@ -1314,80 +1322,168 @@ void on_threads(int n, F f) {
   for (std::thread &th : pool) th.join();
 }
 
-bool run_vcf(const Options &o, const Ped &ped) {
-  LineSource fin;
-  if (!fin.open(o.vcf_files[0])) {
-    std::cout << "Cannot open " << o.vcf_files[0] << std::endl;
-    return false;
+// parts 0..n_parts-1 on at most `threads` threads, dealt round-robin
+template <class F>
+void on_parts(int n_parts, unsigned threads, F f) {
+  const int nt = (int)std::min<unsigned>(threads, (unsigned)n_parts);
+  on_threads(nt, [&](int j) {
+    for (int t = j; t < n_parts; t += nt) f(t);
+  });
+}
+
+// What one parsing thread makes of its contiguous range of a block's lines, in input order.  The same thread
+// formats the same range once the block's sites are back from the GPU.
+struct Item {
+  const char *raw;       // site: the input line (mapped; columns 1-9 and the sample fields are printed from it)
+  uint32_t raw_len;
+  uint32_t prefix_len;   // site: columns 1-9 without the tab after FORMAT
+  uint32_t n_fmt;        // site: FORMAT keys (a missing sample prints that many "NA:")
+  int32_t site;          // the line's index in the block = its site in the batch; -1: an echoed line, text = echo[echo_off, +echo_len)
+  uint32_t echo_off, echo_len;
+  uint32_t smp;          // site: its samples are samples[smp, +n_seq)
+};
+struct Part {
+  vector<Item> items;
+  vector<char> echo;
+  vector<Record::Sample> samples;      // n_seq per site
+  vector<uint32_t> explicit_sites;     // sites with a PL/GL field that is not a plain integer ...
+  vector<double> explicit_lk;          // ... and their N x 3 likelihoods (the batch then goes in as fp64)
+  bool any_failed = false;
+  void clear() {
+    items.clear(), echo.clear(), samples.clear(), explicit_sites.clear(), explicit_lk.clear();
+    any_failed = false;
   }
+};
+
+// ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample and -seg add to a line, one row of kSide each ------------------------
+// The order is the one main checks them and prints its notices in; it is also the order of the fields in a sample column (DNP,
+// JGT:JP, LOP:LOF, SGT) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR).  Header lines have their own order.
+enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg };
+constexpr int kSides = kSeg + 1;
+const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ};
+
+// One side output of a block: the two arrays its C entry fills ([site][...], read as the entry's own types) and its status per site.
+struct SideOut {
+  vector<double> a, b;
+  vector<uint8_t> status;
+  const int8_t *a8() const { return reinterpret_cast<const int8_t *>(a.data()); }
+};
+
+struct VcfRun;
+struct SideBytes { size_t a, b; };
+struct SideRow {
+  SideId id;
+  const char *flag;   // as the notices name it
+  const char *entry;  // its C entries are <entry>_batch and <entry>_prior_batch (VcfRun::call_side)
+  bool method2;       // a form of the sum-product engine only: implies -method 2
+  bool (*on)(const Options &);
+  void (*off)(Options &);
+  bool (*check)(const Options &, const Ped &);  // its own arguments, said with a message (exit -1); null: nothing to check
+  void (*header)(std::ostream &, const Options &);
+  const char *keys, *na;  // its FORMAT keys and what a failed site prints for them; null: it writes INFO keys
+  SideBytes (*bytes)(const VcfRun &);  // per site, of the two arrays
+};
+extern const SideRow kSide[kSides];
+// Row id's fields behind column j of site s, from the ':' on, or its INFO keys for site s: a switch, which the formatter's loop inlines
+[[gnu::always_inline]] inline void put_side(SideId id, TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j);
+
+bool any_side(const Options &o) { return std::any_of(kSide, kSide + kSides, [&](const SideRow &r) { return r.on(o); }); }
+
+struct Slot {
+  vector<std::string_view> lines;
+  vector<Part> parts;
+  int n_parts = 0;
+  size_t n_sites = 0;  // sites of the batch: the block's lines, or (large pedigrees) its sites moved together
+  bool packed = true;
+  bool staged = false;        // parsed into pk_pl / pk_flags because the HIP runtime was not up yet: the flusher copies them over
+  vector<uint16_t> pk_pl;     // pack mode (and staged blocks): the block's arrays live here, nothing is pinned
+  vector<uint8_t> pk_flags;
+  PlBatch io;          // pinned: pl + flags in, gpp / fpp / fgt / status out
+  uint16_t *pl_arr = nullptr;  // where this block is parsed to: io's arrays or the pk_ ones
+  uint8_t *flags_arr = nullptr;
+  vector<double> lk;   // fp64 input, only for a block with a non-integer PL/GL field
+  vector<double> prior;  // -afTag: [line][6], the founders' prior rows (a line that is no site keeps the model's)
+  vector<TextBuf> text;
+  SideOut side[kSides];
+  int64_t site_base = 0;  // -sample: the block's first site among the sites of the file
+};
+
+// One `FamSeq vcf` (or `pack`) run: what is set up once — never changed by the stages — what the stages do change, and the stages.
+struct VcfRun {
+  const Options &o;
+  const Ped &ped;
+  LineSource fin;
+  std::ofstream fout;
   CliModel m;
-  // defaults needed for the header before the ctx exists
-  {
+  bool use_af = false;
+  vector<uint8_t> seg_masks;  // -seg: the patterns' mask rows and INFO keys
+  vector<const char *> seg_keys;
+  double model_rows[2][6];  // -afTag: the rows of a line without a usable frequency, by its Known flag: what the model itself would have used
+  ColumnMap cm;
+  size_t ncol = 0, n_seq = 0, N3 = 0;
+  vector<int> kid_of_col;  // -dnm: column j -> its member's index among the children (famseq_trio_children: the members with parents, PED order), -1 for a founder
+  int n_kids = 0;
+  vector<vector<int>> loc = vector<vector<int>>(25);
+  const PlTable pl;
+  PackWriter packer;
+  const bool as_text = device_text();
+  vector<const SideRow *> sides, fields, infos;  // the rows that are on, in kSide's order: all of them, those with FORMAT keys, those with INFO keys
+  string format_keys = ":GPP:FPP:FGT";           // what a site's FORMAT column gains, with the tab behind it
+  size_t block = 0;
+  unsigned n_threads = 1, parse_threads = 1, format_threads = 1;
+  int compact_from = 12;  // members from which a block's sites are moved together before the GPU call
+  // ... and what the stages change
+  Slot slots[4];  // one being cut and parsed, one at the GPU, one being formatted, one being written
+  Channel to_flusher, to_formatter, to_writer, to_driver;
+  std::atomic<bool> hip_up{false}, flush_ok{true};
+  std::future<famseq_ctx *> ctx_future;
+  famseq_ctx *ctx = nullptr;
+  uint64_t sites_before = 0;  // sites of the blocks cut so far
+  double t_lines = 0, t_parse = 0, t_gather = 0, t_stall = 0, t_gpu = 0, t_format = 0, t_write = 0, t_ctx_wait = 0;
+
+  // the model (its priors are needed for the header before the ctx exists), -seg's masks, -afTag's rows, the active side rows
+  bool set_up() {
     vector<uint8_t> all(ped.n(), 1);
     if (m.init(ped, all, o.mrate, o.lrc) != 0) {
       std::cout << "Cannot initiate family. Please check ped file." << std::endl << "Cannot set family." << std::endl;
       return false;
     }
-    if (o.gN.size() == 3) std::copy(o.gN.begin(), o.gN.end(), m.p.genoProbN);
-    if (o.gK.size() == 3) std::copy(o.gK.begin(), o.gK.end(), m.p.genoProbK);
-    if (o.gXN.size() == 3) std::copy(o.gXN.begin(), o.gXN.end(), m.p.genoProbXN);
-    if (o.gXK.size() == 3) std::copy(o.gXK.begin(), o.gXK.end(), m.p.genoProbXK);
+    m.set_priors(o);
+    use_af = !o.af_tag.empty() && !o.pack_mode;
+    // (main has checked -seg's options: this cannot fail here)
+    if (!o.seg.empty() && !o.pack_mode && !segregation_masks(o, ped, seg_masks, seg_keys)) return false;
+    for (int k = 0; k < 3; ++k) {
+      model_rows[0][k] = m.p.genoProbN[k], model_rows[0][3 + k] = m.p.genoProbXN[k];
+      model_rows[1][k] = m.p.genoProbK[k], model_rows[1][3 + k] = m.p.genoProbXK[k];
+    }
+    for (const SideRow &row : kSide) {
+      if (!row.on(o)) continue;
+      sides.push_back(&row);
+      (row.keys ? fields : infos).push_back(&row);
+      if (row.keys) format_keys += row.keys;
+    }
+    format_keys += '\t';
+    N3 = size_t(3) * ped.n();
+    block = std::min<size_t>(batch_capacity(), size_t(1) << 16);
+    n_threads = std::thread::hardware_concurrency();
+    if (const char *e = std::getenv("FAMSEQ_THREADS")) n_threads = (unsigned)std::atoi(e);
+    n_threads = std::max(1u, std::min(n_threads, 32u));
+    // A block is cut into n_threads parts; how many threads walk them while parsing and while formatting can be set apart
+    // (formatting is the loop's critical path and runs beside the next block's parsing: tools/cli_throughput.py)
+    parse_threads = format_threads = n_threads;
+    if (const char *e = std::getenv("FAMSEQ_PARSE_THREADS")) parse_threads = std::max(1, std::atoi(e));
+    if (const char *e = std::getenv("FAMSEQ_FORMAT_THREADS")) format_threads = std::max(1, std::atoi(e));
+    if (const char *e = std::getenv("FAMSEQ_COMPACT_FROM")) compact_from = std::atoi(e);  // test aid
+    for (Slot &sl : slots) sl.parts.resize(n_threads), sl.text.resize(n_threads);
+    return true;
   }
-  const bool use_af = !o.af_tag.empty() && !o.pack_mode;
-  // -seg: the patterns' mask rows and INFO keys (main has checked the options: this cannot fail here)
-  vector<uint8_t> seg_masks;
-  vector<const char *> seg_keys;
-  if (!o.seg.empty() && !o.pack_mode && !segregation_masks(o, ped, seg_masks, seg_keys)) return false;
-  const size_t n_seg = seg_keys.size();
-  // -afTag: the rows of a line without a usable frequency, by its Known flag: what the model itself would have used
-  double model_rows[2][6];
-  for (int k = 0; k < 3; ++k) {
-    model_rows[0][k] = m.p.genoProbN[k], model_rows[0][3 + k] = m.p.genoProbXN[k];
-    model_rows[1][k] = m.p.genoProbK[k], model_rows[1][3 + k] = m.p.genoProbXK[k];
-  }
-  // pack mode writes a binary file: the text header goes nowhere
-  std::ofstream fout;
-  if (!o.pack_mode) fout.open(o.out_file.c_str());
 
-  // ---- header (file.cpp:143-196): lines are echoed with a one-line lag
-  auto format_tags = [&](bool fallback) {
-    fout << "##FORMAT=<ID=GPP,Number=G,Type=Integer,Description=\"Normalized, Phred-scaled for posterior probability "
-         << (fallback ? "calbulated by Single Method" : "calculated by individual-based Method") << "\">" << std::endl;
-    fout << "##FORMAT=<ID=FPP,Number=G,Type=Integer,Description=\"Normalized, Phred-scaled for posterior probability "
-            "calculated by FamSeqPro\">" << std::endl;
-    fout << "##FORMAT=<ID=FGT,Number=1,Type=String,Description=\"Genotype called by FamSeqPro\">" << std::endl;
-    if (o.dnm)
-      fout << "##FORMAT=<ID=DNP,Number=1,Type=Float,Description=\"Posterior probability of a de novo mutation (genotype "
-              "Mendelian-inconsistent with the parents')\">" << std::endl;
-    if (o.map) {
-      fout << "##FORMAT=<ID=JGT,Number=1,Type=String,Description=\"Genotype in the most probable joint genotype configuration of "
-              "the whole family\">" << std::endl;
-      fout << "##FORMAT=<ID=JP,Number=1,Type=Float,Description=\"Posterior probability of that joint configuration\">" << std::endl;
-    }
-    if (o.loo) {
-      fout << "##FORMAT=<ID=LOP,Number=G,Type=Float,Description=\"Phred-scaled genotype probabilities given the data of every other "
-              "member of the family, the sample's own left out\">" << std::endl;
-      fout << "##FORMAT=<ID=LOF,Number=1,Type=Float,Description=\"Phred-scaled predictive likelihood of the sample's data given the "
-              "other members' (99999: impossible given the relatives)\">" << std::endl;
-    }
-    if (o.sample)
-      fout << "##FORMAT=<ID=SGT,Number=.,Type=Integer,Description=\"Alternate allele counts of the sample in " << o.sample
-           << " joint genotype configurations of the whole family drawn from their posterior (seed " << o.seed << ")\">" << std::endl;
-    if (!o.seg.empty()) {
-      if (o.seg != "recessive")
-        fout << "##INFO=<ID=PSD,Number=1,Type=Float,Description=\"Posterior probability that the affected members, and no unaffected one, "
-                "carry the variant (dominant segregation pattern)\">" << std::endl;
-      if (o.seg != "dominant")
-        fout << "##INFO=<ID=PSR,Number=1,Type=Float,Description=\"Posterior probability that the affected members, and no unaffected one, "
-                "are homozygous for the variant (recessive segregation pattern)\">" << std::endl;
-    }
-    if (o.siteq) {
-      fout << "##INFO=<ID=FQ,Number=1,Type=Float,Description=\"Family variant quality: Phred-scaled posterior probability that every "
-              "member of the family is homozygous reference\">" << std::endl;
-      fout << "##INFO=<ID=FLL,Number=1,Type=Float,Description=\"log10 likelihood of the site's data under the pedigree\">" << std::endl;
-    }
-  };
-  auto fs_info = [&] {
+  void format_tags(bool fallback) {
+    put_format_header(fout, fallback ? "calbulated by Single Method" : "calculated by individual-based Method");
+    for (SideId id : kHeaderOrder)
+      if (kSide[id].on(o)) kSide[id].header(fout, o);
+  }
+  void fs_info() {
     fout << "##FS mutation rate=" << o.mrate << " " << std::endl;
     fout << "##FS genotype frequency in pupulation (Rare): "; put_triple(fout, m.p.genoProbN); fout << std::endl;
     fout << "##FS genotype frequency in population (Common): "; put_triple(fout, m.p.genoProbK); fout << std::endl;
@@ -1396,73 +1492,57 @@ bool run_vcf(const Options &o, const Ped &ped) {
     if (use_af)
       fout << "##FS genotype frequency of a site with 0 < " << o.af_tag << " < 1 in INFO: Hardy-Weinberg at that allele frequency"
            << (o.af_all ? " (-afTagAll: for every field of the line)" : "") << std::endl;
-  };
-  string title;
-  std::string_view line;
-  bool need_tags = true, need_info = true, have_line = false;
-  auto after_hashes = [](std::string_view l, size_t n) { return l.size() > 2 ? l.substr(2, n) : std::string_view(); };
-  while (fin.next(line)) {
-    if (!line.empty() && line[0] == '#') {
-      if (title.size() > 2) {
-        fout << title << std::endl;
-        if (title.compare(2, 6, "FORMAT") == 0 && after_hashes(line, 4) == "INFO" && need_tags) {
-          format_tags(false);
-          need_tags = false;
-        }
-        if (after_hashes(line, 6) == "contig" && need_info) {
-          fs_info();
-          need_info = false;
-        }
-      }
-      title.assign(line);
-      continue;
-    }
-    have_line = true;
-    break;
   }
-  if (need_tags) format_tags(true);
-  if (need_info) fs_info();
-
-  // ---- column mapping (file.cpp:200-232)
-  const vector<string> head = split_keep(title, '\t');
-  if (head.size() < 9) {
-    std::cerr << "The vcf file has no #CHROM header line." << std::endl;
-    return false;
-  }
-  const size_t ncol = head.size() - 9;
-  vector<int> v2p(ncol, -1);
-  vector<uint8_t> sequenced(ped.n(), 0);
-  for (size_t i = 0; i < ncol; i++)
-    for (int j = 0; j < ped.n(); j++)
-      if (head[9 + i] == ped.name[j]) {
-        v2p[i] = j;
-        sequenced[j] = 1;
-        break;
+  // The header (file.cpp:143-196): lines are echoed with a one-line lag, the run's own lines go behind the input's FORMAT lines
+  // and in front of its contig lines, or behind all of them where it has neither.  Returns the last header line, the #CHROM one;
+  // `line` is the first data line where have_line.
+  string echo_header(std::string_view &line, bool &have_line) {
+    string title;
+    bool need_tags = true, need_info = true;
+    auto after_hashes = [](std::string_view l, size_t n) { return l.size() > 2 ? l.substr(2, n) : std::string_view(); };
+    while (fin.next(line)) {
+      if (!line.empty() && line[0] == '#') {
+        if (title.size() > 2) {
+          fout << title << std::endl;
+          if (title.compare(2, 6, "FORMAT") == 0 && after_hashes(line, 4) == "INFO" && need_tags) {
+            format_tags(false);
+            need_tags = false;
+          }
+          if (after_hashes(line, 6) == "contig" && need_info) {
+            fs_info();
+            need_info = false;
+          }
+        }
+        title.assign(line);
+        continue;
       }
-  vector<int> seq_cols;
-  vector<int32_t> seq_members;
-  for (size_t i = 0; i < ncol; i++)
-    if (v2p[i] >= 0) {
-      seq_cols.push_back((int)i);
-      seq_members.push_back(v2p[i]);
+      have_line = true;
+      break;
     }
-  for (int i = 0; i < 9; i++) fout << head[i] << '\t';
-  for (int c : seq_cols) fout << head[9 + c] << '\t';
-  fout << std::endl;
-  // -dnm: column j -> its member's index among the children (famseq_trio_children: the members with parents, PED order), -1 for a founder
-  vector<int> kid_of_col(seq_members.size(), -1);
-  int n_kids = 0;
-  {
+    if (need_tags) format_tags(true);
+    if (need_info) fs_info();
+    return title;
+  }
+  // column mapping (file.cpp:200-232) and the output's #CHROM line
+  bool map_header(const vector<string> &head) {
+    if (head.size() < 9) {
+      std::cerr << "The vcf file has no #CHROM header line." << std::endl;
+      return false;
+    }
+    ncol = head.size() - 9;
+    cm = map_columns(head.data() + 9, ncol, ped);
+    n_seq = cm.cols.size();
+    for (int i = 0; i < 9; i++) fout << head[i] << '\t';
+    for (int c : cm.cols) fout << head[9 + c] << '\t';
+    fout << std::endl;
     vector<int> kid(ped.n(), -1);
     for (int p = 0; p < ped.n(); ++p)
       if (m.mo[p] >= 0) kid[p] = n_kids++;
-    for (size_t j = 0; j < seq_members.size(); ++j) kid_of_col[j] = kid[seq_members[j]];
+    for (int32_t p : cm.members) kid_of_col.push_back(kid[p]);
+    return true;
   }
-
-  // ---- location filter (file.cpp:235-298)
-  vector<vector<int>> loc(25);
-  const bool use_loc = !o.loc_file.empty();
-  if (use_loc) {
+  // location filter (file.cpp:235-298)
+  bool read_locations() {
     std::ifstream fl(o.loc_file.c_str());
     if (!fl.is_open()) {
       std::cout << "Cannot open " << o.loc_file << std::endl;
@@ -1479,66 +1559,14 @@ bool run_vcf(const Options &o, const Ped &ped) {
       loc[c - 1].push_back(p);
     }
     for (auto &v : loc) std::sort(v.begin(), v.end());
+    return true;
   }
-
-  PackWriter packer;
-  famseq_ctx *ctx = nullptr;
-  if (o.pack_mode) {
-    vector<string> names;
-    for (int c : seq_cols) names.push_back(head[9 + c]);
-    if (names.empty() || !packer.open(o.out_file, names)) {
-      std::cout << "Cannot write " << o.out_file << " (or no sample of the vcf file is in the ped file)." << std::endl;
-      return false;
-    }
-  } else if (seq_cols.empty()) {  // nothing to compute and nothing to print per sample: say so instead of walking the file
-    std::cout << "No sample of the vcf file is in the ped file (the names in the ped file's fifth column must match the vcf header)." << std::endl;
-    return false;
-  }
-  // HIP start-up (runtime initialisation, context, streams, code objects: about a quarter of a second) runs on its own
-  // thread while this one cuts and parses the first block(s); the flusher thread, the first to need the context, waits for it.
-  // Until it is there the blocks are parsed into ordinary memory (pinned buffers need the runtime) and copied over — 6 bytes
-  // per sample and site — once it is.
-  std::atomic<bool> hip_up{false};
-  std::future<famseq_ctx *> ctx_future;
-  if (!o.pack_mode)
-    ctx_future = std::async(std::launch::async, [&] {
-      famseq_ctx *c = make_ctx(o, ped, sequenced, m);
-      hip_up = true;
-      return c;
-    });
-  const PlTable pl;
-  const size_t n_seq = seq_cols.size(), N3 = size_t(3) * ped.n();
-  const bool as_text = device_text();
-
-  // What one parsing thread makes of its contiguous range of a block's lines, in input order.  The same thread
-  // formats the same range once the block's sites are back from the GPU.
-  struct Item {
-    const char *raw;       // site: the input line (mapped; columns 1-9 and the sample fields are printed from it)
-    uint32_t raw_len;
-    uint32_t prefix_len;   // site: columns 1-9 without the tab after FORMAT
-    uint32_t n_fmt;        // site: FORMAT keys (a missing sample prints that many "NA:")
-    int32_t site;          // the line's index in the block = its site in the batch; -1: an echoed line, text = echo[echo_off, +echo_len)
-    uint32_t echo_off, echo_len;
-    uint32_t smp;          // site: its samples are samples[smp, +n_seq)
-  };
-  struct Part {
-    vector<Item> items;
-    vector<char> echo;
-    vector<Record::Sample> samples;      // n_seq per site
-    vector<uint32_t> explicit_sites;     // sites with a PL/GL field that is not a plain integer ...
-    vector<double> explicit_lk;          // ... and their N x 3 likelihoods (the batch then goes in as fp64)
-    bool any_failed = false;
-    void clear() {
-      items.clear(), echo.clear(), samples.clear(), explicit_sites.clear(), explicit_lk.clear();
-      any_failed = false;
-    }
-  };
 
   // One input line -> an Item (or nothing).  Pure function of the line (no shared state).  Line q of a block is site q of
   // the batch: a site's flag byte and packed PLs are written where the GPU call will read them (flags_q, pl16: the
   // caller has set them to "all samples missing", which is what a line that is no site stays — computed and ignored;
   // compacting the sites first cost a pass over the batch, and the GPU idles nine tenths of the loop).
-  auto parse_line = [&](std::string_view line, size_t q, Part &out, uint8_t *flags_q, uint16_t *pl16, double *prior_q) {
+  void parse_line(std::string_view line, size_t q, Part &out, uint8_t *flags_q, uint16_t *pl16, double *prior_q) const {
     if (line[0] == '#') return;
     thread_local vector<std::string_view> t, fmt, sub;
     thread_local vector<double> lkrow;
@@ -1551,13 +1579,13 @@ bool run_vcf(const Options &o, const Ped &ped) {
         out.echo.insert(out.echo.end(), t[i].begin(), t[i].end());
         out.echo.push_back('\t');
       }
-      for (int c : seq_cols) {
+      for (int c : cm.cols) {
         out.echo.insert(out.echo.end(), t[9 + c].begin(), t[9 + c].end());
         out.echo.push_back('\t');
       }
       out.items.push_back(Item{nullptr, 0, 0, 0, -1, uint32_t(at), uint32_t(out.echo.size() - at), 0});
     };
-    if (use_loc) {
+    if (!o.loc_file.empty()) {
       const int c = chrom_number(string(t[0]));
       const int p = std::atoi(string(t[1]).c_str());
       if (c < 1 || c > 25 || p == 0) return;
@@ -1583,7 +1611,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
     const uint8_t flags = uint8_t((t[2] != "." ? FAMSEQ_FLAG_KNOWN : 0) | (is_x ? FAMSEQ_FLAG_CHRX : 0));
     split_views(t[8], ':', fmt);
     size_t n_miss = 0;
-    for (int c : seq_cols) n_miss += t[9 + c].size() < 5;
+    for (int c : cm.cols) n_miss += t[9 + c].size() < 5;
     if (n_miss == n_seq) {
       if (o.all_line) echo();
       return;
@@ -1607,7 +1635,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
     lkrow.assign(N3, 1.0);
     bool integral = true;
     size_t col = 0;
-    for (int c : seq_cols) {
+    for (int c : cm.cols) {
       const size_t this_col = col++;
       const std::string_view f = t[9 + c];
       out.samples.push_back({uint32_t(f.data() - base), uint32_t(f.size()), f.size() < 5});
@@ -1619,7 +1647,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
       for (int g = 0; g < 3; g++) {
         const char *e = static_cast<const char *>(std::memchr(b, ',', size_t(end - b)));
         if (!e) e = end;
-        lkrow[size_t(3) * v2p[c] + g] = pl(b, e, &pl16[3 * this_col + g], &integral);
+        lkrow[size_t(3) * cm.member[c] + g] = pl(b, e, &pl16[3 * this_col + g], &integral);
         b = e < end ? e + 1 : end;
       }
     }
@@ -1627,66 +1655,170 @@ bool run_vcf(const Options &o, const Ped &ped) {
       out.explicit_sites.push_back(uint32_t(q));
       out.explicit_lk.insert(out.explicit_lk.end(), lkrow.begin(), lkrow.end());
     }
-  };
+  }
 
-  // ---- the pipeline.  A block of input lines is ONE batch: this thread cuts it into lines, has it parsed on all
+  // ---- the pipeline.  A block of input lines is ONE batch: the driver's thread cuts it into lines, has it parsed on all
   // cores (each thread its contiguous range, into its own Part and into its range of the batch's pinned arrays)
   // and hands the block to the flusher thread — GPU call (famseq_bn_call_batch: posterior, Phred scaling and
   // genotype call on the device), formatting (each thread the range it parsed), one write per thread — while it goes on
   // with the next block in the other slot.  (Before: lines copied one by one out of an ifstream, parsed results moved
   // one by one into the batch by this thread, 0.94 of the loop's 1.0 s per 1 M ten-member sites.)
-  const size_t block = std::min<size_t>(batch_capacity(), size_t(1) << 16);
-  unsigned n_threads = std::thread::hardware_concurrency();
-  if (const char *e = std::getenv("FAMSEQ_THREADS")) n_threads = (unsigned)std::atoi(e);
-  n_threads = std::max(1u, std::min(n_threads, 32u));
-  // A block is cut into n_threads parts; how many threads walk them while parsing and while formatting can be set apart
-  // (formatting is the loop's critical path and runs beside the next block's parsing: tools/cli_throughput.py)
-  unsigned parse_threads = n_threads, format_threads = n_threads;
-  if (const char *e = std::getenv("FAMSEQ_PARSE_THREADS")) parse_threads = std::max(1, std::atoi(e));
-  if (const char *e = std::getenv("FAMSEQ_FORMAT_THREADS")) format_threads = std::max(1, std::atoi(e));
-  auto on_parts = [](int n_parts, unsigned threads, const std::function<void(int)> &f) {
-    const int nt = (int)std::min<unsigned>(threads, (unsigned)n_parts);
-    on_threads(nt, [&](int j) {
-      for (int t = j; t < n_parts; t += nt) f(t);
-    });
-  };
-  struct Slot {
-    vector<std::string_view> lines;
-    vector<Part> parts;
-    int n_parts = 0;
-    size_t n_sites = 0;  // sites of the batch: the block's lines, or (large pedigrees) its sites moved together
-    bool packed = true;
-    bool staged = false;        // parsed into pk_pl / pk_flags because the HIP runtime was not up yet: the flusher copies them over
-    vector<uint16_t> pk_pl;     // pack mode (and staged blocks): the block's arrays live here, nothing is pinned
-    vector<uint8_t> pk_flags;
-    PlBatch io;          // pinned: pl + flags in, gpp / fpp / fgt / status out
-    vector<double> lk;   // fp64 input, only for a block with a non-integer PL/GL field
-    vector<double> prior;  // -afTag: [line][6], the founders' prior rows (a line that is no site keeps the model's)
-    vector<TextBuf> text;
-    vector<double> dnm;      // -dnm: [site][child] de novo posteriors ...
-    vector<uint8_t> tstatus;  // ... and the trio kernel's status per site
-    vector<int8_t> jgt;       // -map: [site][member] the MAP configuration ...
-    vector<double> jp;        // ... its posterior ...
-    vector<uint8_t> jstatus;  // ... and the MAP kernel's status per site
-    vector<double> fll, pref;  // -siteQ: [site] the log10 likelihood and the hom-ref posterior ...
-    vector<uint8_t> estatus;   // ... and the evidence kernel's status per site
-    vector<double> loo, fit;   // -loo: [site][member][3] leave-one-out posteriors, [site][member] the members' fit ...
-    vector<uint8_t> lstatus;   // ... and the leave-one-out kernel's status per site
-    vector<int8_t> sgt;        // -sample: [site][draw][member] the drawn configurations ...
-    vector<uint8_t> sstatus;   // ... and the sampling kernel's status per site
-    int64_t site_base = 0;     // ... the block's first site among the sites of the file
-    vector<double> ppat;       // -seg: [site][pattern] the patterns' posteriors ...
-    vector<uint8_t> pstatus;   // ... and the pattern kernel's status per site
-  } slots[4];  // one being cut and parsed, one at the GPU, one being formatted, one being written
-  bool ok = true;
-  for (Slot &sl : slots) sl.parts.resize(n_threads), sl.text.resize(n_threads);
 
-  double t_lines = 0, t_parse = 0, t_gather = 0, t_stall = 0, t_gpu = 0, t_format = 0, t_write = 0, t_ctx_wait = 0;
-  int compact_from = 12;  // members from which a block's sites are moved together before the GPU call (below)
-  if (const char *e = std::getenv("FAMSEQ_COMPACT_FROM")) compact_from = std::atoi(e);  // test aid
-  Channel to_flusher, to_formatter, to_writer, to_driver;
-  std::atomic<bool> flush_ok{true};
-  std::thread flusher([&] {
+  bool pin(Slot &sl, size_t n) {
+    if (sl.io.cap >= n) return true;
+    sl.io.release();
+    sl.io = PlBatch();
+    if (sl.io.alloc(n, std::max<size_t>(n_seq, 1), as_text)) return true;
+    std::cerr << "cannot allocate pinned host buffers" << std::endl;
+    return false;
+  }
+  // Cut the next block off the input (`line` holds the next unread line) and parse it.  False: nothing was cut, or its pinned
+  // arrays could not be had (*ok cleared).
+  bool cut_and_parse(Slot &sl, std::string_view &line, bool &more, bool *ok) {
+    const double t1 = now_s();
+    sl.lines.clear();
+    while (more && sl.lines.size() < block) {
+      if (line.size() < 2) {  // the reference stops at the first empty line
+        more = false;
+        break;
+      }
+      sl.lines.push_back(line);
+      more = fin.next(line);
+    }
+    const size_t nl = sl.lines.size();
+    if (nl == 0) return false;
+    sl.n_parts = nl < 2048 ? 1 : (int)n_threads;
+    const double t2 = now_s();
+    t_lines += t2 - t1;
+    sl.staged = !o.pack_mode && !hip_up;
+    if (o.pack_mode || sl.staged) {
+      sl.pk_pl.resize(nl * 3 * n_seq), sl.pk_flags.resize(nl);
+    } else if (!pin(sl, nl)) {  // pinned, sized by the first block (a short file does not pay for 65,536 sites)
+      *ok = false;
+      return false;
+    }
+    uint16_t *const pl_arr = sl.pl_arr = o.pack_mode || sl.staged ? sl.pk_pl.data() : sl.io.pl;
+    uint8_t *const flags_arr = sl.flags_arr = o.pack_mode || sl.staged ? sl.pk_flags.data() : sl.io.flags;
+    if (use_af) sl.prior.resize(nl * 6);
+    double *const prior_arr = use_af ? sl.prior.data() : nullptr;
+    on_parts(sl.n_parts, parse_threads, [&](int t) {
+      Part &pt = sl.parts[t];
+      pt.clear();
+      const size_t lo = nl * t / sl.n_parts, hi = nl * (t + 1) / sl.n_parts;
+      std::memset(flags_arr + lo, 0, hi - lo);
+      for (size_t q = lo; prior_arr && q < hi; ++q) std::copy(model_rows[0], model_rows[0] + 6, prior_arr + 6 * q);
+      std::memset(pl_arr + lo * 3 * n_seq, 0xFF, (hi - lo) * 6 * n_seq);  // 0xFFFF x3 = missing sample
+      for (size_t q = lo; q < hi; ++q) parse_line(sl.lines[q], q, pt, flags_arr + q, pl_arr + q * 3 * n_seq, prior_arr ? prior_arr + 6 * q : nullptr);
+    });
+    t_parse += now_s() - t2;
+    bool packed = true;
+    size_t real = 0;
+    for (int t = 0; t < sl.n_parts; ++t) {
+      packed = packed && sl.parts[t].explicit_sites.empty();
+      real += sl.parts[t].samples.size();
+    }
+    sl.n_sites = real ? nl : 0, sl.packed = packed;  // a block without a single site (or without a sequenced sample) calls nothing
+    return true;
+  }
+  // pack mode: records of the integer sites, in input order; nothing goes to the GPU
+  void pack_records(const Slot &sl) {
+    for (int t = 0; t < sl.n_parts; ++t) {
+      const Part &pt = sl.parts[t];
+      size_t x = 0;
+      for (const Item &it : pt.items) {
+        if (it.site < 0) continue;
+        if (x < pt.explicit_sites.size() && pt.explicit_sites[x] == uint32_t(it.site)) {
+          ++x, packer.skipped++;
+          continue;
+        }
+        packer.add(sl.flags_arr[it.site], sl.pl_arr + size_t(it.site) * 3 * n_seq);
+      }
+    }
+  }
+  // A line that is no site costs the GPU a site's work: nothing next to the text work for the usual pedigree, but
+  // 3^N configurations each.  From twelve members on (0.5 M configurations) the sites are moved together first —
+  // in place and in order, one thread: 60 bytes per site.  (-sample: always, so that a site's position in the batch
+  // is its position among the block's sites, and site_base counts the sites of the blocks before.)
+  void move_sites_together(Slot &sl) {
+    const size_t nl = sl.lines.size();
+    double *const prior_arr = use_af ? sl.prior.data() : nullptr;
+    size_t n_real = 0;
+    for (int t = 0; t < sl.n_parts; ++t)
+      for (const Item &it : sl.parts[t].items) n_real += it.site >= 0;
+    if (n_real > 0 && n_real < nl && (ped.n() >= compact_from || o.sample)) {
+      size_t d = 0;
+      for (int t = 0; t < sl.n_parts; ++t) {
+        Part &pt = sl.parts[t];
+        size_t x = 0;
+        for (Item &it : pt.items) {
+          if (it.site < 0) continue;
+          const size_t q = size_t(it.site);
+          if (d != q) {
+            sl.flags_arr[d] = sl.flags_arr[q];
+            std::memmove(sl.pl_arr + d * 3 * n_seq, sl.pl_arr + q * 3 * n_seq, 6 * n_seq);
+            if (prior_arr) std::memmove(prior_arr + 6 * d, prior_arr + 6 * q, 48);
+          }
+          if (x < pt.explicit_sites.size() && pt.explicit_sites[x] == q) pt.explicit_sites[x++] = uint32_t(d);
+          it.site = int32_t(d++);
+        }
+      }
+      sl.n_sites = d;
+    }
+    sl.site_base = (int64_t)sites_before;  // -sample: a site's index is its ordinal among the file's sites, whatever the blocks
+    sites_before += n_real;
+  }
+  // fp64 rows: the table's value for every integer field (what the parser computed for it), the parsed rows of the others
+  void build_lk_rows(Slot &sl) {
+    const size_t n = sl.n_sites;
+    sl.lk.resize(n * N3);
+    on_threads(sl.n_parts, [&](int t) {
+      const size_t lo = n * t / sl.n_parts, hi = n * (t + 1) / sl.n_parts;
+      double *rows = sl.lk.data();
+      std::fill(rows + lo * N3, rows + hi * N3, 1.0);
+      for (size_t q = lo; q < hi; ++q)
+        for (size_t j = 0; j < n_seq; ++j) {
+          const uint16_t *p = &sl.pl_arr[(q * n_seq + j) * 3];
+          if (p[0] == 0xFFFF && p[1] == 0xFFFF && p[2] == 0xFFFF) continue;
+          for (int g = 0; g < 3; ++g) rows[q * N3 + size_t(3) * cm.members[j] + g] = pl.value(p[g]);
+        }
+    });
+    for (int t = 0; t < sl.n_parts; ++t) {
+      const Part &pt = sl.parts[t];
+      for (size_t x = 0; x < pt.explicit_sites.size(); ++x)
+        std::copy(&pt.explicit_lk[x * N3], &pt.explicit_lk[(x + 1) * N3], sl.lk.data() + size_t(pt.explicit_sites[x]) * N3);
+    }
+  }
+
+  // The block's batch through a side output's kernel (full network, whatever -LRC and -method say; -afTagAll: under the rows FPP
+  // and FGT were computed with): its plain or its site-prior entry, whose own arguments ride between the input and the outputs.
+  void call_side(const SideRow &row, Slot &sl) {
+    SideOut &so = sl.side[row.id];
+    const SideBytes by = row.bytes(*this);
+    so.a.resize((sl.n_sites * by.a + 7) / 8), so.b.resize((sl.n_sites * by.b + 7) / 8), so.status.resize(sl.n_sites);
+    const double *lk = sl.packed ? nullptr : sl.lk.data();
+    const uint16_t *pl16 = sl.packed ? sl.io.pl : nullptr;
+    auto entry = [&](auto plain, auto with_prior, auto... tail) {
+      return use_af ? with_prior(ctx, (int64_t)sl.n_sites, lk, pl16, cm.members.data(), (int32_t)n_seq, sl.io.flags, sl.prior.data(), tail...)
+                    : plain(ctx, (int64_t)sl.n_sites, lk, pl16, cm.members.data(), (int32_t)n_seq, sl.io.flags, tail...);
+    };
+    double *const a = so.a.data(), *const b = so.b.data(), *const none = nullptr;
+    int8_t *const a8 = reinterpret_cast<int8_t *>(a);
+    uint8_t *const st = so.status.data();
+    int rc = 0;
+    switch (row.id) {
+      case kDnm: rc = entry(famseq_trio_batch, famseq_trio_prior_batch, none, n_kids ? b : none, st); break;
+      case kMap: rc = entry(famseq_map_batch, famseq_map_prior_batch, a8, b, st); break;
+      case kSiteQ: rc = entry(famseq_evidence_batch, famseq_evidence_prior_batch, a, b, st); break;
+      case kLoo: rc = entry(famseq_loo_batch, famseq_loo_prior_batch, a, b, st); break;
+      case kSample: rc = entry(famseq_sample_batch, famseq_sample_prior_batch, o.seed, sl.site_base, (int32_t)o.sample, a8, none, st); break;
+      case kSeg: rc = entry(famseq_pattern_batch, famseq_pattern_prior_batch, seg_masks.data(), (int32_t)seg_keys.size(), a, none, st); break;
+    }
+    if (rc != 0) {
+      std::cerr << row.entry << (use_af ? "_prior_batch" : "_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
+      flush_ok = false;
+    }
+  }
+  void gpu_loop() {
     for (;;) {
       const int i = to_flusher.take();
       if (i < 0) break;
@@ -1697,155 +1829,35 @@ bool run_vcf(const Options &o, const Ped &ped) {
         t_ctx_wait = now_s() - tw;
         if (!ctx) flush_ok = false;
       }
+      const size_t n_staged = sl.pk_flags.size();
+      if (sl.staged && flush_ok && !pin(sl, n_staged)) flush_ok = false;
       if (sl.staged && flush_ok) {  // parsed before the runtime was up: into the pinned arrays now
-        const size_t nl_ = sl.pk_flags.size();
-        if (sl.io.cap < nl_) {
-          sl.io.release();
-          sl.io = PlBatch();
-          if (!sl.io.alloc(nl_, std::max<size_t>(n_seq, 1), as_text)) {
-            std::cerr << "cannot allocate pinned host buffers" << std::endl;
-            flush_ok = false;
-          }
-        }
-        if (flush_ok) {
-          std::memcpy(sl.io.pl, sl.pk_pl.data(), nl_ * 6 * n_seq);
-          std::memcpy(sl.io.flags, sl.pk_flags.data(), nl_);
-        }
+        std::memcpy(sl.io.pl, sl.pk_pl.data(), n_staged * 6 * n_seq);
+        std::memcpy(sl.io.flags, sl.pk_flags.data(), n_staged);
       }
       const double t0 = now_s();
       if (sl.n_sites > 0 && flush_ok) {
         const double *lk_in = sl.packed ? nullptr : sl.lk.data();
         const int rc = use_af ? famseq_bn_prior_call_batch(ctx, (int64_t)sl.n_sites, lk_in, lk_in ? nullptr : sl.io.pl, sl.io.flags, sl.prior.data(),
-                                                           seq_members.data(), (int32_t)n_seq, sl.io.gpp, sl.io.fpp, sl.io.fgt, sl.io.text, sl.io.status)
-                              : sl.io.call(ctx, sl.n_sites, lk_in, seq_members.data());
+                                                           cm.members.data(), (int32_t)n_seq, sl.io.gpp, sl.io.fpp, sl.io.fgt, sl.io.text, sl.io.status)
+                              : sl.io.call(ctx, sl.n_sites, lk_in, cm.members.data());
         if (rc != 0) {
           std::cerr << (use_af ? "famseq_bn_prior_call_batch" : "famseq_bn_call_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
           flush_ok = false;
         }
-        // the same batch through a side product's kernel (full network, whatever -LRC and -method say; -afTagAll: under the rows FPP
-        // and FGT were computed with): its plain or its site-prior entry, `name` the plain one's
-        auto side = [&](auto plain, auto with_prior, auto *out_a, double *out_b, vector<uint8_t> &status, const char *name) {
-          status.resize(sl.n_sites);
-          const double *lk = sl.packed ? nullptr : sl.lk.data();
-          const uint16_t *pl = sl.packed ? sl.io.pl : nullptr;
-          const int rc = use_af ? with_prior(ctx, (int64_t)sl.n_sites, lk, pl, seq_members.data(), (int32_t)n_seq, sl.io.flags, sl.prior.data(), out_a,
-                                             out_b, status.data())
-                                : plain(ctx, (int64_t)sl.n_sites, lk, pl, seq_members.data(), (int32_t)n_seq, sl.io.flags, out_a, out_b, status.data());
-          if (rc != 0) {
-            std::cerr << name << (use_af ? "_prior_batch" : "_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
-            flush_ok = false;
-          }
-        };
-        if (o.dnm && flush_ok) {
-          sl.dnm.resize(sl.n_sites * size_t(n_kids));
-          side(famseq_trio_batch, famseq_trio_prior_batch, (double *)nullptr, n_kids ? sl.dnm.data() : nullptr, sl.tstatus, "famseq_trio");
-        }
-        if (o.map && flush_ok) {
-          sl.jgt.resize(sl.n_sites * size_t(ped.n())), sl.jp.resize(sl.n_sites);
-          side(famseq_map_batch, famseq_map_prior_batch, sl.jgt.data(), sl.jp.data(), sl.jstatus, "famseq_map");
-        }
-        if (o.siteq && flush_ok) {
-          sl.fll.resize(sl.n_sites), sl.pref.resize(sl.n_sites);
-          side(famseq_evidence_batch, famseq_evidence_prior_batch, sl.fll.data(), sl.pref.data(), sl.estatus, "famseq_evidence");
-        }
-        if (o.loo && flush_ok) {
-          sl.loo.resize(sl.n_sites * size_t(ped.n()) * 3), sl.fit.resize(sl.n_sites * size_t(ped.n()));
-          side(famseq_loo_batch, famseq_loo_prior_batch, sl.loo.data(), sl.fit.data(), sl.lstatus, "famseq_loo");
-        }
-        if (o.sample && flush_ok) {  // (seed, the block's first site and the draws ride between the input and the outputs)
-          sl.sgt.resize(sl.n_sites * size_t(o.sample) * size_t(ped.n()));
-          const uint64_t seed = o.seed;
-          const int64_t base = sl.site_base;
-          const int32_t nd = o.sample;
-          side([=](famseq_ctx *c, int64_t n, const double *lk, const uint16_t *pl, const int32_t *seq, int32_t ns, const uint8_t *fl, int8_t *a,
-                   double *b, uint8_t *st) { return famseq_sample_batch(c, n, lk, pl, seq, ns, fl, seed, base, nd, a, b, st); },
-               [=](famseq_ctx *c, int64_t n, const double *lk, const uint16_t *pl, const int32_t *seq, int32_t ns, const uint8_t *fl,
-                   const double *prior, int8_t *a, double *b, uint8_t *st) {
-                 return famseq_sample_prior_batch(c, n, lk, pl, seq, ns, fl, prior, seed, base, nd, a, b, st);
-               },
-               sl.sgt.data(), (double *)nullptr, sl.sstatus, "famseq_sample");
-        }
-        if (n_seg && flush_ok) {  // (the masks ride between the input and the outputs of both entries)
-          sl.ppat.resize(sl.n_sites * n_seg);
-          const uint8_t *mk = seg_masks.data();
-          const int32_t np = (int32_t)n_seg;
-          side([=](famseq_ctx *c, int64_t n, const double *lk, const uint16_t *pl, const int32_t *seq, int32_t ns, const uint8_t *fl, double *a,
-                   double *b, uint8_t *st) { return famseq_pattern_batch(c, n, lk, pl, seq, ns, fl, mk, np, a, b, st); },
-               [=](famseq_ctx *c, int64_t n, const double *lk, const uint16_t *pl, const int32_t *seq, int32_t ns, const uint8_t *fl,
-                   const double *prior, double *a, double *b, uint8_t *st) {
-                 return famseq_pattern_prior_batch(c, n, lk, pl, seq, ns, fl, prior, mk, np, a, b, st);
-               },
-               sl.ppat.data(), (double *)nullptr, sl.pstatus, "famseq_pattern");
-        }
+        for (const SideRow *row : sides)
+          if (flush_ok) call_side(*row, sl);
       }
       t_gpu += now_s() - t0;
       to_formatter.put(i);
     }
     to_formatter.put(-1);
-  });
-  // -dnm: ":<DNP>" before the closing tab of sample j's field — "." for a founder, NA where the site or its trio posteriors failed
-  auto put_dnp = [&](TextBuf &out, const Slot &sl, size_t s, size_t j, bool failed) {
-    --out.n;
-    out.ch(':');
-    const int kid = kid_of_col[j];
-    if (failed) out.put("NA", 2);
-    else if (kid < 0) out.ch('.');
-    else if (sl.tstatus[s] != 0) out.put("NA", 2);
-    else out.num(sl.dnm[s * size_t(n_kids) + size_t(kid)]);
-    out.ch('\t');
-  };
-  // -map: ":<JGT>:<JP>" before the closing tab of sample j's field — NA:NA where the site or its MAP failed
-  auto put_map = [&](TextBuf &out, const Slot &sl, size_t s, size_t j, bool failed) {
-    --out.n;
-    out.ch(':');
-    if (failed || sl.jstatus[s] != 0) {
-      out.put("NA:NA", 5);
-    } else {
-      const int gt = sl.jgt[s * size_t(ped.n()) + size_t(seq_members[j])];
-      out.put(gt == 0 ? "0/0:" : (gt == 1 ? "0/1:" : "1/1:"), 4);
-      out.num(sl.jp[s]);
-    }
-    out.ch('\t');
-  };
-  // -loo: ":<LOP>:<LOF>" before the closing tab of sample j's field — NA:NA where the site or its leave-one-out kernel failed.
-  // Both by the drivers' rule for FPP: fabs(-10 log10 p), 99999 for 0 (file.cpp:696-745).
-  auto put_loo = [&](TextBuf &out, const Slot &sl, size_t s, size_t j, bool failed) {
-    --out.n;
-    out.ch(':');
-    if (failed || sl.lstatus[s] != 0) {
-      out.put("NA:NA", 5);
-    } else {
-      auto phred = [](double p) { return p == 0 ? 99999.0 : std::fabs(-10.0 * std::log10(p)); };
-      const size_t mem = s * size_t(ped.n()) + size_t(seq_members[j]);
-      for (int g = 0; g < 3; ++g) {
-        out.num(phred(sl.loo[3 * mem + size_t(g)]));
-        out.ch(g < 2 ? ',' : ':');
-      }
-      out.num(phred(sl.fit[mem]));
-    }
-    out.ch('\t');
-  };
-  // -sample: ":<SGT>" before the closing tab of sample j's field, the draws' alt-allele counts comma-separated, draw 0 first — NA
-  // where the site or its sampling kernel failed
-  auto put_sgt = [&](TextBuf &out, const Slot &sl, size_t s, size_t j, bool failed) {
-    --out.n;
-    out.ch(':');
-    if (failed || sl.sstatus[s] != 0) {
-      out.put("NA", 2);
-    } else {
-      const int8_t *g = &sl.sgt[s * size_t(o.sample) * size_t(ped.n()) + size_t(seq_members[j])];
-      for (int k = 0; k < o.sample; ++k) {
-        if (k) out.ch(',');
-        out.ch(char('0' + g[size_t(k) * size_t(ped.n())]));
-      }
-    }
-    out.ch('\t');
-  };
+  }
+
   // -siteQ, -seg: columns 1-8 + FORMAT of a site with "FQ=<x>;FLL=<y>" and / or "PSD=<p>;PSR=<q>" joined to its INFO column (an
   // INFO of "." is replaced); a site whose evidence (pattern kernel) failed does without those keys, and keeps its INFO where none
-  // is left to add.  FQ by the drivers' rule for FPP: fabs(-10 log10 p), 99999 for 0 (file.cpp:696-745); PSD and PSR are plain
-  // probabilities — the value of interest is near 1, where Phred has no resolution.
-  auto put_prefix_info = [&](TextBuf &out, const Slot &sl, size_t s, const char *raw, size_t len) {
+  // is left to add.
+  void put_prefix_info(TextBuf &out, const Slot &sl, size_t s, const char *raw, size_t len) const {
     size_t info = 0, end = 0;  // the INFO column is raw[info, end): between the seventh and the eighth tab
     int tabs = 0;
     for (size_t q = 0; q < len && tabs < 8; ++q)
@@ -1853,8 +1865,9 @@ bool run_vcf(const Options &o, const Ped &ped) {
         if (++tabs == 7) info = q + 1;
         if (tabs == 8) end = q;
       }
-    const bool add_q = o.siteq && sl.estatus[s] == 0, add_seg = n_seg && sl.pstatus[s] == 0;
-    if (tabs < 8 || !(add_q || add_seg)) {
+    bool any = false;
+    for (const SideRow *row : infos) any = any || sl.side[row->id].status[s] == 0;
+    if (tabs < 8 || !any) {
       out.put(raw, len);
       return;
     }
@@ -1863,91 +1876,76 @@ bool run_vcf(const Options &o, const Ped &ped) {
       out.put(raw + info, end - info);
       if (end > info) out.ch(';');
     }
-    if (add_q) {
-      const double p = sl.pref[s];
-      out.put("FQ=", 3);
-      out.num(p == 0 ? 99999.0 : std::fabs(-10.0 * std::log10(p)));
-      out.put(";FLL=", 5);
-      out.num(sl.fll[s]);
-    }
-    for (size_t m = 0; add_seg && m < n_seg; ++m) {
-      if (add_q || m) out.ch(';');
-      out.put(seg_keys[m], 4);
-      out.num(sl.ppat[s * n_seg + m]);
+    bool first = true;
+    for (const SideRow *row : infos) {
+      if (sl.side[row->id].status[s] != 0) continue;
+      if (!first) out.ch(';');
+      first = false;
+      put_side(row->id, out, *this, sl.side[row->id], s, 0);
     }
     out.put(raw + end, len - end);
-  };
+  }
+  // the text of part t of a block, the lines that thread t parsed.  bare: no side field, the sample's text closes its column itself
+  template <bool bare>
+  void format_part(Slot &sl, int t) const {
+    Part &pt = sl.parts[t];
+    TextBuf &out = sl.text[t];
+    out.n = 0;
+    const size_t k = n_seq;
+    for (const Item &it : pt.items) {
+      if (it.site < 0) {
+        out.put(pt.echo.data() + it.echo_off, it.echo_len);
+      } else {
+        const size_t s = size_t(it.site);
+        const Record::Sample *sm = &pt.samples[it.smp];
+        if (infos.empty()) out.put(it.raw, it.prefix_len);  // columns 1-8 + FORMAT
+        else put_prefix_info(out, sl, s, it.raw, it.prefix_len);
+        out.put(format_keys);
+        if (sl.io.status[s] & 3) {  // file.cpp:607-620
+          pt.any_failed = true;
+          for (size_t j = 0; j < k; ++j) {
+            out.put(it.raw + sm[j].off, sm[j].len);
+            out.put(":NA:NA:NA\t", bare ? 10 : 9);
+            if (bare) continue;
+            for (const SideRow *row : fields) out.put(row->na);
+            out.ch('\t');
+          }
+        } else {
+          for (size_t j = 0; j < k; ++j) {
+            if (sm[j].missing) {
+              for (uint32_t q = 0; q < it.n_fmt; ++q) out.put("NA:", 3);
+            } else {
+              out.put(it.raw + sm[j].off, sm[j].len);
+              out.ch(':');
+            }
+            out.called(sl.io.text, sl.io.gpp, sl.io.fpp, sl.io.fgt, s * k + j, bare);
+            if (bare) continue;
+            for (const SideRow *row : fields) put_side(row->id, out, *this, sl.side[row->id], s, j);
+            out.ch('\t');
+          }
+        }
+      }
+      out.ch('\n');
+    }
+  }
   // ... the results are turned into text on their own thread (and its helpers) while the next block is at the GPU ...
-  std::thread formatter([&] {
+  void format_loop() {
     for (;;) {
       const int i = to_formatter.take();
       if (i < 0) break;
       Slot &sl = slots[i];
-      const size_t k = n_seq;
       const double t1 = now_s();
       if (flush_ok) {
-        on_parts(sl.n_parts, format_threads, [&](int t) {
-          Part &pt = sl.parts[t];
-          TextBuf &out = sl.text[t];
-          out.n = 0;
-          for (const Item &it : pt.items) {
-            if (it.site < 0) {
-              out.put(pt.echo.data() + it.echo_off, it.echo_len);
-            } else {
-              const size_t s = size_t(it.site);
-              const Record::Sample *sm = &pt.samples[it.smp];
-              if (o.siteq || n_seg) put_prefix_info(out, sl, s, it.raw, it.prefix_len);
-              else out.put(it.raw, it.prefix_len);  // columns 1-8 + FORMAT
-              out.put(":GPP:FPP:FGT", 12);
-              if (o.dnm) out.put(":DNP", 4);
-              if (o.map) out.put(":JGT:JP", 7);
-              if (o.loo) out.put(":LOP:LOF", 8);
-              if (o.sample) out.put(":SGT", 4);
-              out.ch('\t');
-              if (sl.io.status[s] & 3) {  // file.cpp:607-620
-                pt.any_failed = true;
-                for (size_t j = 0; j < k; ++j) {
-                  out.put(it.raw + sm[j].off, sm[j].len);
-                  out.put(":NA:NA:NA\t", 10);
-                  if (o.dnm) put_dnp(out, sl, s, j, true);
-                  if (o.map) put_map(out, sl, s, j, true);
-                  if (o.loo) put_loo(out, sl, s, j, true);
-                  if (o.sample) put_sgt(out, sl, s, j, true);
-                }
-              } else {
-                for (size_t j = 0; j < k; ++j) {
-                  if (sm[j].missing) {
-                    for (uint32_t q = 0; q < it.n_fmt; ++q) out.put("NA:", 3);
-                  } else {
-                    out.put(it.raw + sm[j].off, sm[j].len);
-                    out.ch(':');
-                  }
-                  if (sl.io.text) {
-                    out.record(sl.io.text + (s * k + j) * FAMSEQ_TEXT_STRIDE);
-                  } else {
-                    out.triples(&sl.io.gpp[(s * k + j) * 3], &sl.io.fpp[(s * k + j) * 3]);
-                    const int gt = sl.io.fgt[s * k + j];
-                    out.put(gt == 0 ? "0/0\t" : (gt == 1 ? "0/1\t" : "1/1\t"), 4);
-                  }
-                  if (o.dnm) put_dnp(out, sl, s, j, false);
-                  if (o.map) put_map(out, sl, s, j, false);
-                  if (o.loo) put_loo(out, sl, s, j, false);
-                  if (o.sample) put_sgt(out, sl, s, j, false);
-                }
-              }
-            }
-            out.ch('\n');
-          }
-        });
+        on_parts(sl.n_parts, format_threads, [&](int t) { fields.empty() ? format_part<true>(sl, t) : format_part<false>(sl, t); });
         t_format += now_s() - t1;
       }
       to_writer.put(i);
     }
     to_writer.put(-1);
-  });
+  }
   // ... and the text goes out on a third thread, so that block k + 1 is at the GPU and being formatted while block k is
   // written (formatting 0.50 s + writing 0.25 s per 3 M ten-member sites were one thread's work in round 2)
-  std::thread writer([&] {
+  void write_loop() {
     for (;;) {
       const int i = to_writer.take();
       if (i < 0) break;
@@ -1971,160 +1969,210 @@ bool run_vcf(const Options &o, const Ped &ped) {
       }
       to_driver.put(i);
     }
-  });
+  }
+};
 
-  const double t_begin = now_s();
-  to_driver.put(0), to_driver.put(1), to_driver.put(2), to_driver.put(3);
-  bool more = have_line;
-  uint64_t sites_before = 0;  // sites of the blocks cut so far
-  while (more && ok && flush_ok) {
-    double t0 = now_s();
-    const int i = to_driver.take();  // a slot whose previous block is written
-    Slot &sl = slots[i];
-    double t1 = now_s();
-    t_stall += t1 - t0;
-    sl.lines.clear();
-    while (more && sl.lines.size() < block) {  // `line` holds the next unread line
-      if (line.size() < 2) {                   // the reference stops at the first empty line
-        more = false;
-        break;
-      }
-      sl.lines.push_back(line);
-      more = fin.next(line);
+// ---- the rows.  A field's text by the drivers' rule for FPP where it is Phred-scaled: fabs(-10 log10 p), 99999 for 0
+// (file.cpp:696-745); a field whose own kernel failed at the site prints what a failed site prints.
+double phred(double p) { return p == 0 ? 99999.0 : std::fabs(-10.0 * std::log10(p)); }
+
+inline void put_dnp(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {  // "." for a founder
+  const int kid = r.kid_of_col[j];
+  if (kid < 0) return out.put(":.", 2);
+  if (so.status[s] != 0) return out.put(":NA", 3);
+  out.ch(':');
+  out.num(so.b[s * size_t(r.n_kids) + size_t(kid)]);
+}
+inline void put_map(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {
+  if (so.status[s] != 0) return out.put(":NA:NA", 6);
+  const int gt = so.a8()[s * size_t(r.ped.n()) + size_t(r.cm.members[j])];
+  out.put(gt == 0 ? ":0/0:" : (gt == 1 ? ":0/1:" : ":1/1:"), 5);
+  out.num(so.b[s]);
+}
+inline void put_loo(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {
+  if (so.status[s] != 0) return out.put(":NA:NA", 6);
+  const size_t mem = s * size_t(r.ped.n()) + size_t(r.cm.members[j]);
+  for (int g = 0; g < 3; ++g) {
+    out.ch(g ? ',' : ':');
+    out.num(phred(so.a[3 * mem + size_t(g)]));
+  }
+  out.ch(':');
+  out.num(phred(so.b[mem]));
+}
+inline void put_sgt(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {  // the draws' alt-allele counts, draw 0 first
+  if (so.status[s] != 0) return out.put(":NA", 3);
+  const size_t n = size_t(r.ped.n());
+  const int8_t *g = so.a8() + s * size_t(r.o.sample) * n + size_t(r.cm.members[j]);
+  for (int k = 0; k < r.o.sample; ++k) {
+    out.ch(k ? ',' : ':');
+    out.ch(char('0' + g[size_t(k) * n]));
+  }
+}
+inline void put_fq(TextBuf &out, const VcfRun &, const SideOut &so, size_t s, size_t) {
+  out.put("FQ=", 3);
+  out.num(phred(so.b[s]));
+  out.put(";FLL=", 5);
+  out.num(so.a[s]);
+}
+// (plain probabilities: the value of interest is near 1, where Phred has no resolution)
+inline void put_seg(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t) {
+  const size_t n_seg = r.seg_keys.size();
+  for (size_t m = 0; m < n_seg; ++m) {
+    if (m) out.ch(';');
+    out.put(r.seg_keys[m], 4);
+    out.num(so.a[s * n_seg + m]);
+  }
+}
+
+[[gnu::always_inline]] inline void put_side(SideId id, TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {
+  switch (id) {
+    case kDnm: return put_dnp(out, r, so, s, j);
+    case kMap: return put_map(out, r, so, s, j);
+    case kSiteQ: return put_fq(out, r, so, s, j);
+    case kLoo: return put_loo(out, r, so, s, j);
+    case kSample: return put_sgt(out, r, so, s, j);
+    case kSeg: return put_seg(out, r, so, s, j);
+  }
+}
+
+// -seg's own options: -affected / -unaffected without it, an unknown model or ID
+bool check_seg(const Options &o, const Ped &ped) {
+  if (o.seg.empty()) {
+    std::cout << "-affected and -unaffected belong to -seg dominant|recessive|both, which was not given." << std::endl;
+    return false;
+  }
+  vector<uint8_t> masks;
+  vector<const char *> keys;
+  return segregation_masks(o, ped, masks, keys);
+}
+
+const SideRow kSide[kSides] = {
+    {kDnm, "-dnm", "famseq_trio", false, [](const Options &o) { return o.dnm; }, [](Options &o) { o.dnm = false; }, nullptr,
+     [](std::ostream &out, const Options &) {
+       out << "##FORMAT=<ID=DNP,Number=1,Type=Float,Description=\"Posterior probability of a de novo mutation (genotype "
+              "Mendelian-inconsistent with the parents')\">" << std::endl;
+     },
+     ":DNP", ":NA", [](const VcfRun &r) { return SideBytes{0, 8 * size_t(r.n_kids)}; }},
+    {kMap, "-map", "famseq_map", false, [](const Options &o) { return o.map; }, [](Options &o) { o.map = false; }, nullptr,
+     [](std::ostream &out, const Options &) {
+       out << "##FORMAT=<ID=JGT,Number=1,Type=String,Description=\"Genotype in the most probable joint genotype configuration of "
+              "the whole family\">" << std::endl;
+       out << "##FORMAT=<ID=JP,Number=1,Type=Float,Description=\"Posterior probability of that joint configuration\">" << std::endl;
+     },
+     ":JGT:JP", ":NA:NA", [](const VcfRun &r) { return SideBytes{size_t(r.ped.n()), 8}; }},
+    {kSiteQ, "-siteQ", "famseq_evidence", true, [](const Options &o) { return o.siteq; }, [](Options &o) { o.siteq = false; }, nullptr,
+     [](std::ostream &out, const Options &) {
+       out << "##INFO=<ID=FQ,Number=1,Type=Float,Description=\"Family variant quality: Phred-scaled posterior probability that every "
+              "member of the family is homozygous reference\">" << std::endl;
+       out << "##INFO=<ID=FLL,Number=1,Type=Float,Description=\"log10 likelihood of the site's data under the pedigree\">" << std::endl;
+     },
+     nullptr, nullptr, [](const VcfRun &) { return SideBytes{8, 8}; }},
+    {kLoo, "-loo", "famseq_loo", true, [](const Options &o) { return o.loo; }, [](Options &o) { o.loo = false; }, nullptr,
+     [](std::ostream &out, const Options &) {
+       out << "##FORMAT=<ID=LOP,Number=G,Type=Float,Description=\"Phred-scaled genotype probabilities given the data of every other "
+              "member of the family, the sample's own left out\">" << std::endl;
+       out << "##FORMAT=<ID=LOF,Number=1,Type=Float,Description=\"Phred-scaled predictive likelihood of the sample's data given the "
+              "other members' (99999: impossible given the relatives)\">" << std::endl;
+     },
+     ":LOP:LOF", ":NA:NA", [](const VcfRun &r) { return SideBytes{24 * size_t(r.ped.n()), 8 * size_t(r.ped.n())}; }},
+    {kSample, "-sample", "famseq_sample", false, [](const Options &o) { return o.sample != 0; }, [](Options &o) { o.sample = 0; }, nullptr,
+     [](std::ostream &out, const Options &o) {
+       out << "##FORMAT=<ID=SGT,Number=.,Type=Integer,Description=\"Alternate allele counts of the sample in " << o.sample
+           << " joint genotype configurations of the whole family drawn from their posterior (seed " << o.seed << ")\">" << std::endl;
+     },
+     ":SGT", ":NA", [](const VcfRun &r) { return SideBytes{size_t(r.o.sample) * size_t(r.ped.n()), 0}; }},
+    // (on: any of its three options, so that main can say which one is missing)
+    {kSeg, "-seg", "famseq_pattern", true, [](const Options &o) { return !(o.seg.empty() && o.affected.empty() && o.unaffected.empty()); },
+     [](Options &o) { o.seg.clear(), o.affected.clear(), o.unaffected.clear(); }, check_seg,
+     [](std::ostream &out, const Options &o) {
+       if (o.seg != "recessive")
+         out << "##INFO=<ID=PSD,Number=1,Type=Float,Description=\"Posterior probability that the affected members, and no unaffected one, "
+                "carry the variant (dominant segregation pattern)\">" << std::endl;
+       if (o.seg != "dominant")
+         out << "##INFO=<ID=PSR,Number=1,Type=Float,Description=\"Posterior probability that the affected members, and no unaffected one, "
+                "are homozygous for the variant (recessive segregation pattern)\">" << std::endl;
+     },
+     nullptr, nullptr, [](const VcfRun &r) { return SideBytes{8 * r.seg_keys.size(), 0}; }},
+};
+
+// `FamSeq vcf` and `FamSeq pack`: the wiring of a VcfRun's stages
+bool run_vcf(const Options &o, const Ped &ped) {
+  VcfRun r{o, ped};
+  if (!r.fin.open(o.vcf_files[0])) {
+    std::cout << "Cannot open " << o.vcf_files[0] << std::endl;
+    return false;
+  }
+  if (!r.set_up()) return false;
+  if (!o.pack_mode) r.fout.open(o.out_file.c_str());  // pack mode writes a binary file: the text header goes nowhere
+  std::string_view line;
+  bool more = false;  // `line` holds a data line that has not been cut into a block yet
+  const vector<string> head = split_keep(r.echo_header(line, more), '\t');
+  if (!r.map_header(head)) return false;
+  if (!o.loc_file.empty() && !r.read_locations()) return false;
+  if (o.pack_mode) {
+    vector<string> names;
+    for (int c : r.cm.cols) names.push_back(head[9 + c]);
+    if (names.empty() || !r.packer.open(o.out_file, names)) {
+      std::cout << "Cannot write " << o.out_file << " (or no sample of the vcf file is in the ped file)." << std::endl;
+      return false;
     }
-    const size_t nl = sl.lines.size();
-    if (nl == 0) {
-      to_driver.put(i);
+  } else if (r.cm.cols.empty()) {  // nothing to compute and nothing to print per sample: say so instead of walking the file
+    std::cout << "No sample of the vcf file is in the ped file (the names in the ped file's fifth column must match the vcf header)." << std::endl;
+    return false;
+  }
+  // HIP start-up (runtime initialisation, context, streams, code objects: about a quarter of a second) runs on its own
+  // thread while this one cuts and parses the first block(s); the flusher thread, the first to need the context, waits for it.
+  // Until it is there the blocks are parsed into ordinary memory (pinned buffers need the runtime) and copied over — 6 bytes
+  // per sample and site — once it is.
+  if (!o.pack_mode)
+    r.ctx_future = std::async(std::launch::async, [&] {
+      famseq_ctx *c = make_ctx(o, ped, r.cm.sequenced, r.m);
+      r.hip_up = true;
+      return c;
+    });
+  std::thread flusher([&] { r.gpu_loop(); }), formatter([&] { r.format_loop(); }), writer([&] { r.write_loop(); });
+  const double t_begin = now_s();
+  for (int i = 0; i < 4; ++i) r.to_driver.put(i);
+  bool ok = true;
+  while (more && ok && r.flush_ok) {
+    const double t0 = now_s();
+    const int i = r.to_driver.take();  // a slot whose previous block is written
+    Slot &sl = r.slots[i];
+    r.t_stall += now_s() - t0;
+    if (!r.cut_and_parse(sl, line, more, &ok)) {
+      r.to_driver.put(i);
       break;
     }
-    sl.n_parts = nl < 2048 ? 1 : (int)n_threads;
-    double t2 = now_s();
-    t_lines += t2 - t1;
-    sl.staged = !o.pack_mode && !hip_up;
-    if (o.pack_mode || sl.staged) {
-      sl.pk_pl.resize(nl * 3 * n_seq), sl.pk_flags.resize(nl);
-    } else if (sl.io.cap < nl) {  // pinned, sized by the first block (a short file does not pay for 65,536 sites)
-      sl.io.release();
-      sl.io = PlBatch();
-      if (!sl.io.alloc(nl, std::max<size_t>(n_seq, 1), as_text)) {
-        std::cerr << "cannot allocate pinned host buffers" << std::endl;
-        ok = false;
-        to_driver.put(i);
-        break;
-      }
+    const double t3 = now_s();
+    if (o.pack_mode) {
+      r.pack_records(sl);
+    } else {
+      r.move_sites_together(sl);
+      if (!sl.packed) r.build_lk_rows(sl);
     }
-    uint16_t *const pl_arr = o.pack_mode || sl.staged ? sl.pk_pl.data() : sl.io.pl;
-    uint8_t *const flags_arr = o.pack_mode || sl.staged ? sl.pk_flags.data() : sl.io.flags;
-    if (use_af) sl.prior.resize(nl * 6);
-    double *const prior_arr = use_af ? sl.prior.data() : nullptr;
-    on_parts(sl.n_parts, parse_threads, [&](int t) {
-      Part &pt = sl.parts[t];
-      pt.clear();
-      const size_t lo = nl * t / sl.n_parts, hi = nl * (t + 1) / sl.n_parts;
-      std::memset(flags_arr + lo, 0, hi - lo);
-      for (size_t q = lo; prior_arr && q < hi; ++q) std::copy(model_rows[0], model_rows[0] + 6, prior_arr + 6 * q);
-      std::memset(pl_arr + lo * 3 * n_seq, 0xFF, (hi - lo) * 6 * n_seq);  // 0xFFFF x3 = missing sample
-      for (size_t q = lo; q < hi; ++q) parse_line(sl.lines[q], q, pt, flags_arr + q, pl_arr + q * 3 * n_seq, prior_arr ? prior_arr + 6 * q : nullptr);
-    });
-    double t3 = now_s();
-    t_parse += t3 - t2;
-    bool packed = true;
-    size_t real = 0;
-    for (int t = 0; t < sl.n_parts; ++t) {
-      packed = packed && sl.parts[t].explicit_sites.empty();
-      real += sl.parts[t].samples.size();
-    }
-    sl.n_sites = real ? nl : 0, sl.packed = packed;  // a block without a single site (or without a sequenced sample) calls nothing
-    if (o.pack_mode) {  // records of the integer sites, in input order; nothing goes to the GPU
-      for (int t = 0; t < sl.n_parts; ++t) {
-        const Part &pt = sl.parts[t];
-        size_t x = 0;
-        for (const Item &it : pt.items) {
-          if (it.site < 0) continue;
-          if (x < pt.explicit_sites.size() && pt.explicit_sites[x] == uint32_t(it.site)) {
-            ++x, packer.skipped++;
-            continue;
-          }
-          packer.add(flags_arr[it.site], pl_arr + size_t(it.site) * 3 * n_seq);
-        }
-      }
-      t_gather += now_s() - t3;
-      to_driver.put(i);
-      continue;
-    }
-    // A line that is no site costs the GPU a site's work: nothing next to the text work for the usual pedigree, but
-    // 3^N configurations each.  From twelve members on (0.5 M configurations) the sites are moved together first —
-    // in place and in order, one thread: 60 bytes per site.
-    size_t n_real = 0;
-    for (int t = 0; t < sl.n_parts; ++t)
-      for (const Item &it : sl.parts[t].items) n_real += it.site >= 0;
-    // (-sample: always, so that a site's position in the batch is its position among the block's sites)
-    if (n_real > 0 && n_real < nl && (ped.n() >= compact_from || o.sample)) {
-      size_t d = 0;
-      for (int t = 0; t < sl.n_parts; ++t) {
-        Part &pt = sl.parts[t];
-        size_t x = 0;
-        for (Item &it : pt.items) {
-          if (it.site < 0) continue;
-          const size_t q = size_t(it.site);
-          if (d != q) {
-            flags_arr[d] = flags_arr[q];
-            std::memmove(pl_arr + d * 3 * n_seq, pl_arr + q * 3 * n_seq, 6 * n_seq);
-            if (prior_arr) std::memmove(prior_arr + 6 * d, prior_arr + 6 * q, 48);
-          }
-          if (x < pt.explicit_sites.size() && pt.explicit_sites[x] == q) pt.explicit_sites[x++] = uint32_t(d);
-          it.site = int32_t(d++);
-        }
-      }
-      sl.n_sites = d;
-    }
-    sl.site_base = (int64_t)sites_before;  // -sample: a site's index is its ordinal among the file's sites, whatever the blocks
-    sites_before += n_real;
-    if (!packed) {
-      // fp64 rows: the table's value for every integer field (what the parser computed for it), the parsed rows of the others
-      const size_t n = sl.n_sites;
-      sl.lk.resize(n * N3);
-      on_threads(sl.n_parts, [&](int t) {
-        const size_t lo = n * t / sl.n_parts, hi = n * (t + 1) / sl.n_parts;
-        double *rows = sl.lk.data();
-        std::fill(rows + lo * N3, rows + hi * N3, 1.0);
-        for (size_t q = lo; q < hi; ++q)
-          for (size_t j = 0; j < n_seq; ++j) {
-            const uint16_t *p = &pl_arr[(q * n_seq + j) * 3];
-            if (p[0] == 0xFFFF && p[1] == 0xFFFF && p[2] == 0xFFFF) continue;
-            for (int g = 0; g < 3; ++g) rows[q * N3 + size_t(3) * seq_members[j] + g] = pl.value(p[g]);
-          }
-      });
-      for (int t = 0; t < sl.n_parts; ++t) {
-        const Part &pt = sl.parts[t];
-        for (size_t x = 0; x < pt.explicit_sites.size(); ++x)
-          std::copy(&pt.explicit_lk[x * N3], &pt.explicit_lk[(x + 1) * N3], sl.lk.data() + size_t(pt.explicit_sites[x]) * N3);
-      }
-    }
-    t_gather += now_s() - t3;
-    to_flusher.put(i);
+    r.t_gather += now_s() - t3;
+    (o.pack_mode ? r.to_driver : r.to_flusher).put(i);
   }
-  to_flusher.put(-1);
+  r.to_flusher.put(-1);
   flusher.join();
   formatter.join();
   writer.join();
-  if (!ctx && ctx_future.valid()) ctx = ctx_future.get();  // a file without a single data line: nobody asked for it yet
-  ok = ok && flush_ok && (o.pack_mode || ctx);
+  if (!r.ctx && r.ctx_future.valid()) r.ctx = r.ctx_future.get();  // a file without a single data line: nobody asked for it yet
+  ok = ok && r.flush_ok && (o.pack_mode || r.ctx);
   if (std::getenv("FAMSEQ_TIMING") && !o.pack_mode)
-    std::cerr << "FamSeq vcf: loop " << now_s() - t_begin << " s; this thread: cutting lines " << t_lines << ", parsing " << t_parse
-              << ", fp64 rows / pack records " << t_gather << ", waiting for the flusher " << t_stall << "; flusher thread: GPU calls " << t_gpu
-              << ", formatting " << t_format << ", writing " << t_write << ", waiting for the context " << t_ctx_wait << std::endl;
-  if (!o.pack_mode)
-    for (Slot &sl : slots) sl.io.release();
+    std::cerr << "FamSeq vcf: loop " << now_s() - t_begin << " s; this thread: cutting lines " << r.t_lines << ", parsing " << r.t_parse
+              << ", fp64 rows / pack records " << r.t_gather << ", waiting for the flusher " << r.t_stall << "; flusher thread: GPU calls " << r.t_gpu
+              << ", formatting " << r.t_format << ", writing " << r.t_write << ", waiting for the context " << r.t_ctx_wait << std::endl;
   if (o.pack_mode) {
-    std::cout << packer.n_sites << " sites packed";
-    if (packer.skipped) std::cout << ", " << packer.skipped << " skipped (PL/GL field is not a plain integer)";
+    std::cout << r.packer.n_sites << " sites packed";
+    if (r.packer.skipped) std::cout << ", " << r.packer.skipped << " skipped (PL/GL field is not a plain integer)";
     std::cout << std::endl;
-    return packer.close();
+    return r.packer.close();
   }
-  fout.close();
-  famseq_destroy(ctx);
-  return ok && !fout.fail();
+  for (Slot &sl : r.slots) sl.io.release();
+  r.fout.close();
+  famseq_destroy(r.ctx);
+  return ok && !r.fout.fail();
 }
 
 // ---- LK driver (file.cpp:1640-1886) ----------------------------------------------------------
@@ -2138,47 +2186,24 @@ bool run_lk(const Options &o, const Ped &ped) {
   string title, line;
   std::getline(fin, title);
   const vector<string> head = split_keep(title, '\t');
-  vector<int> v2p(head.size(), -1);
-  vector<uint8_t> sequenced(ped.n(), 0);
-  for (size_t i = 0; i < head.size(); i++)
-    for (int j = 0; j < ped.n(); j++)
-      if (head[i] == ped.name[j]) {
-        v2p[i] = j;
-        sequenced[j] = 1;
-        break;
-      }
+  const ColumnMap cm = map_columns(head.data(), head.size(), ped);
   CliModel m;
-  famseq_ctx *ctx = make_ctx(o, ped, sequenced, m);
+  famseq_ctx *ctx = make_ctx(o, ped, cm.sequenced, m);
   if (!ctx) return false;
   std::ofstream fout(o.out_file.c_str());
-  fout << "##FORMAT=<ID=GPP,Number=G,Type=Integer,Description=\"Normalized, Phred-scaled for posterior probability "
-          "calculated by individual-base Method\">" << std::endl;
-  fout << "##FORMAT=<ID=FPP,Number=G,Type=Integer,Description=\"Normalized, Phred-scaled for posterior probability "
-          "calculated by FamSeqPro\">" << std::endl;
-  fout << "##FORMAT=<ID=FGT,Number=1,Type=String,Description=\"Genotype called by FamSeqPro\">" << std::endl;
-  fout << "##FS mutation rate=" << o.mrate << " " << std::endl;
-  fout << "##FS genotype frequency in pupulation: "; put_triple(fout, m.p.genoProbN); fout << std::endl;
-  vector<int> seq_cols, seq_members;
-  fout << "#FORMAT\t";
-  for (size_t i = 0; i < head.size(); i++)
-    if (v2p[i] >= 0) {
-      seq_cols.push_back((int)i);
-      seq_members.push_back(v2p[i]);
-      fout << head[i] << '\t';
-    }
-  fout << std::endl;
-  BatchCaller caller(ctx, ped.n(), seq_members, fout, batch_capacity());
+  put_lk_header(fout, o, m, head, cm.cols);
+  BatchCaller caller(ctx, ped.n(), cm.members, fout, batch_capacity());
   vector<double> lk(size_t(3) * ped.n());
   bool ok = true;
   while (ok && std::getline(fin, line)) {
     if (line.size() < 2) break;
     vector<std::string_view> t;
     split_views(line, '\t', t);
-    if (!seq_cols.empty() && t.size() <= size_t(seq_cols.back())) continue;  // short row
+    if (!cm.cols.empty() && t.size() <= size_t(cm.cols.back())) continue;  // short row
     std::fill(lk.begin(), lk.end(), 1.0);
     Record r;
     r.head = "LK:GPP:FPP:FGT\t";
-    for (int c : seq_cols) {
+    for (int c : cm.cols) {
       r.samples.push_back({uint32_t(t[c].data() - line.data()), uint32_t(t[c].size()), false});
       const vector<string> v = split_keep(string(t[c]), ',');
       for (int g = 0; g < 3 && g < (int)v.size(); g++) {
@@ -2186,7 +2211,7 @@ bool run_lk(const Options &o, const Ped &ped) {
         if (o.lk_type == 2) x = std::pow(10.0, x);
         else if (o.lk_type == 3) x = std::exp(x);
         else if (o.lk_type == 4) x = std::pow(10.0, -x / 10.0);
-        lk[size_t(3) * v2p[c] + g] = x;
+        lk[size_t(3) * cm.member[c] + g] = x;
       }
     }
     r.raw = line;
@@ -2209,12 +2234,9 @@ bool run_tune(const Options &o, const Ped &ped) {
   string title;
   while (fin.next(line) && !line.empty() && line[0] == '#') title.assign(line);
   const vector<string> head = split_keep(title, '\t');
-  vector<uint8_t> sequenced(ped.n(), 0);
-  for (size_t i = 9; i < head.size(); i++)
-    for (int j = 0; j < ped.n(); j++)
-      if (head[i] == ped.name[j]) sequenced[j] = 1;
+  const size_t first = std::min<size_t>(9, head.size());
   CliModel m;
-  famseq_ctx *ctx = make_ctx(o, ped, sequenced, m);
+  famseq_ctx *ctx = make_ctx(o, ped, map_columns(head.data() + first, head.size() - first, ped).sequenced, m);
   if (!ctx) return false;
   const int rc = famseq_set_option(ctx, "tune", 1);
   if (rc != 0) std::cout << "Tuning failed: " << famseq_last_error(ctx) << std::endl;
@@ -2328,38 +2350,16 @@ int main(int argc, char **argv) {
     std::cout << "Cannot read Ped file: " << o.ped_file << "." << std::endl << "Cannot set family." << std::endl;
     return -1;
   }
-  if (o.dnm && mode != "vcf") std::cout << "-dnm applies to vcf mode only; ignored here." << std::endl;
-  if (o.dnm && mode == "vcf" && !sum_product_serves(o, ped, "-dnm")) return 255;
-  if (o.map && mode != "vcf") std::cout << "-map applies to vcf mode only; ignored here." << std::endl;
-  if (o.map && mode == "vcf" && !sum_product_serves(o, ped, "-map")) return 255;
-  if (o.siteq && mode != "vcf") {
-    std::cout << "-siteQ applies to vcf mode only; ignored here." << std::endl;
-    o.siteq = false;
-  }
-  if (o.siteq && !sum_product_serves(o, ped, "-siteQ")) return 255;
-  if (o.loo && mode != "vcf") {
-    std::cout << "-loo applies to vcf mode only; ignored here." << std::endl;
-    o.loo = false;
-  }
-  if (o.loo && !sum_product_serves(o, ped, "-loo")) return 255;
-  if (o.sample && mode != "vcf") {
-    std::cout << "-sample applies to vcf mode only; ignored here." << std::endl;
-    o.sample = 0;
-  }
-  if (o.sample && !sum_product_serves(o, ped, "-sample")) return 255;
-  if ((!o.seg.empty() || !o.affected.empty() || !o.unaffected.empty()) && mode != "vcf") {
-    std::cout << "-seg applies to vcf mode only; ignored here." << std::endl;
-    o.seg.clear(), o.affected.clear(), o.unaffected.clear();
-  }
-  if (o.seg.empty() && !(o.affected.empty() && o.unaffected.empty())) {
-    std::cout << "-affected and -unaffected belong to -seg dominant|recessive|both, which was not given." << std::endl;
-    return -1;
-  }
-  if (!o.seg.empty()) {
-    vector<uint8_t> masks;
-    vector<const char *> keys;
-    if (!segregation_masks(o, ped, masks, keys)) return -1;
-    if (!sum_product_serves(o, ped, "-seg")) return 255;
+  for (const SideRow &row : kSide) {  // (outside vcf mode nothing reads the options this switches off)
+    if (!row.on(o)) continue;
+    if (mode != "vcf") {
+      std::cout << row.flag << " applies to vcf mode only; ignored here." << std::endl;
+      row.off(o);
+      continue;
+    }
+    if (row.check && !row.check(o, ped)) return -1;
+    if (!sum_product_serves(o, ped, row.flag)) return 255;
+    if (row.method2) o.method = 2;  // the evidence, leave-one-out and pattern kernels are the sum-product engine's
   }
   if (o.af_conflict) {
     std::cout << "-afTag and -afTagAll cannot be combined: give the INFO key once." << std::endl;
@@ -2369,7 +2369,7 @@ int main(int argc, char **argv) {
     if (mode != "vcf") {
       std::cout << (o.af_all ? "-afTagAll" : "-afTag") << " applies to vcf mode only; ignored here." << std::endl;
       o.af_tag.clear();
-    } else if (!o.af_all && (o.dnm || o.map || o.siteq || o.loo || o.sample || !o.seg.empty())) {
+    } else if (!o.af_all && any_side(o)) {
       std::cout << "-afTag cannot be combined with -dnm or -map: their kernels use the model's priors, and one output line must not mix two models."
                 << std::endl;
       return -1;
@@ -2379,7 +2379,6 @@ int main(int argc, char **argv) {
       o.method = 2;  // site priors are served by the sum-product engine
     }
   }
-  if (o.siteq || o.loo || !o.seg.empty()) o.method = 2;  // the evidence, leave-one-out and pattern kernels are the sum-product engine's
   const double t0 = now_s();
   if (o.tune_mode) return run_tune(o, ped) ? 0 : -1;
   const bool ok = o.pl_mode ? run_pl(o, ped) : (o.lk_mode ? run_lk(o, ped) : run_vcf(o, ped));

@@ -4,6 +4,8 @@
   tools/cli_throughput.py [n_sites] --packed   only the packed paths (`FamSeq PL`, `FamSeq PL -binOutput`); the packed
                                                input is written straight from the generator (no VCF text), so
                                                millions of sites take seconds to set up
+  --vcf-flags="-dnm -map ..."                  extra flags for the `FamSeq vcf` run (the side outputs' path)
+  --cli=PATH                                   the binary to time instead of bin/FamSeq (the library is the tree's either way)
 Each command is run twice; the second (page cache and kernel cache warm) is reported, with the first in brackets."""
 import os, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,12 +16,13 @@ from famseq_amd import synth, pedigree, plfile
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(args[0]) if args else 500_000
 packed_only = "--packed" in sys.argv
+opts = dict(a[2:].split("=", 1) for a in sys.argv[1:] if a.startswith("--") and "=" in a)
 ped = pedigree.synthetic_pedigree(args[1] if len(args) > 1 else "ped10")  # tools/cli_throughput.py 5000000 trio
 mo, fa = ped.relations()
 d = tempfile.mkdtemp(prefix="fscli")
 pedf, vcf, fspl = os.path.join(d, "p.ped"), os.path.join(d, "s.vcf"), os.path.join(d, "s.fspl")
 pedigree.write_ped(ped, pedf)
-cli = os.path.join(ROOT, "bin", "FamSeq")
+cli = opts.get("cli", os.path.join(ROOT, "bin", "FamSeq"))
 
 
 def run(a, label, **env):
@@ -44,8 +47,9 @@ else:
     pl, known, geno = synth.gen_sites(mo, fa, n, synth.SEED_BASE + 2)
     t0 = time.time(); synth.write_vcf(vcf, ped.names, pl, known, geno)
     print("wrote %d-site VCF (%.0f MB) in %.1f s" % (n, os.path.getsize(vcf) / 1e6, time.time() - t0), flush=True)
-    run(["vcf", "-vcfFile", vcf, "-pedFile", pedf, "-output", os.path.join(d, "o.vcf")], "FamSeq vcf")
-    run(["vcf", "-vcfFile", vcf, "-pedFile", pedf, "-output", os.path.join(d, "oh.vcf")], "vcf, host fmt", FAMSEQ_HOST_FORMAT="1")
+    vcf_flags = opts.get("vcf-flags", "").split()
+    run(["vcf", "-vcfFile", vcf, "-pedFile", pedf, "-output", os.path.join(d, "o.vcf")] + vcf_flags, "FamSeq vcf")
+    run(["vcf", "-vcfFile", vcf, "-pedFile", pedf, "-output", os.path.join(d, "oh.vcf")] + vcf_flags, "vcf, host fmt", FAMSEQ_HOST_FORMAT="1")
     same = subprocess.call(["cmp", "-s", os.path.join(d, "o.vcf"), os.path.join(d, "oh.vcf")]) == 0
     print("device-formatted and host-formatted output identical:", same, flush=True)
     os.unlink(os.path.join(d, "oh.vcf"))
