@@ -88,6 +88,7 @@ ABI_SYMBOLS = [
     "famseq_loo_batch", "famseq_loo_batch_device", "famseq_loo_prior_batch", "famseq_loo_prior_batch_device",
     "famseq_pattern_batch", "famseq_pattern_batch_device", "famseq_pattern_prior_batch", "famseq_pattern_prior_batch_device",
     "famseq_sample_batch", "famseq_sample_batch_device", "famseq_sample_prior_batch", "famseq_sample_prior_batch_device",
+    "famseq_af_batch", "famseq_af_batch_device",
 ]
 # (and famseq_philox4x32_10, the one name with digits in it: philox4x32 below)
 PL_MISSING = 0xFFFF
@@ -184,6 +185,10 @@ def lib():
             host.argtypes = [C.c_void_p, C.c_int64, dp, u16p, ip, C.c_int32, bp] + [dp] * prior + more[0] + [out_a, dp, bp]
             dev.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp] + [vp] * prior + more[1] + [vp, vp, vp, vp]
             host.restype = dev.restype = C.c_int
+    # (the allele-frequency entries: no site-prior form; af0 and n_iter stand where the others' `more` does)
+    L.famseq_af_batch.argtypes = [C.c_void_p, C.c_int64, dp, u16p, ip, C.c_int32, bp, dp, C.c_int32, dp, dp, bp]
+    L.famseq_af_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp]
+    L.famseq_af_batch.restype = L.famseq_af_batch_device.restype = C.c_int
     u32p = C.POINTER(C.c_uint32)
     L.famseq_philox4x32_10.argtypes = [u32p, u32p, u32p]
     L.famseq_philox4x32_10.restype = None
@@ -645,6 +650,28 @@ class Context:
         """pattern_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
         self._side_device("pattern", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_pat_post, d_loglik, d_status, stream,
                           (d_masks or None, int(n_patterns)))
+
+    def af_batch(self, af0, n_iter, lk=None, pl16=None, seq_members=None, flags=None, want_af=True, want_loglik=True):
+        """The founders' allele frequency by maximum likelihood: -> (af[S] float64, loglik[S,2] float64, status[S] uint8).
+        n_iter (0 .. 64) EM steps from af0 ([S], or a scalar for every site; each in [0, 1]) on the allele frequency q of the
+        founders' Hardy-Weinberg prior, hwe_priors' rows: af[s] is q after the steps (n_iter = 0: af0's bits), loglik[s, 0] the
+        site's log10 likelihood at that q on evidence_batch's scale, loglik[s, 1] the same at q = 0 (-inf where the data exclude
+        it); their difference is the log10 likelihood ratio for "the allele is present among the founders".  All NaN where
+        status != 0 (1: the single-posterior rule under af0's rows; 2: a total weight or a founder's row sum that is not a
+        positive finite number).  No early exit: n_iter = a, then n_iter = b from the returned af, gives the bits of one call
+        with n_iter = a + b.  Of the flags only FLAG_CHRX is read.  Input as evidence_batch.  want_* False: not computed, None."""
+        n = np.asarray(lk).size // (3 * self.n) if lk is not None else (len(pl16) if pl16 is not None else 0)
+        q = np.ascontiguousarray(np.full(n, af0) if np.ndim(af0) == 0 else af0, dtype=np.float64)
+        if q.shape != (n,):
+            raise ValueError("af0 must be a scalar or have one value per site")
+        outs = lambda s: (np.empty(s) if want_af else None, np.empty((s, 2)) if want_loglik else None)
+        return self._side_host("af", None, lk, pl16, seq_members, flags, outs, (_p(q, C.c_double), int(n_iter)))
+
+    def af_batch_device(self, n_sites, d_af0, n_iter, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_af=0, d_loglik=0, d_status=0, stream=0):
+        """af_batch on resident buffers (raw device pointers as ints; 0 = not given), d_af0 [n_sites] float64 among them;
+        enqueues on `stream` and returns."""
+        self._side_device("af", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_af, d_loglik, d_status, stream,
+                          (d_af0 or None, int(n_iter)))
 
     def loo_prior_batch_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_loo=0, d_fit=0, d_status=0, stream=0):
         """loo_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""

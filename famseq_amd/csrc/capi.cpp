@@ -229,7 +229,7 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
   // "<stem>_kernels", "<stem>_prior_kernels" of a side product: build (and on a device ctx load) the kernel of that output form now
   for (const SideProduct &p : side_table())
     for (bool site_prior : {false, true})
-      if (k == std::string(p.stem) + (site_prior ? "_prior_kernels" : "_kernels")) {
+      if ((!site_prior || p.has_prior()) && k == std::string(p.stem) + (site_prior ? "_prior_kernels" : "_kernels")) {
         if (value < 1 || value > p.n_forms) return fail(c, FAMSEQ_E_ARG, k + " takes " + p.takes);
         return load_or_fail(c, p.kind_of((int)value, site_prior));
       }
@@ -366,7 +366,8 @@ std::string trio_json(const famseq_ctx *c) {
   for (int i = 0; i < n_first; ++i) o += side_json(c, side_table()[i], false);
   o += ",\"prior_code_object\":\"" + json_str(c->kern[K_PRIOR].k.path) + "\",\"prior_variant\":" + std::to_string(c->kern[K_PRIOR].variant);
   for (int i = 0; i < n_first; ++i) o += side_json(c, side_table()[i], true);
-  for (int i = n_first; i < SIDE_COUNT; ++i) o += side_json(c, side_table()[i], false) + side_json(c, side_table()[i], true);
+  for (int i = n_first; i < SIDE_COUNT; ++i)
+    o += side_json(c, side_table()[i], false) + (side_table()[i].has_prior() ? side_json(c, side_table()[i], true) : std::string());
   const std::string bt = std::to_string(elim_block_threads(c->model));  // (every side product's kernel runs in these workgroups)
   return o + ",\"evidence_block_threads\":" + bt + ",\"loo_block_threads\":" + bt;
 }
@@ -733,7 +734,7 @@ int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl
   return 0;
 }
 
-// What the twenty entries below share.  On the device path (`device`) the arrays are the caller's resident buffers and the
+// What the side products' entries below share.  On the device path (`device`) the arrays are the caller's resident buffers and the
 // kernel is enqueued on `stream`; on the host path they are chunked and pipelined (side_batch) on the product's own buffers.
 // The order of the checks is what callers have come to rely on: a site-prior device entry asks for d_prior before anything
 // else, a site-prior host entry checks its input and its prior rows (prior_ready) first, then every entry trio_prologue.
@@ -774,11 +775,29 @@ int check_sample(famseq_ctx *c, const SampleIn &smp) {
   if (smp.site_base < 0) return fail(c, FAMSEQ_E_ARG, "site_base must be >= 0, got " + std::to_string(smp.site_base));
   return 0;
 }
+// What the allele-frequency entries take beside: the start values [n_sites] (host entry: the caller's host array, staged chunk
+// by chunk where the site-prior forms stage their rows; device entry: resident) and the number of steps.
+struct AfIn {
+  const double *af0;
+  int32_t n_iter;
+};
+int check_af(famseq_ctx *c, const AfIn &af, int64_t n_sites, bool device) {
+  if (af.n_iter < 0 || af.n_iter > FAMSEQ_MAX_AF_ITER)
+    return fail(c, FAMSEQ_E_ARG, "n_iter must be 0.." + std::to_string(FAMSEQ_MAX_AF_ITER) + ", got " + std::to_string(af.n_iter));
+  if (!af.af0) return fail(c, FAMSEQ_E_ARG, "af0 must be given (one start value per site)");
+  if (!device)
+    for (int64_t s = 0; s < n_sites; ++s)
+      if (!(af.af0[s] >= 0.0 && af.af0[s] <= 1.0))
+        return fail(c, FAMSEQ_E_ARG, "af0 entries must be finite numbers in [0, 1] (site " + std::to_string(s) + ")");
+  return 0;
+}
 int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device, const SideIn &in, const double *prior, void *out_a,
-               void *out_b, uint8_t *status, void *stream_ = nullptr, const PatternIn *pat = nullptr, const SampleIn *smp = nullptr) {
+               void *out_b, uint8_t *status, void *stream_ = nullptr, const PatternIn *pat = nullptr, const SampleIn *smp = nullptr,
+               const AfIn *af = nullptr) {
   if (!c) return FAMSEQ_E_ARG;
   if (pat && check_patterns(c, *pat, device) != 0) return FAMSEQ_E_ARG;
   if (smp && check_sample(c, *smp) != 0) return FAMSEQ_E_ARG;
+  if (af && check_af(c, *af, in.n_sites, device) != 0) return FAMSEQ_E_ARG;
   const SideProduct &p = side_table()[id];
   const int kind = p.kind_of(form, site_prior);
   const int64_t n_sites = in.n_sites;
@@ -797,7 +816,13 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
   const unsigned long seed = smp ? (unsigned long)smp->seed : 0;
   const long site_base = smp ? long(smp->site_base) : 0;
   const int32_t n_draws = smp ? smp->n_draws : 1;
-  const MoreArgs lead = pat ? MoreArgs{&d_masks, &n_patterns} : smp ? MoreArgs{&seed, &site_base, &n_draws} : MoreArgs{};
+  // ... or the allele-frequency kernel's start values (the host path: the chunk's staged copy, side_batch) and n_iter
+  const double *d_af0 = af ? af->af0 : nullptr;
+  const int32_t n_iter = af ? af->n_iter : 0;
+  const MoreArgs lead = pat   ? MoreArgs{&d_masks, &n_patterns}
+                        : smp ? MoreArgs{&seed, &site_base, &n_draws}
+                        : af  ? MoreArgs{&d_af0, &n_iter}
+                              : MoreArgs{};
   if (!device) {
     size_t row[2];
     p.rows(c->model, smp ? n_draws : n_patterns, row);
@@ -810,6 +835,9 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
       HIP_TRY(c, hipMemcpyAsync(c->d_masks.p, c->masks_host.data(), bytes, hipMemcpyHostToDevice, c->stream[1]));
       d_masks = c->d_masks.as<uint8_t>();
     }
+    if (af)
+      return side_batch(c, c->side_slots[id], c->kern[kind], n_sites, in.lk, in.pl16, in.n_seq, in.flags, out_a, row[0], out_b, row[1], status,
+                        af->af0, lead, -1, 0, sizeof(double), 0);
     return side_batch(c, c->side_slots[id], c->kern[kind], n_sites, in.lk, in.pl16, in.n_seq, in.flags, out_a, row[0], out_b, row[1], status, prior,
                       lead, smp ? 1 : -1, site_base);
   }
@@ -1000,6 +1028,24 @@ extern "C" int famseq_sample_prior_batch_device(famseq_ctx *c, int64_t n_sites, 
   const SampleIn smp{seed, site_base, n_draws};
   return side_entry(c, SIDE_SAMPLE, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_samp_gt, d_samp_post, d_status,
                     stream, nullptr, &smp);
+}
+
+// ---- the founders' allele frequency by maximum likelihood: the evidence entries with the start values and the number of steps ---
+
+extern "C" int famseq_af_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                               int32_t n_seq, const uint8_t *flags, const double *af0, int32_t n_iter, double *af, double *loglik,
+                               uint8_t *status) {
+  const AfIn in{af0, n_iter};
+  return side_entry(c, SIDE_AF, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, af, loglik, status, nullptr, nullptr,
+                    nullptr, &in);
+}
+
+extern "C" int famseq_af_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16, const int32_t *seq_members,
+                                      int32_t n_seq, const uint8_t *d_flags, const double *d_af0, int32_t n_iter, double *d_af,
+                                      double *d_loglik, uint8_t *d_status, void *stream) {
+  const AfIn in{d_af0, n_iter};
+  return side_entry(c, SIDE_AF, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_af, d_loglik, d_status, stream,
+                    nullptr, nullptr, &in);
 }
 
 // The sampling kernels' generator on the host: the text they carry (philox_src.h), compiled here.

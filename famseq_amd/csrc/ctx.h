@@ -55,7 +55,7 @@ struct DevBuf {
 };
 
 // A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp; the trio,
-// MAP, evidence, leave-one-out, pattern and sampling kinds are the rows of side_table() below.
+// MAP, evidence, leave-one-out, pattern, sampling and allele-frequency kinds are the rows of side_table() below.
 enum KernelKind {
   K_LANE = 0,  // K_LANE + d: the enumeration with 3^d lanes per site; d = 0 (one lane per site) serves large batches,
                // d = 1..kEnumMaxGroupDigits batches too small to give every lane of the chip a site (compiled on first use of each d)
@@ -75,6 +75,7 @@ enum KernelKind {
   K_PATTERN_PRIOR,                                 // ... with the founders' prior per site
   K_SAMPLE,                                        // exact joint posterior draws
   K_SAMPLE_PRIOR,                                  // ... with the founders' prior per site
+  K_AF,                                            // the founders' allele frequency by maximum likelihood (no site-prior form)
   K_COUNT
 };
 
@@ -115,17 +116,19 @@ struct SlotSet {
 // A side product of the sum-product engine: a generated kernel that takes the common argument list and writes two outputs per
 // site and a status byte, in a plain form and in one that reads the founders' prior per site.  Everything its ABI entries, its
 // prebuild options, its plan keys and its loader differ in is one row of side_table() (kernels.cpp).
-enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_SAMPLE, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
+enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_SAMPLE, SIDE_AF, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
 struct SideProduct {
   const char *stem;   // "trio": the entry points famseq_trio[_prior], the options trio[_prior]_kernels, the plan keys trio[_prior]_*
   const char *what;   // load_or_fail's message starts "[site priors, ]<what> (sum-product engine): "
   const char *takes;  // the values of its prebuild options, as their refusal names them
   int kind, prior_kind, n_forms;  // output form f = 1 .. n_forms is kind + f - 1, its site-prior form prior_kind + f - 1
+                                  // (prior_kind < 0: the product has no site-prior form — no <stem>_prior_* name exists anywhere)
   int n_variants;
   std::string (*source)(const Model &, int variant, int form, bool site_prior);
   // bytes per site of the two outputs; per_call: what the call itself says of them (the pattern entries' n_patterns, the sampling entries' n_draws; 1 elsewhere)
   void (*rows)(const Model &, int per_call, size_t row[2]);
   int kind_of(int form, bool site_prior) const { return (site_prior ? prior_kind : kind) + form - 1; }
+  bool has_prior() const { return prior_kind >= 0; }
 };
 using SideTable = const SideProduct[SIDE_COUNT];
 SideTable &side_table();
@@ -206,7 +209,7 @@ inline int fail(famseq_ctx *c, int code, const std::string &msg) {
 // What a generated kernel takes behind the common eight arguments, in the order of its parameter list: the address of each
 // argument's value (hipModuleLaunchKernel's form).  The call-path forms take their CallIO, the site-prior kernels their prior
 // rows, the pattern kernels their masks and n_patterns and the sampling kernels their seed, site_base and n_draws in front of
-// those; the plain forms nothing.
+// those, the allele-frequency kernel its start values and n_iter; the plain forms nothing.
 struct MoreArgs {
   static constexpr int kMax = 4;
   void *at[kMax] = {};
@@ -256,9 +259,11 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq);
 // prior: the site-prior forms' rows [n_sites][6], staged chunk by chunk alongside the likelihoods (NULL: the plain forms).
 // lead: what the kernel takes between the common arguments and the prior rows (the same for every chunk, but for lead.at[base_at]
 // where base_at >= 0: the kernel's site_base, which every chunk gets as site_base + its first site's index in the call).
+// prior_row: the bytes per site of what is staged as `prior`; staged_at >= 0: the staged array is the kernel's argument
+// lead.at[staged_at] instead of its last (famseq_af's start values: 8 bytes per site, in front of n_iter).
 int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
                const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior = nullptr,
-               const MoreArgs &lead = {}, int base_at = -1, int64_t site_base = 0);
+               const MoreArgs &lead = {}, int base_at = -1, int64_t site_base = 0, size_t prior_row = 6 * sizeof(double), int staged_at = -1);
 
 }  // namespace famseq
 #endif

@@ -353,6 +353,92 @@ class Emitter {
     return head.str() + pass + per_pass + "      }\n";
   }
 
+  // The founders' allele frequency by maximum likelihood (famseq_af): EM on q, every step one sum pass and the founders' marginals
+  // under the Hardy-Weinberg rows of the step's q, all steps on one read of the site's rows.  The loop is `#pragma unroll 1`
+  // over it_ = -1 .. n_it_ and its text stands once whatever n_it_ is: pass -1 runs at q = 0 (the rows (1, 0, 0) exactly) and keeps
+  // only its total weight, pass t = 0 .. n_it_ runs at q_t, and every pass but the first and the last takes the update
+  //   q' = min(sum_founders count_f / C, 1),  count_f = (m_f1 + 2 m_f2) / (m_f0 + m_f1 + m_f2)  [a male founder at a chrX site:
+  //   m_f2 / (m_f0 + m_f1 + m_f2)],  C = 2 founders  [chrX: 2 female founders + male founders],  founders in PED order.
+  // A pass forms its rows pa_<g> / pm_<g> from its q with famseq_hwe_priors' expressions, shadowing the shell's (which hold
+  // the start value's rows, for the single posterior's failure rule); founder_prior(), loc() and a cut member's lam follow.  Its
+  // total weight is evidence_body's: the same statements, so that a call without steps has famseq_evidence_prior's bits.  The
+  // founders' marginals are marginal(p)'s; under conditioning they are accumulated over the cut assignments with the weight of
+  // the rest of the network, as conditioned_body does (a cut founder adds Wall at its assigned genotype).  They stand behind a
+  // wave-uniform branch (upd_), so the two passes that need the total weight alone form the messages towards the roots only.
+  // Reads qs_ (the start value), n_it_, xs_ (the site is on chrX); sets bn_fail where a pass's total weight or a founder's row
+  // sum is not a positive finite number.  Leaves q_ (after n_it_ steps), Zq_ = Z(q_) and Z0_ = Z(0), scaled as evidence_body's Z_.
+  std::string af_body() {
+    std::vector<int> founders;
+    int n_female = 0, n_male = 0;
+    for (int p = 0; p < g_.N; ++p)
+      if (m_.mother[p] < 0) {
+        founders.push_back(p);
+        ++(kind(p) == 0 ? n_male : n_female);
+      }
+    const char *finite = " <= 1.79769313486231570815e308";
+    std::ostringstream head;
+    head << "      double q_ = qs_, Z0_ = 0, Zq_ = 0;\n"
+         << "#pragma unroll 1\n      for (int it_ = -1; it_ <= n_it_; ++it_) {\n"
+         << "      const bool upd_ = it_ >= 0 && it_ < n_it_;\n"
+         << "      const double qp_ = it_ < 0 ? 0.0 : q_, pp_ = 1 - qp_;\n"
+         << "      const double pa_0 = pp_ * pp_, pa_1 = 2 * qp_ * pp_, pa_2 = qp_ * qp_;\n"
+         << "      const double pm_0 = xs_ ? pp_ : pa_0, pm_1 = xs_ ? 0.0 : pa_1, pm_2 = xs_ ? qp_ : pa_2;\n";
+    // the step: from the founders' rows `row`<p>_<g>, in PED order
+    auto update = [&](const std::string &row) {
+      std::ostringstream u;
+      u << "      double A_ = 0;\n";
+      for (int p : founders) {
+        const std::string r = row + num(p);
+        const std::string both = "(" + r + "_1 + 2 * " + r + "_2)";
+        u << "      { const double s = (" << r << "_0 + " << r << "_1) + " << r << "_2; if (!(s > 0 && s" << finite << ")) bn_fail = true;\n"
+          << "        A_ = A_ + " << (kind(p) == 0 ? "(xs_ ? " + r + "_2 : " + both + ")" : both) << " / s; }\n";
+      }
+      u << "      const double qn_ = A_ / (xs_ ? " << 2 * n_female + n_male << ".0 : " << 2 * (n_female + n_male) << ".0);\n"
+        << "      q_ = qn_ < 1.0 ? qn_ : 1.0;\n";
+      return u.str();
+    };
+    const std::string keep =
+        "      if (it_ < 0) Z0_ = Zp_;\n"
+        "      else {\n"
+        "        if (!(Zp_ > 0 && Zp_" + std::string(finite) + ")) { bn_fail = true; break; }\n"
+        "        Zq_ = Zp_;\n"
+        "      }\n";
+    std::string pass;
+    if (g_.cut.empty()) {
+      fence(1);
+      component_sums();
+      o_ << "      const double Zp_ = " << times_sums("") << ";\n";
+      fence(1);
+      o_ << keep << "      if (upd_) {\n";
+      for (int p : founders) marginal(p);
+      o_ << update("m") << "      }\n";
+      pass = o_.str();
+    } else {
+      std::ostringstream decls;
+      decls << "      double Zt_ = 0;\n";
+      for (int p : founders) decls << "      double acc" << p << "_0 = 0, acc" << p << "_1 = 0, acc" << p << "_2 = 0;\n";
+      pass = cut_loop(decls.str(), /*wc=*/true, /*wall=*/true, [&] {
+               o_ << "      Zt_ = Zt_ + Wall;\n";
+               fence(1);
+               o_ << "      if (upd_) {\n";
+               for (int p : founders) {
+                 if (g_.is_cut(p)) {
+                   for (int g = 0; g < 3; ++g) o_ << "      acc" << p << "_" << g << " += a" << p << " == " << g << " ? Wall : 0.0;\n";
+                   continue;
+                 }
+                 marginal(p);
+                 for (int g = 0; g < 3; ++g)
+                   o_ << "      acc" << p << "_" << g << " = __builtin_fma(m" << p << "_" << g << ", Wc" << g_.comp[p] << ", acc" << p << "_" << g
+                      << ");\n";
+                 fence(1);
+               }
+               o_ << "      }\n";
+             }) +
+             "      const double Zp_ = Zt_;\n" + keep + "      if (upd_) {\n" + update("acc") + "      }\n";
+    }
+    return head.str() + pass + "      }\n";
+  }
+
   // Leave-one-out (famseq_loo): for every member p its cavity row k<p>_g, the product of everything the network says of g_p but
   // p's own likelihood: the founder's prior (a child has none) times the message of every adjacent family.  Member p's
   // marginal is c<p>_g * prod of the same messages; here the likelihood is left out of the product, never divided out of it
@@ -1078,6 +1164,9 @@ struct LaneShell {
   // that passes it runs the body.
   bool shortcut = false;
   bool fence_single = false, chrx_loop = false, site_prior = false;
+  // the founders' prior is the kernel's own: it defines pa_<g> / pm_<g> itself (site_vars), the single posterior and the flags
+  // follow as with site_prior, and there is no prior_g to read (famseq_af)
+  bool own_prior = false;
   // Where the likelihoods live.  lean: read from the lane's row in global memory at each use (volatile: never kept in a
   // register).  Otherwise members lds_from .. N-1 keep theirs in a per-lane LDS row (3 doubles each, odd stride) and are read
   // from there at each use; the others live in registers.  The last members' local factors have the longest live ranges (the
@@ -1118,7 +1207,7 @@ std::string lane_shell(const Model &m, const LaneShell &d) {
     << "    const double *lg = lk_g + site * W3;\n"
     << d.site_decls
     // (site priors: the Known bit chooses between two rows of the model that this kernel does not read)
-    << "    const int fl = flags_g ? (flags_g[site] & " << (d.site_prior ? 2 : 3) << ") : 0;\n"
+    << "    const int fl = flags_g ? (flags_g[site] & " << (d.site_prior || d.own_prior ? 2 : 3) << ") : 0;\n"
     << (d.shortcut ? "" : "    const bool xchr_ = (fl & 2) != 0;\n")
     << "    const double *tcf = s_tc + fl * 108;\n"
     << "    bool single_fail = false, full = false, bn_fail = false;\n"
@@ -1135,7 +1224,7 @@ std::string lane_shell(const Model &m, const LaneShell &d) {
   }
   if (d.site_prior && !d.shortcut) s << (prior_late ? "    PRIOR_LOAD(site);\n" : "") << kPriorNames;
   SingleOptions so;
-  so.store = d.shortcut, so.fence = d.fence_single, so.site_prior = d.site_prior;
+  so.store = d.shortcut, so.fence = d.fence_single, so.site_prior = d.site_prior || d.own_prior;
   s << single_posterior_statements(m, so) << d.after_single
     << (d.shortcut ? open_body(d.chrx_loop, "full && !single_fail") : open_body(d.chrx_loop, "!single_fail", "xchr_ == (x_ == 1)", ""))
     << d.body << close_body(d.chrx_loop) << d.epilogue << "  }\n}\n";
@@ -1369,6 +1458,55 @@ std::string pattern_source(const Model &m, int variant, bool site_prior) {
                "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.bt = elim_block_threads(m, false);
   d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  return lane_shell(m, d);
+}
+
+// The allele-frequency kernel: the evidence kernel's rules and shell; the founders' prior is the unknown, so there is one form only.
+// Beyond the common arguments: af0_g[n_sites], the start values, and n_iter (0 .. FAMSEQ_MAX_AF_ITER; the host checks, the kernel
+// clamps).  Outputs per site: af = q after n_iter steps (8 bytes) and loglik[2] = log10 Z(q) and log10 Z(0) without the reference's
+// 1e7 (16 bytes; -inf where the data exclude q = 0, which is a result), status; any may be null.  Status 1: the single posterior's
+// rule under the start value's rows; 2: a start value outside [0, 1] (whatever the rows it gives say), a pass's total weight or a
+// founder's row sum that is not a positive finite number.  Per-pass state: q, Z(q) and Z(0), three doubles in registers.
+std::string af_source(const Model &m, int variant) {
+  const Graph g = graph_or_throw(m);
+  if (variant < 0 || variant >= kAfVariants) throw std::runtime_error("af_source: variant must be 0.." + std::to_string(kAfVariants - 1));
+  const int f = variant;
+  EmitOptions eo = emit_options(f, "pg", /*site_prior=*/true);
+  LaneShell d;
+  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
+  d.entry = "famseq_af";
+  d.comment = describe("founder allele frequency by maximum likelihood (EM, a sum pass per step)", g, std::to_string(f), false) +
+              "\n// One step from q: the founders' rows are ((1-q)^2, 2q(1-q), q^2) and, male founders at a chrX site, (1-q, 0, q); with m_f the"
+              "\n// marginal of founder f under them, q' = min(sum_f count_f / C, 1), count_f = (m_f1 + 2 m_f2) / (m_f0 + m_f1 + m_f2) (a male"
+              "\n// founder at a chrX site: m_f2 / (m_f0 + m_f1 + m_f2)), C = 2 founders (chrX: 2 female founders + male founders), founders in"
+              "\n// PED order.  n_iter steps from af0, no early exit: the result is a function of the inputs alone.";
+  d.outputs = "double *__restrict__ af_g, double *__restrict__ loglik_g";
+  d.more_args = ", const double *__restrict__ af0_g, int n_iter";
+  d.defines = "#define MAXIT " + std::to_string(FAMSEQ_MAX_AF_ITER) + "\n";
+  d.prologue = "  const int n_it_ = n_iter < 0 ? 0 : (n_iter > MAXIT ? MAXIT : n_iter);\n";
+  // the start value's rows, for the single posterior's rule (famseq_hwe_priors' expressions; a pass forms its own the same way)
+  d.site_vars =
+      "    double af_q = kNaN, af_l0 = kNaN, af_l1 = kNaN;\n"
+      "    const double q0_ = af0_g[site];\n"
+      "    const bool af_bad = !(q0_ >= 0.0 && q0_ <= 1.0);\n"
+      "    const double qs_ = af_bad ? 0.5 : q0_;  // (what the passes of such a site run on: nothing of them is kept)\n"
+      "    const bool xs_ = (fl & 2) != 0;\n"
+      "    const double p0_ = 1 - q0_;\n"
+      "    const double pa_0 = p0_ * p0_, pa_1 = 2 * q0_ * p0_, pa_2 = q0_ * q0_;\n"
+      "    const double pm_0 = xs_ ? p0_ : pa_0, pm_1 = xs_ ? 0.0 : pa_1, pm_2 = xs_ ? q0_ : pa_2;\n";
+  Emitter e(m, g, eo);
+  const std::string digits = std::to_string(e.evidence_scale_digits()) + ".0";
+  d.body = e.af_body() +
+           "      if (!bn_fail) { af_q = q_; af_l0 = log10(Zq_) - " + digits + "; af_l1 = log10(Z0_) - " + digits + "; }\n";
+  d.epilogue = "    if (af_bad || single_fail || bn_fail) af_q = af_l0 = af_l1 = kNaN;\n"
+               "    if (af_g) __builtin_nontemporal_store(af_q, af_g + site);\n"
+               "    if (loglik_g) {\n"
+               "      __builtin_nontemporal_store(af_l0, loglik_g + 2 * site);\n"
+               "      __builtin_nontemporal_store(af_l1, loglik_g + 2 * site + 1);\n"
+               "    }\n"
+               "    if (status_g) status_g[site] = af_bad ? 2 : (single_fail ? 1 : (bn_fail ? 2 : 0));\n";
+  d.bt = elim_block_threads(m, false);
+  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.own_prior = true;
   return lane_shell(m, d);
 }
 

@@ -88,6 +88,15 @@ constexpr int kPatternVariants = 4;
 // site_prior: famseq_pattern_prior, with a trailing `prior` [n_sites][6] behind n_patterns (as trio_source's).
 std::string pattern_source(const Model &m, int variant, bool site_prior = false);
 
+// The founders' allele frequency by maximum likelihood (famseq_af_batch).  HIP source of
+// `extern "C" __global__ famseq_af(lk, flags, af, loglik, status, n_sites, tc, lc, af0, n_iter)`: per site n_iter EM steps on the
+// allele frequency q of the founders' Hardy-Weinberg prior from af0 — a step is one sum pass of famseq_evidence and the founders'
+// marginals under the rows of its q — all on one read of the site's rows: af = q after the steps, loglik[0] = log10 Z(q) and
+// loglik[1] = log10 Z(0), famseq_evidence's scale.  The prior is the unknown, so there is no site-prior form.  variant 0..3: the
+// fence levels of famseq_elim's; every variant gives the same bits.  Throws if the engine does not serve the pedigree.
+constexpr int kAfVariants = 4;
+std::string af_source(const Model &m, int variant);
+
 // Exact joint posterior draws (famseq_sample_batch).  HIP source of
 // `extern "C" __global__ famseq_sample(lk, flags, samp_gt, samp_post, status, n_sites, tc, lc, seed, site_base, n_draws)`: per site
 // and draw k a joint configuration samp_gt[k][N] (int8, PED order) drawn with probability w(g) / Z and samp_post[k], that

@@ -5,6 +5,7 @@
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
 //              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-loo] [-afTag KEY | -afTagAll KEY]
 //              [-seg dominant|recessive|both -affected ID[,ID...] [-unaffected ID[,ID...]]] [-sample K [-seed S]]
+//              [-afEM T [-afStart X]]
 //   FamSeq LK  -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -24,7 +25,8 @@
 // -loo (vcf mode) each sample's leave-one-out genotype probabilities and fit (LOP, LOF), and -seg (vcf mode) the posterior probability
 // that the variant segregates with the phenotype of the members named by -affected / -unaffected, under a dominant and / or a
 // recessive model, to the INFO column (PSD, PSR), and -sample K (vcf mode) each sample's alt-allele counts in K joint configurations
-// of the family drawn from their posterior (SGT).
+// of the family drawn from their posterior (SGT), and -afEM T (vcf mode) the maximum-likelihood allele frequency among the founders after
+// T EM steps and its log10 likelihood ratio against an allele frequency of 0, to the INFO column (FAF, FAL).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -193,6 +195,12 @@ struct Options {
   // -seg dominant|recessive|both: PSD and / or PSR keys in the INFO column (vcf mode), the posterior probability of the genotype
   // pattern that model gives the members of -affected and -unaffected (PED IDs, comma-separated)
   string seg, affected, unaffected;
+  // -afEM T [-afStart X]: FAF and FAL keys in the INFO column (vcf mode), the founders' allele frequency after T EM steps from X and
+  // the log10 likelihood ratio against "no founder carries the allele" (kAfUnset: not given; kAfBad: given, not a number)
+  static constexpr int kAfUnset = -1, kAfBad = -2;
+  int af_em = kAfUnset;
+  double af_start = 0.5;
+  bool af_start_given = false;
   string af_tag;     // -afTag KEY: the founders' prior of a line from the allele frequency KEY= of its INFO column (vcf mode)
   bool af_conflict = false;  // both -afTag and -afTagAll were given
   bool af_all = false;  // -afTagAll KEY: -afTag KEY, applied to every field a line prints (DNP, JGT and JP too: may go with -dnm / -map)
@@ -346,6 +354,23 @@ int parse_options(int argc, char **argv, Options &o) {
                     << std::endl;
           o.sample = 0;
           rv = 1;
+        }
+      }
+    } else if (opt == "afEM" || opt == "afStart") {
+      i++;
+      if (missing(i)) {
+        std::cout << "The value of -" << opt << " hasn't been set. The option is ignored." << std::endl;
+        i--;
+        rv = 1;
+      } else {  // (what the value may be: check_af_em, with the other side options' checks)
+        char *end = nullptr;
+        if (opt == "afEM") {
+          const long t = std::strtol(argv[i], &end, 10);
+          o.af_em = end == argv[i] || *end || t < 0 || t > 1000000 ? Options::kAfBad : (int)t;
+        } else {
+          o.af_start = std::strtod(argv[i], &end);
+          if (end == argv[i] || *end) o.af_start = -1;
+          o.af_start_given = true;
         }
       }
     } else if (opt == "seg" || opt == "affected" || opt == "unaffected") {
@@ -1355,12 +1380,13 @@ struct Part {
   }
 };
 
-// ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample and -seg add to a line, one row of kSide each ------------------------
+// ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample, -seg and -afEM add to a line, one row of kSide each ----------------
 // The order is the one main checks them and prints its notices in; it is also the order of the fields in a sample column (DNP,
-// JGT:JP, LOP:LOF, SGT) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR).  Header lines have their own order.
-enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg };
-constexpr int kSides = kSeg + 1;
-const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ};
+// JGT:JP, LOP:LOF, SGT) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL).  Header lines have their
+// own order.
+enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm };
+constexpr int kSides = kAfEm + 1;
+const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm};
 
 // One side output of a block: the two arrays its C entry fills ([site][...], read as the entry's own types) and its status per site.
 struct SideOut {
@@ -1374,7 +1400,7 @@ struct SideBytes { size_t a, b; };
 struct SideRow {
   SideId id;
   const char *flag;   // as the notices name it
-  const char *entry;  // its C entries are <entry>_batch and <entry>_prior_batch (VcfRun::call_side)
+  const char *entry;  // its C entries are <entry>_batch and <entry>_prior_batch (VcfRun::call_side; -afEM: the first alone)
   bool method2;       // a form of the sum-product engine only: implies -method 2
   bool (*on)(const Options &);
   void (*off)(Options &);
@@ -1812,9 +1838,14 @@ struct VcfRun {
       case kLoo: rc = entry(famseq_loo_batch, famseq_loo_prior_batch, a, b, st); break;
       case kSample: rc = entry(famseq_sample_batch, famseq_sample_prior_batch, o.seed, sl.site_base, (int32_t)o.sample, a8, none, st); break;
       case kSeg: rc = entry(famseq_pattern_batch, famseq_pattern_prior_batch, seg_masks.data(), (int32_t)seg_keys.size(), a, none, st); break;
+      case kAfEm: {  // the prior is its unknown: one entry, whatever -afTagAll says of the line
+        const vector<double> af0(sl.n_sites, o.af_start);
+        rc = famseq_af_batch(ctx, (int64_t)sl.n_sites, lk, pl16, cm.members.data(), (int32_t)n_seq, sl.io.flags, af0.data(), (int32_t)o.af_em, a, b, st);
+        break;
+      }
     }
     if (rc != 0) {
-      std::cerr << row.entry << (use_af ? "_prior_batch" : "_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
+      std::cerr << row.entry << (use_af && row.id != kAfEm ? "_prior_batch" : "_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
       flush_ok = false;
     }
   }
@@ -1854,9 +1885,9 @@ struct VcfRun {
     to_formatter.put(-1);
   }
 
-  // -siteQ, -seg: columns 1-8 + FORMAT of a site with "FQ=<x>;FLL=<y>" and / or "PSD=<p>;PSR=<q>" joined to its INFO column (an
-  // INFO of "." is replaced); a site whose evidence (pattern kernel) failed does without those keys, and keeps its INFO where none
-  // is left to add.
+  // -siteQ, -seg, -afEM: columns 1-8 + FORMAT of a site with "FQ=<x>;FLL=<y>", "PSD=<p>;PSR=<q>" and / or "FAF=<q>;FAL=<r>" joined to
+  // its INFO column (an INFO of "." is replaced); a site whose evidence (pattern, allele-frequency kernel) failed does without those
+  // keys, and keeps its INFO where none is left to add.
   void put_prefix_info(TextBuf &out, const Slot &sl, size_t s, const char *raw, size_t len) const {
     size_t info = 0, end = 0;  // the INFO column is raw[info, end): between the seventh and the eighth tab
     int tabs = 0;
@@ -2024,6 +2055,14 @@ inline void put_seg(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, 
   }
 }
 
+// (FAL: inf where the data exclude an allele frequency of 0)
+inline void put_faf(TextBuf &out, const VcfRun &, const SideOut &so, size_t s, size_t) {
+  out.put("FAF=", 4);
+  out.num(so.a[s]);
+  out.put(";FAL=", 5);
+  out.num(so.b[2 * s] - so.b[2 * s + 1]);
+}
+
 [[gnu::always_inline]] inline void put_side(SideId id, TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {
   switch (id) {
     case kDnm: return put_dnp(out, r, so, s, j);
@@ -2032,6 +2071,7 @@ inline void put_seg(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, 
     case kLoo: return put_loo(out, r, so, s, j);
     case kSample: return put_sgt(out, r, so, s, j);
     case kSeg: return put_seg(out, r, so, s, j);
+    case kAfEm: return put_faf(out, r, so, s, j);
   }
 }
 
@@ -2044,6 +2084,23 @@ bool check_seg(const Options &o, const Ped &ped) {
   vector<uint8_t> masks;
   vector<const char *> keys;
   return segregation_masks(o, ped, masks, keys);
+}
+
+// -afEM's own options: -afStart without it, a step count or a start value out of range
+bool check_af_em(const Options &o, const Ped &) {
+  if (o.af_em == Options::kAfUnset) {
+    std::cout << "-afStart belongs to -afEM T, which was not given." << std::endl;
+    return false;
+  }
+  if (o.af_em < 0 || o.af_em > FAMSEQ_MAX_AF_ITER) {
+    std::cout << "-afEM takes the number of EM steps, 0.." << FAMSEQ_MAX_AF_ITER << "." << std::endl;
+    return false;
+  }
+  if (!(o.af_start > 0.0 && o.af_start < 1.0)) {
+    std::cout << "-afStart takes the allele frequency the steps start from, a number in (0, 1); default 0.5." << std::endl;
+    return false;
+  }
+  return true;
 }
 
 const SideRow kSide[kSides] = {
@@ -2093,6 +2150,16 @@ const SideRow kSide[kSides] = {
                 "are homozygous for the variant (recessive segregation pattern)\">" << std::endl;
      },
      nullptr, nullptr, [](const VcfRun &r) { return SideBytes{8 * r.seg_keys.size(), 0}; }},
+    // (on: either of its options, so that main can say which one is missing)
+    {kAfEm, "-afEM", "famseq_af", true, [](const Options &o) { return o.af_em != Options::kAfUnset || o.af_start_given; },
+     [](Options &o) { o.af_em = Options::kAfUnset, o.af_start_given = false; }, check_af_em,
+     [](std::ostream &out, const Options &o) {
+       out << "##INFO=<ID=FAF,Number=1,Type=Float,Description=\"Maximum-likelihood allele frequency among the family's founders after "
+           << o.af_em << " EM steps from " << o.af_start << "\">" << std::endl;
+       out << "##INFO=<ID=FAL,Number=1,Type=Float,Description=\"log10 likelihood ratio of the site's data at that allele frequency against "
+              "no founder carrying the allele\">" << std::endl;
+     },
+     nullptr, nullptr, [](const VcfRun &) { return SideBytes{8, 16}; }},
 };
 
 // `FamSeq vcf` and `FamSeq pack`: the wiring of a VcfRun's stages
@@ -2297,6 +2364,10 @@ void help() {
             << "\t\tadd PSD (dominant: the affected carry the variant, the unaffected do not) and / or PSR (recessive: the affected are" << std::endl
             << "\t\thomozygous for it, the unaffected are not), the posterior probability of that pattern given the whole family's data," << std::endl
             << "\t\tto the INFO column. Implies -method 2; may be combined with -dnm, -map, -siteQ, -loo and -afTagAll; not with -afTag." << std::endl
+            << "-afEM T\t\t(vcf) Add FAF, the maximum-likelihood allele frequency among the family's founders after T (0.." << FAMSEQ_MAX_AF_ITER << ") EM steps" << std::endl
+            << "\t\tfrom -afStart X (in (0, 1), default 0.5), and FAL, the log10 likelihood ratio of the site's data at that frequency against" << std::endl
+            << "\t\t\"no founder carries the allele\" (inf where the data exclude that), to the INFO column. No prior enters either; no other" << std::endl
+            << "\t\tfield changes. Implies -method 2; may be combined with -dnm, -map, -siteQ, -loo, -sample, -seg and -afTagAll; not with -afTag." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl

@@ -34,6 +34,9 @@ SideTable &side_table() {
       {"sample", "joint posterior draws", "1", K_SAMPLE, K_SAMPLE_PRIOR, 1, kSampleVariants,
        [](const Model &m, int v, int, bool site_prior) { return sample_source(m, v, site_prior); },
        [](const Model &m, int n_draws, size_t row[2]) { row[0] = size_t(n_draws) * m.n_members, row[1] = size_t(n_draws) * sizeof(double); }},  // samp_gt[K][N], samp_post[K]
+      {"af", "founder allele frequency", "1", K_AF, -1, 1, kAfVariants,
+       [](const Model &m, int v, int, bool) { return af_source(m, v); },
+       [](const Model &, int, size_t row[2]) { row[0] = sizeof(double), row[1] = 2 * sizeof(double); }},  // af, loglik[2]
   };
   return table;
 }
@@ -81,7 +84,7 @@ struct SideKind {
 SideKind side_of(int kind) {
   for (const SideProduct &p : side_table())
     for (bool site_prior : {false, true})
-      if (kind >= p.kind_of(1, site_prior) && kind <= p.kind_of(p.n_forms, site_prior)) return {&p, site_prior, kind - p.kind_of(1, site_prior) + 1};
+      if ((!site_prior || p.has_prior()) && kind >= p.kind_of(1, site_prior) && kind <= p.kind_of(p.n_forms, site_prior)) return {&p, site_prior, kind - p.kind_of(1, site_prior) + 1};
   return {nullptr, false, 0};
 }
 
@@ -281,7 +284,7 @@ int grid_for(const famseq_ctx *c, int64_t n_sites) {
 
 // The generated kernels share one argument list; what the third and fourth are depends on the kind (posterior and single
 // posterior rows, joint and de novo posteriors, MAP genotypes and their posterior, log10 likelihood and hom-ref posterior, leave-one-out rows and fit, pattern
-// posteriors and log10 likelihood, drawn configurations and their posteriors), so they pass through untyped; so does what some kinds take behind the eighth (MoreArgs).
+// posteriors and log10 likelihood, drawn configurations and their posteriors, allele frequency and its two log10 likelihoods), so they pass through untyped; so does what some kinds take behind the eighth (MoreArgs).
 hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,
                             void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk, const MoreArgs &more) {
   const int spc = sites_per_chunk > 0 ? sites_per_chunk : g.block_threads;

@@ -222,10 +222,10 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
 // per-site outputs (NULL: not wanted), a_row / b_row their bytes per site (0: the pedigree has none).
 int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
                const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior, const MoreArgs &lead,
-               int base_at, int64_t site_base) {
+               int base_at, int64_t site_base, size_t prior_row_, int staged_at) {
   const int N = c->model.n_members;
   const size_t row = size_t(3) * N * sizeof(double), pl_row = pl16 ? size_t(n_seq) * 3 * sizeof(uint16_t) : 0;
-  const size_t prior_row = prior ? 6 * sizeof(double) : 0;
+  const size_t prior_row = prior ? prior_row_ : 0;
   ChunkJob job;
   job.n_sites = n_sites;
   job.chunk = chunk_for(c, n_sites, std::max(row, a_row + 1));
@@ -249,7 +249,8 @@ int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, c
     MoreArgs more = lead;
     const long chunk_base = long(site_base + lo);  // (read when the launch is enqueued)
     if (base_at >= 0) more.at[base_at] = const_cast<long *>(&chunk_base);
-    more.at[more.n++] = &d_prior;  // (behind the last parameter of a plain form: not read)
+    if (staged_at >= 0) more.at[staged_at] = &d_prior;
+    else more.at[more.n++] = &d_prior;  // (behind the last parameter of a plain form: not read)
     HIP_TRY(c, launch_generated(c, g, n, d[B_LK].as<double>(), flags ? d[B_FLAGS].as<uint8_t>() : nullptr, out_a ? d[B_OUT_A].p : nullptr,
                                 out_b ? d[B_OUT_B].p : nullptr, status ? d[B_STATUS].as<uint8_t>() : nullptr, s_k, 0, more));
     return 0;

@@ -556,6 +556,49 @@ int famseq_sample_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const dou
 /* The generator of the entries above, one block: Philox4x32-10 of counter ctr under key -> out (Random123's known answers). */
 void famseq_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
+/* ---- the founders' allele frequency by maximum likelihood ---------------------------------------------------------------
+ * Parameter learning: the site-prior entries above take the founders' allele frequency from outside; this one estimates it
+ * from the family's own reads, by EM on the pedigree network, and reports the likelihood ratio against "no founder carries
+ * the allele", a variant statistic that rests on no prior at all.
+ * The founders' genotypes at a site are Hardy-Weinberg draws at allele frequency q: with p = 1 - q the rows famseq_hwe_priors
+ * makes, (p p, 2 q p, q q) for female founders and every founder off chrX, (p, 0, q) for male founders at a chrX site.  Z(q)
+ * is the network's total weight under those rows, m_f(q) founder f's marginal row.  One step from q:
+ *     A = sum over the founders, in PED order, of (m_f1 + 2 m_f2) / (m_f0 + m_f1 + m_f2)
+ *         [a male founder at a chrX site: m_f2 / (m_f0 + m_f1 + m_f2)]
+ *     C = 2 (founders)   [at a chrX site: 2 (female founders) + (male founders)]
+ *     q' = min(A / C, 1.0)
+ *   af0 [n_sites]        the start values, each in [0, 1]; required.
+ *   n_iter               the steps T, 0 .. FAMSEQ_MAX_AF_ITER.  No early exit and no convergence test: the trip count is the
+ *              call's, and the result is "q after T steps", a function of the site's inputs alone.
+ *   af [n_sites]         q_T; T = 0 returns af0's bits.
+ *   loglik [n_sites][2]  [0] log10 Z(q_T) on famseq_evidence_batch's scale — at T = 0 famseq_evidence_prior_batch's bits on
+ *              famseq_hwe_priors(af0); it does not decrease with T.  [1] the same at q = 0, where every founder is hom-ref: -inf
+ *              where the data exclude that, which is a result, not a failure.  [0] - [1] is the log10 likelihood ratio for
+ *              "the allele is present among the founders".
+ *   status [n_sites]     0 OK; 1 the single-posterior failure rule of famseq_bn_batch under af0's rows (what
+ *              famseq_evidence_prior_batch says of famseq_hwe_priors(af0)); 2 an af0 outside [0, 1] (device entry; the host
+ *              entry refuses the call), a Z(q_t), t = 0 .. T, that is <= 0 or not finite, or a founder's row sum that is.
+ *              Wherever status != 0, af and both loglik entries are NaN.  FAMSEQ_FLAG_KNOWN is not read.
+ * Chaining: T = a, then T = b from the first call's af, gives the bits of one call with T = a + b.
+ * One kernel launch reads a site's rows once and runs T + 2 sum passes on them (the founders' marginals in T of them).  Served
+ * by the sum-product engine's graph as famseq_evidence_batch is, whatever the context's engine; the kernel (famseq_af) is
+ * compiled on the first call or ahead through famseq_set_option "af_kernels" = 1.  famseq_plan_json: "af_code_object",
+ * "af_variant".  The prior is the unknown here: there is no site-prior form.
+ * FAMSEQ_E_ARG, with a message and before the device is asked for: n_iter outside 0 .. FAMSEQ_MAX_AF_ITER, af0 NULL, (host
+ * entry) the first af0[s] that is not a finite number in [0, 1], named by its site index. */
+#define FAMSEQ_MAX_AF_ITER 64
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_evidence_batch.  Any of af / loglik / status may be NULL. */
+int famseq_af_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                    int32_t n_seq, const uint8_t *flags, const double *af0, int32_t n_iter, double *af, double *loglik,
+                    uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array), d_af0 among them — nothing is checked
+ * of its contents: enqueues on `stream` (a hipStream_t; NULL = the default stream) and returns without synchronising. */
+int famseq_af_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16, const int32_t *seq_members,
+                           int32_t n_seq, const uint8_t *d_flags, const double *d_af0, int32_t n_iter, double *d_af,
+                           double *d_loglik, uint8_t *d_status, void *stream);
+
 /* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] = ((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);
