@@ -210,6 +210,10 @@ extern "C" void famseq_destroy(famseq_ctx *c) {
     for (int s = 0; s < kSlots; ++s)
       for (hipEvent_t ev : {c->ev_in[s], c->ev_done[s], c->ev_out[s]})
         if (ev) (void)hipEventDestroy(ev);
+    if (c->ev_state) (void)hipEventDestroy(c->ev_state);
+    for (hipEvent_t ev : c->ev_stage)
+      if (ev) (void)hipEventDestroy(ev);
+    if (c->stage_mem) (void)hipHostFree(c->stage_mem);
   }
   delete c;  // (its device buffers go with it)
 }
@@ -419,13 +423,83 @@ extern "C" int famseq_bn_batch_device(famseq_ctx *c, int64_t n_sites, const doub
 
 namespace {
 
-// Upload the sequenced-member list (VCF column order) and its inverse when it changes.
-int set_sequenced(famseq_ctx *c, const int32_t *seq, int n_seq) {
+// A device-entry call that touches what the context's device entries share (ctx.h, ev_state): begin() puts it behind the last
+// such call where that one went to another stream — the event is recorded on that stream only now, behind everything it has
+// been given since, so calls that stay on one stream pay nothing — and names its own stream as the one to wait for next.
+// Never waits on the host, unless that other stream is gone (destroyed by its owner: the whole device is waited for instead).
+struct StateCall {
+  hipStream_t stream = nullptr;
+  int begin(famseq_ctx *c, hipStream_t s) {
+    if (c->state_used && c->state_stream != s) {
+      if (!c->ev_state) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_state, hipEventDisableTiming));
+      if (hipEventRecord(c->ev_state, c->state_stream) == hipSuccess) {
+        HIP_TRY(c, hipStreamWaitEvent(s, c->ev_state, 0));
+      } else {
+        (void)hipGetLastError();
+        HIP_TRY(c, hipDeviceSynchronize());
+      }
+    }
+    c->state_stream = stream = s, c->state_used = true;
+    return 0;
+  }
+};
+
+// Before the host touches that state (a host entry rewrites the maps, the scratch is freed to grow): every device-entry call
+// that uses it has run.  (Each is behind its predecessor, so the last one's stream stands for all.)
+int state_drained(famseq_ctx *c) {
+  if (c->state_used && hipStreamSynchronize(c->state_stream) != hipSuccess) {
+    (void)hipGetLastError();
+    HIP_TRY(c, hipDeviceSynchronize());
+  }
+  return 0;
+}
+
+// Small host blocks to device memory on `stream`, without waiting for it: through the next pinned slot of the context's ring.
+// The host waits only where all kStageRing slots hold copies that have not run yet.
+struct StageCopy {
+  void *dst;
+  const void *src;
+  size_t bytes;
+};
+int stage_copies(famseq_ctx *c, hipStream_t stream, std::initializer_list<StageCopy> list) {
+  if (!c->stage_mem) {
+    c->stage_bytes = (std::max(sizeof(CallIO), size_t(3) * c->model.n_members * sizeof(int32_t)) + 63) / 64 * 64;
+    for (hipEvent_t &ev : c->ev_stage)
+      if (!ev) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    void *p = nullptr;
+    HIP_TRY(c, hipHostMalloc(&p, c->stage_bytes * kStageRing, hipHostMallocDefault));
+    c->stage_mem = static_cast<char *>(p);
+  }
+  const int i = c->stage_next;
+  if (c->stage_used[i]) HIP_TRY(c, hipEventSynchronize(c->ev_stage[i]));
+  char *at = c->stage_mem + size_t(i) * c->stage_bytes;
+  size_t used = 0;
+  for (const StageCopy &a : list) {
+    if (!a.bytes) continue;
+    if (used + a.bytes > c->stage_bytes) return fail(c, FAMSEQ_E_HIP, "staging slot too small (internal)");
+    std::memcpy(at + used, a.src, a.bytes);
+    HIP_TRY(c, hipMemcpyAsync(a.dst, at + used, a.bytes, hipMemcpyHostToDevice, stream));
+    used += a.bytes;
+  }
+  HIP_TRY(c, hipEventRecord(c->ev_stage[i], stream));
+  c->stage_used[i] = true;
+  c->stage_next = (i + 1) % kStageRing;
+  return 0;
+}
+
+// Upload the sequenced-member list (VCF column order) and its inverse when it changes.  A host entry (state == NULL) first waits
+// for the device-entry calls that read the maps, or that brought them up to date on a stream of the caller's, then copies
+// synchronously; a device entry, inside its StateCall, copies on its stream, behind whatever still reads the old maps.
+int set_sequenced(famseq_ctx *c, const int32_t *seq, int n_seq, const StateCall *state = nullptr) {
   if (n_seq < 0 || n_seq > c->model.n_members || (n_seq > 0 && !seq)) return fail(c, FAMSEQ_E_ARG, "bad sequenced-member list");
   std::vector<int32_t> v(seq, seq + n_seq), col(c->model.n_members, -1);
   for (int k = 0; k < n_seq; ++k) {
     if (v[k] < 0 || v[k] >= c->model.n_members || col[v[k]] >= 0) return fail(c, FAMSEQ_E_ARG, "bad sequenced-member list");
     col[v[k]] = k;
+  }
+  if (!state) {
+    const int rc = state_drained(c);
+    if (rc != 0) return rc;
   }
   if (c->d_seq && v == c->seq_members) return 0;
   for (DevBuf *b : {&c->d_seq, &c->d_col, &c->d_slot})
@@ -434,11 +508,25 @@ int set_sequenced(famseq_ctx *c, const int32_t *seq, int n_seq) {
   std::vector<int32_t> slot(col);
   for (int p = 0, next = n_seq; p < c->model.n_members; ++p)
     if (slot[p] < 0) slot[p] = next++;
-  HIP_TRY(c, hipMemcpy(c->d_slot.p, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (n_seq) HIP_TRY(c, hipMemcpy(c->d_seq.p, v.data(), n_seq * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(c->d_col.p, col.data(), col.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  const size_t all = slot.size() * sizeof(int32_t);
+  if (state) {
+    const int rc = stage_copies(c, state->stream, {{c->d_slot.p, slot.data(), all}, {c->d_seq.p, v.data(), n_seq * sizeof(int32_t)}, {c->d_col.p, col.data(), all}});
+    if (rc != 0) {
+      c->seq_members.assign(1, -1);  // (what reached the device is unknown; no caller can name this list: the next call uploads again)
+      return rc;
+    }
+  } else {
+    HIP_TRY(c, hipMemcpy(c->d_slot.p, slot.data(), all, hipMemcpyHostToDevice));
+    if (n_seq) HIP_TRY(c, hipMemcpy(c->d_seq.p, v.data(), n_seq * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_col.p, col.data(), all, hipMemcpyHostToDevice));
+  }
   c->seq_members = v;
   return 0;
+}
+
+bool same_call_io(const CallIO &a, const CallIO &b) {  // (field by field: the struct has padding)
+  return a.pl == b.pl && a.lut == b.lut && a.col == b.col && a.slot == b.slot && a.gpp == b.gpp && a.fpp == b.fpp && a.fgt == b.fgt &&
+         a.n_seq == b.n_seq && a.magic_w == b.magic_w && a.magic_n == b.magic_n && a.phase_clk == b.phase_clk;
 }
 
 }  // namespace
@@ -641,9 +729,11 @@ extern "C" int famseq_bn_call_batch_device(famseq_ctx *c, int64_t n_sites, const
   if (rc != 0) return rc;
   if (d_text && (reinterpret_cast<uintptr_t>(d_text) & 15)) return fail(c, FAMSEQ_E_ARG, "d_text must be 16-byte aligned");
   HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = set_sequenced(c, seq_members, n_seq)) != 0) return rc;
-  if (n_sites == 0) return 0;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
+  // the maps, the argument block and the scratch are the context's: this call takes its place behind the last one that used them
+  StateCall state;
+  if ((rc = state.begin(c, stream)) != 0 || (rc = set_sequenced(c, seq_members, n_seq, &state)) != 0) return rc;
+  if (n_sites == 0) return 0;
   const int N = c->model.n_members;
   const bool want_text = d_text != nullptr;
   // what the stages write: the caller's arrays, or scratch of this context's for those the caller does not ask for but a later
@@ -655,7 +745,9 @@ extern "C" int famseq_bn_call_batch_device(famseq_ctx *c, int64_t n_sites, const
   DevBuf *tmp = c->dev_tmp;  // lk, post, single; gpp, fpp, fgt; status
   if ((need_rows && (!tmp[0] || c->dev_tmp_sites < n_sites)) || (need_called && (!tmp[3] || c->dev_tmp_sites < n_sites || c->dev_tmp_seq < n_seq)) ||
       (need_status && (!tmp[6] || c->dev_tmp_sites < n_sites))) {
-    HIP_TRY(c, hipStreamSynchronize(stream));  // nothing of an earlier call may still use what is freed here
+    // nothing of an earlier call, on whatever stream, may still use what is freed here: the one wait of this entry, on the
+    // first call and where a batch is larger than any before
+    if ((rc = state_drained(c)) != 0) return rc;
     const int64_t cap = std::max(n_sites, c->dev_tmp_sites);
     const int seqcap = std::max<int>(n_seq, c->dev_tmp_seq);
     const bool had_rows = bool(tmp[0]), had_called = bool(tmp[3]);
@@ -679,11 +771,11 @@ extern "C" int famseq_bn_call_batch_device(famseq_ctx *c, int64_t n_sites, const
   if (d_pl16 && (rc = upload_lut(c)) != 0) return rc;
   const CallIO cio = make_call_io(c, d_pl16, gpp, fpp, fgt, n_seq);
   if (!c->d_call_dev) HIP_TRY(c, c->d_call_dev.alloc(sizeof(CallIO)));
-  if (!c->call_dev_valid || std::memcmp(&cio, &c->call_dev_host, sizeof cio) != 0) {
-    // the argument block changes only when the caller's pointers do: written synchronously, after whatever of this stream
-    // may still read the old one
-    HIP_TRY(c, hipStreamSynchronize(stream));
-    HIP_TRY(c, hipMemcpy(c->d_call_dev.p, &cio, sizeof cio, hipMemcpyHostToDevice));
+  if (!c->call_dev_valid || !same_call_io(cio, c->call_dev_host)) {
+    // the argument block changes only when the caller's pointers do: written on this stream, behind whatever may still read
+    // the old one (an earlier call on another stream: StateCall)
+    c->call_dev_valid = false;
+    if ((rc = stage_copies(c, stream, {{c->d_call_dev.p, &cio, sizeof cio}})) != 0) return rc;
     c->call_dev_host = cio, c->call_dev_valid = true;
   }
   hipError_t e = hipSuccess;
@@ -720,15 +812,18 @@ namespace {
 int trio_form(const void *joint, const void *dnm) { return (joint ? 2 : 0) | (dnm || !joint ? 1 : 0); }
 
 // Arguments the side products' entries check the same way; loads the kernel of that kind (trio: of the form the outputs ask for).
+// state: a device entry's (on `stream`), begun here where the input is packed — the maps and the unpacked rows are the
+// context's; on likelihood rows a device entry uses nothing of the context's that changes.  NULL: a host entry.
 int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl16, const int32_t *seq_members, int32_t n_seq,
-                  int kind) {
+                  int kind, StateCall *state = nullptr, hipStream_t stream = nullptr) {
   int rc = check_input(c, n_sites, lk, pl16, "lk / pl16", false, n_seq);
   if (rc != 0) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   if ((rc = load_or_fail(c, kind)) != 0) return rc;
   if (pl16) {
     if (n_seq < 1) return fail(c, FAMSEQ_E_ARG, "n_seq must be >= 1");
-    if ((rc = set_sequenced(c, seq_members, n_seq)) != 0) return rc;
+    if (state && (rc = state->begin(c, stream)) != 0) return rc;
+    if ((rc = set_sequenced(c, seq_members, n_seq, state)) != 0) return rc;
     if ((rc = upload_lut(c)) != 0) return rc;
   }
   return 0;
@@ -808,7 +903,10 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
     if ((rc = check_input(c, n_sites, in.lk, in.pl16, "lk / pl16", false, in.n_seq)) != 0 || (rc = prior_ready(c, n_sites, in.flags, prior, kind)) != 0)
       return rc;
   }
-  if ((rc = trio_prologue(c, n_sites, in.lk, in.pl16, in.seq_members, in.n_seq, kind)) != 0 || n_sites == 0) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  StateCall state;  // (a device entry on packed input)
+  if ((rc = trio_prologue(c, n_sites, in.lk, in.pl16, in.seq_members, in.n_seq, kind, device ? &state : nullptr, stream)) != 0 || n_sites == 0)
+    return rc;
   // the arguments in front of the prior rows (the pattern kernels' masks and their number)
   const uint8_t *d_masks = pat ? pat->masks : nullptr;
   const int32_t n_patterns = pat ? pat->n_patterns : 1;
@@ -841,12 +939,11 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
     return side_batch(c, c->side_slots[id], c->kern[kind], n_sites, in.lk, in.pl16, in.n_seq, in.flags, out_a, row[0], out_b, row[1], status, prior,
                       lead, smp ? 1 : -1, site_base);
   }
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
   const double *d_lk = in.lk;
   if (in.pl16) {  // packed input is unpacked into likelihood rows this context keeps (grown on demand)
     const int N = c->model.n_members;
     if (c->trio_dev_sites < n_sites) {
-      HIP_TRY(c, hipStreamSynchronize(stream));  // nothing of an earlier call may still use what is freed here
+      if ((rc = state_drained(c)) != 0) return rc;  // nothing of an earlier call, on whatever stream, may still use what is freed here
       c->trio_dev_sites = 0;
       HIP_TRY(c, c->trio_dev_lk.alloc(size_t(n_sites) * 3 * N * sizeof(double)));
       c->trio_dev_sites = n_sites;

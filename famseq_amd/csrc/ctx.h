@@ -97,6 +97,7 @@ struct GenKernel {
 
 constexpr int kSlots = 2;
 constexpr int kStages = 3;
+constexpr int kStageRing = 16;  // pinned staging slots of the device entries' small uploads (famseq_ctx::stage_mem)
 
 // The device side of the chunked host pipeline: kSlots copies of every array a chunk passes through.  A set only grows
 // (in sites and in bytes per site), so that varying batch sizes do not thrash.
@@ -184,6 +185,23 @@ struct famseq_ctx {
   int64_t dev_tmp_sites = 0;
   int dev_tmp_seq = 0;
   famseq::DevBuf trio_dev_lk;  // the side products' device entries' likelihood rows for packed input
+  // What the device entries share across calls — the column maps, d_call_dev, dev_tmp, trio_dev_lk — is used in the order the
+  // calls are issued, whatever streams they are on: state_stream is the stream of the last device-entry call that touches any
+  // of it; such a call on another stream records ev_state on state_stream and waits for it, a host entry and a growth of the
+  // scratch wait for state_stream on the host.  Every such call is behind its predecessor that way, so the last stream stands
+  // for all of them, and calls that stay on one stream record and wait for nothing.  The entries that use none of that state
+  // (famseq_bn_batch_device, famseq_bn_prior_batch_device, the side entries on d_lk) take no part.
+  hipEvent_t ev_state = nullptr;
+  hipStream_t state_stream = nullptr;
+  bool state_used = false;
+  // The maps and the argument block reach the device on the caller's stream, from pinned memory (an asynchronous copy from
+  // pageable memory waits for the stream): a ring of kStageRing slots of stage_bytes each, a slot written again only after the
+  // copy out of it has run (ev_stage, recorded behind that copy; stage_used: it has been).
+  char *stage_mem = nullptr;
+  size_t stage_bytes = 0;
+  hipEvent_t ev_stage[famseq::kStageRing] = {};
+  bool stage_used[famseq::kStageRing] = {};
+  int stage_next = 0;
   // the pattern host entries' masks: FAMSEQ_MAX_PATTERNS rows, staged per call from a copy the context keeps, on the compute stream
   famseq::DevBuf d_masks;
   std::vector<uint8_t> masks_host;

@@ -192,7 +192,29 @@ int famseq_bn_batch_sharded(famseq_ctx *const *ctxs, int n_ctx, int64_t n_sites,
 
 /* Device buffers already resident in HBM on ctx's device.  Enqueues on `stream`
  * (a hipStream_t; NULL = the default stream) and returns without synchronising.
- * d_post_single and d_status may be NULL. */
+ * d_post_single and d_status may be NULL.
+ *
+ * THE STREAM RULE, of this and of every other entry whose name ends in _device and that takes a stream (each refers here):
+ *   - Everything the entry does on the device — kernels, and the small uploads some entries make — is enqueued on `stream`,
+ *     in the order of the calls; the host returns while the stream may still be busy with what was put on it before.  The
+ *     caller's buffers, inputs and outputs, belong to the call until the stream has passed it.
+ *   - What may block the host is the first call of a kind or of a shape, and nothing after it: loading (or compiling) a
+ *     kernel the context has not used yet, uploading a table on first use, and allocating or growing scratch this context
+ *     keeps (famseq_bn_call_batch_device for batches that are not served fused or outputs the caller does not pass; the side
+ *     entries' unpacked rows for d_pl16) — growing waits until every earlier call that uses that scratch has run, on
+ *     whatever stream, and a batch no larger than one before it grows nothing.  Also: once 16 uploads of changed
+ *     seq_members / changed pointers are enqueued and none has run, the next one waits for the oldest.
+ *   - Calls that touch state the context keeps on the device — the column maps made from seq_members, the call path's
+ *     argument block, the scratch above: famseq_bn_call_batch_device always, a side entry when it is given d_pl16 — take
+ *     effect in the order they are issued, whatever streams they are on: such a call on another stream than the last one's
+ *     waits on the device (an event recorded on that stream when the later call is issued, hipStreamWaitEvent) for that one
+ *     and for what its stream has been given since, and a host entry that reads or rewrites the maps waits for them on the
+ *     host.  A later call never changes what an earlier, still pending one reads; calls that stay on one stream add no event
+ *     and no wait.  (A stream should outlive the work it was given; where the last such call's stream has been destroyed, the
+ *     next one waits for the whole device instead.)  famseq_bn_batch_device,
+ *     famseq_bn_prior_batch_device and the side entries given d_lk use no such state: no event, no wait, and calls on
+ *     different streams may overlap.
+ *   - Capturing these entries into a HIP graph is not supported (uploads from staging memory the context reuses, events). */
 int famseq_bn_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint8_t *d_flags,
                            double *d_post, double *d_post_single, uint8_t *d_status, void *stream);
 
@@ -242,8 +264,9 @@ int famseq_bn_call_text_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk
                               const uint8_t *flags, const int32_t *seq_members, int32_t n_seq, char *text, uint8_t *status);
 
 /* The call path on DEVICE buffers already resident on ctx's device: enqueues on `stream` (a hipStream_t; NULL = the default stream)
- * and returns without synchronising; nothing crosses the host link.  Exactly one of d_lk / d_pl16; seq_members is a HOST array
- * (uploaded when it changes); any of d_gpp / d_fpp / d_fgt / d_status / d_text may be NULL (d_text: 16-byte aligned,
+ * and returns without synchronising (the stream rule at famseq_bn_batch_device; this entry uses the context's column maps,
+ * argument block and scratch); nothing crosses the host link.  Exactly one of d_lk / d_pl16; seq_members is a HOST array
+ * (uploaded on `stream` when it changes); any of d_gpp / d_fpp / d_fgt / d_status / d_text may be NULL (d_text: 16-byte aligned,
  * [n_sites][n_seq][FAMSEQ_TEXT_STRIDE]).  The same kernels as famseq_bn_call_batch / famseq_bn_call_text_batch; batches they do not
  * serve fused go through scratch rows this context keeps (grown on demand). */
 int famseq_bn_call_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
@@ -280,7 +303,7 @@ int famseq_trio_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const 
                       int32_t n_seq, const uint8_t *flags, double *joint, double *dnm, uint8_t *status);
 
 /* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
- * NULL = the default stream) and returns without synchronising.  Packed input goes through likelihood rows this context keeps. */
+ * NULL = the default stream) and returns without synchronising (the stream rule at famseq_bn_batch_device).  Packed input goes through likelihood rows this context keeps. */
 int famseq_trio_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                              const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_joint, double *d_dnm,
                              uint8_t *d_status, void *stream);
@@ -310,7 +333,7 @@ int famseq_map_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const u
                      int32_t n_seq, const uint8_t *flags, int8_t *map_gt, double *map_post, uint8_t *status);
 
 /* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
- * NULL = the default stream) and returns without synchronising. */
+ * NULL = the default stream) and returns without synchronising (the stream rule at famseq_bn_batch_device). */
 int famseq_map_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                             const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, int8_t *d_map_gt,
                             double *d_map_post, uint8_t *d_status, void *stream);
@@ -337,7 +360,7 @@ int famseq_bn_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, co
                           double *post, double *post_single, uint8_t *status);
 
 /* The same on device buffers resident on ctx's device: enqueues on `stream` (a hipStream_t; NULL = the default stream) and
- * returns without synchronising.  Nothing is checked of d_prior's contents. */
+ * returns without synchronising (the stream rule at famseq_bn_batch_device).  Nothing is checked of d_prior's contents. */
 int famseq_bn_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint8_t *d_flags,
                                  const double *d_prior, double *d_post, double *d_single, uint8_t *d_status, void *stream);
 
@@ -372,7 +395,7 @@ int famseq_map_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, c
                            int32_t n_seq, const uint8_t *flags, const double *prior, int8_t *map_gt, double *map_post, uint8_t *status);
 
 /* The same on device buffers resident on ctx's device (seq_members is a host array): enqueue on `stream` (a hipStream_t;
- * NULL = the default stream) and return without synchronising.  Nothing is checked of d_prior's contents. */
+ * NULL = the default stream) and return without synchronising (the stream rule at famseq_bn_batch_device).  Nothing is checked of d_prior's contents. */
 int famseq_trio_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                    const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                    double *d_joint, double *d_dnm, uint8_t *d_status, void *stream);
@@ -405,7 +428,7 @@ int famseq_evidence_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, co
                           int32_t n_seq, const uint8_t *flags, double *loglik, double *pref, uint8_t *status);
 
 /* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
- * NULL = the default stream) and returns without synchronising. */
+ * NULL = the default stream) and returns without synchronising (the stream rule at famseq_bn_batch_device). */
 int famseq_evidence_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                  const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_loglik, double *d_pref,
                                  uint8_t *d_status, void *stream);
@@ -449,7 +472,7 @@ int famseq_loo_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const u
                      int32_t n_seq, const uint8_t *flags, double *loo, double *fit, uint8_t *status);
 
 /* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
- * NULL = the default stream) and returns without synchronising. */
+ * NULL = the default stream) and returns without synchronising (the stream rule at famseq_bn_batch_device). */
 int famseq_loo_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16, const int32_t *seq_members,
                             int32_t n_seq, const uint8_t *d_flags, double *d_loo, double *d_fit, uint8_t *d_status, void *stream);
 
@@ -493,7 +516,7 @@ int famseq_pattern_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, con
 
 /* The same on device buffers resident on ctx's device (seq_members is a host array), d_masks among them — it must stay valid
  * and unchanged until the kernel has run, and only its low three bits per byte are read: enqueues on `stream` (a hipStream_t;
- * NULL = the default stream) and returns without synchronising. */
+ * NULL = the default stream) and returns without synchronising (the stream rule at famseq_bn_batch_device). */
 int famseq_pattern_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                 const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const uint8_t *d_masks,
                                 int32_t n_patterns, double *d_pat_post, double *d_loglik, uint8_t *d_status, void *stream);
@@ -537,7 +560,7 @@ int famseq_sample_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, cons
                         double *samp_post, uint8_t *status);
 
 /* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
- * NULL = the default stream) and returns without synchronising. */
+ * NULL = the default stream) and returns without synchronising (the stream rule at famseq_bn_batch_device). */
 int famseq_sample_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, uint64_t seed, int64_t site_base,
                                int32_t n_draws, int8_t *d_samp_gt, double *d_samp_post, uint8_t *d_status, void *stream);
@@ -594,7 +617,7 @@ int famseq_af_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const ui
                     uint8_t *status);
 
 /* The same on device buffers resident on ctx's device (seq_members is a host array), d_af0 among them — nothing is checked
- * of its contents: enqueues on `stream` (a hipStream_t; NULL = the default stream) and returns without synchronising. */
+ * of its contents: enqueues on `stream` (a hipStream_t; NULL = the default stream) and returns without synchronising (the stream rule at famseq_bn_batch_device). */
 int famseq_af_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16, const int32_t *seq_members,
                            int32_t n_seq, const uint8_t *d_flags, const double *d_af0, int32_t n_iter, double *d_af,
                            double *d_loglik, uint8_t *d_status, void *stream);

@@ -147,6 +147,7 @@ def _nccl_worker(rank, world, port, n_sites, out):
     lk, fl = fs.synth.gen_batch_torch(mo.tolist(), fa.tolist(), hi - lo, 1, first_site=lo, device=dev)
     post = torch.empty_like(lk)
     ctx = fs.Context(fs.make_model(ped), device=rank, enum_impl=1)  # one kernel on both sides: same bits
+    # (the null stream; a busy side stream of the caller's: tests/test_gpu_streams.py)
     ctx.bn_batch_device(hi - lo, lk.data_ptr(), fl.data_ptr(), post.data_ptr(), 0, 0, torch.cuda.current_stream().cuda_stream)
     full = fs.shard.gather_sites(post, n_sites)  # RCCL all_gather on the device tensors
     t = fs.shard.max_over_ranks(1.0 + rank, device=dev)

@@ -126,7 +126,7 @@ def test_device_resident_call_path_gives_the_host_entry_bits(label, opts):
     d_gpp, d_fpp = torch.empty((s, ped.n, 3), dtype=torch.float64, device=dev), torch.empty((s, ped.n, 3), dtype=torch.float64, device=dev)
     d_fgt, d_st = torch.empty((s, ped.n), dtype=torch.int8, device=dev), torch.empty(s, dtype=torch.uint8, device=dev)
     d_text = torch.zeros((s, ped.n, fs.TEXT_STRIDE), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = torch.cuda.current_stream().cuda_stream  # (the null stream; a busy side stream of the caller's: tests/test_gpu_streams.py)
     ctx.bn_call_batch_device(s, seq, d_pl16=d_pl.data_ptr(), d_flags=d_fl.data_ptr(), d_gpp=d_gpp.data_ptr(), d_fpp=d_fpp.data_ptr(),
                              d_fgt=d_fgt.data_ptr(), d_status=d_st.data_ptr(), d_text=d_text.data_ptr(), stream=stream)
     torch.cuda.synchronize()
