@@ -89,6 +89,7 @@ ABI_SYMBOLS = [
     "famseq_pattern_batch", "famseq_pattern_batch_device", "famseq_pattern_prior_batch", "famseq_pattern_prior_batch_device",
     "famseq_sample_batch", "famseq_sample_batch_device", "famseq_sample_prior_batch", "famseq_sample_prior_batch_device",
     "famseq_af_batch", "famseq_af_batch_device",
+    "famseq_relabel_batch", "famseq_relabel_batch_device", "famseq_relabel_prior_batch", "famseq_relabel_prior_batch_device",
 ]
 # (and famseq_philox4x32_10, the one name with digits in it: philox4x32 below)
 PL_MISSING = 0xFFFF
@@ -177,8 +178,10 @@ def lib():
     # (more: what an entry takes between the prior rows and its outputs, as the host and the device entry declare it)
     masks = ([bp, C.c_int32], [vp, C.c_int32])
     draws = ([C.c_uint64, C.c_int64, C.c_int32],) * 2  # seed, site_base, n_draws
+    assigns = ([ip, C.c_int32], [vp, C.c_int32])
     for name, out_a, more in (("trio", dp, ([], [])), ("map", C.POINTER(C.c_int8), ([], [])), ("evidence", dp, ([], [])), ("loo", dp, ([], [])),
-                              ("pattern", dp, masks), ("sample", C.POINTER(C.c_int8), draws)):
+                              ("pattern", dp, masks), ("sample", C.POINTER(C.c_int8), draws),
+                              ("relabel", dp, assigns)):
         for prior in (0, 1):
             host = getattr(L, "famseq_%s%s_batch" % (name, "_prior" * prior))
             dev = getattr(L, "famseq_%s%s_batch_device" % (name, "_prior" * prior))
@@ -292,6 +295,26 @@ def segregation_masks(n, affected, unaffected=(), model="dominant"):
     row = np.full(n, 7, np.uint8)
     row[aff], row[unaff] = SEGREGATION_MASKS[model]
     return row
+
+
+MAX_RELABEL = 64
+
+
+def swap_assignments(n, members=None):
+    """The assignment rows of every transposition of two of `members` (member indices in PED order; default all n) for
+    Context.relabel_batch: -> (assign [M, n] int32, pairs), pairs[k] = (i, j) the two members row k exchanges, i before j in the
+    order of `members`, the pairs ordered (first, second) in that order.  Everybody else keeps their own row."""
+    mem = list(range(n)) if members is None else [int(i) for i in members]
+    for i in mem:
+        if not 0 <= i < n:
+            raise ValueError("member index %d is outside 0..%d" % (i, n - 1))
+    if len(set(mem)) != len(mem):
+        raise ValueError("members are listed twice: %s" % sorted(i for i in set(mem) if mem.count(i) > 1))
+    pairs = [(mem[a], mem[b]) for a in range(len(mem)) for b in range(a + 1, len(mem))]
+    assign = np.tile(np.arange(n, dtype=np.int32), (len(pairs), 1))
+    for k, (i, j) in enumerate(pairs):
+        assign[k, i], assign[k, j] = j, i
+    return assign, pairs
 
 
 def make_model(ped: Pedigree, mrate=1e-7, lc=1.0, genoProbN=None, genoProbK=None, genoProbXN=None,
@@ -650,6 +673,48 @@ class Context:
         """pattern_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
         self._side_device("pattern", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_pat_post, d_loglik, d_status, stream,
                           (d_masks or None, int(n_patterns)))
+
+    @staticmethod
+    def _assign(assign, n):
+        """assign [M, N] (or one row [N]) as a contiguous int32 array."""
+        a = np.ascontiguousarray(assign, dtype=np.int32)
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[1] != n:
+            raise ValueError("assign must have shape [n_assign, %d]" % n)
+        return a
+
+    def relabel_batch(self, assign, lk=None, pl16=None, seq_members=None, flags=None, want_alt=True, want_loglik=True):
+        """Relabelling evidence: -> (alt_loglik[S,M] float64, loglik[S] float64, status[S] uint8).
+        assign [M, N] int32 (PED order): assign[m, p] is the member whose likelihood row member p is given under hypothesis m,
+        -1 for no data (the row (1, 1, 1)); a row need not be a permutation.  alt_loglik[s, m] = log10 of the site's likelihood
+        under the pedigree with the rows so assigned (evidence_batch's bits on the rows rearranged; -inf where it is exactly 0);
+        loglik is evidence_batch's.  alt_loglik - loglik summed over sites is the log10 Bayes factor of the relabelling.
+        swap_assignments() makes the rows of every transposition.  Input is either lk [S,N,3] float64 or pl16 [S,n_seq,3] uint16
+        in VCF column order (seq_members: their PED indices).  want_* False: not computed, None."""
+        a = self._assign(assign, self.n)
+        outs = lambda s: (np.empty((s, a.shape[0])) if want_alt else None, np.empty(s) if want_loglik else None)
+        return self._side_host("relabel", None, lk, pl16, seq_members, flags, outs, (_p(a, C.c_int32), a.shape[0]))
+
+    def relabel_prior_batch(self, prior, assign, lk=None, pl16=None, seq_members=None, flags=None, want_alt=True, want_loglik=True):
+        """relabel_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give relabel_batch's bits."""
+        a = self._assign(assign, self.n)
+        outs = lambda s: (np.empty((s, a.shape[0])) if want_alt else None, np.empty(s) if want_loglik else None)
+        return self._side_host("relabel", prior, lk, pl16, seq_members, flags, outs, (_p(a, C.c_int32), a.shape[0]))
+
+    def relabel_device(self, n_sites, d_assign, n_assign, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_alt=0, d_loglik=0,
+                             d_status=0, stream=0):
+        """relabel_batch on resident buffers (raw device pointers as ints; 0 = not given), d_assign [n_assign, N] int32 among
+        them (an entry outside 0 .. N-1 is taken as -1); enqueues on `stream` and returns."""
+        self._side_device("relabel", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_alt, d_loglik, d_status, stream,
+                          (d_assign or None, int(n_assign)))
+
+    def relabel_prior_device(self, n_sites, d_prior, d_assign, n_assign, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_alt=0,
+                                   d_loglik=0, d_status=0, stream=0):
+        """relabel_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("relabel", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_alt, d_loglik, d_status, stream,
+                          (d_assign or None, int(n_assign)))
 
     def af_batch(self, af0, n_iter, lk=None, pl16=None, seq_members=None, flags=None, want_af=True, want_loglik=True):
         """The founders' allele frequency by maximum likelihood: -> (af[S] float64, loglik[S,2] float64, status[S] uint8).

@@ -886,10 +886,28 @@ int check_af(famseq_ctx *c, const AfIn &af, int64_t n_sites, bool device) {
         return fail(c, FAMSEQ_E_ARG, "af0 entries must be finite numbers in [0, 1] (site " + std::to_string(s) + ")");
   return 0;
 }
+// What the relabelling entries take beside: the assignments [n_assign][N] (host entry: the caller's host array; device entry: resident).
+struct RelabelIn {
+  const int32_t *assign;
+  int32_t n_assign;
+};
+int check_relabel(famseq_ctx *c, const RelabelIn &rel, bool device) {
+  const int N = c->model.n_members;
+  if (rel.n_assign < 1 || rel.n_assign > FAMSEQ_MAX_RELABEL)
+    return fail(c, FAMSEQ_E_ARG, "n_assign must be 1.." + std::to_string(FAMSEQ_MAX_RELABEL) + ", got " + std::to_string(rel.n_assign));
+  if (!rel.assign) return fail(c, FAMSEQ_E_ARG, "assign must be given (n_assign rows of one int32 per member)");
+  if (!device)
+    for (size_t i = 0, n = size_t(rel.n_assign) * N; i < n; ++i)
+      if (rel.assign[i] < -1 || rel.assign[i] >= N)
+        return fail(c, FAMSEQ_E_ARG, "assign: assignment " + std::to_string(i / N) + ", member " + std::to_string(i % N) + " is " +
+                                         std::to_string(rel.assign[i]) + "; an entry is -1 (no data) or a member index 0.." + std::to_string(N - 1));
+  return 0;
+}
 int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device, const SideIn &in, const double *prior, void *out_a,
                void *out_b, uint8_t *status, void *stream_ = nullptr, const PatternIn *pat = nullptr, const SampleIn *smp = nullptr,
-               const AfIn *af = nullptr) {
+               const AfIn *af = nullptr, const RelabelIn *rel = nullptr) {
   if (!c) return FAMSEQ_E_ARG;
+  if (rel && check_relabel(c, *rel, device) != 0) return FAMSEQ_E_ARG;
   if (pat && check_patterns(c, *pat, device) != 0) return FAMSEQ_E_ARG;
   if (smp && check_sample(c, *smp) != 0) return FAMSEQ_E_ARG;
   if (af && check_af(c, *af, in.n_sites, device) != 0) return FAMSEQ_E_ARG;
@@ -917,13 +935,24 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
   // ... or the allele-frequency kernel's start values (the host path: the chunk's staged copy, side_batch) and n_iter
   const double *d_af0 = af ? af->af0 : nullptr;
   const int32_t n_iter = af ? af->n_iter : 0;
-  const MoreArgs lead = pat   ? MoreArgs{&d_masks, &n_patterns}
+  // ... or the relabelling kernels' assignments and their number
+  const int32_t *d_assign = rel ? rel->assign : nullptr;
+  const int32_t n_assign = rel ? rel->n_assign : 1;
+  const MoreArgs lead = rel   ? MoreArgs{&d_assign, &n_assign}
+                        : pat ? MoreArgs{&d_masks, &n_patterns}
                         : smp ? MoreArgs{&seed, &site_base, &n_draws}
                         : af  ? MoreArgs{&d_af0, &n_iter}
                               : MoreArgs{};
   if (!device) {
     size_t row[2];
-    p.rows(c->model, smp ? n_draws : n_patterns, row);
+    p.rows(c->model, smp ? n_draws : (rel ? n_assign : n_patterns), row);
+    if (rel) {  // (staged as the masks below are)
+      const size_t n = size_t(n_assign) * c->model.n_members;
+      if (!c->d_assign) HIP_TRY(c, c->d_assign.alloc(size_t(FAMSEQ_MAX_RELABEL) * c->model.n_members * sizeof(int32_t)));
+      c->assign_host.assign(rel->assign, rel->assign + n);
+      HIP_TRY(c, hipMemcpyAsync(c->d_assign.p, c->assign_host.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream[1]));
+      d_assign = c->d_assign.as<int32_t>();
+    }
     if (pat) {
       // The masks go through a copy the context keeps into a buffer it owns, on the stream the chunks' kernels run on: ordered
       // with them by the stream itself.  (A host entry returns with its streams drained, so neither is in use by an earlier call.)
@@ -1143,6 +1172,41 @@ extern "C" int famseq_af_batch_device(famseq_ctx *c, int64_t n_sites, const doub
   const AfIn in{d_af0, n_iter};
   return side_entry(c, SIDE_AF, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_af, d_loglik, d_status, stream,
                     nullptr, nullptr, &in);
+}
+
+// ---- relabelling evidence: the evidence entries with the assignments of rows to members and their number -------------------
+
+extern "C" int famseq_relabel_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                    int32_t n_seq, const uint8_t *flags, const int32_t *assign, int32_t n_assign, double *alt_loglik,
+                                    double *loglik, uint8_t *status) {
+  const RelabelIn rel{assign, n_assign};
+  return side_entry(c, SIDE_RELABEL, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, alt_loglik, loglik, status, nullptr,
+                    nullptr, nullptr, nullptr, &rel);
+}
+
+extern "C" int famseq_relabel_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const int32_t *d_assign,
+                                           int32_t n_assign, double *d_alt_loglik, double *d_loglik, uint8_t *d_status, void *stream) {
+  const RelabelIn rel{d_assign, n_assign};
+  return side_entry(c, SIDE_RELABEL, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_alt_loglik, d_loglik,
+                    d_status, stream, nullptr, nullptr, nullptr, &rel);
+}
+
+extern "C" int famseq_relabel_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
+                                          const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
+                                          const int32_t *assign, int32_t n_assign, double *alt_loglik, double *loglik, uint8_t *status) {
+  const RelabelIn rel{assign, n_assign};
+  return side_entry(c, SIDE_RELABEL, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, alt_loglik, loglik, status, nullptr,
+                    nullptr, nullptr, nullptr, &rel);
+}
+
+extern "C" int famseq_relabel_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                                 const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                                 const int32_t *d_assign, int32_t n_assign, double *d_alt_loglik, double *d_loglik,
+                                                 uint8_t *d_status, void *stream) {
+  const RelabelIn rel{d_assign, n_assign};
+  return side_entry(c, SIDE_RELABEL, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_alt_loglik, d_loglik,
+                    d_status, stream, nullptr, nullptr, nullptr, &rel);
 }
 
 // The sampling kernels' generator on the host: the text they carry (philox_src.h), compiled here.

@@ -353,6 +353,51 @@ class Emitter {
     return head.str() + pass + per_pass + "      }\n";
   }
 
+  // Relabelling evidence (famseq_relabel): the sum pass of evidence_body, run n_assign + 1 times on one read of the site's rows,
+  // pass j giving member p the likelihood row that row j of the assignment table names (pass 0: the identity).  The substitution
+  // is made where the names l<p>_<g> are resolved, before loc() sees them, so the founders' priors, the site's own prior rows, the
+  // male chrX row and a cut member's lam all follow unchanged.  The table is wave-uniform: the shell packs it into LDS words once
+  // per workgroup (s_aw: `bits` bits per member, row 0 the identity, "no data" and every entry outside 0 .. N-1 stored as N), and a
+  // pass reads its words into scalar registers; e<p> = 3 * entry is scalar arithmetic.  The loop is `#pragma unroll 1`: the
+  // pass's text stands once whatever n_assign is.  The names are macros in both forms and are defined again here:
+  //   rows in LDS (lds_rows)  the lane's row holds N + 1 triples, the last (1, 1, 1): member p's entry g is lrow[e<p> + g], and
+  //                           "no data" is an index like any other;
+  //   lean                    read from the site's row in global memory at each use, at the entry clamped into the row (N reads
+  //                           member 0's), a select putting 1.0 in the place of what was read.
+  // Per pass: Zp_, the pass's total weight (scaled as evidence_body's Z_: evidence_scale_digits()), then `per_pass`.
+  std::string relabel_body(const std::string &per_pass, bool lds_rows, int bits) {
+    const int per = 32 / bits, naw = (g_.N + per - 1) / per;
+    std::ostringstream head;
+    for (int p = 0; p < g_.N; ++p)
+      for (int g = 0; g < 3; ++g) {
+        head << "#undef l" << p << "_" << g << "\n#define l" << p << "_" << g;
+        if (lds_rows) head << " lrow[e" << p << " + " << g << "]\n";
+        else head << " __extension__ ({ const double v_ = lgv[e" << p << " + " << g << "]; o" << p << " ? 1.0 : v_; })\n";
+      }
+    head << "#pragma unroll 1\n      for (int ps_ = 0; ps_ <= last_; ++ps_) {\n";
+    for (int k = 0; k < naw; ++k)
+      head << "      const unsigned aw" << k << " = __builtin_amdgcn_readfirstlane(s_aw[ps_ * " << naw << " + " << k << "]);\n";
+    for (int p = 0; p < g_.N; ++p) {
+      const std::string entry = "(int)((aw" + num(p / per) + " >> " + num(bits * (p % per)) + ") & " + num((1 << bits) - 1) + "u)";
+      if (lds_rows) head << "      const int e" << p << " = 3 * " << entry << ";\n";
+      else
+        head << "      const int n" << p << " = " << entry << ";\n      const bool o" << p << " = n" << p << " >= " << g_.N << ";\n"
+             << "      const int e" << p << " = o" << p << " ? 0 : 3 * n" << p << ";\n";
+    }
+    std::string pass;
+    if (g_.cut.empty()) {
+      fence(1);
+      component_sums();
+      o_ << "      const double Zp_ = " << times_sums("") << ";\n";
+      fence(1);
+      pass = o_.str();
+    } else {
+      pass = cut_loop("      double Zt_ = 0;\n", /*wc=*/false, /*wall=*/true, [&] { o_ << "      Zt_ = Zt_ + Wall;\n"; fence(1); }) +
+             "      const double Zp_ = Zt_;\n";
+    }
+    return head.str() + pass + per_pass + "      }\n";
+  }
+
   // The founders' allele frequency by maximum likelihood (famseq_af): EM on q, every step one sum pass and the founders' marginals
   // under the Hardy-Weinberg rows of the step's q, all steps on one read of the site's rows.  The loop is `#pragma unroll 1`
   // over it_ = -1 .. n_it_ and its text stands once whatever n_it_ is: pass -1 runs at q = 0 (the rows (1, 0, 0) exactly) and keeps
@@ -1173,10 +1218,11 @@ struct LaneShell {
   // upward pass of the first marginal touches every member, and member p's factor is needed again at its own marginal).
   bool lean = false;
   int lds_from = 1 << 30;
+  int lds_extra = 0;  // doubles of the lane's LDS row behind the members' (the kernel's own: famseq_relabel's triple of ones)
 };
 
 std::string lane_shell(const Model &m, const LaneShell &d) {
-  const int N = m.n_members, W3 = 3 * N, first_lds = std::min(N, d.lds_from), n_lds = d.lean ? 0 : N - first_lds, LP = (3 * n_lds) | 1;
+  const int N = m.n_members, W3 = 3 * N, first_lds = std::min(N, d.lds_from), n_lds = d.lean ? 0 : N - first_lds, LP = (3 * n_lds + d.lds_extra) | 1;
   // the lane's prior row is asked for before its likelihoods; FAMSEQ_PRIOR_LATE=1 (tuning aid; not famseq_elim_prior's): after them
   const bool prior_late = !d.shortcut && env_int("FAMSEQ_PRIOR_LATE", 0) != 0;
   std::ostringstream s;
@@ -1457,6 +1503,73 @@ std::string pattern_source(const Model &m, int variant, bool site_prior) {
                "    if (loglik_g) __builtin_nontemporal_store(pt_ll, loglik_g + site);\n"
                "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.bt = elim_block_threads(m, false);
+  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  return lane_shell(m, d);
+}
+
+// The relabelling kernel: the evidence kernel's rules and shell.  Beyond the common arguments: assign_g[n_assign][N] (int32: which
+// member's row member p is given; -1 "no data", and every other entry outside 0 .. N-1 is taken as -1, so nothing outside the
+// site's row is ever read) and n_assign (1 .. FAMSEQ_MAX_RELABEL; the host checks, the kernel clamps).  Outputs per site:
+// alt[n_assign], log10 Z_a without the reference's 1e7 — not clamped; -inf where Z_a is exactly 0, which is a result — and loglik,
+// famseq_evidence's, from the identity pass; either may be null (without alt only the identity pass runs).  Only an identity Z
+// that is not a positive finite number fails the site (status 2).
+// Where the rows live: a pass indexes them by a run-time (wave-uniform) value, which registers do not allow.  Where BT lane rows
+// of 3 (N + 1) doubles (odd stride: no bank conflicts) fit the 64 KB of static LDS beside the tables they sit there, read once
+// per pass into the pass's registers; otherwise, and from forty members on as every lean kernel, the site's row in global memory
+// is read again at each use.  FAMSEQ_RELABEL_LEAN=1 (a tuning aid) takes the second form at every size.
+std::string relabel_source(const Model &m, int variant, bool site_prior) {
+  const Graph g = graph_or_throw(m);
+  if (variant < 0 || variant >= kRelabelVariants)
+    throw std::runtime_error("relabel_source: variant must be 0.." + std::to_string(kRelabelVariants - 1));
+  const int f = variant, N = m.n_members, bits = N < 255 ? 8 : 16, naw = (N + 32 / bits - 1) / (32 / bits);
+  LaneShell d;
+  d.bt = elim_block_threads(m, false);
+  const size_t lds_bytes = size_t(d.bt) * ((3 * (N + 1)) | 1) * sizeof(double) + 432 * sizeof(double) +
+                           size_t(FAMSEQ_MAX_RELABEL + 1) * naw * sizeof(unsigned);
+  const bool lds_rows = N < 40 && lds_bytes <= (size_t(64) << 10) && env_int("FAMSEQ_RELABEL_LEAN", 0) == 0;
+  EmitOptions eo = emit_options(f, "pg", site_prior);
+  eo.lean = N >= 40;  // as trio_source
+  d.lean = !lds_rows;
+  if (lds_rows) d.lds_from = 0, d.lds_extra = 3;
+  d.entry = "famseq_relabel";
+  d.comment = describe("relabelling evidence (sum pass per assignment)", g, std::to_string(f), site_prior);
+  d.outputs = "double *__restrict__ alt_g, double *__restrict__ loglik_g";
+  d.more_args = ", const int *__restrict__ assign_g, int n_assign";
+  d.defines = "#define NMEM " + std::to_string(N) + "\n#define NAW " + std::to_string(naw) + "\n#define MAXREL " +
+              std::to_string(FAMSEQ_MAX_RELABEL) + "\n";
+  d.shared = "  __shared__ unsigned s_aw[(MAXREL + 1) * NAW];  // the passes' assignments: " + std::to_string(bits) +
+             " bits per member, row 0 (the identity pass) 0 .. N-1, NMEM for \"no data\"\n";
+  d.prologue =
+      "  const int na_ = n_assign < 0 ? 0 : (n_assign > MAXREL ? MAXREL : n_assign);\n"
+      "  for (int i = tid; i < (na_ + 1) * NAW; i += BT) {\n"
+      "    const int ps = i / NAW, w = i - ps * NAW;\n"
+      "    unsigned v = 0;\n"
+      "    for (int j = 0; j < " + std::to_string(32 / bits) + " && " + std::to_string(32 / bits) + " * w + j < NMEM; ++j) {\n"
+      "      const int p = " + std::to_string(32 / bits) + " * w + j;\n"
+      "      const int a = ps ? assign_g[(ps - 1) * NMEM + p] : p;\n"
+      "      v |= (a >= 0 && a < NMEM ? (unsigned)a : (unsigned)NMEM) << (" + std::to_string(bits) + " * j);\n"
+      "    }\n"
+      "    s_aw[i] = v;\n"
+      "  }\n";
+  d.site_decls = "    double *ap = alt_g ? alt_g + site * na_ : nullptr;\n"
+                 "    const int last_ = ap ? na_ : 0;\n";
+  d.site_vars = "    double rl_ll = kNaN;\n";
+  if (lds_rows) d.site_vars += "    lw[" + std::to_string(3 * N) + "] = 1.0; lw[" + std::to_string(3 * N + 1) + "] = 1.0; lw[" + std::to_string(3 * N + 2) + "] = 1.0;\n";
+  Emitter e(m, g, eo);
+  const std::string digits = std::to_string(e.evidence_scale_digits()) + ".0";
+  d.body = e.relabel_body(
+      "      if (ps_ == 0) {\n"
+      "        if (!(Zp_ > 0 && Zp_ <= 1.79769313486231570815e308)) { bn_fail = true; break; }\n"
+      "        rl_ll = log10(Zp_) - " + digits + ";\n"
+      "      } else {\n"
+      "        __builtin_nontemporal_store(log10(Zp_) - " + digits + ", ap + (ps_ - 1));\n"
+      "      }\n",
+      lds_rows, bits);
+  d.epilogue = "    if (single_fail || bn_fail) {\n      rl_ll = kNaN;\n"
+               "      if (ap) {\n#pragma unroll 1\n        for (int k = 0; k < na_; ++k) ap[k] = kNaN;\n      }\n"
+               "    }\n"
+               "    if (loglik_g) __builtin_nontemporal_store(rl_ll, loglik_g + site);\n"
+               "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
   return lane_shell(m, d);
 }

@@ -88,6 +88,17 @@ constexpr int kPatternVariants = 4;
 // site_prior: famseq_pattern_prior, with a trailing `prior` [n_sites][6] behind n_patterns (as trio_source's).
 std::string pattern_source(const Model &m, int variant, bool site_prior = false);
 
+// Relabelling evidence (famseq_relabel_batch).  HIP source of
+// `extern "C" __global__ famseq_relabel(lk, flags, alt, loglik, status, n_sites, tc, lc, assign, n_assign)`: per site and
+// assignment j — assign[j][p] names the member whose likelihood row member p (PED order) is given, -1 (or anything else outside
+// 0 .. N-1) the row (1, 1, 1) — alt[j] = log10 Z_a, the network's total weight with the rows so assigned, famseq_evidence's scale
+// (-inf where it is exactly 0); and loglik, famseq_evidence's.  The sum pass of famseq_evidence, n_assign + 1 times on one read of
+// the site's rows.  variant 0..3: the fence levels of famseq_elim's; every variant gives the same bits.  Throws if the engine does
+// not serve the pedigree.
+constexpr int kRelabelVariants = 4;
+// site_prior: famseq_relabel_prior, with a trailing `prior` [n_sites][6] behind n_assign (as trio_source's).
+std::string relabel_source(const Model &m, int variant, bool site_prior = false);
+
 // The founders' allele frequency by maximum likelihood (famseq_af_batch).  HIP source of
 // `extern "C" __global__ famseq_af(lk, flags, af, loglik, status, n_sites, tc, lc, af0, n_iter)`: per site n_iter EM steps on the
 // allele frequency q of the founders' Hardy-Weinberg prior from af0 — a step is one sum pass of famseq_evidence and the founders'

@@ -5,8 +5,8 @@
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
 //              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-loo] [-afTag KEY | -afTagAll KEY]
 //              [-seg dominant|recessive|both -affected ID[,ID...] [-unaffected ID[,ID...]]] [-sample K [-seed S]]
-//              [-afEM T [-afStart X]]
-//   FamSeq LK  -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
+//              [-afEM T [-afStart X]] [-swapCheck FILE]
+//   FamSeq LK -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
 //   readPed / setFam                     file.cpp:24-62, 1888-1968
@@ -26,7 +26,8 @@
 // that the variant segregates with the phenotype of the members named by -affected / -unaffected, under a dominant and / or a
 // recessive model, to the INFO column (PSD, PSR), and -sample K (vcf mode) each sample's alt-allele counts in K joint configurations
 // of the family drawn from their posterior (SGT), and -afEM T (vcf mode) the maximum-likelihood allele frequency among the founders after
-// T EM steps and its log10 likelihood ratio against an allele frequency of 0, to the INFO column (FAF, FAL).
+// T EM steps and its log10 likelihood ratio against an allele frequency of 0, to the INFO column (FAF, FAL), and -swapCheck FILE (vcf
+// mode) writes, behind the last site, the log10 Bayes factor of every two sequenced samples' exchange over the whole file.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -201,6 +202,10 @@ struct Options {
   int af_em = kAfUnset;
   double af_start = 0.5;
   bool af_start_given = false;
+  // -swapCheck FILE: after the last site, the report of every two sequenced samples' exchange (vcf mode): the log10 Bayes factor
+  // of the file's fit to the pedigree with the two relabelled against the labelling as given
+  string swap_file;
+  bool swap_given = false;
   string af_tag;     // -afTag KEY: the founders' prior of a line from the allele frequency KEY= of its INFO column (vcf mode)
   bool af_conflict = false;  // both -afTag and -afTagAll were given
   bool af_all = false;  // -afTagAll KEY: -afTag KEY, applied to every field a line prints (DNP, JGT and JP too: may go with -dnm / -map)
@@ -372,6 +377,16 @@ int parse_options(int argc, char **argv, Options &o) {
           if (end == argv[i] || *end) o.af_start = -1;
           o.af_start_given = true;
         }
+      }
+    } else if (opt == "swapCheck") {
+      i++;
+      if (missing(i)) {
+        std::cout << "The report file of -swapCheck hasn't been set. The option is ignored." << std::endl;
+        i--;
+        rv = 1;
+      } else {
+        o.swap_file = argv[i];
+        o.swap_given = true;
       }
     } else if (opt == "seg" || opt == "affected" || opt == "unaffected") {
       i++;
@@ -1380,13 +1395,14 @@ struct Part {
   }
 };
 
-// ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample, -seg and -afEM add to a line, one row of kSide each ----------------
+// ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample, -seg and -afEM add to a line, one row of kSide each; -swapCheck, which
+// ---- adds nothing to any line and writes a report of its own behind the last site (SideRow::report), is a row too -------------
 // The order is the one main checks them and prints its notices in; it is also the order of the fields in a sample column (DNP,
 // JGT:JP, LOP:LOF, SGT) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL).  Header lines have their
 // own order.
-enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm };
-constexpr int kSides = kAfEm + 1;
-const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm};
+enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap };
+constexpr int kSides = kSwap + 1;
+const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap};
 
 // One side output of a block: the two arrays its C entry fills ([site][...], read as the entry's own types) and its status per site.
 struct SideOut {
@@ -1408,6 +1424,9 @@ struct SideRow {
   void (*header)(std::ostream &, const Options &);
   const char *keys, *na;  // its FORMAT keys and what a failed site prints for them; null: it writes INFO keys
   SideBytes (*bytes)(const VcfRun &);  // per site, of the two arrays
+  // its per-line text is empty (no header line, no FORMAT or INFO key: the output file is the one without it); what its kernel
+  // says of a block is summed up site by site (VcfRun::add_report) and written behind the last site (VcfRun::write_report)
+  bool report = false;
 };
 extern const SideRow kSide[kSides];
 // Row id's fields behind column j of site s, from the ':' on, or its INFO keys for site s: a switch, which the formatter's loop inlines
@@ -1444,6 +1463,16 @@ struct VcfRun {
   bool use_af = false;
   vector<uint8_t> seg_masks;  // -seg: the patterns' mask rows and INFO keys
   vector<const char *> seg_keys;
+  // -swapCheck: the exchange of every two sequenced samples, in VCF column order, as assignment rows [pair][N] (PED order), and
+  // what the sites so far add up to, in file order: per pair the sum of alt_loglik - loglik over the used sites where alt_loglik
+  // is finite and the number of used sites where it is -inf; the used and the skipped (status != 0) sites, the used sites' loglik
+  vector<int32_t> swap_assign;
+  vector<std::pair<int, int>> swap_cols;  // the two columns of a pair, as indices into cm.cols
+  vector<double> swap_bf;
+  vector<uint64_t> swap_impossible;
+  uint64_t swap_used = 0, swap_skipped = 0;
+  double swap_loglik = 0;
+  vector<string> sample_names;  // -swapCheck: the VCF's name of column j of cm.cols
   double model_rows[2][6];  // -afTag: the rows of a line without a usable frequency, by its Known flag: what the model itself would have used
   ColumnMap cm;
   size_t ncol = 0, n_seq = 0, N3 = 0;
@@ -1485,6 +1514,7 @@ struct VcfRun {
     for (const SideRow &row : kSide) {
       if (!row.on(o)) continue;
       sides.push_back(&row);
+      if (row.report) continue;
       (row.keys ? fields : infos).push_back(&row);
       if (row.keys) format_keys += row.keys;
     }
@@ -1502,6 +1532,19 @@ struct VcfRun {
     if (const char *e = std::getenv("FAMSEQ_COMPACT_FROM")) compact_from = std::atoi(e);  // test aid
     for (Slot &sl : slots) sl.parts.resize(n_threads), sl.text.resize(n_threads);
     return true;
+  }
+
+  // -swapCheck: every two sequenced samples, in VCF column order (head: the #CHROM line's columns)
+  void set_up_swaps(const vector<string> &head) {
+    const size_t N = size_t(ped.n()), k = cm.cols.size();
+    for (int c : cm.cols) sample_names.push_back(head[9 + c]);
+    for (size_t a = 0; a < k; ++a)
+      for (size_t b = a + 1; b < k; ++b) {
+        swap_cols.push_back({int(a), int(b)});
+        const size_t at = swap_assign.size();
+        for (size_t p = 0; p < N; ++p) swap_assign.push_back(int32_t(p));
+        swap_assign[at + cm.members[a]] = cm.members[b], swap_assign[at + cm.members[b]] = cm.members[a];
+      }
   }
 
   void format_tags(bool fallback) {
@@ -1838,6 +1881,7 @@ struct VcfRun {
       case kLoo: rc = entry(famseq_loo_batch, famseq_loo_prior_batch, a, b, st); break;
       case kSample: rc = entry(famseq_sample_batch, famseq_sample_prior_batch, o.seed, sl.site_base, (int32_t)o.sample, a8, none, st); break;
       case kSeg: rc = entry(famseq_pattern_batch, famseq_pattern_prior_batch, seg_masks.data(), (int32_t)seg_keys.size(), a, none, st); break;
+      case kSwap: return call_swap(sl, so, lk, pl16);
       case kAfEm: {  // the prior is its unknown: one entry, whatever -afTagAll says of the line
         const vector<double> af0(sl.n_sites, o.af_start);
         rc = famseq_af_batch(ctx, (int64_t)sl.n_sites, lk, pl16, cm.members.data(), (int32_t)n_seq, sl.io.flags, af0.data(), (int32_t)o.af_em, a, b, st);
@@ -1848,6 +1892,60 @@ struct VcfRun {
       std::cerr << row.entry << (use_af && row.id != kAfEm ? "_prior_batch" : "_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
       flush_ok = false;
     }
+  }
+  // -swapCheck: the pairs in groups of at most FAMSEQ_MAX_RELABEL per call, each group's columns summed up over the block's
+  // sites in file order behind its call (a pair's sum is its own: the order of the pairs does not enter).  The first group also
+  // counts the sites and sums their loglik, which is every group's.
+  void call_swap(Slot &sl, SideOut &so, const double *lk, const uint16_t *pl16) {
+    const size_t n_pairs = swap_cols.size(), N = size_t(ped.n());
+    if (swap_bf.empty()) swap_bf.assign(n_pairs, 0.0), swap_impossible.assign(n_pairs, 0);
+    for (size_t first = 0; first == 0 || first < n_pairs; first += FAMSEQ_MAX_RELABEL) {
+      const size_t n = std::min<size_t>(FAMSEQ_MAX_RELABEL, n_pairs - first);
+      // (a file with one sequenced sample has no pair: the identity alone, for the sites' count and their loglik)
+      vector<int32_t> ident(N);
+      for (size_t p = 0; p < N; ++p) ident[p] = int32_t(p);
+      const int32_t *assign = n_pairs ? swap_assign.data() + first * N : ident.data();
+      const int32_t n_assign = n_pairs ? int32_t(n) : 1;
+      double *const alt = n_pairs ? so.a.data() : nullptr;
+      const int rc = use_af ? famseq_relabel_prior_batch(ctx, (int64_t)sl.n_sites, lk, pl16, cm.members.data(), (int32_t)n_seq, sl.io.flags,
+                                                         sl.prior.data(), assign, n_assign, alt, so.b.data(), so.status.data())
+                            : famseq_relabel_batch(ctx, (int64_t)sl.n_sites, lk, pl16, cm.members.data(), (int32_t)n_seq, sl.io.flags, assign,
+                                                   n_assign, alt, so.b.data(), so.status.data());
+      if (rc != 0) {
+        std::cerr << (use_af ? "famseq_relabel_prior_batch" : "famseq_relabel_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
+        flush_ok = false;
+        return;
+      }
+      add_report(sl, so, first, n_pairs ? n : 0);
+    }
+  }
+  // the block's sites (not its other lines), in file order
+  void add_report(const Slot &sl, const SideOut &so, size_t first, size_t n) {
+    for (int t = 0; t < sl.n_parts; ++t)
+      for (const Item &it : sl.parts[t].items) {
+        if (it.site < 0) continue;
+        const size_t s = size_t(it.site);
+        if (so.status[s] != 0) {
+          swap_skipped += first == 0;
+          continue;
+        }
+        if (first == 0) ++swap_used, swap_loglik += so.b[s];
+        for (size_t k = 0; k < n; ++k) {
+          const double alt = so.a[s * n + k];
+          if (std::isfinite(alt)) swap_bf[first + k] += alt - so.b[s];
+          else ++swap_impossible[first + k];
+        }
+      }
+  }
+  bool write_report() const {
+    std::FILE *f = std::fopen(o.swap_file.c_str(), "w");
+    if (!f) return false;
+    std::fprintf(f, "#sites_used=%llu\tsites_skipped=%llu\tlog10_lik=%.6f\n", (unsigned long long)swap_used, (unsigned long long)swap_skipped, swap_loglik);
+    std::fprintf(f, "#sample_a\tsample_b\tlog10_BF\tsites_impossible\n");
+    for (size_t k = 0; k < swap_cols.size(); ++k)
+      std::fprintf(f, "%s\t%s\t%.6f\t%llu\n", sample_names[swap_cols[k].first].c_str(), sample_names[swap_cols[k].second].c_str(),
+                   swap_bf.empty() ? 0.0 : swap_bf[k], (unsigned long long)(swap_impossible.empty() ? 0 : swap_impossible[k]));
+    return std::fclose(f) == 0;
   }
   void gpu_loop() {
     for (;;) {
@@ -2072,6 +2170,7 @@ inline void put_faf(TextBuf &out, const VcfRun &, const SideOut &so, size_t s, s
     case kSample: return put_sgt(out, r, so, s, j);
     case kSeg: return put_seg(out, r, so, s, j);
     case kAfEm: return put_faf(out, r, so, s, j);
+    case kSwap: return;  // (a report row: nothing on a line)
   }
 }
 
@@ -2100,6 +2199,18 @@ bool check_af_em(const Options &o, const Ped &) {
     std::cout << "-afStart takes the allele frequency the steps start from, a number in (0, 1); default 0.5." << std::endl;
     return false;
   }
+  return true;
+}
+
+// -swapCheck's own: the report file must be writable before any input is read (opened for appending: an existing file is kept
+// as it is until the run's own report replaces it)
+bool check_swap(const Options &o, const Ped &) {
+  std::FILE *f = o.swap_file.empty() ? nullptr : std::fopen(o.swap_file.c_str(), "a");
+  if (!f) {
+    std::cout << "Cannot write " << o.swap_file << " (the report file of -swapCheck)." << std::endl;
+    return false;
+  }
+  std::fclose(f);
   return true;
 }
 
@@ -2160,6 +2271,9 @@ const SideRow kSide[kSides] = {
               "no founder carrying the allele\">" << std::endl;
      },
      nullptr, nullptr, [](const VcfRun &) { return SideBytes{8, 16}; }},
+    {kSwap, "-swapCheck", "famseq_relabel", true, [](const Options &o) { return o.swap_given; },
+     [](Options &o) { o.swap_given = false, o.swap_file.clear(); }, check_swap, [](std::ostream &, const Options &) {}, nullptr, nullptr,
+     [](const VcfRun &r) { return SideBytes{8 * std::min<size_t>(FAMSEQ_MAX_RELABEL, r.swap_cols.size()), 8}; }, /*report=*/true},
 };
 
 // `FamSeq vcf` and `FamSeq pack`: the wiring of a VcfRun's stages
@@ -2176,6 +2290,7 @@ bool run_vcf(const Options &o, const Ped &ped) {
   const vector<string> head = split_keep(r.echo_header(line, more), '\t');
   if (!r.map_header(head)) return false;
   if (!o.loc_file.empty() && !r.read_locations()) return false;
+  if (o.swap_given && !o.pack_mode) r.set_up_swaps(head);
   if (o.pack_mode) {
     vector<string> names;
     for (int c : r.cm.cols) names.push_back(head[9 + c]);
@@ -2239,6 +2354,10 @@ bool run_vcf(const Options &o, const Ped &ped) {
   for (Slot &sl : r.slots) sl.io.release();
   r.fout.close();
   famseq_destroy(r.ctx);
+  if (ok && o.swap_given && !r.write_report()) {
+    std::cout << "Cannot write " << o.swap_file << " (the report file of -swapCheck)." << std::endl;
+    return false;
+  }
   return ok && !r.fout.fail();
 }
 
@@ -2368,6 +2487,12 @@ void help() {
             << "\t\tfrom -afStart X (in (0, 1), default 0.5), and FAL, the log10 likelihood ratio of the site's data at that frequency against" << std::endl
             << "\t\t\"no founder carries the allele\" (inf where the data exclude that), to the INFO column. No prior enters either; no other" << std::endl
             << "\t\tfield changes. Implies -method 2; may be combined with -dnm, -map, -siteQ, -loo, -sample, -seg and -afTagAll; not with -afTag." << std::endl
+            << "-swapCheck FILE\t(vcf) After the last site write FILE: for every two sequenced samples, in VCF column order, log10_BF, the sum over" << std::endl
+            << "\t\tthe file's sites of the log10 likelihood of the site under the pedigree with the two samples exchanged minus that with the" << std::endl
+            << "\t\tlabels as given (positive favours the exchange), and sites_impossible, the sites the exchange makes impossible, which the" << std::endl
+            << "\t\tsum leaves out; line 1 counts the sites used and skipped (failed) and gives the file's log10 likelihood. Adds nothing to" << std::endl
+            << "\t\tany output line. Implies -method 2; may be combined with every other option above, under -afTagAll with the line's prior;" << std::endl
+            << "\t\tnot with -afTag." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl

@@ -37,6 +37,9 @@ SideTable &side_table() {
       {"af", "founder allele frequency", "1", K_AF, -1, 1, kAfVariants,
        [](const Model &m, int v, int, bool) { return af_source(m, v); },
        [](const Model &, int, size_t row[2]) { row[0] = sizeof(double), row[1] = 2 * sizeof(double); }},  // af, loglik[2]
+      {"relabel", "relabelling evidence", "1", K_RELABEL, K_RELABEL_PRIOR, 1, kRelabelVariants,
+       [](const Model &m, int v, int, bool site_prior) { return relabel_source(m, v, site_prior); },
+       [](const Model &, int n_assign, size_t row[2]) { row[0] = size_t(n_assign) * sizeof(double), row[1] = sizeof(double); }},  // alt_loglik[M], loglik
   };
   return table;
 }

@@ -622,6 +622,57 @@ int famseq_af_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk,
                            int32_t n_seq, const uint8_t *d_flags, const double *d_af0, int32_t n_iter, double *d_af,
                            double *d_loglik, uint8_t *d_status, void *stream);
 
+/* ---- relabelling evidence: which sample-to-member labelling fits the pedigree ---------------------------------------------
+ * Every query above takes the labelling of the samples for granted.  An assignment a[N] says, for every member p in PED order,
+ * which member's likelihood row it is given: a[p] in 0 .. N-1, or -1 for "no data", the row (1, 1, 1).  It need not be a
+ * permutation (a row may be used twice); the identity is a[p] = p.  Z_a is the network's total weight, as famseq_evidence_batch
+ * forms it, with member p's row replaced by row a[p] of the site as given.  The substitution happens before anything else sees
+ * the row: the founders' priors, the site's own prior rows, the male chrX row and a conditioned member's factor follow
+ * unchanged, and a female's row handed to a male at a chrX site loses its heterozygote entry as a male's own row would.
+ * Summed over sites, alt_loglik[.][j] - loglik is the log10 Bayes factor of relabelling j against the labelling as given.
+ *   assign [n_assign][N]    int32, the same for every site of the call.
+ *   n_assign                1 .. FAMSEQ_MAX_RELABEL (the transpositions of eleven samples are 55).
+ *   alt_loglik [n_sites][n_assign]   log10 Z_a on famseq_evidence_batch's scale: bit for bit that entry's loglik on the rows
+ *              rearranged on the host wherever that call has status 0, and loglik's bits for an identity row.  Not clamped:
+ *              -inf where Z_a is exactly 0 (at mutation rate 0 a Mendel-impossible relabelling; a male at a chrX site handed
+ *              (0, x, 0)), which is a result, not a failure; for rows in [0, 1] finite or -inf.  A column's value depends
+ *              neither on n_assign nor on the other rows of assign.
+ *   loglik [n_sites]        the identity's value: famseq_evidence_batch's bits.
+ *   status [n_sites]        0 OK; 1 the single-posterior failure rule of famseq_bn_batch, applied to the rows as given; 2 the
+ *              as-given total weight Z is <= 0 or not finite.  Wherever status != 0, alt_loglik and loglik of the site are NaN.
+ *              There is no -LRC shortcut.
+ * One kernel launch reads a site's rows once and runs the sum pass n_assign + 1 times on them.  Served by the sum-product
+ * engine's graph as famseq_evidence_batch is, whatever the context's engine; compiled on the first call or ahead through
+ * famseq_set_option "relabel_kernels" = 1.  famseq_plan_json: "relabel_code_object", "relabel_variant".
+ * FAMSEQ_E_ARG, with a message and before the device is asked for: n_assign outside 1 .. FAMSEQ_MAX_RELABEL, assign NULL, (host
+ * entries) the first entry outside -1 .. N-1, named by assignment and member. */
+#define FAMSEQ_MAX_RELABEL 64
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_evidence_batch.  assign is a host array, staged by the library.
+ * Any of alt_loglik / loglik / status may be NULL; without alt_loglik only the identity pass runs. */
+int famseq_relabel_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                         int32_t n_seq, const uint8_t *flags, const int32_t *assign /*[n_assign][N]*/, int32_t n_assign,
+                         double *alt_loglik, double *loglik, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array), d_assign among them — it must stay valid
+ * and unchanged until the kernel has run, and nothing is checked of its contents: the kernel takes every entry outside
+ * 0 .. N-1 as -1 ("no data"), so it never reads outside the site's row.  Enqueues on `stream` (a hipStream_t; NULL = the
+ * default stream) and returns without synchronising (the stream rule at famseq_bn_batch_device). */
+int famseq_relabel_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const int32_t *d_assign,
+                                int32_t n_assign, double *d_alt_loglik, double *d_loglik, uint8_t *d_status, void *stream);
+
+/* With the founders' genotype prior given per site: prior[n_sites][6], as for famseq_evidence_prior_batch.  Given rows that equal
+ * the model's constants the outputs are, bit for bit, famseq_relabel_batch's.  "relabel_prior_kernels" = 1 builds the kernel
+ * (famseq_relabel_prior) ahead; famseq_plan_json: "relabel_prior_code_object", "relabel_prior_variant". */
+int famseq_relabel_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                               int32_t n_seq, const uint8_t *flags, const double *prior, const int32_t *assign, int32_t n_assign,
+                               double *alt_loglik, double *loglik, uint8_t *status);
+int famseq_relabel_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                      const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                      const int32_t *d_assign, int32_t n_assign, double *d_alt_loglik, double *d_loglik,
+                                      uint8_t *d_status, void *stream);
+
 /* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] = ((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);
