@@ -10,6 +10,14 @@ RANDOM_SEEDS = range(10)        # tests/test_gpu_random_pedigrees.py, tests/test
 WIDE_SIZES = (24, 32, 48)       # tests/golden/wide_peds.npz (oracle/gen_golden_wide.py)
 WIDE_RANDOM_SEEDS = range(6)    # tests/test_gpu_wide.py
 WIDE_EXTRA_SIZES = (128,)       # beyond what LDS rows could stage: tests/test_wide.py, tests/test_gpu_wide.py (against the numpy oracle)
+# tests/test_gpu_side_variants.py, tests/test_side_variants_host.py: the smallest pedigrees that reach each body of the
+# sum-product generator — loop-free, one conditioned member with everybody sequenced, three conditioned members with three
+# members unsequenced — on which every fence level of every side-product kernel is forced in turn
+SIDE_VARIANT_PEDIGREES = ("trio", "cousins", "random15")
+SIDE_VARIANTS = 4               # kTrioVariants .. kRelabelVariants (csrc/elim_codegen.h)
+# (stem, output forms, has a site-prior sibling): side_table() of csrc/kernels.cpp
+SIDE_PRODUCTS = (("trio", 3, True), ("map", 1, True), ("evidence", 1, True), ("loo", 1, True), ("pattern", 1, True),
+                 ("sample", 1, True), ("af", 1, False), ("relabel", 1, True))
 
 
 def soak_pedigree(seed, max_n=10):
@@ -38,3 +46,19 @@ def wide_random_pedigree(seed):
     rng = np.random.RandomState(4200 + seed)
     ped = grow_pedigree(rng, int(rng.randint(21, 61)), allow_loops=False)
     return rng, ped, [1e-7, 1e-4, 0.0][seed % 3]
+
+
+def side_variant_pedigree(name):
+    """A pedigree of SIDE_VARIANT_PEDIGREES (or any synthetic_pedigree name, or random<seed>): `cousins` is a first-cousin
+    marriage, nine members, one loop; random15 is random_pedigree(15), nine members of which three carry no reads."""
+    from .pedigree import Pedigree, synthetic_pedigree
+
+    if name == "cousins":
+        ids, mids, fids = [1, 2, 3, 4, 5, 6, 7, 8, 9], [0, 0, 2, 2, 0, 0, 5, 4, 8], [0, 0, 1, 1, 0, 0, 3, 6, 7]
+        ped = Pedigree(ids, mids, fids, [1, 2, 1, 2, 2, 1, 1, 2, 1], ["s%d" % i for i in ids])
+    elif name.startswith("random"):
+        ped = random_pedigree(int(name[6:]))[1]
+    else:
+        ped = synthetic_pedigree(name)
+    ped.relations()
+    return ped

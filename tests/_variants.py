@@ -5,7 +5,7 @@ and the compiler's register allocation.  These fixtures let a test force each in
 import numpy as np
 
 import famseq_amd as fs
-from famseq_amd.prebuild_sets import random_pedigree
+from famseq_amd.prebuild_sets import side_variant_pedigree
 
 # trio .. ped15:12 (both the 7- and the 6-member block of the lane kernel exist from there on), a first-cousin loop
 # (one conditioned member) and random_pedigree(15) (nine members, three unsequenced, three conditioned)
@@ -19,15 +19,8 @@ TINY_SITES = range(30, 34)   # row sums below 1e-290: the guarded plain-division
 
 
 def pedigree(name):
-    if name == "cousins":
-        ids, mids, fids = [1, 2, 3, 4, 5, 6, 7, 8, 9], [0, 0, 2, 2, 0, 0, 5, 4, 8], [0, 0, 1, 1, 0, 0, 3, 6, 7]
-        ped = fs.Pedigree(ids, mids, fids, [1, 2, 1, 2, 2, 1, 1, 2, 1], ["s%d" % i for i in ids])
-    elif name.startswith("random"):
-        ped = random_pedigree(int(name[6:]))[1]
-    else:
-        ped = fs.synthetic_pedigree(name)
-    ped.relations()
-    return ped
+    """(one definition with build(), which pre-builds the side products' variants for three of these)"""
+    return side_variant_pedigree(name)
 
 
 def variant_flags(n_sites):

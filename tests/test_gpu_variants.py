@@ -5,12 +5,15 @@ Which variant a pedigree gets is decided by the static picker, the tuner and the
 forced — the plain kernels through their pick notes (pick_lane / pick_elim), the call-path forms through
 $FAMSEQ_VARIANT_ONLY — the plan is checked to name it, and its outputs go against the reference and against the other
 variants of the same family, which must agree bit for bit (see tests/test_generated_host.py, the host twin, for why).
+The site-prior kernel famseq_elim_prior has no contest of its own — it runs in the variant famseq_elim takes — and is moved
+with it through pick_elim, all twelve.  (The side products' fence levels: tests/test_gpu_side_variants.py.)
 
 Pick notes are written into a private kernel cache of this session: the in-tree cache and the per-user one, from which the
 rest of the suite and bench.py load, never see them."""
 import numpy as np
 import pytest
 
+import _prior as P
 import _variants as V
 import famseq_amd as fs
 
@@ -76,6 +79,14 @@ def load(ped, family, v, base=0, monkeypatch=None):
             plan = ctx.plan()
             assert plan["elim_variant"] == v
             obj = plan["elim_code_object"]
+        elif family == "prior":  # famseq_elim_prior has no contest of its own: it runs in the variant famseq_elim takes
+            ctx.set_option("pick_elim", v)
+            ctx.set_option("engine", fs.ENGINE_ELIM)
+            ctx.set_option("prior_kernels", 1)
+            plan = ctx.plan()
+            assert plan["elim_variant"] == v and plan["prior_variant"] == v
+            obj = plan["prior_code_object"]
+            assert obj.endswith(".hsaco") and obj != plan["elim_code_object"]
         elif family == "lane_call":
             ctx.set_option("pick_lane", base)
             ctx.set_option("enum_impl", 1)
@@ -213,6 +224,51 @@ def test_every_call_variant(name, family, monkeypatch):
         np.testing.assert_allclose(fpp[ok], phred(post[ok][:, seq_]), rtol=1e-12, atol=0)
         assert np.array_equal(fgt[ok], fs.call_genotypes(post[ok][:, seq_]).reshape(-1, len(seq_)))
         assert np.all(np.isnan(fpp[~ok])) and np.all(fgt[~ok] == -1) and np.all(np.isnan(gpp[~s_ok]))
+
+
+PRIOR_PEDIGREES = ("quad", "cousins", "random15")  # loop-free, one conditioned member, three (and three members without reads)
+_PRIOR_REF, _PRIOR_RUNS = {}, {}
+
+
+def prior_batch(name):
+    """The variant batch of the pedigree with Hardy-Weinberg rows of frequencies uniform in (0.01, 0.5), and the per-site oracle
+    of tests/_prior.py on them, asserted well-conditioned (on the oracle alone); computed once."""
+    if name not in _PRIOR_REF:
+        ped, lk, flags, _, _ = batch(name)
+        hwe = fs.hwe_priors(np.random.RandomState(len(name)).uniform(0.01, 0.5, len(lk)))
+        ref = P.reference(ped, lk, flags, hwe, mrate=V.MRATE)
+        P.assert_well_conditioned(ped, lk, flags, hwe, ref, mrate=V.MRATE)
+        assert set(np.unique(ref[2])) >= {0, 1, 2, 0x80}
+        _PRIOR_REF[name] = (hwe, ref)
+    return _PRIOR_REF[name]
+
+
+@pytest.mark.parametrize("v", range(12))
+@pytest.mark.parametrize("name", PRIOR_PEDIGREES)
+def test_the_site_prior_kernel_in_every_variant(name, v, monkeypatch):
+    """famseq_elim_prior (K_PRIOR) in each of famseq_elim's twelve variants, the registers-first (4-7) and the no-LDS family
+    (8-11) included: on the model's own rows famseq_elim's bits in the same variant, on Hardy-Weinberg rows the per-site
+    oracle at tests/_prior.py's tolerances, ragged sub-batches the bits of the slices, and every variant variant 0's bits."""
+    ped, lk, flags, has_bn_fail, ref = batch(name)
+    hwe, href = prior_batch(name)
+    ctx, _, bt = load(ped, "prior", v)
+    try:
+        assert wraps(len(flags), bt), (name, v, bt)
+        model = fs.make_model(ped, mrate=V.MRATE)
+        plain = ctx.bn_batch(lk, flags)
+        V.check_against_reference(*plain, ref, has_bn_fail, what="%s: elim variant %d" % (name, v))
+        assert V.same_bits(ctx.bn_prior_batch(lk, P.model_rows(model, flags), flags), plain), (name, v, "the model's rows")
+        out = ctx.bn_prior_batch(lk, hwe, flags)
+        P.check(out, href, "%s: site-prior kernel, variant %d, Hardy-Weinberg rows" % (name, v))
+        for s in sizes(bt):
+            assert V.same_bits(ctx.bn_prior_batch(lk[:s], hwe[:s], flags[:s]), tuple(x[:s] for x in out)), (name, v, s)
+        plan = ctx.plan()
+        assert plan["elim_variant"] == v and plan["prior_variant"] == v
+    finally:
+        ctx.close()
+    first = _PRIOR_RUNS.setdefault(name, (v, out, plain))
+    assert V.same_bits(out, first[1]), "%s: site-prior kernel, variant %d differs from variant %d" % (name, v, first[0])
+    assert V.same_bits(plain, first[2]), "%s: famseq_elim, variant %d differs from variant %d" % (name, v, first[0])
 
 
 @pytest.mark.parametrize("name", ["ped10", "ped15:12"])
