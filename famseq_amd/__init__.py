@@ -90,6 +90,8 @@ ABI_SYMBOLS = [
     "famseq_sample_batch", "famseq_sample_batch_device", "famseq_sample_prior_batch", "famseq_sample_prior_batch_device",
     "famseq_af_batch", "famseq_af_batch_device",
     "famseq_relabel_batch", "famseq_relabel_batch_device", "famseq_relabel_prior_batch", "famseq_relabel_prior_batch_device",
+    "famseq_rate_tables",
+    "famseq_mutrate_batch", "famseq_mutrate_batch_device", "famseq_mutrate_prior_batch", "famseq_mutrate_prior_batch_device",
 ]
 # (and famseq_philox4x32_10, the one name with digits in it: philox4x32 below)
 PL_MISSING = 0xFFFF
@@ -179,9 +181,10 @@ def lib():
     masks = ([bp, C.c_int32], [vp, C.c_int32])
     draws = ([C.c_uint64, C.c_int64, C.c_int32],) * 2  # seed, site_base, n_draws
     assigns = ([ip, C.c_int32], [vp, C.c_int32])
+    rates = ([dp, C.c_int32], [vp, C.c_int32])  # the host entries take the rates, the device entries the resident tables
     for name, out_a, more in (("trio", dp, ([], [])), ("map", C.POINTER(C.c_int8), ([], [])), ("evidence", dp, ([], [])), ("loo", dp, ([], [])),
                               ("pattern", dp, masks), ("sample", C.POINTER(C.c_int8), draws),
-                              ("relabel", dp, assigns)):
+                              ("relabel", dp, assigns), ("mutrate", dp, rates)):
         for prior in (0, 1):
             host = getattr(L, "famseq_%s%s_batch" % (name, "_prior" * prior))
             dev = getattr(L, "famseq_%s%s_batch_device" % (name, "_prior" * prior))
@@ -192,6 +195,8 @@ def lib():
     L.famseq_af_batch.argtypes = [C.c_void_p, C.c_int64, dp, u16p, ip, C.c_int32, bp, dp, C.c_int32, dp, dp, bp]
     L.famseq_af_batch_device.argtypes = [C.c_void_p, C.c_int64, vp, vp, ip, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp]
     L.famseq_af_batch.restype = L.famseq_af_batch_device.restype = C.c_int
+    L.famseq_rate_tables.argtypes = [C.c_void_p, dp, C.c_int32, dp]
+    L.famseq_rate_tables.restype = C.c_int
     u32p = C.POINTER(C.c_uint32)
     L.famseq_philox4x32_10.argtypes = [u32p, u32p, u32p]
     L.famseq_philox4x32_10.restype = None
@@ -298,6 +303,8 @@ def segregation_masks(n, affected, unaffected=(), model="dominant"):
 
 
 MAX_RELABEL = 64
+MAX_RATES = 32
+RATE_TABLE_DOUBLES = 432
 
 
 def swap_assignments(n, members=None):
@@ -715,6 +722,56 @@ class Context:
         """relabel_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
         self._side_device("relabel", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_alt, d_loglik, d_status, stream,
                           (d_assign or None, int(n_assign)))
+
+    @staticmethod
+    def _rates(rates):
+        """rates (a scalar or [R]) as a contiguous float64 array."""
+        r = np.ascontiguousarray(rates, dtype=np.float64)
+        if r.ndim == 0:
+            r = r[None]
+        if r.ndim != 1:
+            raise ValueError("rates must be a list of mutation rates")
+        return r
+
+    def rate_tables(self, rates):
+        """The factor tables of `rates` for mutrate_device: -> [R, 432] float64, block r this context's own table with the
+        transmission tables of rates[r] (bit for bit the table of a context made with mrate = rates[r]).  Needs no device."""
+        r = self._rates(rates)
+        tables = np.empty((len(r), RATE_TABLE_DOUBLES))
+        self._check(lib().famseq_rate_tables(self._h, _p(r, C.c_double), len(r), _p(tables, C.c_double)), "famseq_rate_tables")
+        return tables
+
+    def mutrate_batch(self, rates, lk=None, pl16=None, seq_members=None, flags=None, want_rates=True, want_loglik=True):
+        """The mutation-rate likelihood profile: -> (rate_loglik[S,R] float64, loglik[S] float64, status[S] uint8).
+        rates [R] (1 .. MAX_RATES numbers in [0, 1]).  rate_loglik[s, r] = log10 of the site's likelihood under the pedigree with
+        the mutation rate rates[r] (evidence_batch's bits on a context made with that mrate; -inf where it is exactly 0, as at
+        rate 0 on a Mendel-impossible site); loglik is evidence_batch's under this context's own rate.  Summed over sites a column
+        is the log10 likelihood of its rate; rate_loglik[:, r] - rate_loglik[:, r0] with rates[r0] = 0 is the log10 Bayes factor
+        "the site needs a mutation".  Input is either lk [S,N,3] float64 or pl16 [S,n_seq,3] uint16 in VCF column order
+        (seq_members: their PED indices).  want_* False: not computed, None."""
+        r = self._rates(rates)
+        outs = lambda s: (np.empty((s, len(r))) if want_rates else None, np.empty(s) if want_loglik else None)
+        return self._side_host("mutrate", None, lk, pl16, seq_members, flags, outs, (_p(r, C.c_double), len(r)))
+
+    def mutrate_prior_batch(self, prior, rates, lk=None, pl16=None, seq_members=None, flags=None, want_rates=True, want_loglik=True):
+        """mutrate_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give mutrate_batch's bits."""
+        r = self._rates(rates)
+        outs = lambda s: (np.empty((s, len(r))) if want_rates else None, np.empty(s) if want_loglik else None)
+        return self._side_host("mutrate", prior, lk, pl16, seq_members, flags, outs, (_p(r, C.c_double), len(r)))
+
+    def mutrate_device(self, n_sites, d_tables, n_rates, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_rate_loglik=0, d_loglik=0,
+                       d_status=0, stream=0):
+        """mutrate_batch on resident buffers (raw device pointers as ints; 0 = not given), d_tables [n_rates, 432] float64 among
+        them (rate_tables() makes them; they must stay unchanged until the kernel has run); enqueues on `stream` and returns."""
+        self._side_device("mutrate", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_rate_loglik, d_loglik, d_status, stream,
+                          (d_tables or None, int(n_rates)))
+
+    def mutrate_prior_device(self, n_sites, d_prior, d_tables, n_rates, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_rate_loglik=0,
+                             d_loglik=0, d_status=0, stream=0):
+        """mutrate_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("mutrate", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_rate_loglik, d_loglik, d_status, stream,
+                          (d_tables or None, int(n_rates)))
 
     def af_batch(self, af0, n_iter, lk=None, pl16=None, seq_members=None, flags=None, want_af=True, want_loglik=True):
         """The founders' allele frequency by maximum likelihood: -> (af[S] float64, loglik[S,2] float64, status[S] uint8).

@@ -370,10 +370,13 @@ std::string trio_json(const famseq_ctx *c) {
   for (int i = 0; i < n_first; ++i) o += side_json(c, side_table()[i], false);
   o += ",\"prior_code_object\":\"" + json_str(c->kern[K_PRIOR].k.path) + "\",\"prior_variant\":" + std::to_string(c->kern[K_PRIOR].variant);
   for (int i = 0; i < n_first; ++i) o += side_json(c, side_table()[i], true);
-  for (int i = n_first; i < SIDE_COUNT; ++i)
+  for (int i = n_first; i < SIDE_MUTRATE; ++i)
     o += side_json(c, side_table()[i], false) + (side_table()[i].has_prior() ? side_json(c, side_table()[i], true) : std::string());
   const std::string bt = std::to_string(elim_block_threads(c->model));  // (every side product's kernel runs in these workgroups)
-  return o + ",\"evidence_block_threads\":" + bt + ",\"loo_block_threads\":" + bt;
+  o += ",\"evidence_block_threads\":" + bt + ",\"loo_block_threads\":" + bt;
+  for (int i = SIDE_MUTRATE; i < SIDE_COUNT; ++i)  // (the products added since: behind every older key)
+    o += side_json(c, side_table()[i], false) + (side_table()[i].has_prior() ? side_json(c, side_table()[i], true) : std::string());
+  return o;
 }
 }  // namespace
 
@@ -903,10 +906,37 @@ int check_relabel(famseq_ctx *c, const RelabelIn &rel, bool device) {
                                          std::to_string(rel.assign[i]) + "; an entry is -1 (no data) or a member index 0.." + std::to_string(N - 1));
   return 0;
 }
+// What the mutation-rate entries take beside: the rates (host entries: the caller's host array, from which the library builds and
+// stages the tables) or the tables [n_rates][FAMSEQ_RATE_TABLE_DOUBLES] (device entries: resident), and their number.
+struct RateIn {
+  const double *rates;     // host entries
+  const double *d_tables;  // device entries
+  int32_t n_rates;
+};
+int check_rates(famseq_ctx *c, const double *rates, int32_t n_rates, const char *name, bool values) {
+  if (n_rates < 1 || n_rates > FAMSEQ_MAX_RATES)
+    return fail(c, FAMSEQ_E_ARG, "n_rates must be 1.." + std::to_string(FAMSEQ_MAX_RATES) + ", got " + std::to_string(n_rates));
+  if (!rates) return fail(c, FAMSEQ_E_ARG, std::string(name) + " must be given (" + (values ? "n_rates mutation rates)" : "n_rates factor tables of " +
+                                               std::to_string(FAMSEQ_RATE_TABLE_DOUBLES) + " doubles)"));
+  if (values)
+    for (int32_t r = 0; r < n_rates; ++r)
+      if (!(rates[r] >= 0.0 && rates[r] <= 1.0))
+        return fail(c, FAMSEQ_E_ARG, "rates[" + std::to_string(r) + "] must be a finite number in [0, 1]");
+  return 0;
+}
+// famseq_rate_tables' blocks: the model's factor table rebuilt with the transmission tables of each rate
+void rate_tables(const Model &m, const double *rates, int32_t n_rates, double *tables) {
+  Model at = m;
+  for (int32_t r = 0; r < n_rates; ++r) {
+    famseq_transmission_tables(rates[r], at.pcp2, at.pcp2Xf, at.pcp2Xm);
+    build_factor_tables(at, tables + size_t(r) * FAMSEQ_RATE_TABLE_DOUBLES);
+  }
+}
 int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device, const SideIn &in, const double *prior, void *out_a,
                void *out_b, uint8_t *status, void *stream_ = nullptr, const PatternIn *pat = nullptr, const SampleIn *smp = nullptr,
-               const AfIn *af = nullptr, const RelabelIn *rel = nullptr) {
+               const AfIn *af = nullptr, const RelabelIn *rel = nullptr, const RateIn *mr = nullptr) {
   if (!c) return FAMSEQ_E_ARG;
+  if (mr && check_rates(c, device ? mr->d_tables : mr->rates, mr->n_rates, device ? "d_tables" : "rates", !device) != 0) return FAMSEQ_E_ARG;
   if (rel && check_relabel(c, *rel, device) != 0) return FAMSEQ_E_ARG;
   if (pat && check_patterns(c, *pat, device) != 0) return FAMSEQ_E_ARG;
   if (smp && check_sample(c, *smp) != 0) return FAMSEQ_E_ARG;
@@ -938,14 +968,26 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
   // ... or the relabelling kernels' assignments and their number
   const int32_t *d_assign = rel ? rel->assign : nullptr;
   const int32_t n_assign = rel ? rel->n_assign : 1;
-  const MoreArgs lead = rel   ? MoreArgs{&d_assign, &n_assign}
+  // ... or the mutation-rate kernels' tables and their number
+  const double *d_tables = mr ? mr->d_tables : nullptr;
+  const int32_t n_rates = mr ? mr->n_rates : 1;
+  const MoreArgs lead = mr    ? MoreArgs{&d_tables, &n_rates}
+                        : rel ? MoreArgs{&d_assign, &n_assign}
                         : pat ? MoreArgs{&d_masks, &n_patterns}
                         : smp ? MoreArgs{&seed, &site_base, &n_draws}
                         : af  ? MoreArgs{&d_af0, &n_iter}
                               : MoreArgs{};
   if (!device) {
     size_t row[2];
-    p.rows(c->model, smp ? n_draws : (rel ? n_assign : n_patterns), row);
+    p.rows(c->model, smp ? n_draws : (rel ? n_assign : (mr ? n_rates : n_patterns)), row);
+    if (mr) {  // (the tables of the call's rates, staged as the masks below are)
+      const size_t n = size_t(n_rates) * FAMSEQ_RATE_TABLE_DOUBLES;
+      if (!c->d_rate_tables) HIP_TRY(c, c->d_rate_tables.alloc(size_t(FAMSEQ_MAX_RATES) * FAMSEQ_RATE_TABLE_DOUBLES * sizeof(double)));
+      c->rate_tables_host.resize(n);
+      rate_tables(c->model, mr->rates, n_rates, c->rate_tables_host.data());
+      HIP_TRY(c, hipMemcpyAsync(c->d_rate_tables.p, c->rate_tables_host.data(), n * sizeof(double), hipMemcpyHostToDevice, c->stream[1]));
+      d_tables = c->d_rate_tables.as<double>();
+    }
     if (rel) {  // (staged as the masks below are)
       const size_t n = size_t(n_assign) * c->model.n_members;
       if (!c->d_assign) HIP_TRY(c, c->d_assign.alloc(size_t(FAMSEQ_MAX_RELABEL) * c->model.n_members * sizeof(int32_t)));
@@ -1207,6 +1249,49 @@ extern "C" int famseq_relabel_prior_batch_device(famseq_ctx *c, int64_t n_sites,
   const RelabelIn rel{d_assign, n_assign};
   return side_entry(c, SIDE_RELABEL, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_alt_loglik, d_loglik,
                     d_status, stream, nullptr, nullptr, nullptr, &rel);
+}
+
+// ---- the mutation-rate likelihood profile: the evidence entries with one factor table per rate ----------------------------------
+
+extern "C" int famseq_rate_tables(famseq_ctx *c, const double *rates, int32_t n_rates, double *tables) {
+  if (!c) return FAMSEQ_E_ARG;
+  if (check_rates(c, rates, n_rates, "rates", true) != 0) return FAMSEQ_E_ARG;
+  if (!tables) return fail(c, FAMSEQ_E_ARG, "tables must be given (n_rates blocks of " + std::to_string(FAMSEQ_RATE_TABLE_DOUBLES) + " doubles)");
+  rate_tables(c->model, rates, n_rates, tables);
+  return 0;
+}
+
+extern "C" int famseq_mutrate_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                    int32_t n_seq, const uint8_t *flags, const double *rates, int32_t n_rates, double *rate_loglik,
+                                    double *loglik, uint8_t *status) {
+  const RateIn mr{rates, nullptr, n_rates};
+  return side_entry(c, SIDE_MUTRATE, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, rate_loglik, loglik, status, nullptr,
+                    nullptr, nullptr, nullptr, nullptr, &mr);
+}
+
+extern "C" int famseq_mutrate_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_tables,
+                                           int32_t n_rates, double *d_rate_loglik, double *d_loglik, uint8_t *d_status, void *stream) {
+  const RateIn mr{nullptr, d_tables, n_rates};
+  return side_entry(c, SIDE_MUTRATE, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_rate_loglik, d_loglik,
+                    d_status, stream, nullptr, nullptr, nullptr, nullptr, &mr);
+}
+
+extern "C" int famseq_mutrate_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
+                                          const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
+                                          const double *rates, int32_t n_rates, double *rate_loglik, double *loglik, uint8_t *status) {
+  const RateIn mr{rates, nullptr, n_rates};
+  return side_entry(c, SIDE_MUTRATE, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, rate_loglik, loglik, status, nullptr,
+                    nullptr, nullptr, nullptr, nullptr, &mr);
+}
+
+extern "C" int famseq_mutrate_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                                 const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                                 const double *d_tables, int32_t n_rates, double *d_rate_loglik, double *d_loglik,
+                                                 uint8_t *d_status, void *stream) {
+  const RateIn mr{nullptr, d_tables, n_rates};
+  return side_entry(c, SIDE_MUTRATE, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_rate_loglik, d_loglik,
+                    d_status, stream, nullptr, nullptr, nullptr, nullptr, &mr);
 }
 
 // The sampling kernels' generator on the host: the text they carry (philox_src.h), compiled here.

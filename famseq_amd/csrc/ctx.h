@@ -55,7 +55,8 @@ struct DevBuf {
 };
 
 // A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp; the trio,
-// MAP, evidence, leave-one-out, pattern, sampling, allele-frequency and relabelling kinds are the rows of side_table() below.
+// MAP, evidence, leave-one-out, pattern, sampling, allele-frequency, relabelling and mutation-rate kinds are the rows of
+// side_table() below.
 enum KernelKind {
   K_LANE = 0,  // K_LANE + d: the enumeration with 3^d lanes per site; d = 0 (one lane per site) serves large batches,
                // d = 1..kEnumMaxGroupDigits batches too small to give every lane of the chip a site (compiled on first use of each d)
@@ -78,6 +79,8 @@ enum KernelKind {
   K_AF,                                            // the founders' allele frequency by maximum likelihood (no site-prior form)
   K_RELABEL,                                       // relabelling evidence: the sum pass once per assignment of rows to members
   K_RELABEL_PRIOR,                                 // ... with the founders' prior per site
+  K_MUTRATE,                                       // mutation-rate likelihood profile: the sum pass once per transmission table
+  K_MUTRATE_PRIOR,                                 // ... with the founders' prior per site
   K_COUNT
 };
 
@@ -119,7 +122,7 @@ struct SlotSet {
 // A side product of the sum-product engine: a generated kernel that takes the common argument list and writes two outputs per
 // site and a status byte, in a plain form and in one that reads the founders' prior per site.  Everything its ABI entries, its
 // prebuild options, its plan keys and its loader differ in is one row of side_table() (kernels.cpp).
-enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_SAMPLE, SIDE_AF, SIDE_RELABEL, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
+enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_SAMPLE, SIDE_AF, SIDE_RELABEL, SIDE_MUTRATE, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
 struct SideProduct {
   const char *stem;   // "trio": the entry points famseq_trio[_prior], the options trio[_prior]_kernels, the plan keys trio[_prior]_*
   const char *what;   // load_or_fail's message starts "[site priors, ]<what> (sum-product engine): "
@@ -128,7 +131,7 @@ struct SideProduct {
                                   // (prior_kind < 0: the product has no site-prior form — no <stem>_prior_* name exists anywhere)
   int n_variants;
   std::string (*source)(const Model &, int variant, int form, bool site_prior);
-  // bytes per site of the two outputs; per_call: what the call itself says of them (the pattern entries' n_patterns, the sampling entries' n_draws, the relabelling entries' n_assign; 1 elsewhere)
+  // bytes per site of the two outputs; per_call: what the call itself says of them (the pattern entries' n_patterns, the sampling entries' n_draws, the relabelling entries' n_assign, the mutation-rate entries' n_rates; 1 elsewhere)
   void (*rows)(const Model &, int per_call, size_t row[2]);
   int kind_of(int form, bool site_prior) const { return (site_prior ? prior_kind : kind) + form - 1; }
   bool has_prior() const { return prior_kind >= 0; }
@@ -210,6 +213,9 @@ struct famseq_ctx {
   // ... and the relabelling host entries' assignments: FAMSEQ_MAX_RELABEL rows of int32, staged the same way
   famseq::DevBuf d_assign;
   std::vector<int32_t> assign_host;
+  // ... and the mutation-rate host entries' factor tables: FAMSEQ_MAX_RATES blocks of FAMSEQ_RATE_TABLE_DOUBLES, staged the same way
+  famseq::DevBuf d_rate_tables;
+  std::vector<double> rate_tables_host;
   int64_t trio_dev_sites = 0;
   std::string tune_report;  // what famseq_set_option "tune" measured (famseq_plan_json "tune")
   std::string err, json;
@@ -232,8 +238,8 @@ inline int fail(famseq_ctx *c, int code, const std::string &msg) {
 // What a generated kernel takes behind the common eight arguments, in the order of its parameter list: the address of each
 // argument's value (hipModuleLaunchKernel's form).  The call-path forms take their CallIO, the site-prior kernels their prior
 // rows, the pattern kernels their masks and n_patterns and the sampling kernels their seed, site_base and n_draws in front of
-// those, the allele-frequency kernel its start values and n_iter, the relabelling kernels their assignments and n_assign; the
-// plain forms nothing.
+// those, the allele-frequency kernel its start values and n_iter, the relabelling kernels their assignments and n_assign, the
+// mutation-rate kernels their tables and n_rates; the plain forms nothing.
 struct MoreArgs {
   static constexpr int kMax = 4;
   void *at[kMax] = {};

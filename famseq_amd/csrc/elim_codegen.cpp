@@ -155,6 +155,9 @@ struct EmitOptions {
   // the founders' prior is the site's own — the lane's variables pa_<g> (female founders; every founder off chrX) / pm_<g>
   // (male), see prior_source — instead of the model's rows in tcf[]
   bool site_prior = false;
+  // where given: every transmission entry is read from this pointer's block instead (tcx's layout: kind * 27 + 9 gc + 3 gm + gf),
+  // whatever scalar_t says — famseq_mutrate's pass-local table
+  const char *t_from = nullptr;
 };
 
 // fence level f of a kernel's variant (0..3; 3 fences the single posterior too, which is the shell's): what the emitter does
@@ -170,7 +173,8 @@ EmitOptions emit_options(int f, const char *out, bool site_prior) {
 class Emitter {
  public:
   Emitter(const Model &m, const Graph &g, const EmitOptions &o)
-      : m_(m), g_(g), fences_(o.fences), scalar_t_(o.scalar_t), out_(o.out), lean_(o.lean), lean_from_(o.lean_from), site_prior_(o.site_prior) {}
+      : m_(m), g_(g), fences_(o.fences), out_(o.out), lean_(o.lean), lean_from_(o.lean_from), site_prior_(o.site_prior),
+        t_from_(o.t_from ? o.t_from : (o.scalar_t ? "tcx" : "tcf")) {}
 
   std::string body() {
     if (g_.cut.empty()) {
@@ -339,18 +343,7 @@ class Emitter {
       for (int p = 0; p < g_.N; ++p)
         for (int g = 0; g < 3; ++g)
           head << "      const double l" << p << "_" << g << " = " << bit(p, g) << " ? r" << p << "_" << g << " : 0.0;\n";
-    std::string pass;
-    if (g_.cut.empty()) {
-      fence(1);
-      component_sums();
-      o_ << "      const double Zp_ = " << times_sums("") << ";\n";
-      fence(1);
-      pass = o_.str();
-    } else {
-      pass = cut_loop("      double Zt_ = 0;\n", /*wc=*/false, /*wall=*/true, [&] { o_ << "      Zt_ = Zt_ + Wall;\n"; fence(1); }) +
-             "      const double Zp_ = Zt_;\n";
-    }
-    return head.str() + pass + per_pass + "      }\n";
+    return head.str() + sum_pass() + per_pass + "      }\n";
   }
 
   // Relabelling evidence (famseq_relabel): the sum pass of evidence_body, run n_assign + 1 times on one read of the site's rows,
@@ -384,18 +377,25 @@ class Emitter {
         head << "      const int n" << p << " = " << entry << ";\n      const bool o" << p << " = n" << p << " >= " << g_.N << ";\n"
              << "      const int e" << p << " = o" << p << " ? 0 : 3 * n" << p << ";\n";
     }
-    std::string pass;
-    if (g_.cut.empty()) {
-      fence(1);
-      component_sums();
-      o_ << "      const double Zp_ = " << times_sums("") << ";\n";
-      fence(1);
-      pass = o_.str();
-    } else {
-      pass = cut_loop("      double Zt_ = 0;\n", /*wc=*/false, /*wall=*/true, [&] { o_ << "      Zt_ = Zt_ + Wall;\n"; fence(1); }) +
-             "      const double Zp_ = Zt_;\n";
-    }
-    return head.str() + pass + per_pass + "      }\n";
+    return head.str() + sum_pass() + per_pass + "      }\n";
+  }
+
+  // The mutation-rate likelihood profile (famseq_mutrate): the sum pass of evidence_body, run n_rates + 1 times on one read of
+  // the site's rows, pass 0 with the transmission entries of the context's own table (tc_g), pass r + 1 with those of block r of
+  // rt_g (build_factor_tables' layout, 432 doubles a block).  Every T() of the pass reads trt[] (EmitOptions::t_from), which
+  // the pass sets in front; the founders' priors (tcf[], or the site's own rows), the rows and a cut member's lam are the
+  // operands they are in evidence_body, so a pass is that body's statements on another table.
+  // trt is wave-uniform in every variant (the pass number through readfirstlane, x_ the chrX loop's, which the fence-free
+  // variant takes as well here): the entries arrive by scalar loads, as tcx's do, and cost neither a VGPR nor a vector-memory
+  // instruction per use, which a table addressed by the lane's flags would.
+  // The loop is `#pragma unroll 1`: the pass's text stands once whatever n_rates is.
+  // Per pass: Zp_, the pass's total weight (scaled as evidence_body's Z_: evidence_scale_digits()), then `per_pass`.
+  std::string mutrate_body(const std::string &per_pass) {
+    std::ostringstream head;
+    head << "#pragma unroll 1\n      for (int ps_ = 0; ps_ <= last_; ++ps_) {\n"
+         << "      const int pu_ = __builtin_amdgcn_readfirstlane(ps_);\n"
+         << "      const double *trt = (pu_ == 0 ? tc_g : rt_g + (long)(pu_ - 1) * RTD) + x_ * 216;\n";
+    return head.str() + sum_pass() + per_pass + "      }\n";
   }
 
   // The founders' allele frequency by maximum likelihood (famseq_af): EM on q, every step one sum pass and the founders' marginals
@@ -737,6 +737,20 @@ class Emitter {
     o_.str("");
     return out;
   }
+  // One sum pass inside a per-pass loop (pattern_body, relabel_body, mutrate_body): evidence_body's statements for the total
+  // weight, which it leaves in Zp_.  Leaves o_ empty.
+  std::string sum_pass() {
+    if (!g_.cut.empty())
+      return cut_loop("      double Zt_ = 0;\n", /*wc=*/false, /*wall=*/true, [&] { o_ << "      Zt_ = Zt_ + Wall;\n"; fence(1); }) +
+             "      const double Zp_ = Zt_;\n";
+    fence(1);
+    component_sums();
+    o_ << "      const double Zp_ = " << times_sums("") << ";\n";
+    fence(1);
+    const std::string pass = o_.str();
+    o_.str("");
+    return pass;
+  }
   // Zc<c>: the total weight of component c, from the marginal of its representative
   void component_sums() {
     for (size_t c = 0; c < g_.rep.size(); ++c) {
@@ -861,11 +875,11 @@ class Emitter {
   const Model &m_;
   const Graph &g_;
   const int fences_;  // (EmitOptions)
-  const bool scalar_t_;
   const std::string out_;
   const bool lean_;
   const int lean_from_;
   const bool site_prior_;
+  const std::string t_from_;  // the array T() reads
   std::ostringstream o_;
   std::map<std::string, bool> done_;
   int uid_ = 0;
@@ -900,7 +914,7 @@ class Emitter {
     return m_.mother[p] < 0 ? (male ? 0 : 1) : (male ? 2 : 3);
   }
   std::string T(int child, int gc, int gm, int gf) const {
-    return std::string(scalar_t_ ? "tcx[" : "tcf[") + num(kind(child) * 27 + 9 * gc + 3 * gm + gf) + "]";
+    return t_from_ + "[" + num(kind(child) * 27 + 9 * gc + 3 * gm + gf) + "]";
   }
 
   // member p's local factor at genotype g without the component's scale: lk for a child, prior * lk for a founder (the prior
@@ -1571,6 +1585,50 @@ std::string relabel_source(const Model &m, int variant, bool site_prior) {
                "    if (loglik_g) __builtin_nontemporal_store(rl_ll, loglik_g + site);\n"
                "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  return lane_shell(m, d);
+}
+
+// The mutation-rate kernel: the evidence kernel's rules and shell, and its LDS (the factor tables alone: a pass's table is read
+// where it lies).  Beyond the common arguments: rt_g[n_rates][432], one factor table per rate, of which only the transmission
+// entries are read (whatever they hold: nothing is indexed by them), and n_rates (1 .. FAMSEQ_MAX_RATES; the host checks, the
+// kernel clamps).  Outputs per site: rate_ll[n_rates], log10 Z_r without the reference's 1e7 — not clamped; -inf where Z_r is
+// exactly 0 (rate 0 on a Mendel-impossible row), which is a result — and loglik, famseq_evidence's, from the pass on the
+// context's own table; either may be null (without rate_ll only that pass runs).  Only the context's own Z that is not a
+// positive finite number fails the site (status 2).  The rows stay where famseq_evidence has them: registers, lean from forty.
+std::string mutrate_source(const Model &m, int variant, bool site_prior) {
+  const Graph g = graph_or_throw(m);
+  if (variant < 0 || variant >= kMutrateVariants)
+    throw std::runtime_error("mutrate_source: variant must be 0.." + std::to_string(kMutrateVariants - 1));
+  const int f = variant;
+  EmitOptions eo = emit_options(f, "pg", site_prior);
+  eo.t_from = "trt";
+  LaneShell d;
+  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
+  d.entry = "famseq_mutrate";
+  d.comment = describe("mutation-rate likelihood profile (sum pass per rate)", g, std::to_string(f), site_prior);
+  d.outputs = "double *__restrict__ rate_ll_g, double *__restrict__ loglik_g";
+  d.more_args = ", const double *__restrict__ rt_g, int n_rates";
+  d.defines = "#define MAXRATES " + std::to_string(FAMSEQ_MAX_RATES) + "\n#define RTD " + std::to_string(FAMSEQ_RATE_TABLE_DOUBLES) + "\n";
+  d.prologue = "  const int nr_ = n_rates < 0 ? 0 : (n_rates > MAXRATES ? MAXRATES : n_rates);\n";
+  d.site_decls = "    double *rp = rate_ll_g ? rate_ll_g + site * nr_ : nullptr;\n"
+                 "    const int last_ = rp ? nr_ : 0;\n";
+  d.site_vars = "    double mr_ll = kNaN;\n";
+  Emitter e(m, g, eo);
+  const std::string digits = std::to_string(e.evidence_scale_digits()) + ".0";
+  d.body = e.mutrate_body(
+      "      if (ps_ == 0) {\n"
+      "        if (!(Zp_ > 0 && Zp_ <= 1.79769313486231570815e308)) { bn_fail = true; break; }\n"
+      "        mr_ll = log10(Zp_) - " + digits + ";\n"
+      "      } else {\n"
+      "        __builtin_nontemporal_store(log10(Zp_) - " + digits + ", rp + (ps_ - 1));\n"
+      "      }\n");
+  d.epilogue = "    if (single_fail || bn_fail) {\n      mr_ll = kNaN;\n"
+               "      if (rp) {\n#pragma unroll 1\n        for (int k = 0; k < nr_; ++k) rp[k] = kNaN;\n      }\n"
+               "    }\n"
+               "    if (loglik_g) __builtin_nontemporal_store(mr_ll, loglik_g + site);\n"
+               "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
+  d.bt = elim_block_threads(m, false);
+  d.fence_single = f >= 3, d.chrx_loop = true, d.site_prior = site_prior;  // (variant 0 too: mutrate_body)
   return lane_shell(m, d);
 }
 

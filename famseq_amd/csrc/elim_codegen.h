@@ -99,6 +99,17 @@ constexpr int kRelabelVariants = 4;
 // site_prior: famseq_relabel_prior, with a trailing `prior` [n_sites][6] behind n_assign (as trio_source's).
 std::string relabel_source(const Model &m, int variant, bool site_prior = false);
 
+// The mutation-rate likelihood profile (famseq_mutrate_batch).  HIP source of
+// `extern "C" __global__ famseq_mutrate(lk, flags, rate_ll, loglik, status, n_sites, tc, lc, rt, n_rates)`: per site and rate r
+// rate_ll[r] = log10 Z_r, the network's total weight with the children's transmission entries taken from block r of
+// rt[n_rates][432] (build_factor_tables' layout; the founders' priors stay tc's, or the site's own), famseq_evidence's scale
+// (-inf where it is exactly 0); and loglik, famseq_evidence's, under tc itself.  The sum pass of famseq_evidence, n_rates + 1
+// times on one read of the site's rows.  variant 0..3: the fence levels of famseq_elim's; every variant gives the same bits, and
+// in every one a pass's entries arrive by scalar loads (variant 0 takes the chrX loop as well).  Throws if the engine does not serve the pedigree.
+constexpr int kMutrateVariants = 4;
+// site_prior: famseq_mutrate_prior, with a trailing `prior` [n_sites][6] behind n_rates (as trio_source's).
+std::string mutrate_source(const Model &m, int variant, bool site_prior = false);
+
 // The founders' allele frequency by maximum likelihood (famseq_af_batch).  HIP source of
 // `extern "C" __global__ famseq_af(lk, flags, af, loglik, status, n_sites, tc, lc, af0, n_iter)`: per site n_iter EM steps on the
 // allele frequency q of the founders' Hardy-Weinberg prior from af0 — a step is one sum pass of famseq_evidence and the founders'

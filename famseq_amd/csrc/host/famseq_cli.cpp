@@ -5,7 +5,7 @@
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
 //              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-loo] [-afTag KEY | -afTagAll KEY]
 //              [-seg dominant|recessive|both -affected ID[,ID...] [-unaffected ID[,ID...]]] [-sample K [-seed S]]
-//              [-afEM T [-afStart X]] [-swapCheck FILE]
+//              [-afEM T [-afStart X]] [-swapCheck FILE] [-mRateScan FILE [-mRateGrid r1,r2,...]]
 //   FamSeq LK -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -27,7 +27,8 @@
 // recessive model, to the INFO column (PSD, PSR), and -sample K (vcf mode) each sample's alt-allele counts in K joint configurations
 // of the family drawn from their posterior (SGT), and -afEM T (vcf mode) the maximum-likelihood allele frequency among the founders after
 // T EM steps and its log10 likelihood ratio against an allele frequency of 0, to the INFO column (FAF, FAL), and -swapCheck FILE (vcf
-// mode) writes, behind the last site, the log10 Bayes factor of every two sequenced samples' exchange over the whole file.
+// mode) writes, behind the last site, the log10 Bayes factor of every two sequenced samples' exchange over the whole file, and
+// -mRateScan FILE (vcf mode) the file's log10 likelihood at every mutation rate of a grid.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -206,6 +207,12 @@ struct Options {
   // of the file's fit to the pedigree with the two relabelled against the labelling as given
   string swap_file;
   bool swap_given = false;
+  // -mRateScan FILE [-mRateGrid r1,r2,...]: after the last site, the file's log10 likelihood at every mutation rate of the grid
+  // (vcf mode).  rate_grid_bad: the first entry of -mRateGrid that is no number in [0, 1], as it was given
+  string rate_file;
+  bool rate_scan_given = false, rate_grid_given = false, rate_grid_is_bad = false;
+  vector<double> rate_grid = {0, 1e-9, 1e-8, 1e-7, 1e-6, 1e-5, 1e-4, 1e-3};
+  string rate_grid_bad;
   string af_tag;     // -afTag KEY: the founders' prior of a line from the allele frequency KEY= of its INFO column (vcf mode)
   bool af_conflict = false;  // both -afTag and -afTagAll were given
   bool af_all = false;  // -afTagAll KEY: -afTag KEY, applied to every field a line prints (DNP, JGT and JP too: may go with -dnm / -map)
@@ -387,6 +394,23 @@ int parse_options(int argc, char **argv, Options &o) {
       } else {
         o.swap_file = argv[i];
         o.swap_given = true;
+      }
+    } else if (opt == "mRateScan") {  // (what may be wrong with either: check_rate_scan, with the other side options' checks)
+      o.rate_scan_given = true;
+      if (!missing(i + 1)) o.rate_file = argv[++i];
+    } else if (opt == "mRateGrid") {
+      o.rate_grid_given = true;
+      o.rate_grid.clear();
+      // (no value, or one that starts like an option: the grid stays empty, which check_rate_scan refuses)
+      const string text = missing(i + 1) ? "" : argv[++i];
+      for (size_t at = 0; !text.empty() && at <= text.size();) {
+        const size_t end = std::min(text.find(',', at), text.size());
+        const string entry = text.substr(at, end - at);
+        char *stop = nullptr;
+        const double v = std::strtod(entry.c_str(), &stop);
+        if ((entry.empty() || *stop || !(v >= 0.0 && v <= 1.0)) && !o.rate_grid_is_bad) o.rate_grid_is_bad = true, o.rate_grid_bad = entry;
+        o.rate_grid.push_back(v);
+        at = end + 1;
       }
     } else if (opt == "seg" || opt == "affected" || opt == "unaffected") {
       i++;
@@ -1395,14 +1419,14 @@ struct Part {
   }
 };
 
-// ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample, -seg and -afEM add to a line, one row of kSide each; -swapCheck, which
-// ---- adds nothing to any line and writes a report of its own behind the last site (SideRow::report), is a row too -------------
+// ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample, -seg and -afEM add to a line, one row of kSide each; -swapCheck and
+// ---- -mRateScan, which add nothing to any line and write a report of their own behind the last site (SideRow::report), are rows too
 // The order is the one main checks them and prints its notices in; it is also the order of the fields in a sample column (DNP,
 // JGT:JP, LOP:LOF, SGT) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL).  Header lines have their
 // own order.
-enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap };
-constexpr int kSides = kSwap + 1;
-const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap};
+enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap, kRateScan };
+constexpr int kSides = kRateScan + 1;
+const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap, kRateScan};
 
 // One side output of a block: the two arrays its C entry fills ([site][...], read as the entry's own types) and its status per site.
 struct SideOut {
@@ -1425,7 +1449,8 @@ struct SideRow {
   const char *keys, *na;  // its FORMAT keys and what a failed site prints for them; null: it writes INFO keys
   SideBytes (*bytes)(const VcfRun &);  // per site, of the two arrays
   // its per-line text is empty (no header line, no FORMAT or INFO key: the output file is the one without it); what its kernel
-  // says of a block is summed up site by site (VcfRun::add_report) and written behind the last site (VcfRun::write_report)
+  // says of a block is summed up site by site (VcfRun::add_report / add_rate_report) and written behind the last site
+  // (VcfRun::write_report / write_rate_report)
   bool report = false;
 };
 extern const SideRow kSide[kSides];
@@ -1473,6 +1498,13 @@ struct VcfRun {
   uint64_t swap_used = 0, swap_skipped = 0;
   double swap_loglik = 0;
   vector<string> sample_names;  // -swapCheck: the VCF's name of column j of cm.cols
+  // -mRateScan: what the sites so far add up to, in file order: per rate of the grid the sum of rate_loglik over the used sites
+  // (one -inf makes it -inf) and the number of used sites where it is -inf; the used and the skipped (status != 0) sites, the
+  // used sites' loglik under the run's own -mRate
+  vector<double> rate_sum;
+  vector<uint64_t> rate_impossible;
+  uint64_t rate_used = 0, rate_skipped = 0;
+  double rate_own = 0;
   double model_rows[2][6];  // -afTag: the rows of a line without a usable frequency, by its Known flag: what the model itself would have used
   ColumnMap cm;
   size_t ncol = 0, n_seq = 0, N3 = 0;
@@ -1882,6 +1914,10 @@ struct VcfRun {
       case kSample: rc = entry(famseq_sample_batch, famseq_sample_prior_batch, o.seed, sl.site_base, (int32_t)o.sample, a8, none, st); break;
       case kSeg: rc = entry(famseq_pattern_batch, famseq_pattern_prior_batch, seg_masks.data(), (int32_t)seg_keys.size(), a, none, st); break;
       case kSwap: return call_swap(sl, so, lk, pl16);
+      case kRateScan:
+        rc = entry(famseq_mutrate_batch, famseq_mutrate_prior_batch, o.rate_grid.data(), (int32_t)o.rate_grid.size(), a, b, st);
+        if (rc == 0) add_rate_report(sl, so);
+        break;
       case kAfEm: {  // the prior is its unknown: one entry, whatever -afTagAll says of the line
         const vector<double> af0(sl.n_sites, o.af_start);
         rc = famseq_af_batch(ctx, (int64_t)sl.n_sites, lk, pl16, cm.members.data(), (int32_t)n_seq, sl.io.flags, af0.data(), (int32_t)o.af_em, a, b, st);
@@ -1945,6 +1981,45 @@ struct VcfRun {
     for (size_t k = 0; k < swap_cols.size(); ++k)
       std::fprintf(f, "%s\t%s\t%.6f\t%llu\n", sample_names[swap_cols[k].first].c_str(), sample_names[swap_cols[k].second].c_str(),
                    swap_bf.empty() ? 0.0 : swap_bf[k], (unsigned long long)(swap_impossible.empty() ? 0 : swap_impossible[k]));
+    return std::fclose(f) == 0;
+  }
+  // -mRateScan: the block's sites (not its other lines), in file order
+  void add_rate_report(const Slot &sl, const SideOut &so) {
+    const size_t n = o.rate_grid.size();
+    if (rate_sum.empty()) rate_sum.assign(n, 0.0), rate_impossible.assign(n, 0);
+    for (int t = 0; t < sl.n_parts; ++t)
+      for (const Item &it : sl.parts[t].items) {
+        if (it.site < 0) continue;
+        const size_t s = size_t(it.site);
+        if (so.status[s] != 0) {
+          ++rate_skipped;
+          continue;
+        }
+        ++rate_used, rate_own += so.b[s];
+        for (size_t k = 0; k < n; ++k) {
+          rate_sum[k] += so.a[s * n + k];
+          rate_impossible[k] += std::isinf(so.a[s * n + k]);
+        }
+      }
+  }
+  bool write_rate_report() const {
+    std::FILE *f = std::fopen(o.rate_file.c_str(), "w");
+    if (!f) return false;
+    const size_t n = o.rate_grid.size();
+    const vector<double> sum = rate_sum.empty() ? vector<double>(n, 0.0) : rate_sum;  // (a file without a site)
+    auto put = [&](double v) { std::isinf(v) ? std::fprintf(f, "\t-inf") : std::fprintf(f, "\t%.6f", v); };
+    std::fprintf(f, "# -mRateScan: %llu sites used, %llu skipped; -mRate %g log10_lik %.6f\n", (unsigned long long)rate_used,
+                 (unsigned long long)rate_skipped, o.mrate, rate_own);
+    std::fprintf(f, "rate\tlog10_lik\tdelta\tn_impossible\n");
+    size_t best = 0;
+    for (size_t k = 0; k < n; ++k) {
+      std::fprintf(f, "%g", o.rate_grid[k]);
+      put(sum[k]);
+      put(sum[k] - rate_own);
+      std::fprintf(f, "\t%llu\n", (unsigned long long)(rate_impossible.empty() ? 0 : rate_impossible[k]));
+      if (sum[k] > sum[best]) best = k;  // (the first of the largest)
+    }
+    std::fprintf(f, "best\t%g\n", o.rate_grid[best]);
     return std::fclose(f) == 0;
   }
   void gpu_loop() {
@@ -2171,6 +2246,7 @@ inline void put_faf(TextBuf &out, const VcfRun &, const SideOut &so, size_t s, s
     case kSeg: return put_seg(out, r, so, s, j);
     case kAfEm: return put_faf(out, r, so, s, j);
     case kSwap: return;  // (a report row: nothing on a line)
+    case kRateScan: return;
   }
 }
 
@@ -2208,6 +2284,35 @@ bool check_swap(const Options &o, const Ped &) {
   std::FILE *f = o.swap_file.empty() ? nullptr : std::fopen(o.swap_file.c_str(), "a");
   if (!f) {
     std::cout << "Cannot write " << o.swap_file << " (the report file of -swapCheck)." << std::endl;
+    return false;
+  }
+  std::fclose(f);
+  return true;
+}
+
+// -mRateScan's own: its two options go together, the grid holds 1 .. FAMSEQ_MAX_RATES numbers in [0, 1], and the report file must
+// be writable before any input is read (as check_swap)
+bool check_rate_scan(const Options &o, const Ped &) {
+  if (!o.rate_scan_given) {
+    std::cout << "-mRateGrid gives the rates of -mRateScan FILE, which hasn't been set." << std::endl;
+    return false;
+  }
+  if (o.rate_grid.empty()) {
+    std::cout << "-mRateGrid takes the mutation rates to scan, r1,r2,...: the grid is empty." << std::endl;
+    return false;
+  }
+  if (o.rate_grid.size() > FAMSEQ_MAX_RATES) {
+    std::cout << "-mRateGrid takes at most " << FAMSEQ_MAX_RATES << " rates, not " << o.rate_grid.size() << "." << std::endl;
+    return false;
+  }
+  if (o.rate_grid_is_bad) {
+    std::cout << "-mRateGrid takes mutation rates, numbers in [0, 1], not \"" << o.rate_grid_bad << "\"." << std::endl;
+    return false;
+  }
+  std::FILE *f = o.rate_file.empty() ? nullptr : std::fopen(o.rate_file.c_str(), "a");
+  if (!f) {
+    std::cout << "Cannot write " << (o.rate_file.empty() ? "the report file of -mRateScan: it hasn't been set." : o.rate_file + " (the report file of -mRateScan).")
+              << std::endl;
     return false;
   }
   std::fclose(f);
@@ -2274,6 +2379,10 @@ const SideRow kSide[kSides] = {
     {kSwap, "-swapCheck", "famseq_relabel", true, [](const Options &o) { return o.swap_given; },
      [](Options &o) { o.swap_given = false, o.swap_file.clear(); }, check_swap, [](std::ostream &, const Options &) {}, nullptr, nullptr,
      [](const VcfRun &r) { return SideBytes{8 * std::min<size_t>(FAMSEQ_MAX_RELABEL, r.swap_cols.size()), 8}; }, /*report=*/true},
+    // (on: either of its options, so that main can say which one is missing)
+    {kRateScan, "-mRateScan", "famseq_mutrate", true, [](const Options &o) { return o.rate_scan_given || o.rate_grid_given; },
+     [](Options &o) { o.rate_scan_given = o.rate_grid_given = false, o.rate_file.clear(); }, check_rate_scan, [](std::ostream &, const Options &) {},
+     nullptr, nullptr, [](const VcfRun &r) { return SideBytes{8 * r.o.rate_grid.size(), 8}; }, /*report=*/true},
 };
 
 // `FamSeq vcf` and `FamSeq pack`: the wiring of a VcfRun's stages
@@ -2356,6 +2465,10 @@ bool run_vcf(const Options &o, const Ped &ped) {
   famseq_destroy(r.ctx);
   if (ok && o.swap_given && !r.write_report()) {
     std::cout << "Cannot write " << o.swap_file << " (the report file of -swapCheck)." << std::endl;
+    return false;
+  }
+  if (ok && o.rate_scan_given && !r.write_rate_report()) {
+    std::cout << "Cannot write " << o.rate_file << " (the report file of -mRateScan)." << std::endl;
     return false;
   }
   return ok && !r.fout.fail();
@@ -2493,6 +2606,12 @@ void help() {
             << "\t\tsum leaves out; line 1 counts the sites used and skipped (failed) and gives the file's log10 likelihood. Adds nothing to" << std::endl
             << "\t\tany output line. Implies -method 2; may be combined with every other option above, under -afTagAll with the line's prior;" << std::endl
             << "\t\tnot with -afTag." << std::endl
+            << "-mRateScan FILE\t(vcf) After the last site write FILE: for every mutation rate of -mRateGrid r1,r2,... (1.." << FAMSEQ_MAX_RATES << " numbers in [0, 1];" << std::endl
+            << "\t\tdefault 0,1e-9,1e-8,1e-7,1e-6,1e-5,1e-4,1e-3) log10_lik, the sum over the file's sites of the log10 likelihood of the" << std::endl
+            << "\t\tsite under the pedigree at that rate (-inf once one site is impossible at it), delta, that sum minus the one at the run's" << std::endl
+            << "\t\town -mRate, and n_impossible, the sites impossible at the rate; the last line names the best rate of the grid, line 1 counts" << std::endl
+            << "\t\tthe sites used and skipped (failed). Adds nothing to any output line. Implies -method 2; may be combined with every other" << std::endl
+            << "\t\toption above, under -afTagAll with the line's prior; not with -afTag." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl

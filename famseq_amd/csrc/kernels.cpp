@@ -40,6 +40,9 @@ SideTable &side_table() {
       {"relabel", "relabelling evidence", "1", K_RELABEL, K_RELABEL_PRIOR, 1, kRelabelVariants,
        [](const Model &m, int v, int, bool site_prior) { return relabel_source(m, v, site_prior); },
        [](const Model &, int n_assign, size_t row[2]) { row[0] = size_t(n_assign) * sizeof(double), row[1] = sizeof(double); }},  // alt_loglik[M], loglik
+      {"mutrate", "mutation-rate likelihood profile", "1", K_MUTRATE, K_MUTRATE_PRIOR, 1, kMutrateVariants,
+       [](const Model &m, int v, int, bool site_prior) { return mutrate_source(m, v, site_prior); },
+       [](const Model &, int n_rates, size_t row[2]) { row[0] = size_t(n_rates) * sizeof(double), row[1] = sizeof(double); }},  // rate_loglik[R], loglik
   };
   return table;
 }

@@ -673,7 +673,69 @@ int famseq_relabel_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const do
                                       const int32_t *d_assign, int32_t n_assign, double *d_alt_loglik, double *d_loglik,
                                       uint8_t *d_status, void *stream);
 
-/* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] = ((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
+/* ---- the mutation-rate likelihood profile: which rate the data support --------------------------------------------------------
+ * The network has two kinds of parameters.  The founders' prior is given per site (the *_prior_batch entries) or learned
+ * (famseq_af_batch); the mutation rate behind the transmission tables is fixed when the context is made.  These entries give, for
+ * up to FAMSEQ_MAX_RATES rates at once, the site's likelihood under each.  A rate's factor table is the context's own
+ * (4 flag combinations x 4 member kinds x 27 doubles, FAMSEQ_RATE_TABLE_DOUBLES in all) with the three transmission tables
+ * replaced by famseq_transmission_tables(rate); Z_r is the network's total weight, as famseq_evidence_batch forms it, with the
+ * children's transmission entries taken from table r.  The founders' priors stay those of the context (by the Known flag) or, in
+ * the prior form, of the site's row; the single-posterior rule never reads a transmission table, so it does not depend on r.
+ * With rate 0 in the grid, rate_loglik[.][r] - rate_loglik[.][r0] is the log10 Bayes factor "this site needs a mutation to be
+ * explained"; summed over sites the columns give the maximum-likelihood rate.
+ *   rates [n_rates]         finite numbers in [0, 1], the same for every site of the call.
+ *   n_rates                 1 .. FAMSEQ_MAX_RATES.
+ *   rate_loglik [n_sites][n_rates]   log10 Z_r on famseq_evidence_batch's scale.  The contract: wherever a context created from
+ *              the same pedigree and priors with mrate = rates[r] answers status 0 on the same rows, rate_loglik[s][r] is that
+ *              call's loglik, bit for bit.  Not clamped: -inf where Z_r is exactly 0 (rate 0 on a Mendel-impossible row with
+ *              exact zeros), which is a result, not a failure.  A column's bits depend neither on n_rates nor on the other
+ *              rates; two equal rates give equal bits; a rate equal to the mrate the model was made with gives loglik's bits.
+ *   loglik [n_sites]        famseq_evidence_batch's bits under the context's own tables.
+ *   status [n_sites]        0 OK; 1 the single-posterior failure rule of famseq_bn_batch, applied to the rows as given; 2 the
+ *              context's own total weight Z is <= 0 or not finite.  Wherever status != 0, rate_loglik and loglik of the site are
+ *              NaN.  There is no -LRC shortcut.
+ * One kernel launch reads a site's rows once and runs the sum pass n_rates + 1 times on them, a pass's transmission entries
+ * arriving through a wave-uniform pointer.  Served by the sum-product engine's graph as famseq_evidence_batch is, whatever the
+ * context's engine; compiled on the first call or ahead through famseq_set_option "mutrate_kernels" = 1 (a context without a
+ * device generates and cross-compiles it).  famseq_plan_json: "mutrate_code_object", "mutrate_variant".
+ * FAMSEQ_E_ARG, with a message and before the device is asked for: n_rates outside 1 .. FAMSEQ_MAX_RATES, rates / d_tables NULL,
+ * (host entries and famseq_rate_tables) the first rates[r] that is not a finite number in [0, 1], named by its index. */
+#define FAMSEQ_MAX_RATES 32
+#define FAMSEQ_RATE_TABLE_DOUBLES 432
+
+/* tables[n_rates][FAMSEQ_RATE_TABLE_DOUBLES]: block r is the context's own factor table with the three transmission tables
+ * replaced by famseq_transmission_tables(rates[r]) — what the device entries below take, once uploaded.  Block r equals, bit for
+ * bit, the table of a context made with mrate = rates[r].  Works on a context without a device. */
+int famseq_rate_tables(famseq_ctx *ctx, const double *rates, int32_t n_rates, double *tables);
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_evidence_batch.  rates is a host array; the library builds the
+ * tables (famseq_rate_tables) and stages them.  Any of rate_loglik / loglik / status may be NULL; without rate_loglik only the
+ * pass on the context's own tables runs. */
+int famseq_mutrate_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                         int32_t n_seq, const uint8_t *flags, const double *rates, int32_t n_rates, double *rate_loglik /*[n_sites][n_rates]*/,
+                         double *loglik /*[n_sites]*/, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array), d_tables [n_rates][432] among them — it must
+ * stay valid and unchanged until the kernel has run, and nothing is checked of its contents: the kernel reads only the
+ * transmission entries of a block and indexes nothing by them.  Enqueues on `stream` (a hipStream_t; NULL = the default stream)
+ * and returns without synchronising (the stream rule at famseq_bn_batch_device: with d_lk no context state, no event and no wait;
+ * with d_pl16 through the kept scratch rows, like every side entry). */
+int famseq_mutrate_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_tables,
+                                int32_t n_rates, double *d_rate_loglik, double *d_loglik, uint8_t *d_status, void *stream);
+
+/* With the founders' genotype prior given per site: prior[n_sites][6], as for famseq_evidence_prior_batch.  Given rows that equal
+ * the model's constants the outputs are, bit for bit, famseq_mutrate_batch's.  "mutrate_prior_kernels" = 1 builds the kernel
+ * (famseq_mutrate_prior) ahead; famseq_plan_json: "mutrate_prior_code_object", "mutrate_prior_variant". */
+int famseq_mutrate_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                               int32_t n_seq, const uint8_t *flags, const double *prior, const double *rates, int32_t n_rates,
+                               double *rate_loglik, double *loglik, uint8_t *status);
+int famseq_mutrate_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                      const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                      const double *d_tables, int32_t n_rates, double *d_rate_loglik, double *d_loglik,
+                                      uint8_t *d_status, void *stream);
+
+/* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] =((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);
 
