@@ -224,7 +224,7 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
   if (!c || !key) return FAMSEQ_E_ARG;
   const std::string k(key);
   if (c->big) {  // no enumeration here: its knobs have nothing to act on
-    for (const char *e : {"fixed_digits", "low_members", "block_threads", "enum_impl", "group_digits", "pick_lane", "tune", "lane_min_sites"})
+    for (const char *e : {"fixed_digits", "low_members", "block_threads", "enum_impl", "group_digits", "pick_lane", "tune", "lane_min_sites", "bulk_min_sites"})
       if (k == e) return fail(c, FAMSEQ_E_ARG, "option " + k + " belongs to the enumeration engine, which serves up to 20 members");
     if (k == "engine" && value == FAMSEQ_ENGINE_ENUM)
       return fail(c, FAMSEQ_E_ARG, "the 3^N enumeration serves up to 20 members; this pedigree has " + std::to_string(c->model.n_members));
@@ -249,6 +249,11 @@ extern "C" int famseq_set_option(famseq_ctx *c, const char *key, int64_t value) 
     return 0;
   }
   else if (k == "lane_min_sites") { c->lane_min_sites = value; return 0; }
+  else if (k == "bulk_min_sites") {  // from how many sites on the bulk slot serves a one-lane-per-site launch; -1: never
+    if (value < -1) return fail(c, FAMSEQ_E_ARG, "bulk_min_sites takes a site count, or -1 (the bulk slot is off)");
+    c->bulk_min_sites = value;
+    return 0;
+  }
   else if (k == "tune") {
     if (value != 1) return fail(c, FAMSEQ_E_ARG, "tune takes 1");
     return tune(c);
@@ -390,6 +395,8 @@ extern "C" const char *famseq_plan_json(famseq_ctx *c) {
               ",\"enum_supported\":0,\"device\":" + std::to_string(c->device) + ",\"cus\":" + std::to_string(c->n_cus) + trio_json(c) + "}";
     return c->json.c_str();
   }
+  bulk_prebuild(c);  // (a plan-only context: whoever warms a cache through plan() leaves nothing for the first large launch)
+  const GenKernel &bulk = c->kern[K_LANE_BULK];
   c->json = c->plan.json();
   c->json.pop_back();
   c->json += ",\"engine\":" + std::to_string(c->engine) + ",\"elim_supported\":" +
@@ -409,7 +416,13 @@ extern "C" const char *famseq_plan_json(famseq_ctx *c) {
              json_str(elim_call.error.substr(0, 300)) + "\",\"enum_lane_call_reads_rows\":" + std::to_string(c->lane_reads_rows) +
              ",\"enum_lane_call_variant\":" + std::to_string(lane_call.variant) + ",\"elim_call_variant\":" +
              std::to_string(elim_call.variant) + ",\"tune\":\"" +
-             json_str(c->tune_report) + "\"" + trio_json(c) + "}";
+             json_str(c->tune_report) + "\"" +
+             // the bulk slot (kernels.cpp, bulk_serves); the enum_lane_* keys above describe K_LANE whichever kernel served
+             // (in front of the side products' keys: the latest of those are pinned to the end of the plan)
+             ",\"enum_bulk_code_object\":\"" + json_str(bulk.k.path) + "\",\"enum_bulk_variant\":" + std::to_string(bulk.variant) +
+             ",\"enum_bulk_shape\":\"" + (bulk.variant >= 0 ? enumgen_describe(c->model, bulk.variant) : std::string()) +
+             "\",\"enum_bulk_min_sites\":" + std::to_string(bulk_min_sites(c)) + ",\"enum_bulk_failed\":" + (bulk.failed ? "1" : "0") +
+             ",\"enum_last_kind\":\"" + c->last_kind + "\"" + trio_json(c) + "}";
   return c->json.c_str();
 }
 

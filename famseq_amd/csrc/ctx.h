@@ -81,6 +81,8 @@ enum KernelKind {
   K_RELABEL_PRIOR,                                 // ... with the founders' prior per site
   K_MUTRATE,                                       // mutation-rate likelihood profile: the sum pass once per transmission table
   K_MUTRATE_PRIOR,                                 // ... with the founders' prior per site
+  K_LANE_BULK,  // the one-lane-per-site enumeration in the outer-leaf plan (lane variant 8 + K_LANE's block shape and fencing): serves
+                // large batches where that text differs from K_LANE's (kernels.cpp, bulk_serves); no pick, no contest of its own
   K_COUNT
 };
 
@@ -161,6 +163,13 @@ struct famseq_ctx {
   // pedigree.  enum_impl: -1 auto (lane for large batches), 0 team, 1 lane.  group_digits: -1 auto (by batch size), 0..4 forced.
   int enum_impl = -1;
   int group_digits = -1, last_group_digits = 0;
+  // The bulk slot (K_LANE_BULK): a one-lane-per-site launch of a context that is free to choose (enum_impl < 0, group_digits < 0)
+  // goes to it from bulk_min_sites sites on.  -2: the default, sixteen chunks per resident wave (16 x 64 x CUs x 4: below that a
+  // launch is under 2.5 ms on MI355X, and a second module load and a second set of last bits are not worth it); -1: the slot is off.
+  int64_t bulk_min_sites = -2;
+  int bulk_any = -1;                // does the pedigree have the form at all, in either block shape (worked out once per context)
+  int bulk_differs = -1;            // does variant 8 + b differ from K_LANE's 4 + b (unknown until K_LANE has its variant)
+  const char *last_kind = "";       // which enumeration kernel served the last launch: "team", "group", "lane", "bulk"
   int lane_first = -1;  // where the lane kernel's variant contest starts (lane_first_variant(): worked out once per context)
   int lane_reads_rows = -1;  // does the lane call-path kernel re-read fp64 rows from global memory (unknown until it is built)
   int trio_last = 0;         // the trio output form asked for last (famseq_plan_json)
@@ -261,8 +270,12 @@ void drop_lane_kernels(famseq_ctx *c);  // what a new pick of the lane variant m
 int lane_first_variant(const famseq_ctx *c);  // 4 where the lane kernel has the once-per-site form (variants 4-7), else 0
 hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, void *d_out_a,
                             void *d_out_b, uint8_t *d_status, hipStream_t stream, int sites_per_chunk = 0, const MoreArgs &more = {});
+// call_sites: the size of the host call this launch is a chunk of (0: the launch is the call).  Whether the bulk slot serves is
+// decided from it, so that every chunk of a call goes the same way and equal calls give equal bits, resident or staged.
 hipError_t launch_engine(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, double *d_post, double *d_single,
-                         uint8_t *d_status, hipStream_t stream);
+                         uint8_t *d_status, hipStream_t stream, int64_t call_sites = 0);
+int64_t bulk_min_sites(const famseq_ctx *c);  // the threshold in force (-1: off)
+void bulk_prebuild(famseq_ctx *c);            // a plan-only context that holds K_LANE compiles the bulk object too, where the pedigree has one
 bool call_fuses(famseq_ctx *c, int64_t n_sites, bool packed_in);
 bool launch_engine_fused(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, uint8_t *d_status, bool packed_in,
                          const CallIO *d_io, hipStream_t stream, hipError_t *err);

@@ -20,6 +20,9 @@
 //     level further out: the innermost looped member joins the block, prefix tables that mention no loop digit are built once
 //     per site into the lane's LDS row, and the prefix members' marginals are formed after the loops (OnceEmitter, "The
 //     once-per-site form"): lane variants 4-7 (enum_codegen.h); FAMSEQ_LANE_HOIST=0 keeps the per-prefix text there too.
+//   * where a founder and its leaf children can be that super-leaf, with their other parent as the outermost loop, the table mentions
+//     one loop digit and is built three times per site (outer_leaf_shape, "The outer-leaf plan"): lane variants 8-11, where a cost
+//     model takes it; FAMSEQ_LANE_OUTER=0 keeps the text of 4-7.  Loops are then no longer parents first (BlockPlan::factor_pos).
 // BlockPlan holds what is decided about a block shape, row_layout the lane's LDS row per form, Emitter the text both forms
 // share; lane_form chooses between PrefixEmitter and OnceEmitter.
 // The generic team-per-site kernel remains the fallback (small batches, no compiler at run time).
@@ -44,8 +47,9 @@ std::string num(int x) { return std::to_string(x); }
 
 struct Shape {
   int N = 0;
-  std::vector<int> outer, unrolled;  // both in parents-before-children order
+  std::vector<int> outer, unrolled;  // both in parents-before-children order (outer: unless loops_as_given)
   std::vector<int> upos;             // member -> level in `unrolled` or -1
+  bool loops_as_given = false;       // the outer-leaf plan: `outer` is the loop order, and its first member may enclose its parents
 };
 
 int kind_of(const Model &m, int p) {
@@ -167,7 +171,7 @@ struct BlockPlan {
       const int p = s.unrolled[k];
       entries.push_back(m.mother[p] < 0 ? 3 : 3 * (s.upos[m.mother[p]] >= 0 ? 3 : 1) * (s.upos[m.father[p]] >= 0 ? 3 : 1));
     }
-    order_outer_loops();
+    if (!s.loops_as_given) order_outer_loops();
     wb.assign(nu, -1);
     qb.assign(nu + 1, -1);
     for (int k = nu - 1; k >= 0; --k) {
@@ -184,6 +188,13 @@ struct BlockPlan {
     for (size_t k = 0; k < outer.size(); ++k)
       if (outer[k] == member) return (int)k;
     return -1;
+  }
+  // Loop level at which looped member p's own factor can be formed: the deepest of its own and its parents'.  Its own level,
+  // while loops run parents first; in the outer-leaf plan the outermost member's factor waits for its parents' digits.
+  int factor_pos(int p) const {
+    int k = outer_pos(p);
+    if (m.mother[p] >= 0) k = std::max(k, std::max(outer_pos(m.mother[p]), outer_pos(m.father[p])));
+    return k;
   }
   int looped_tables() const {  // unrolled members with a looped parent
     return (int)std::count_if(wb.begin(), wb.end(), [](int b) { return b >= 0; });
@@ -482,8 +493,13 @@ class Emitter {
     const bool carried_l = inner && pre_ >= 2 && L_.l_in_lds;
     const bool early_acc = slot_read_ahead() && !carried_l;
     std::string f_expr = carried_l ? "lq_" : lk_g;
-    if (!folded(p))
+    if (!folded(p) && p_.factor_pos(p) == (int)k)
       f_expr = (inner && m_.mother[p] >= 0 ? carried_entry("tcx", t_index(p, "@", -1, -1, p, "@")) : t_tab(p) + "[" + t_index(p, g, -1, -1) + "]") + " * " + f_expr;
+    // (the outer-leaf plan) a member looped outside a parent of its own: its transmission entry joins the product here, where the
+    // last digit it mentions is known; its marginal slot is still added to where its own loop's step ends
+    for (size_t j = 0; j < k; ++j)
+      if (const int q = outer_[j]; m_.mother[q] >= 0 && p_.factor_pos(q) == (int)k)
+        f_expr = (inner ? carried_entry("tcx", t_index(q, "g" + num(q), -1, -1, p, "@")) : t_tab(q) + "[" + t_index(q, "g" + num(q), -1, -1) + "]") + " * " + f_expr;
     if (inner) o_ << prologue_;
     if (carried_l)  // this loop's own LDS reads, one step ahead: the member's likelihood, its marginal slot
       o_ << ind << "double lq_ = " << S_ << "[" << L_.lik_base + 3 * (int)k << "], aq_ = " << S_ << "[" << 3 * (int)k << "];\n";
@@ -1028,19 +1044,64 @@ int once_row_len(const BlockPlan &p, int bt) {
 }
 
 struct LaneForm {
-  bool once = false, late = false;
+  bool once = false, late = false, outer_leaf = false;
   Shape shape;  // of the form taken
   int row_len = 0;
   bool scalar_t = false;
   std::string body;                       // (empty where it was not asked for and the cost model did not need it)
   double fp64_parent = 0, fp64_once = 0;  // the cost model's counts (once: 0 where the form does not apply)
+  double fp64_outer = 0;                  // ... and the outer-leaf plan's (0 where it does not apply or was not asked for)
 };
+
+// The outer-leaf plan (lane variants 8-11): the once-per-site form cut elsewhere.  Where a founder f has one or two children, all
+// leaves and all by the same other parent r, the super-leaf table of {f, children} mentions one digit outside itself, r's.
+// With r the OUTERMOST loop the table is built three times per site instead of once per step; everything else is the
+// once-per-site form as it is.  r then encloses its own parents' loops: its factor joins the product at the innermost of their
+// levels (BlockPlan::factor_pos).  From the once-per-site form's shape `h`: r first in the loops, f and its children last in
+// the block, every other member where it was.  false: no such cut at f.
+bool outer_leaf_shape(const Model &m, const Shape &h, int f, Shape *out) {
+  const int N = m.n_members;
+  if (m.mother[f] >= 0) return false;
+  std::vector<int> kids;
+  int r = -1;
+  for (int i = 0; i < N; ++i) {
+    if (m.mother[i] < 0 || (m.mother[i] != f && m.father[i] != f)) continue;
+    const int other = m.mother[i] == f ? m.father[i] : m.mother[i];
+    if (r >= 0 && other != r) return false;
+    r = other;
+    kids.push_back(i);
+  }
+  if (kids.empty() || kids.size() > 2 || r == f) return false;
+  std::vector<char> leaf(N, 0), looped(N, 0);
+  leaf[f] = 1;
+  for (int c : kids) leaf[c] = 1;
+  for (int i = 0; i < N; ++i)
+    if (m.mother[i] >= 0 && (std::count(kids.begin(), kids.end(), m.mother[i]) || std::count(kids.begin(), kids.end(), m.father[i]))) return false;
+  Shape s;
+  s.N = N, s.loops_as_given = true;
+  s.outer.push_back(r);
+  for (int p : h.outer)
+    if (p != r && !leaf[p]) s.outer.push_back(p);
+  for (int p : h.unrolled)
+    if (p != r && !leaf[p]) s.unrolled.push_back(p);
+  s.unrolled.push_back(f);
+  s.unrolled.insert(s.unrolled.end(), kids.begin(), kids.end());
+  if (s.unrolled.size() > 7 || s.outer.size() < 2) return false;
+  for (int p : s.outer) looped[p] = 1;
+  for (int p : s.outer)  // a looped member's factor mentions loop digits only
+    if (m.mother[p] >= 0 && !(looped[m.mother[p]] && looped[m.father[p]])) return false;
+  s.upos.assign(N, -1);
+  for (size_t k = 0; k < s.unrolled.size(); ++k) s.upos[s.unrolled[k]] = (int)k;
+  *out = s;
+  return true;
+}
 
 // Shape, form, row length and body of the one-lane-per-site kernel (group_digits = 0) for the block shape `s`.
 // may_once (variants 4-7, not the call path: that form keeps the per-prefix text, and its posteriors differ from the
 // once-per-site form's in their last bits): the once-per-site form (OnceEmitter) where it applies, fits four workgroups
 // per CU and executes fewer fp64 statements per site than the per-prefix form; FAMSEQ_LANE_HOIST=0 (tuning aid) keeps the latter.
-LaneForm lane_form(const Model &m, const Shape &s, bool call_mode, bool may_once, bool need_body = true) {
+// may_outer (variants 8-11): beyond that, the outer-leaf plan where it applies and the cost model takes it (below).
+LaneForm lane_form(const Model &m, const Shape &s, bool call_mode, bool may_once, bool need_body = true, bool may_outer = false) {
   LaneForm f;
   f.shape = s;
   if (s.unrolled.empty()) return f;
@@ -1097,6 +1158,30 @@ LaneForm lane_form(const Model &m, const Shape &s, bool call_mode, bool may_once
   f.fp64_once = fp64_statements(body);
   if (f.fp64_once >= f.fp64_parent) return f;
   f.once = true, f.shape = h, f.row_len = hrow, f.body = std::move(body);
+  if (!may_outer || env_int("FAMSEQ_LANE_OUTER", 1) == 0) return f;  // (the variable: a tuning aid; 0 keeps the once-per-site text)
+  // The outer-leaf plan: every founder that allows the cut is a candidate; the lowest count wins, on a tie the lowest founder.
+  // Taken only where it executes at least 1 % fewer fp64 statements than the once-per-site form: below that a second text,
+  // with last bits of its own, is not worth having (a condition, not a prediction).
+  LaneForm best;
+  for (int fo = 0; fo < m.n_members; ++fo) {
+    Shape c;
+    if (!outer_leaf_shape(m, h, fo, &c)) continue;
+    const BlockPlan cplan(m, c);
+    // the super-leaf is the founder and its children, and its table mentions the outermost loop digit and no other
+    if (!cplan.once_applies() || cplan.qb[cplan.np()] != 0 || cplan.s.unrolled[cplan.np()] != fo) continue;
+    const int crow = once_row_len(cplan, bt);
+    if (crow == 0) continue;
+    const RowLayout clayout = row_layout(cplan, crow, true);
+    if (!clayout.fits) continue;
+    std::string cbody = OnceEmitter(cplan, clayout, f.scalar_t, prefetch).body();
+    const double count = fp64_statements(cbody);
+    if (best.fp64_outer > 0 && count >= best.fp64_outer) continue;
+    best.fp64_outer = count, best.shape = c, best.row_len = crow, best.body = std::move(cbody);
+  }
+  if (best.fp64_outer <= 0) return f;
+  f.fp64_outer = best.fp64_outer;
+  if (best.fp64_outer > 0.99 * f.fp64_once) return f;
+  f.outer_leaf = true, f.shape = best.shape, f.row_len = best.row_len, f.body = std::move(best.body);
   return f;
 }
 
@@ -1107,6 +1192,7 @@ Shape variant_shape(const Model &m, const LaneVariant &v) { return choose_shape(
 LaneVariant enumgen_variant(int variant, int group_digits) {
   LaneVariant v;
   v.once = variant >= 4 && group_digits == 0;
+  v.outer_leaf = variant >= 8 && group_digits == 0;
   v.plain = variant < 0 ? variant : variant & 3;
   v.cap = group_digits == 0 && (v.plain == 0 || v.plain == 1) ? 7 : 6;
   v.fence_single = v.plain > 0 && (v.plain & 1);
@@ -1115,7 +1201,7 @@ LaneVariant enumgen_variant(int variant, int group_digits) {
 
 std::string enumgen_describe(const Model &m, int variant) {
   const LaneVariant v = enumgen_variant(variant);
-  const LaneForm f = lane_form(m, variant_shape(m, v), false, v.once, /*need_body=*/false);
+  const LaneForm f = lane_form(m, variant_shape(m, v), false, v.once, /*need_body=*/false, v.outer_leaf);
   std::string d = "looped members [";
   for (size_t k = 0; k < f.shape.outer.size(); ++k) d += (k ? " " : "") + num(f.shape.outer[k]);
   d += "], unrolled block [";
@@ -1125,6 +1211,12 @@ std::string enumgen_describe(const Model &m, int variant) {
     char buf[160];
     std::snprintf(buf, sizeof buf, ", prefix tables and marginals once per site (%.0f fp64 statements per site against %.0f)", f.fp64_once,
                   f.fp64_parent);
+    d += buf;
+  }
+  if (f.outer_leaf) {
+    char buf[200];
+    std::snprintf(buf, sizeof buf, "; outer-leaf plan: the super-leaf table once per step of member %d's loop (%.0f fp64 statements per site against %.0f)",
+                  f.shape.outer[0], f.fp64_outer, f.fp64_once);
     d += buf;
   }
   return d;
@@ -1234,9 +1326,15 @@ bool enumgen_has_once_form(const Model &m) {
   return false;
 }
 
+bool enumgen_has_outer_leaf(const Model &m, int variant) {
+  const LaneVariant v = enumgen_variant(8 + (variant & 3));
+  return lane_form(m, variant_shape(m, v), false, true, /*need_body=*/false, true).outer_leaf;
+}
+
 std::string enumgen_source(const Model &m, int variant_asked, int group_digits, bool call_mode, bool call_ct_out) {
   // variants 4-7: variants 0-3 with the block's prefix levels in the once-per-site form, where the cost model takes it (lane_form);
-  // where it does not — and in the lanes-per-site forms — they are the text of 0-3
+  // where it does not — and in the lanes-per-site forms — they are the text of 0-3; variants 8-11: 4-7 in the outer-leaf plan
+  // under the same rule
   const LaneVariant v = enumgen_variant(variant_asked, group_digits);
   const Shape s = variant_shape(m, v);
   if (s.unrolled.empty()) throw std::runtime_error("enumeration codegen: empty unrolled set");
@@ -1258,12 +1356,13 @@ std::string enumgen_source(const Model &m, int variant_asked, int group_digits, 
     const std::string body = PrefixEmitter(plan, layout, false, false, 0).body();
     return grouped_shell(m, what, body, reduce_body(), bt, min_waves, v.fence_single, row_len, group);
   }
-  LaneForm f = lane_form(m, s, call_mode, v.once && !call_mode);
+  LaneForm f = lane_form(m, s, call_mode, v.once && !call_mode, true, v.outer_leaf && !call_mode);
   ShellOptions o;
   o.entry = "famseq_enum_lane";
   o.comment = "3^N enumeration, lane per site, " + std::to_string(f.shape.outer.size()) + " looped + " + std::to_string(f.shape.unrolled.size()) +
-              " unrolled members, variant " + std::to_string(f.once ? variant_asked : v.plain);
+              " unrolled members, variant " + std::to_string(f.outer_leaf ? variant_asked : f.once ? 4 + v.plain : v.plain);
   if (f.once) o.comment += ", prefix tables and marginals once per site";
+  if (f.outer_leaf) o.comment += ", super-leaf table once per step of the outermost loop (member " + std::to_string(f.shape.outer[0]) + ")";
   if (f.shape.unrolled.size() > s.unrolled.size()) o.comment += " (looped member " + std::to_string(f.shape.unrolled[0]) + " unrolled ahead of the block)";
   if (call_mode) o.comment += ", call path";
   if (f.late) o.comment += ", compute-first shell";

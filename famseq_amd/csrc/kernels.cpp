@@ -63,6 +63,11 @@ struct KernelSpec {
 
 }  // namespace
 
+int64_t bulk_min_sites(const famseq_ctx *c) {
+  if (c->bulk_min_sites != -2) return c->bulk_min_sites;
+  return int64_t(16) * 64 * 4 * (c->n_cus > 0 ? c->n_cus : 256);  // (a plan-only context has no device: MI355X's 256 CUs)
+}
+
 // 4 where the pedigree's lane kernel has the once-per-site form (variants 4-7 differ from 0-3), else 0.  Generating the
 // candidates to find out costs milliseconds, so it is done once per context; a generator that throws means "no such form".
 int lane_first_variant(const famseq_ctx *c) {
@@ -101,7 +106,8 @@ KernelSpec kernel_spec(const famseq_ctx *c, int kind) {
     // (one lane per site: the contest starts at the once-per-site variants where the pedigree has that form; elsewhere 4-7 are
     // the texts of 0-3 again, reached only when all of those spill, and then cache hits)
     const bool once = d == 0 && lane_first_variant(c) == 4;
-    return {[&m, d](int v) { return enumgen_source(m, v, d); }, kEnumVariants, once ? 4 : 0, d == 0, "famseq_enum_lane",
+    // (a pick may name any of kEnumVariants; the contest ranges over the first kEnumContestVariants)
+    return {[&m, d](int v) { return enumgen_source(m, v, d); }, kEnumContestVariants, once ? 4 : 0, d == 0, "famseq_enum_lane",
             enumgen_block_threads(m, d)};
   }
   if (const SideKind k = side_of(kind); k.p) {
@@ -140,6 +146,30 @@ bool have(const famseq_ctx *c, const GenKernel &g) { return g.k.fn || (c->plan_o
 int load_kernel(famseq_ctx *c, int kind, std::string *why) {
   GenKernel &g = c->kern[kind];
   if (have(c, g)) return 0;
+  if (kind == K_LANE_BULK) {  // one text, no pick, no contest: K_LANE's block shape and fencing in the outer-leaf plan
+    try {
+      const int variant = 8 + (c->kern[K_LANE].variant & 3);
+      const std::string src = enumgen_source(c->model, variant, 0);
+      int scratch = -1;
+      const std::string path = jit_compile(src, &scratch);
+      if (scratch > 0) throw std::runtime_error("the bulk form spills " + std::to_string(scratch) + " bytes per lane");
+      g.variant = variant;
+      if (c->plan_only()) {
+        g.k.path = path;
+        return 0;
+      }
+      if (hipSetDevice(c->device) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
+      g.k = jit_load(src, "famseq_enum_lane");
+      g.block_threads = enumgen_block_threads(c->model, 0);
+    } catch (const std::exception &e) {
+      *why = e.what();
+      return FAMSEQ_E_HIP;
+    }
+    int nb = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, g.k.fn, g.block_threads, 0) != hipSuccess) nb = 1;
+    g.blocks_per_cu = std::max(nb, 1);
+    return 0;
+  }
   try {
     const KernelSpec s = kernel_spec(c, kind);
     // a measured pick (the autotuner's note, or the table build() ships) is loaded as it is: the spill contest is
@@ -147,7 +177,7 @@ int load_kernel(famseq_ctx *c, int kind, std::string *why) {
     const std::function<std::string(int)> &chooser = s.variant_of ? s.variant_of : s.source;
     const int pick = s.honours_pick ? jit_read_pick(chooser(0)) : -1;
     std::string src;
-    if (pick >= 0 && pick < s.n_variants) {
+    if (pick >= 0 && pick < (is_lane(kind) ? kEnumVariants : s.n_variants)) {
       src = s.source(pick);
       g.variant = pick;
     } else if (s.variant_of) {
@@ -195,7 +225,7 @@ bool load_or_remember(famseq_ctx *c, int kind) {
   if (g.failed) return false;
   if (have(c, g)) return true;
   std::string why;
-  if (kind == K_LANE_CALL && !load_or_remember(c, K_LANE)) {  // its block shape and fencing are the plain kernel's
+  if ((kind == K_LANE_CALL || kind == K_LANE_BULK) && !load_or_remember(c, K_LANE)) {  // its block shape and fencing are the plain kernel's
     why = "the plain lane kernel is unavailable: " + c->kern[K_LANE].error;
   } else {
     const int rc = load_kernel(c, kind, &why);
@@ -206,7 +236,12 @@ bool load_or_remember(famseq_ctx *c, int kind) {
   g.failed = true;
   const bool quiet = std::getenv("FAMSEQ_QUIET") != nullptr;  // else said once per ctx and kernel, where a user of the CLI or of the
                                                               // library sees it (also in famseq_plan_json)
-  if (is_lane(kind)) {
+  if (kind == K_LANE_BULK) {  // K_LANE serves instead: same results to the project's tolerance, the super-leaf table rebuilt per step
+    g.error = why;
+    if (!quiet)
+      std::fprintf(stderr, "famseq: the large-batch form of the per-pedigree enumeration kernel is unavailable (%s); the plain form serves every batch\n",
+                   why.substr(0, 300).c_str());
+  } else if (is_lane(kind)) {
     const int d = kind - K_LANE;
     std::string &lane_error = c->kern[K_LANE].error;
     if (d == 0 || lane_error.empty()) lane_error = why;
@@ -235,6 +270,10 @@ void drop_lane_kernels(famseq_ctx *c) {
   c->kern[K_LANE].drop();
   c->kern[K_LANE_CALL].drop();
   c->lane_reads_rows = -1;
+  GenKernel &bulk = c->kern[K_LANE_BULK];  // (its text follows K_LANE's variant: a verdict on the old one says nothing of the new)
+  bulk.drop();
+  bulk.failed = false, bulk.error.clear();
+  c->bulk_differs = -1;
 }
 
 namespace {
@@ -263,6 +302,35 @@ int pick_group_digits(const famseq_ctx *c, int64_t n_sites) {
   return best;
 }
 
+// Is a call of n_sites a bulk call: the context free to choose, the call at or above the threshold, the pedigree one that has the
+// form?  Such a call runs one lane per site whatever the cost model of small batches says (at the default threshold it says
+// so anyway; a lower threshold is its owner's word that the bulk form serves from there on).
+bool bulk_wanted(famseq_ctx *c, int64_t n_sites) {
+  const int64_t min_sites = bulk_min_sites(c);
+  if (c->enum_impl >= 0 || c->group_digits >= 0 || min_sites < 0 || n_sites < min_sites) return false;
+  if (c->bulk_any < 0) {
+    try {
+      c->bulk_any = enumgen_has_outer_leaf(c->model, 4) || enumgen_has_outer_leaf(c->model, 6) ? 1 : 0;
+    } catch (const std::exception &) {
+      c->bulk_any = 0;
+    }
+  }
+  return c->bulk_any == 1;
+}
+
+// Does the bulk slot serve a one-lane-per-site launch that belongs to a call of n_sites?  (K_LANE is loaded: its variant is known.)
+bool bulk_serves(famseq_ctx *c, int64_t n_sites) {
+  if (!bulk_wanted(c, n_sites)) return false;
+  if (c->bulk_differs < 0) {
+    try {
+      c->bulk_differs = enumgen_has_outer_leaf(c->model, c->kern[K_LANE].variant) ? 1 : 0;
+    } catch (const std::exception &) {
+      c->bulk_differs = 0;
+    }
+  }
+  return c->bulk_differs == 1 && load_or_remember(c, K_LANE_BULK);
+}
+
 // Can the generated kernel with 3^d lanes per site run without a compilation (loaded, or its code object on disk)?
 bool generated_ready(famseq_ctx *c, int d) {
   if (c->lanes(d).k.fn) return true;
@@ -288,6 +356,15 @@ int grid_for(const famseq_ctx *c, int64_t n_sites) {
 
 }  // namespace
 
+void bulk_prebuild(famseq_ctx *c) {
+  if (c->plan_only() && !c->kern[K_LANE].k.path.empty() && bulk_min_sites(c) >= 0) {
+    const int impl = c->enum_impl, digits = c->group_digits;
+    c->enum_impl = c->group_digits = -1;  // (what a context that is free to choose would load)
+    (void)bulk_serves(c, bulk_min_sites(c));
+    c->enum_impl = impl, c->group_digits = digits;
+  }
+}
+
 // The generated kernels share one argument list; what the third and fourth are depends on the kind (posterior and single
 // posterior rows, joint and de novo posteriors, MAP genotypes and their posterior, log10 likelihood and hom-ref posterior, leave-one-out rows and fit, pattern
 // posteriors and log10 likelihood, drawn configurations and their posteriors, allele frequency and its two log10 likelihoods), so they pass through untyped; so does what some kinds take behind the eighth (MoreArgs).
@@ -306,20 +383,28 @@ hipError_t launch_generated(famseq_ctx *c, const GenKernel &g, int64_t n_sites, 
 }
 
 hipError_t launch_engine(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint8_t *d_flags, double *d_post, double *d_single,
-                         uint8_t *d_status, hipStream_t stream) {
+                         uint8_t *d_status, hipStream_t stream, int64_t call_sites) {
   if (c->engine == FAMSEQ_ENGINE_ELIM)
     return launch_generated(c, c->kern[K_ELIM], n_sites, d_lk, d_flags, d_post, d_single, d_status, stream);
-  const bool want_lane = c->enum_impl == 1 || (c->enum_impl < 0 && (n_sites >= c->lane_min_sites ||
-                                                                    generated_ready(c, pick_group_digits(c, n_sites))));
+  const int64_t whole = call_sites > 0 ? call_sites : n_sites;
+  const bool bulk = bulk_wanted(c, whole);  // (every chunk of such a call, a short last one too)
+  const bool want_lane = c->enum_impl == 1 || bulk || (c->enum_impl < 0 && (n_sites >= c->lane_min_sites ||
+                                                                            generated_ready(c, pick_group_digits(c, n_sites))));
   if (want_lane) {
-    int d = pick_group_digits(c, n_sites);
+    int d = bulk ? 0 : pick_group_digits(c, n_sites);
     if (d > 0 && !load_or_remember(c, K_LANE + d)) d = 0;  // that group size does not build: one lane per site before the compiled-in kernel
     if (load_or_remember(c, K_LANE + d)) {
       c->last_group_digits = d;
+      if (d == 0 && bulk_serves(c, whole)) {
+        c->last_kind = "bulk";
+        return launch_generated(c, c->kern[K_LANE_BULK], n_sites, d_lk, d_flags, d_post, d_single, d_status, stream);
+      }
+      c->last_kind = d > 0 ? "group" : "lane";
       return launch_generated(c, c->lanes(d), n_sites, d_lk, d_flags, d_post, d_single, d_status, stream,
                               d > 0 ? enumgen_sites_per_chunk(c->model, d) : 0);
     }
   }
+  c->last_kind = "team";
   return launch_bn_enum(c->plan, c->kp, grid_for(c, n_sites), c->d_img.as<uint32_t>(), c->d_tc.as<double>(), n_sites, d_lk, d_flags, d_post,
                         d_single, d_status, stream);
 }

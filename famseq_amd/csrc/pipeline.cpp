@@ -198,7 +198,7 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
         HIP_TRY(c, launch_generated(c, c->kern[K_PRIOR], n, d_lk, d_flags, d_post, need_single ? d_single : nullptr, d_status, s_k, 0,
                                     {&d_prior}));
       else
-        HIP_TRY(c, launch_engine(c, n, d_lk, d_flags, d_post, need_single ? d_single : nullptr, d_status, s_k));
+        HIP_TRY(c, launch_engine(c, n, d_lk, d_flags, d_post, need_single ? d_single : nullptr, d_status, s_k, n_sites));
       if (called)
         HIP_TRY(c, launch_phred_call(d_post, d_single, d_status, c->d_seq.as<int32_t>(), N, n_seq, n, d_gpp, d_fpp, d[B_FGT].as<int8_t>(), s_k));
     }

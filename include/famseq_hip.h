@@ -144,6 +144,12 @@ const char *famseq_last_error(famseq_ctx *ctx);
  *                   says otherwise; -1 (default) = the generated kernel, lanes per site chosen by batch size,
  *                   for batches of >= "lane_min_sites" (256) sites when it can be built, the team kernel
  *                   otherwise (tiny calls never wait for a compile)
+ *   "bulk_min_sites"  from how many sites on a one-lane-per-site launch of a context that is free to choose ("enum_impl" -1,
+ *                   "group_digits" -1) is served by the large-batch form of the generated kernel (lane variants 8-11: the
+ *                   super-leaf table built once per step of the outermost loop), where the pedigree has one; its posteriors
+ *                   differ from the plain form's in their last bits.  Default: 16 chunks per resident wave (1,048,576 on
+ *                   MI355X); -1 = never.  A host entry decides once per call, from the call's size; famseq_plan_json
+ *                   "enum_last_kind" says which kernel served the last launch
  *   "tune"          1 = time the candidates of this pedigree's generated kernels on this device (where a static rule
  *                   picks a variant: the enumeration kernel's 7- or 6-member unrolled block, the sum-product kernel's
  *                   fence variant and where it keeps the likelihoods) on synthetic rows, a few milliseconds each, and keep the winners' indices as notes
