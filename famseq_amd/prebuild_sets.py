@@ -23,6 +23,48 @@ SIDE_PRODUCTS = (("trio", 3, True), ("map", 1, True), ("evidence", 1, True), ("l
 SIDE_PRODUCTS_SINCE = (("mutrate", 1, True),)
 
 
+# The pedigrees on which the lane kernel's variants 4-11 (csrc/enum_codegen.h: 4-7 the once-per-site form, 8-11 the outer-leaf
+# plan) are texts of their own, at mutation rate 0: the forced-variant matrices (tests/test_gpu_variants.py and its host twin in
+# tests/test_generated_host.py) run them beside their own pedigrees, on most of which 4-11 are the text of 0-3.
+# name -> (distinct texts among variants 0-11, which of 4 != 0, 6 != 2, 8 != 4, 10 != 6 hold); tests/test_lane_form_pedigrees.py
+# pins both from plan-only contexts, so that a generator change which makes one decline a form is seen.
+#   ped10       10 members, 10 sequenced   the benchmark shape
+#   random1025   9 /  7                    outer-leaf plan with unsequenced members in and beside the super-leaf
+#   random188    7 /  5                    blocks of five unrolled members, two loop digits
+#   random3796   9 /  6                    a second nine-member cut
+#   soak26      10 /  6                    a marriage loop, the seven-member block; no outer-leaf text
+#   soak33       8 /  6                    a six-member block, prefix tables of two members rebuilt per step
+#   random1      8 /  5                    the once-per-site form taken for the six-member block only
+#   grown11     11 / 10                    the once-per-site form above ten members
+#   grown13     13 / 11                    six looped members ahead of a seven-member block
+LANE_FORM_PEDIGREES = {
+    "ped10": (12, (True, True, True, True)),
+    "random1025": (12, (True, True, True, True)),
+    "random188": (12, (True, True, True, True)),
+    "random3796": (12, (True, True, True, True)),
+    "soak26": (8, (True, True, False, False)),
+    "soak33": (8, (True, True, False, False)),
+    "random1": (6, (False, True, False, False)),
+    "grown11": (8, (True, True, False, False)),
+    "grown13": (8, (True, True, False, False)),
+}
+GROWN_SEEDS = {11: 32109, 13: 32319}  # grown<n>: RandomState seeds found by a scan of grown pedigrees of n members that take the form
+
+
+def lane_form_pedigree(name):
+    """A pedigree of LANE_FORM_PEDIGREES (the matrices run every one at mutation rate 0): a side_variant_pedigree name,
+    soak<seed> (soak_pedigree's pedigree, not its mutation rate) or grown<n>."""
+    if name.startswith("soak"):
+        ped = soak_pedigree(int(name[4:]))[1]
+    elif name.startswith("grown"):
+        n = int(name[5:])
+        ped = grow_pedigree(np.random.RandomState(GROWN_SEEDS[n]), n, allow_loops=False)
+    else:
+        return side_variant_pedigree(name)
+    ped.relations()
+    return ped
+
+
 def soak_pedigree(seed, max_n=10):
     """-> (rng positioned after the pedigree draw, pedigree, mutation rate)."""
     rng = np.random.RandomState(9000 + seed)

@@ -10,6 +10,7 @@ import pytest
 
 import famseq_amd as fs
 import oracle
+import _variants as V
 from test_gpu_enum_once import check, resident
 
 pytestmark = pytest.mark.gpu
@@ -182,3 +183,85 @@ def test_the_default_threshold_on_resident_arrays(ped10):
     assert torch.equal(d_st, d_st[:320][idx])
     # ... and the first 320 rows are the oracle's
     check((d_post[:320].cpu().numpy(), d_single[:320].cpu().numpy(), d_st[:320].cpu().numpy()), tuple(x[:320] for x in ref0), "default threshold")
+
+
+# ---- the bulk slot on pedigrees other than the ten-member one ----------------------------------------------------------------
+
+_OTHER = {}
+
+
+def other(name):
+    """(pedigree, lk, flags, has_bn_fail, oracle's answer) for UNIQUE sites of the variant matrices' batch (tests/_variants.py:
+    every flag combination in every wave, the planted shortcut, failure, -LRC and tiny-row-sum sites), mutation rate 0."""
+    if name not in _OTHER:
+        ped = V.pedigree(name)
+        lk, flags, has_bn_fail = V.variant_batch(ped, UNIQUE, seed=len(name))
+        _OTHER[name] = (ped, lk, flags, has_bn_fail, V.reference(ped, lk, flags))
+    return _OTHER[name]
+
+
+@pytest.fixture
+def own_cache(tmp_path, monkeypatch):
+    """A kernel cache of the test's own: the lane picks below are notes that no other context may start from.  (Such a
+    context consults that directory only, so the two or three kernels of a test are compiled where it runs.)"""
+    monkeypatch.setenv("FAMSEQ_KERNEL_CACHE", str(tmp_path))
+
+
+@pytest.mark.parametrize("pick", [4, 5, 6, 7])
+@pytest.mark.parametrize("name", ["random1025", "random188"])
+def test_the_bulk_slot_follows_the_lane_pick_on_other_pedigrees(name, pick, own_cache):
+    """Nine members of which two carry no reads (in and beside the super-leaf) and seven members with a five-member block, under
+    each lane pick of the once-per-site form: bulk_min_sites = 320 on a context with default options otherwise sends 319 sites
+    wherever the batch size does, 320 and 383 to the bulk object, which is variant 8 + (pick & 3); the lane slot keeps the pick.
+    Outputs against the oracle; the resident call and a host call in chunks below the threshold the host call's bits."""
+    ped, lk, flags, has_bn_fail, ref = other(name)
+    ctx = fs.Context(fs.make_model(ped, mrate=V.MRATE))
+    try:
+        ctx.set_option("pick_lane", pick)
+        ctx.set_option("bulk_min_sites", 320)
+        for n, bulk in ((319, False), (320, True), (383, True)):
+            got = ctx.bn_batch(lk[:n], flags[:n])
+            plan = ctx.plan()
+            assert (plan["enum_last_kind"] == "bulk") == bulk, (n, plan["enum_last_kind"])
+            V.check_against_reference(*got, tuple(x[:n] for x in ref), has_bn_fail, what="%s, lane pick %d: %d sites, threshold 320" % (name, pick, n))
+            again = resident(ctx, lk[:n], flags[:n])
+            assert (ctx.plan()["enum_last_kind"] == "bulk") == bulk, n
+            assert V.same_bits(got, again), n
+            if bulk:
+                assert plan["enum_group_digits_last"] == 0 and plan["enum_bulk_variant"] == 8 + (plan["enum_lane_variant"] & 3) and plan["enum_bulk_failed"] == 0
+                assert plan["enum_lane_variant"] == pick and plan["enum_bulk_min_sites"] == 320
+                assert plan["enum_bulk_code_object"].endswith(".hsaco") and plan["enum_bulk_code_object"] != plan["enum_lane_code_object"]
+                assert OUTER in plan["enum_bulk_shape"] and OUTER not in plan["enum_lane_shape"] and V.ONCE in plan["enum_lane_shape"]
+                ctx.set_option("chunk_sites", 100)  # chunks of 100 sites and a short last one, each below the threshold
+                chunked = ctx.bn_batch(lk[:n], flags[:n])
+                assert ctx.plan()["enum_last_kind"] == "bulk"
+                ctx.set_option("chunk_sites", 0)
+                assert V.same_bits(again, chunked), n
+                print("served by the bulk object: %s, members %d, lane pick %d, bulk variant %d, %d sites" % (name, ped.n, pick, plan["enum_bulk_variant"], n))
+    finally:
+        ctx.close()
+
+
+def test_a_pedigree_without_the_cut_is_never_served_by_a_bulk_object(own_cache):
+    """soak26 (a marriage loop; the once-per-site form, no outer-leaf text) with default options and a lowered threshold: at
+    and above it a host call goes wherever the batch size sends it, and a resident call of one site per lane of a chip at
+    one wave per SIMD — where the cost model of small batches takes one lane per site for every pedigree — runs on the lane
+    kernel; there is no bulk object.  (The large batch repeats the UNIQUE sites by index, each row the oracle's for its site.)"""
+    ped, lk, flags, has_bn_fail, ref = other("soak26")
+    ctx = fs.Context(fs.make_model(ped, mrate=V.MRATE))
+    try:
+        ctx.set_option("bulk_min_sites", 320)
+        for n in (320, 383):
+            got = ctx.bn_batch(lk[:n], flags[:n])
+            plan = ctx.plan()
+            assert plan["enum_last_kind"] in ("lane", "group", "team") and plan["enum_bulk_code_object"] == "" and plan["enum_bulk_variant"] == -1, (n, plan["enum_last_kind"])
+            V.check_against_reference(*got, tuple(x[:n] for x in ref), has_bn_fail, what="soak26: %d sites" % n)
+            assert V.same_bits(got, resident(ctx, lk[:n], flags[:n])), n
+        idx = np.arange(plan["cus"] * 256) % UNIQUE
+        got = resident(ctx, np.ascontiguousarray(lk[idx]), np.ascontiguousarray(flags[idx]))
+        plan = ctx.plan()
+        assert plan["enum_last_kind"] == "lane" and plan["enum_group_digits_last"] == 0 and plan["enum_bulk_code_object"] == "" and plan["enum_bulk_failed"] == 0
+        assert V.ONCE in plan["enum_lane_shape"] and OUTER not in plan["enum_lane_shape"]
+        V.check_against_reference(*got, tuple(x[idx] for x in ref), has_bn_fail, what="soak26: %d sites" % len(idx))
+    finally:
+        ctx.close()

@@ -7,6 +7,9 @@ $FAMSEQ_VARIANT_ONLY — the plan is checked to name it, and its outputs go agai
 variants of the same family, which must agree bit for bit (see tests/test_generated_host.py, the host twin, for why).
 The site-prior kernel famseq_elim_prior has no contest of its own — it runs in the variant famseq_elim takes — and is moved
 with it through pick_elim, all twelve.  (The side products' fence levels: tests/test_gpu_side_variants.py.)
+The lane kernel's twelve variants are three forms of four (per-prefix text, once per site, outer-leaf plan); the later two are
+texts of their own on some pedigrees only, so the lane family also runs on V.LANE_PEDIGREES (famseq_amd/prebuild_sets.py
+LANE_FORM_PEDIGREES), a form to a test, and a variant whose code object has a lower variant's name is checked by that name.
 
 Pick notes are written into a private kernel cache of this session: the in-tree cache and the per-user one, from which the
 rest of the suite and bench.py load, never see them."""
@@ -19,7 +22,8 @@ import famseq_amd as fs
 
 pytestmark = pytest.mark.gpu
 
-VARIANTS = dict(lane=4, elim=12, lane_call=4, elim_call=8)
+VARIANTS = dict(lane=V.LANE_VARIANTS, elim=12, lane_call=4, elim_call=8)
+ORACLE_SITES = 128  # distinct sites of the grown pedigrees (eleven and thirteen members: 3^11 and 3^13 configurations per site in the oracle)
 # One launch per call (chunk_sites: the host would otherwise split a call into launches of 256 sites) on a grid of 2
 # workgroups: at 1600 sites every workgroup wraps its persistent loop at least three times, for every workgroup size the
 # generated kernels use (BT <= 256), so what carries from one iteration to the next (LDS reuse after the stage-out, the
@@ -49,8 +53,16 @@ _REF = {}
 def batch(name):
     if name not in _REF:
         ped = V.pedigree(name)
-        lk, flags, has_bn_fail = V.variant_batch(ped, N_SITES, seed=len(name))
-        _REF[name] = (ped, lk, flags, has_bn_fail, V.reference(ped, lk, flags))
+        if name.startswith("grown"):
+            # the oracle answers ORACLE_SITES distinct sites (every planted one among them) and the batch repeats them by index:
+            # every output row is compared with the oracle's row for its site (waves 64..127 of each repeat stay uniform in chrX)
+            lk, flags, has_bn_fail = V.variant_batch(ped, ORACLE_SITES, seed=len(name))
+            idx = np.arange(N_SITES) % ORACLE_SITES
+            ref = tuple(np.ascontiguousarray(x[idx]) for x in V.reference(ped, lk, flags))
+            _REF[name] = (ped, np.ascontiguousarray(lk[idx]), np.ascontiguousarray(flags[idx]), has_bn_fail, ref)
+        else:
+            lk, flags, has_bn_fail = V.variant_batch(ped, N_SITES, seed=len(name))
+            _REF[name] = (ped, lk, flags, has_bn_fail, V.reference(ped, lk, flags))
     return _REF[name]
 
 
@@ -144,7 +156,7 @@ def lane_bases(ped, monkeypatch):
     return [0] if shapes[0] == shapes[1] else [0, 2]
 
 
-def plain_runs(name, family, variants, monkeypatch):
+def plain_runs(name, family, variants, monkeypatch, also=None):
     ped, lk, flags, has_bn_fail, ref = batch(name)
     runs = {}
     for v in variants:
@@ -156,16 +168,48 @@ def plain_runs(name, family, variants, monkeypatch):
             for s in sizes(bt):  # the same context again, ragged around its chunk of sites (one launch each)
                 out = run(ctx, family, seq, lk[:s], flags[:s])
                 assert V.same_bits(out, tuple(x[:s] for x in runs[v])), (name, family, v, s)
+            if also:
+                also(ctx, v, runs[v])
         finally:
             ctx.close()
     return runs
 
 
-@pytest.mark.parametrize("family", ["lane", "elim"])
-@pytest.mark.parametrize("name", V.PEDIGREES)
-def test_every_plain_variant(name, family, monkeypatch):
+# every plain family on V.PEDIGREES; the lane family also on the pedigrees that take its once-per-site form and outer-leaf plan
+PLAIN = [(n, f) for n in V.PEDIGREES for f in ("lane", "elim")] + [(n, "lane") for n in V.LANE_PEDIGREES[len(V.PEDIGREES):]]
+_LANE_RUNS = {}  # name -> {lane variant: its outputs}: what a later form of the same pedigree is compared with
+
+
+def lane_plan_checks(name, names, shapes):
+    """plain_runs' `also` for a lane variant, on the loaded context: the code object is the text the plan-only context named, the
+    plan's description carries the once-per-site and the outer-leaf phrase exactly where that text is the form's own, and one
+    call through the resident entry (famseq_bn_batch_device on arrays that live on the device) gives the host entry's bits."""
+    import os
+
+    from test_gpu_enum_once import resident
+
+    _, lk, flags, _, _ = batch(name)
+
+    def check(ctx, v, out):
+        plan = ctx.plan()
+        assert plan["enum_lane_variant"] == v and os.path.basename(plan["enum_lane_code_object"]) == names[v] + ".hsaco", (name, v)
+        once, outer = v >= 4 and names[v] != names[v & 3], v >= 8 and names[v] != names[v - 4]
+        assert plan["enum_lane_shape"] == shapes[v] and (V.ONCE in shapes[v]) == once and (V.OUTER in shapes[v]) == outer, (name, v, shapes[v])
+        assert V.same_bits(resident(ctx, lk, flags), out), "%s: lane variant %d, the resident entry" % (name, v)
+        assert ctx.plan()["enum_last_kind"] == "lane" and ctx.plan()["enum_group_digits_last"] == 0, (name, v)
+
+    return check
+
+
+@pytest.mark.parametrize("name,family", PLAIN)
+def test_every_plain_variant(name, family, tmp_path, monkeypatch):
+    """(the lane family: its variants 0-3, the per-prefix text; 4-11 in test_the_later_forms_of_the_lane_kernel)"""
     ped = batch(name)[0]
-    runs = plain_runs(name, family, range(VARIANTS[family]), monkeypatch)
+    also = None
+    if family == "lane":
+        names, shapes = V.lane_texts(ped, tmp_path, monkeypatch)
+        also = lane_plan_checks(name, names, shapes)
+    runs = plain_runs(name, family, range(4 if family == "lane" else VARIANTS[family]), monkeypatch, also)
     two_blocks = family == "lane" and lane_bases(ped, monkeypatch) == [0, 2]
     for v, out in runs.items():
         b = (v & 2) if two_blocks else 0
@@ -175,6 +219,42 @@ def test_every_plain_variant(name, family, monkeypatch):
         assert np.array_equal(a[2], c[2]) and np.array_equal(a[1].view(np.uint64), c[1].view(np.uint64))
         ok = (a[2] & 3) == 0
         np.testing.assert_allclose(a[0][ok], c[0][ok], rtol=1e-12, atol=0)
+    if family == "lane":
+        _LANE_RUNS.setdefault(name, {}).update(runs)
+
+
+@pytest.mark.parametrize("form", [1, 2], ids=["once-per-site", "outer-leaf"])
+@pytest.mark.parametrize("name", V.LANE_PEDIGREES)
+def test_the_later_forms_of_the_lane_kernel(name, form, tmp_path, monkeypatch):
+    """Lane variants 4-7 (the once-per-site form) and 8-11 (the outer-leaf plan), four to a test.  A variant whose code object
+    has the name of a lower variant's is that text (the name is a content hash): the equality is asserted and nothing is
+    loaded, which is all there is to do on most of V.PEDIGREES; tests/test_lane_form_pedigrees.py pins where the texts differ.
+    Every text of its own runs through plain_runs as variants 0-3 do — the oracle, one launch on a grid of 2 that wraps,
+    ragged sizes — and lane_plan_checks.  Within the form: a fencing pair the same bits, the two block shapes as variants 0
+    and 2 (V.check_lane_relations).  Between forms nothing is asserted; each is held to the oracle, their largest deviation
+    is printed.
+    A context with $FAMSEQ_KERNEL_CACHE set consults that directory only (csrc/jit.cpp jit_compile), so nothing build()
+    could pre-build would be found from the private cache: the up to four kernels of a test are compiled where it runs,
+    about a second each."""
+    ped = batch(name)[0]
+    names, shapes = V.lane_texts(ped, tmp_path, monkeypatch)
+    first = V.first_with_text(names)
+    if name in V.LANE_FORM_PEDIGREES:
+        assert (len(set(names)), V.form_relations(names)) == V.LANE_FORM_PEDIGREES[name], (name, names)
+    group = range(4 * form, 4 * form + 4)
+    own = [v for v in group if first[v] == v]
+    for v in group:
+        assert first[v] == v or (first[v] < 4 * form and names[v] == names[v - 4]), (name, v, names)
+    if not own:
+        return
+    have = _LANE_RUNS.setdefault(name, {})
+    also = lane_plan_checks(name, names, shapes)
+    have.update(plain_runs(name, "lane", own, monkeypatch, also))
+    # (a variant of this form that is a lower form's text, and the lower forms for the deviation: from their own tests where
+    # those ran in this session, else loaded here — from the private cache of the session where it holds them)
+    missing = sorted({first[v] for v in group} | {first[v & 3] for v in group} - set(have))
+    have.update(plain_runs(name, "lane", [v for v in missing if v not in have], monkeypatch))
+    V.check_lane_relations(name, names, have, shapes[0] != shapes[2], "device", forms=[form])
 
 
 def phred(p):
@@ -271,28 +351,71 @@ def test_the_site_prior_kernel_in_every_variant(name, v, monkeypatch):
     assert V.same_bits(plain, first[2]), "%s: famseq_elim, variant %d differs from variant %d" % (name, v, first[0])
 
 
-@pytest.mark.parametrize("name", ["ped10", "ped15:12"])
-def test_every_lanes_per_site_form(name, monkeypatch):
+def lanes_per_site_forms(name, digits=None, pick=None):
+    """The lanes-per-site kernels of `digits` (default: every one the pedigree has), each on a context of its own — under the
+    lane pick `pick`, if given — against the oracle; small sub-batches the bits of the slices."""
     ped, lk, flags, has_bn_fail, ref = batch(name)
     model = fs.make_model(ped, mrate=V.MRATE)
     ctx = fs.Context(model, device=0)
     dmax = ctx.plan()["enum_group_digits_max"]
     ctx.close()
     assert dmax >= 2
-    for d in range(1, dmax + 1):
+    for d in range(1, dmax + 1) if digits is None else sorted({min(d, dmax) for d in digits}):
         ctx = fs.Context(model, device=0)
         try:
             one_launch(ctx)
+            if pick is not None:
+                ctx.set_option("pick_lane", pick)
             ctx.set_option("enum_impl", 1)
             ctx.set_option("group_digits", d)
             out = ctx.bn_batch(lk, flags)
             assert ctx.plan()["enum_group_digits_last"] == d
+            assert pick is None or ctx.plan()["enum_lane_variant"] == pick
             V.check_against_reference(*out, ref, has_bn_fail, what="%s: lanes-per-site d = %d" % (name, d))
             for s in (1, 2, 3, 65):
                 assert V.same_bits(ctx.bn_batch(lk[:s], flags[:s]), tuple(x[:s] for x in out)), (name, d, s)
         finally:
             ctx.close()
-        print("loaded and confirmed by the plan: members %d, lanes-per-site d = %d" % (ped.n, d))
+        print("loaded and confirmed by the plan: members %d, lanes-per-site d = %d%s" % (ped.n, d, "" if pick is None else ", lane pick %d" % pick))
+
+
+@pytest.mark.parametrize("name", ["ped10", "ped15:12"])
+def test_every_lanes_per_site_form(name, monkeypatch):
+    lanes_per_site_forms(name)
+
+
+@pytest.mark.parametrize("name", ["random1025", "grown11"])
+def test_lanes_per_site_forms_beside_an_outer_leaf_pick(name, monkeypatch):
+    """The lanes-per-site forms switch the once-per-site form and the outer-leaf plan off (enumgen_variant(v, d > 0)): with
+    pick_lane = 8 in the cache, 3 lanes per site and the most lanes per site the pedigree has, against the oracle.  (That
+    their code objects are those of pick 2: tests/test_lane_form_pedigrees.py.)"""
+    lanes_per_site_forms(name, digits=(1, 99), pick=8)
+
+
+def test_the_call_path_under_an_outer_leaf_pick(monkeypatch):
+    """The call-path form keeps the per-prefix text (enumgen_call_variant): on random1025, whose variant 8 is the outer-leaf plan,
+    famseq_bn_call_batch under pick_lane = 8 gives the bits it gives under pick_lane = 0, each on a context of its own."""
+    ped, lk, flags, _, ref = batch("random1025")
+    outs = {}
+    for pick in (0, 8):
+        ctx = fs.Context(fs.make_model(ped, mrate=V.MRATE), device=0)
+        try:
+            one_launch(ctx)
+            ctx.set_option("pick_lane", pick)
+            ctx.set_option("enum_impl", 1)
+            ctx.set_option("group_digits", 0)
+            ctx.set_option("call_kernels", 2)
+            seq = np.nonzero(ped.sequenced)[0][::-1].astype(np.int32).copy()
+            outs[pick] = ctx.bn_call_batch(seq, lk=lk, flags=flags)
+            plan = ctx.plan()
+            assert plan["enum_lane_variant"] == pick and plan["enum_lane_call_code_object"].endswith(".hsaco")
+            assert (V.OUTER in plan["enum_lane_shape"]) == (pick == 8)
+            outs[pick, "object"] = plan["enum_lane_call_code_object"]
+        finally:
+            ctx.close()
+    assert outs[0, "object"] == outs[8, "object"]
+    assert np.array_equal(outs[0][3], ref[2]) and ((ref[2] & 3) == 0).sum() > len(flags) // 2
+    assert V.same_bits(outs[8], outs[0])
 
 
 @pytest.mark.parametrize("n", sorted(WIDE))
