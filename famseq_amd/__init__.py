@@ -92,6 +92,8 @@ ABI_SYMBOLS = [
     "famseq_relabel_batch", "famseq_relabel_batch_device", "famseq_relabel_prior_batch", "famseq_relabel_prior_batch_device",
     "famseq_rate_tables",
     "famseq_mutrate_batch", "famseq_mutrate_batch_device", "famseq_mutrate_prior_batch", "famseq_mutrate_prior_batch_device",
+    "famseq_allele_tables",
+    "famseq_origin_batch", "famseq_origin_batch_device", "famseq_origin_prior_batch", "famseq_origin_prior_batch_device",
 ]
 # (and famseq_philox4x32_10, the one name with digits in it: philox4x32 below)
 PL_MISSING = 0xFFFF
@@ -184,7 +186,7 @@ def lib():
     rates = ([dp, C.c_int32], [vp, C.c_int32])  # the host entries take the rates, the device entries the resident tables
     for name, out_a, more in (("trio", dp, ([], [])), ("map", C.POINTER(C.c_int8), ([], [])), ("evidence", dp, ([], [])), ("loo", dp, ([], [])),
                               ("pattern", dp, masks), ("sample", C.POINTER(C.c_int8), draws),
-                              ("relabel", dp, assigns), ("mutrate", dp, rates)):
+                              ("relabel", dp, assigns), ("mutrate", dp, rates), ("origin", dp, ([], []))):
         for prior in (0, 1):
             host = getattr(L, "famseq_%s%s_batch" % (name, "_prior" * prior))
             dev = getattr(L, "famseq_%s%s_batch_device" % (name, "_prior" * prior))
@@ -197,6 +199,8 @@ def lib():
     L.famseq_af_batch.restype = L.famseq_af_batch_device.restype = C.c_int
     L.famseq_rate_tables.argtypes = [C.c_void_p, dp, C.c_int32, dp]
     L.famseq_rate_tables.restype = C.c_int
+    L.famseq_allele_tables.argtypes = [C.c_void_p, dp]
+    L.famseq_allele_tables.restype = C.c_int
     u32p = C.POINTER(C.c_uint32)
     L.famseq_philox4x32_10.argtypes = [u32p, u32p, u32p]
     L.famseq_philox4x32_10.restype = None
@@ -305,6 +309,7 @@ def segregation_masks(n, affected, unaffected=(), model="dominant"):
 MAX_RELABEL = 64
 MAX_RATES = 32
 RATE_TABLE_DOUBLES = 432
+ALLELE_TABLE_DOUBLES = 48
 
 
 def swap_assignments(n, members=None):
@@ -773,6 +778,43 @@ class Context:
         self._side_device("mutrate", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_rate_loglik, d_loglik, d_status, stream,
                           (d_tables or None, int(n_rates)))
 
+    def allele_tables(self):
+        """The allele-level transmission rows origin_batch uses: -> [2 chrX, 2 child sex (0 son, 1 daughter), 2 parent (0 mother,
+        1 father), 2 allele, 3 parent's genotype] float64, for the mutation rate the model's tables were made with (plan()
+        ["origin_mrate"]).  FamseqError for a model with custom transmission tables.  Needs no device."""
+        t = np.empty((2, 2, 2, 2, 3))
+        self._check(lib().famseq_allele_tables(self._h, _p(t, C.c_double)), "famseq_allele_tables")
+        return t
+
+    def _origin(self, prior, lk, pl16, seq_members, flags, want_origin, want_hettx):
+        k = len(self.trio_children()) if (lk is None) != (pl16 is None) else 0  # (else _inputs says what is wrong)
+        outs = lambda s: (np.empty((s, k, 4)) if want_origin else None, np.empty((s, k, 4)) if want_hettx else None)
+        return self._side_host("origin", prior, lk, pl16, seq_members, flags, outs)
+
+    def origin_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_origin=True, want_hettx=True):
+        """Phase by transmission: -> (origin[S,K,4] float64, hettx[S,K,4] float64, status[S] uint8), child k being member
+        trio_children()[k].  origin[s, k, 2 a + b] is the posterior that the child received allele a (0 ref, 1 alt) from its
+        mother and b from its father, given everybody's data (a row sums to 1; a son at a chrX site has no paternal allele:
+        entries 1 and 3 are 0).  hettx[s, k] = (P(g_m = 1, a = 1), P(g_m = 1, a = 0), P(g_f = 1, b = 1), P(g_f = 1, b = 0)): the
+        expected transmissions from heterozygous parents, what a transmission test sums over families.  Both NaN where status
+        != 0.  Input as evidence_batch: either lk [S,N,3] float64 or pl16 [S,n_seq,3] uint16 in VCF column order (seq_members:
+        their PED indices).  want_* False: not computed, None.  phased_calls(origin) makes the a|b call."""
+        return self._origin(None, lk, pl16, seq_members, flags, want_origin, want_hettx)
+
+    def origin_prior_batch(self, prior, lk=None, pl16=None, seq_members=None, flags=None, want_origin=True, want_hettx=True):
+        """origin_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give origin_batch's bits."""
+        return self._origin(prior, lk, pl16, seq_members, flags, want_origin, want_hettx)
+
+    def origin_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_origin=0, d_hettx=0, d_status=0, stream=0):
+        """origin_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("origin", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_origin, d_hettx, d_status, stream)
+
+    def origin_prior_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_origin=0, d_hettx=0, d_status=0,
+                            stream=0):
+        """origin_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("origin", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_origin, d_hettx, d_status, stream)
+
     def af_batch(self, af0, n_iter, lk=None, pl16=None, seq_members=None, flags=None, want_af=True, want_loglik=True):
         """The founders' allele frequency by maximum likelihood: -> (af[S] float64, loglik[S,2] float64, status[S] uint8).
         n_iter (0 .. 64) EM steps from af0 ([S], or a scalar for every site; each in [0, 1]) on the allele frequency q of the
@@ -852,6 +894,17 @@ def bn_batch_device_sharded(contexts, n_sites, d_lk, d_flags, d_post, d_single=N
     if rc != 0:
         msgs = [lib().famseq_last_error(c._h).decode() for c in contexts]
         raise FamseqError("famseq_bn_batch_device_sharded failed (%d): %s" % (rc, "; ".join(m for m in msgs if m)))
+
+
+def phased_calls(origin):
+    """The phased call of origin_batch's rows: origin [..., 4] -> (index [...] int8, probability [...] float64), index = 2 a + b
+    of the largest entry (a the maternal, b the paternal allele; the lowest index among equals), probability that entry; -1 and
+    NaN for a NaN row."""
+    o = np.asarray(origin, dtype=np.float64)
+    bad = np.isnan(o).any(axis=-1)
+    idx = np.argmax(np.where(bad[..., None], 0.0, o), axis=-1)  # (np.argmax: the first of equals)
+    prob = np.take_along_axis(o, idx[..., None], axis=-1)[..., 0]
+    return np.where(bad, -1, idx).astype(np.int8), np.where(bad, np.nan, prob)
 
 
 def call_genotypes(post):

@@ -379,9 +379,16 @@ std::string trio_json(const famseq_ctx *c) {
     o += side_json(c, side_table()[i], false) + (side_table()[i].has_prior() ? side_json(c, side_table()[i], true) : std::string());
   const std::string bt = std::to_string(elim_block_threads(c->model));  // (every side product's kernel runs in these workgroups)
   o += ",\"evidence_block_threads\":" + bt + ",\"loo_block_threads\":" + bt;
-  for (int i = SIDE_MUTRATE; i < SIDE_COUNT; ++i)  // (the products added since: behind every older key)
+  // The products added since stand behind every older key but in front of the mutation-rate profile's four.  That order is kept
+  // for one reason only: tests/test_mutrate_host.py pins those four to the end of the plan, and existing tests stay as they are.
+  for (int i = SIDE_MUTRATE + 1; i < SIDE_COUNT; ++i)
     o += side_json(c, side_table()[i], false) + (side_table()[i].has_prior() ? side_json(c, side_table()[i], true) : std::string());
-  return o;
+  // the mutation rate the origin kernels' allele rows are made for (null: the model's tables are not one rate's)
+  char rate[40] = "null";
+  double mu = 0;
+  if (origin_rate(c->model, &mu)) std::snprintf(rate, sizeof rate, "%.17g", mu);
+  o += std::string(",\"origin_mrate\":") + rate;
+  return o + side_json(c, side_table()[SIDE_MUTRATE], false) + side_json(c, side_table()[SIDE_MUTRATE], true);
 }
 }  // namespace
 
@@ -949,6 +956,7 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
                void *out_b, uint8_t *status, void *stream_ = nullptr, const PatternIn *pat = nullptr, const SampleIn *smp = nullptr,
                const AfIn *af = nullptr, const RelabelIn *rel = nullptr, const RateIn *mr = nullptr) {
   if (!c) return FAMSEQ_E_ARG;
+  if (id == SIDE_ORIGIN && origin_model(c) != 0) return FAMSEQ_E_ARG;  // (said before the device is asked for)
   if (mr && check_rates(c, device ? mr->d_tables : mr->rates, mr->n_rates, device ? "d_tables" : "rates", !device) != 0) return FAMSEQ_E_ARG;
   if (rel && check_relabel(c, *rel, device) != 0) return FAMSEQ_E_ARG;
   if (pat && check_patterns(c, *pat, device) != 0) return FAMSEQ_E_ARG;
@@ -984,7 +992,21 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
   // ... or the mutation-rate kernels' tables and their number
   const double *d_tables = mr ? mr->d_tables : nullptr;
   const int32_t n_rates = mr ? mr->n_rates : 1;
-  const MoreArgs lead = mr    ? MoreArgs{&d_tables, &n_rates}
+  // ... or the origin kernels' allele rows: the context's own, uploaded on their first use and never changed
+  const double *d_allele = nullptr;
+  if (id == SIDE_ORIGIN) {
+    if (!c->d_allele) {
+      double rows[FAMSEQ_ALLELE_TABLE_DOUBLES];
+      build_allele_tables(c->origin_mrate, rows);
+      HIP_TRY(c, c->d_allele.alloc(sizeof rows));
+      const hipError_t e = hipMemcpy(c->d_allele.p, rows, sizeof rows, hipMemcpyHostToDevice);  // (blocking: done when it returns)
+      if (e != hipSuccess) c->d_allele.release();
+      HIP_TRY(c, e);
+    }
+    d_allele = c->d_allele.as<double>();
+  }
+  const MoreArgs lead = id == SIDE_ORIGIN ? MoreArgs{&d_allele}
+                        : mr  ? MoreArgs{&d_tables, &n_rates}
                         : rel ? MoreArgs{&d_assign, &n_assign}
                         : pat ? MoreArgs{&d_masks, &n_patterns}
                         : smp ? MoreArgs{&seed, &site_base, &n_draws}
@@ -1305,6 +1327,41 @@ extern "C" int famseq_mutrate_prior_batch_device(famseq_ctx *c, int64_t n_sites,
   const RateIn mr{nullptr, d_tables, n_rates};
   return side_entry(c, SIDE_MUTRATE, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_rate_loglik, d_loglik,
                     d_status, stream, nullptr, nullptr, nullptr, nullptr, &mr);
+}
+
+// ---- phase by transmission: each child's alleles by parent of origin, and the transmissions from heterozygous parents ----------
+
+extern "C" int famseq_allele_tables(famseq_ctx *c, double *tables) {
+  if (!c) return FAMSEQ_E_ARG;
+  if (origin_model(c) != 0) return FAMSEQ_E_ARG;
+  if (!tables) return fail(c, FAMSEQ_E_ARG, "tables must be given (" + std::to_string(FAMSEQ_ALLELE_TABLE_DOUBLES) + " doubles)");
+  build_allele_tables(c->origin_mrate, tables);
+  return 0;
+}
+
+extern "C" int famseq_origin_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                   int32_t n_seq, const uint8_t *flags, double *origin, double *hettx, uint8_t *status) {
+  return side_entry(c, SIDE_ORIGIN, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, origin, hettx, status);
+}
+
+extern "C" int famseq_origin_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                          const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_origin,
+                                          double *d_hettx, uint8_t *d_status, void *stream) {
+  return side_entry(c, SIDE_ORIGIN, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_origin, d_hettx, d_status,
+                    stream);
+}
+
+extern "C" int famseq_origin_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                         int32_t n_seq, const uint8_t *flags, const double *prior, double *origin, double *hettx,
+                                         uint8_t *status) {
+  return side_entry(c, SIDE_ORIGIN, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, origin, hettx, status);
+}
+
+extern "C" int famseq_origin_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                                const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                                double *d_origin, double *d_hettx, uint8_t *d_status, void *stream) {
+  return side_entry(c, SIDE_ORIGIN, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_origin, d_hettx,
+                    d_status, stream);
 }
 
 // The sampling kernels' generator on the host: the text they carry (philox_src.h), compiled here.

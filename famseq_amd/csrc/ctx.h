@@ -55,7 +55,7 @@ struct DevBuf {
 };
 
 // A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp; the trio,
-// MAP, evidence, leave-one-out, pattern, sampling, allele-frequency, relabelling and mutation-rate kinds are the rows of
+// MAP, evidence, leave-one-out, pattern, sampling, allele-frequency, relabelling, mutation-rate and origin kinds are the rows of
 // side_table() below.
 enum KernelKind {
   K_LANE = 0,  // K_LANE + d: the enumeration with 3^d lanes per site; d = 0 (one lane per site) serves large batches,
@@ -81,6 +81,8 @@ enum KernelKind {
   K_RELABEL_PRIOR,                                 // ... with the founders' prior per site
   K_MUTRATE,                                       // mutation-rate likelihood profile: the sum pass once per transmission table
   K_MUTRATE_PRIOR,                                 // ... with the founders' prior per site
+  K_ORIGIN,                                        // phase by transmission: each child's alleles by parent of origin
+  K_ORIGIN_PRIOR,                                  // ... with the founders' prior per site
   K_LANE_BULK,  // the one-lane-per-site enumeration in the outer-leaf plan (lane variant 8 + K_LANE's block shape and fencing): serves
                 // large batches where that text differs from K_LANE's (kernels.cpp, bulk_serves); no pick, no contest of its own
   K_COUNT
@@ -124,7 +126,7 @@ struct SlotSet {
 // A side product of the sum-product engine: a generated kernel that takes the common argument list and writes two outputs per
 // site and a status byte, in a plain form and in one that reads the founders' prior per site.  Everything its ABI entries, its
 // prebuild options, its plan keys and its loader differ in is one row of side_table() (kernels.cpp).
-enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_SAMPLE, SIDE_AF, SIDE_RELABEL, SIDE_MUTRATE, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
+enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_SAMPLE, SIDE_AF, SIDE_RELABEL, SIDE_MUTRATE, SIDE_ORIGIN, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
 struct SideProduct {
   const char *stem;   // "trio": the entry points famseq_trio[_prior], the options trio[_prior]_kernels, the plan keys trio[_prior]_*
   const char *what;   // load_or_fail's message starts "[site priors, ]<what> (sum-product engine): "
@@ -225,6 +227,12 @@ struct famseq_ctx {
   // ... and the mutation-rate host entries' factor tables: FAMSEQ_MAX_RATES blocks of FAMSEQ_RATE_TABLE_DOUBLES, staged the same way
   famseq::DevBuf d_rate_tables;
   std::vector<double> rate_tables_host;
+  // the origin kernels' allele rows (FAMSEQ_ALLELE_TABLE_DOUBLES), uploaded once, on their first use, and never changed; and the
+  // mutation rate they are made for, recovered from the model's tables (origin_state: 0 not looked at, 1 found, -1 the tables
+  // are nobody's famseq_transmission_tables: no allele-level model)
+  famseq::DevBuf d_allele;
+  double origin_mrate = 0;
+  int origin_state = 0;
   int64_t trio_dev_sites = 0;
   std::string tune_report;  // what famseq_set_option "tune" measured (famseq_plan_json "tune")
   std::string err, json;
@@ -248,7 +256,7 @@ inline int fail(famseq_ctx *c, int code, const std::string &msg) {
 // argument's value (hipModuleLaunchKernel's form).  The call-path forms take their CallIO, the site-prior kernels their prior
 // rows, the pattern kernels their masks and n_patterns and the sampling kernels their seed, site_base and n_draws in front of
 // those, the allele-frequency kernel its start values and n_iter, the relabelling kernels their assignments and n_assign, the
-// mutation-rate kernels their tables and n_rates; the plain forms nothing.
+// mutation-rate kernels their tables and n_rates, the origin kernels their allele rows; the plain forms nothing.
 struct MoreArgs {
   static constexpr int kMax = 4;
   void *at[kMax] = {};
@@ -263,6 +271,11 @@ struct MoreArgs {
 // The sum-product family (K_ELIM, K_PRIOR and every kind of side_table()): 0, or an error (FAMSEQ_E_ARG: the engine does not serve
 // this pedigree; FAMSEQ_E_HIP) that is not remembered, the next call tries again.
 int load_or_fail(famseq_ctx *c, int kind);
+// The origin kernels' precondition: the model's three transmission tables are, bit for bit, famseq_transmission_tables(mu) for
+// mu = pcp2Xm[18] (c->origin_mrate).  0, or FAMSEQ_E_ARG with its message; asks nothing of a device.
+int origin_model(famseq_ctx *c);
+// ... the same question of a model alone: true and the rate in *mu, or false; changes nothing
+bool origin_rate(const Model &m, double *mu);
 // The lane kinds and both call-path forms: false when the kernel is unavailable, which is remembered and said once on
 // stderr; the caller falls back (team kernel, separate stages).
 bool load_or_remember(famseq_ctx *c, int kind);

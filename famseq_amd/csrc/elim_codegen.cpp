@@ -260,6 +260,55 @@ class Emitter {
     return loop + o_.str();
   }
 
+  // Phase by transmission (famseq_origin): for every child c (PED order, as trio_body) the network with c's transmission factor
+  // replaced by its allele-level form tm(a | gm) * tf(b | gf), a and b the alleles (0 ref, 1 alt) c received from mother and
+  // father and c's genotype gamma(a, b): a + b, at a chrX site 2 a for a son.  With C and x what trio() multiplies (fac2var's
+  // product for the message F -> c, and c's own message), per child, every sum in the order written:
+  //   p(a, gm, gf) = tm(a | gm) * C(gm, gf)                          M(a, gf) = (p(a, 0, gf) + p(a, 1, gf)) + p(a, 2, gf)
+  //   q(a, b, gf)  = tf(b | gf) * M(a, gf)                           O(a, b)  = ((q(a, b, 0) + q(a, b, 1)) + q(a, b, 2)) * x(gamma(a, b))
+  //   r(a, b)      = (tf(b | 0) * p(a, 1, 0) + tf(b | 1) * p(a, 1, 1)) + tf(b | 2) * p(a, 1, 2)      [the mother het: M's middle terms]
+  //   Hm(a)        = r(a, 0) * x(gamma(a, 0)) + r(a, 1) * x(gamma(a, 1))
+  //   Hf(b)        = q(0, b, 1) * x(gamma(0, b)) + q(1, b, 1) * x(gamma(1, b))                        [the father het: O's middle terms]
+  // Outputs: origin[2 a + b] = O(a, b) / s, s = ((O(0,0) + O(0,1)) + O(1,0)) + O(1,1), the total weight of c's component, and
+  // hettx = (Hm(1), Hm(0), Hf(1), Hf(0)) / s.  Products and sums of non-negative numbers only: a term with a factor of exactly 0
+  // is exactly 0.0.  The allele rows are not in the text (a kernel is cached per pedigree, not per rate): alx[], the block of
+  // the chrX pass under way of build_allele_tables' table, a wave-uniform pointer, so that an entry arrives by a scalar load.
+  // Loops: the eight sums accumulated over the cut assignments with the weight of the rest of the network, normalised once
+  // behind the last assignment, as trio_body does.
+  std::string origin_body(const std::vector<int> &kids) {
+    const int K = (int)kids.size();
+    const std::string head = "      const double *alx = al_g + x_ * 24;\n";
+    if (g_.cut.empty()) {
+      for (int c = 0; c < (int)g_.rep.size(); ++c)  // (a lone founder's component: as trio_body)
+        if (g_.nb[g_.rep[c]].empty()) {
+          const std::string l = loc(g_.rep[c]);
+          o_ << "      if (((" << l << "_0 + " << l << "_1) + " << l << "_2) <= 0) bn_fail = true;\n";
+        }
+      for (int k = 0; k < K; ++k) {
+        const std::string n = origin(family_of(kids[k]), kids[k]);
+        origin_out(k, n + "O", n + "H");
+      }
+      return head + o_.str();
+    }
+    std::ostringstream decls;
+    for (int k = 0; k < K; ++k)
+      decls << "      double to" << k << "_0 = 0, to" << k << "_1 = 0, to" << k << "_2 = 0, to" << k << "_3 = 0, th" << k << "_0 = 0, th" << k
+            << "_1 = 0, th" << k << "_2 = 0, th" << k << "_3 = 0;\n";
+    const std::string loop = cut_loop(decls.str(), /*wc=*/true, /*wall=*/false, [&] {
+      for (int k = 0; k < K; ++k) {
+        const int F = family_of(kids[k]);
+        const std::string n = origin(F, kids[k]), W = "Wc" + num(family_comp(F));
+        for (const char *t : {"o", "h"})
+          for (int i = 0; i < 4; ++i)
+            o_ << "      t" << t << k << "_" << i << " = __builtin_fma(" << n << (t[0] == 'o' ? "O" : "H") << "_" << i << ", " << W << ", t" << t << k
+               << "_" << i << ");\n";
+        fence(1);
+      }
+    });
+    for (int k = 0; k < K; ++k) origin_out(k, "to" + num(k), "th" + num(k));
+    return head + loop + o_.str();
+  }
+
   // The joint MAP configuration (famseq_map): g* = argmax_g w(g) and its posterior w(g*) / Z, by message passing under two
   // semirings on the same graph.  One root per component (g_.rep); only the messages that point towards a root are formed.
   //   sum pass  Z = prod_c sum_g m_root(g): marginal(root), the code every other form uses.
@@ -870,6 +919,73 @@ class Emitter {
        << "        const double dm_ = xchr_ ? " << mX << " : " << mA << ";\n"
        << "        if (s < 1e-290) { asm volatile(\"\" ::: \"memory\"); " << stores("/", "s") << " }\n"
        << "        else { const double r = 1.0 / s; " << stores("*", "r") << " } }\n";
+  }
+
+  // child c's four unnormalised origin terms o<c>O_<2 a + b> and four het-transmission terms o<c>H_<i> (origin_body's sums)
+  std::string origin(int F, int c) {
+    (void)fac2var(F, c);  // its product C of the parents' messages and the other children's summaries
+    const std::string C = "f" + num(F) + "v" + num(c) + "w", xc = var2fac(c, F), n = "o" + num(c);
+    const bool son = m_.gender[c] == 1;
+    // build_allele_tables' row of the pass's block: [child sex][parent][allele][genotype]
+    auto A = [&](int parent, int a, int g) { return "alx[" + num((son ? 0 : 12) + 6 * parent + 3 * a + g) + "]"; };
+    auto p = [&](int a, int gm, int gf) { return n + "p_" + num(a) + num(gm) + num(gf); };
+    auto M = [&](int a, int gf) { return n + "M_" + num(a) + num(gf); };
+    auto q = [&](int a, int b, int gf) { return n + "q_" + num(a) + num(b) + num(gf); };
+    auto x = [&](int a, int b) { return n + "x_" + num(a) + num(b); };
+    for (int a = 0; a < 2; ++a)
+      for (int gm = 0; gm < 3; ++gm)
+        for (int gf = 0; gf < 3; ++gf)
+          o_ << "      const double " << p(a, gm, gf) << " = " << A(0, a, gm) << " * " << C << "_" << gm << gf << ";\n";
+    for (int a = 0; a < 2; ++a)
+      for (int gf = 0; gf < 3; ++gf)
+        o_ << "      const double " << M(a, gf) << " = (" << p(a, 0, gf) << " + " << p(a, 1, gf) << ") + " << p(a, 2, gf) << ";\n";
+    fence(2);
+    for (int a = 0; a < 2; ++a)
+      for (int b = 0; b < 2; ++b) {
+        for (int gf = 0; gf < 3; ++gf) o_ << "      const double " << q(a, b, gf) << " = " << A(1, b, gf) << " * " << M(a, gf) << ";\n";
+        // the child's message at gamma(a, b): a son's genotype at a chrX site is 2 a
+        o_ << "      const double " << x(a, b) << " = ";
+        if (son && a + b != 2 * a) o_ << "x_ ? " << xc << "_" << 2 * a << " : " << xc << "_" << a + b;
+        else o_ << xc << "_" << a + b;
+        o_ << ";\n"
+           << "      const double " << n << "O_" << 2 * a + b << " = ((" << q(a, b, 0) << " + " << q(a, b, 1) << ") + " << q(a, b, 2) << ") * "
+           << x(a, b) << ";\n";
+      }
+    for (int a = 1; a >= 0; --a) {  // (hettx's order: the alternative allele first)
+      for (int b = 0; b < 2; ++b)
+        o_ << "      const double " << n << "r_" << a << b << " = (" << A(1, b, 0) << " * " << p(a, 1, 0) << " + " << A(1, b, 1) << " * " << p(a, 1, 1)
+           << ") + " << A(1, b, 2) << " * " << p(a, 1, 2) << ";\n";
+      o_ << "      const double " << n << "H_" << 1 - a << " = " << n << "r_" << a << "0 * " << x(a, 0) << " + " << n << "r_" << a << "1 * " << x(a, 1)
+         << ";\n";
+    }
+    for (int b = 1; b >= 0; --b)
+      o_ << "      const double " << n << "H_" << 3 - b << " = " << q(0, b, 1) << " * " << x(0, b) << " + " << q(1, b, 1) << " * " << x(1, b) << ";\n";
+    fence(1);
+    return n;
+  }
+
+  // child k's outputs from its four origin terms O_<i> and four het-transmission terms H_<i>: og[4 k + i] = O_i / s and
+  // hg[4 k + i] = H_i / s, s the origin terms' sum left to right, in trio_out's arithmetic (one reciprocal; the divisions behind a
+  // real branch for a sum in the subnormal range).  A sum that is not a positive finite number fails the site.
+  // Plain stores, as trio_out's: a lane's rows lie 32 K bytes from its neighbour's, an instruction writes 8 bytes into each of 64
+  // lines, and it is the L2 that makes whole lines of them: 1.7 ms per 10 M ten-member sites, 0.46 of 8 TB/s
+  // (profiles/origin/rate.txt).  Non-temporal stores, which serve the outputs that a wave writes as whole lines, do not serve
+  // these: each piece would be handed on by itself.
+  void origin_out(int k, const std::string &O, const std::string &H) {
+    auto stores = [&](const char *op, const char *by) {
+      std::string t;
+      for (const char *out : {"og", "hg"}) {
+        t += std::string(" if (") + out + ") {";
+        for (int i = 0; i < 4; ++i)
+          t += std::string(" ") + out + "[" + num(4 * k + i) + "] = " + (out[0] == 'o' ? O : H) + "_" + num(i) + " " + op + " " + by + ";";
+        t += " }";
+      }
+      return t;
+    };
+    o_ << "      { const double s = ((" << O << "_0 + " << O << "_1) + " << O << "_2) + " << O << "_3;\n"
+       << "        if (!(s > 0 && s <= 1.79769313486231570815e308)) bn_fail = true;\n"
+       << "        if (s < 1e-290) { asm volatile(\"\" ::: \"memory\");" << stores("/", "s") << " }\n"
+       << "        else { const double r = 1.0 / s;" << stores("*", "r") << " } }\n";
   }
 
   const Model &m_;
@@ -1629,6 +1745,54 @@ std::string mutrate_source(const Model &m, int variant, bool site_prior) {
                "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.bt = elim_block_threads(m, false);
   d.fence_single = f >= 3, d.chrx_loop = true, d.site_prior = site_prior;  // (variant 0 too: mutrate_body)
+  return lane_shell(m, d);
+}
+
+// The allele rows of famseq_origin: t(1 | g) = (mu, 1/2, 1 - mu) and t(0 | g) = (1 - mu, 1/2, mu) for a parent who hands one of
+// two alleles on; a father's X reaches a daughter from a hemizygous genotype (the heterozygous column 0) and never reaches a son,
+// whose row for "no allele" (0) is (1, 0, 1).  [chrX][child sex: 0 son, 1 daughter][parent: 0 mother, 1 father][allele][genotype].
+void build_allele_tables(double mu, double *t) {
+  const double u = 1.0 - mu;
+  const double two[2][3] = {{u, 0.5, mu}, {mu, 0.5, u}}, hemi[2][3] = {{u, 0.0, mu}, {mu, 0.0, u}}, none[2][3] = {{1.0, 0.0, 1.0}, {0.0, 0.0, 0.0}};
+  for (int x = 0; x < 2; ++x)
+    for (int sex = 0; sex < 2; ++sex)
+      for (int parent = 0; parent < 2; ++parent) {
+        const double(*row)[3] = (x == 0 || parent == 0) ? two : (sex == 0 ? none : hemi);
+        for (int a = 0; a < 2; ++a)
+          for (int g = 0; g < 3; ++g) t[24 * x + 12 * sex + 6 * parent + 3 * a + g] = row[a][g];
+      }
+}
+
+// The origin kernel: the trio kernel's rules and shell.  Beyond the common arguments: al_g[FAMSEQ_ALLELE_TABLE_DOUBLES],
+// build_allele_tables' rows for the model's mutation rate.  Outputs per site: origin[K][4] and hettx[K][4] (Emitter::origin_body;
+// either may be null: its stores are skipped), status.  Every variant takes the chrX loop, the fence-free one too (as
+// famseq_mutrate does): the allele rows are read through the pass's wave-uniform pointer alx and cost no vector register.
+std::string origin_source(const Model &m, int variant, bool site_prior) {
+  const Graph g = graph_or_throw(m);
+  if (variant < 0 || variant >= kOriginVariants)
+    throw std::runtime_error("origin_source: variant must be 0.." + std::to_string(kOriginVariants - 1));
+  const int f = variant;
+  const std::vector<int> kids = trio_children(m);
+  EmitOptions eo = emit_options(f, "pg", site_prior);
+  LaneShell d;
+  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
+  d.entry = "famseq_origin";
+  d.comment = describe("phase by transmission (parental origin per child)", g, std::to_string(f), site_prior);
+  d.outputs = "double *__restrict__ origin_g, double *__restrict__ hettx_g";
+  d.more_args = ", const double *__restrict__ al_g";
+  d.defines = "#define NKID " + std::to_string(kids.size()) + "\n";
+  d.site_decls = "    double *og = origin_g ? origin_g + site * (4 * NKID) : nullptr;\n"
+                 "    double *hg = hettx_g ? hettx_g + site * (4 * NKID) : nullptr;\n"
+                 "    (void)og; (void)hg;\n";
+  d.body = Emitter(m, g, eo).origin_body(kids);
+  d.epilogue =
+      "    if (single_fail || bn_fail) {\n"
+      "      if (og) {\n#pragma unroll 1\n        for (int k = 0; k < 4 * NKID; ++k) og[k] = kNaN;\n      }\n"
+      "      if (hg) {\n#pragma unroll 1\n        for (int k = 0; k < 4 * NKID; ++k) hg[k] = kNaN;\n      }\n"
+      "    }\n"
+      "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
+  d.bt = elim_block_threads(m, false);
+  d.fence_single = f >= 3, d.chrx_loop = true, d.site_prior = site_prior;
   return lane_shell(m, d);
 }
 

@@ -110,6 +110,20 @@ constexpr int kMutrateVariants = 4;
 // site_prior: famseq_mutrate_prior, with a trailing `prior` [n_sites][6] behind n_rates (as trio_source's).
 std::string mutrate_source(const Model &m, int variant, bool site_prior = false);
 
+// Phase by transmission (famseq_origin_batch).  HIP source of
+// `extern "C" __global__ famseq_origin(lk, flags, origin, hettx, status, n_sites, tc, lc, al)`: per site and child k
+// (trio_children's order) origin[k][2 a + b], the posterior that the child received allele a (0 ref, 1 alt) from its mother and b
+// from its father, and hettx[k] = (P(g_m = 1, a = 1), P(g_m = 1, a = 0), P(g_f = 1, b = 1), P(g_f = 1, b = 0)): the network of
+// famseq_evidence with the child's transmission factor replaced by tm(a | g_m) tf(b | g_f), whose rows the kernel reads from
+// al[48] (build_allele_tables) — the text holds no rate.  variant 0..3: the fence levels of famseq_elim's, every one with the
+// chrX loop (the rows arrive by scalar loads).  Throws if the engine does not serve the pedigree.
+constexpr int kOriginVariants = 4;
+// site_prior: famseq_origin_prior, with a trailing `prior` [n_sites][6] behind al (as trio_source's).
+std::string origin_source(const Model &m, int variant, bool site_prior = false);
+// al[FAMSEQ_ALLELE_TABLE_DOUBLES] for the mutation rate mu: [chrX][child sex: 0 son, 1 daughter][parent: 0 mother, 1 father]
+// [allele][parent's genotype]
+void build_allele_tables(double mu, double *tables);
+
 // The founders' allele frequency by maximum likelihood (famseq_af_batch).  HIP source of
 // `extern "C" __global__ famseq_af(lk, flags, af, loglik, status, n_sites, tc, lc, af0, n_iter)`: per site n_iter EM steps on the
 // allele frequency q of the founders' Hardy-Weinberg prior from af0 — a step is one sum pass of famseq_evidence and the founders'

@@ -5,7 +5,7 @@
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
 //              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-loo] [-afTag KEY | -afTagAll KEY]
 //              [-seg dominant|recessive|both -affected ID[,ID...] [-unaffected ID[,ID...]]] [-sample K [-seed S]]
-//              [-afEM T [-afStart X]] [-swapCheck FILE] [-mRateScan FILE [-mRateGrid r1,r2,...]]
+//              [-afEM T [-afStart X]] [-swapCheck FILE] [-mRateScan FILE [-mRateGrid r1,r2,...]] [-phase]
 //   FamSeq LK -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -28,7 +28,8 @@
 // of the family drawn from their posterior (SGT), and -afEM T (vcf mode) the maximum-likelihood allele frequency among the founders after
 // T EM steps and its log10 likelihood ratio against an allele frequency of 0, to the INFO column (FAF, FAL), and -swapCheck FILE (vcf
 // mode) writes, behind the last site, the log10 Bayes factor of every two sequenced samples' exchange over the whole file, and
-// -mRateScan FILE (vcf mode) the file's log10 likelihood at every mutation rate of a grid.
+// -mRateScan FILE (vcf mode) the file's log10 likelihood at every mutation rate of a grid, and -phase (vcf mode) each child's genotype
+// phased by transmission, maternal|paternal, with its posterior (PGT, PGP).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -191,6 +192,7 @@ struct Options {
   bool dnm = false;  // -dnm: a DNP field per sample (vcf mode)
   bool map = false;  // -map: JGT and JP fields per sample (vcf mode)
   bool siteq = false;  // -siteQ: FQ and FLL keys in the INFO column (vcf mode)
+  bool phase = false;  // -phase: PGT and PGP fields per sample, the phased genotype by transmission and its probability (vcf mode)
   bool loo = false;    // -loo: LOP and LOF fields per sample, the leave-one-out posteriors and the member's fit (vcf mode)
   int sample = 0;      // -sample K: an SGT field per sample, its alt-allele counts in K joint posterior draws of the family (vcf mode)
   uint64_t seed = 0;   // -seed S: the draws' seed
@@ -351,6 +353,8 @@ int parse_options(int argc, char **argv, Options &o) {
       o.siteq = true;
     } else if (opt == "loo") {
       o.loo = true;
+    } else if (opt == "phase") {
+      o.phase = true;
     } else if (opt == "sample" || opt == "seed") {
       i++;
       if (missing(i)) {
@@ -1422,16 +1426,17 @@ struct Part {
 // ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample, -seg and -afEM add to a line, one row of kSide each; -swapCheck and
 // ---- -mRateScan, which add nothing to any line and write a report of their own behind the last site (SideRow::report), are rows too
 // The order is the one main checks them and prints its notices in; it is also the order of the fields in a sample column (DNP,
-// JGT:JP, LOP:LOF, SGT) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL).  Header lines have their
+// JGT:JP, LOP:LOF, SGT, PGT:PGP) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL).  Header lines have their
 // own order.
-enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap, kRateScan };
-constexpr int kSides = kRateScan + 1;
-const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap, kRateScan};
+enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap, kRateScan, kPhase };
+constexpr int kSides = kPhase + 1;
+const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap, kRateScan, kPhase};
 
 // One side output of a block: the two arrays its C entry fills ([site][...], read as the entry's own types) and its status per site.
 struct SideOut {
   vector<double> a, b;
   vector<uint8_t> status;
+  const uint8_t *flags = nullptr;  // the block's flags per site (-phase: a son's field at a chrX site is haploid)
   const int8_t *a8() const { return reinterpret_cast<const int8_t *>(a.data()); }
 };
 
@@ -1914,6 +1919,10 @@ struct VcfRun {
       case kSample: rc = entry(famseq_sample_batch, famseq_sample_prior_batch, o.seed, sl.site_base, (int32_t)o.sample, a8, none, st); break;
       case kSeg: rc = entry(famseq_pattern_batch, famseq_pattern_prior_batch, seg_masks.data(), (int32_t)seg_keys.size(), a, none, st); break;
       case kSwap: return call_swap(sl, so, lk, pl16);
+      case kPhase:
+        so.flags = sl.io.flags;
+        rc = entry(famseq_origin_batch, famseq_origin_prior_batch, n_kids ? a : none, none, st);
+        break;
       case kRateScan:
         rc = entry(famseq_mutrate_batch, famseq_mutrate_prior_batch, o.rate_grid.data(), (int32_t)o.rate_grid.size(), a, b, st);
         if (rc == 0) add_rate_report(sl, so);
@@ -2236,8 +2245,28 @@ inline void put_faf(TextBuf &out, const VcfRun &, const SideOut &so, size_t s, s
   out.num(so.b[2 * s] - so.b[2 * s + 1]);
 }
 
+// -phase: "a|b" (the maternal allele first) of the largest of the child's four origin posteriors, the lowest index 2 a + b among
+// equals, and that posterior; a son at a chrX site has the maternal allele alone; "." for a founder and at a failed site
+inline void put_phase(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {
+  const int kid = r.kid_of_col[j];
+  if (kid < 0 || so.status[s] != 0) return out.put(":.:.", 4);
+  const double *p = so.a.data() + 4 * (s * size_t(r.n_kids) + size_t(kid));
+  int best = 0;
+  for (int i = 1; i < 4; ++i)
+    if (p[i] > p[best]) best = i;
+  out.ch(':');
+  out.ch(char('0' + (best >> 1)));
+  if (!((so.flags[s] & FAMSEQ_FLAG_CHRX) && r.ped.gender[size_t(r.cm.members[j])] == 1)) {
+    out.ch('|');
+    out.ch(char('0' + (best & 1)));
+  }
+  out.ch(':');
+  out.num(p[best]);
+}
+
 [[gnu::always_inline]] inline void put_side(SideId id, TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {
   switch (id) {
+    case kPhase: return put_phase(out, r, so, s, j);
     case kDnm: return put_dnp(out, r, so, s, j);
     case kMap: return put_map(out, r, so, s, j);
     case kSiteQ: return put_fq(out, r, so, s, j);
@@ -2383,6 +2412,14 @@ const SideRow kSide[kSides] = {
     {kRateScan, "-mRateScan", "famseq_mutrate", true, [](const Options &o) { return o.rate_scan_given || o.rate_grid_given; },
      [](Options &o) { o.rate_scan_given = o.rate_grid_given = false, o.rate_file.clear(); }, check_rate_scan, [](std::ostream &, const Options &) {},
      nullptr, nullptr, [](const VcfRun &r) { return SideBytes{8 * r.o.rate_grid.size(), 8}; }, /*report=*/true},
+    {kPhase, "-phase", "famseq_origin", true, [](const Options &o) { return o.phase; }, [](Options &o) { o.phase = false; }, nullptr,
+     [](std::ostream &out, const Options &) {
+       out << "##FORMAT=<ID=PGT,Number=1,Type=String,Description=\"Phased genotype by transmission, maternal|paternal allele (0 ref, 1 alt): "
+              "the most probable pair of alleles received from mother and father given the whole family's data; the maternal allele "
+              "alone for a son on chromosome X; . for a founder\">" << std::endl;
+       out << "##FORMAT=<ID=PGP,Number=1,Type=Float,Description=\"Posterior probability of that maternal|paternal pair\">" << std::endl;
+     },
+     ":PGT:PGP", ":.:.", [](const VcfRun &r) { return SideBytes{32 * size_t(r.n_kids), 0}; }},
 };
 
 // `FamSeq vcf` and `FamSeq pack`: the wiring of a VcfRun's stages
@@ -2600,6 +2637,10 @@ void help() {
             << "\t\tfrom -afStart X (in (0, 1), default 0.5), and FAL, the log10 likelihood ratio of the site's data at that frequency against" << std::endl
             << "\t\t\"no founder carries the allele\" (inf where the data exclude that), to the INFO column. No prior enters either; no other" << std::endl
             << "\t\tfield changes. Implies -method 2; may be combined with -dnm, -map, -siteQ, -loo, -sample, -seg and -afTagAll; not with -afTag." << std::endl
+            << "-phase\t\t(vcf) Add PGT, the sample's genotype phased by transmission as maternal|paternal allele (the most probable pair of" << std::endl
+            << "\t\talleles received from mother and father given the whole family's data; the maternal allele alone for a son on" << std::endl
+            << "\t\tchromosome X; . for a founder), and PGP, that pair's posterior probability, to every sample column. Implies -method 2;" << std::endl
+            << "\t\tmay be combined with every other option above, under -afTagAll with the line's prior; not with -afTag." << std::endl
             << "-swapCheck FILE\t(vcf) After the last site write FILE: for every two sequenced samples, in VCF column order, log10_BF, the sum over" << std::endl
             << "\t\tthe file's sites of the log10 likelihood of the site under the pedigree with the two samples exchanged minus that with the" << std::endl
             << "\t\tlabels as given (positive favours the exchange), and sites_impossible, the sites the exchange makes impossible, which the" << std::endl

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 
 #include "bn_kernel.h"
@@ -43,6 +44,9 @@ SideTable &side_table() {
       {"mutrate", "mutation-rate likelihood profile", "1", K_MUTRATE, K_MUTRATE_PRIOR, 1, kMutrateVariants,
        [](const Model &m, int v, int, bool site_prior) { return mutrate_source(m, v, site_prior); },
        [](const Model &, int n_rates, size_t row[2]) { row[0] = size_t(n_rates) * sizeof(double), row[1] = sizeof(double); }},  // rate_loglik[R], loglik
+      {"origin", "phase by transmission", "1", K_ORIGIN, K_ORIGIN_PRIOR, 1, kOriginVariants,
+       [](const Model &m, int v, int, bool site_prior) { return origin_source(m, v, site_prior); },
+       [](const Model &m, int, size_t row[2]) { row[0] = row[1] = 4 * trio_children(m).size() * sizeof(double); }},  // origin[K][4], hettx[K][4]
   };
   return table;
 }
@@ -205,6 +209,23 @@ int load_kernel(famseq_ctx *c, int kind, std::string *why) {
 
 }  // namespace
 
+bool origin_rate(const Model &m, double *mu_out) {
+  const double mu = m.pcp2Xm[18];  // the son's T(2 | 0, 0)
+  if (!(mu >= 0.0 && mu <= 1.0)) return false;
+  double a[27], xf[27], xm[27];
+  famseq_transmission_tables(mu, a, xf, xm);
+  if (std::memcmp(a, m.pcp2, sizeof a) != 0 || std::memcmp(xf, m.pcp2Xf, sizeof xf) != 0 || std::memcmp(xm, m.pcp2Xm, sizeof xm) != 0) return false;
+  *mu_out = mu;
+  return true;
+}
+
+int origin_model(famseq_ctx *c) {
+  if (c->origin_state == 0) c->origin_state = origin_rate(c->model, &c->origin_mrate) ? 1 : -1;
+  if (c->origin_state > 0) return 0;
+  return fail(c, FAMSEQ_E_ARG, "phase by transmission: there is no allele-level model for custom transmission tables (the model's pcp2, pcp2Xf and "
+                               "pcp2Xm are not famseq_transmission_tables of one mutation rate)");
+}
+
 int load_or_fail(famseq_ctx *c, int kind) {
   const SideKind k = side_of(kind);
   if (k.p && k.p->n_forms > 1) (k.site_prior ? c->trio_prior_last : c->trio_last) = k.form;  // (the trio kernels: famseq_plan_json)
@@ -215,6 +236,7 @@ int load_or_fail(famseq_ctx *c, int kind) {
                                  : kind == K_PRIOR ? "site priors (sum-product engine): " : "elimination engine: ";
     return fail(c, FAMSEQ_E_ARG, what + why);
   }
+  if (k.p && k.p->kind == K_ORIGIN && origin_model(c) != 0) return FAMSEQ_E_ARG;
   if (load_kernel(c, kind, &why) != 0) return fail(c, FAMSEQ_E_HIP, why);
   return 0;
 }

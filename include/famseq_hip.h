@@ -741,6 +741,59 @@ int famseq_mutrate_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const do
                                       const double *d_tables, int32_t n_rates, double *d_rate_loglik, double *d_loglik,
                                       uint8_t *d_status, void *stream);
 
+/* ---- phase by transmission: which parent a child's alleles came from --------------------------------------------------------
+ * The marginals, the trio joint, the MAP call and the draws give a child's genotype; these entries give its phase.  For child k
+ * (famseq_trio_children's order) with mother m and father f the network is famseq_evidence_batch's with the child's
+ * transmission factor T(g_c | g_m, g_f) replaced by its allele-level form tm(a | g_m) * tf(b | g_f): a, b in {0 ref, 1 alt}
+ * are the alleles received from mother and father, and the child's genotype is gamma(a, b).  With t(1 | g) = (mu, 1/2, 1 - mu)
+ * and t(0 | g) = (1 - mu, 1/2, mu) for g = 0, 1, 2:
+ *   autosome, and a daughter at a chrX site   gamma = a + b, tm = t; tf = t, at a chrX site with the g_f = 1 column 0
+ *   a son at a chrX site                      gamma = 2 a, tm = t; tf(0 | g_f) = (1, 0, 1), tf(1 | .) = 0: his father gives no X
+ * Summed over (a, b) with gamma(a, b) = g_c the product is the model's table (to 2.2e-16 relative; the son's exactly).
+ *   origin [n_sites][K][4]  index 2 a + b: P(a, b | everybody's data); a row sums to 1.  For a son at a chrX site entries 1 and 3
+ *              are 0.0.
+ *   hettx  [n_sites][K][4]  (P(g_m = 1, a = 1), P(g_m = 1, a = 0), P(g_f = 1, b = 1), P(g_f = 1, b = 0)): the posterior-expected
+ *              transmissions from heterozygous parents, what a transmission test sums over families.  hettx[0] + hettx[1] is
+ *              P(g_m = 1 | data).  At a chrX site the father's pair is 0.0.
+ *   status [n_sites]        0 OK; 1 the single-posterior failure rule of famseq_bn_batch; 2 a child's normaliser (the sum of its
+ *              four unnormalised origin terms, left to right) is <= 0 or not finite.  Wherever status != 0 both outputs of the
+ *              whole site are NaN.  There is no -LRC shortcut.
+ * A term that holds a factor of exactly 0 is exactly 0.0: at mutation rate 0 every Mendel-impossible entry is 0.0, a result.
+ * famseq_model carries tables, not a rate: mu is taken to be pcp2Xm[18], and pcp2, pcp2Xf and pcp2Xm must be, bit for bit,
+ * famseq_transmission_tables(mu); otherwise FAMSEQ_E_ARG (there is no allele-level model for custom tables), said before the
+ * device is asked for.  famseq_plan_json: "origin_mrate" (null for such a model).
+ * Served by the sum-product engine's graph as famseq_evidence_batch is, whatever the context's engine; compiled on the first
+ * call or ahead through famseq_set_option "origin_kernels" = 1 (a context without a device generates and cross-compiles it).
+ * The kernel's text holds no rate: it reads the allele rows from a table the context uploads once, on the first call.
+ * famseq_plan_json: "origin_code_object", "origin_variant". */
+#define FAMSEQ_ALLELE_TABLE_DOUBLES 48
+
+/* tables[2 chrX][2 child sex: 0 son, 1 daughter][2 parent: 0 mother, 1 father][2 allele][3 parent's genotype]: tm and tf above for
+ * the model's mutation rate.  Works on a context without a device. */
+int famseq_allele_tables(famseq_ctx *ctx, double *tables /*[FAMSEQ_ALLELE_TABLE_DOUBLES]*/);
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_evidence_batch.  Any of origin / hettx / status may be NULL. */
+int famseq_origin_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                        int32_t n_seq, const uint8_t *flags, double *origin /*[n_sites][K][4]*/, double *hettx /*[n_sites][K][4]*/,
+                        uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array).  Enqueues on `stream` (a hipStream_t; NULL =
+ * the default stream) and returns without synchronising (the stream rule at famseq_bn_batch_device: with d_lk no context state
+ * beyond the allele rows, which the first call of a context uploads with a blocking copy before it enqueues anything; with
+ * d_pl16 through the kept scratch rows, like every side entry). */
+int famseq_origin_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                               const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_origin, double *d_hettx,
+                               uint8_t *d_status, void *stream);
+
+/* With the founders' genotype prior given per site: prior[n_sites][6], as for famseq_evidence_prior_batch.  Given rows that equal
+ * the model's constants the outputs are, bit for bit, famseq_origin_batch's.  "origin_prior_kernels" = 1 builds the kernel
+ * (famseq_origin_prior) ahead; famseq_plan_json: "origin_prior_code_object", "origin_prior_variant". */
+int famseq_origin_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                              int32_t n_seq, const uint8_t *flags, const double *prior, double *origin, double *hettx, uint8_t *status);
+int famseq_origin_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                     const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                     double *d_origin, double *d_hettx, uint8_t *d_status, void *stream);
+
 /* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] =((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);
