@@ -94,6 +94,7 @@ ABI_SYMBOLS = [
     "famseq_mutrate_batch", "famseq_mutrate_batch_device", "famseq_mutrate_prior_batch", "famseq_mutrate_prior_batch_device",
     "famseq_allele_tables",
     "famseq_origin_batch", "famseq_origin_batch_device", "famseq_origin_prior_batch", "famseq_origin_prior_batch_device",
+    "famseq_weight_batch", "famseq_weight_batch_device", "famseq_weight_prior_batch", "famseq_weight_prior_batch_device",
 ]
 # (and famseq_philox4x32_10, the one name with digits in it: philox4x32 below)
 PL_MISSING = 0xFFFF
@@ -183,10 +184,10 @@ def lib():
     masks = ([bp, C.c_int32], [vp, C.c_int32])
     draws = ([C.c_uint64, C.c_int64, C.c_int32],) * 2  # seed, site_base, n_draws
     assigns = ([ip, C.c_int32], [vp, C.c_int32])
-    rates = ([dp, C.c_int32], [vp, C.c_int32])  # the host entries take the rates, the device entries the resident tables
+    rates = ([dp, C.c_int32], [vp, C.c_int32])  # the host entries take the rates (weights), the device entries the resident tables
     for name, out_a, more in (("trio", dp, ([], [])), ("map", C.POINTER(C.c_int8), ([], [])), ("evidence", dp, ([], [])), ("loo", dp, ([], [])),
                               ("pattern", dp, masks), ("sample", C.POINTER(C.c_int8), draws),
-                              ("relabel", dp, assigns), ("mutrate", dp, rates), ("origin", dp, ([], []))):
+                              ("relabel", dp, assigns), ("mutrate", dp, rates), ("origin", dp, ([], [])), ("weight", dp, rates)):
         for prior in (0, 1):
             host = getattr(L, "famseq_%s%s_batch" % (name, "_prior" * prior))
             dev = getattr(L, "famseq_%s%s_batch_device" % (name, "_prior" * prior))
@@ -306,8 +307,28 @@ def segregation_masks(n, affected, unaffected=(), model="dominant"):
     return row
 
 
+def penetrance_weights(n, affected, unaffected=(), pen=(0.0, 1.0, 1.0)):
+    """The weight table [n, 3] float64 of a penetrance model for Context.weight_batch; affected / unaffected: member indices (PED
+    order); pen = (f0, f1, f2), the probability of being affected given 0, 1, 2 alt alleles.  An affected member's row is pen, an
+    unaffected member's 1 - pen, anyone else's ones (phenotype unknown).  pen = (0, 1, 1) is segregation_masks' dominant model,
+    (0, 0, 1) its recessive one."""
+    f = np.asarray(pen, dtype=np.float64)
+    if f.shape != (3,) or not np.all((f >= 0) & (f <= 1)):
+        raise ValueError("pen must be three probabilities (f0, f1, f2) in [0, 1], got %r" % (pen,))
+    aff, unaff = [int(i) for i in affected], [int(i) for i in unaffected]
+    for i in aff + unaff:
+        if not 0 <= i < n:
+            raise ValueError("member index %d is outside 0..%d" % (i, n - 1))
+    if set(aff) & set(unaff):
+        raise ValueError("members %s are listed as affected and as unaffected" % sorted(set(aff) & set(unaff)))
+    w = np.ones((n, 3))
+    w[aff], w[unaff] = f, 1.0 - f
+    return w
+
+
 MAX_RELABEL = 64
 MAX_RATES = 32
+MAX_WEIGHTS = 32
 RATE_TABLE_DOUBLES = 432
 ALLELE_TABLE_DOUBLES = 48
 
@@ -777,6 +798,48 @@ class Context:
         """mutrate_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
         self._side_device("mutrate", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_rate_loglik, d_loglik, d_status, stream,
                           (d_tables or None, int(n_rates)))
+
+    def _weights(self, weights):
+        """weights ([N, 3] or [M, N, 3]) as a contiguous float64 array [M, N, 3]."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[1:] != (self.n, 3):
+            raise ValueError("weights must be [M, %d, 3] (or one table [%d, 3]), got %s" % (self.n, self.n, list(w.shape)))
+        return w
+
+    def weight_batch(self, weights, lk=None, pl16=None, seq_members=None, flags=None, want_wt=True, want_loglik=True):
+        """Per-member genotype weights: -> (wt_loglik[S,M] float64, loglik[S] float64, status[S] uint8).
+        weights [M, N, 3] (1 .. MAX_WEIGHTS tables; a single [N, 3] table is accepted; finite numbers >= 0, above 1 included):
+        wt_loglik[s, m] = log10 Z(lk * weights[m]), evidence_batch's bits on the rows lk[s] * weights[m] formed in double (-inf
+        where that is exactly 0); loglik is evidence_batch's on the rows as they are.  wt_loglik[:, m] - loglik is
+        log10 E[prod_p w_p(g_p) | data] under the exact joint posterior: with penetrance_weights() the phenotypes' probability
+        given the reads, with w = t ** count a moment generating function.  Every member has a row of weights, sequenced or not.
+        Input is either lk [S,N,3] float64 or pl16 [S,n_seq,3] uint16 in VCF column order (seq_members: their PED indices).
+        want_* False: not computed, None."""
+        w = self._weights(weights)
+        outs = lambda s: (np.empty((s, w.shape[0])) if want_wt else None, np.empty(s) if want_loglik else None)
+        return self._side_host("weight", None, lk, pl16, seq_members, flags, outs, (_p(w, C.c_double), w.shape[0]))
+
+    def weight_prior_batch(self, prior, weights, lk=None, pl16=None, seq_members=None, flags=None, want_wt=True, want_loglik=True):
+        """weight_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give weight_batch's bits."""
+        w = self._weights(weights)
+        outs = lambda s: (np.empty((s, w.shape[0])) if want_wt else None, np.empty(s) if want_loglik else None)
+        return self._side_host("weight", prior, lk, pl16, seq_members, flags, outs, (_p(w, C.c_double), w.shape[0]))
+
+    def weight_device(self, n_sites, d_weights, n_weights, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_wt_loglik=0, d_loglik=0,
+                      d_status=0, stream=0):
+        """weight_batch on resident buffers (raw device pointers as ints; 0 = not given), d_weights [n_weights, N, 3] float64
+        among them (unchecked; it must stay unchanged until the kernel has run); enqueues on `stream` and returns."""
+        self._side_device("weight", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_wt_loglik, d_loglik, d_status, stream,
+                          (d_weights or None, int(n_weights)))
+
+    def weight_prior_device(self, n_sites, d_prior, d_weights, n_weights, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_wt_loglik=0,
+                            d_loglik=0, d_status=0, stream=0):
+        """weight_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("weight", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_wt_loglik, d_loglik, d_status, stream,
+                          (d_weights or None, int(n_weights)))
 
     def allele_tables(self):
         """The allele-level transmission rows origin_batch uses: -> [2 chrX, 2 child sex (0 son, 1 daughter), 2 parent (0 mother,

@@ -952,10 +952,33 @@ void rate_tables(const Model &m, const double *rates, int32_t n_rates, double *t
     build_factor_tables(at, tables + size_t(r) * FAMSEQ_RATE_TABLE_DOUBLES);
   }
 }
+// What the weight entries take beside: the tables [n_weights][N][3] (host entries: the caller's host array, which the library
+// checks and stages; device entries: resident, unchecked) and their number.
+struct WeightIn {
+  const double *weights;
+  int32_t n_weights;
+};
+int check_weights(famseq_ctx *c, const WeightIn &wt, bool device) {
+  const int N = c->model.n_members;
+  if (wt.n_weights < 1 || wt.n_weights > FAMSEQ_MAX_WEIGHTS)
+    return fail(c, FAMSEQ_E_ARG, "n_weights must be 1.." + std::to_string(FAMSEQ_MAX_WEIGHTS) + ", got " + std::to_string(wt.n_weights));
+  if (!wt.weights)
+    return fail(c, FAMSEQ_E_ARG, std::string(device ? "d_weights" : "weights") + " must be given (n_weights tables of three doubles per member)");
+  if (!device)
+    for (size_t i = 0, n = size_t(wt.n_weights) * 3 * N; i < n; ++i)
+      if (!(wt.weights[i] >= 0.0 && wt.weights[i] <= 1.79769313486231570815e308)) {
+        char v[40];
+        std::snprintf(v, sizeof v, "%g", wt.weights[i]);
+        return fail(c, FAMSEQ_E_ARG, "a weight is a finite number >= 0: weight table " + std::to_string(i / (3 * size_t(N))) + ", member " +
+                                         std::to_string(i / 3 % N) + ", genotype " + std::to_string(i % 3) + " is " + v);
+      }
+  return 0;
+}
 int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device, const SideIn &in, const double *prior, void *out_a,
                void *out_b, uint8_t *status, void *stream_ = nullptr, const PatternIn *pat = nullptr, const SampleIn *smp = nullptr,
-               const AfIn *af = nullptr, const RelabelIn *rel = nullptr, const RateIn *mr = nullptr) {
+               const AfIn *af = nullptr, const RelabelIn *rel = nullptr, const RateIn *mr = nullptr, const WeightIn *wt = nullptr) {
   if (!c) return FAMSEQ_E_ARG;
+  if (wt && check_weights(c, *wt, device) != 0) return FAMSEQ_E_ARG;
   if (id == SIDE_ORIGIN && origin_model(c) != 0) return FAMSEQ_E_ARG;  // (said before the device is asked for)
   if (mr && check_rates(c, device ? mr->d_tables : mr->rates, mr->n_rates, device ? "d_tables" : "rates", !device) != 0) return FAMSEQ_E_ARG;
   if (rel && check_relabel(c, *rel, device) != 0) return FAMSEQ_E_ARG;
@@ -1005,7 +1028,11 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
     }
     d_allele = c->d_allele.as<double>();
   }
+  // ... or the weight kernels' tables and their number
+  const double *d_weights = wt ? wt->weights : nullptr;
+  const int32_t n_weights = wt ? wt->n_weights : 1;
   const MoreArgs lead = id == SIDE_ORIGIN ? MoreArgs{&d_allele}
+                        : wt  ? MoreArgs{&d_weights, &n_weights}
                         : mr  ? MoreArgs{&d_tables, &n_rates}
                         : rel ? MoreArgs{&d_assign, &n_assign}
                         : pat ? MoreArgs{&d_masks, &n_patterns}
@@ -1014,7 +1041,14 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
                               : MoreArgs{};
   if (!device) {
     size_t row[2];
-    p.rows(c->model, smp ? n_draws : (rel ? n_assign : (mr ? n_rates : n_patterns)), row);
+    p.rows(c->model, smp ? n_draws : (rel ? n_assign : (mr ? n_rates : (wt ? n_weights : n_patterns))), row);
+    if (wt) {  // (staged as the masks below are)
+      const size_t n = size_t(n_weights) * 3 * c->model.n_members;
+      if (!c->d_weights) HIP_TRY(c, c->d_weights.alloc(size_t(FAMSEQ_MAX_WEIGHTS) * 3 * c->model.n_members * sizeof(double)));
+      c->weights_host.assign(wt->weights, wt->weights + n);
+      HIP_TRY(c, hipMemcpyAsync(c->d_weights.p, c->weights_host.data(), n * sizeof(double), hipMemcpyHostToDevice, c->stream[1]));
+      d_weights = c->d_weights.as<double>();
+    }
     if (mr) {  // (the tables of the call's rates, staged as the masks below are)
       const size_t n = size_t(n_rates) * FAMSEQ_RATE_TABLE_DOUBLES;
       if (!c->d_rate_tables) HIP_TRY(c, c->d_rate_tables.alloc(size_t(FAMSEQ_MAX_RATES) * FAMSEQ_RATE_TABLE_DOUBLES * sizeof(double)));
@@ -1362,6 +1396,41 @@ extern "C" int famseq_origin_prior_batch_device(famseq_ctx *c, int64_t n_sites, 
                                                 double *d_origin, double *d_hettx, uint8_t *d_status, void *stream) {
   return side_entry(c, SIDE_ORIGIN, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_origin, d_hettx,
                     d_status, stream);
+}
+
+// ---- per-member genotype weights: the evidence entries with one table of weights per pass --------------------------------------
+
+extern "C" int famseq_weight_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                   int32_t n_seq, const uint8_t *flags, const double *weights, int32_t n_weights, double *wt_loglik,
+                                   double *loglik, uint8_t *status) {
+  const WeightIn wt{weights, n_weights};
+  return side_entry(c, SIDE_WEIGHT, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, wt_loglik, loglik, status, nullptr,
+                    nullptr, nullptr, nullptr, nullptr, nullptr, &wt);
+}
+
+extern "C" int famseq_weight_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                          const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_weights,
+                                          int32_t n_weights, double *d_wt_loglik, double *d_loglik, uint8_t *d_status, void *stream) {
+  const WeightIn wt{d_weights, n_weights};
+  return side_entry(c, SIDE_WEIGHT, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_wt_loglik, d_loglik,
+                    d_status, stream, nullptr, nullptr, nullptr, nullptr, nullptr, &wt);
+}
+
+extern "C" int famseq_weight_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
+                                         const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
+                                         const double *weights, int32_t n_weights, double *wt_loglik, double *loglik, uint8_t *status) {
+  const WeightIn wt{weights, n_weights};
+  return side_entry(c, SIDE_WEIGHT, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, wt_loglik, loglik, status, nullptr,
+                    nullptr, nullptr, nullptr, nullptr, nullptr, &wt);
+}
+
+extern "C" int famseq_weight_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                                const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                                const double *d_weights, int32_t n_weights, double *d_wt_loglik, double *d_loglik,
+                                                uint8_t *d_status, void *stream) {
+  const WeightIn wt{d_weights, n_weights};
+  return side_entry(c, SIDE_WEIGHT, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_wt_loglik, d_loglik,
+                    d_status, stream, nullptr, nullptr, nullptr, nullptr, nullptr, &wt);
 }
 
 // The sampling kernels' generator on the host: the text they carry (philox_src.h), compiled here.

@@ -55,7 +55,7 @@ struct DevBuf {
 };
 
 // A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp; the trio,
-// MAP, evidence, leave-one-out, pattern, sampling, allele-frequency, relabelling, mutation-rate and origin kinds are the rows of
+// MAP, evidence, leave-one-out, pattern, sampling, allele-frequency, relabelling, mutation-rate, origin and weight kinds are the rows of
 // side_table() below.
 enum KernelKind {
   K_LANE = 0,  // K_LANE + d: the enumeration with 3^d lanes per site; d = 0 (one lane per site) serves large batches,
@@ -83,6 +83,8 @@ enum KernelKind {
   K_MUTRATE_PRIOR,                                 // ... with the founders' prior per site
   K_ORIGIN,                                        // phase by transmission: each child's alleles by parent of origin
   K_ORIGIN_PRIOR,                                  // ... with the founders' prior per site
+  K_WEIGHT,                                        // per-member genotype weights: the sum pass once per weight table
+  K_WEIGHT_PRIOR,                                  // ... with the founders' prior per site
   K_LANE_BULK,  // the one-lane-per-site enumeration in the outer-leaf plan (lane variant 8 + K_LANE's block shape and fencing): serves
                 // large batches where that text differs from K_LANE's (kernels.cpp, bulk_serves); no pick, no contest of its own
   K_COUNT
@@ -126,7 +128,7 @@ struct SlotSet {
 // A side product of the sum-product engine: a generated kernel that takes the common argument list and writes two outputs per
 // site and a status byte, in a plain form and in one that reads the founders' prior per site.  Everything its ABI entries, its
 // prebuild options, its plan keys and its loader differ in is one row of side_table() (kernels.cpp).
-enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_SAMPLE, SIDE_AF, SIDE_RELABEL, SIDE_MUTRATE, SIDE_ORIGIN, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
+enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_SAMPLE, SIDE_AF, SIDE_RELABEL, SIDE_MUTRATE, SIDE_ORIGIN, SIDE_WEIGHT, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
 struct SideProduct {
   const char *stem;   // "trio": the entry points famseq_trio[_prior], the options trio[_prior]_kernels, the plan keys trio[_prior]_*
   const char *what;   // load_or_fail's message starts "[site priors, ]<what> (sum-product engine): "
@@ -135,7 +137,7 @@ struct SideProduct {
                                   // (prior_kind < 0: the product has no site-prior form — no <stem>_prior_* name exists anywhere)
   int n_variants;
   std::string (*source)(const Model &, int variant, int form, bool site_prior);
-  // bytes per site of the two outputs; per_call: what the call itself says of them (the pattern entries' n_patterns, the sampling entries' n_draws, the relabelling entries' n_assign, the mutation-rate entries' n_rates; 1 elsewhere)
+  // bytes per site of the two outputs; per_call: what the call itself says of them (the pattern entries' n_patterns, the sampling entries' n_draws, the relabelling entries' n_assign, the mutation-rate entries' n_rates, the weight entries' n_weights; 1 elsewhere)
   void (*rows)(const Model &, int per_call, size_t row[2]);
   int kind_of(int form, bool site_prior) const { return (site_prior ? prior_kind : kind) + form - 1; }
   bool has_prior() const { return prior_kind >= 0; }
@@ -227,6 +229,9 @@ struct famseq_ctx {
   // ... and the mutation-rate host entries' factor tables: FAMSEQ_MAX_RATES blocks of FAMSEQ_RATE_TABLE_DOUBLES, staged the same way
   famseq::DevBuf d_rate_tables;
   std::vector<double> rate_tables_host;
+  // ... and the weight host entries' tables: FAMSEQ_MAX_WEIGHTS tables of 3 N doubles, staged the same way
+  famseq::DevBuf d_weights;
+  std::vector<double> weights_host;
   // the origin kernels' allele rows (FAMSEQ_ALLELE_TABLE_DOUBLES), uploaded once, on their first use, and never changed; and the
   // mutation rate they are made for, recovered from the model's tables (origin_state: 0 not looked at, 1 found, -1 the tables
   // are nobody's famseq_transmission_tables: no allele-level model)
@@ -256,7 +261,8 @@ inline int fail(famseq_ctx *c, int code, const std::string &msg) {
 // argument's value (hipModuleLaunchKernel's form).  The call-path forms take their CallIO, the site-prior kernels their prior
 // rows, the pattern kernels their masks and n_patterns and the sampling kernels their seed, site_base and n_draws in front of
 // those, the allele-frequency kernel its start values and n_iter, the relabelling kernels their assignments and n_assign, the
-// mutation-rate kernels their tables and n_rates, the origin kernels their allele rows; the plain forms nothing.
+// mutation-rate kernels their tables and n_rates, the origin kernels their allele rows, the weight kernels their tables and
+// n_weights; the plain forms nothing.
 struct MoreArgs {
   static constexpr int kMax = 4;
   void *at[kMax] = {};

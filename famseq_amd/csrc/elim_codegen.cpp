@@ -447,6 +447,44 @@ class Emitter {
     return head.str() + sum_pass() + per_pass + "      }\n";
   }
 
+  // Per-member genotype weights (famseq_weight): the sum pass of evidence_body, run n_weights + 1 times on one read of the
+  // site's rows.  Pass 0 takes the rows as they are; pass m = 1 .. n_weights takes member p's entry g as
+  // r<p>_<g> * wt[(m - 1) * 3 N + 3 p + g] — one rounded multiplication, formed where the names l<p>_<g> are resolved, before
+  // loc() sees it, so the founders' priors, the site's own prior rows, the male chrX row and a cut member's lam all follow
+  // unchanged, and the pass is evidence_body's statements on the rows lk * w formed in double.  Every member has a weight,
+  // sequenced or not (a phenotype needs no reads): an unsequenced member's row is the one the shell supplies.
+  // The weights are read where they lie, through wtp, a wave-uniform pointer (the pass number through readfirstlane, member
+  // and genotype constants of the text), as mutrate_body reads trt: they arrive by scalar loads and cost neither a VGPR nor a
+  // vector-memory instruction per use; (32 + 1) * 3 N doubles would not fit the LDS beside the tables of the wide pedigrees.
+  // Pass 0 multiplies by 1.0, which changes no bit of a row (x * 1.0 is x for every double), so the text is the same in every
+  // pass; its wtp points at the batch's first likelihood row — 3 N readable doubles whatever the call gave as its table, whose
+  // values the select drops — so that wt_g is not read by a call that wants no weighted pass.
+  // The loop is `#pragma unroll 1`: the pass's text stands once whatever n_weights is.  Where the likelihoods sit in registers
+  // (r<p>_<g>: the shell's l<p>_<g> under another name) a pass's weighted values shadow the shell's names; in the lean form the
+  // names are macros and are defined again, row and weight read afresh at each use and multiplied there.
+  // Per pass: Zp_, the pass's total weight (scaled as evidence_body's Z_: evidence_scale_digits()), then `per_pass`.
+  std::string weight_body(const std::string &per_pass) {
+    std::ostringstream head;
+    if (!lean_) {
+      for (int p = 0; p < g_.N; ++p)
+        head << "      const double r" << p << "_0 = l" << p << "_0, r" << p << "_1 = l" << p << "_1, r" << p << "_2 = l" << p << "_2;\n";
+    } else {
+      for (int p = 0; p < g_.N; ++p)
+        for (int g = 0; g < 3; ++g)
+          head << "#undef l" << p << "_" << g << "\n#define l" << p << "_" << g << " __extension__ ({ const double v_ = lgv[" << 3 * p + g
+               << "]; const double w_ = wtp[" << 3 * p + g << "]; v_ * (pu_ == 0 ? 1.0 : w_); })\n";
+    }
+    head << "#pragma unroll 1\n      for (int ps_ = 0; ps_ <= last_; ++ps_) {\n"
+         << "      const int pu_ = __builtin_amdgcn_readfirstlane(ps_);\n"
+         << "      const double *wtp = pu_ == 0 ? lk_g : wt_g + (long)(pu_ - 1) * W3;\n";
+    if (!lean_)
+      for (int p = 0; p < g_.N; ++p)
+        for (int g = 0; g < 3; ++g)
+          head << "      const double wg" << p << "_" << g << " = wtp[" << 3 * p + g << "];\n      const double l" << p << "_" << g << " = r" << p
+               << "_" << g << " * (pu_ == 0 ? 1.0 : wg" << p << "_" << g << ");\n";
+    return head.str() + sum_pass() + per_pass + "      }\n";
+  }
+
   // The founders' allele frequency by maximum likelihood (famseq_af): EM on q, every step one sum pass and the founders' marginals
   // under the Hardy-Weinberg rows of the step's q, all steps on one read of the site's rows.  The loop is `#pragma unroll 1`
   // over it_ = -1 .. n_it_ and its text stands once whatever n_it_ is: pass -1 runs at q = 0 (the rows (1, 0, 0) exactly) and keeps
@@ -1745,6 +1783,51 @@ std::string mutrate_source(const Model &m, int variant, bool site_prior) {
                "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
   d.bt = elim_block_threads(m, false);
   d.fence_single = f >= 3, d.chrx_loop = true, d.site_prior = site_prior;  // (variant 0 too: mutrate_body)
+  return lane_shell(m, d);
+}
+
+// The weight kernel: the evidence kernel's rules and shell, and its LDS (the factor tables alone: a pass's weights are read where
+// they lie).  Beyond the common arguments: wt_g[n_weights][N][3], one table of per-member genotype weights per pass (whatever
+// they hold: nothing is indexed by them; the host entries admit finite numbers >= 0, above 1 included), and n_weights
+// (1 .. FAMSEQ_MAX_WEIGHTS; the host checks, the kernel clamps).  Outputs per site: wt_ll[n_weights], log10 Z_m without the
+// reference's 1e7, Z_m the network's total weight on the rows lk * w_m — not clamped; -inf where Z_m is exactly 0 and +inf where
+// it overflows, which are results — and loglik, famseq_evidence's, from the pass on the rows as they are; either may be null
+// (without wt_ll only that pass runs, and wt_g is not read).  Only the unweighted Z that is not a positive finite number fails
+// the site (status 2).  The rows stay where famseq_evidence has them: registers (twice, as famseq_pattern: the real rows and
+// the pass's weighted copy, which the compiler is free to form at its use instead), lean from forty.
+std::string weight_source(const Model &m, int variant, bool site_prior) {
+  const Graph g = graph_or_throw(m);
+  if (variant < 0 || variant >= kWeightVariants)
+    throw std::runtime_error("weight_source: variant must be 0.." + std::to_string(kWeightVariants - 1));
+  const int f = variant;
+  EmitOptions eo = emit_options(f, "pg", site_prior);
+  LaneShell d;
+  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
+  d.entry = "famseq_weight";
+  d.comment = describe("per-member genotype weights (sum pass per weight table)", g, std::to_string(f), site_prior);
+  d.outputs = "double *__restrict__ wt_ll_g, double *__restrict__ loglik_g";
+  d.more_args = ", const double *__restrict__ wt_g, int n_weights";
+  d.defines = "#define MAXWT " + std::to_string(FAMSEQ_MAX_WEIGHTS) + "\n";
+  d.prologue = "  const int nw_ = n_weights < 0 ? 0 : (n_weights > MAXWT ? MAXWT : n_weights);\n";
+  d.site_decls = "    double *wp = wt_ll_g ? wt_ll_g + site * nw_ : nullptr;\n"
+                 "    const int last_ = wp ? nw_ : 0;\n";
+  d.site_vars = "    double wt_l0 = kNaN;\n";
+  Emitter e(m, g, eo);
+  const std::string digits = std::to_string(e.evidence_scale_digits()) + ".0";
+  d.body = e.weight_body(
+      "      if (ps_ == 0) {\n"
+      "        if (!(Zp_ > 0 && Zp_ <= 1.79769313486231570815e308)) { bn_fail = true; break; }\n"
+      "        wt_l0 = log10(Zp_) - " + digits + ";\n"
+      "      } else {\n"
+      "        __builtin_nontemporal_store(log10(Zp_) - " + digits + ", wp + (ps_ - 1));\n"
+      "      }\n");
+  d.epilogue = "    if (single_fail || bn_fail) {\n      wt_l0 = kNaN;\n"
+               "      if (wp) {\n#pragma unroll 1\n        for (int k = 0; k < nw_; ++k) wp[k] = kNaN;\n      }\n"
+               "    }\n"
+               "    if (loglik_g) __builtin_nontemporal_store(wt_l0, loglik_g + site);\n"
+               "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
+  d.bt = elim_block_threads(m, false);
+  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
   return lane_shell(m, d);
 }
 

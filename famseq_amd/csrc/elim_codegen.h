@@ -110,6 +110,17 @@ constexpr int kMutrateVariants = 4;
 // site_prior: famseq_mutrate_prior, with a trailing `prior` [n_sites][6] behind n_rates (as trio_source's).
 std::string mutrate_source(const Model &m, int variant, bool site_prior = false);
 
+// Per-member genotype weights (famseq_weight_batch).  HIP source of
+// `extern "C" __global__ famseq_weight(lk, flags, wt_ll, loglik, status, n_sites, tc, lc, wt, n_weights)`: per site and table m
+// wt_ll[m] = log10 Z_m, the network's total weight with member p's likelihood entry g multiplied (once, rounded) by
+// wt[m][p][g] — every member's, sequenced or not — on famseq_evidence's scale (-inf where it is exactly 0, not clamped); and
+// loglik, famseq_evidence's, on the rows as they are.  The sum pass of famseq_evidence, n_weights + 1 times on one read of the
+// site's rows; a pass's weights are read through a wave-uniform pointer.  variant 0..3: the fence levels of famseq_elim's;
+// every variant gives the same bits.  Throws if the engine does not serve the pedigree.
+constexpr int kWeightVariants = 4;
+// site_prior: famseq_weight_prior, with a trailing `prior` [n_sites][6] behind n_weights (as trio_source's).
+std::string weight_source(const Model &m, int variant, bool site_prior = false);
+
 // Phase by transmission (famseq_origin_batch).  HIP source of
 // `extern "C" __global__ famseq_origin(lk, flags, origin, hettx, status, n_sites, tc, lc, al)`: per site and child k
 // (trio_children's order) origin[k][2 a + b], the posterior that the child received allele a (0 ref, 1 alt) from its mother and b

@@ -6,6 +6,7 @@
 //              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-loo] [-afTag KEY | -afTagAll KEY]
 //              [-seg dominant|recessive|both -affected ID[,ID...] [-unaffected ID[,ID...]]] [-sample K [-seed S]]
 //              [-afEM T [-afStart X]] [-swapCheck FILE] [-mRateScan FILE [-mRateGrid r1,r2,...]] [-phase]
+//              [-segPen F0,F1,F2[/F0,F1,F2...] -affected ID[,ID...] [-unaffected ID[,ID...]]]
 //   FamSeq LK -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -29,7 +30,8 @@
 // T EM steps and its log10 likelihood ratio against an allele frequency of 0, to the INFO column (FAF, FAL), and -swapCheck FILE (vcf
 // mode) writes, behind the last site, the log10 Bayes factor of every two sequenced samples' exchange over the whole file, and
 // -mRateScan FILE (vcf mode) the file's log10 likelihood at every mutation rate of a grid, and -phase (vcf mode) each child's genotype
-// phased by transmission, maternal|paternal, with its posterior (PGT, PGP).
+// phased by transmission, maternal|paternal, with its posterior (PGT, PGP), and -segPen (vcf mode) the log10 Bayes factor of the
+// phenotypes of -affected / -unaffected under one or more penetrance models, to the INFO column (PSL).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -39,6 +41,7 @@
 #include <fstream>
 #include <future>
 #include <iostream>
+#include <limits>
 #include <charconv>
 #include <chrono>
 #include <condition_variable>
@@ -199,6 +202,12 @@ struct Options {
   // -seg dominant|recessive|both: PSD and / or PSR keys in the INFO column (vcf mode), the posterior probability of the genotype
   // pattern that model gives the members of -affected and -unaffected (PED IDs, comma-separated)
   string seg, affected, unaffected;
+  // -segPen F0,F1,F2[/F0,F1,F2...]: for each penetrance model (the probability of being affected given 0, 1, 2 alt alleles) the
+  // log10 Bayes factor of the phenotypes of -affected / -unaffected (vcf mode).  pen: three numbers per model; pen_bad: the first
+  // model that is not three numbers in [0, 1], as it was given
+  bool pen_given = false, pen_is_bad = false;
+  vector<double> pen;
+  string pen_bad;
   // -afEM T [-afStart X]: FAF and FAL keys in the INFO column (vcf mode), the founders' allele frequency after T EM steps from X and
   // the log10 likelihood ratio against "no founder carries the allele" (kAfUnset: not given; kAfBad: given, not a number)
   static constexpr int kAfUnset = -1, kAfBad = -2;
@@ -414,6 +423,29 @@ int parse_options(int argc, char **argv, Options &o) {
         const double v = std::strtod(entry.c_str(), &stop);
         if ((entry.empty() || *stop || !(v >= 0.0 && v <= 1.0)) && !o.rate_grid_is_bad) o.rate_grid_is_bad = true, o.rate_grid_bad = entry;
         o.rate_grid.push_back(v);
+        at = end + 1;
+      }
+    } else if (opt == "segPen") {  // (what may be wrong with it: check_seg_pen, with the other side options' checks)
+      o.pen_given = true;
+      o.pen.clear();
+      // (no value, or one that starts like an option: one empty model, which check_seg_pen refuses)
+      const string text = missing(i + 1) ? "" : argv[++i];
+      for (size_t at = 0; at <= text.size();) {
+        const size_t end = std::min(text.find('/', at), text.size());
+        const string model = text.substr(at, end - at);
+        int got = 0;
+        bool bad = false;
+        for (size_t f = 0; f <= model.size();) {
+          const size_t fe = std::min(model.find(',', f), model.size());
+          const string entry = model.substr(f, fe - f);
+          char *stop = nullptr;
+          const double v = std::strtod(entry.c_str(), &stop);
+          bad = bad || entry.empty() || *stop || !(v >= 0.0 && v <= 1.0);
+          if (got < 3) o.pen.push_back(v);
+          ++got, f = fe + 1;
+        }
+        if ((bad || got != 3) && !o.pen_is_bad) o.pen_is_bad = true, o.pen_bad = model;
+        for (; got < 3; ++got) o.pen.push_back(0.0);
         at = end + 1;
       }
     } else if (opt == "seg" || opt == "affected" || opt == "unaffected") {
@@ -829,6 +861,8 @@ bool sum_product_serves(const Options &o, const Ped &ped, const char *flag_text)
   return k >= 0;
 }
 
+bool phenotype_roles(const Options &o, const Ped &ped, vector<int> &role);
+
 // -seg: the mask rows of its patterns in the order they are printed (PSD, PSR), [n_patterns][N] in PED order, from the PED IDs of
 // -affected and -unaffected.  false with a message: an unknown model, no -affected, an ID the PED file does not hold, an ID in both.
 bool segregation_masks(const Options &o, const Ped &ped, vector<uint8_t> &masks, vector<const char *> &keys) {
@@ -840,7 +874,21 @@ bool segregation_masks(const Options &o, const Ped &ped, vector<uint8_t> &masks,
     std::cout << "-seg needs the affected members: -affected ID[,ID...] (PED IDs)." << std::endl;
     return false;
   }
-  vector<int> role(ped.n(), 0);  // 1 affected, 2 unaffected
+  vector<int> role;
+  if (!phenotype_roles(o, ped, role)) return false;
+  masks.clear(), keys.clear();
+  for (int model = 0; model < 2; ++model) {  // dominant: affected 6, unaffected 1; recessive: 4, 3; anyone else 7
+    if (o.seg != "both" && o.seg != (model ? "recessive" : "dominant")) continue;
+    keys.push_back(model ? "PSR=" : "PSD=");
+    for (int i = 0; i < ped.n(); ++i) masks.push_back(role[i] == 1 ? (model ? 4 : 6) : (role[i] == 2 ? (model ? 3 : 1) : 7));
+  }
+  return true;
+}
+
+// The members of -affected and -unaffected (-seg, -segPen): role[i] of member i (PED order) 1 affected, 2 unaffected, 0 neither.
+// false with a message: an ID the PED file does not hold, an ID in both.
+bool phenotype_roles(const Options &o, const Ped &ped, vector<int> &role) {
+  role.assign(ped.n(), 0);
   for (int r = 1; r <= 2; ++r) {
     std::istringstream in(r == 1 ? o.affected : o.unaffected);
     string tok;
@@ -861,12 +909,18 @@ bool segregation_masks(const Options &o, const Ped &ped, vector<uint8_t> &masks,
       role[at] = r;
     }
   }
-  masks.clear(), keys.clear();
-  for (int model = 0; model < 2; ++model) {  // dominant: affected 6, unaffected 1; recessive: 4, 3; anyone else 7
-    if (o.seg != "both" && o.seg != (model ? "recessive" : "dominant")) continue;
-    keys.push_back(model ? "PSR=" : "PSD=");
-    for (int i = 0; i < ped.n(); ++i) masks.push_back(role[i] == 1 ? (model ? 4 : 6) : (role[i] == 2 ? (model ? 3 : 1) : 7));
-  }
+  return true;
+}
+
+// -segPen: the weight tables of its models, [n_models][N][3] in PED order: an affected member's row is the model's (f0, f1, f2),
+// an unaffected member's 1 - f, anyone else's ones.  false with a message, as phenotype_roles.
+bool penetrance_tables(const Options &o, const Ped &ped, vector<double> &tables) {
+  vector<int> role;
+  if (!phenotype_roles(o, ped, role)) return false;
+  tables.clear();
+  for (size_t m = 0; m < o.pen.size() / 3; ++m)
+    for (int i = 0; i < ped.n(); ++i)
+      for (int g = 0; g < 3; ++g) tables.push_back(role[i] == 1 ? o.pen[3 * m + g] : (role[i] == 2 ? 1.0 - o.pen[3 * m + g] : 1.0));
   return true;
 }
 
@@ -1426,11 +1480,11 @@ struct Part {
 // ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample, -seg and -afEM add to a line, one row of kSide each; -swapCheck and
 // ---- -mRateScan, which add nothing to any line and write a report of their own behind the last site (SideRow::report), are rows too
 // The order is the one main checks them and prints its notices in; it is also the order of the fields in a sample column (DNP,
-// JGT:JP, LOP:LOF, SGT, PGT:PGP) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL).  Header lines have their
+// JGT:JP, LOP:LOF, SGT, PGT:PGP) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL, then PSL).  Header lines have their
 // own order.
-enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap, kRateScan, kPhase };
-constexpr int kSides = kPhase + 1;
-const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap, kRateScan, kPhase};
+enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap, kRateScan, kPhase, kSegPen };
+constexpr int kSides = kSegPen + 1;
+const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap, kRateScan, kPhase, kSegPen};
 
 // One side output of a block: the two arrays its C entry fills ([site][...], read as the entry's own types) and its status per site.
 struct SideOut {
@@ -1493,6 +1547,9 @@ struct VcfRun {
   bool use_af = false;
   vector<uint8_t> seg_masks;  // -seg: the patterns' mask rows and INFO keys
   vector<const char *> seg_keys;
+  // -segPen: the models' weight tables [n_models][N][3], and the all-ones likelihood rows of the null call (grown to the largest
+  // block: the phenotypes' probability under the pedigree and the founders' prior alone, by the block's flags and priors)
+  vector<double> pen_tables, ones_lk;
   // -swapCheck: the exchange of every two sequenced samples, in VCF column order, as assignment rows [pair][N] (PED order), and
   // what the sites so far add up to, in file order: per pair the sum of alt_loglik - loglik over the used sites where alt_loglik
   // is finite and the number of used sites where it is -inf; the used and the skipped (status != 0) sites, the used sites' loglik
@@ -1544,6 +1601,7 @@ struct VcfRun {
     use_af = !o.af_tag.empty() && !o.pack_mode;
     // (main has checked -seg's options: this cannot fail here)
     if (!o.seg.empty() && !o.pack_mode && !segregation_masks(o, ped, seg_masks, seg_keys)) return false;
+    if (o.pen_given && !o.pack_mode && !penetrance_tables(o, ped, pen_tables)) return false;
     for (int k = 0; k < 3; ++k) {
       model_rows[0][k] = m.p.genoProbN[k], model_rows[0][3 + k] = m.p.genoProbXN[k];
       model_rows[1][k] = m.p.genoProbK[k], model_rows[1][3 + k] = m.p.genoProbXK[k];
@@ -1919,6 +1977,7 @@ struct VcfRun {
       case kSample: rc = entry(famseq_sample_batch, famseq_sample_prior_batch, o.seed, sl.site_base, (int32_t)o.sample, a8, none, st); break;
       case kSeg: rc = entry(famseq_pattern_batch, famseq_pattern_prior_batch, seg_masks.data(), (int32_t)seg_keys.size(), a, none, st); break;
       case kSwap: return call_swap(sl, so, lk, pl16);
+      case kSegPen: rc = call_seg_pen(sl, so, lk, pl16); break;
       case kPhase:
         so.flags = sl.io.flags;
         rc = entry(famseq_origin_batch, famseq_origin_prior_batch, n_kids ? a : none, none, st);
@@ -1937,6 +1996,36 @@ struct VcfRun {
       std::cerr << row.entry << (use_af && row.id != kAfEm ? "_prior_batch" : "_batch") << " failed (" << rc << "): " << famseq_last_error(ctx) << std::endl;
       flush_ok = false;
     }
+  }
+  // -segPen: two launches per block.  The first on the block's rows, the second — the null — on all-ones rows with the block's
+  // flags and priors: the phenotypes' probability under the pedigree and the founders' prior alone.  Leaves in so.a[s * M + m]
+  // what PSL prints, (wt_ll - loglik) - (wt_ll0 - loglik0): NaN where the site failed or the null is -inf, and no status but 0
+  // (a failed site prints "." like a value that does not exist).
+  int call_seg_pen(Slot &sl, SideOut &so, const double *lk, const uint16_t *pl16) {
+    const size_t n = sl.n_sites, M = o.pen.size() / 3;
+    if (ones_lk.size() < n * N3) ones_lk.assign(n * N3, 1.0);
+    double *const a = so.a.data(), *const a0 = a + n * M, *const b = so.b.data(), *const b0 = b + n;
+    uint8_t *const st = so.status.data();
+    vector<uint8_t> st0(n);
+    const double *w = pen_tables.data();
+    int rc;
+    if (use_af) {
+      rc = famseq_weight_prior_batch(ctx, (int64_t)n, lk, pl16, cm.members.data(), (int32_t)n_seq, sl.io.flags, sl.prior.data(), w, (int32_t)M, a, b, st);
+      if (rc == 0) rc = famseq_weight_prior_batch(ctx, (int64_t)n, ones_lk.data(), nullptr, nullptr, 0, sl.io.flags, sl.prior.data(), w, (int32_t)M, a0, b0, st0.data());
+    } else {
+      rc = famseq_weight_batch(ctx, (int64_t)n, lk, pl16, cm.members.data(), (int32_t)n_seq, sl.io.flags, w, (int32_t)M, a, b, st);
+      if (rc == 0) rc = famseq_weight_batch(ctx, (int64_t)n, ones_lk.data(), nullptr, nullptr, 0, sl.io.flags, w, (int32_t)M, a0, b0, st0.data());
+    }
+    if (rc != 0) return rc;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t s = 0; s < n; ++s) {
+      for (size_t m = 0; m < M; ++m) {
+        const double null = a0[s * M + m] - b0[s];
+        a[s * M + m] = (st[s] != 0 || st0[s] != 0 || !std::isfinite(null)) ? nan : (a[s * M + m] - b[s]) - null;
+      }
+      st[s] = 0;
+    }
+    return 0;
   }
   // -swapCheck: the pairs in groups of at most FAMSEQ_MAX_RELABEL per call, each group's columns summed up over the block's
   // sites in file order behind its call (a pair's sum is its own: the order of the pairs does not enter).  The first group also
@@ -2264,8 +2353,23 @@ inline void put_phase(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s
   out.num(p[best]);
 }
 
+// -segPen: one value per model, printed as FLL's are; "-inf" where the data rule the phenotypes out under the model, "." where
+// there is no value (VcfRun::call_seg_pen)
+inline void put_psl(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t) {
+  const size_t M = r.o.pen.size() / 3;
+  out.put("PSL=", 4);
+  for (size_t m = 0; m < M; ++m) {
+    if (m) out.ch(',');
+    const double v = so.a[s * M + m];
+    if (std::isnan(v)) out.ch('.');
+    else if (std::isinf(v)) v < 0 ? out.put("-inf", 4) : out.put("inf", 3);
+    else out.num(v);
+  }
+}
+
 [[gnu::always_inline]] inline void put_side(SideId id, TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {
   switch (id) {
+    case kSegPen: return put_psl(out, r, so, s, j);
     case kPhase: return put_phase(out, r, so, s, j);
     case kDnm: return put_dnp(out, r, so, s, j);
     case kMap: return put_map(out, r, so, s, j);
@@ -2281,13 +2385,31 @@ inline void put_phase(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s
 
 // -seg's own options: -affected / -unaffected without it, an unknown model or ID
 bool check_seg(const Options &o, const Ped &ped) {
-  if (o.seg.empty()) {
+  if (o.seg.empty()) {  // (with -segPen the two lists are its own and this row is off)
     std::cout << "-affected and -unaffected belong to -seg dominant|recessive|both, which was not given." << std::endl;
     return false;
   }
   vector<uint8_t> masks;
   vector<const char *> keys;
   return segregation_masks(o, ped, masks, keys);
+}
+
+// -segPen's own: 1 .. FAMSEQ_MAX_WEIGHTS models of three numbers in [0, 1], -affected, and the IDs of both lists
+bool check_seg_pen(const Options &o, const Ped &ped) {
+  if (o.pen_is_bad) {
+    std::cout << "-segPen takes penetrance models F0,F1,F2[/F0,F1,F2...], three numbers in [0, 1] each, not \"" << o.pen_bad << "\"." << std::endl;
+    return false;
+  }
+  if (o.pen.size() / 3 > FAMSEQ_MAX_WEIGHTS) {
+    std::cout << "-segPen takes at most " << FAMSEQ_MAX_WEIGHTS << " models, not " << o.pen.size() / 3 << "." << std::endl;
+    return false;
+  }
+  if (o.affected.empty()) {
+    std::cout << "-segPen needs the affected members: -affected ID[,ID...] (PED IDs)." << std::endl;
+    return false;
+  }
+  vector<double> tables;
+  return penetrance_tables(o, ped, tables);
 }
 
 // -afEM's own options: -afStart without it, a step count or a start value out of range
@@ -2384,7 +2506,9 @@ const SideRow kSide[kSides] = {
      },
      ":SGT", ":NA", [](const VcfRun &r) { return SideBytes{size_t(r.o.sample) * size_t(r.ped.n()), 0}; }},
     // (on: any of its three options, so that main can say which one is missing)
-    {kSeg, "-seg", "famseq_pattern", true, [](const Options &o) { return !(o.seg.empty() && o.affected.empty() && o.unaffected.empty()); },
+    // (with -segPen and without -seg the two lists are -segPen's)
+    {kSeg, "-seg", "famseq_pattern", true,
+     [](const Options &o) { return !o.seg.empty() || (!o.pen_given && !(o.affected.empty() && o.unaffected.empty())); },
      [](Options &o) { o.seg.clear(), o.affected.clear(), o.unaffected.clear(); }, check_seg,
      [](std::ostream &out, const Options &o) {
        if (o.seg != "recessive")
@@ -2420,6 +2544,15 @@ const SideRow kSide[kSides] = {
        out << "##FORMAT=<ID=PGP,Number=1,Type=Float,Description=\"Posterior probability of that maternal|paternal pair\">" << std::endl;
      },
      ":PGT:PGP", ":.:.", [](const VcfRun &r) { return SideBytes{32 * size_t(r.n_kids), 0}; }},
+    // (its bytes: wt_loglik and loglik of the block's rows and of the null call's, VcfRun::call_seg_pen)
+    {kSegPen, "-segPen", "famseq_weight", true, [](const Options &o) { return o.pen_given; },
+     [](Options &o) { o.pen_given = false, o.pen.clear(); }, check_seg_pen,
+     [](std::ostream &out, const Options &) {
+       out << "##INFO=<ID=PSL,Number=.,Type=Float,Description=\"log10 Bayes factor of the phenotypes of the affected and unaffected members "
+              "under each penetrance model of -segPen: their probability given the whole family's data over their probability under the "
+              "pedigree and the founders' prior alone (-inf: the data rule them out; .: no value)\">" << std::endl;
+     },
+     nullptr, nullptr, [](const VcfRun &r) { return SideBytes{16 * (r.o.pen.size() / 3), 16}; }},
 };
 
 // `FamSeq vcf` and `FamSeq pack`: the wiring of a VcfRun's stages
@@ -2653,6 +2786,12 @@ void help() {
             << "\t\town -mRate, and n_impossible, the sites impossible at the rate; the last line names the best rate of the grid, line 1 counts" << std::endl
             << "\t\tthe sites used and skipped (failed). Adds nothing to any output line. Implies -method 2; may be combined with every other" << std::endl
             << "\t\toption above, under -afTagAll with the line's prior; not with -afTag." << std::endl
+            << "-segPen MODELS\t(vcf) MODELS F0,F1,F2[/F0,F1,F2...], 1.." << FAMSEQ_MAX_WEIGHTS << " penetrance models (the probability of being affected given 0, 1," << std::endl
+            << "\t\t2 alt alleles, numbers in [0, 1]), with -affected ID[,ID...] and optionally -unaffected ID[,ID...] (PED IDs): add PSL, one" << std::endl
+            << "\t\tvalue per model, the log10 Bayes factor of the phenotypes: their probability given the whole family's data (phenocopies" << std::endl
+            << "\t\tand incomplete penetrance allowed: -seg dominant is the corner 0,1,1) over their probability under the pedigree and the" << std::endl
+            << "\t\tfounders' prior alone; -inf where the data rule them out, . where the site failed. With or without -seg. Implies" << std::endl
+            << "\t\t-method 2; may be combined with every other option above, under -afTagAll with the line's prior; not with -afTag." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl

@@ -47,6 +47,9 @@ SideTable &side_table() {
       {"origin", "phase by transmission", "1", K_ORIGIN, K_ORIGIN_PRIOR, 1, kOriginVariants,
        [](const Model &m, int v, int, bool site_prior) { return origin_source(m, v, site_prior); },
        [](const Model &m, int, size_t row[2]) { row[0] = row[1] = 4 * trio_children(m).size() * sizeof(double); }},  // origin[K][4], hettx[K][4]
+      {"weight", "per-member genotype weights", "1", K_WEIGHT, K_WEIGHT_PRIOR, 1, kWeightVariants,
+       [](const Model &m, int v, int, bool site_prior) { return weight_source(m, v, site_prior); },
+       [](const Model &, int n_weights, size_t row[2]) { row[0] = size_t(n_weights) * sizeof(double), row[1] = sizeof(double); }},  // wt_loglik[M], loglik
   };
   return table;
 }

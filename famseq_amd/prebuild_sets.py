@@ -14,13 +14,14 @@ WIDE_EXTRA_SIZES = (128,)       # beyond what LDS rows could stage: tests/test_w
 # sum-product generator — loop-free, one conditioned member with everybody sequenced, three conditioned members with three
 # members unsequenced — on which every fence level of every side-product kernel is forced in turn
 SIDE_VARIANT_PEDIGREES = ("trio", "cousins", "random15")
-SIDE_VARIANTS = 4               # kTrioVariants .. kOriginVariants (csrc/elim_codegen.h)
+SIDE_VARIANTS = 4               # kTrioVariants .. kWeightVariants (csrc/elim_codegen.h)
 # (stem, output forms, has a site-prior sibling): side_table() of csrc/kernels.cpp
 SIDE_PRODUCTS = (("trio", 3, True), ("map", 1, True), ("evidence", 1, True), ("loo", 1, True), ("pattern", 1, True),
                  ("sample", 1, True), ("af", 1, False), ("relabel", 1, True))
 # ... and the rows side_table() has gained since tests/_side_variants.py's matrix was drawn up (their own GPU tests force their
-# levels: tests/test_gpu_mutrate.py, tests/test_gpu_origin.py); build() pre-builds the four levels of both lists
-SIDE_PRODUCTS_SINCE = (("mutrate", 1, True), ("origin", 1, True))
+# levels: tests/test_gpu_mutrate.py, tests/test_gpu_origin.py, tests/test_gpu_weight.py); build() pre-builds the four levels of both
+# lists
+SIDE_PRODUCTS_SINCE = (("mutrate", 1, True), ("origin", 1, True), ("weight", 1, True))
 
 
 # The pedigrees on which the lane kernel's variants 4-11 (csrc/enum_codegen.h: 4-7 the once-per-site form, 8-11 the outer-leaf

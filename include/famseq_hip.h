@@ -794,6 +794,63 @@ int famseq_origin_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const dou
                                      const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                      double *d_origin, double *d_hettx, uint8_t *d_status, void *stream);
 
+/* ---- per-member genotype weights: the expectation of a product of per-member factors under the joint posterior ---------------
+ * E[ prod_p w_p(g_p) | data ] = Z(lk o w) / Z(lk), for up to FAMSEQ_MAX_WEIGHTS weight tables w at once: the soft form of the
+ * pattern entries' 0/1 masks.  With w_p = the penetrance (f0, f1, f2) of an affected member and 1 - f of an unaffected one it is
+ * P(phenotypes | reads, pedigree) with phenocopies and incomplete penetrance; with w = t^count a moment generating function of a
+ * genotype count; a phenotype likelihood folded into the evidence.
+ *   weights [n_weights][N][3]   member p's weight of genotype g in table m at weights[(m * N + p) * 3 + g], the same for every
+ *              site of the call; every member has a row, sequenced or not.  Finite numbers >= 0; above 1 is legal.
+ *   n_weights               1 .. FAMSEQ_MAX_WEIGHTS.
+ *   wt_loglik [n_sites][n_weights]   log10 Z_m on famseq_evidence_batch's scale, Z_m the network's total weight with every
+ *              likelihood entry multiplied once, in double, by its weight.  The contract: wherever famseq_evidence_batch (the
+ *              prior form: famseq_evidence_prior_batch) answers status 0 on the rows lk[s][p][g] * weights[m][p][g] formed in
+ *              double on the host, wt_loglik[s][m] is that call's loglik, bit for bit; where it does not although this call has
+ *              status 0, Z_m is exactly 0 and the entry is -inf, which is a result, not a failure.  Hence a column depends on
+ *              neither n_weights nor the other tables; a table of ones gives loglik's bits; equal tables give equal bits; a 0/1
+ *              table gives the Z_m of the pattern with those masks (10^(wt_loglik - loglik) is famseq_pattern_batch's posterior
+ *              up to its own rounding); packed and fp64 input give the same bits.  Nothing is clamped: a Z_m that overflows
+ *              gives +inf, a result.
+ *   loglik [n_sites]        famseq_evidence_batch's bits on the rows as they are.
+ *   status [n_sites]        0 OK; 1 the single-posterior failure rule of famseq_bn_batch, applied to the rows as given; 2 the
+ *              unweighted total weight Z is <= 0 or not finite.  Wherever status != 0, wt_loglik and loglik of the site are NaN.
+ *              There is no -LRC shortcut.
+ * One kernel launch reads a site's rows once and runs the sum pass n_weights + 1 times on them, a pass's weights arriving
+ * through a wave-uniform pointer.  Served by the sum-product engine's graph as famseq_evidence_batch is, whatever the context's
+ * engine; compiled on the first call or ahead through famseq_set_option "weight_kernels" = 1 (a context without a device
+ * generates and cross-compiles it).  famseq_plan_json: "weight_code_object", "weight_variant".
+ * FAMSEQ_E_ARG, with a message and before the device is asked for: n_weights outside 1 .. FAMSEQ_MAX_WEIGHTS, weights /
+ * d_weights NULL, (host entries) the first weight that is not a finite number >= 0 ("... weight table 2, member 1, genotype 0
+ * is -0.5"), a pedigree the engine does not serve (the engine's message). */
+#define FAMSEQ_MAX_WEIGHTS 32
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_evidence_batch.  weights is a host array; the library checks
+ * it and stages it on the stream the chunks' kernels run on.  Any of wt_loglik / loglik / status may be NULL; without wt_loglik
+ * only the unweighted pass runs. */
+int famseq_weight_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                        int32_t n_seq, const uint8_t *flags, const double *weights, int32_t n_weights,
+                        double *wt_loglik /*[n_sites][n_weights]*/, double *loglik /*[n_sites]*/, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array), d_weights [n_weights][N][3] among them — it
+ * must stay valid and unchanged until the kernel has run, and nothing is checked of its contents: the kernel indexes nothing by
+ * them.  Enqueues on `stream` (a hipStream_t; NULL = the default stream) and returns without synchronising (the stream rule at
+ * famseq_bn_batch_device: with d_lk no context state, no event and no wait; with d_pl16 through the kept scratch rows, like every
+ * side entry). */
+int famseq_weight_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                               const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_weights,
+                               int32_t n_weights, double *d_wt_loglik, double *d_loglik, uint8_t *d_status, void *stream);
+
+/* With the founders' genotype prior given per site: prior[n_sites][6], as for famseq_evidence_prior_batch.  Given rows that equal
+ * the model's constants the outputs are, bit for bit, famseq_weight_batch's.  "weight_prior_kernels" = 1 builds the kernel
+ * (famseq_weight_prior) ahead; famseq_plan_json: "weight_prior_code_object", "weight_prior_variant". */
+int famseq_weight_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                              int32_t n_seq, const uint8_t *flags, const double *prior, const double *weights, int32_t n_weights,
+                              double *wt_loglik, double *loglik, uint8_t *status);
+int famseq_weight_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                     const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                     const double *d_weights, int32_t n_weights, double *d_wt_loglik, double *d_loglik,
+                                     uint8_t *d_status, void *stream);
+
 /* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] =((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);

@@ -7,9 +7,20 @@ level the unforced contest (csrc/jit.cpp jit_pick_variant: the first that spills
 No GPU: plan-only contexts; after build() every object is a cache hit.
 
     python tools/side_variant_resources.py > profiles/side_variants/resources.txt
+
+With arguments, one product on pedigrees of the caller's choice, registers and LDS too:
+
+    python tools/side_variant_resources.py weight trio ped10 wide32 wide48 > profiles/weight/resources.txt
+
+prints, for each pedigree (a synthetic_pedigree name, or wide<N>) and each of the product's eight code objects (fence levels 0..3,
+plain and site-prior), VGPRs, AGPRs, scratch, waves per SIMD and LDS from the compiler's remarks on the kept source (hipcc
+--offload-arch=gfx950 with the flags of csrc/jit.cpp; no GPU), and the level the contest takes.
 """
 import os
+import re
+import subprocess
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
@@ -52,5 +63,46 @@ def main():
                     print("  %-9s %-15s %4d | %5d %5d %5d %5d | v%d" % (name, key, form, *scratch, taken))
 
 
+def remarks(src):
+    """The kernel-resource-usage remarks of one kept source -> {name: value}."""
+    p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--genco",
+                        "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, src], capture_output=True, text=True, check=True)
+    return {k.strip(): int(v) for k, v in re.findall(r"remark: +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", p.stderr)}
+
+
+def one_product(stem, names):
+    print("# registers, scratch (bytes per lane), waves per SIMD and LDS (bytes per workgroup) of famseq_%s / famseq_%s_prior, every fence level" % (stem, stem))
+    print("# (gfx950, -O3, -ffp-contract=off; from the compiler's remarks on each kept source), and the level the contest takes")
+    with tempfile.TemporaryDirectory() as cache:
+        os.environ["FAMSEQ_KERNEL_CACHE"], os.environ["FAMSEQ_KEEP_SRC"] = cache, "1"
+        for name in names:
+            ped = sets.wide_pedigree(int(name[4:])) if name.startswith("wide") else fs.synthetic_pedigree(name)
+            print("== %s (%d members)" % (name, ped.n))
+            for key in (stem, stem + "_prior"):
+                taken = None
+                for v in list(range(sets.SIDE_VARIANTS)) + [None]:
+                    os.environ.pop("FAMSEQ_VARIANT_ONLY", None)
+                    if v is not None:
+                        os.environ["FAMSEQ_VARIANT_ONLY"] = str(v)
+                    ctx = fs.Context(fs.make_model(ped), device=-1)
+                    try:
+                        ctx.set_option(key + "_kernels", 1)
+                        plan = ctx.plan()
+                    finally:
+                        ctx.close()
+                        os.environ.pop("FAMSEQ_VARIANT_ONLY", None)
+                    if v is None:
+                        taken = plan[key + "_variant"]
+                        continue
+                    assert plan[key + "_variant"] == v
+                    r = remarks(plan[key + "_code_object"][:-6] + ".hip")
+                    print("  %-14s v%d | VGPRs %3d  AGPRs %3d  scratch %4d  VGPRs spilled %3d  waves/SIMD %d  LDS %5d" %
+                          (key, v, r["VGPRs"], r["AGPRs"], r["ScratchSize"], r["VGPRs Spill"], r["Occupancy"], r["LDS Size"]))
+                print("  %-14s contest: v%d" % (key, taken))
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 2:
+        one_product(sys.argv[1], sys.argv[2:])
+    else:
+        main()
