@@ -1685,6 +1685,10 @@ std::string pattern_source(const Model &m, int variant, bool site_prior) {
 // of 3 (N + 1) doubles (odd stride: no bank conflicts) fit the 64 KB of static LDS beside the tables they sit there, read once
 // per pass into the pass's registers; otherwise, and from forty members on as every lean kernel, the site's row in global memory
 // is read again at each use.  FAMSEQ_RELABEL_LEAN=1 (a tuning aid) takes the second form at every size.
+// That makes three forms, not two.  With 64-lane workgroups the budget ends at 37 members (64 936 bytes; 38 members need
+// 65 960), not at 39: at 38 and 39 members the shell already reads global rows (d.lean) while the emitter is not lean yet
+// (eo.lean, from forty on) and keeps its local factors in variables.  tests/test_edge_pedigrees.py pins the three from the
+// emitted text (edge37, edge38 / edge39, edge40 of famseq_amd/prebuild_sets.py), tests/test_gpu_edge_pedigrees.py runs them.
 std::string relabel_source(const Model &m, int variant, bool site_prior) {
   const Graph g = graph_or_throw(m);
   if (variant < 0 || variant >= kRelabelVariants)

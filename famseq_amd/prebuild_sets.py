@@ -52,6 +52,40 @@ LANE_FORM_PEDIGREES = {
 GROWN_SEEDS = {11: 32109, 13: 32319}  # grown<n>: RandomState seeds found by a scan of grown pedigrees of n members that take the form
 
 
+# The edges of the sum-product generator's decision space that no other device test reaches (tests/test_gpu_edge_pedigrees.py
+# runs every side product on all nine and the main engines on the looped five; tests/test_edge_pedigrees.py pins every column
+# below, and the forms named here, from plan-only contexts, so that a generator change which moves an edge says which recipe to
+# move).  Each is grow_pedigree(RandomState(seed), n, allow_loops) followed by relations().
+#   edge37..edge40: loop-free, around two size edges.  Every side source is lean (likelihood rows read from memory where they
+#     are used, the emitter's local factors macros over them) from 40 members on; 39 members are the widest register-resident
+#     form, 117 doubles of likelihoods per lane, where the variant contest climbs highest.  relabel_source has three forms: up to
+#     37 members the lane's rows in LDS (BT = 64: 64 936 of 65 536 bytes at 37), at 38 and 39 the shell reads the site's row
+#     from global memory while the emitter is not lean, from 40 on both are lean.
+#   loop12..loop20: marriage loops above ten members (1 to 3 conditioned members: 3, 9 or 27 passes over a long message
+#     schedule, and the call path's 128-lane workgroups, which start at 11 members).
+# name -> (seed, members, loops allowed, sequenced members, conditioned members, the mutation rate its tests make the model with)
+EDGE_PEDIGREES = {
+    "edge37": (53037, 37, False, 29, 0, 1e-7),
+    "edge38": (53038, 38, False, 29, 0, 1e-4),
+    "edge39": (53039, 39, False, 26, 0, 1e-7),
+    "edge40": (53040, 40, False, 31, 0, 0.0),
+    "loop12": (53202, 12, True, 8, 3, 0.0),
+    "loop13": (53300, 13, True, 12, 2, 1e-4),
+    "loop14": (53403, 14, True, 10, 1, 1e-7),
+    "loop16": (53600, 16, True, 10, 3, 0.0),
+    "loop20": (54000, 20, True, 18, 3, 1e-7),
+}
+EDGE_LANE_MAX = 13  # the looped recipes of at most this many members also run the lane enumeration kernel (3^13 per site)
+
+
+def edge_pedigree(name):
+    """A pedigree of EDGE_PEDIGREES."""
+    seed, n, loops = EDGE_PEDIGREES[name][:3]
+    ped = grow_pedigree(np.random.RandomState(seed), n, allow_loops=loops)
+    ped.relations()
+    return ped
+
+
 def lane_form_pedigree(name):
     """A pedigree of LANE_FORM_PEDIGREES (the matrices run every one at mutation rate 0): a side_variant_pedigree name,
     soak<seed> (soak_pedigree's pedigree, not its mutation rate) or grown<n>."""

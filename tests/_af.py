@@ -4,7 +4,9 @@ the device): the reference, a numpy EM loop over the project's existing referenc
 Per step at q: the founders' rows are fs.hwe_priors(q); Z(q) is tests/_prior_joint.py's factors through tests/_maxproduct.py's
 elimination (with the reference's 1e7); the founders' marginals come, up to twenty members, from tests/_prior.py's reference
 (the compiled oracle, one model per site, its -LRC shortcut switched off) and beyond from the same elimination: three totals per
-founder, that founder's row masked to one genotype.  The update is the ABI's:
+founder, that founder's row masked to one genotype (oracle_upto lowers the size at which the elimination takes over: the oracle
+enumerates 3^N configurations per site, which above some thirteen members is no reference a test can wait for).  The update is
+the ABI's:
     A = sum over founders, PED order, of (m1 + 2 m2) / (m0 + m1 + m2)   [male founder at a chrX site: m2 / (m0 + m1 + m2)]
     C = 2 founders   [chrX: 2 female founders + male founders];   q' = min(A / C, 1)
 Z(0) is the elimination under rows (1, 0, 0), which is what hwe_priors(0) gives exactly.
@@ -30,10 +32,10 @@ def founders_of(ped):
     return [p for p in range(ped.n) if mo[p] < 0]
 
 
-def founder_rows(ped, mrate, lk, flags, prior):
+def founder_rows(ped, mrate, lk, flags, prior, oracle_upto=20):
     """{founder: m[S, 3]}: the founders' marginal rows (any positive scale) under prior[S, 6]."""
     founders = founders_of(ped)
-    if ped.n <= 20:
+    if ped.n <= oracle_upto:
         post, _, st = P.reference(ped, lk, flags, prior, mrate=mrate, lc=2.0)
         assert np.all(st == 0)
         return {f: post[:, f] for f in founders}
@@ -49,10 +51,10 @@ def founder_rows(ped, mrate, lk, flags, prior):
     return rows
 
 
-def step(ped, mrate, lk, flags, q):
+def step(ped, mrate, lk, flags, q, oracle_upto=20):
     """One EM step from q[S] -> q'[S]."""
     chrx = (np.asarray(flags) & fs.FLAG_CHRX) != 0
-    rows = founder_rows(ped, mrate, lk, flags, fs.hwe_priors(q))
+    rows = founder_rows(ped, mrate, lk, flags, fs.hwe_priors(q), oracle_upto)
     a = np.zeros(len(q))
     n_female = n_male = 0
     for f in founders_of(ped):  # PED order, left to right
@@ -71,7 +73,7 @@ class Reference:
     status[S] (under af0's rows).  The caller's sites are expected to be good ones: every step asserts it."""
 
 
-def reference(ped, mrate, lk, flags, af0, n_iter):
+def reference(ped, mrate, lk, flags, af0, n_iter, oracle_upto=20):
     r = Reference()
     af0 = np.asarray(af0, float)
     s = lk.shape[0]
@@ -81,7 +83,7 @@ def reference(ped, mrate, lk, flags, af0, n_iter):
     r.q, r.z = np.empty((n_iter + 1, s)), np.empty((n_iter + 1, s))
     r.q[0], r.z[0] = af0, z
     for t in range(n_iter):
-        r.q[t + 1] = step(ped, mrate, lk, flags, r.q[t])
+        r.q[t + 1] = step(ped, mrate, lk, flags, r.q[t], oracle_upto)
         r.z[t + 1] = total(ped, mrate, lk, flags, fs.hwe_priors(r.q[t + 1]))[0]
         assert np.all(r.z[t + 1] >= FLOOR)
     r.z0 = total(ped, mrate, lk, flags, fs.hwe_priors(np.zeros(s)))[0]
