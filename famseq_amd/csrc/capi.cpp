@@ -854,8 +854,9 @@ int trio_prologue(famseq_ctx *c, int64_t n_sites, const void *lk, const void *pl
 
 // What the side products' entries below share.  On the device path (`device`) the arrays are the caller's resident buffers and the
 // kernel is enqueued on `stream`; on the host path they are chunked and pipelined (side_batch) on the product's own buffers.
-// The order of the checks is what callers have come to rely on: a site-prior device entry asks for d_prior before anything
-// else, a site-prior host entry checks its input and its prior rows (prior_ready) first, then every entry trio_prologue.
+// The order of the checks is what callers have come to rely on: the product's extra arguments (check_extra), then a site-prior
+// device entry asks for d_prior, a site-prior host entry checks its input and its prior rows (prior_ready), then every entry
+// trio_prologue.
 struct SideIn {
   int64_t n_sites;
   const double *lk;
@@ -863,131 +864,60 @@ struct SideIn {
   const int32_t *seq_members;
   int32_t n_seq;
   const uint8_t *flags;
+  const double *prior = nullptr;  // the site-prior entries' rows
 };
-// What the pattern entries take beside: the masks [n_patterns][N] (host entry: the caller's host array; device entry: resident).
-struct PatternIn {
-  const uint8_t *masks;
-  int32_t n_patterns;
+struct SideOut {
+  void *a, *b;  // the product's two outputs per site
+  uint8_t *status;
+  void *stream = nullptr;  // the device entries' hipStream_t
 };
-// Said before anything else, so that a context without a device says it too.
-int check_patterns(famseq_ctx *c, const PatternIn &pat, bool device) {
-  if (pat.n_patterns < 1 || pat.n_patterns > FAMSEQ_MAX_PATTERNS)
-    return fail(c, FAMSEQ_E_ARG, "n_patterns must be 1.." + std::to_string(FAMSEQ_MAX_PATTERNS) + ", got " + std::to_string(pat.n_patterns));
-  if (!pat.masks) return fail(c, FAMSEQ_E_ARG, "masks must be given (n_patterns rows of one byte per member)");
-  if (!device)
-    for (size_t i = 0, n = size_t(pat.n_patterns) * c->model.n_members; i < n; ++i)
-      if (pat.masks[i] > 7)
-        return fail(c, FAMSEQ_E_ARG, "masks: pattern " + std::to_string(i / c->model.n_members) + ", member " + std::to_string(i % c->model.n_members) +
-                                         " is " + std::to_string(pat.masks[i]) + "; a mask is 0..7 (bit g: genotype g allowed)");
-  return 0;
+
+// What a product's ExtraSpec asks of the entry's extra arguments.  Said before anything else, so that a context without a device
+// says it too.  A device entry's table is resident: given or not is all that can be said of it.
+int check_extra(famseq_ctx *c, const ExtraSpec &xs, const SideExtra &x, int64_t n_sites, bool device) {
+  if (xs.precondition && xs.precondition(c) != 0) return FAMSEQ_E_ARG;
+  if (xs.count && (x.count < xs.lo || x.count > xs.hi))
+    return fail(c, FAMSEQ_E_ARG, std::string(xs.count) + " must be " + std::to_string(xs.lo) + ".." + std::to_string(xs.hi) + ", got " +
+                                     std::to_string(x.count));
+  if (std::strchr(xs.params, 'b') && x.site_base < 0) return fail(c, FAMSEQ_E_ARG, "site_base must be >= 0, got " + std::to_string(x.site_base));
+  if (xs.name && !x.table)
+    return fail(c, FAMSEQ_E_ARG, std::string(device && xs.device_name ? xs.device_name : xs.name) + " must be given (" +
+                                     (device && xs.device_given ? xs.device_given : xs.given) + ")");
+  return !device && xs.check ? xs.check(c, x.table, x.count, n_sites) : 0;
 }
-// What the sampling entries take beside: the seed, the absolute index of the call's first site and the draws per site.
-struct SampleIn {
-  uint64_t seed;
-  int64_t site_base;
-  int32_t n_draws;
-};
-int check_sample(famseq_ctx *c, const SampleIn &smp) {
-  if (smp.n_draws < 1 || smp.n_draws > FAMSEQ_MAX_DRAWS)
-    return fail(c, FAMSEQ_E_ARG, "n_draws must be 1.." + std::to_string(FAMSEQ_MAX_DRAWS) + ", got " + std::to_string(smp.n_draws));
-  if (smp.site_base < 0) return fail(c, FAMSEQ_E_ARG, "site_base must be >= 0, got " + std::to_string(smp.site_base));
-  return 0;
-}
-// What the allele-frequency entries take beside: the start values [n_sites] (host entry: the caller's host array, staged chunk
-// by chunk where the site-prior forms stage their rows; device entry: resident) and the number of steps.
-struct AfIn {
-  const double *af0;
-  int32_t n_iter;
-};
-int check_af(famseq_ctx *c, const AfIn &af, int64_t n_sites, bool device) {
-  if (af.n_iter < 0 || af.n_iter > FAMSEQ_MAX_AF_ITER)
-    return fail(c, FAMSEQ_E_ARG, "n_iter must be 0.." + std::to_string(FAMSEQ_MAX_AF_ITER) + ", got " + std::to_string(af.n_iter));
-  if (!af.af0) return fail(c, FAMSEQ_E_ARG, "af0 must be given (one start value per site)");
-  if (!device)
-    for (int64_t s = 0; s < n_sites; ++s)
-      if (!(af.af0[s] >= 0.0 && af.af0[s] <= 1.0))
-        return fail(c, FAMSEQ_E_ARG, "af0 entries must be finite numbers in [0, 1] (site " + std::to_string(s) + ")");
-  return 0;
-}
-// What the relabelling entries take beside: the assignments [n_assign][N] (host entry: the caller's host array; device entry: resident).
-struct RelabelIn {
-  const int32_t *assign;
-  int32_t n_assign;
-};
-int check_relabel(famseq_ctx *c, const RelabelIn &rel, bool device) {
-  const int N = c->model.n_members;
-  if (rel.n_assign < 1 || rel.n_assign > FAMSEQ_MAX_RELABEL)
-    return fail(c, FAMSEQ_E_ARG, "n_assign must be 1.." + std::to_string(FAMSEQ_MAX_RELABEL) + ", got " + std::to_string(rel.n_assign));
-  if (!rel.assign) return fail(c, FAMSEQ_E_ARG, "assign must be given (n_assign rows of one int32 per member)");
-  if (!device)
-    for (size_t i = 0, n = size_t(rel.n_assign) * N; i < n; ++i)
-      if (rel.assign[i] < -1 || rel.assign[i] >= N)
-        return fail(c, FAMSEQ_E_ARG, "assign: assignment " + std::to_string(i / N) + ", member " + std::to_string(i % N) + " is " +
-                                         std::to_string(rel.assign[i]) + "; an entry is -1 (no data) or a member index 0.." + std::to_string(N - 1));
-  return 0;
-}
-// What the mutation-rate entries take beside: the rates (host entries: the caller's host array, from which the library builds and
-// stages the tables) or the tables [n_rates][FAMSEQ_RATE_TABLE_DOUBLES] (device entries: resident), and their number.
-struct RateIn {
-  const double *rates;     // host entries
-  const double *d_tables;  // device entries
-  int32_t n_rates;
-};
-int check_rates(famseq_ctx *c, const double *rates, int32_t n_rates, const char *name, bool values) {
-  if (n_rates < 1 || n_rates > FAMSEQ_MAX_RATES)
-    return fail(c, FAMSEQ_E_ARG, "n_rates must be 1.." + std::to_string(FAMSEQ_MAX_RATES) + ", got " + std::to_string(n_rates));
-  if (!rates) return fail(c, FAMSEQ_E_ARG, std::string(name) + " must be given (" + (values ? "n_rates mutation rates)" : "n_rates factor tables of " +
-                                               std::to_string(FAMSEQ_RATE_TABLE_DOUBLES) + " doubles)"));
-  if (values)
-    for (int32_t r = 0; r < n_rates; ++r)
-      if (!(rates[r] >= 0.0 && rates[r] <= 1.0))
-        return fail(c, FAMSEQ_E_ARG, "rates[" + std::to_string(r) + "] must be a finite number in [0, 1]");
-  return 0;
-}
-// famseq_rate_tables' blocks: the model's factor table rebuilt with the transmission tables of each rate
-void rate_tables(const Model &m, const double *rates, int32_t n_rates, double *tables) {
-  Model at = m;
-  for (int32_t r = 0; r < n_rates; ++r) {
-    famseq_transmission_tables(rates[r], at.pcp2, at.pcp2Xf, at.pcp2Xm);
-    build_factor_tables(at, tables + size_t(r) * FAMSEQ_RATE_TABLE_DOUBLES);
+
+// The device table of a product that keeps one (ExtraSpec::via X_CALL: a host entry's table; X_CONST: the product's constant), in
+// *d_table.  The buffer is allocated once, at the largest count.  X_CALL: the table goes through the copy the context keeps, on
+// the stream the chunks' kernels run on: ordered with them by the stream itself, and the copy outlives the call's arrays.  (A
+// host entry returns with its streams drained, so neither is in use by an earlier call.)  X_CONST: uploaded on its first use.
+int stage_extra(famseq_ctx *c, SideId id, const ExtraSpec &xs, const SideExtra &x, const void **d_table) {
+  DevBuf &d = c->d_extra[id];
+  const bool once = xs.via == X_CONST;
+  if (!once || !d) {
+    const size_t bytes = xs.bytes(c->model) * x.count;
+    if (!d) HIP_TRY(c, d.alloc(xs.bytes(c->model) * xs.hi));
+    std::vector<uint8_t> &h = c->extra_host[id];
+    h.resize(bytes);
+    if (xs.build) xs.build(c, x.table, x.count, h.data());
+    else std::memcpy(h.data(), x.table, bytes);
+    if (!once) HIP_TRY(c, hipMemcpyAsync(d.p, h.data(), bytes, hipMemcpyHostToDevice, c->stream[1]));
+    else if (const hipError_t e = hipMemcpy(d.p, h.data(), bytes, hipMemcpyHostToDevice); e != hipSuccess) {  // (blocking: done when it returns)
+      d.release();
+      HIP_TRY(c, e);
+    }
   }
-}
-// What the weight entries take beside: the tables [n_weights][N][3] (host entries: the caller's host array, which the library
-// checks and stages; device entries: resident, unchecked) and their number.
-struct WeightIn {
-  const double *weights;
-  int32_t n_weights;
-};
-int check_weights(famseq_ctx *c, const WeightIn &wt, bool device) {
-  const int N = c->model.n_members;
-  if (wt.n_weights < 1 || wt.n_weights > FAMSEQ_MAX_WEIGHTS)
-    return fail(c, FAMSEQ_E_ARG, "n_weights must be 1.." + std::to_string(FAMSEQ_MAX_WEIGHTS) + ", got " + std::to_string(wt.n_weights));
-  if (!wt.weights)
-    return fail(c, FAMSEQ_E_ARG, std::string(device ? "d_weights" : "weights") + " must be given (n_weights tables of three doubles per member)");
-  if (!device)
-    for (size_t i = 0, n = size_t(wt.n_weights) * 3 * N; i < n; ++i)
-      if (!(wt.weights[i] >= 0.0 && wt.weights[i] <= 1.79769313486231570815e308)) {
-        char v[40];
-        std::snprintf(v, sizeof v, "%g", wt.weights[i]);
-        return fail(c, FAMSEQ_E_ARG, "a weight is a finite number >= 0: weight table " + std::to_string(i / (3 * size_t(N))) + ", member " +
-                                         std::to_string(i / 3 % N) + ", genotype " + std::to_string(i % 3) + " is " + v);
-      }
+  *d_table = d.p;
   return 0;
 }
-int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device, const SideIn &in, const double *prior, void *out_a,
-               void *out_b, uint8_t *status, void *stream_ = nullptr, const PatternIn *pat = nullptr, const SampleIn *smp = nullptr,
-               const AfIn *af = nullptr, const RelabelIn *rel = nullptr, const RateIn *mr = nullptr, const WeightIn *wt = nullptr) {
+
+int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device, const SideIn &in, const SideOut &out, const SideExtra &x = {}) {
   if (!c) return FAMSEQ_E_ARG;
-  if (wt && check_weights(c, *wt, device) != 0) return FAMSEQ_E_ARG;
-  if (id == SIDE_ORIGIN && origin_model(c) != 0) return FAMSEQ_E_ARG;  // (said before the device is asked for)
-  if (mr && check_rates(c, device ? mr->d_tables : mr->rates, mr->n_rates, device ? "d_tables" : "rates", !device) != 0) return FAMSEQ_E_ARG;
-  if (rel && check_relabel(c, *rel, device) != 0) return FAMSEQ_E_ARG;
-  if (pat && check_patterns(c, *pat, device) != 0) return FAMSEQ_E_ARG;
-  if (smp && check_sample(c, *smp) != 0) return FAMSEQ_E_ARG;
-  if (af && check_af(c, *af, in.n_sites, device) != 0) return FAMSEQ_E_ARG;
   const SideProduct &p = side_table()[id];
+  const ExtraSpec &xs = p.extra;
+  if (check_extra(c, xs, x, in.n_sites, device) != 0) return FAMSEQ_E_ARG;
   const int kind = p.kind_of(form, site_prior);
   const int64_t n_sites = in.n_sites;
+  const double *prior = in.prior;
   int rc;
   if (site_prior && device) {
     if (n_sites > 0 && !prior) return fail(c, FAMSEQ_E_ARG, "d_prior must be given (six doubles per site)");
@@ -995,89 +925,35 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
     if ((rc = check_input(c, n_sites, in.lk, in.pl16, "lk / pl16", false, in.n_seq)) != 0 || (rc = prior_ready(c, n_sites, in.flags, prior, kind)) != 0)
       return rc;
   }
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipStream_t stream = static_cast<hipStream_t>(out.stream);
   StateCall state;  // (a device entry on packed input)
   if ((rc = trio_prologue(c, n_sites, in.lk, in.pl16, in.seq_members, in.n_seq, kind, device ? &state : nullptr, stream)) != 0 || n_sites == 0)
     return rc;
-  // the arguments in front of the prior rows (the pattern kernels' masks and their number)
-  const uint8_t *d_masks = pat ? pat->masks : nullptr;
-  const int32_t n_patterns = pat ? pat->n_patterns : 1;
-  // ... or the sampling kernels' seed, site_base (the host path: per chunk, side_batch) and n_draws
-  const unsigned long seed = smp ? (unsigned long)smp->seed : 0;
-  const long site_base = smp ? long(smp->site_base) : 0;
-  const int32_t n_draws = smp ? smp->n_draws : 1;
-  // ... or the allele-frequency kernel's start values (the host path: the chunk's staged copy, side_batch) and n_iter
-  const double *d_af0 = af ? af->af0 : nullptr;
-  const int32_t n_iter = af ? af->n_iter : 0;
-  // ... or the relabelling kernels' assignments and their number
-  const int32_t *d_assign = rel ? rel->assign : nullptr;
-  const int32_t n_assign = rel ? rel->n_assign : 1;
-  // ... or the mutation-rate kernels' tables and their number
-  const double *d_tables = mr ? mr->d_tables : nullptr;
-  const int32_t n_rates = mr ? mr->n_rates : 1;
-  // ... or the origin kernels' allele rows: the context's own, uploaded on their first use and never changed
-  const double *d_allele = nullptr;
-  if (id == SIDE_ORIGIN) {
-    if (!c->d_allele) {
-      double rows[FAMSEQ_ALLELE_TABLE_DOUBLES];
-      build_allele_tables(c->origin_mrate, rows);
-      HIP_TRY(c, c->d_allele.alloc(sizeof rows));
-      const hipError_t e = hipMemcpy(c->d_allele.p, rows, sizeof rows, hipMemcpyHostToDevice);  // (blocking: done when it returns)
-      if (e != hipSuccess) c->d_allele.release();
-      HIP_TRY(c, e);
+  // the kernel's arguments in front of the prior rows, in the order the product's row gives
+  const void *table = x.table;
+  if ((xs.via == X_CONST || (xs.via == X_CALL && !device)) && (rc = stage_extra(c, id, xs, x, &table)) != 0) return rc;
+  const int32_t count = x.count;
+  const unsigned long seed = (unsigned long)x.seed;
+  const long site_base = long(x.site_base);
+  MoreArgs lead;
+  PerChunk per{prior, 6 * sizeof(double)};  // (the host path)
+  for (const char *a = xs.params; *a; ++a) switch (*a) {
+      case 't':
+        if (xs.via == X_SITE) per = {x.table, xs.bytes(c->model), lead.n};  // (the chunk's staged copy)
+        lead.add(&table);
+        break;
+      case 'n': lead.add(&count); break;
+      case 's': lead.add(&seed); break;
+      case 'b':
+        per.base_at = lead.n, per.site_base = x.site_base;
+        lead.add(&site_base);
+        break;
     }
-    d_allele = c->d_allele.as<double>();
-  }
-  // ... or the weight kernels' tables and their number
-  const double *d_weights = wt ? wt->weights : nullptr;
-  const int32_t n_weights = wt ? wt->n_weights : 1;
-  const MoreArgs lead = id == SIDE_ORIGIN ? MoreArgs{&d_allele}
-                        : wt  ? MoreArgs{&d_weights, &n_weights}
-                        : mr  ? MoreArgs{&d_tables, &n_rates}
-                        : rel ? MoreArgs{&d_assign, &n_assign}
-                        : pat ? MoreArgs{&d_masks, &n_patterns}
-                        : smp ? MoreArgs{&seed, &site_base, &n_draws}
-                        : af  ? MoreArgs{&d_af0, &n_iter}
-                              : MoreArgs{};
   if (!device) {
     size_t row[2];
-    p.rows(c->model, smp ? n_draws : (rel ? n_assign : (mr ? n_rates : (wt ? n_weights : n_patterns))), row);
-    if (wt) {  // (staged as the masks below are)
-      const size_t n = size_t(n_weights) * 3 * c->model.n_members;
-      if (!c->d_weights) HIP_TRY(c, c->d_weights.alloc(size_t(FAMSEQ_MAX_WEIGHTS) * 3 * c->model.n_members * sizeof(double)));
-      c->weights_host.assign(wt->weights, wt->weights + n);
-      HIP_TRY(c, hipMemcpyAsync(c->d_weights.p, c->weights_host.data(), n * sizeof(double), hipMemcpyHostToDevice, c->stream[1]));
-      d_weights = c->d_weights.as<double>();
-    }
-    if (mr) {  // (the tables of the call's rates, staged as the masks below are)
-      const size_t n = size_t(n_rates) * FAMSEQ_RATE_TABLE_DOUBLES;
-      if (!c->d_rate_tables) HIP_TRY(c, c->d_rate_tables.alloc(size_t(FAMSEQ_MAX_RATES) * FAMSEQ_RATE_TABLE_DOUBLES * sizeof(double)));
-      c->rate_tables_host.resize(n);
-      rate_tables(c->model, mr->rates, n_rates, c->rate_tables_host.data());
-      HIP_TRY(c, hipMemcpyAsync(c->d_rate_tables.p, c->rate_tables_host.data(), n * sizeof(double), hipMemcpyHostToDevice, c->stream[1]));
-      d_tables = c->d_rate_tables.as<double>();
-    }
-    if (rel) {  // (staged as the masks below are)
-      const size_t n = size_t(n_assign) * c->model.n_members;
-      if (!c->d_assign) HIP_TRY(c, c->d_assign.alloc(size_t(FAMSEQ_MAX_RELABEL) * c->model.n_members * sizeof(int32_t)));
-      c->assign_host.assign(rel->assign, rel->assign + n);
-      HIP_TRY(c, hipMemcpyAsync(c->d_assign.p, c->assign_host.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream[1]));
-      d_assign = c->d_assign.as<int32_t>();
-    }
-    if (pat) {
-      // The masks go through a copy the context keeps into a buffer it owns, on the stream the chunks' kernels run on: ordered
-      // with them by the stream itself.  (A host entry returns with its streams drained, so neither is in use by an earlier call.)
-      const size_t bytes = size_t(n_patterns) * c->model.n_members;
-      if (!c->d_masks) HIP_TRY(c, c->d_masks.alloc(size_t(FAMSEQ_MAX_PATTERNS) * c->model.n_members));
-      c->masks_host.assign(pat->masks, pat->masks + bytes);
-      HIP_TRY(c, hipMemcpyAsync(c->d_masks.p, c->masks_host.data(), bytes, hipMemcpyHostToDevice, c->stream[1]));
-      d_masks = c->d_masks.as<uint8_t>();
-    }
-    if (af)
-      return side_batch(c, c->side_slots[id], c->kern[kind], n_sites, in.lk, in.pl16, in.n_seq, in.flags, out_a, row[0], out_b, row[1], status,
-                        af->af0, lead, -1, 0, sizeof(double), 0);
-    return side_batch(c, c->side_slots[id], c->kern[kind], n_sites, in.lk, in.pl16, in.n_seq, in.flags, out_a, row[0], out_b, row[1], status, prior,
-                      lead, smp ? 1 : -1, site_base);
+    p.rows(c->model, count, row);
+    return side_batch(c, c->side_slots[id], c->kern[kind], n_sites, in.lk, in.pl16, in.n_seq, in.flags, out.a, row[0], out.b, row[1], out.status, lead,
+                      per);
   }
   const double *d_lk = in.lk;
   if (in.pl16) {  // packed input is unpacked into likelihood rows this context keeps (grown on demand)
@@ -1091,145 +967,137 @@ int side_entry(famseq_ctx *c, SideId id, int form, bool site_prior, bool device,
     d_lk = c->trio_dev_lk.as<double>();
     HIP_TRY(c, launch_unpack_pl16(in.pl16, c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, in.n_seq, n_sites, c->trio_dev_lk.as<double>(), stream));
   }
-  MoreArgs more = lead;
-  more.at[more.n++] = &prior;  // (behind the last parameter of a plain form: not read)
-  HIP_TRY(c, launch_generated(c, c->kern[kind], n_sites, d_lk, in.flags, out_a, out_b, status, stream, 0, more));
+  lead.add(&prior);  // (behind the last parameter of a plain form: not read)
+  HIP_TRY(c, launch_generated(c, c->kern[kind], n_sites, d_lk, in.flags, out.a, out.b, out.status, stream, 0, lead));
   return 0;
 }
 
 }  // namespace
 
-// ---- trio posteriors, the joint MAP configuration, the evidence (the site's log10 likelihood and the hom-ref posterior), the
-// ---- leave-one-out posteriors and fit, the genotype-pattern posteriors, each
-// ---- plain and with the founders' prior per site, on host and on resident buffers: side_entry --------------------------------
+// ---- the side products (the rows of side_table()), each plain and with the founders' prior per site, on host and on resident
+// ---- buffers: one call of side_entry with the common arguments, the outputs and what the product takes beside ------------------
 
 extern "C" int famseq_trio_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                  int32_t n_seq, const uint8_t *flags, double *joint, double *dnm, uint8_t *status) {
-  return side_entry(c, SIDE_TRIO, trio_form(joint, dnm), false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, joint, dnm, status);
+  return side_entry(c, SIDE_TRIO, trio_form(joint, dnm), false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, {joint, dnm, status});
 }
 
 extern "C" int famseq_trio_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                         const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_joint,
                                         double *d_dnm, uint8_t *d_status, void *stream) {
-  return side_entry(c, SIDE_TRIO, trio_form(d_joint, d_dnm), false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_joint,
-                    d_dnm, d_status, stream);
+  return side_entry(c, SIDE_TRIO, trio_form(d_joint, d_dnm), false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags},
+                    {d_joint, d_dnm, d_status, stream});
 }
 
 extern "C" int famseq_trio_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                        int32_t n_seq, const uint8_t *flags, const double *prior, double *joint, double *dnm,
                                        uint8_t *status) {
-  return side_entry(c, SIDE_TRIO, trio_form(joint, dnm), true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, joint, dnm, status);
+  return side_entry(c, SIDE_TRIO, trio_form(joint, dnm), true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior}, {joint, dnm, status});
 }
 
 extern "C" int famseq_trio_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                               const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                               double *d_joint, double *d_dnm, uint8_t *d_status, void *stream) {
-  return side_entry(c, SIDE_TRIO, trio_form(d_joint, d_dnm), true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_joint,
-                    d_dnm, d_status, stream);
+  return side_entry(c, SIDE_TRIO, trio_form(d_joint, d_dnm), true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior},
+                    {d_joint, d_dnm, d_status, stream});
 }
 
 extern "C" int famseq_map_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                 int32_t n_seq, const uint8_t *flags, int8_t *map_gt, double *map_post, uint8_t *status) {
-  return side_entry(c, SIDE_MAP, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, map_gt, map_post, status);
+  return side_entry(c, SIDE_MAP, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, {map_gt, map_post, status});
 }
 
 extern "C" int famseq_map_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                        const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, int8_t *d_map_gt,
                                        double *d_map_post, uint8_t *d_status, void *stream) {
-  return side_entry(c, SIDE_MAP, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_map_gt, d_map_post, d_status,
-                    stream);
+  return side_entry(c, SIDE_MAP, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, {d_map_gt, d_map_post, d_status, stream});
 }
 
 extern "C" int famseq_map_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                       int32_t n_seq, const uint8_t *flags, const double *prior, int8_t *map_gt, double *map_post,
                                       uint8_t *status) {
-  return side_entry(c, SIDE_MAP, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, map_gt, map_post, status);
+  return side_entry(c, SIDE_MAP, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior}, {map_gt, map_post, status});
 }
 
 extern "C" int famseq_map_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                              const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                              int8_t *d_map_gt, double *d_map_post, uint8_t *d_status, void *stream) {
-  return side_entry(c, SIDE_MAP, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_map_gt, d_map_post, d_status,
-                    stream);
+  return side_entry(c, SIDE_MAP, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior},
+                    {d_map_gt, d_map_post, d_status, stream});
 }
 
 extern "C" int famseq_evidence_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                      int32_t n_seq, const uint8_t *flags, double *loglik, double *pref, uint8_t *status) {
-  return side_entry(c, SIDE_EVID, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, loglik, pref, status);
+  return side_entry(c, SIDE_EVID, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, {loglik, pref, status});
 }
 
 extern "C" int famseq_evidence_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                             const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_loglik,
                                             double *d_pref, uint8_t *d_status, void *stream) {
-  return side_entry(c, SIDE_EVID, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_loglik, d_pref, d_status,
-                    stream);
+  return side_entry(c, SIDE_EVID, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, {d_loglik, d_pref, d_status, stream});
 }
 
 extern "C" int famseq_evidence_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
                                            const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
                                            double *loglik, double *pref, uint8_t *status) {
-  return side_entry(c, SIDE_EVID, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, loglik, pref, status);
+  return side_entry(c, SIDE_EVID, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior}, {loglik, pref, status});
 }
 
 extern "C" int famseq_evidence_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                                   const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                                   double *d_loglik, double *d_pref, uint8_t *d_status, void *stream) {
-  return side_entry(c, SIDE_EVID, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_loglik, d_pref, d_status,
-                    stream);
+  return side_entry(c, SIDE_EVID, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior}, {d_loglik, d_pref, d_status, stream});
 }
 
 extern "C" int famseq_loo_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                 int32_t n_seq, const uint8_t *flags, double *loo, double *fit, uint8_t *status) {
-  return side_entry(c, SIDE_LOO, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, loo, fit, status);
+  return side_entry(c, SIDE_LOO, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, {loo, fit, status});
 }
 
 extern "C" int famseq_loo_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                        const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_loo, double *d_fit,
                                        uint8_t *d_status, void *stream) {
-  return side_entry(c, SIDE_LOO, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_loo, d_fit, d_status, stream);
+  return side_entry(c, SIDE_LOO, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, {d_loo, d_fit, d_status, stream});
 }
 
 extern "C" int famseq_loo_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                       int32_t n_seq, const uint8_t *flags, const double *prior, double *loo, double *fit, uint8_t *status) {
-  return side_entry(c, SIDE_LOO, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, loo, fit, status);
+  return side_entry(c, SIDE_LOO, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior}, {loo, fit, status});
 }
 
 extern "C" int famseq_loo_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                              const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                              double *d_loo, double *d_fit, uint8_t *d_status, void *stream) {
-  return side_entry(c, SIDE_LOO, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_loo, d_fit, d_status,
-                    stream);
+  return side_entry(c, SIDE_LOO, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior}, {d_loo, d_fit, d_status, stream});
 }
 
 extern "C" int famseq_pattern_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                     int32_t n_seq, const uint8_t *flags, const uint8_t *masks, int32_t n_patterns, double *pat_post,
                                     double *loglik, uint8_t *status) {
-  const PatternIn pat{masks, n_patterns};
-  return side_entry(c, SIDE_PATTERN, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, pat_post, loglik, status, nullptr, &pat);
+  return side_entry(c, SIDE_PATTERN, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags},
+                    {pat_post, loglik, status}, {masks, n_patterns});
 }
 
 extern "C" int famseq_pattern_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                            const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const uint8_t *d_masks,
                                            int32_t n_patterns, double *d_pat_post, double *d_loglik, uint8_t *d_status, void *stream) {
-  const PatternIn pat{d_masks, n_patterns};
-  return side_entry(c, SIDE_PATTERN, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_pat_post, d_loglik, d_status,
-                    stream, &pat);
+  return side_entry(c, SIDE_PATTERN, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags},
+                    {d_pat_post, d_loglik, d_status, stream}, {d_masks, n_patterns});
 }
 
 extern "C" int famseq_pattern_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
                                           const uint8_t *masks, int32_t n_patterns, double *pat_post, double *loglik, uint8_t *status) {
-  const PatternIn pat{masks, n_patterns};
-  return side_entry(c, SIDE_PATTERN, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, pat_post, loglik, status, nullptr, &pat);
+  return side_entry(c, SIDE_PATTERN, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior},
+                    {pat_post, loglik, status}, {masks, n_patterns});
 }
 
 extern "C" int famseq_pattern_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                                  const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                                  const uint8_t *d_masks, int32_t n_patterns, double *d_pat_post, double *d_loglik,
                                                  uint8_t *d_status, void *stream) {
-  const PatternIn pat{d_masks, n_patterns};
-  return side_entry(c, SIDE_PATTERN, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_pat_post, d_loglik, d_status,
-                    stream, &pat);
+  return side_entry(c, SIDE_PATTERN, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior},
+                    {d_pat_post, d_loglik, d_status, stream}, {d_masks, n_patterns});
 }
 
 // ---- exact joint posterior draws: the MAP entries with the seed, the first site's absolute index and the draws per site -------
@@ -1237,34 +1105,30 @@ extern "C" int famseq_pattern_prior_batch_device(famseq_ctx *c, int64_t n_sites,
 extern "C" int famseq_sample_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                    int32_t n_seq, const uint8_t *flags, uint64_t seed, int64_t site_base, int32_t n_draws, int8_t *samp_gt,
                                    double *samp_post, uint8_t *status) {
-  const SampleIn smp{seed, site_base, n_draws};
-  return side_entry(c, SIDE_SAMPLE, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, samp_gt, samp_post, status, nullptr,
-                    nullptr, &smp);
+  return side_entry(c, SIDE_SAMPLE, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags},
+                    {samp_gt, samp_post, status}, {seed, site_base, n_draws});
 }
 
 extern "C" int famseq_sample_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, uint64_t seed, int64_t site_base,
                                           int32_t n_draws, int8_t *d_samp_gt, double *d_samp_post, uint8_t *d_status, void *stream) {
-  const SampleIn smp{seed, site_base, n_draws};
-  return side_entry(c, SIDE_SAMPLE, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_samp_gt, d_samp_post, d_status,
-                    stream, nullptr, &smp);
+  return side_entry(c, SIDE_SAMPLE, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags},
+                    {d_samp_gt, d_samp_post, d_status, stream}, {seed, site_base, n_draws});
 }
 
 extern "C" int famseq_sample_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                          int32_t n_seq, const uint8_t *flags, const double *prior, uint64_t seed, int64_t site_base,
                                          int32_t n_draws, int8_t *samp_gt, double *samp_post, uint8_t *status) {
-  const SampleIn smp{seed, site_base, n_draws};
-  return side_entry(c, SIDE_SAMPLE, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, samp_gt, samp_post, status, nullptr,
-                    nullptr, &smp);
+  return side_entry(c, SIDE_SAMPLE, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior},
+                    {samp_gt, samp_post, status}, {seed, site_base, n_draws});
 }
 
 extern "C" int famseq_sample_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                                 const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                                 uint64_t seed, int64_t site_base, int32_t n_draws, int8_t *d_samp_gt, double *d_samp_post,
                                                 uint8_t *d_status, void *stream) {
-  const SampleIn smp{seed, site_base, n_draws};
-  return side_entry(c, SIDE_SAMPLE, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_samp_gt, d_samp_post, d_status,
-                    stream, nullptr, &smp);
+  return side_entry(c, SIDE_SAMPLE, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior},
+                    {d_samp_gt, d_samp_post, d_status, stream}, {seed, site_base, n_draws});
 }
 
 // ---- the founders' allele frequency by maximum likelihood: the evidence entries with the start values and the number of steps ---
@@ -1272,17 +1136,14 @@ extern "C" int famseq_sample_prior_batch_device(famseq_ctx *c, int64_t n_sites, 
 extern "C" int famseq_af_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                int32_t n_seq, const uint8_t *flags, const double *af0, int32_t n_iter, double *af, double *loglik,
                                uint8_t *status) {
-  const AfIn in{af0, n_iter};
-  return side_entry(c, SIDE_AF, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, af, loglik, status, nullptr, nullptr,
-                    nullptr, &in);
+  return side_entry(c, SIDE_AF, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, {af, loglik, status}, {af0, n_iter});
 }
 
 extern "C" int famseq_af_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16, const int32_t *seq_members,
                                       int32_t n_seq, const uint8_t *d_flags, const double *d_af0, int32_t n_iter, double *d_af,
                                       double *d_loglik, uint8_t *d_status, void *stream) {
-  const AfIn in{d_af0, n_iter};
-  return side_entry(c, SIDE_AF, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_af, d_loglik, d_status, stream,
-                    nullptr, nullptr, &in);
+  return side_entry(c, SIDE_AF, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags},
+                    {d_af, d_loglik, d_status, stream}, {d_af0, n_iter});
 }
 
 // ---- relabelling evidence: the evidence entries with the assignments of rows to members and their number -------------------
@@ -1290,41 +1151,37 @@ extern "C" int famseq_af_batch_device(famseq_ctx *c, int64_t n_sites, const doub
 extern "C" int famseq_relabel_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                     int32_t n_seq, const uint8_t *flags, const int32_t *assign, int32_t n_assign, double *alt_loglik,
                                     double *loglik, uint8_t *status) {
-  const RelabelIn rel{assign, n_assign};
-  return side_entry(c, SIDE_RELABEL, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, alt_loglik, loglik, status, nullptr,
-                    nullptr, nullptr, nullptr, &rel);
+  return side_entry(c, SIDE_RELABEL, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags},
+                    {alt_loglik, loglik, status}, {assign, n_assign});
 }
 
 extern "C" int famseq_relabel_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                            const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const int32_t *d_assign,
                                            int32_t n_assign, double *d_alt_loglik, double *d_loglik, uint8_t *d_status, void *stream) {
-  const RelabelIn rel{d_assign, n_assign};
-  return side_entry(c, SIDE_RELABEL, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_alt_loglik, d_loglik,
-                    d_status, stream, nullptr, nullptr, nullptr, &rel);
+  return side_entry(c, SIDE_RELABEL, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags},
+                    {d_alt_loglik, d_loglik, d_status, stream}, {d_assign, n_assign});
 }
 
 extern "C" int famseq_relabel_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
                                           const int32_t *assign, int32_t n_assign, double *alt_loglik, double *loglik, uint8_t *status) {
-  const RelabelIn rel{assign, n_assign};
-  return side_entry(c, SIDE_RELABEL, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, alt_loglik, loglik, status, nullptr,
-                    nullptr, nullptr, nullptr, &rel);
+  return side_entry(c, SIDE_RELABEL, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior},
+                    {alt_loglik, loglik, status}, {assign, n_assign});
 }
 
 extern "C" int famseq_relabel_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                                  const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                                  const int32_t *d_assign, int32_t n_assign, double *d_alt_loglik, double *d_loglik,
                                                  uint8_t *d_status, void *stream) {
-  const RelabelIn rel{d_assign, n_assign};
-  return side_entry(c, SIDE_RELABEL, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_alt_loglik, d_loglik,
-                    d_status, stream, nullptr, nullptr, nullptr, &rel);
+  return side_entry(c, SIDE_RELABEL, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior},
+                    {d_alt_loglik, d_loglik, d_status, stream}, {d_assign, n_assign});
 }
 
 // ---- the mutation-rate likelihood profile: the evidence entries with one factor table per rate ----------------------------------
 
 extern "C" int famseq_rate_tables(famseq_ctx *c, const double *rates, int32_t n_rates, double *tables) {
   if (!c) return FAMSEQ_E_ARG;
-  if (check_rates(c, rates, n_rates, "rates", true) != 0) return FAMSEQ_E_ARG;
+  if (check_extra(c, side_table()[SIDE_MUTRATE].extra, {rates, n_rates}, 0, false) != 0) return FAMSEQ_E_ARG;
   if (!tables) return fail(c, FAMSEQ_E_ARG, "tables must be given (n_rates blocks of " + std::to_string(FAMSEQ_RATE_TABLE_DOUBLES) + " doubles)");
   rate_tables(c->model, rates, n_rates, tables);
   return 0;
@@ -1333,34 +1190,30 @@ extern "C" int famseq_rate_tables(famseq_ctx *c, const double *rates, int32_t n_
 extern "C" int famseq_mutrate_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                     int32_t n_seq, const uint8_t *flags, const double *rates, int32_t n_rates, double *rate_loglik,
                                     double *loglik, uint8_t *status) {
-  const RateIn mr{rates, nullptr, n_rates};
-  return side_entry(c, SIDE_MUTRATE, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, rate_loglik, loglik, status, nullptr,
-                    nullptr, nullptr, nullptr, nullptr, &mr);
+  return side_entry(c, SIDE_MUTRATE, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags},
+                    {rate_loglik, loglik, status}, {rates, n_rates});
 }
 
 extern "C" int famseq_mutrate_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                            const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_tables,
                                            int32_t n_rates, double *d_rate_loglik, double *d_loglik, uint8_t *d_status, void *stream) {
-  const RateIn mr{nullptr, d_tables, n_rates};
-  return side_entry(c, SIDE_MUTRATE, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_rate_loglik, d_loglik,
-                    d_status, stream, nullptr, nullptr, nullptr, nullptr, &mr);
+  return side_entry(c, SIDE_MUTRATE, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags},
+                    {d_rate_loglik, d_loglik, d_status, stream}, {d_tables, n_rates});
 }
 
 extern "C" int famseq_mutrate_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
                                           const double *rates, int32_t n_rates, double *rate_loglik, double *loglik, uint8_t *status) {
-  const RateIn mr{rates, nullptr, n_rates};
-  return side_entry(c, SIDE_MUTRATE, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, rate_loglik, loglik, status, nullptr,
-                    nullptr, nullptr, nullptr, nullptr, &mr);
+  return side_entry(c, SIDE_MUTRATE, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior},
+                    {rate_loglik, loglik, status}, {rates, n_rates});
 }
 
 extern "C" int famseq_mutrate_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                                  const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                                  const double *d_tables, int32_t n_rates, double *d_rate_loglik, double *d_loglik,
                                                  uint8_t *d_status, void *stream) {
-  const RateIn mr{nullptr, d_tables, n_rates};
-  return side_entry(c, SIDE_MUTRATE, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_rate_loglik, d_loglik,
-                    d_status, stream, nullptr, nullptr, nullptr, nullptr, &mr);
+  return side_entry(c, SIDE_MUTRATE, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior},
+                    {d_rate_loglik, d_loglik, d_status, stream}, {d_tables, n_rates});
 }
 
 // ---- phase by transmission: each child's alleles by parent of origin, and the transmissions from heterozygous parents ----------
@@ -1375,27 +1228,26 @@ extern "C" int famseq_allele_tables(famseq_ctx *c, double *tables) {
 
 extern "C" int famseq_origin_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                    int32_t n_seq, const uint8_t *flags, double *origin, double *hettx, uint8_t *status) {
-  return side_entry(c, SIDE_ORIGIN, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, origin, hettx, status);
+  return side_entry(c, SIDE_ORIGIN, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, {origin, hettx, status});
 }
 
 extern "C" int famseq_origin_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_origin,
                                           double *d_hettx, uint8_t *d_status, void *stream) {
-  return side_entry(c, SIDE_ORIGIN, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_origin, d_hettx, d_status,
-                    stream);
+  return side_entry(c, SIDE_ORIGIN, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, {d_origin, d_hettx, d_status, stream});
 }
 
 extern "C" int famseq_origin_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                          int32_t n_seq, const uint8_t *flags, const double *prior, double *origin, double *hettx,
                                          uint8_t *status) {
-  return side_entry(c, SIDE_ORIGIN, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, origin, hettx, status);
+  return side_entry(c, SIDE_ORIGIN, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior}, {origin, hettx, status});
 }
 
 extern "C" int famseq_origin_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                                 const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                                 double *d_origin, double *d_hettx, uint8_t *d_status, void *stream) {
-  return side_entry(c, SIDE_ORIGIN, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_origin, d_hettx,
-                    d_status, stream);
+  return side_entry(c, SIDE_ORIGIN, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior},
+                    {d_origin, d_hettx, d_status, stream});
 }
 
 // ---- per-member genotype weights: the evidence entries with one table of weights per pass --------------------------------------
@@ -1403,34 +1255,30 @@ extern "C" int famseq_origin_prior_batch_device(famseq_ctx *c, int64_t n_sites, 
 extern "C" int famseq_weight_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
                                    int32_t n_seq, const uint8_t *flags, const double *weights, int32_t n_weights, double *wt_loglik,
                                    double *loglik, uint8_t *status) {
-  const WeightIn wt{weights, n_weights};
-  return side_entry(c, SIDE_WEIGHT, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, nullptr, wt_loglik, loglik, status, nullptr,
-                    nullptr, nullptr, nullptr, nullptr, nullptr, &wt);
+  return side_entry(c, SIDE_WEIGHT, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags},
+                    {wt_loglik, loglik, status}, {weights, n_weights});
 }
 
 extern "C" int famseq_weight_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_weights,
                                           int32_t n_weights, double *d_wt_loglik, double *d_loglik, uint8_t *d_status, void *stream) {
-  const WeightIn wt{d_weights, n_weights};
-  return side_entry(c, SIDE_WEIGHT, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, nullptr, d_wt_loglik, d_loglik,
-                    d_status, stream, nullptr, nullptr, nullptr, nullptr, nullptr, &wt);
+  return side_entry(c, SIDE_WEIGHT, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags},
+                    {d_wt_loglik, d_loglik, d_status, stream}, {d_weights, n_weights});
 }
 
 extern "C" int famseq_weight_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
                                          const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
                                          const double *weights, int32_t n_weights, double *wt_loglik, double *loglik, uint8_t *status) {
-  const WeightIn wt{weights, n_weights};
-  return side_entry(c, SIDE_WEIGHT, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, prior, wt_loglik, loglik, status, nullptr,
-                    nullptr, nullptr, nullptr, nullptr, nullptr, &wt);
+  return side_entry(c, SIDE_WEIGHT, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior},
+                    {wt_loglik, loglik, status}, {weights, n_weights});
 }
 
 extern "C" int famseq_weight_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
                                                 const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
                                                 const double *d_weights, int32_t n_weights, double *d_wt_loglik, double *d_loglik,
                                                 uint8_t *d_status, void *stream) {
-  const WeightIn wt{d_weights, n_weights};
-  return side_entry(c, SIDE_WEIGHT, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, d_prior, d_wt_loglik, d_loglik,
-                    d_status, stream, nullptr, nullptr, nullptr, nullptr, nullptr, &wt);
+  return side_entry(c, SIDE_WEIGHT, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior},
+                    {d_wt_loglik, d_loglik, d_status, stream}, {d_weights, n_weights});
 }
 
 // The sampling kernels' generator on the host: the text they carry (philox_src.h), compiled here.

@@ -1,6 +1,7 @@
 // ctx.h — what the host translation units of libfamseq_hip.so share: the context behind the C ABI, the record of a
-// generated kernel and the device buffers a context owns.  capi.cpp is the extern "C" surface and its argument checks,
-// kernels.cpp loads, launches and tunes the generated kernels, pipeline.cpp moves host batches through the device.
+// generated kernel, the device buffers a context owns and the table of the side products (SideProduct: their kernels, and what
+// their entries take beside the common arguments).  capi.cpp is the extern "C" surface and its argument checks, kernels.cpp
+// holds side_table() and loads, launches and tunes the generated kernels, pipeline.cpp moves host batches through the device.
 #ifndef FAMSEQ_CTX_H_
 #define FAMSEQ_CTX_H_
 
@@ -54,9 +55,8 @@ struct DevBuf {
   explicit operator bool() const { return p != nullptr; }
 };
 
-// A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp; the trio,
-// MAP, evidence, leave-one-out, pattern, sampling, allele-frequency, relabelling, mutation-rate, origin and weight kinds are the rows of
-// side_table() below.
+// A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp; the side
+// products' kinds (K_TRIO .. K_WEIGHT_PRIOR) are the rows of side_table() below.
 enum KernelKind {
   K_LANE = 0,  // K_LANE + d: the enumeration with 3^d lanes per site; d = 0 (one lane per site) serves large batches,
                // d = 1..kEnumMaxGroupDigits batches too small to give every lane of the chip a site (compiled on first use of each d)
@@ -125,6 +125,48 @@ struct SlotSet {
   }
 };
 
+// What a side entry takes beside the common arguments: at most one table and one count, and the sampling entries' seed and
+// site_base.  What each of them is for a product, how it is checked and how it reaches the kernel: the product's ExtraSpec.
+struct SideExtra {
+  const void *table = nullptr;  // host entries: the caller's host array; device entries: resident
+  int32_t count = 1;
+  uint64_t seed = 0;
+  int64_t site_base = 0;  // the absolute index of the call's first site
+  SideExtra() = default;
+  SideExtra(const void *table_, int32_t count_) : table(table_), count(count_) {}
+  SideExtra(uint64_t seed_, int64_t site_base_, int32_t n_draws) : count(n_draws), seed(seed_), site_base(site_base_) {}
+};
+// How a host entry's table reaches the device (a device entry's is resident):
+enum ExtraVia {
+  X_NONE,   // no table: the entries take nothing beside, or scalars only (ExtraSpec::params)
+  X_CALL,   // one table per call: staged at its size from the context's copy into a buffer allocated once at the largest count
+  X_SITE,   // one element per site: staged chunk by chunk where the site-prior forms stage their rows
+  X_CONST,  // no table of the caller's: rows made from the context's model, uploaded on their first use and never changed
+};
+// The argument side of a product: one column of side_table().  Plain data and functions; the generic code is capi.cpp's
+// check_extra, stage_extra and side_entry.
+struct ExtraSpec {
+  ExtraVia via = X_NONE;
+  // the kernel's parameters between the common ones and the prior rows, in order: 't' the table, 'n' the count, 's' the seed,
+  // 'b' site_base (a host entry's chunks: plus the chunk's first index)
+  const char *params = "";
+  // the count: "<count> must be <lo>..<hi>, got <v>" (NULL: the entries take none)
+  const char *count = nullptr;
+  int lo = 1, hi = 1;
+  // the table: "<name> must be given (<given>)" (name NULL: none to give)
+  const char *name = nullptr, *given = nullptr;
+  // host entries: the first value of the table that is out of range (fail()'s code), or 0
+  int (*check)(famseq_ctx *, const void *table, int32_t count, int64_t n_sites) = nullptr;
+  // X_CALL: bytes of the device table per count; X_SITE: per site; X_CONST: in all
+  size_t (*bytes)(const Model &) = nullptr;
+  // X_CALL, X_CONST: fills the context's copy of the device table (NULL: the caller's table as it is)
+  void (*build)(const famseq_ctx *, const void *table, int32_t count, void *staged) = nullptr;
+  // where the device entries call the table otherwise, or say otherwise what is to be given
+  const char *device_name = nullptr, *device_given = nullptr;
+  // asked of the context before anything else, whatever the arguments (the origin kernels' origin_model)
+  int (*precondition)(famseq_ctx *) = nullptr;
+};
+
 // A side product of the sum-product engine: a generated kernel that takes the common argument list and writes two outputs per
 // site and a status byte, in a plain form and in one that reads the founders' prior per site.  Everything its ABI entries, its
 // prebuild options, its plan keys and its loader differ in is one row of side_table() (kernels.cpp).
@@ -137,8 +179,9 @@ struct SideProduct {
                                   // (prior_kind < 0: the product has no site-prior form — no <stem>_prior_* name exists anywhere)
   int n_variants;
   std::string (*source)(const Model &, int variant, int form, bool site_prior);
-  // bytes per site of the two outputs; per_call: what the call itself says of them (the pattern entries' n_patterns, the sampling entries' n_draws, the relabelling entries' n_assign, the mutation-rate entries' n_rates, the weight entries' n_weights; 1 elsewhere)
-  void (*rows)(const Model &, int per_call, size_t row[2]);
+  // bytes per site of the two outputs; count: the call's SideExtra::count (1 where the entries take none), for the rows that read it
+  void (*rows)(const Model &, int count, size_t row[2]);
+  ExtraSpec extra;
   int kind_of(int form, bool site_prior) const { return (site_prior ? prior_kind : kind) + form - 1; }
   bool has_prior() const { return prior_kind >= 0; }
 };
@@ -220,22 +263,13 @@ struct famseq_ctx {
   hipEvent_t ev_stage[famseq::kStageRing] = {};
   bool stage_used[famseq::kStageRing] = {};
   int stage_next = 0;
-  // the pattern host entries' masks: FAMSEQ_MAX_PATTERNS rows, staged per call from a copy the context keeps, on the compute stream
-  famseq::DevBuf d_masks;
-  std::vector<uint8_t> masks_host;
-  // ... and the relabelling host entries' assignments: FAMSEQ_MAX_RELABEL rows of int32, staged the same way
-  famseq::DevBuf d_assign;
-  std::vector<int32_t> assign_host;
-  // ... and the mutation-rate host entries' factor tables: FAMSEQ_MAX_RATES blocks of FAMSEQ_RATE_TABLE_DOUBLES, staged the same way
-  famseq::DevBuf d_rate_tables;
-  std::vector<double> rate_tables_host;
-  // ... and the weight host entries' tables: FAMSEQ_MAX_WEIGHTS tables of 3 N doubles, staged the same way
-  famseq::DevBuf d_weights;
-  std::vector<double> weights_host;
-  // the origin kernels' allele rows (FAMSEQ_ALLELE_TABLE_DOUBLES), uploaded once, on their first use, and never changed; and the
-  // mutation rate they are made for, recovered from the model's tables (origin_state: 0 not looked at, 1 found, -1 the tables
-  // are nobody's famseq_transmission_tables: no allele-level model)
-  famseq::DevBuf d_allele;
+  // a product's device table (ExtraSpec::via X_CALL: the host entries' masks, assignments, factor tables or weights, allocated
+  // once at the largest count and staged per call on the compute stream; X_CONST: the origin kernels' allele rows) and the copy
+  // of it the context keeps, which outlives the asynchronous copy out of it
+  famseq::DevBuf d_extra[famseq::SIDE_COUNT];
+  std::vector<uint8_t> extra_host[famseq::SIDE_COUNT];
+  // the mutation rate the origin kernels' allele rows are made for, recovered from the model's tables (origin_state: 0 not
+  // looked at, 1 found, -1 the tables are nobody's famseq_transmission_tables: no allele-level model)
   double origin_mrate = 0;
   int origin_state = 0;
   int64_t trio_dev_sites = 0;
@@ -259,24 +293,25 @@ inline int fail(famseq_ctx *c, int code, const std::string &msg) {
 
 // What a generated kernel takes behind the common eight arguments, in the order of its parameter list: the address of each
 // argument's value (hipModuleLaunchKernel's form).  The call-path forms take their CallIO, the site-prior kernels their prior
-// rows, the pattern kernels their masks and n_patterns and the sampling kernels their seed, site_base and n_draws in front of
-// those, the allele-frequency kernel its start values and n_iter, the relabelling kernels their assignments and n_assign, the
-// mutation-rate kernels their tables and n_rates, the origin kernels their allele rows, the weight kernels their tables and
-// n_weights; the plain forms nothing.
+// rows, a side product's kernels what its ExtraSpec::params names in front of those; the plain forms nothing.
 struct MoreArgs {
   static constexpr int kMax = 4;
   void *at[kMax] = {};
   int n = 0;
   MoreArgs() = default;
   MoreArgs(std::initializer_list<const void *> list) {
-    for (const void *a : list) at[n++] = const_cast<void *>(a);
+    for (const void *a : list) add(a);
   }
+  void add(const void *a) { at[n++] = const_cast<void *>(a); }
 };
 
 // ---- kernels.cpp ----
 // The sum-product family (K_ELIM, K_PRIOR and every kind of side_table()): 0, or an error (FAMSEQ_E_ARG: the engine does not serve
 // this pedigree; FAMSEQ_E_HIP) that is not remembered, the next call tries again.
 int load_or_fail(famseq_ctx *c, int kind);
+// The mutation-rate entries' tables (famseq_rate_tables' blocks): the model's factor table rebuilt with the transmission tables
+// of each rate.
+void rate_tables(const Model &m, const double *rates, int32_t n_rates, double *tables);
 // The origin kernels' precondition: the model's three transmission tables are, bit for bit, famseq_transmission_tables(mu) for
 // mu = pcp2Xm[18] (c->origin_mrate).  0, or FAMSEQ_E_ARG with its message; asks nothing of a device.
 int origin_model(famseq_ctx *c);
@@ -317,15 +352,23 @@ int upload_lut(famseq_ctx *c);
 CallIO make_call_io(const famseq_ctx *c, const uint16_t *d_pl, double *d_gpp, double *d_fpp, int8_t *d_fgt, int32_t n_seq,
                     unsigned long long *d_phase_clk = nullptr);
 int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq);
+// Which of a side kernel's trailing arguments differ from chunk to chunk of a host call.
+struct PerChunk {
+  // a host array with `row` bytes per site, staged chunk by chunk alongside the likelihoods (NULL: none): the site-prior forms'
+  // rows, or a product's per-site table (ExtraSpec::via X_SITE).  The chunk's device copy is argument `at` of lead, or, at < 0,
+  // one more argument behind lead (where the prior rows stand; NULL for a plain form, which does not read it).
+  const void *staged = nullptr;
+  size_t row = 0;
+  int at = -1;
+  // base_at >= 0: argument base_at of lead is site_base + the index of the chunk's first site in the call
+  int base_at = -1;
+  int64_t site_base = 0;
+};
 // The side products' host entries: lk or packed PLs through kernel `g`, whose two outputs have a_row / b_row bytes per site.
-// prior: the site-prior forms' rows [n_sites][6], staged chunk by chunk alongside the likelihoods (NULL: the plain forms).
-// lead: what the kernel takes between the common arguments and the prior rows (the same for every chunk, but for lead.at[base_at]
-// where base_at >= 0: the kernel's site_base, which every chunk gets as site_base + its first site's index in the call).
-// prior_row: the bytes per site of what is staged as `prior`; staged_at >= 0: the staged array is the kernel's argument
-// lead.at[staged_at] instead of its last (famseq_af's start values: 8 bytes per site, in front of n_iter).
+// lead: what the kernel takes between the common arguments and the prior rows, the same for every chunk but for what `per` says.
 int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
-               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior = nullptr,
-               const MoreArgs &lead = {}, int base_at = -1, int64_t site_base = 0, size_t prior_row = 6 * sizeof(double), int staged_at = -1);
+               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const MoreArgs &lead = {},
+               const PerChunk &per = {});
 
 }  // namespace famseq
 #endif

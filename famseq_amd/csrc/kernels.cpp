@@ -13,6 +13,67 @@
 
 namespace famseq {
 
+void rate_tables(const Model &m, const double *rates, int32_t n_rates, double *tables) {
+  Model at = m;
+  for (int32_t r = 0; r < n_rates; ++r) {
+    famseq_transmission_tables(rates[r], at.pcp2, at.pcp2Xf, at.pcp2Xm);
+    build_factor_tables(at, tables + size_t(r) * FAMSEQ_RATE_TABLE_DOUBLES);
+  }
+}
+
+namespace {
+
+// The side products' ExtraSpec::check: the first value of a host entry's table that is out of range.
+int check_masks(famseq_ctx *c, const void *table, int32_t n_patterns, int64_t) {
+  const uint8_t *masks = static_cast<const uint8_t *>(table);
+  for (size_t i = 0, N = c->model.n_members, n = size_t(n_patterns) * N; i < n; ++i)
+    if (masks[i] > 7)
+      return fail(c, FAMSEQ_E_ARG, "masks: pattern " + std::to_string(i / N) + ", member " + std::to_string(i % N) + " is " +
+                                       std::to_string(masks[i]) + "; a mask is 0..7 (bit g: genotype g allowed)");
+  return 0;
+}
+int check_af0(famseq_ctx *c, const void *table, int32_t, int64_t n_sites) {
+  const double *af0 = static_cast<const double *>(table);
+  for (int64_t s = 0; s < n_sites; ++s)
+    if (!(af0[s] >= 0.0 && af0[s] <= 1.0))
+      return fail(c, FAMSEQ_E_ARG, "af0 entries must be finite numbers in [0, 1] (site " + std::to_string(s) + ")");
+  return 0;
+}
+int check_assign(famseq_ctx *c, const void *table, int32_t n_assign, int64_t) {
+  const int32_t *assign = static_cast<const int32_t *>(table);
+  const int N = c->model.n_members;
+  for (size_t i = 0, n = size_t(n_assign) * N; i < n; ++i)
+    if (assign[i] < -1 || assign[i] >= N)
+      return fail(c, FAMSEQ_E_ARG, "assign: assignment " + std::to_string(i / N) + ", member " + std::to_string(i % N) + " is " +
+                                       std::to_string(assign[i]) + "; an entry is -1 (no data) or a member index 0.." + std::to_string(N - 1));
+  return 0;
+}
+int check_rates(famseq_ctx *c, const void *table, int32_t n_rates, int64_t) {
+  const double *rates = static_cast<const double *>(table);
+  for (int32_t r = 0; r < n_rates; ++r)
+    if (!(rates[r] >= 0.0 && rates[r] <= 1.0))
+      return fail(c, FAMSEQ_E_ARG, "rates[" + std::to_string(r) + "] must be a finite number in [0, 1]");
+  return 0;
+}
+int check_weights(famseq_ctx *c, const void *table, int32_t n_weights, int64_t) {
+  const double *weights = static_cast<const double *>(table);
+  const size_t N = c->model.n_members;
+  for (size_t i = 0, n = size_t(n_weights) * 3 * N; i < n; ++i)
+    if (!(weights[i] >= 0.0 && weights[i] <= 1.79769313486231570815e308)) {
+      char v[40];
+      std::snprintf(v, sizeof v, "%g", weights[i]);
+      return fail(c, FAMSEQ_E_ARG, "a weight is a finite number >= 0: weight table " + std::to_string(i / (3 * N)) + ", member " +
+                                       std::to_string(i / 3 % N) + ", genotype " + std::to_string(i % 3) + " is " + v);
+    }
+  return 0;
+}
+
+#define FS_STR_(x) #x
+#define FS_STR(x) FS_STR_(x)
+
+}  // namespace
+
+// The columns of a row: SideProduct and, the last, its ExtraSpec (ctx.h).
 SideTable &side_table() {
   static SideTable table = {
       {"trio", "trio posteriors", "1 (dnm), 2 (joint) or 3 (both)", K_TRIO, K_TRIO_PRIOR, 3, kTrioVariants, trio_source,
@@ -31,25 +92,44 @@ SideTable &side_table() {
        [](const Model &m, int, size_t row[2]) { row[0] = 3 * size_t(m.n_members) * sizeof(double), row[1] = size_t(m.n_members) * sizeof(double); }},  // loo[N][3], fit[N]
       {"pattern", "genotype-pattern posteriors", "1", K_PATTERN, K_PATTERN_PRIOR, 1, kPatternVariants,
        [](const Model &m, int v, int, bool site_prior) { return pattern_source(m, v, site_prior); },
-       [](const Model &, int n_patterns, size_t row[2]) { row[0] = size_t(n_patterns) * sizeof(double), row[1] = sizeof(double); }},  // pat_post[M], loglik
+       [](const Model &, int n_patterns, size_t row[2]) { row[0] = size_t(n_patterns) * sizeof(double), row[1] = sizeof(double); },  // pat_post[M], loglik
+       {X_CALL, "tn", "n_patterns", 1, FAMSEQ_MAX_PATTERNS, "masks", "n_patterns rows of one byte per member", check_masks,
+        [](const Model &m) { return size_t(m.n_members); }}},
       {"sample", "joint posterior draws", "1", K_SAMPLE, K_SAMPLE_PRIOR, 1, kSampleVariants,
        [](const Model &m, int v, int, bool site_prior) { return sample_source(m, v, site_prior); },
-       [](const Model &m, int n_draws, size_t row[2]) { row[0] = size_t(n_draws) * m.n_members, row[1] = size_t(n_draws) * sizeof(double); }},  // samp_gt[K][N], samp_post[K]
+       [](const Model &m, int n_draws, size_t row[2]) { row[0] = size_t(n_draws) * m.n_members, row[1] = size_t(n_draws) * sizeof(double); },  // samp_gt[K][N], samp_post[K]
+       {X_NONE, "sbn", "n_draws", 1, FAMSEQ_MAX_DRAWS}},
       {"af", "founder allele frequency", "1", K_AF, -1, 1, kAfVariants,
        [](const Model &m, int v, int, bool) { return af_source(m, v); },
-       [](const Model &, int, size_t row[2]) { row[0] = sizeof(double), row[1] = 2 * sizeof(double); }},  // af, loglik[2]
+       [](const Model &, int, size_t row[2]) { row[0] = sizeof(double), row[1] = 2 * sizeof(double); },  // af, loglik[2]
+       {X_SITE, "tn", "n_iter", 0, FAMSEQ_MAX_AF_ITER, "af0", "one start value per site", check_af0,
+        [](const Model &) { return sizeof(double); }}},
       {"relabel", "relabelling evidence", "1", K_RELABEL, K_RELABEL_PRIOR, 1, kRelabelVariants,
        [](const Model &m, int v, int, bool site_prior) { return relabel_source(m, v, site_prior); },
-       [](const Model &, int n_assign, size_t row[2]) { row[0] = size_t(n_assign) * sizeof(double), row[1] = sizeof(double); }},  // alt_loglik[M], loglik
+       [](const Model &, int n_assign, size_t row[2]) { row[0] = size_t(n_assign) * sizeof(double), row[1] = sizeof(double); },  // alt_loglik[M], loglik
+       {X_CALL, "tn", "n_assign", 1, FAMSEQ_MAX_RELABEL, "assign", "n_assign rows of one int32 per member", check_assign,
+        [](const Model &m) { return size_t(m.n_members) * sizeof(int32_t); }}},
       {"mutrate", "mutation-rate likelihood profile", "1", K_MUTRATE, K_MUTRATE_PRIOR, 1, kMutrateVariants,
        [](const Model &m, int v, int, bool site_prior) { return mutrate_source(m, v, site_prior); },
-       [](const Model &, int n_rates, size_t row[2]) { row[0] = size_t(n_rates) * sizeof(double), row[1] = sizeof(double); }},  // rate_loglik[R], loglik
+       [](const Model &, int n_rates, size_t row[2]) { row[0] = size_t(n_rates) * sizeof(double), row[1] = sizeof(double); },  // rate_loglik[R], loglik
+       // (the host entries take the rates and stage the tables made from them; the device entries take the tables)
+       {X_CALL, "tn", "n_rates", 1, FAMSEQ_MAX_RATES, "rates", "n_rates mutation rates", check_rates,
+        [](const Model &) { return FAMSEQ_RATE_TABLE_DOUBLES * sizeof(double); },
+        [](const famseq_ctx *c, const void *rates, int32_t n_rates, void *staged) {
+          rate_tables(c->model, static_cast<const double *>(rates), n_rates, static_cast<double *>(staged));
+        },
+        "d_tables", "n_rates factor tables of " FS_STR(FAMSEQ_RATE_TABLE_DOUBLES) " doubles"}},
       {"origin", "phase by transmission", "1", K_ORIGIN, K_ORIGIN_PRIOR, 1, kOriginVariants,
        [](const Model &m, int v, int, bool site_prior) { return origin_source(m, v, site_prior); },
-       [](const Model &m, int, size_t row[2]) { row[0] = row[1] = 4 * trio_children(m).size() * sizeof(double); }},  // origin[K][4], hettx[K][4]
+       [](const Model &m, int, size_t row[2]) { row[0] = row[1] = 4 * trio_children(m).size() * sizeof(double); },  // origin[K][4], hettx[K][4]
+       {X_CONST, "t", nullptr, 1, 1, nullptr, nullptr, nullptr, [](const Model &) { return FAMSEQ_ALLELE_TABLE_DOUBLES * sizeof(double); },
+        [](const famseq_ctx *c, const void *, int32_t, void *staged) { build_allele_tables(c->origin_mrate, static_cast<double *>(staged)); },
+        nullptr, nullptr, origin_model}},  // (said before the device is asked for)
       {"weight", "per-member genotype weights", "1", K_WEIGHT, K_WEIGHT_PRIOR, 1, kWeightVariants,
        [](const Model &m, int v, int, bool site_prior) { return weight_source(m, v, site_prior); },
-       [](const Model &, int n_weights, size_t row[2]) { row[0] = size_t(n_weights) * sizeof(double), row[1] = sizeof(double); }},  // wt_loglik[M], loglik
+       [](const Model &, int n_weights, size_t row[2]) { row[0] = size_t(n_weights) * sizeof(double), row[1] = sizeof(double); },  // wt_loglik[M], loglik
+       {X_CALL, "tn", "n_weights", 1, FAMSEQ_MAX_WEIGHTS, "weights", "n_weights tables of three doubles per member", check_weights,
+        [](const Model &m) { return 3 * size_t(m.n_members) * sizeof(double); }, nullptr, "d_weights"}},
   };
   return table;
 }

@@ -218,26 +218,28 @@ int run_host(famseq_ctx *c, int64_t n_sites, const HostIO &io, int n_seq) {
   return rc;
 }
 
-// ... and the trio and MAP entries (plain and site-prior): per chunk [unpack] -> kernel, on the entry's own set of slots.  out_a / out_b: the two
-// per-site outputs (NULL: not wanted), a_row / b_row their bytes per site (0: the pedigree has none).
+// ... and every side product's host entries (side_table(); plain and site-prior): per chunk [unpack] -> kernel, on the product's own
+// set of slots.  out_a / out_b: the two per-site outputs (NULL: not wanted), a_row / b_row their bytes per site (0: the pedigree
+// has none).  What a product's kernel takes beside the common arguments arrives as `lead`, made by the caller; `per` names the
+// arguments a chunk gets its own value of: the device copy of what is staged with the chunk in B_PRIOR, and site_base.
 int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, const double *lk, const uint16_t *pl16, int32_t n_seq,
-               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const double *prior, const MoreArgs &lead,
-               int base_at, int64_t site_base, size_t prior_row_, int staged_at) {
+               const uint8_t *flags, void *out_a, size_t a_row, void *out_b, size_t b_row, uint8_t *status, const MoreArgs &lead,
+               const PerChunk &per) {
   const int N = c->model.n_members;
   const size_t row = size_t(3) * N * sizeof(double), pl_row = pl16 ? size_t(n_seq) * 3 * sizeof(uint16_t) : 0;
-  const size_t prior_row = prior ? prior_row_ : 0;
+  const size_t staged_row = per.staged ? per.row : 0;
   ChunkJob job;
   job.n_sites = n_sites;
   job.chunk = chunk_for(c, n_sites, std::max(row, a_row + 1));
   size_t want[B_COUNT] = {};
   want[B_LK] = row, want[B_FLAGS] = want[B_STATUS] = 1, want[B_PL] = pl_row, want[B_OUT_A] = a_row, want[B_OUT_B] = b_row;
-  want[B_PRIOR] = prior_row;
+  want[B_PRIOR] = staged_row;
   const int rc = reserve(c, t, job.chunk, want);
   if (rc != 0) return rc;
   job.copy_in(B_PL, pl_row, pl16);
   if (!pl16) job.copy_in(B_LK, row, lk);
   job.copy_in(B_FLAGS, 1, flags);
-  job.copy_in(B_PRIOR, prior_row, prior);
+  job.copy_in(B_PRIOR, staged_row, per.staged);
   job.copy_out(B_OUT_A, a_row, out_a);
   job.copy_out(B_OUT_B, b_row, out_b);
   job.copy_out(B_STATUS, 1, status);
@@ -245,12 +247,12 @@ int side_batch(famseq_ctx *c, SlotSet &t, const GenKernel &g, int64_t n_sites, c
     DevBuf *d = t.buf[s];
     if (pl16)
       HIP_TRY(c, launch_unpack_pl16(d[B_PL].as<uint16_t>(), c->d_col.as<int32_t>(), c->d_lut.as<double>(), N, n_seq, n, d[B_LK].as<double>(), s_k));
-    const void *d_prior = prior ? d[B_PRIOR].p : nullptr;
+    const void *d_staged = per.staged ? d[B_PRIOR].p : nullptr;
     MoreArgs more = lead;
-    const long chunk_base = long(site_base + lo);  // (read when the launch is enqueued)
-    if (base_at >= 0) more.at[base_at] = const_cast<long *>(&chunk_base);
-    if (staged_at >= 0) more.at[staged_at] = &d_prior;
-    else more.at[more.n++] = &d_prior;  // (behind the last parameter of a plain form: not read)
+    const long chunk_base = long(per.site_base + lo);  // (read when the launch is enqueued)
+    if (per.base_at >= 0) more.at[per.base_at] = const_cast<long *>(&chunk_base);
+    if (per.at >= 0) more.at[per.at] = &d_staged;
+    else more.add(&d_staged);  // (behind the last parameter of a plain form: not read)
     HIP_TRY(c, launch_generated(c, g, n, d[B_LK].as<double>(), flags ? d[B_FLAGS].as<uint8_t>() : nullptr, out_a ? d[B_OUT_A].p : nullptr,
                                 out_b ? d[B_OUT_B].p : nullptr, status ? d[B_STATUS].as<uint8_t>() : nullptr, s_k, 0, more));
     return 0;

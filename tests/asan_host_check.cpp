@@ -4,7 +4,7 @@
 // -fsanitize=address,undefined, and drives them the way the ABI's callers do on plan-only
 // contexts: model setup and its rejections, plan options (valid and invalid), every variant and form of
 // both generators (the sum-product family's site-prior, trio and MAP kernels among them), the JSON description, the error paths of the compute entry points without a
-// device, and the JIT's failure path (no compiler) of every kind of generated kernel.  Any sanitizer
+// device (the side products' table of extra arguments and its value checks among them), and the JIT's failure path (no compiler) of every kind of generated kernel.  Any sanitizer
 // report aborts with a non-zero exit status; the program prints one line per pedigree.
 #include <dirent.h>
 
@@ -162,6 +162,38 @@ void drive(const Ped &p) {
     CHECK(famseq_trio_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, joint.data(), dnm.data(), st.data()) == FAMSEQ_E_NODEVICE);
     CHECK(famseq_map_batch(c, 4, nullptr, pl.data(), seq.data(), n, nullptr, fgt.data(), post.data(), st.data()) == FAMSEQ_E_NODEVICE);
     CHECK(std::strstr(famseq_last_error(c), "no CPU path") != nullptr);
+    // the side products whose entries take a table, a count or sampling's scalars: the table's row is walked and its check reads
+    // every value of the caller's array (then the device is what is missing); the last value bad, no count, no table
+    std::vector<uint8_t> masks(2 * n, 7);
+    std::vector<int32_t> assign(2 * n, -1);
+    std::vector<double> rates(2, 1e-7), weights(2 * 3 * n, 1.0), af0(4, 0.1), out(FAMSEQ_RATE_TABLE_DOUBLES + 64 * n);
+    double *o = out.data();
+    CHECK(famseq_pattern_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, masks.data(), 2, o, o, st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_relabel_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, assign.data(), 2, o, o, st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_mutrate_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, rates.data(), 2, o, o, st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_weight_prior_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, lk.data(), weights.data(), 2, o, o, st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_af_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, af0.data(), 8, o, o, st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_sample_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, 7, 1000, 3, fgt.data(), o, st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_origin_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, o, o, st.data()) == FAMSEQ_E_NODEVICE);
+    CHECK(famseq_loo_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, o, o, st.data()) == FAMSEQ_E_NODEVICE);
+    masks.back() = 8, assign.back() = n, rates.back() = 1.5, weights.back() = -1.0, af0.back() = 1.5;
+    CHECK(famseq_pattern_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, masks.data(), 2, o, o, st.data()) == FAMSEQ_E_ARG);
+    CHECK(std::strstr(famseq_last_error(c), "masks: pattern 1, member") != nullptr);
+    CHECK(famseq_relabel_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, assign.data(), 2, o, o, st.data()) == FAMSEQ_E_ARG);
+    CHECK(std::strstr(famseq_last_error(c), "assign: assignment 1, member") != nullptr);
+    CHECK(famseq_mutrate_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, rates.data(), 2, o, o, st.data()) == FAMSEQ_E_ARG);
+    CHECK(famseq_rate_tables(c, rates.data(), 2, o) == FAMSEQ_E_ARG && std::strstr(famseq_last_error(c), "rates[1] must be") != nullptr);
+    CHECK(famseq_rate_tables(c, rates.data(), 1, o) == 0);
+    CHECK(famseq_weight_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, weights.data(), 2, o, o, st.data()) == FAMSEQ_E_ARG);
+    CHECK(std::strstr(famseq_last_error(c), "weight table 1, member") != nullptr);
+    CHECK(famseq_af_batch(c, 4, lk.data(), nullptr, seq.data(), n, nullptr, af0.data(), 8, o, o, st.data()) == FAMSEQ_E_ARG);
+    CHECK(std::strstr(famseq_last_error(c), "(site 3)") != nullptr);
+    CHECK(famseq_weight_batch_device(c, 4, nullptr, nullptr, seq.data(), n, nullptr, weights.data(), 33, o, o, st.data(), nullptr) == FAMSEQ_E_ARG);
+    CHECK(std::strstr(famseq_last_error(c), "n_weights must be 1..32, got 33") != nullptr);
+    CHECK(famseq_mutrate_batch_device(c, 4, nullptr, nullptr, seq.data(), n, nullptr, nullptr, 2, o, o, st.data(), nullptr) == FAMSEQ_E_ARG);
+    CHECK(std::strstr(famseq_last_error(c), "d_tables must be given (n_rates factor tables of 432 doubles)") != nullptr);
+    CHECK(famseq_sample_batch(c, 4, nullptr, nullptr, seq.data(), n, nullptr, 7, -1, 3, fgt.data(), o, st.data()) == FAMSEQ_E_ARG);
+    CHECK(std::strstr(famseq_last_error(c), "site_base must be >= 0, got -1") != nullptr);
   }
   std::vector<int8_t> g(n * 4);
   famseq_call_genotypes(lk.data(), n * 4, g.data());
