@@ -362,127 +362,120 @@ class Emitter {
   // the decimal digits of scale in evidence_body's Z_ and W0_
   int evidence_scale_digits() const { return 7 * (g_.cut.empty() ? (int)g_.scaled.size() : 1); }
 
-  // Genotype-pattern posteriors (famseq_pattern): the sum pass of evidence_body, run n_patterns + 1 times on one read of the
-  // site's rows.  Pass 0 takes the rows as they are; pass m = 1 .. n_patterns takes member p's entry g as
-  // (mask[m - 1][p] >> g) & 1 ? l_g : 0.0 — a select, no multiplication, no rounding — formed before loc() sees it, so the
-  // founders' priors, the site's own prior rows, the male chrX row and a cut member's lam all follow unchanged.  The masks are
-  // wave-uniform: the shell packs them into LDS words once per workgroup (s_mw: four bits per member, eight members per word,
-  // row 0 all ones), and a pass reads its NMW words into scalar registers.  The loop is `#pragma unroll 1`: the pass's text
-  // stands once whatever n_patterns is.  Where the likelihoods sit in registers (r<p>_<g>: the shell's l<p>_<g> under another
-  // name) a pass's masked values shadow the shell's names; in the lean form the names are macros and are defined again, the
-  // row read afresh at each use and the select applied to what was read.
-  // Per pass: Zp_, the pass's total weight (scaled as evidence_body's Z_: evidence_scale_digits()), then `per_pass`.
-  std::string pattern_body(const std::string &per_pass) {
-    const int nmw = (g_.N + 7) / 8;
-    std::ostringstream head;
-    auto bit = [&](int p, int g) { return "(mw" + num(p / 8) + " >> " + num(4 * (p % 8) + g) + ") & 1u"; };
-    if (!lean_) {
-      for (int p = 0; p < g_.N; ++p)
-        head << "      const double r" << p << "_0 = l" << p << "_0, r" << p << "_1 = l" << p << "_1, r" << p << "_2 = l" << p << "_2;\n";
-    } else {
-      for (int p = 0; p < g_.N; ++p)
-        for (int g = 0; g < 3; ++g)
-          head << "#undef l" << p << "_" << g << "\n#define l" << p << "_" << g << " __extension__ ({ const double v_ = lgv[" << 3 * p + g
-               << "]; " << bit(p, g) << " ? v_ : 0.0; })\n";
+  // ---- The per-pass products (famseq_pattern, famseq_relabel, famseq_mutrate, famseq_weight): the sum pass of evidence_body run
+  // count + 1 times on one read of the site's rows — pass 0 on the network as it is, pass k >= 1 on what row k - 1 of the
+  // product's table makes of it.  What they share is written here once:
+  //   - the loop is `#pragma unroll 1`: the pass's text stands once whatever the count is;
+  //   - per pass: Zp_, the pass's total weight (scaled as evidence_body's Z_: evidence_scale_digits()), then `per_pass`
+  //     (pass_product(): pass 0 keeps the evidence, a later pass stores its result);
+  //   - only pass 0's Z that is not a positive finite number fails the site: per_pass breaks out of the loop there.
+  // `before` stands in front of the loop and `inside` in front of the pass: what the product does to the network, which is all
+  // that pattern_body, relabel_body, mutrate_body and weight_body write.  `counter` is the loop's variable (part of the text).
+  std::string pass_loop(const std::string &before, const std::string &inside, const std::string &counter, const std::string &per_pass) {
+    return before + "#pragma unroll 1\n      for (int " + counter + " = 0; " + counter + " <= last_; ++" + counter + ") {\n" + inside + sum_pass() +
+           per_pass + "      }\n";
+  }
+  // A pass that takes the members' rows changed, entry by entry (pattern_body, weight_body), the change made where the names
+  // l<p>_<g> are resolved, before loc() sees them, so the founders' priors, the site's own prior rows, the male chrX row and a
+  // cut member's lam all follow unchanged.  Where the likelihoods sit in registers they are copied in front of the loop
+  // (r<p>_<g>: the shell's l<p>_<g> under another name) and a pass's changed values shadow the shell's names; in the lean form
+  // the names are macros and are defined again, the row read afresh at each use (v_) and changed there.  value(p, g, row) gives
+  // the statements in front of entry g of member p, if any, and the entry as an expression of `row` (r<p>_<g> or v_).
+  using RowValue = std::function<std::pair<std::string, std::string>(int p, int g, const std::string &row)>;
+  void changed_rows(std::ostream &before, std::ostream &inside, const RowValue &value) {
+    for (int p = 0; p < g_.N; ++p) {
+      if (!lean_) before << "      const double r" << p << "_0 = l" << p << "_0, r" << p << "_1 = l" << p << "_1, r" << p << "_2 = l" << p << "_2;\n";
+      for (int g = 0; g < 3; ++g) {
+        const std::string l = "l" + num(p) + "_" + num(g);
+        const auto [pre, v] = value(p, g, lean_ ? "v_" : "r" + num(p) + "_" + num(g));
+        if (lean_)
+          before << "#undef " << l << "\n#define " << l << " __extension__ ({ const double v_ = lgv[" << 3 * p + g << "]; " << pre << v << "; })\n";
+        else
+          inside << pre << "      const double " << l << " = " << v << ";\n";
+      }
     }
-    head << "#pragma unroll 1\n      for (int pt_ = 0; pt_ <= last_; ++pt_) {\n";
-    for (int k = 0; k < nmw; ++k)
-      head << "      const unsigned mw" << k << " = __builtin_amdgcn_readfirstlane(s_mw[pt_ * " << nmw << " + " << k << "]);\n";
-    if (!lean_)
-      for (int p = 0; p < g_.N; ++p)
-        for (int g = 0; g < 3; ++g)
-          head << "      const double l" << p << "_" << g << " = " << bit(p, g) << " ? r" << p << "_" << g << " : 0.0;\n";
-    return head.str() + sum_pass() + per_pass + "      }\n";
   }
 
-  // Relabelling evidence (famseq_relabel): the sum pass of evidence_body, run n_assign + 1 times on one read of the site's rows,
-  // pass j giving member p the likelihood row that row j of the assignment table names (pass 0: the identity).  The substitution
-  // is made where the names l<p>_<g> are resolved, before loc() sees them, so the founders' priors, the site's own prior rows, the
-  // male chrX row and a cut member's lam all follow unchanged.  The table is wave-uniform: the shell packs it into LDS words once
-  // per workgroup (s_aw: `bits` bits per member, row 0 the identity, "no data" and every entry outside 0 .. N-1 stored as N), and a
-  // pass reads its words into scalar registers; e<p> = 3 * entry is scalar arithmetic.  The loop is `#pragma unroll 1`: the
-  // pass's text stands once whatever n_assign is.  The names are macros in both forms and are defined again here:
+  // Genotype-pattern posteriors (famseq_pattern): pass m = 1 .. n_patterns takes member p's entry g as
+  // (mask[m - 1][p] >> g) & 1 ? l_g : 0.0 — a select, no multiplication, no rounding (changed_rows).  The masks are
+  // wave-uniform: the shell packs them into LDS words once per workgroup (s_mw: four bits per member, eight members per word,
+  // row 0 all ones), and a pass reads its NMW words into scalar registers.
+  std::string pattern_body(const std::string &counter, const std::string &per_pass) {
+    const int nmw = (g_.N + 7) / 8;
+    std::ostringstream before, inside;
+    for (int k = 0; k < nmw; ++k)
+      inside << "      const unsigned mw" << k << " = __builtin_amdgcn_readfirstlane(s_mw[" << counter << " * " << nmw << " + " << k << "]);\n";
+    changed_rows(before, inside, [&](int p, int g, const std::string &row) {
+      return std::make_pair(std::string(), "(mw" + num(p / 8) + " >> " + num(4 * (p % 8) + g) + ") & 1u ? " + row + " : 0.0");
+    });
+    return pass_loop(before.str(), inside.str(), counter, per_pass);
+  }
+
+  // Relabelling evidence (famseq_relabel): pass j gives member p the likelihood row that row j of the assignment table names
+  // (pass 0: the identity).  The substitution is made where the names l<p>_<g> are resolved, before loc() sees them, so the
+  // founders' priors, the site's own prior rows, the male chrX row and a cut member's lam all follow unchanged.  The table is
+  // wave-uniform: the shell packs it into LDS words once per workgroup (s_aw: `bits` bits per member, row 0 the identity, "no
+  // data" and every entry outside 0 .. N-1 stored as N), and a pass reads its words into scalar registers; e<p> = 3 * entry is
+  // scalar arithmetic.  The names are macros in both forms and are defined again here:
   //   rows in LDS (lds_rows)  the lane's row holds N + 1 triples, the last (1, 1, 1): member p's entry g is lrow[e<p> + g], and
   //                           "no data" is an index like any other;
   //   lean                    read from the site's row in global memory at each use, at the entry clamped into the row (N reads
   //                           member 0's), a select putting 1.0 in the place of what was read.
-  // Per pass: Zp_, the pass's total weight (scaled as evidence_body's Z_: evidence_scale_digits()), then `per_pass`.
-  std::string relabel_body(const std::string &per_pass, bool lds_rows, int bits) {
+  std::string relabel_body(const std::string &counter, const std::string &per_pass, bool lds_rows, int bits) {
     const int per = 32 / bits, naw = (g_.N + per - 1) / per;
-    std::ostringstream head;
+    std::ostringstream before, inside;
     for (int p = 0; p < g_.N; ++p)
       for (int g = 0; g < 3; ++g) {
-        head << "#undef l" << p << "_" << g << "\n#define l" << p << "_" << g;
-        if (lds_rows) head << " lrow[e" << p << " + " << g << "]\n";
-        else head << " __extension__ ({ const double v_ = lgv[e" << p << " + " << g << "]; o" << p << " ? 1.0 : v_; })\n";
+        before << "#undef l" << p << "_" << g << "\n#define l" << p << "_" << g;
+        if (lds_rows) before << " lrow[e" << p << " + " << g << "]\n";
+        else before << " __extension__ ({ const double v_ = lgv[e" << p << " + " << g << "]; o" << p << " ? 1.0 : v_; })\n";
       }
-    head << "#pragma unroll 1\n      for (int ps_ = 0; ps_ <= last_; ++ps_) {\n";
     for (int k = 0; k < naw; ++k)
-      head << "      const unsigned aw" << k << " = __builtin_amdgcn_readfirstlane(s_aw[ps_ * " << naw << " + " << k << "]);\n";
+      inside << "      const unsigned aw" << k << " = __builtin_amdgcn_readfirstlane(s_aw[" << counter << " * " << naw << " + " << k << "]);\n";
     for (int p = 0; p < g_.N; ++p) {
       const std::string entry = "(int)((aw" + num(p / per) + " >> " + num(bits * (p % per)) + ") & " + num((1 << bits) - 1) + "u)";
-      if (lds_rows) head << "      const int e" << p << " = 3 * " << entry << ";\n";
+      if (lds_rows) inside << "      const int e" << p << " = 3 * " << entry << ";\n";
       else
-        head << "      const int n" << p << " = " << entry << ";\n      const bool o" << p << " = n" << p << " >= " << g_.N << ";\n"
-             << "      const int e" << p << " = o" << p << " ? 0 : 3 * n" << p << ";\n";
+        inside << "      const int n" << p << " = " << entry << ";\n      const bool o" << p << " = n" << p << " >= " << g_.N << ";\n"
+               << "      const int e" << p << " = o" << p << " ? 0 : 3 * n" << p << ";\n";
     }
-    return head.str() + sum_pass() + per_pass + "      }\n";
+    return pass_loop(before.str(), inside.str(), counter, per_pass);
   }
 
-  // The mutation-rate likelihood profile (famseq_mutrate): the sum pass of evidence_body, run n_rates + 1 times on one read of
-  // the site's rows, pass 0 with the transmission entries of the context's own table (tc_g), pass r + 1 with those of block r of
-  // rt_g (build_factor_tables' layout, 432 doubles a block).  Every T() of the pass reads trt[] (EmitOptions::t_from), which
-  // the pass sets in front; the founders' priors (tcf[], or the site's own rows), the rows and a cut member's lam are the
-  // operands they are in evidence_body, so a pass is that body's statements on another table.
+  // The mutation-rate likelihood profile (famseq_mutrate): pass 0 with the transmission entries of the context's own table
+  // (tc_g), pass r + 1 with those of block r of rt_g (build_factor_tables' layout, 432 doubles a block).  Every T() of the pass
+  // reads trt[] (EmitOptions::t_from), which the pass sets in front; the founders' priors (tcf[], or the site's own rows), the
+  // rows and a cut member's lam are the operands they are in evidence_body, so a pass is that body's statements on another table.
   // trt is wave-uniform in every variant (the pass number through readfirstlane, x_ the chrX loop's, which the fence-free
   // variant takes as well here): the entries arrive by scalar loads, as tcx's do, and cost neither a VGPR nor a vector-memory
   // instruction per use, which a table addressed by the lane's flags would.
-  // The loop is `#pragma unroll 1`: the pass's text stands once whatever n_rates is.
-  // Per pass: Zp_, the pass's total weight (scaled as evidence_body's Z_: evidence_scale_digits()), then `per_pass`.
-  std::string mutrate_body(const std::string &per_pass) {
-    std::ostringstream head;
-    head << "#pragma unroll 1\n      for (int ps_ = 0; ps_ <= last_; ++ps_) {\n"
-         << "      const int pu_ = __builtin_amdgcn_readfirstlane(ps_);\n"
-         << "      const double *trt = (pu_ == 0 ? tc_g : rt_g + (long)(pu_ - 1) * RTD) + x_ * 216;\n";
-    return head.str() + sum_pass() + per_pass + "      }\n";
+  std::string mutrate_body(const std::string &counter, const std::string &per_pass) {
+    return pass_loop("",
+                     "      const int pu_ = __builtin_amdgcn_readfirstlane(" + counter + ");\n"
+                     "      const double *trt = (pu_ == 0 ? tc_g : rt_g + (long)(pu_ - 1) * RTD) + x_ * 216;\n",
+                     counter, per_pass);
   }
 
-  // Per-member genotype weights (famseq_weight): the sum pass of evidence_body, run n_weights + 1 times on one read of the
-  // site's rows.  Pass 0 takes the rows as they are; pass m = 1 .. n_weights takes member p's entry g as
-  // r<p>_<g> * wt[(m - 1) * 3 N + 3 p + g] — one rounded multiplication, formed where the names l<p>_<g> are resolved, before
-  // loc() sees it, so the founders' priors, the site's own prior rows, the male chrX row and a cut member's lam all follow
-  // unchanged, and the pass is evidence_body's statements on the rows lk * w formed in double.  Every member has a weight,
-  // sequenced or not (a phenotype needs no reads): an unsequenced member's row is the one the shell supplies.
+  // Per-member genotype weights (famseq_weight): pass m = 1 .. n_weights takes member p's entry g as
+  // r<p>_<g> * wt[(m - 1) * 3 N + 3 p + g] — one rounded multiplication (changed_rows; lean: row and weight read afresh at each
+  // use and multiplied there) — and the pass is evidence_body's statements on the rows lk * w formed in double.  Every member has
+  // a weight, sequenced or not (a phenotype needs no reads): an unsequenced member's row is the one the shell supplies.
   // The weights are read where they lie, through wtp, a wave-uniform pointer (the pass number through readfirstlane, member
   // and genotype constants of the text), as mutrate_body reads trt: they arrive by scalar loads and cost neither a VGPR nor a
   // vector-memory instruction per use; (32 + 1) * 3 N doubles would not fit the LDS beside the tables of the wide pedigrees.
   // Pass 0 multiplies by 1.0, which changes no bit of a row (x * 1.0 is x for every double), so the text is the same in every
   // pass; its wtp points at the batch's first likelihood row — 3 N readable doubles whatever the call gave as its table, whose
   // values the select drops — so that wt_g is not read by a call that wants no weighted pass.
-  // The loop is `#pragma unroll 1`: the pass's text stands once whatever n_weights is.  Where the likelihoods sit in registers
-  // (r<p>_<g>: the shell's l<p>_<g> under another name) a pass's weighted values shadow the shell's names; in the lean form the
-  // names are macros and are defined again, row and weight read afresh at each use and multiplied there.
-  // Per pass: Zp_, the pass's total weight (scaled as evidence_body's Z_: evidence_scale_digits()), then `per_pass`.
-  std::string weight_body(const std::string &per_pass) {
-    std::ostringstream head;
-    if (!lean_) {
-      for (int p = 0; p < g_.N; ++p)
-        head << "      const double r" << p << "_0 = l" << p << "_0, r" << p << "_1 = l" << p << "_1, r" << p << "_2 = l" << p << "_2;\n";
-    } else {
-      for (int p = 0; p < g_.N; ++p)
-        for (int g = 0; g < 3; ++g)
-          head << "#undef l" << p << "_" << g << "\n#define l" << p << "_" << g << " __extension__ ({ const double v_ = lgv[" << 3 * p + g
-               << "]; const double w_ = wtp[" << 3 * p + g << "]; v_ * (pu_ == 0 ? 1.0 : w_); })\n";
-    }
-    head << "#pragma unroll 1\n      for (int ps_ = 0; ps_ <= last_; ++ps_) {\n"
-         << "      const int pu_ = __builtin_amdgcn_readfirstlane(ps_);\n"
-         << "      const double *wtp = pu_ == 0 ? lk_g : wt_g + (long)(pu_ - 1) * W3;\n";
-    if (!lean_)
-      for (int p = 0; p < g_.N; ++p)
-        for (int g = 0; g < 3; ++g)
-          head << "      const double wg" << p << "_" << g << " = wtp[" << 3 * p + g << "];\n      const double l" << p << "_" << g << " = r" << p
-               << "_" << g << " * (pu_ == 0 ? 1.0 : wg" << p << "_" << g << ");\n";
-    return head.str() + sum_pass() + per_pass + "      }\n";
+  std::string weight_body(const std::string &counter, const std::string &per_pass) {
+    std::ostringstream before, inside;
+    inside << "      const int pu_ = __builtin_amdgcn_readfirstlane(" << counter << ");\n"
+           << "      const double *wtp = pu_ == 0 ? lk_g : wt_g + (long)(pu_ - 1) * W3;\n";
+    changed_rows(before, inside, [&](int p, int g, const std::string &row) {
+      const std::string at = "wtp[" + num(3 * p + g) + "]", w = lean_ ? "w_" : "wg" + num(p) + "_" + num(g);
+      return std::make_pair(lean_ ? "const double w_ = " + at + "; " : "      const double " + w + " = " + at + ";\n",
+                            row + " * (pu_ == 0 ? 1.0 : " + w + ")");
+    });
+    return pass_loop(before.str(), inside.str(), counter, per_pass);
   }
 
   // The founders' allele frequency by maximum likelihood (famseq_af): EM on q, every step one sum pass and the founders' marginals
@@ -824,8 +817,8 @@ class Emitter {
     o_.str("");
     return out;
   }
-  // One sum pass inside a per-pass loop (pattern_body, relabel_body, mutrate_body): evidence_body's statements for the total
-  // weight, which it leaves in Zp_.  Leaves o_ empty.
+  // One sum pass inside a per-pass loop (pass_loop): evidence_body's statements for the total weight, which it leaves in Zp_.
+  // Leaves o_ empty.
   std::string sum_pass() {
     if (!g_.cut.empty())
       return cut_loop("      double Zt_ = 0;\n", /*wc=*/false, /*wall=*/true, [&] { o_ << "      Zt_ = Zt_ + Wall;\n"; fence(1); }) +
@@ -1355,8 +1348,8 @@ namespace {
 // and stores its results straight back — 8 bytes per lane and instruction, a cache line per lane.  What the staged shell
 // (kernel_shell) buys with its LDS rows (coalesced 16-byte accesses) costs it the CU's LDS: 3N doubles per lane leave two
 // waves per CU at 48 members and nothing beyond about a hundred; this form needs 3.4 KB of LDS (the factor tables) whatever
-// N is, runs four waves per CU, and has no barrier after the first.  Three kernels have this form and fill in what differs:
-// famseq_elim's variants 8..11 (direct_source), famseq_trio (trio_source) and famseq_map (map_source).
+// N is, runs four waves per CU, and has no barrier after the first.  famseq_elim's variants 8..11 (direct_source) and every side
+// product have this form: they start from begin_side() and fill in what differs.
 // site_prior: the lane's row of prior_g in three 16-byte loads issued beside the likelihood loads, the Known bit not read.
 struct LaneShell {
   std::string entry;       // ("_prior" is appended with site priors)
@@ -1460,6 +1453,81 @@ Graph graph_or_throw(const Model &m) {
   return g;
 }
 
+// What every user of lane_shell starts from: the graph, the fence level f = variant (checked against the kernel's count), the
+// emitter's options and a shell with the common rules set — entry famseq_<name>, the comment describe() makes of `lead`, the
+// workgroup size, which fences and loops level f takes, and where the likelihoods live: from forty members on they are read
+// from the lane's row at each use (lean, shell and emitter alike), as variant 8+ of famseq_elim does when asked: 3 N doubles of
+// registers are the widest pedigrees' wall.  A kernel that deviates overrides behind the call and says why; each ends in its
+// own `return lane_shell(m, d)`.
+struct SideShell {
+  Graph g;
+  int f;
+  EmitOptions eo;
+  LaneShell d;
+};
+SideShell begin_side(const Model &m, const std::string &name, const std::string &lead, int variant, int n_variants, bool site_prior) {
+  SideShell s{graph_or_throw(m), variant, {}, {}};
+  if (variant < 0 || variant >= n_variants)
+    throw std::runtime_error(name + "_source: variant must be 0.." + std::to_string(n_variants - 1));
+  s.eo = emit_options(s.f, "pg", site_prior);
+  s.d.lean = s.eo.lean = m.n_members >= 40;
+  s.d.entry = "famseq_" + name;
+  s.d.comment = describe(lead, s.g, std::to_string(s.f), site_prior);
+  s.d.bt = elim_block_threads(m, false);
+  s.d.fence_single = s.f >= 3, s.d.chrx_loop = s.f >= 1, s.d.site_prior = site_prior;
+  return s;
+}
+
+// ---- Text that the epilogues share.
+// the status byte of a kernel with the trio kernel's rules
+std::string status_store() { return "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n"; }
+// `inner` for a site that failed
+std::string fail_block(const std::string &inner) { return "    if (single_fail || bn_fail) {\n" + inner + "    }\n"; }
+// ptr[0 .. count) = value under `guard` (the pointer itself where none is given: a null output is skipped), the loop
+// `#pragma unroll 1`; `indent`: the guard's column (6 inside fail_block)
+std::string fill(const std::string &ptr, const std::string &count, const std::string &value = "kNaN", const std::string &guard = "", int indent = 6) {
+  const std::string in(indent, ' ');
+  return in + "if (" + (guard.empty() ? ptr : guard) + ") {\n#pragma unroll 1\n" + in + "  for (int k = 0; k < " + count + "; ++k) " + ptr + "[k] = " + value +
+         ";\n" + in + "}\n";
+}
+// a count argument clamped into 0 .. its define, once per workgroup (the host checks, the kernel clamps)
+std::string clamp_count(const std::string &n, const std::string &arg, const std::string &max) {
+  return "  const int " + n + " = " + arg + " < 0 ? 0 : (" + arg + " > " + max + " ? " + max + " : " + arg + ");\n";
+}
+
+// A per-pass product (Emitter::pass_loop), as far as its shell goes.  Such a kernel has the evidence kernel's rules and shell.
+// Beyond the common arguments it takes a table and a count (1 .. its maximum; the host checks, the kernel clamps); its outputs
+// per site are one value per row of the table and loglik, famseq_evidence's, from pass 0; either may be null, and without the
+// first only pass 0 runs (last_).  A new one supplies this record, its table's arguments and staging, and an Emitter body that
+// hands pass_loop what a pass does to the network.
+struct PassProduct {
+  const char *out_arg, *out;      // the per-pass output: the kernel's argument and the site's pointer into it
+  const char *n_arg, *n, *n_max;  // the count: the kernel's argument, its clamped value, the define that bounds it
+  const char *counter;            // the loop's variable
+  const char *ll;                 // pass 0's log10 Z without the reference's 1e7: loglik
+  const char *result = nullptr;   // what a later pass stores, of its Zp_; none: its log10 Z as pass 0's, not clamped
+  bool z0 = false;                // pass 0's Zp_ is kept in Z0_ for `result`
+};
+// Fills in the shell's side of product p — the clamp (d.prologue), the output pointer and last_ (site_decls), the variables
+// (site_vars), NaN for a failed site and the loglik store (epilogue) — and returns the `per_pass` text of its body: pass 0
+// fails the site and leaves the loop where Zp_ is not a positive finite number, else keeps loglik; a later pass stores.
+// `digits`: Emitter::evidence_scale_digits().
+std::string pass_product(const PassProduct &p, int digits, LaneShell &d) {
+  const std::string out = p.out, n = p.n, ct = p.counter, ll = p.ll, log = "log10(Zp_) - " + std::to_string(digits) + ".0";
+  d.prologue = clamp_count(n, p.n_arg, p.n_max);
+  d.site_decls = "    double *" + out + " = " + p.out_arg + " ? " + p.out_arg + " + site * " + n + " : nullptr;\n"
+                 "    const int last_ = " + out + " ? " + n + " : 0;\n";
+  d.site_vars = "    double " + ll + " = kNaN" + (p.z0 ? ", Z0_ = 0" : "") + ";\n";
+  d.epilogue = fail_block("      " + ll + " = kNaN;\n" + fill(out, n)) +
+               "    if (loglik_g) __builtin_nontemporal_store(" + ll + ", loglik_g + site);\n" + status_store();
+  return "      if (" + ct + " == 0) {\n"
+         "        if (!(Zp_ > 0 && Zp_ <= 1.79769313486231570815e308)) { bn_fail = true; break; }\n"
+         "        " + (p.z0 ? "Z0_ = Zp_; " : "") + ll + " = " + log + ";\n"
+         "      } else {\n"
+         "        __builtin_nontemporal_store(" + (p.result ? p.result : log) + ", " + out + " + (" + ct + " - 1));\n"
+         "      }\n";
+}
+
 }  // namespace
 
 std::vector<int> trio_children(const Model &m) {
@@ -1472,7 +1540,10 @@ std::vector<int> trio_children(const Model &m) {
 // The trio kernel: no single posterior stored and no shortcut, every site that passes the single-posterior rule runs the full
 // network.  Outputs per site: joint[27 K] and dnm[K] (either may be null), status.
 std::string trio_source(const Model &m, int variant, int form, bool site_prior) {
-  const Graph g = graph_or_throw(m);
+  const bool want_dnm = form & 1, want_joint = form & 2;
+  // (the fence level is the variant's low two bits: every value is taken; the output form is the kernel's own argument)
+  auto [g, f, eo, d] = begin_side(m, "trio", "trio posteriors (" + std::string(want_dnm && want_joint ? "de novo + joint" : (want_dnm ? "de novo" : "joint")) + ")",
+                                  variant & 3, 4, site_prior);
   if (form < 1 || form > 3) throw std::runtime_error("trio_source: form must be 1 (dnm), 2 (joint) or 3 (both)");
   const std::vector<int> kids = trio_children(m);
   // the de novo mask: where the mutation-free transmission table of the child is exactly 0 (model.cpp), [autosome, chrX][K][27]
@@ -1484,16 +1555,6 @@ std::string trio_source(const Model &m, int variant, int form, bool site_prior) 
       mask[0][27 * k + i] = a0[i];
       mask[1][27 * k + i] = m.gender[kids[k]] == 1 ? xm0[i] : xf0[i];
     }
-  const int f = variant & 3;
-  const bool want_dnm = form & 1, want_joint = form & 2;
-  EmitOptions eo = emit_options(f, "pg", site_prior);
-  LaneShell d;
-  // (from forty members on the likelihoods are read from the lane's row at each use, as variant 8+ of famseq_elim does when asked:
-  // 3 N doubles of registers are the widest pedigrees' wall)
-  d.lean = eo.lean = m.n_members >= 40;
-  d.entry = "famseq_trio";
-  d.comment = describe("trio posteriors (" + std::string(want_dnm && want_joint ? "de novo + joint" : (want_dnm ? "de novo" : "joint")) + ")", g,
-                       std::to_string(f), site_prior);
   d.outputs = "double *__restrict__ joint_g, double *__restrict__ dnm_g";
   d.defines = "#define NKID " + std::to_string(kids.size()) + "\n";
   // (an output this form does not write is a null constant: its stores fold away)
@@ -1501,14 +1562,7 @@ std::string trio_source(const Model &m, int variant, int form, bool site_prior) 
                  (want_dnm ? "    double *dg = dnm_g ? dnm_g + site * NKID : nullptr;\n" : "    double *const dg = nullptr;\n") +
                  "    (void)jg; (void)dg;\n";
   d.body = Emitter(m, g, eo).trio_body(kids, mask, want_joint);
-  d.epilogue =
-      "    if (single_fail || bn_fail) {\n"
-      "      if (dg) {\n#pragma unroll 1\n        for (int k = 0; k < NKID; ++k) dg[k] = kNaN;\n      }\n"
-      "      if (jg) {\n#pragma unroll 1\n        for (int k = 0; k < 27 * NKID; ++k) jg[k] = kNaN;\n      }\n"
-      "    }\n"
-      "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
-  d.bt = elim_block_threads(m, false);
-  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  d.epilogue = fail_block(fill("dg", "NKID") + fill("jg", "27 * NKID")) + status_store();
   return lane_shell(m, d);
 }
 
@@ -1517,14 +1571,8 @@ std::string trio_source(const Model &m, int variant, int form, bool site_prior) 
 // workgroup's BT consecutive sites are staged in LDS (BT * N bytes) and written out together, a wave's stores contiguous —
 // in 32-bit words where the block's first byte is 4-aligned, in bytes otherwise.
 std::string map_source(const Model &m, int variant, bool site_prior) {
-  const Graph g = graph_or_throw(m);
-  if (variant < 0 || variant >= kMapVariants) throw std::runtime_error("map_source: variant must be 0.." + std::to_string(kMapVariants - 1));
-  const int f = variant, N = m.n_members, nw = (N + 3) / 4;
-  EmitOptions eo = emit_options(f, "pg", site_prior);
-  LaneShell d;
-  d.lean = eo.lean = N >= 40;  // as trio_source
-  d.entry = "famseq_map";
-  d.comment = describe("joint MAP configuration (max-product)", g, std::to_string(f), site_prior);
+  auto [g, f, eo, d] = begin_side(m, "map", "joint MAP configuration (max-product)", variant, kMapVariants, site_prior);
+  const int N = m.n_members, nw = (N + 3) / 4;
   d.outputs = "signed char *__restrict__ gt_g, double *__restrict__ post_g";
   d.defines = "#define NMEM " + std::to_string(N) + "\n";
   d.shared = "  __shared__ unsigned s_gt[(BT * NMEM + 3) / 4];  // the workgroup's genotype rows, as they lie in map_gt\n"
@@ -1541,7 +1589,7 @@ std::string map_source(const Model &m, int variant, bool site_prior) {
   for (int k = 0; k < nw; ++k) end << " gw" << k << " = 0xffffffffu;";
   end << "\n    }\n"
       << "    if (post_g) __builtin_nontemporal_store(map_p, post_g + site);\n"
-      << "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n"
+      << status_store()
       << "    if (gt_g) {\n";
   if (N % 4 == 0)
     for (int k = 0; k < nw; ++k) end << "      s_gt[tid * " << nw << " + " << k << "] = gw" << k << ";\n";
@@ -1560,8 +1608,6 @@ std::string map_source(const Model &m, int variant, bool site_prior) {
       << "      LDS_BARRIER();\n"
       << "    }\n";
   d.epilogue = end.str();
-  d.bt = elim_block_threads(m, false);
-  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
   return lane_shell(m, d);
 }
 
@@ -1569,15 +1615,7 @@ std::string map_source(const Model &m, int variant, bool site_prior) {
 // (the total weight without the reference's 1e7), pref = the posterior probability that every member is hom-ref, status; any
 // may be null.  A total weight that is not a positive finite number fails the site (status 2); a hom-ref weight of 0 does not.
 std::string evidence_source(const Model &m, int variant, bool site_prior) {
-  const Graph g = graph_or_throw(m);
-  if (variant < 0 || variant >= kEvidenceVariants)
-    throw std::runtime_error("evidence_source: variant must be 0.." + std::to_string(kEvidenceVariants - 1));
-  const int f = variant;
-  EmitOptions eo = emit_options(f, "pg", site_prior);
-  LaneShell d;
-  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
-  d.entry = "famseq_evidence";
-  d.comment = describe("evidence and hom-ref posterior (sum pass)", g, std::to_string(f), site_prior);
+  auto [g, f, eo, d] = begin_side(m, "evidence", "evidence and hom-ref posterior (sum pass)", variant, kEvidenceVariants, site_prior);
   d.outputs = "double *__restrict__ loglik_g, double *__restrict__ pref_g";
   d.site_vars = "    double ev_ll = kNaN, ev_p0 = kNaN;\n";
   Emitter e(m, g, eo);
@@ -1585,10 +1623,7 @@ std::string evidence_source(const Model &m, int variant, bool site_prior) {
            "      if (!(Z_ > 0 && Z_ <= 1.79769313486231570815e308)) bn_fail = true;\n"
            "      else { ev_ll = log10(Z_) - " + std::to_string(e.evidence_scale_digits()) + ".0; ev_p0 = W0_ / Z_; }\n";
   d.epilogue = "    if (loglik_g) __builtin_nontemporal_store(ev_ll, loglik_g + site);\n"
-               "    if (pref_g) __builtin_nontemporal_store(ev_p0, pref_g + site);\n"
-               "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
-  d.bt = elim_block_threads(m, false);
-  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+               "    if (pref_g) __builtin_nontemporal_store(ev_p0, pref_g + site);\n" + status_store();
   return lane_shell(m, d);
 }
 
@@ -1597,32 +1632,18 @@ std::string evidence_source(const Model &m, int variant, bool site_prior) {
 // null output's stores fold away).  Stored straight from the lane, as famseq_elim's variants 8..11 store post.  A cavity row
 // whose sum is not a positive finite number fails the site (status 2); a total weight of 0 does not: every fit is 0.0 then.
 std::string loo_source(const Model &m, int variant, bool site_prior) {
-  const Graph g = graph_or_throw(m);
-  if (variant < 0 || variant >= kLooVariants) throw std::runtime_error("loo_source: variant must be 0.." + std::to_string(kLooVariants - 1));
-  const int f = variant;
-  EmitOptions eo = emit_options(f, "pg", site_prior);
-  LaneShell d;
-  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
-  d.entry = "famseq_loo";
-  d.comment = describe("leave-one-out posteriors and fit", g, std::to_string(f), site_prior);
+  auto [g, f, eo, d] = begin_side(m, "loo", "leave-one-out posteriors and fit", variant, kLooVariants, site_prior);
   d.outputs = "double *__restrict__ loo_g, double *__restrict__ fit_g";
   d.defines = "#define NMEM " + std::to_string(m.n_members) + "\n";
   d.site_decls = "    double *og = loo_g ? loo_g + site * W3 : nullptr;\n"
                  "    double *fg = fit_g ? fit_g + site * NMEM : nullptr;\n"
                  "    (void)og; (void)fg;\n";
   d.body = Emitter(m, g, eo).loo_body();
-  d.epilogue =
-      "    if (single_fail || bn_fail) {\n"
-      "      if (og) {\n#pragma unroll 1\n        for (int k = 0; k < W3; ++k) og[k] = kNaN;\n      }\n"
-      "      if (fg) {\n#pragma unroll 1\n        for (int k = 0; k < NMEM; ++k) fg[k] = kNaN;\n      }\n"
-      "    }\n"
-      "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
-  d.bt = elim_block_threads(m, false);
-  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  d.epilogue = fail_block(fill("og", "W3") + fill("fg", "NMEM")) + status_store();
   return lane_shell(m, d);
 }
 
-// The pattern kernel: the evidence kernel's rules and shell.  Beyond the common arguments: mask_g[n_patterns][N] (bit g of an entry
+// The pattern kernel: a per-pass product (PassProduct).  Beyond the common arguments: mask_g[n_patterns][N] (bit g of an entry
 // set: genotype g is allowed to that member) and n_patterns (1 .. FAMSEQ_MAX_PATTERNS; the host checks, the kernel clamps).
 // Outputs per site: ppost[n_patterns], pattern m's posterior Z_m / Z — a true division, so that a pattern that allows everything
 // gives exactly 1.0 — and loglik, famseq_evidence's, from the unmasked pass; either may be null (without ppost only the unmasked
@@ -1632,50 +1653,28 @@ std::string loo_source(const Model &m, int variant, bool site_prior) {
 // Where the likelihoods live: in registers twice under forty members (the real rows and the pass's masked copy, which the
 // compiler is free to form at its use instead), from forty on read from the lane's row at each use, as the evidence kernel does.
 std::string pattern_source(const Model &m, int variant, bool site_prior) {
-  const Graph g = graph_or_throw(m);
-  if (variant < 0 || variant >= kPatternVariants)
-    throw std::runtime_error("pattern_source: variant must be 0.." + std::to_string(kPatternVariants - 1));
-  const int f = variant, N = m.n_members, nmw = (N + 7) / 8;
-  EmitOptions eo = emit_options(f, "pg", site_prior);
-  LaneShell d;
-  d.lean = eo.lean = N >= 40;  // as trio_source
-  d.entry = "famseq_pattern";
-  d.comment = describe("genotype-pattern posteriors (sum pass per pattern)", g, std::to_string(f), site_prior);
+  auto [g, f, eo, d] = begin_side(m, "pattern", "genotype-pattern posteriors (sum pass per pattern)", variant, kPatternVariants, site_prior);
+  const int N = m.n_members, nmw = (N + 7) / 8;
   d.outputs = "double *__restrict__ ppost_g, double *__restrict__ loglik_g";
   d.more_args = ", const unsigned char *__restrict__ mask_g, int n_patterns";
   d.defines = "#define NMEM " + std::to_string(N) + "\n#define NMW " + std::to_string(nmw) + "\n#define MAXPAT " +
               std::to_string(FAMSEQ_MAX_PATTERNS) + "\n";
   d.shared = "  __shared__ unsigned s_mw[(MAXPAT + 1) * NMW];  // the passes' masks: four bits per member, row 0 (the unmasked pass) all ones\n";
-  d.prologue =
-      "  const int np_ = n_patterns < 0 ? 0 : (n_patterns > MAXPAT ? MAXPAT : n_patterns);\n"
+  const PassProduct pass{"ppost_g", "pp", "n_patterns", "np_", "MAXPAT", "pt_", "pt_ll", "Zp_ / Z0_", /*z0=*/true};
+  Emitter e(m, g, eo);
+  const std::string per_pass = pass_product(pass, e.evidence_scale_digits(), d);
+  d.prologue +=
       "  for (int i = tid; i < (np_ + 1) * NMW; i += BT) {\n"
       "    const int pt = i / NMW, w = i - pt * NMW;\n"
       "    unsigned v = 0;\n"
       "    for (int j = 0; j < 8 && 8 * w + j < NMEM; ++j) v |= (pt ? (unsigned)mask_g[(pt - 1) * NMEM + 8 * w + j] & 7u : 7u) << (4 * j);\n"
       "    s_mw[i] = v;\n"
       "  }\n";
-  d.site_decls = "    double *pp = ppost_g ? ppost_g + site * np_ : nullptr;\n"
-                 "    const int last_ = pp ? np_ : 0;\n";
-  d.site_vars = "    double pt_ll = kNaN, Z0_ = 0;\n";
-  Emitter e(m, g, eo);
-  d.body = e.pattern_body(
-      "      if (pt_ == 0) {\n"
-      "        if (!(Zp_ > 0 && Zp_ <= 1.79769313486231570815e308)) { bn_fail = true; break; }\n"
-      "        Z0_ = Zp_; pt_ll = log10(Zp_) - " + std::to_string(e.evidence_scale_digits()) + ".0;\n"
-      "      } else {\n"
-      "        __builtin_nontemporal_store(Zp_ / Z0_, pp + (pt_ - 1));\n"
-      "      }\n");
-  d.epilogue = "    if (single_fail || bn_fail) {\n      pt_ll = kNaN;\n"
-               "      if (pp) {\n#pragma unroll 1\n        for (int k = 0; k < np_; ++k) pp[k] = kNaN;\n      }\n"
-               "    }\n"
-               "    if (loglik_g) __builtin_nontemporal_store(pt_ll, loglik_g + site);\n"
-               "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
-  d.bt = elim_block_threads(m, false);
-  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  d.body = e.pattern_body(pass.counter, per_pass);
   return lane_shell(m, d);
 }
 
-// The relabelling kernel: the evidence kernel's rules and shell.  Beyond the common arguments: assign_g[n_assign][N] (int32: which
+// The relabelling kernel: a per-pass product (PassProduct).  Beyond the common arguments: assign_g[n_assign][N] (int32: which
 // member's row member p is given; -1 "no data", and every other entry outside 0 .. N-1 is taken as -1, so nothing outside the
 // site's row is ever read) and n_assign (1 .. FAMSEQ_MAX_RELABEL; the host checks, the kernel clamps).  Outputs per site:
 // alt[n_assign], log10 Z_a without the reference's 1e7 — not clamped; -inf where Z_a is exactly 0, which is a result — and loglik,
@@ -1690,108 +1689,60 @@ std::string pattern_source(const Model &m, int variant, bool site_prior) {
 // (eo.lean, from forty on) and keeps its local factors in variables.  tests/test_edge_pedigrees.py pins the three from the
 // emitted text (edge37, edge38 / edge39, edge40 of famseq_amd/prebuild_sets.py), tests/test_gpu_edge_pedigrees.py runs them.
 std::string relabel_source(const Model &m, int variant, bool site_prior) {
-  const Graph g = graph_or_throw(m);
-  if (variant < 0 || variant >= kRelabelVariants)
-    throw std::runtime_error("relabel_source: variant must be 0.." + std::to_string(kRelabelVariants - 1));
-  const int f = variant, N = m.n_members, bits = N < 255 ? 8 : 16, naw = (N + 32 / bits - 1) / (32 / bits);
-  LaneShell d;
-  d.bt = elim_block_threads(m, false);
+  auto [g, f, eo, d] = begin_side(m, "relabel", "relabelling evidence (sum pass per assignment)", variant, kRelabelVariants, site_prior);
+  const int N = m.n_members, bits = N < 255 ? 8 : 16, per = 32 / bits, naw = (N + per - 1) / per;
   const size_t lds_bytes = size_t(d.bt) * ((3 * (N + 1)) | 1) * sizeof(double) + 432 * sizeof(double) +
                            size_t(FAMSEQ_MAX_RELABEL + 1) * naw * sizeof(unsigned);
   const bool lds_rows = N < 40 && lds_bytes <= (size_t(64) << 10) && env_int("FAMSEQ_RELABEL_LEAN", 0) == 0;
-  EmitOptions eo = emit_options(f, "pg", site_prior);
-  eo.lean = N >= 40;  // as trio_source
-  d.lean = !lds_rows;
+  d.lean = !lds_rows;  // (the shell's rows: the three forms above; the emitter stays lean from forty on)
   if (lds_rows) d.lds_from = 0, d.lds_extra = 3;
-  d.entry = "famseq_relabel";
-  d.comment = describe("relabelling evidence (sum pass per assignment)", g, std::to_string(f), site_prior);
   d.outputs = "double *__restrict__ alt_g, double *__restrict__ loglik_g";
   d.more_args = ", const int *__restrict__ assign_g, int n_assign";
   d.defines = "#define NMEM " + std::to_string(N) + "\n#define NAW " + std::to_string(naw) + "\n#define MAXREL " +
               std::to_string(FAMSEQ_MAX_RELABEL) + "\n";
   d.shared = "  __shared__ unsigned s_aw[(MAXREL + 1) * NAW];  // the passes' assignments: " + std::to_string(bits) +
              " bits per member, row 0 (the identity pass) 0 .. N-1, NMEM for \"no data\"\n";
-  d.prologue =
-      "  const int na_ = n_assign < 0 ? 0 : (n_assign > MAXREL ? MAXREL : n_assign);\n"
+  const PassProduct pass{"alt_g", "ap", "n_assign", "na_", "MAXREL", "ps_", "rl_ll"};
+  Emitter e(m, g, eo);
+  const std::string per_pass = pass_product(pass, e.evidence_scale_digits(), d);
+  d.prologue +=
       "  for (int i = tid; i < (na_ + 1) * NAW; i += BT) {\n"
       "    const int ps = i / NAW, w = i - ps * NAW;\n"
       "    unsigned v = 0;\n"
-      "    for (int j = 0; j < " + std::to_string(32 / bits) + " && " + std::to_string(32 / bits) + " * w + j < NMEM; ++j) {\n"
-      "      const int p = " + std::to_string(32 / bits) + " * w + j;\n"
+      "    for (int j = 0; j < " + std::to_string(per) + " && " + std::to_string(per) + " * w + j < NMEM; ++j) {\n"
+      "      const int p = " + std::to_string(per) + " * w + j;\n"
       "      const int a = ps ? assign_g[(ps - 1) * NMEM + p] : p;\n"
       "      v |= (a >= 0 && a < NMEM ? (unsigned)a : (unsigned)NMEM) << (" + std::to_string(bits) + " * j);\n"
       "    }\n"
       "    s_aw[i] = v;\n"
       "  }\n";
-  d.site_decls = "    double *ap = alt_g ? alt_g + site * na_ : nullptr;\n"
-                 "    const int last_ = ap ? na_ : 0;\n";
-  d.site_vars = "    double rl_ll = kNaN;\n";
   if (lds_rows) d.site_vars += "    lw[" + std::to_string(3 * N) + "] = 1.0; lw[" + std::to_string(3 * N + 1) + "] = 1.0; lw[" + std::to_string(3 * N + 2) + "] = 1.0;\n";
-  Emitter e(m, g, eo);
-  const std::string digits = std::to_string(e.evidence_scale_digits()) + ".0";
-  d.body = e.relabel_body(
-      "      if (ps_ == 0) {\n"
-      "        if (!(Zp_ > 0 && Zp_ <= 1.79769313486231570815e308)) { bn_fail = true; break; }\n"
-      "        rl_ll = log10(Zp_) - " + digits + ";\n"
-      "      } else {\n"
-      "        __builtin_nontemporal_store(log10(Zp_) - " + digits + ", ap + (ps_ - 1));\n"
-      "      }\n",
-      lds_rows, bits);
-  d.epilogue = "    if (single_fail || bn_fail) {\n      rl_ll = kNaN;\n"
-               "      if (ap) {\n#pragma unroll 1\n        for (int k = 0; k < na_; ++k) ap[k] = kNaN;\n      }\n"
-               "    }\n"
-               "    if (loglik_g) __builtin_nontemporal_store(rl_ll, loglik_g + site);\n"
-               "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
-  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  d.body = e.relabel_body(pass.counter, per_pass, lds_rows, bits);
   return lane_shell(m, d);
 }
 
-// The mutation-rate kernel: the evidence kernel's rules and shell, and its LDS (the factor tables alone: a pass's table is read
-// where it lies).  Beyond the common arguments: rt_g[n_rates][432], one factor table per rate, of which only the transmission
+// The mutation-rate kernel: a per-pass product (PassProduct), with the evidence kernel's LDS (the factor tables alone: a pass's
+// table is read where it lies).  Beyond the common arguments: rt_g[n_rates][432], one factor table per rate, of which only the transmission
 // entries are read (whatever they hold: nothing is indexed by them), and n_rates (1 .. FAMSEQ_MAX_RATES; the host checks, the
 // kernel clamps).  Outputs per site: rate_ll[n_rates], log10 Z_r without the reference's 1e7 — not clamped; -inf where Z_r is
 // exactly 0 (rate 0 on a Mendel-impossible row), which is a result — and loglik, famseq_evidence's, from the pass on the
 // context's own table; either may be null (without rate_ll only that pass runs).  Only the context's own Z that is not a
 // positive finite number fails the site (status 2).  The rows stay where famseq_evidence has them: registers, lean from forty.
 std::string mutrate_source(const Model &m, int variant, bool site_prior) {
-  const Graph g = graph_or_throw(m);
-  if (variant < 0 || variant >= kMutrateVariants)
-    throw std::runtime_error("mutrate_source: variant must be 0.." + std::to_string(kMutrateVariants - 1));
-  const int f = variant;
-  EmitOptions eo = emit_options(f, "pg", site_prior);
+  auto [g, f, eo, d] = begin_side(m, "mutrate", "mutation-rate likelihood profile (sum pass per rate)", variant, kMutrateVariants, site_prior);
   eo.t_from = "trt";
-  LaneShell d;
-  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
-  d.entry = "famseq_mutrate";
-  d.comment = describe("mutation-rate likelihood profile (sum pass per rate)", g, std::to_string(f), site_prior);
+  d.chrx_loop = true;  // (variant 0 too: mutrate_body)
   d.outputs = "double *__restrict__ rate_ll_g, double *__restrict__ loglik_g";
   d.more_args = ", const double *__restrict__ rt_g, int n_rates";
   d.defines = "#define MAXRATES " + std::to_string(FAMSEQ_MAX_RATES) + "\n#define RTD " + std::to_string(FAMSEQ_RATE_TABLE_DOUBLES) + "\n";
-  d.prologue = "  const int nr_ = n_rates < 0 ? 0 : (n_rates > MAXRATES ? MAXRATES : n_rates);\n";
-  d.site_decls = "    double *rp = rate_ll_g ? rate_ll_g + site * nr_ : nullptr;\n"
-                 "    const int last_ = rp ? nr_ : 0;\n";
-  d.site_vars = "    double mr_ll = kNaN;\n";
+  const PassProduct pass{"rate_ll_g", "rp", "n_rates", "nr_", "MAXRATES", "ps_", "mr_ll"};
   Emitter e(m, g, eo);
-  const std::string digits = std::to_string(e.evidence_scale_digits()) + ".0";
-  d.body = e.mutrate_body(
-      "      if (ps_ == 0) {\n"
-      "        if (!(Zp_ > 0 && Zp_ <= 1.79769313486231570815e308)) { bn_fail = true; break; }\n"
-      "        mr_ll = log10(Zp_) - " + digits + ";\n"
-      "      } else {\n"
-      "        __builtin_nontemporal_store(log10(Zp_) - " + digits + ", rp + (ps_ - 1));\n"
-      "      }\n");
-  d.epilogue = "    if (single_fail || bn_fail) {\n      mr_ll = kNaN;\n"
-               "      if (rp) {\n#pragma unroll 1\n        for (int k = 0; k < nr_; ++k) rp[k] = kNaN;\n      }\n"
-               "    }\n"
-               "    if (loglik_g) __builtin_nontemporal_store(mr_ll, loglik_g + site);\n"
-               "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
-  d.bt = elim_block_threads(m, false);
-  d.fence_single = f >= 3, d.chrx_loop = true, d.site_prior = site_prior;  // (variant 0 too: mutrate_body)
+  d.body = e.mutrate_body(pass.counter, pass_product(pass, e.evidence_scale_digits(), d));
   return lane_shell(m, d);
 }
 
-// The weight kernel: the evidence kernel's rules and shell, and its LDS (the factor tables alone: a pass's weights are read where
-// they lie).  Beyond the common arguments: wt_g[n_weights][N][3], one table of per-member genotype weights per pass (whatever
+// The weight kernel: a per-pass product (PassProduct), with the evidence kernel's LDS (the factor tables alone: a pass's
+// weights are read where they lie).  Beyond the common arguments: wt_g[n_weights][N][3], one table of per-member genotype weights per pass (whatever
 // they hold: nothing is indexed by them; the host entries admit finite numbers >= 0, above 1 included), and n_weights
 // (1 .. FAMSEQ_MAX_WEIGHTS; the host checks, the kernel clamps).  Outputs per site: wt_ll[n_weights], log10 Z_m without the
 // reference's 1e7, Z_m the network's total weight on the rows lk * w_m — not clamped; -inf where Z_m is exactly 0 and +inf where
@@ -1800,38 +1751,13 @@ std::string mutrate_source(const Model &m, int variant, bool site_prior) {
 // the site (status 2).  The rows stay where famseq_evidence has them: registers (twice, as famseq_pattern: the real rows and
 // the pass's weighted copy, which the compiler is free to form at its use instead), lean from forty.
 std::string weight_source(const Model &m, int variant, bool site_prior) {
-  const Graph g = graph_or_throw(m);
-  if (variant < 0 || variant >= kWeightVariants)
-    throw std::runtime_error("weight_source: variant must be 0.." + std::to_string(kWeightVariants - 1));
-  const int f = variant;
-  EmitOptions eo = emit_options(f, "pg", site_prior);
-  LaneShell d;
-  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
-  d.entry = "famseq_weight";
-  d.comment = describe("per-member genotype weights (sum pass per weight table)", g, std::to_string(f), site_prior);
+  auto [g, f, eo, d] = begin_side(m, "weight", "per-member genotype weights (sum pass per weight table)", variant, kWeightVariants, site_prior);
   d.outputs = "double *__restrict__ wt_ll_g, double *__restrict__ loglik_g";
   d.more_args = ", const double *__restrict__ wt_g, int n_weights";
   d.defines = "#define MAXWT " + std::to_string(FAMSEQ_MAX_WEIGHTS) + "\n";
-  d.prologue = "  const int nw_ = n_weights < 0 ? 0 : (n_weights > MAXWT ? MAXWT : n_weights);\n";
-  d.site_decls = "    double *wp = wt_ll_g ? wt_ll_g + site * nw_ : nullptr;\n"
-                 "    const int last_ = wp ? nw_ : 0;\n";
-  d.site_vars = "    double wt_l0 = kNaN;\n";
+  const PassProduct pass{"wt_ll_g", "wp", "n_weights", "nw_", "MAXWT", "ps_", "wt_l0"};
   Emitter e(m, g, eo);
-  const std::string digits = std::to_string(e.evidence_scale_digits()) + ".0";
-  d.body = e.weight_body(
-      "      if (ps_ == 0) {\n"
-      "        if (!(Zp_ > 0 && Zp_ <= 1.79769313486231570815e308)) { bn_fail = true; break; }\n"
-      "        wt_l0 = log10(Zp_) - " + digits + ";\n"
-      "      } else {\n"
-      "        __builtin_nontemporal_store(log10(Zp_) - " + digits + ", wp + (ps_ - 1));\n"
-      "      }\n");
-  d.epilogue = "    if (single_fail || bn_fail) {\n      wt_l0 = kNaN;\n"
-               "      if (wp) {\n#pragma unroll 1\n        for (int k = 0; k < nw_; ++k) wp[k] = kNaN;\n      }\n"
-               "    }\n"
-               "    if (loglik_g) __builtin_nontemporal_store(wt_l0, loglik_g + site);\n"
-               "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
-  d.bt = elim_block_threads(m, false);
-  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  d.body = e.weight_body(pass.counter, pass_product(pass, e.evidence_scale_digits(), d));
   return lane_shell(m, d);
 }
 
@@ -1855,16 +1781,9 @@ void build_allele_tables(double mu, double *t) {
 // either may be null: its stores are skipped), status.  Every variant takes the chrX loop, the fence-free one too (as
 // famseq_mutrate does): the allele rows are read through the pass's wave-uniform pointer alx and cost no vector register.
 std::string origin_source(const Model &m, int variant, bool site_prior) {
-  const Graph g = graph_or_throw(m);
-  if (variant < 0 || variant >= kOriginVariants)
-    throw std::runtime_error("origin_source: variant must be 0.." + std::to_string(kOriginVariants - 1));
-  const int f = variant;
+  auto [g, f, eo, d] = begin_side(m, "origin", "phase by transmission (parental origin per child)", variant, kOriginVariants, site_prior);
+  d.chrx_loop = true;  // (variant 0 too: alx, above)
   const std::vector<int> kids = trio_children(m);
-  EmitOptions eo = emit_options(f, "pg", site_prior);
-  LaneShell d;
-  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
-  d.entry = "famseq_origin";
-  d.comment = describe("phase by transmission (parental origin per child)", g, std::to_string(f), site_prior);
   d.outputs = "double *__restrict__ origin_g, double *__restrict__ hettx_g";
   d.more_args = ", const double *__restrict__ al_g";
   d.defines = "#define NKID " + std::to_string(kids.size()) + "\n";
@@ -1872,14 +1791,7 @@ std::string origin_source(const Model &m, int variant, bool site_prior) {
                  "    double *hg = hettx_g ? hettx_g + site * (4 * NKID) : nullptr;\n"
                  "    (void)og; (void)hg;\n";
   d.body = Emitter(m, g, eo).origin_body(kids);
-  d.epilogue =
-      "    if (single_fail || bn_fail) {\n"
-      "      if (og) {\n#pragma unroll 1\n        for (int k = 0; k < 4 * NKID; ++k) og[k] = kNaN;\n      }\n"
-      "      if (hg) {\n#pragma unroll 1\n        for (int k = 0; k < 4 * NKID; ++k) hg[k] = kNaN;\n      }\n"
-      "    }\n"
-      "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
-  d.bt = elim_block_threads(m, false);
-  d.fence_single = f >= 3, d.chrx_loop = true, d.site_prior = site_prior;
+  d.epilogue = fail_block(fill("og", "4 * NKID") + fill("hg", "4 * NKID")) + status_store();
   return lane_shell(m, d);
 }
 
@@ -1890,22 +1802,18 @@ std::string origin_source(const Model &m, int variant, bool site_prior) {
 // rule under the start value's rows; 2: a start value outside [0, 1] (whatever the rows it gives say), a pass's total weight or a
 // founder's row sum that is not a positive finite number.  Per-pass state: q, Z(q) and Z(0), three doubles in registers.
 std::string af_source(const Model &m, int variant) {
-  const Graph g = graph_or_throw(m);
-  if (variant < 0 || variant >= kAfVariants) throw std::runtime_error("af_source: variant must be 0.." + std::to_string(kAfVariants - 1));
-  const int f = variant;
-  EmitOptions eo = emit_options(f, "pg", /*site_prior=*/true);
-  LaneShell d;
-  d.lean = eo.lean = m.n_members >= 40;  // as trio_source
-  d.entry = "famseq_af";
-  d.comment = describe("founder allele frequency by maximum likelihood (EM, a sum pass per step)", g, std::to_string(f), false) +
-              "\n// One step from q: the founders' rows are ((1-q)^2, 2q(1-q), q^2) and, male founders at a chrX site, (1-q, 0, q); with m_f the"
-              "\n// marginal of founder f under them, q' = min(sum_f count_f / C, 1), count_f = (m_f1 + 2 m_f2) / (m_f0 + m_f1 + m_f2) (a male"
-              "\n// founder at a chrX site: m_f2 / (m_f0 + m_f1 + m_f2)), C = 2 founders (chrX: 2 female founders + male founders), founders in"
-              "\n// PED order.  n_iter steps from af0, no early exit: the result is a function of the inputs alone.";
+  auto [g, f, eo, d] = begin_side(m, "af", "founder allele frequency by maximum likelihood (EM, a sum pass per step)", variant, kAfVariants, false);
+  // the founders' prior is the kernel's own: the emitter reads the lane's pa_<g> / pm_<g> as with site priors, the shell has no
+  // prior_g to read
+  eo.site_prior = true, d.own_prior = true;
+  d.comment += "\n// One step from q: the founders' rows are ((1-q)^2, 2q(1-q), q^2) and, male founders at a chrX site, (1-q, 0, q); with m_f the"
+               "\n// marginal of founder f under them, q' = min(sum_f count_f / C, 1), count_f = (m_f1 + 2 m_f2) / (m_f0 + m_f1 + m_f2) (a male"
+               "\n// founder at a chrX site: m_f2 / (m_f0 + m_f1 + m_f2)), C = 2 founders (chrX: 2 female founders + male founders), founders in"
+               "\n// PED order.  n_iter steps from af0, no early exit: the result is a function of the inputs alone.";
   d.outputs = "double *__restrict__ af_g, double *__restrict__ loglik_g";
   d.more_args = ", const double *__restrict__ af0_g, int n_iter";
   d.defines = "#define MAXIT " + std::to_string(FAMSEQ_MAX_AF_ITER) + "\n";
-  d.prologue = "  const int n_it_ = n_iter < 0 ? 0 : (n_iter > MAXIT ? MAXIT : n_iter);\n";
+  d.prologue = clamp_count("n_it_", "n_iter", "MAXIT");
   // the start value's rows, for the single posterior's rule (famseq_hwe_priors' expressions; a pass forms its own the same way)
   d.site_vars =
       "    double af_q = kNaN, af_l0 = kNaN, af_l1 = kNaN;\n"
@@ -1927,8 +1835,6 @@ std::string af_source(const Model &m, int variant) {
                "      __builtin_nontemporal_store(af_l1, loglik_g + 2 * site + 1);\n"
                "    }\n"
                "    if (status_g) status_g[site] = af_bad ? 2 : (single_fail ? 1 : (bn_fail ? 2 : 0));\n";
-  d.bt = elim_block_threads(m, false);
-  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.own_prior = true;
   return lane_shell(m, d);
 }
 
@@ -1973,36 +1879,27 @@ static __device__ __forceinline__ unsigned fs_pick9(double u, const double *e) {
 // per lane do not fit a stage in LDS beside the messages — in 32-bit words where a row starts 4-aligned, in bytes otherwise:
 // every store lies inside the site's n_draws * N bytes whatever the alignment of samp_gt.
 std::string sample_source(const Model &m, int variant, bool site_prior) {
-  const Graph g = graph_or_throw(m);
-  if (variant < 0 || variant >= kSampleVariants)
-    throw std::runtime_error("sample_source: variant must be 0.." + std::to_string(kSampleVariants - 1));
-  const int f = variant, N = m.n_members;
-  EmitOptions eo = emit_options(f, "pg", site_prior);
-  LaneShell d;
-  d.lean = eo.lean = N >= 40;  // as trio_source
-  d.bt = elim_block_threads(m, false);
+  auto [g, f, eo, d] = begin_side(m, "sample", "exact joint posterior draws (forward filtering, backward sampling)", variant, kSampleVariants, site_prior);
+  const int N = m.n_members;
   Emitter e(m, g, eo);
   d.body = e.sample_body();
   const int vp = e.sample_row_doubles() | 1, D = e.sample_decisions();
   // (the factor tables, the rows and what the compiler keeps for itself within the CU's 160 KB)
   if (size_t(d.bt) * vp * sizeof(double) > size_t(150) << 10)
     throw std::runtime_error("sample_source: the messages of " + std::to_string(N) + " members do not fit the lanes' LDS rows");
-  d.entry = "famseq_sample";
-  d.comment = describe("exact joint posterior draws (forward filtering, backward sampling)", g, std::to_string(f), site_prior) +
-              "\n// Random numbers: Philox4x32-10, key (seed, seed >> 32), counter (i, i >> 32, draw, block), i the site's absolute index."
-              "\n// Word w of a draw is element w % 4 of block w / 4; u = (word + 0.5) 2^-32 (one decision resolves 2^-32 of probability)."
-              "\n// Decision d of a draw takes word d, d counting in the order the walk is written below: the root of every component, then the"
-              "\n// families in reverse message order, in each the other parent or the parent pair, then its remaining children: D = " +
-              std::to_string(D) + " words." +
-              (g.cut.empty() ? "" : "\n// Assignment as_ of the conditioned members takes word D + as_ for its selection.");
+  d.comment += "\n// Random numbers: Philox4x32-10, key (seed, seed >> 32), counter (i, i >> 32, draw, block), i the site's absolute index."
+               "\n// Word w of a draw is element w % 4 of block w / 4; u = (word + 0.5) 2^-32 (one decision resolves 2^-32 of probability)."
+               "\n// Decision d of a draw takes word d, d counting in the order the walk is written below: the root of every component, then the"
+               "\n// families in reverse message order, in each the other parent or the parent pair, then its remaining children: D = " +
+               std::to_string(D) + " words." +
+               (g.cut.empty() ? "" : "\n// Assignment as_ of the conditioned members takes word D + as_ for its selection.");
   d.outputs = "signed char *__restrict__ gt_g, double *__restrict__ post_g";
   d.more_args = ", unsigned long seed, long site_base, int n_draws";
   d.defines = "#define NMEM " + std::to_string(N) + "\n#define MAXDRAW " + std::to_string(FAMSEQ_MAX_DRAWS) + "\n#define VP " + std::to_string(vp) +
               "\n#define FS_PHILOX_FN static __device__ __forceinline__\n" + kPhiloxText + "\n" + kSampleHelpers;
   d.shared = "  __shared__ double s_v[BT * VP];  // the member -> family messages of the collect pass, one padded row per lane\n";
   d.prologue = std::string() +
-               "  const unsigned key0_ = (unsigned)seed, key1_ = (unsigned)(seed >> 32);\n"
-               "  const int nd_ = n_draws < 0 ? 0 : (n_draws > MAXDRAW ? MAXDRAW : n_draws);\n"
+               "  const unsigned key0_ = (unsigned)seed, key1_ = (unsigned)(seed >> 32);\n" + clamp_count("nd_", "n_draws", "MAXDRAW") +
                "  double *const sw = s_v + tid * VP;\n" +
                // Read through a plain pointer.  Under forty members hipcc then turns a read at a genotype of 0..2 into three reads and
                // a select, forwards the stores, and keeps the messages in registers (the row takes no LDS at all); from forty on,
@@ -2017,50 +1914,43 @@ std::string sample_source(const Model &m, int variant, bool site_prior) {
                  "    double *sp_ = post_g ? post_g + site * nd_ : nullptr;\n"
                  "    const unsigned long ai_ = (unsigned long)(site_base + site);\n"
                  "    const unsigned ilo_ = (unsigned)ai_, ihi_ = (unsigned)(ai_ >> 32);\n";
-  d.epilogue =
-      "    if (single_fail || bn_fail) {\n"
-      "      if (gg) {\n#pragma unroll 1\n        for (int k = 0; k < nd_ * NMEM; ++k) gg[k] = (signed char)-1;\n      }\n"
-      "      if (sp_) {\n#pragma unroll 1\n        for (int k = 0; k < nd_; ++k) sp_[k] = kNaN;\n      }\n"
-      "    }\n"
-      "    if (status_g) status_g[site] = single_fail ? 1 : (bn_fail ? 2 : 0);\n";
-  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
+  d.epilogue = fail_block(fill("gg", "nd_ * NMEM", "(signed char)-1") + fill("sp_", "nd_")) + status_store();
   return lane_shell(m, d);
 }
 
 namespace {
 
 // famseq_elim's variants 8..11 (the widest pedigrees): lane_shell's form of it, famseq_elim's rules
-std::string direct_source(const Model &m, const Graph &g, int variant, bool site_prior) {
-  const int f = variant & 3, N = m.n_members;
-  EmitOptions eo = emit_options(f, "pg", site_prior);
-  LaneShell d;
+std::string direct_source(const Model &m, int variant, bool site_prior) {
+  // (the fence level is the variant's low two bits: every value is taken)
+  auto [g, f, eo, d] = begin_side(m, "elim", "exact sum-product", variant & 3, 4, site_prior);
+  const int N = m.n_members;
+  // (the comment names the kernel's variant, 8..11, and its form)
+  d.comment = describe("exact sum-product", g, std::to_string(variant) + " (rows straight from and to global memory)", site_prior);
+  // where the likelihoods live is this kernel's own rule: registers at every size unless asked, LDS rows for the last members
   d.lean = eo.lean = env_int("FAMSEQ_ELIM_LEAN", 0) != 0;  // tuning aid
   // members whose likelihoods live in the lane's LDS row rather than in registers: at four waves per CU a lane has 73 doubles
   // of LDS, 24 members.  Pays from the mid-fifties on, where the scratch it spares outweighs the LDS latency it adds (2 M
   // sites: 48 members 2.37-2.50 -> 2.55-2.59 ms, 64: 4.72-4.91 -> 4.25-4.44, 96: 10.3-10.5 -> 9.07; scratch 1276 -> 956 B at 64)
   const int n_lds = std::max(0, std::min(env_int("FAMSEQ_ELIM_LDSL", N >= 56 ? 24 : 0), N));  // (the variable: a tuning aid)
   d.lds_from = eo.lean_from = d.lean ? N : N - n_lds;
-  d.entry = "famseq_elim";
-  d.comment = describe("exact sum-product", g, std::to_string(variant) + " (rows straight from and to global memory)", site_prior);
   d.outputs = "double *__restrict__ post_g, double *__restrict__ single_g";
   d.min_waves = std::max(1, env_int("FAMSEQ_ELIM_MINWAVES", 1));  // tuning aid
   d.shortcut = true;
   d.site_decls = "    double *pg = post_g + site * W3;\n"
                  "    double *row = single_g ? single_g + site * W3 : pg;  // where the single posterior goes\n";
   d.after_single =
-      "    if (single_fail) {\n#pragma unroll 1\n      for (int k = 0; k < W3; ++k) row[k] = kNaN;\n    }\n"
+      fill("row", "W3", "kNaN", "single_fail", 4) +
       // a site that does not take the full computation: its posterior IS the single posterior (family.cpp:793-878) or NaN
-      "    if (single_g && !(full && !single_fail)) {\n#pragma unroll 1\n      for (int k = 0; k < W3; ++k) pg[k] = row[k];\n    }\n";
-  d.body = Emitter(m, g, eo).body() + "      if (bn_fail) {\n#pragma unroll 1\n        for (int k = 0; k < W3; ++k) pg[k] = kNaN;\n      }\n";
+      fill("pg", "W3", "row[k]", "single_g && !(full && !single_fail)", 4);
+  d.body = Emitter(m, g, eo).body() + fill("pg", "W3", "kNaN", "bn_fail");
   d.epilogue = "    if (status_g) status_g[site] = single_fail ? 1 : (!full ? 0x80 : (bn_fail ? 2 : 0));\n";
-  d.bt = elim_block_threads(m, false);
-  d.fence_single = f >= 3, d.chrx_loop = f >= 1, d.site_prior = site_prior;
   return lane_shell(m, d);
 }
 
 std::string sum_product_source(const Model &m, int variant, bool call_mode, bool site_prior) {
+  if (variant >= 8 && !call_mode) return direct_source(m, variant, site_prior);  // no LDS staging
   const Graph g = graph_or_throw(m);
-  if (variant >= 8 && !call_mode) return direct_source(m, g, variant, site_prior);  // no LDS staging
   ShellOptions o;
   o.entry = site_prior ? "famseq_elim_prior" : "famseq_elim";
   o.bt = elim_block_threads(m, call_mode);

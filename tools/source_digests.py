@@ -28,7 +28,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import famseq_amd as fs  # noqa: E402
-from famseq_amd.prebuild_sets import random_pedigree, wide_pedigree  # noqa: E402
+from famseq_amd.prebuild_sets import (EDGE_PEDIGREES, SIDE_PRODUCTS, SIDE_PRODUCTS_SINCE, SIDE_VARIANTS, edge_pedigree,  # noqa: E402
+                                      random_pedigree, wide_pedigree)
 
 TWO_CUT_SEED = 99  # the first random_pedigree seed whose loops need exactly two conditioned members (seeds 0..117 searched)
 
@@ -39,6 +40,8 @@ def _named(name):
         return fs.Pedigree(ids, mids, fids, [1, 2, 1, 2, 2, 1, 1, 2, 1], ["s%d" % i for i in ids])
     if name == "lone":  # a trio and a member of no nuclear family (trio_body's lone-founder branch)
         return fs.Pedigree([1, 2, 3, 4], [0, 0, 2, 0], [0, 0, 1, 0], [1, 2, 1, 2], ["s1", "s2", "s3", "s4"])
+    if name in EDGE_PEDIGREES:
+        return edge_pedigree(name)
     if name.startswith("random"):
         return random_pedigree(int(name[6:]))[1]
     if name.startswith("wide"):
@@ -54,6 +57,17 @@ def _named(name):
 # constant: none); for every other pedigree lane/4..7 are recorded as the text of lane/0..3.
 PEDIGREES = ("trio", "quad", "ped5", "ped10", "ped15:12", "cousins", "random15", "random0", "random3", "random%d" % TWO_CUT_SEED,
              "wide24", "wide48", "wide64", "lone", "random34")
+
+# The matrix has two layers, so that a manifest written before the second existed still checks against the first alone.
+# The base layer is the above with SWITCHES: the main engines, the lane kernels, trio and map (digests(name)).  The side layer
+# (digests(name, side=True)) is the base layer plus every other row of side_table() (csrc/kernels.cpp), as (stem, has a site-prior
+# sibling): cases "<stem>/<v>" and "<stem>_prior/<v>", v < SIDE_VARIANTS, SIDE_SWITCHES, and four more pedigrees, edge37 ..
+# edge40 (prebuild_sets.EDGE_PEDIGREES), the side products around their size edges — relabel_source's three forms (LDS rows up to
+# 37 members, global rows under an emitter that is not lean at 38 and 39, both lean from 40) and every side product's switch
+# to the lean form between 39 and 40.  tests/golden/generated_sources.json holds the side layer.
+SIDE_PEDIGREES = PEDIGREES + ("edge37", "edge38", "edge39", "edge40")
+SIDE_STEMS = tuple((stem, has_prior) for stem, _, has_prior in SIDE_PRODUCTS + SIDE_PRODUCTS_SINCE if stem not in ("trio", "map"))
+REFUSED = "refused"  # recorded in the digest's place where the generator declines the pedigree (sample_source: LDS rows)
 
 # One case per tuning switch at a value that is not its default, in a kernel family that reads it: (switch, value, pedigree,
 # cases).  ped10, and wide48 for the form without LDS staging.  A case is "<family>/<variant>" as _one_variant names it.
@@ -90,6 +104,12 @@ SWITCHES = (
     ("FAMSEQ_LANE_CAP", "5", "ped10", ("lane/5",)),
     ("FAMSEQ_LANE_TABLE_BUDGET", "40", "ped10", ("lane/1",)),
 )
+# ... and the side layer's: the switches the side products read
+SIDE_SWITCHES = (
+    ("FAMSEQ_PRIOR_LATE", "1", "ped10", ("evidence_prior/1", "weight_prior/1")),
+    ("FAMSEQ_RELABEL_LEAN", "1", "ped10", ("relabel/1",)),
+    ("FAMSEQ_SAMPLE_ROWS", "1", "ped10", ("sample/1",)),
+)
 
 
 TEXTS = None  # a dict: the source texts are kept in it by digest (--dump, and the test's report of a mismatch)
@@ -106,8 +126,22 @@ def _digest(plan, key, index=None):
     return digest
 
 
-def _one_variant(ped, v, env):
-    """Every kernel family's source in variant v (the families that have that many variants), under `env`."""
+def _side_digest(ctx, key):
+    """The source of side product `key` ("<stem>" or "<stem>_prior"), or REFUSED where its generator throws for the pedigree."""
+    try:
+        ctx.set_option(key + "_kernels", 1)
+    except fs.FamseqError as e:
+        if "_source: " not in str(e):  # (not the generator's own word: a failure, not a refusal)
+            raise
+        if TEXTS is not None:
+            TEXTS[REFUSED] = ("%s\n" % e).encode()
+        return REFUSED
+    return _digest(ctx.plan(), key + "_code_object")
+
+
+def _one_variant(ped, v, env, side=False):
+    """Every kernel family's source in variant v (the families that have that many variants), under `env`; side: the side
+    layer's families too."""
     out = {}
     cache = tempfile.mkdtemp(prefix="famseq_digests_")
     base = dict(FAMSEQ_KERNEL_CACHE=cache, FAMSEQ_JIT_SOURCE_ONLY="1", FAMSEQ_KEEP_SRC="1", FAMSEQ_QUIET="1", FAMSEQ_VARIANT_ONLY=str(v))
@@ -145,24 +179,29 @@ def _one_variant(ped, v, env):
                 out["map/%d" % v] = _digest(ctx.plan(), "map_code_object")
                 ctx.set_option("map_prior_kernels", 1)
                 out["map_prior/%d" % v] = _digest(ctx.plan(), "map_prior_code_object")
+            if side and v < SIDE_VARIANTS:
+                for stem, has_prior in SIDE_STEMS:
+                    for key in [stem] + ([stem + "_prior"] if has_prior else []):
+                        out["%s/%d" % (key, v)] = _side_digest(ctx, key)
             ctx.close()
     finally:
         shutil.rmtree(cache, ignore_errors=True)
     return out
 
 
-def digests(name):
-    """{case: sha256} of pedigree `name`: every family in every variant, and the cases of SWITCHES on that pedigree."""
+def digests(name, side=False):
+    """{case: sha256} of pedigree `name`: every family in every variant, and the cases of SWITCHES on that pedigree; side: with
+    the side layer's families and the cases of SIDE_SWITCHES."""
     ped = _named(name)
     ped.relations()
     out = {}
     for v in range(12):
-        for k, d in _one_variant(ped, v, {}).items():
+        for k, d in _one_variant(ped, v, {}, side).items():
             out["%s %s" % (name, k)] = d
-    for key, value, where, cases in SWITCHES:
+    for key, value, where, cases in SWITCHES + (SIDE_SWITCHES if side else ()):
         if where == name:
             for case in cases:
-                got = _one_variant(ped, int(case.split("/")[1]), {key: value})
+                got = _one_variant(ped, int(case.split("/")[1]), {key: value}, side)
                 out["%s %s %s=%s" % (name, case, key, value)] = got[case]
     return out
 
@@ -175,8 +214,8 @@ def main():
         TEXTS = {}
         os.makedirs(sys.argv[3], exist_ok=True)
     out = {}
-    for name in PEDIGREES:
-        mine = digests(name)
+    for name in SIDE_PEDIGREES:
+        mine = digests(name, side=True)
         out.update(mine)
         if TEXTS is not None:
             for case, digest in mine.items():
@@ -185,7 +224,7 @@ def main():
             TEXTS.clear()
     with open(sys.argv[1], "w") as f:
         f.write(json.dumps(out, indent=0, sort_keys=True) + "\n")
-    print("%s: %d cases over %d pedigrees" % (sys.argv[1], len(out), len(PEDIGREES)))
+    print("%s: %d cases over %d pedigrees" % (sys.argv[1], len(out), len(SIDE_PEDIGREES)))
 
 
 if __name__ == "__main__":
