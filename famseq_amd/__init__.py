@@ -95,6 +95,7 @@ ABI_SYMBOLS = [
     "famseq_allele_tables",
     "famseq_origin_batch", "famseq_origin_batch_device", "famseq_origin_prior_batch", "famseq_origin_prior_batch_device",
     "famseq_weight_batch", "famseq_weight_batch_device", "famseq_weight_prior_batch", "famseq_weight_prior_batch_device",
+    "famseq_maxmarg_batch", "famseq_maxmarg_batch_device", "famseq_maxmarg_prior_batch", "famseq_maxmarg_prior_batch_device",
 ]
 # (and famseq_philox4x32_10, the one name with digits in it: philox4x32 below)
 PL_MISSING = 0xFFFF
@@ -187,7 +188,8 @@ def lib():
     rates = ([dp, C.c_int32], [vp, C.c_int32])  # the host entries take the rates (weights), the device entries the resident tables
     for name, out_a, more in (("trio", dp, ([], [])), ("map", C.POINTER(C.c_int8), ([], [])), ("evidence", dp, ([], [])), ("loo", dp, ([], [])),
                               ("pattern", dp, masks), ("sample", C.POINTER(C.c_int8), draws),
-                              ("relabel", dp, assigns), ("mutrate", dp, rates), ("origin", dp, ([], [])), ("weight", dp, rates)):
+                              ("relabel", dp, assigns), ("mutrate", dp, rates), ("origin", dp, ([], [])), ("weight", dp, rates),
+                              ("maxmarg", dp, ([], []))):
         for prior in (0, 1):
             host = getattr(L, "famseq_%s%s_batch" % (name, "_prior" * prior))
             dev = getattr(L, "famseq_%s%s_batch_device" % (name, "_prior" * prior))
@@ -900,6 +902,30 @@ class Context:
         self._side_device("af", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_af, d_loglik, d_status, stream,
                           (d_af0 or None, int(n_iter)))
 
+    def maxmarg_batch(self, lk=None, pl16=None, seq_members=None, flags=None, want_maxmarg=True, want_top=True):
+        """Max-marginals and the runner-up of the joint MAP call: -> (maxmarg[S,N,3] float64, top[S,2] float64, status[S] uint8).
+        maxmarg[s, p, a] is the posterior of the best configuration in which member p has genotype a (exactly 0.0 where none
+        has positive weight); top[s] = (map_batch's map_post, bit for bit; the second-largest configuration's posterior).
+        Status as for map_batch; failed sites are NaN.  joint_call_quality() makes the per-member call and its quality of
+        maxmarg.  Inputs as for map_batch.  want_maxmarg / want_top False: that output is not computed and returned as None."""
+        outs = lambda s: (np.empty((s, self.n, 3)) if want_maxmarg else None, np.empty((s, 2)) if want_top else None)
+        return self._side_host("maxmarg", None, lk, pl16, seq_members, flags, outs)
+
+    def maxmarg_prior_batch(self, prior, lk=None, pl16=None, seq_members=None, flags=None, want_maxmarg=True, want_top=True):
+        """maxmarg_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give maxmarg_batch's bits."""
+        outs = lambda s: (np.empty((s, self.n, 3)) if want_maxmarg else None, np.empty((s, 2)) if want_top else None)
+        return self._side_host("maxmarg", prior, lk, pl16, seq_members, flags, outs)
+
+    def maxmarg_device(self, n_sites, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_maxmarg=0, d_top=0, d_status=0, stream=0):
+        """maxmarg_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("maxmarg", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_maxmarg, d_top, d_status, stream)
+
+    def maxmarg_prior_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_maxmarg=0, d_top=0, d_status=0,
+                                   stream=0):
+        """maxmarg_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("maxmarg", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_maxmarg, d_top, d_status, stream)
+
     def loo_prior_batch_device(self, n_sites, d_prior, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_loo=0, d_fit=0, d_status=0, stream=0):
         """loo_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
         self._side_device("loo", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_loo, d_fit, d_status, stream)
@@ -968,6 +994,22 @@ def phased_calls(origin):
     idx = np.argmax(np.where(bad[..., None], 0.0, o), axis=-1)  # (np.argmax: the first of equals)
     prob = np.take_along_axis(o, idx[..., None], axis=-1)[..., 0]
     return np.where(bad, -1, idx).astype(np.int8), np.where(bad, np.nan, prob)
+
+
+def joint_call_quality(maxmarg):
+    """The per-member joint call of maxmarg_batch's rows and its quality: maxmarg [..., 3] -> (jgt [...] int8, jgq [...] float64).
+    jgt is the row's largest entry (the lowest genotype among equals); jgq = -10 log10(second largest of the row / largest), the
+    Phred-scaled ratio between the best configuration and the best one in which the member is called differently: +inf where
+    the second largest is 0, 0 under an exact tie.  -1 and NaN for a NaN row."""
+    m = np.asarray(maxmarg, dtype=np.float64)
+    bad = np.isnan(m).any(axis=-1)
+    rows = np.where(bad[..., None], 1.0, m)
+    jgt = np.argmax(rows, axis=-1)  # (np.argmax: the first of equals)
+    ordered = np.sort(rows, axis=-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        jgq = np.abs(-10.0 * np.log10(ordered[..., 1] / ordered[..., 2]))
+    jgq = np.where(ordered[..., 1] == 0, np.inf, jgq)
+    return np.where(bad, -1, jgt).astype(np.int8), np.where(bad, np.nan, jgq)
 
 
 def call_genotypes(post):

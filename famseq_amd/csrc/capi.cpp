@@ -1281,6 +1281,31 @@ extern "C" int famseq_weight_prior_batch_device(famseq_ctx *c, int64_t n_sites, 
                     {d_wt_loglik, d_loglik, d_status, stream}, {d_weights, n_weights});
 }
 
+// ---- max-marginals and the runner-up of the joint call: the MAP entries with a row per member in the place of one genotype ------
+
+extern "C" int famseq_maxmarg_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                    int32_t n_seq, const uint8_t *flags, double *maxmarg, double *top, uint8_t *status) {
+  return side_entry(c, SIDE_MAXMARG, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags}, {maxmarg, top, status});
+}
+
+extern "C" int famseq_maxmarg_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                           const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_maxmarg, double *d_top,
+                                           uint8_t *d_status, void *stream) {
+  return side_entry(c, SIDE_MAXMARG, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags}, {d_maxmarg, d_top, d_status, stream});
+}
+
+extern "C" int famseq_maxmarg_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                          int32_t n_seq, const uint8_t *flags, const double *prior, double *maxmarg, double *top, uint8_t *status) {
+  return side_entry(c, SIDE_MAXMARG, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior}, {maxmarg, top, status});
+}
+
+extern "C" int famseq_maxmarg_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                                 const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                                 double *d_maxmarg, double *d_top, uint8_t *d_status, void *stream) {
+  return side_entry(c, SIDE_MAXMARG, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior},
+                    {d_maxmarg, d_top, d_status, stream});
+}
+
 // The sampling kernels' generator on the host: the text they carry (philox_src.h), compiled here.
 namespace {
 #define FS_PHILOX_FN inline

@@ -609,6 +609,72 @@ class Emitter {
     return loop + o_.str();
   }
 
+  // Max-marginals (famseq_maxmarg): for every member p and genotype a, M[p][a] = max over the configurations g with g_p = a of
+  // w(g) — marginal(p) in the (max, x) semiring: every family -> member message of the max pass, both directions, and no
+  // back-pointer (bp_ off: a message is a plain maximum, v_max_f64; on non-negative finite numbers that is the value arg_max's
+  // strict-greater compare-select keeps).  With xm<p>_g = loc(p) * prod_F xf<F>v<p>_g and Xc<c> the maximum of component c (the
+  // row maximum of its root, as map_assignment forms it), member p of component c has the row xm<p>_g * prod_{c' != c} Xc<c'>.
+  // Z_ and W_ are map_body's own expressions — the sum pass towards the roots (its sums pinned where they are formed: pin_sums),
+  // the roots' maxima multiplied left to right — so that W_ / Z_ has famseq_map's bits; a row's maximum equals W_ to rounding only (another order of multiplication).
+  // The runner-up: every configuration but the best differs from it at some member, so the second-largest weight is the largest
+  // row entry beside the rows' arg-maxes (scanned 0, 1, 2, replaced on strictly greater); under exact ties it equals W_.
+  // Loops: inside the cut loop.  Accumulators start at 0; per assignment a member p that is not cut takes acc<p>_g =
+  // max(acc<p>_g, xm<p>_g * (Lam * prod_{c' != c} Xc<c'>)), a cut member k acc<k>_{a_k} = max(acc<k>_{a_k}, Lam * prod_c Xc<c>);
+  // Zt_ and Wb_ accumulate as in map_body.  An entry without a supporting configuration of positive weight is a product with a
+  // factor of exactly 0 in every assignment: exactly 0.0.
+  // Each row is stored as it is formed, divided by Z_ (a true division, map_post's arithmetic): 3 doubles per message alive in
+  // both directions, the live set of loo_body.  Sets mm_w / mm_n (W_ / Z_, the runner-up / Z_) and bn_fail.
+  std::string maxmarg_body() {
+    const char *ok = "      if (!(Z_ > 0 && Z_ <= 1.79769313486231570815e308) || !(W_ > 0)) bn_fail = true;\n";
+    bp_ = false;
+    if (g_.cut.empty()) {
+      component_sums();
+      pin_sums();
+      max_roots();
+      o_ << "      const double Z_ = " << times_sums("", -1, "Zs") << ", W_ = " << times_sums("", -1, "Xc") << ";\n" << ok << "      double nx_ = 0;\n";
+      fence(1);
+      for (int p = 0; p < g_.N; ++p) {
+        const std::string rest = times_sums("", g_.comp[p], "Xc");
+        std::string row = max_marginal(p);
+        if (!rest.empty()) {
+          o_ << "      const double xo" << p << " = " << rest << ";\n";
+          for (int g = 0; g < 3; ++g) o_ << "      const double xr" << p << "_" << g << " = " << row << "_" << g << " * xo" << p << ";\n";
+          row = "xr" + num(p);
+        }
+        maxmarg_out(p, row);
+      }
+      o_ << "      mm_w = W_ / Z_; mm_n = nx_ / Z_;\n";
+      return o_.str();
+    }
+    std::ostringstream decls;
+    decls << "      double Zt_ = 0, Wb_ = 0;\n";
+    for (int p = 0; p < g_.N; ++p) decls << "      double acc" << p << "_0 = 0, acc" << p << "_1 = 0, acc" << p << "_2 = 0;\n";
+    const std::string loop = cut_loop(decls.str(), /*wc=*/false, /*wall=*/false, [&] {
+      pin_sums();
+      max_roots();
+      o_ << "      Zt_ = Zt_ + " << times_sums("Lam", -1, "Zs") << ";\n      const double Wa_ = " << times_sums("Lam", -1, "Xc") << ";\n"
+         << "      if (Wa_ > Wb_) Wb_ = Wa_;\n";
+      fence(1);
+      for (int p = 0; p < g_.N; ++p) {
+        if (g_.is_cut(p)) {
+          for (int g = 0; g < 3; ++g)
+            o_ << "      acc" << p << "_" << g << " = a" << p << " == " << g << " ? __builtin_fmax(acc" << p << "_" << g << ", Wa_) : acc" << p << "_" << g
+               << ";\n";
+          continue;
+        }
+        const std::string row = max_marginal(p);
+        o_ << "      const double xo" << p << " = " << times_sums("Lam", g_.comp[p], "Xc") << ";\n";
+        for (int g = 0; g < 3; ++g)
+          o_ << "      acc" << p << "_" << g << " = __builtin_fmax(acc" << p << "_" << g << ", " << row << "_" << g << " * xo" << p << ");\n";
+        fence(1);
+      }
+    });
+    o_ << "      const double Z_ = Zt_, W_ = Wb_;\n" << ok << "      double nx_ = 0;\n";
+    for (int p = 0; p < g_.N; ++p) maxmarg_out(p, "acc" + num(p));
+    o_ << "      mm_w = W_ / Z_; mm_n = nx_ / Z_;\n";
+    return loop + o_.str();
+  }
+
   // Exact joint posterior draws (famseq_sample): nd_ configurations per site, each drawn with probability w(g) / Z, by the walk
   // map_body's back-track takes with a weighted random choice in the place of every arg-max (forward filtering, backward sampling).
   //   collect   map_body's sum pass: component_sums(), one root per component, only the messages that point towards a root.
@@ -845,6 +911,61 @@ class Emitter {
     return e;
   }
 
+  // member p's unnormalised max-marginal row xm<p>_g (maxmarg_body): local * the max-pass messages of the adjacent families
+  std::string max_marginal(int p) {
+    const std::string n = "xm" + num(p);
+    if (once(n)) {
+      mx_ = true;
+      std::vector<std::string> in = {loc(p)};
+      for (int F : g_.nb[p]) in.push_back(max_fac2var(F, p));
+      products(n, in);
+      mx_ = false;
+    }
+    return n;
+  }
+  // Zs<c>: component c's total weight Zc<c> (component_sums' value, bit for bit), pinned: an empty volatile asm takes it as an
+  // operand, and volatile asms keep their order, the fences among them, so the sum pass's arithmetic is over before the max
+  // pass's starts.  Left to itself the compiler spreads it over the max pass, whose messages are alive in both directions: the
+  // 40-member kernel (eight components) then keeps 1.1 KB of scratch per lane where the pinned one keeps none and the
+  // leave-one-out kernel keeps none (profiles/maxmarg/resources.txt).
+  void pin_sums() {
+    for (size_t c = 0; c < g_.rep.size(); ++c)
+      o_ << "      double Zs" << c << " = Zc" << c << "; asm volatile(\"\" : \"+v\"(Zs" << c << ") :: \"memory\");\n";
+  }
+  // Xc<c>: the maximum of component c, the row maximum of its root's max-marginal (maxmarg_body; map_assignment's values).
+  // A row of component c is scaled by the maxima of every other component, so all of them stand in front of the first row.  With
+  // several components in the lean form (forty members and more) the messages towards a root are formed in a scope of their own
+  // here, the maximum pinned behind it (as pin_sums), and formed again where the component's rows are (the same statements, the
+  // same values: done_ is put back).  Kept, the upward messages of every component would be alive at once: the 64-member
+  // kernel (thirteen components) 624 B of scratch per lane against 300, the 40-member one 196 AGPRs against 158; the lean form's
+  // operands are volatile reads, which the compiler does not merge, and the vector ALU has the time.  Under forty members the
+  // operands are registers and the compiler would merge the two copies anyway.
+  void max_roots() {
+    fence(1);
+    const bool again = lean_ && g_.rep.size() > 1;
+    for (size_t c = 0; c < g_.rep.size(); ++c) {
+      const std::map<std::string, bool> before = done_;
+      if (again) o_ << "      double Xc" << c << ";\n      {\n";
+      const std::string r = max_marginal(g_.rep[c]);
+      o_ << "      " << (again ? "" : "const double ") << "Xc" << c << " = __builtin_fmax(__builtin_fmax(" << r << "_0, " << r << "_1), " << r << "_2);\n";
+      if (again) {
+        o_ << "      }\n      asm volatile(\"\" : \"+v\"(Xc" << c << ") :: \"memory\");\n";
+        done_ = before;
+      }
+    }
+  }
+  // member p's max-marginal outputs from its unnormalised row `from`: mg[3 p + g] = from_g / Z_, and the row's largest entry
+  // beside its arg-max (first of equals) into the runner-up nx_
+  void maxmarg_out(int p, const std::string &from) {
+    const std::string a = from + "_0", b = from + "_1", c = from + "_2";
+    o_ << "      { const double t_ = " << b << " > " << a << " ? " << b << " : " << a << ";\n"
+       << "        const double s_ = " << c << " > t_ ? t_ : (" << b << " > " << a << " ? __builtin_fmax(" << a << ", " << c << ") : __builtin_fmax(" << b << ", " << c
+       << "));\n"
+       << "        nx_ = __builtin_fmax(nx_, s_);\n"
+       << "        if (mg) { mg[" << 3 * p << "] = " << a << " / Z_; mg[" << 3 * p + 1 << "] = " << b << " / Z_; mg[" << 3 * p + 2 << "] = " << c << " / Z_; } }\n";
+    fence(1);
+  }
+
   // map_body for one assignment of the cut members (loops) or for the pedigree as it is: the max pass, the back-track, and Z_ / W_
   // (Zt_ / Wb_ over the assignments)
   void map_assignment(bool loops) {
@@ -1032,6 +1153,7 @@ class Emitter {
   int uid_ = 0;
   // the max pass of map_body: messages named x..., and what the back-track needs of each family -> member message
   bool mx_ = false;
+  bool bp_ = true;  // the max pass keeps its arg-maxes (map_body); off: plain maxima (maxmarg_body)
   struct Step {
     int F, t;
     std::string bp;                    // the message's packed arg-maxes
@@ -1203,6 +1325,14 @@ class Emitter {
   std::string max_child_sum(int F, int c) {
     const std::string x = var2fac(c, F);
     const std::string n = "xa" + num(uid_++);
+    if (!bp_) {
+      for (int gm = 0; gm < 3; ++gm)
+        for (int gf = 0; gf < 3; ++gf)
+          o_ << "      const double " << n << "_" << gm << gf << " = __builtin_fmax(__builtin_fmax(" << T(c, 0, gm, gf) << " * " << x << "_0, " << T(c, 1, gm, gf)
+             << " * " << x << "_1), " << T(c, 2, gm, gf) << " * " << x << "_2);\n";
+      fence(2);
+      return n;
+    }
     o_ << "      unsigned " << n << "b = 0;\n";
     for (int gm = 0; gm < 3; ++gm)
       for (int gf = 0; gf < 3; ++gf) {
@@ -1228,7 +1358,7 @@ class Emitter {
         st.kid_bp.push_back(sums.back() + "b");
       }
     const std::string C = pair_product(F, t, n, sums);
-    o_ << "      unsigned " << n << "b = 0;\n";
+    if (bp_) o_ << "      unsigned " << n << "b = 0;\n";
     for (int g = 0; g < 3; ++g) {
       std::vector<std::string> e;
       if (t == fam.mo) {
@@ -1239,10 +1369,16 @@ class Emitter {
         for (int gm = 0; gm < 3; ++gm)
           for (int gf = 0; gf < 3; ++gf) e.push_back(T(t, g, gm, gf) + " * " + C + "_" + num(gm) + num(gf));
       }
-      arg_max(n + "_" + num(g), e, n + "b", (e.size() == 9 ? 4 : 2) * g);
+      if (bp_) {
+        arg_max(n + "_" + num(g), e, n + "b", (e.size() == 9 ? 4 : 2) * g);
+        continue;
+      }
+      std::string mx = e[0];
+      for (size_t i = 1; i < e.size(); ++i) mx = "__builtin_fmax(" + mx + ", " + e[i] + ")";
+      o_ << "      const double " << n << "_" << g << " = " << mx << ";\n";
     }
     fence(1);
-    steps_.push_back(st);
+    if (bp_) steps_.push_back(st);
     return n;
   }
 
@@ -1640,6 +1776,26 @@ std::string loo_source(const Model &m, int variant, bool site_prior) {
                  "    (void)og; (void)fg;\n";
   d.body = Emitter(m, g, eo).loo_body();
   d.epilogue = fail_block(fill("og", "W3") + fill("fg", "NMEM")) + status_store();
+  return lane_shell(m, d);
+}
+
+// The max-marginal kernel: the MAP kernel's rules.  Outputs per site: maxmarg[3 N] (member p's row max_{g: g_p = a} w(g) / Z) and
+// top[2] (the best configuration's posterior, famseq_map's map_post bit for bit, and the runner-up's), status; any may be null (a
+// null output's stores fold away).  The rows are stored straight from the lane as they are formed, as famseq_loo's; a site that
+// fails is filled with NaN behind the body.  Where the likelihoods live is famseq_loo's rule (begin_side): this is that kernel's
+// live set, a maximum in the place of an addition.
+std::string maxmarg_source(const Model &m, int variant, bool site_prior) {
+  auto [g, f, eo, d] = begin_side(m, "maxmarg", "max-marginals and the runner-up (max-product, both directions)", variant, kMaxmargVariants, site_prior);
+  d.outputs = "double *__restrict__ maxmarg_g, double *__restrict__ top_g";
+  d.site_decls = "    double *mg = maxmarg_g ? maxmarg_g + site * W3 : nullptr;\n"
+                 "    (void)mg;\n";
+  d.site_vars = "    double mm_w = kNaN, mm_n = kNaN;\n";
+  d.body = Emitter(m, g, eo).maxmarg_body();
+  d.epilogue = fail_block("      mm_w = kNaN; mm_n = kNaN;\n" + fill("mg", "W3")) +
+               "    if (top_g) {\n"
+               "      __builtin_nontemporal_store(mm_w, top_g + 2 * site);\n"
+               "      __builtin_nontemporal_store(mm_n, top_g + 2 * site + 1);\n"
+               "    }\n" + status_store();
   return lane_shell(m, d);
 }
 

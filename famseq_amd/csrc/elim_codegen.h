@@ -78,6 +78,16 @@ constexpr int kLooVariants = 4;
 // site_prior: famseq_loo_prior, with a trailing `prior` [n_sites][6] (as trio_source's).
 std::string loo_source(const Model &m, int variant, bool site_prior = false);
 
+// Max-marginals and the runner-up of the joint call (famseq_maxmarg_batch).  HIP source of
+// `extern "C" __global__ famseq_maxmarg(lk, flags, maxmarg, top, status, n_sites, tc, lc)`: per site and member p (PED order)
+// maxmarg[3 p + a] = max_{g: g_p = a} w(g) / Z — famseq_map's max pass in both directions, without back-pointers — and
+// top = (w(g*) / Z, the second-largest w / Z): top[0] is famseq_map's map_post bit for bit (the same expressions for W and Z).
+// An entry without a supporting configuration of positive weight is exactly 0.0.  variant 0..3: the fence levels of
+// famseq_elim's; every variant gives the same bits.  Throws if the engine does not serve the pedigree.
+constexpr int kMaxmargVariants = 4;
+// site_prior: famseq_maxmarg_prior, with a trailing `prior` [n_sites][6] (as trio_source's).
+std::string maxmarg_source(const Model &m, int variant, bool site_prior = false);
+
 // Genotype-pattern posteriors (famseq_pattern_batch).  HIP source of
 // `extern "C" __global__ famseq_pattern(lk, flags, ppost, loglik, status, n_sites, tc, lc, mask, n_patterns)`: per site and pattern
 // m — mask[m][p] holds in bit g whether member p (PED order) may have genotype g — ppost[m] = Z_m / Z, the posterior probability

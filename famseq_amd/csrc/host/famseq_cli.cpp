@@ -5,7 +5,7 @@
 //              [-mRate r] [-genoProbN a b c] [-genoProbK a b c] [-genoProbXN a c]
 //              [-genoProbXK a c] [-LRC x] [-dnm] [-map] [-siteQ] [-loo] [-afTag KEY | -afTagAll KEY]
 //              [-seg dominant|recessive|both -affected ID[,ID...] [-unaffected ID[,ID...]]] [-sample K [-seed S]]
-//              [-afEM T [-afStart X]] [-swapCheck FILE] [-mRateScan FILE [-mRateGrid r1,r2,...]] [-phase]
+//              [-afEM T [-afStart X]] [-swapCheck FILE] [-mRateScan FILE [-mRateGrid r1,r2,...]] [-phase] [-mapQ]
 //              [-segPen F0,F1,F2[/F0,F1,F2...] -affected ID[,ID...] [-unaffected ID[,ID...]]]
 //   FamSeq LK -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
@@ -197,6 +197,7 @@ struct Options {
   bool siteq = false;  // -siteQ: FQ and FLL keys in the INFO column (vcf mode)
   bool phase = false;  // -phase: PGT and PGP fields per sample, the phased genotype by transmission and its probability (vcf mode)
   bool loo = false;    // -loo: LOP and LOF fields per sample, the leave-one-out posteriors and the member's fit (vcf mode)
+  bool mapq = false;   // -mapQ: a JGQ field per sample, the quality of its joint call, and the runner-up's JP2 in the INFO column (vcf mode)
   int sample = 0;      // -sample K: an SGT field per sample, its alt-allele counts in K joint posterior draws of the family (vcf mode)
   uint64_t seed = 0;   // -seed S: the draws' seed
   // -seg dominant|recessive|both: PSD and / or PSR keys in the INFO column (vcf mode), the posterior probability of the genotype
@@ -364,6 +365,8 @@ int parse_options(int argc, char **argv, Options &o) {
       o.loo = true;
     } else if (opt == "phase") {
       o.phase = true;
+    } else if (opt == "mapQ") {
+      o.mapq = true;
     } else if (opt == "sample" || opt == "seed") {
       i++;
       if (missing(i)) {
@@ -1480,11 +1483,11 @@ struct Part {
 // ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample, -seg and -afEM add to a line, one row of kSide each; -swapCheck and
 // ---- -mRateScan, which add nothing to any line and write a report of their own behind the last site (SideRow::report), are rows too
 // The order is the one main checks them and prints its notices in; it is also the order of the fields in a sample column (DNP,
-// JGT:JP, LOP:LOF, SGT, PGT:PGP) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL, then PSL).  Header lines have their
-// own order.
-enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap, kRateScan, kPhase, kSegPen };
-constexpr int kSides = kSegPen + 1;
-const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap, kRateScan, kPhase, kSegPen};
+// JGT:JP, LOP:LOF, SGT, PGT:PGP, JGQ) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL, then PSL, then JP2).  Header
+// lines have their own order.
+enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap, kRateScan, kPhase, kSegPen, kMapQ };
+constexpr int kSides = kMapQ + 1;
+const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap, kRateScan, kPhase, kSegPen, kMapQ};
 
 // One side output of a block: the two arrays its C entry fills ([site][...], read as the entry's own types) and its status per site.
 struct SideOut {
@@ -1511,8 +1514,10 @@ struct SideRow {
   // says of a block is summed up site by site (VcfRun::add_report / add_rate_report) and written behind the last site
   // (VcfRun::write_report / write_rate_report)
   bool report = false;
+  bool info_too = false;  // beside its FORMAT keys it joins a key to the INFO column (-mapQ: JGQ per sample, JP2 per site)
 };
 extern const SideRow kSide[kSides];
+constexpr size_t kInfoColumn = ~size_t(0);  // put_side's j where a row with FORMAT keys is asked for its INFO key
 // Row id's fields behind column j of site s, from the ':' on, or its INFO keys for site s: a switch, which the formatter's loop inlines
 [[gnu::always_inline]] inline void put_side(SideId id, TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j);
 
@@ -1610,8 +1615,8 @@ struct VcfRun {
       if (!row.on(o)) continue;
       sides.push_back(&row);
       if (row.report) continue;
-      (row.keys ? fields : infos).push_back(&row);
-      if (row.keys) format_keys += row.keys;
+      if (row.keys) fields.push_back(&row), format_keys += row.keys;
+      if (!row.keys || row.info_too) infos.push_back(&row);
     }
     format_keys += '\t';
     N3 = size_t(3) * ped.n();
@@ -1974,6 +1979,7 @@ struct VcfRun {
       case kMap: rc = entry(famseq_map_batch, famseq_map_prior_batch, a8, b, st); break;
       case kSiteQ: rc = entry(famseq_evidence_batch, famseq_evidence_prior_batch, a, b, st); break;
       case kLoo: rc = entry(famseq_loo_batch, famseq_loo_prior_batch, a, b, st); break;
+      case kMapQ: rc = entry(famseq_maxmarg_batch, famseq_maxmarg_prior_batch, a, b, st); break;
       case kSample: rc = entry(famseq_sample_batch, famseq_sample_prior_batch, o.seed, sl.site_base, (int32_t)o.sample, a8, none, st); break;
       case kSeg: rc = entry(famseq_pattern_batch, famseq_pattern_prior_batch, seg_masks.data(), (int32_t)seg_keys.size(), a, none, st); break;
       case kSwap: return call_swap(sl, so, lk, pl16);
@@ -2183,7 +2189,7 @@ struct VcfRun {
       if (sl.side[row->id].status[s] != 0) continue;
       if (!first) out.ch(';');
       first = false;
-      put_side(row->id, out, *this, sl.side[row->id], s, 0);
+      put_side(row->id, out, *this, sl.side[row->id], s, kInfoColumn);
     }
     out.put(raw + end, len - end);
   }
@@ -2367,8 +2373,27 @@ inline void put_psl(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, 
   }
 }
 
+// -mapQ: JGQ, the Phred-scaled ratio of the largest entry of the member's max-marginal row to its second largest (99999 where
+// the second largest is 0: no configuration of positive weight calls the member differently), printed as FPP is; in the INFO
+// column JP2, the runner-up configuration's posterior
+inline void put_mapq(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {
+  if (j == kInfoColumn) {
+    out.put("JP2=", 4);
+    return out.num(so.b[2 * s + 1]);
+  }
+  if (so.status[s] != 0) return out.put(":NA", 3);
+  const double *m = so.a.data() + 3 * (s * size_t(r.ped.n()) + size_t(r.cm.members[j]));
+  int best = 0;
+  for (int g = 1; g < 3; ++g)
+    if (m[g] > m[best]) best = g;
+  const double second = std::max(m[(best + 1) % 3], m[(best + 2) % 3]);
+  out.ch(':');
+  out.num(second == 0 ? 99999.0 : std::fabs(-10.0 * std::log10(second / m[best])));
+}
+
 [[gnu::always_inline]] inline void put_side(SideId id, TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {
   switch (id) {
+    case kMapQ: return put_mapq(out, r, so, s, j);
     case kSegPen: return put_psl(out, r, so, s, j);
     case kPhase: return put_phase(out, r, so, s, j);
     case kDnm: return put_dnp(out, r, so, s, j);
@@ -2553,6 +2578,16 @@ const SideRow kSide[kSides] = {
               "pedigree and the founders' prior alone (-inf: the data rule them out; .: no value)\">" << std::endl;
      },
      nullptr, nullptr, [](const VcfRun &r) { return SideBytes{16 * (r.o.pen.size() / 3), 16}; }},
+    // (not tied to -map: with both, JGT stays the MAP kernel's, whose tie rule differs from a row's arg-max only under exact ties)
+    {kMapQ, "-mapQ", "famseq_maxmarg", true, [](const Options &o) { return o.mapq; }, [](Options &o) { o.mapq = false; }, nullptr,
+     [](std::ostream &out, const Options &) {
+       out << "##FORMAT=<ID=JGQ,Number=1,Type=Float,Description=\"Quality of the sample's genotype in the most probable joint configuration of "
+              "the whole family: Phred-scaled ratio of the posterior of the best configuration in which the sample has another genotype to "
+              "that of the best configuration (99999: no such configuration has any probability)\">" << std::endl;
+       out << "##INFO=<ID=JP2,Number=1,Type=Float,Description=\"Posterior probability of the second most probable joint genotype "
+              "configuration of the whole family\">" << std::endl;
+     },
+     ":JGQ", ":NA", [](const VcfRun &r) { return SideBytes{24 * size_t(r.ped.n()), 16}; }, /*report=*/false, /*info_too=*/true},
 };
 
 // `FamSeq vcf` and `FamSeq pack`: the wiring of a VcfRun's stages
@@ -2792,6 +2827,11 @@ void help() {
             << "\t\tand incomplete penetrance allowed: -seg dominant is the corner 0,1,1) over their probability under the pedigree and the" << std::endl
             << "\t\tfounders' prior alone; -inf where the data rule them out, . where the site failed. With or without -seg. Implies" << std::endl
             << "\t\t-method 2; may be combined with every other option above, under -afTagAll with the line's prior; not with -afTag." << std::endl
+            << "-mapQ\t\t(vcf) Add JGQ, the quality of the sample's genotype in the most probable joint configuration of the family (what -map" << std::endl
+            << "\t\tprints as JGT): the Phred-scaled ratio between that configuration's posterior and the best configuration's in which the" << std::endl
+            << "\t\tsample has another genotype (99999: none has any probability), to every sample column, and JP2, the posterior of the" << std::endl
+            << "\t\tsecond most probable configuration, to the INFO column. With or without -map. Implies -method 2; may be combined with" << std::endl
+            << "\t\tevery other option above, under -afTagAll with the line's prior; not with -afTag." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl

@@ -130,6 +130,9 @@ SideTable &side_table() {
        [](const Model &, int n_weights, size_t row[2]) { row[0] = size_t(n_weights) * sizeof(double), row[1] = sizeof(double); },  // wt_loglik[M], loglik
        {X_CALL, "tn", "n_weights", 1, FAMSEQ_MAX_WEIGHTS, "weights", "n_weights tables of three doubles per member", check_weights,
         [](const Model &m) { return 3 * size_t(m.n_members) * sizeof(double); }, nullptr, "d_weights"}},
+      {"maxmarg", "max-marginals", "1", K_MAXMARG, K_MAXMARG_PRIOR, 1, kMaxmargVariants,
+       [](const Model &m, int v, int, bool site_prior) { return maxmarg_source(m, v, site_prior); },
+       [](const Model &m, int, size_t row[2]) { row[0] = 3 * size_t(m.n_members) * sizeof(double), row[1] = 2 * sizeof(double); }},  // maxmarg[N][3], top[2]
   };
   return table;
 }

@@ -22,6 +22,13 @@ SIDE_PRODUCTS = (("trio", 3, True), ("map", 1, True), ("evidence", 1, True), ("l
 # levels: tests/test_gpu_mutrate.py, tests/test_gpu_origin.py, tests/test_gpu_weight.py); build() pre-builds the four levels of both
 # lists
 SIDE_PRODUCTS_SINCE = (("mutrate", 1, True), ("origin", 1, True), ("weight", 1, True))
+# ... and since tests/_edge.py's matrix was drawn up over those two (its own GPU tests: tests/test_gpu_maxmarg.py); build()
+# pre-builds this list as it does the others
+SIDE_PRODUCTS_LATER = (("maxmarg", 1, True),)
+# The pedigrees tests/test_gpu_maxmarg.py and tests/test_cli_mapq_gpu.py run beside the lists above (side_variant_pedigree's
+# names and wide<n>; random0 and random6 are test_gpu_map.py's loop0 and loop1): build() compiles the max-marginal kernel and its
+# site-prior sibling for each, so that no test waits for a compiler on the device
+MAXMARG_PEDIGREES = ("trio", "quad", "ped5", "ped10", "ped15", "random0", "random6", "wide24", "wide64")
 
 
 # The pedigrees on which the lane kernel's variants 4-11 (csrc/enum_codegen.h: 4-7 the once-per-site form, 8-11 the outer-leaf
@@ -138,6 +145,8 @@ def side_variant_pedigree(name):
         ped = Pedigree(ids, mids, fids, [1, 2, 1, 2, 2, 1, 1, 2, 1], ["s%d" % i for i in ids])
     elif name.startswith("random"):
         ped = random_pedigree(int(name[6:]))[1]
+    elif name.startswith("wide"):
+        ped = wide_pedigree(int(name[4:]))
     else:
         ped = synthetic_pedigree(name)
     ped.relations()

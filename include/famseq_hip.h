@@ -851,6 +851,52 @@ int famseq_weight_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const dou
                                      const double *d_weights, int32_t n_weights, double *d_wt_loglik, double *d_loglik,
                                      uint8_t *d_status, void *stream);
 
+/* ---- max-marginals and the runner-up: the quality of the joint MAP call -----------------------------------------------------
+ * famseq_map_batch gives the most probable configuration g* and its posterior; this entry says what holds the rest.  With w as
+ * for famseq_map_batch and Z = sum_g w(g), by max-product message passing in both directions (no back-pointers) on the
+ * sum-product engine's graph, O(27 N) per site:
+ *   maxmarg [n_sites][N][3] fp64   maxmarg[p][a] = max_{g: g_p = a} w(g) / Z: the posterior of the best configuration in which
+ *              member p has genotype a.  Exactly 0.0 where no configuration of positive weight has g_p = a: a result, not a
+ *              failure.  The ratio of a row's two largest entries is the Phred-scalable quality of member p's joint call.
+ *   top     [n_sites][2] fp64      top[0] = w(g*) / Z; top[1] = the second-largest configuration weight / Z, the runner-up's
+ *              posterior (under exact ties it equals top[0]; 0.0 where one configuration holds all the weight).
+ *   status  [n_sites]              0 OK; 1 the single-posterior failure rule of famseq_bn_batch; 2 the total or the maximum
+ *              weight is <= 0 or not finite.  There is no -LRC shortcut.  Wherever status != 0, maxmarg and top are NaN.
+ * The contract.  Bit for bit: top[0] is famseq_map_batch's map_post (the prior form: famseq_map_prior_batch's) — the kernel forms
+ * the maximum and the total with that kernel's expressions; packed and fp64 input give the same bits; a site's result does not
+ * depend on the batch, its chunking or the launch; every variant of the kernel gives the same bits.  To rounding (1e-9
+ * relative): max_a maxmarg[p][a] = top[0] for every p (a row's maximum is formed in another order of multiplication);
+ * maxmarg[p][a] <= the sum-product engine's famseq_bn_batch post[p][a], a maximum being at most the sum; maxmarg[p][a] * Z is the
+ * maximum weight famseq_map_batch finds on the rows with member p's row zeroed except entry a.
+ * The runner-up is the largest entry beside the rows' arg-maxes (each row scanned 0, 1, 2, replaced on strictly greater): every
+ * configuration but the best differs from it at some member.
+ * Served for every pedigree the engine serves: loop-free ones of any size, loops up to three conditioned members; any other gets
+ * FAMSEQ_E_ARG with the engine's message.  The kernel is compiled on the first call, or ahead through famseq_set_option
+ * "maxmarg_kernels" = 1 (a plan-only context generates and cross-compiles it).  famseq_plan_json: "maxmarg_code_object",
+ * "maxmarg_variant". */
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_map_batch (exactly one of lk / pl16).  Any of maxmarg / top /
+ * status may be NULL. */
+int famseq_maxmarg_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                         int32_t n_seq, const uint8_t *flags, double *maxmarg, double *top, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array): enqueues on `stream` (a hipStream_t;
+ * NULL = the default stream) and returns without synchronising (the stream rule at famseq_bn_batch_device: with d_lk no context
+ * state, no event and no wait; with d_pl16 through the kept scratch rows, like every side entry). */
+int famseq_maxmarg_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, double *d_maxmarg, double *d_top,
+                                uint8_t *d_status, void *stream);
+
+/* With the founders' genotype prior given per site: prior[n_sites][6], as for famseq_map_prior_batch.  Given rows that equal the
+ * model's constants the outputs are, bit for bit, famseq_maxmarg_batch's.  "maxmarg_prior_kernels" = 1 builds the kernel
+ * (famseq_maxmarg_prior) ahead; it takes the variant its plain sibling's contest takes.  famseq_plan_json:
+ * "maxmarg_prior_code_object", "maxmarg_prior_variant".  Nothing is checked of d_prior's contents. */
+int famseq_maxmarg_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                               int32_t n_seq, const uint8_t *flags, const double *prior, double *maxmarg, double *top, uint8_t *status);
+int famseq_maxmarg_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                      const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                      double *d_maxmarg, double *d_top, uint8_t *d_status, void *stream);
+
 /* Hardy-Weinberg rows for the site-prior entries above, on the host: prior[i] =((1-q)^2, 2q(1-q), q^2, 1-q, 0, q) for q = af[i]
  * (the male chrX row has the shape of genoProbXN: no heterozygotes). */
 void famseq_hwe_priors(int64_t n, const double *af, double *prior /*[n][6]*/);

@@ -10,6 +10,7 @@ regenerates the matrix and compares.
     python tools/source_digests.py OUT.json              # write the manifest (to record a deliberate change of emitted text)
     python tools/source_digests.py OUT.json --dump DIR   # ... and every source text, one file per case: run it on two commits
                                                          # and `diff -r` the directories to see what changed
+    python tools/source_digests.py --later OUT.json      # the manifest of the products added since (LATER_STEMS, below)
 
 The sources are obtained the way the host tests obtain them: a plan-only context with FAMSEQ_JIT_SOURCE_ONLY,
 FAMSEQ_KEEP_SRC and a scratch FAMSEQ_KERNEL_CACHE; FAMSEQ_VARIANT_ONLY forces the variant; the .hip file is read next to
@@ -28,8 +29,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import famseq_amd as fs  # noqa: E402
-from famseq_amd.prebuild_sets import (EDGE_PEDIGREES, SIDE_PRODUCTS, SIDE_PRODUCTS_SINCE, SIDE_VARIANTS, edge_pedigree,  # noqa: E402
-                                      random_pedigree, wide_pedigree)
+from famseq_amd.prebuild_sets import (EDGE_PEDIGREES, SIDE_PRODUCTS, SIDE_PRODUCTS_LATER, SIDE_PRODUCTS_SINCE, SIDE_VARIANTS,  # noqa: E402
+                                      edge_pedigree, random_pedigree, wide_pedigree)
 
 TWO_CUT_SEED = 99  # the first random_pedigree seed whose loops need exactly two conditioned members (seeds 0..117 searched)
 
@@ -67,6 +68,11 @@ PEDIGREES = ("trio", "quad", "ped5", "ped10", "ped15:12", "cousins", "random15",
 # to the lean form between 39 and 40.  tests/golden/generated_sources.json holds the side layer.
 SIDE_PEDIGREES = PEDIGREES + ("edge37", "edge38", "edge39", "edge40")
 SIDE_STEMS = tuple((stem, has_prior) for stem, _, has_prior in SIDE_PRODUCTS + SIDE_PRODUCTS_SINCE if stem not in ("trio", "map"))
+# A third layer, in a manifest of its own (a manifest that exists is a test's yardstick and is not rewritten for a new product):
+# the rows side_table() has gained since the side layer's manifest was written (prebuild_sets.SIDE_PRODUCTS_LATER), on
+# SIDE_PEDIGREES, cases "<stem>/<v>" and "<stem>_prior/<v>" as in the side layer and nothing else (later_digests(name)).
+# tests/golden/generated_sources_later.json holds it; tests/test_generated_sources_later.py compares.
+LATER_STEMS = tuple((stem, has_prior) for stem, _, has_prior in SIDE_PRODUCTS_LATER)
 REFUSED = "refused"  # recorded in the digest's place where the generator declines the pedigree (sample_source: LDS rows)
 
 # One case per tuning switch at a value that is not its default, in a kernel family that reads it: (switch, value, pedigree,
@@ -139,15 +145,22 @@ def _side_digest(ctx, key):
     return _digest(ctx.plan(), key + "_code_object")
 
 
-def _one_variant(ped, v, env, side=False):
+def _one_variant(ped, v, env, side=False, later=False):
     """Every kernel family's source in variant v (the families that have that many variants), under `env`; side: the side
-    layer's families too."""
+    layer's families too; later: the third layer's families and no others."""
     out = {}
     cache = tempfile.mkdtemp(prefix="famseq_digests_")
     base = dict(FAMSEQ_KERNEL_CACHE=cache, FAMSEQ_JIT_SOURCE_ONLY="1", FAMSEQ_KEEP_SRC="1", FAMSEQ_QUIET="1", FAMSEQ_VARIANT_ONLY=str(v))
     try:
         with mock.patch.dict(os.environ, dict(base, **env)):
             model = fs.make_model(ped)
+            if later:
+                ctx = fs.Context(model, device=-1)
+                for stem, has_prior in LATER_STEMS:
+                    for key in [stem] + ([stem + "_prior"] if has_prior else []):
+                        out["%s/%d" % (key, v)] = _side_digest(ctx, key)
+                ctx.close()
+                return out
             if ped.n <= fs.MAXN and v < 8:  # the enumeration's lane kernel, its lanes-per-site forms and its call form
                 ctx = fs.Context(model, device=-1)
                 ctx.set_option("enum_impl", 1)
@@ -206,8 +219,23 @@ def digests(name, side=False):
     return out
 
 
+def later_digests(name):
+    """{case: sha256} of pedigree `name` in the third layer: LATER_STEMS' families in every fence level."""
+    ped = _named(name)
+    ped.relations()
+    return {"%s %s" % (name, k): d for v in range(SIDE_VARIANTS) for k, d in _one_variant(ped, v, {}, later=True).items()}
+
+
 def main():
     global TEXTS
+    if len(sys.argv) == 3 and sys.argv[1] == "--later":
+        out = {}
+        for name in SIDE_PEDIGREES:
+            out.update(later_digests(name))
+        with open(sys.argv[2], "w") as f:
+            f.write(json.dumps(out, indent=0, sort_keys=True) + "\n")
+        print("%s: %d cases over %d pedigrees" % (sys.argv[2], len(out), len(SIDE_PEDIGREES)))
+        return
     if len(sys.argv) not in (2, 4) or (len(sys.argv) == 4 and sys.argv[2] != "--dump"):
         sys.exit(__doc__)
     if len(sys.argv) == 4:
