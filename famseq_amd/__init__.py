@@ -96,6 +96,7 @@ ABI_SYMBOLS = [
     "famseq_origin_batch", "famseq_origin_batch_device", "famseq_origin_prior_batch", "famseq_origin_prior_batch_device",
     "famseq_weight_batch", "famseq_weight_batch_device", "famseq_weight_prior_batch", "famseq_weight_prior_batch_device",
     "famseq_maxmarg_batch", "famseq_maxmarg_batch_device", "famseq_maxmarg_prior_batch", "famseq_maxmarg_prior_batch_device",
+    "famseq_charfn_batch", "famseq_charfn_batch_device", "famseq_charfn_prior_batch", "famseq_charfn_prior_batch_device",
 ]
 # (and famseq_philox4x32_10, the one name with digits in it: philox4x32 below)
 PL_MISSING = 0xFFFF
@@ -189,7 +190,7 @@ def lib():
     for name, out_a, more in (("trio", dp, ([], [])), ("map", C.POINTER(C.c_int8), ([], [])), ("evidence", dp, ([], [])), ("loo", dp, ([], [])),
                               ("pattern", dp, masks), ("sample", C.POINTER(C.c_int8), draws),
                               ("relabel", dp, assigns), ("mutrate", dp, rates), ("origin", dp, ([], [])), ("weight", dp, rates),
-                              ("maxmarg", dp, ([], []))):
+                              ("maxmarg", dp, ([], [])), ("charfn", dp, rates)):
         for prior in (0, 1):
             host = getattr(L, "famseq_%s%s_batch" % (name, "_prior" * prior))
             dev = getattr(L, "famseq_%s%s_batch_device" % (name, "_prior" * prior))
@@ -331,6 +332,65 @@ def penetrance_weights(n, affected, unaffected=(), pen=(0.0, 1.0, 1.0)):
 MAX_RELABEL = 64
 MAX_RATES = 32
 MAX_WEIGHTS = 32
+MAX_CWEIGHTS = 64
+COUNT_KINDS = {"carriers": (0, 1, 1), "alleles": (0, 1, 2), "homalt": (0, 0, 1)}
+COUNT_CLIP = 1e-12  # count_from_cf: a probability in [-COUNT_CLIP, 0) is rounding below an exact 0 (charfn_batch's absolute bar)
+
+
+def count_scores(n, members=None, kind="carriers"):
+    """The per-member genotype scores [n, 3] int64 of an additive count for count_tables / Context.count_batch: the members
+    named (indices in PED order; default all n) score (0, 1, 1) per genotype for kind "carriers", (0, 1, 2) for "alleles" — the
+    genotype index as coded: a male's genotype 2 at a chrX site counts 2 — and (0, 0, 1) for "homalt"; everyone else scores 0."""
+    if kind not in COUNT_KINDS:
+        raise ValueError("kind must be 'carriers', 'alleles' or 'homalt', got %r" % (kind,))
+    mem = list(range(n)) if members is None else [int(i) for i in members]
+    for i in mem:
+        if not 0 <= i < n:
+            raise ValueError("member index %d is outside 0..%d" % (i, n - 1))
+    if len(set(mem)) != len(mem):
+        raise ValueError("members are listed twice: %s" % sorted(i for i in set(mem) if mem.count(i) > 1))
+    scores = np.zeros((n, 3), np.int64)
+    scores[mem] = COUNT_KINDS[kind]
+    return scores
+
+
+def count_tables(scores):
+    """The complex weight tables of the count sum_p scores[p][g_p] for Context.charfn_batch: -> (tables [M // 2 + 1, N, 3]
+    complex128, D).  D = sum_p max_g scores[p][g] is the count's largest value, M = D + 1 the length of its distribution, and
+    table j is omega^(j * scores), omega = exp(2 pi i / M), for j = 0 .. M // 2: the other frequencies are these ones' conjugates
+    (count_from_cf).  scores: non-negative integers [N, 3]."""
+    sc = np.asarray(scores)
+    if sc.ndim != 2 or sc.shape[1] != 3 or sc.dtype.kind not in "iu" or np.any(sc < 0):
+        raise ValueError("scores must be non-negative integers [N, 3]")
+    D = int(sc.max(axis=1).sum())
+    M = D + 1
+    if M // 2 + 1 > MAX_CWEIGHTS:
+        raise ValueError("a count that reaches D = %d needs %d tables, more than the %d of one call" % (D, M // 2 + 1, MAX_CWEIGHTS))
+    j = np.arange(M // 2 + 1)[:, None, None]
+    # (the exponent reduced mod M in integers, so that omega^(j s) is exact at the quarter turns and equal where j s mod M is)
+    return np.exp(2j * np.pi * ((j * sc[None].astype(np.int64)) % M) / M), D
+
+
+def count_from_cf(cf, D):
+    """The count's distribution from its characteristic function at the frequencies count_tables gives: cf [S, D // 2 + 1]
+    complex (or [S, D // 2 + 1, 2] float64, charfn_batch's own) -> dist [S, D + 1] float64, dist[s, k] = P(count = k | data) =
+    (1 / M) sum_j phi_j omega^(-j k) with M = D + 1, the missing frequencies the conjugates of those given; the real part.
+    Values in [-1e-12, 0), rounding below an exact 0, become 0.0; nothing is renormalised; a failed site's row (NaN) stays NaN."""
+    phi = np.asarray(cf)
+    if not np.iscomplexobj(phi):
+        phi = phi[..., 0] + 1j * phi[..., 1]
+    M = int(D) + 1
+    if phi.ndim != 2 or phi.shape[1] != M // 2 + 1:
+        raise ValueError("cf must hold %d frequencies per site for D = %d, got %s" % (M // 2 + 1, D, list(phi.shape)))
+    full = np.empty((phi.shape[0], M), np.complex128)
+    full[:, :M // 2 + 1] = phi
+    j = np.arange(M // 2 + 1, M)
+    full[:, j] = np.conj(phi[:, M - j])
+    jk = (np.arange(M)[:, None] * np.arange(M)[None, :]) % M
+    with np.errstate(invalid="ignore"):
+        dist = (full @ np.exp(-2j * np.pi * jk / M)).real / M
+        dist[(dist < 0) & (dist >= -COUNT_CLIP)] = 0.0
+    return dist
 RATE_TABLE_DOUBLES = 432
 ALLELE_TABLE_DOUBLES = 48
 
@@ -842,6 +902,64 @@ class Context:
         """weight_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
         self._side_device("weight", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_wt_loglik, d_loglik, d_status, stream,
                           (d_weights or None, int(n_weights)))
+
+    def _cweights(self, cweights):
+        """cweights (complex [N, 3] / [M, N, 3], or real [M, N, 3, 2]) as a contiguous float64 array [M, N, 3, 2]."""
+        w = np.asarray(cweights)
+        if np.iscomplexobj(w):
+            w = np.ascontiguousarray(w, dtype=np.complex128)
+            if w.ndim == 2:
+                w = w[None]
+            w = w.view(np.float64).reshape(w.shape + (2,))
+        else:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.ndim != 4 or w.shape[1:] != (self.n, 3, 2):
+            raise ValueError("cweights must be complex [M, %d, 3] (or real [M, %d, 3, 2]), got %s" % (self.n, self.n, list(np.shape(cweights))))
+        return w
+
+    def charfn_batch(self, cweights, lk=None, pl16=None, seq_members=None, flags=None, want_cf=True, want_loglik=True):
+        """Complex per-member weights: -> (cf[S,M] complex128, loglik[S] float64, status[S] uint8).
+        cweights complex [M, N, 3] (1 .. MAX_CWEIGHTS tables; a single [N, 3] table, or real [M, N, 3, 2] = (re, im), is
+        accepted; finite): cf[s, m] = E[prod_p w_m[p][g_p] | data] = Z(lk * w_m) / Z(lk) under the exact joint posterior, to
+        1e-12 ABSOLUTE times Z(lk * |w_m|) / Z(lk) (1 for unit-modulus weights); loglik is evidence_batch's.  With
+        count_tables() the characteristic function of a count, which count_from_cf() turns into its distribution
+        (count_batch does both).  Input is either lk [S,N,3] float64 or pl16 [S,n_seq,3] uint16 in VCF column order
+        (seq_members: their PED indices).  want_* False: not computed, None."""
+        return self._charfn(None, cweights, lk, pl16, seq_members, flags, want_cf, want_loglik)
+
+    def charfn_prior_batch(self, prior, cweights, lk=None, pl16=None, seq_members=None, flags=None, want_cf=True, want_loglik=True):
+        """charfn_batch with the founders' genotype prior given per site (prior [S, 6] as for bn_prior_batch; of the flags only
+        FLAG_CHRX is read).  Rows equal to the model's constants give charfn_batch's bits."""
+        return self._charfn(prior, cweights, lk, pl16, seq_members, flags, want_cf, want_loglik)
+
+    def _charfn(self, prior, cweights, lk, pl16, seq_members, flags, want_cf, want_loglik):
+        w = self._cweights(cweights)
+        outs = lambda s: (np.empty((s, w.shape[0], 2)) if want_cf else None, np.empty(s) if want_loglik else None)
+        cf, ll, st = self._side_host("charfn", prior, lk, pl16, seq_members, flags, outs, (_p(w, C.c_double), w.shape[0]))
+        return (None if cf is None else cf.view(np.complex128)[..., 0]), ll, st
+
+    def charfn_device(self, n_sites, d_cweights, n_tables, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_cf=0, d_loglik=0, d_status=0,
+                      stream=0):
+        """charfn_batch on resident buffers (raw device pointers as ints; 0 = not given), d_cweights [n_tables, N, 3, 2] float64
+        among them (unchecked; it must stay unchanged until the kernel has run), d_cf [n_sites, n_tables, 2]; enqueues on
+        `stream` and returns."""
+        self._side_device("charfn", n_sites, d_lk, d_pl16, seq_members, d_flags, None, d_cf, d_loglik, d_status, stream,
+                          (d_cweights or None, int(n_tables)))
+
+    def charfn_prior_device(self, n_sites, d_prior, d_cweights, n_tables, d_lk=0, d_pl16=0, seq_members=(), d_flags=0, d_cf=0,
+                            d_loglik=0, d_status=0, stream=0):
+        """charfn_prior_batch on resident buffers (raw device pointers as ints; 0 = not given); enqueues on `stream` and returns."""
+        self._side_device("charfn", n_sites, d_lk, d_pl16, seq_members, d_flags, d_prior or 0, d_cf, d_loglik, d_status, stream,
+                          (d_cweights or None, int(n_tables)))
+
+    def count_batch(self, scores, lk=None, pl16=None, seq_members=None, flags=None, prior=None):
+        """The exact posterior distribution of the count sum_p scores[p][g_p] (count_scores()): -> (dist[S, D + 1] float64,
+        loglik[S], status[S]), dist[s, k] = P(count = k | data), each to 1e-12 absolute (count_from_cf's rules: not
+        renormalised, NaN where status != 0).  One charfn_batch call (prior [S, 6] given: charfn_prior_batch) at the
+        D // 2 + 1 frequencies of count_tables(scores) and an inverse DFT on the host."""
+        tables, D = count_tables(scores)
+        cf, ll, st = self._charfn(prior, tables, lk, pl16, seq_members, flags, True, True)
+        return count_from_cf(cf, D), ll, st
 
     def allele_tables(self):
         """The allele-level transmission rows origin_batch uses: -> [2 chrX, 2 child sex (0 son, 1 daughter), 2 parent (0 mother,

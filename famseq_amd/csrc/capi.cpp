@@ -1281,6 +1281,37 @@ extern "C" int famseq_weight_prior_batch_device(famseq_ctx *c, int64_t n_sites, 
                     {d_wt_loglik, d_loglik, d_status, stream}, {d_weights, n_weights});
 }
 
+// ---- complex per-member weights: the weight entries with complex tables, two doubles out per table and site ---------------------
+
+extern "C" int famseq_charfn_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                                   int32_t n_seq, const uint8_t *flags, const double *cweights, int32_t n_tables, double *cf,
+                                   double *loglik, uint8_t *status) {
+  return side_entry(c, SIDE_CHARFN, 1, false, false, {n_sites, lk, pl16, seq_members, n_seq, flags},
+                    {cf, loglik, status}, {cweights, n_tables});
+}
+
+extern "C" int famseq_charfn_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                          const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_cweights,
+                                          int32_t n_tables, double *d_cf, double *d_loglik, uint8_t *d_status, void *stream) {
+  return side_entry(c, SIDE_CHARFN, 1, false, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags},
+                    {d_cf, d_loglik, d_status, stream}, {d_cweights, n_tables});
+}
+
+extern "C" int famseq_charfn_prior_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16,
+                                         const int32_t *seq_members, int32_t n_seq, const uint8_t *flags, const double *prior,
+                                         const double *cweights, int32_t n_tables, double *cf, double *loglik, uint8_t *status) {
+  return side_entry(c, SIDE_CHARFN, 1, true, false, {n_sites, lk, pl16, seq_members, n_seq, flags, prior},
+                    {cf, loglik, status}, {cweights, n_tables});
+}
+
+extern "C" int famseq_charfn_prior_batch_device(famseq_ctx *c, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                                const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                                const double *d_cweights, int32_t n_tables, double *d_cf, double *d_loglik,
+                                                uint8_t *d_status, void *stream) {
+  return side_entry(c, SIDE_CHARFN, 1, true, true, {n_sites, d_lk, d_pl16, seq_members, n_seq, d_flags, d_prior},
+                    {d_cf, d_loglik, d_status, stream}, {d_cweights, n_tables});
+}
+
 // ---- max-marginals and the runner-up of the joint call: the MAP entries with a row per member in the place of one genotype ------
 
 extern "C" int famseq_maxmarg_batch(famseq_ctx *c, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,

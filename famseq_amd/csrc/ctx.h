@@ -56,7 +56,7 @@ struct DevBuf {
 };
 
 // A generated (per-pedigree) kernel a context may hold.  The kinds, and how each is made: kernel_spec in kernels.cpp; the side
-// products' kinds (K_TRIO .. K_MAXMARG_PRIOR) are the rows of side_table() below.
+// products' kinds (K_TRIO .. K_CHARFN_PRIOR) are the rows of side_table() below.
 enum KernelKind {
   K_LANE = 0,  // K_LANE + d: the enumeration with 3^d lanes per site; d = 0 (one lane per site) serves large batches,
                // d = 1..kEnumMaxGroupDigits batches too small to give every lane of the chip a site (compiled on first use of each d)
@@ -87,6 +87,8 @@ enum KernelKind {
   K_WEIGHT_PRIOR,                                  // ... with the founders' prior per site
   K_MAXMARG,                                       // max-marginals and the runner-up: the max pass in both directions
   K_MAXMARG_PRIOR,                                 // ... with the founders' prior per site
+  K_CHARFN,                                        // count characteristic function: the real sum pass, then a complex one per weight table
+  K_CHARFN_PRIOR,                                  // ... with the founders' prior per site
   K_LANE_BULK,  // the one-lane-per-site enumeration in the outer-leaf plan (lane variant 8 + K_LANE's block shape and fencing): serves
                 // large batches where that text differs from K_LANE's (kernels.cpp, bulk_serves); no pick, no contest of its own
   K_COUNT
@@ -172,7 +174,7 @@ struct ExtraSpec {
 // A side product of the sum-product engine: a generated kernel that takes the common argument list and writes two outputs per
 // site and a status byte, in a plain form and in one that reads the founders' prior per site.  Everything its ABI entries, its
 // prebuild options, its plan keys and its loader differ in is one row of side_table() (kernels.cpp).
-enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_SAMPLE, SIDE_AF, SIDE_RELABEL, SIDE_MUTRATE, SIDE_ORIGIN, SIDE_WEIGHT, SIDE_MAXMARG, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
+enum SideId { SIDE_TRIO, SIDE_MAP, SIDE_EVID, SIDE_LOO, SIDE_PATTERN, SIDE_SAMPLE, SIDE_AF, SIDE_RELABEL, SIDE_MUTRATE, SIDE_ORIGIN, SIDE_WEIGHT, SIDE_MAXMARG, SIDE_CHARFN, SIDE_COUNT };  // (also the index of its staging buffers, famseq_ctx::side_slots)
 struct SideProduct {
   const char *stem;   // "trio": the entry points famseq_trio[_prior], the options trio[_prior]_kernels, the plan keys trio[_prior]_*
   const char *what;   // load_or_fail's message starts "[site priors, ]<what> (sum-product engine): "
@@ -317,6 +319,9 @@ void rate_tables(const Model &m, const double *rates, int32_t n_rates, double *t
 // The origin kernels' precondition: the model's three transmission tables are, bit for bit, famseq_transmission_tables(mu) for
 // mu = pcp2Xm[18] (c->origin_mrate).  0, or FAMSEQ_E_ARG with its message; asks nothing of a device.
 int origin_model(famseq_ctx *c);
+// 0, or FAMSEQ_E_ARG with the engine's message where it does not serve the context's pedigree: the characteristic-function
+// entries' ExtraSpec::precondition, which says so before the device is asked for
+int charfn_served(famseq_ctx *c);
 // ... the same question of a model alone: true and the rate in *mu, or false; changes nothing
 bool origin_rate(const Model &m, double *mu);
 // The lane kinds and both call-path forms: false when the kernel is unavailable, which is remembered and said once on

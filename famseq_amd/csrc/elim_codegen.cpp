@@ -25,6 +25,7 @@
 #include <functional>
 #include <map>
 #include <numeric>
+#include <set>
 #include <sstream>
 #include <stdexcept>
 #include <vector>
@@ -478,6 +479,21 @@ class Emitter {
     return pass_loop(before.str(), inside.str(), counter, per_pass);
   }
 
+  // Exact count distributions (famseq_charfn): the sum pass over complex per-member weights.  Pass 0 is the real sum pass on the
+  // rows as they are (sum_pass(): Zp_, then `pass0`), in a scope of its own in front of the loop; passes 1 .. last_ are one
+  // `#pragma unroll 1` loop around the complex pass (complex_pass(): Zp_r / Zp_i, then `per_pass`), entered only where pass 0
+  // did not fail the site.  Pass m takes member p's entry g as the pair (l * w_re, l * w_im), w = cw[m - 1][p][g] — two rounded
+  // multiplications, formed where the member's local factor is (in registers under the lean threshold, at each use from it on).
+  // The table is read where it lies, through cwp, a wave-uniform pointer (the pass number through readfirstlane, member,
+  // genotype and part constants of the text), as weight_body reads wtp: the entries arrive by scalar loads.
+  std::string charfn_body(const std::string &counter, const std::string &pass0, const std::string &per_pass) {
+    const std::string first = "      {\n" + sum_pass() + pass0 + "      }\n";
+    return first + "      if (!bn_fail) {\n#pragma unroll 1\n      for (int " + counter + " = 1; " + counter + " <= last_; ++" + counter + ") {\n" +
+           "      const int pu_ = __builtin_amdgcn_readfirstlane(" + counter + ");\n"
+           "      const double *cwp = cw_g + (long)(pu_ - 1) * CW6;\n" +
+           complex_pass() + per_pass + "      }\n      }\n";
+  }
+
   // The founders' allele frequency by maximum likelihood (famseq_af): EM on q, every step one sum pass and the founders' marginals
   // under the Hardy-Weinberg rows of the step's q, all steps on one read of the site's rows.  The loop is `#pragma unroll 1`
   // over it_ = -1 .. n_it_ and its text stands once whatever n_it_ is: pass -1 runs at q = 0 (the rows (1, 0, 0) exactly) and keeps
@@ -910,6 +926,227 @@ class Emitter {
       if (c != skip) e = e.empty() ? sum + num(c) : "(" + e + " * " + sum + num(c) + ")";
     return e;
   }
+
+  // ---- The complex sum pass (charfn_body): the sum pass's messages with member p's likelihood entry the complex number
+  // l * w.  The third arithmetic beside the sum pass's and the max pass's: the same three message kinds on the same graph, their
+  // names prefixed "z", every value a pair of doubles <name>r / <name>i — or one double <name>, where it is real whatever the
+  // weights are: a cut member's indicator and what is made of real values alone (zreal_).  The transmission entries, the founders'
+  // priors and the 1e7 scales are real.  A product of two pairs is (a c - b d, a d + b c), of a real and a pair componentwise; a
+  // sum, and an fma chain with a real T, componentwise — each component the statement the real pass has, in its order.  So every
+  // operation is even (real parts) or odd (imaginary parts) in the imaginary parts: a conjugate table gives the conjugate, and
+  // with imaginary parts of +0.0 and real parts >= 0 the imaginary parts stay +0.0 and the real parts are the real pass's bits on
+  // the rows l * w_re (b d is +0.0 and x - 0.0 is x).  A product of more than two factors goes left to right through
+  // temporaries (zt<id>), so that no operand's text stands more than twice.
+  struct Cx {
+    std::string re, im;  // im empty: a real value
+    bool bind = false;   // an expression that costs a read at each mention (lean local factors): named before it is used twice
+    bool real() const { return im.empty(); }
+  };
+  Cx zval(const std::string &n, const std::string &idx) const {
+    const std::string s = n + "_" + idx;
+    return zreal_.count(n) ? Cx{s, ""} : Cx{s + "r", s + "i", zbind_.count(n) != 0};
+  }
+  void zdef(const std::string &s, const Cx &v) {
+    if (v.real()) o_ << "      const double " << s << " = " << v.re << ";\n";
+    else o_ << "      const double " << s << "r = " << v.re << ", " << s << "i = " << v.im << ";\n";
+  }
+  Cx ztemp(const Cx &v) {
+    const std::string t = "zt" + num(uid_++);
+    zdef(t, v);
+    return v.real() ? Cx{t, ""} : Cx{t + "r", t + "i"};
+  }
+  Cx zmul(Cx a, Cx b) {
+    if (a.real() && b.real()) return {a.re + " * " + b.re, ""};
+    if (a.bind && !b.real()) a = ztemp(a);
+    if (b.bind) b = ztemp(b);
+    if (a.real()) return {a.re + " * " + b.re, a.re + " * " + b.im};
+    if (b.real()) return {a.re + " * " + b.re, a.im + " * " + b.re};
+    return {"(" + a.re + " * " + b.re + " - " + a.im + " * " + b.im + ")", "(" + a.re + " * " + b.im + " + " + a.im + " * " + b.re + ")"};
+  }
+  // the factors' product, left to right
+  Cx zprod(const std::vector<Cx> &f) {
+    if (f.empty()) return {"1.0", ""};
+    Cx acc = f[0];
+    for (size_t k = 1; k < f.size(); ++k) {
+      if (k > 1) acc = ztemp(acc);
+      acc = zmul(acc, f[k]);
+    }
+    return acc;
+  }
+  // (a + b) + c
+  static Cx zsum3(const Cx &a, const Cx &b, const Cx &c) {
+    Cx s{"(" + a.re + " + " + b.re + ") + " + c.re, ""};
+    if (!a.real()) s.im = "(" + a.im + " + " + b.im + ") + " + c.im;
+    return s;
+  }
+  // whether every one of the names is real
+  bool zall_real(const std::vector<std::string> &names) const {
+    for (const std::string &n : names)
+      if (!zreal_.count(n)) return false;
+    return true;
+  }
+
+  // member p's local factor zc<p>_g: loc()'s, on the weighted pair
+  std::string zloc(int p) {
+    const std::string n = "zc" + num(p);
+    if (once(n)) {
+      bool scale = false;
+      for (int s : g_.scaled) scale |= s == p;
+      const bool lean = lean_ || p >= lean_from_;
+      if (lean) zbind_.insert(n);
+      for (int g = 0; g < 3; ++g)
+        for (int part = 0; part < 2; ++part) {
+          std::string e = "(l" + num(p) + "_" + num(g) + " * cwp[" + num(6 * p + 2 * g + part) + "])";
+          if (m_.mother[p] < 0) e = "(" + founder_prior(p, g) + " * " + e + ")";
+          if (scale) e = "(10000000.0 * " + e + ")";
+          const std::string v = n + "_" + num(g) + (part ? "i" : "r");
+          if (lean) o_ << "#define " << v << " " << e << "\n";
+          else o_ << "      const double " << v << " = " << e << ";\n";
+        }
+      if (!lean) fence(2);
+    }
+    return n;
+  }
+  // `name`_g = the product of the messages `in`, per genotype
+  void zproducts(const std::string &name, const std::vector<std::string> &in) {
+    if (zall_real(in)) zreal_.insert(name);
+    for (int g = 0; g < 3; ++g) {
+      std::vector<Cx> f;
+      for (const std::string &i : in) f.push_back(zval(i, num(g)));
+      zdef(name + "_" + num(g), zprod(f));
+    }
+  }
+  std::string zvar2fac(int p, int F) {
+    const std::string n = "zv" + num(p) + "f" + num(F);
+    if (!once(n)) return n;
+    if (g_.is_cut(p)) {
+      zreal_.insert(n);
+      for (int g = 0; g < 3; ++g) o_ << "      const double " << n << "_" << g << " = a" << p << " == " << g << " ? 1.0 : 0.0;\n";
+      return n;
+    }
+    std::vector<std::string> in = {zloc(p)};
+    for (int F2 : g_.nb[p])
+      if (F2 != F) in.push_back(zfac2var(F2, p));
+    zproducts(n, in);
+    return n;
+  }
+  // T * x + acc, componentwise (acc empty: T * x)
+  static Cx zfma(const std::string &T, const Cx &x, const Cx &acc) {
+    auto part = [&](const std::string &xv, const std::string &a) { return a.empty() ? T + " * " + xv : "__builtin_fma(" + T + ", " + xv + ", " + a + ")"; };
+    return {part(x.re, acc.re), x.real() ? "" : part(x.im, acc.im)};
+  }
+  std::string zchild_sum(int F, int c) {
+    const std::string x = zvar2fac(c, F);
+    const std::string n = "za" + num(uid_++);
+    if (zreal_.count(x)) zreal_.insert(n);
+    for (int gm = 0; gm < 3; ++gm)
+      for (int gf = 0; gf < 3; ++gf)
+        zdef(n + "_" + num(gm) + num(gf),
+             zfma(T(c, 2, gm, gf), zval(x, "2"), zfma(T(c, 1, gm, gf), zval(x, "1"), zfma(T(c, 0, gm, gf), zval(x, "0"), {}))));
+    fence(2);
+    return n;
+  }
+  std::string zfac2var(int F, int t) {
+    const std::string n = "zf" + num(F) + "v" + num(t);
+    if (!once(n)) return n;
+    const Family &fam = g_.fam[F];
+    std::vector<std::string> in;  // pair_product's factors: the parents' messages present, the other children's summaries
+    if (t != fam.mo) in.push_back(zvar2fac(fam.mo, F));
+    if (t != fam.fa) in.push_back(zvar2fac(fam.fa, F));
+    const size_t n_parents = in.size();
+    for (int c : fam.kids)
+      if (c != t) in.push_back(zchild_sum(F, c));
+    const std::string C = n + "w";
+    if (zall_real(in)) zreal_.insert(C), zreal_.insert(n);
+    for (int gm = 0; gm < 3; ++gm)
+      for (int gf = 0; gf < 3; ++gf) {
+        std::vector<Cx> f;
+        size_t k = 0;
+        if (t != fam.mo) f.push_back(zval(in[k++], num(gm)));
+        if (t != fam.fa) f.push_back(zval(in[k++], num(gf)));
+        for (k = n_parents; k < in.size(); ++k) f.push_back(zval(in[k], num(gm) + num(gf)));
+        zdef(C + "_" + num(gm) + num(gf), zprod(f));
+      }
+    for (int g = 0; g < 3; ++g) {
+      auto c = [&](int gm, int gf) { return zval(C, num(gm) + num(gf)); };
+      Cx v;
+      if (t == fam.mo) v = zsum3(c(g, 0), c(g, 1), c(g, 2));
+      else if (t == fam.fa) v = zsum3(c(0, g), c(1, g), c(2, g));
+      else
+        for (int gm = 0; gm < 3; ++gm)
+          for (int gf = 0; gf < 3; ++gf) {
+            const bool first = gm == 0 && gf == 0;
+            v = zfma(T(t, g, gm, gf), c(gm, gf), first ? Cx{} : v);
+            if (first) v.re = "(" + v.re + ")", v.im = v.im.empty() ? "" : "(" + v.im + ")";
+          }
+      zdef(n + "_" + num(g), v);
+    }
+    fence(1);
+    return n;
+  }
+  void zmarginal(int p) {
+    if (!once("zm" + num(p))) return;
+    std::vector<std::string> in = {zloc(p)};
+    for (int F : g_.nb[p]) in.push_back(zfac2var(F, p));
+    zproducts("zm" + num(p), in);
+  }
+  // zZ<c>_0: the total weight of component c
+  std::vector<Cx> zcomponent_sums() {
+    std::vector<Cx> sums;
+    for (size_t c = 0; c < g_.rep.size(); ++c) {
+      const std::string m = "zm" + num(g_.rep[c]), n = "zZ" + num((int)c);
+      zmarginal(g_.rep[c]);
+      if (zreal_.count(m)) zreal_.insert(n);
+      zdef(n + "_0", zsum3(zval(m, "0"), zval(m, "1"), zval(m, "2")));
+      sums.push_back(zval(n, "0"));
+    }
+    return sums;
+  }
+  // One complex pass inside charfn_body's loop: sum_pass()'s statements, which leave the pass's total weight in Zp_r / Zp_i.
+  // Leaves o_ empty.
+  std::string complex_pass() {
+    auto named = [&](const std::string &n, Cx v) {  // the total as a pair whatever it is made of
+      if (v.real()) v.im = "0.0";
+      zdef(n, v);
+    };
+    std::string pass;
+    if (g_.cut.empty()) {
+      fence(1);
+      named("Zp_", zprod(zcomponent_sums()));
+      fence(1);
+      pass = o_.str();
+    } else {
+      int total = 1;
+      for (size_t k = 0; k < g_.cut.size(); ++k) total *= 3;
+      std::ostringstream head;
+      head << "      double Zt_r = 0, Zt_i = 0;\n#pragma unroll 1\n      for (int as_ = 0; as_ < " << total << "; ++as_) {\n";
+      int div = 1;
+      for (int k : g_.cut) {
+        head << "      const int a" << k << " = (as_ / " << div << ") % 3;\n";
+        div *= 3;
+      }
+      std::vector<Cx> f = {{"10000000.0", ""}};
+      for (int k : g_.cut) {
+        const std::string c = zloc(k), lam = "zlam" + num(k);
+        auto pick = [&](const char *part) {
+          return "a" + num(k) + " == 0 ? " + c + "_0" + part + " : (a" + num(k) + " == 1 ? " + c + "_1" + part + " : " + c + "_2" + part + ")";
+        };
+        zdef(lam, {pick("r"), pick("i")});
+        f.push_back({lam + "r", lam + "i"});
+      }
+      named("zLam", zprod(f));
+      f = {{"zLamr", "zLami"}};
+      for (const Cx &z : zcomponent_sums()) f.push_back(z);
+      named("zWall", zprod(f));
+      o_ << "      Zt_r = Zt_r + zWallr; Zt_i = Zt_i + zWalli;\n";
+      fence(1);
+      pass = head.str() + o_.str() + "      }\n      const double Zp_r = Zt_r, Zp_i = Zt_i;\n";
+    }
+    o_.str("");
+    return pass;
+  }
+  std::set<std::string> zreal_;  // the complex pass's names that hold one double
+  std::set<std::string> zbind_;  // ... and those that are macros over volatile reads
 
   // member p's unnormalised max-marginal row xm<p>_g (maxmarg_body): local * the max-pass messages of the adjacent families
   std::string max_marginal(int p) {
@@ -1643,24 +1880,35 @@ struct PassProduct {
   const char *ll;                 // pass 0's log10 Z without the reference's 1e7: loglik
   const char *result = nullptr;   // what a later pass stores, of its Zp_; none: its log10 Z as pass 0's, not clamped
   bool z0 = false;                // pass 0's Zp_ is kept in Z0_ for `result`
+  const char *result_im = nullptr;  // where given: a pass's result is two doubles, `result` and this one (16 bytes per pass)
 };
 // Fills in the shell's side of product p — the clamp (d.prologue), the output pointer and last_ (site_decls), the variables
 // (site_vars), NaN for a failed site and the loglik store (epilogue) — and returns the `per_pass` text of its body: pass 0
 // fails the site and leaves the loop where Zp_ is not a positive finite number, else keeps loglik; a later pass stores.
-// `digits`: Emitter::evidence_scale_digits().
-std::string pass_product(const PassProduct &p, int digits, LaneShell &d) {
+// `digits`: Emitter::evidence_scale_digits().  With `pass0`: that pass's check and keep go there (it fails the site without a
+// loop to leave) and the later passes' store alone is returned.
+std::string pass_product(const PassProduct &p, int digits, LaneShell &d, std::string *pass0 = nullptr) {
   const std::string out = p.out, n = p.n, ct = p.counter, ll = p.ll, log = "log10(Zp_) - " + std::to_string(digits) + ".0";
+  const std::string wide = p.result_im ? "2 * " : "", ok = "Zp_ > 0 && Zp_ <= 1.79769313486231570815e308";
+  const std::string keep = (p.z0 ? "Z0_ = Zp_; " : "") + ll + " = " + log + ";";
   d.prologue = clamp_count(n, p.n_arg, p.n_max);
-  d.site_decls = "    double *" + out + " = " + p.out_arg + " ? " + p.out_arg + " + site * " + n + " : nullptr;\n"
+  d.site_decls = "    double *" + out + " = " + p.out_arg + " ? " + p.out_arg + " + site * " + (p.result_im ? "(2 * " + n + ")" : n) + " : nullptr;\n"
                  "    const int last_ = " + out + " ? " + n + " : 0;\n";
   d.site_vars = "    double " + ll + " = kNaN" + (p.z0 ? ", Z0_ = 0" : "") + ";\n";
-  d.epilogue = fail_block("      " + ll + " = kNaN;\n" + fill(out, n)) +
+  d.epilogue = fail_block("      " + ll + " = kNaN;\n" + fill(out, wide + n)) +
                "    if (loglik_g) __builtin_nontemporal_store(" + ll + ", loglik_g + site);\n" + status_store();
+  const std::string store =
+      p.result_im ? "        __builtin_nontemporal_store(" + std::string(p.result) + ", " + out + " + 2 * (" + ct + " - 1));\n"
+                    "        __builtin_nontemporal_store(" + p.result_im + ", " + out + " + 2 * (" + ct + " - 1) + 1);\n"
+                  : "        __builtin_nontemporal_store(" + (p.result ? p.result : log) + ", " + out + " + (" + ct + " - 1));\n";
+  if (pass0) {  // pass 0 stands apart, in front of a loop over the later passes alone (Emitter::charfn_body)
+    *pass0 = "      if (!(" + ok + ")) bn_fail = true;\n      else { " + keep + " }\n";
+    return store;
+  }
   return "      if (" + ct + " == 0) {\n"
-         "        if (!(Zp_ > 0 && Zp_ <= 1.79769313486231570815e308)) { bn_fail = true; break; }\n"
-         "        " + (p.z0 ? "Z0_ = Zp_; " : "") + ll + " = " + log + ";\n"
-         "      } else {\n"
-         "        __builtin_nontemporal_store(" + (p.result ? p.result : log) + ", " + out + " + (" + ct + " - 1));\n"
+         "        if (!(" + ok + ")) { bn_fail = true; break; }\n"
+         "        " + keep + "\n"
+         "      } else {\n" + store +
          "      }\n";
 }
 
@@ -1914,6 +2162,35 @@ std::string weight_source(const Model &m, int variant, bool site_prior) {
   const PassProduct pass{"wt_ll_g", "wp", "n_weights", "nw_", "MAXWT", "ps_", "wt_l0"};
   Emitter e(m, g, eo);
   d.body = e.weight_body(pass.counter, pass_product(pass, e.evidence_scale_digits(), d));
+  return lane_shell(m, d);
+}
+
+// The characteristic-function kernel: a per-pass product (PassProduct) with the weight kernel's shell and rules, whose later
+// passes are complex (Emitter::charfn_body).  Beyond the common arguments: cw_g[n_tables][N][3][2], one table of complex
+// per-member genotype weights per pass (re, im; whatever they hold: nothing is indexed by them), and n_tables
+// (1 .. FAMSEQ_MAX_CWEIGHTS; the host checks, the kernel clamps).  Outputs per site: cf[n_tables][2] = (Re Z_m / Z0, Im Z_m / Z0),
+// true divisions, Z_m the network's total weight on the rows lk * w_m and Z0 on the rows as they are — not clamped; a Z_m of
+// exactly 0 gives (0.0, 0.0), which is a result — and loglik, famseq_evidence's, from pass 0; either may be null (without cf only
+// pass 0 runs, and cw_g is not read).  Only a Z0 that is not a positive finite number fails the site (status 2).
+// Where the rows live: this product has a lean threshold of its own, 25 members (kCharfnLeanFrom; begin_side's is forty).  The
+// complex messages double the pass's live set, and the register-resident form — rows in registers, a member's weighted pair
+// formed where its local factor is — runs out of registers before forty: without scratch in every variant at 10, 20 and 24
+// members, at 28 the site-prior form spills in every variant (24-128 B per lane) and the plain one in variant 0, at 32 both do
+// (the site-prior form 164-372 B), at 39 every variant of both (84-644 B).  The lean form — rows read from the lane's row at each
+// use, the weights by scalar loads beside them — keeps no scratch in any variant at 21, 32, 39, 40 and 64 members (variants 1-3
+// at two to three waves per SIMD).  profiles/charfn/resources.txt holds both surveys.
+constexpr int kCharfnLeanFrom = 25;
+std::string charfn_source(const Model &m, int variant, bool site_prior) {
+  auto [g, f, eo, d] = begin_side(m, "charfn", "count characteristic function (real sum pass, then a complex sum pass per weight table)", variant, kCharfnVariants, site_prior);
+  d.lean = eo.lean = m.n_members >= env_int("FAMSEQ_CHARFN_LEAN_FROM", kCharfnLeanFrom);  // (the variable: a tuning aid)
+  d.outputs = "double *__restrict__ cf_g, double *__restrict__ loglik_g";
+  d.more_args = ", const double *__restrict__ cw_g, int n_tables";
+  d.defines = "#define MAXCW " + std::to_string(FAMSEQ_MAX_CWEIGHTS) + "\n#define CW6 " + std::to_string(6 * m.n_members) + "\n";
+  const PassProduct pass{"cf_g", "cp", "n_tables", "nt_", "MAXCW", "ps_", "cf_l0", "Zp_r / Z0_", /*z0=*/true, "Zp_i / Z0_"};
+  Emitter e(m, g, eo);
+  std::string pass0;
+  const std::string per_pass = pass_product(pass, e.evidence_scale_digits(), d, &pass0);
+  d.body = e.charfn_body(pass.counter, pass0, per_pass);
   return lane_shell(m, d);
 }
 

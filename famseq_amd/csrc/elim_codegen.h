@@ -131,6 +131,18 @@ constexpr int kWeightVariants = 4;
 // site_prior: famseq_weight_prior, with a trailing `prior` [n_sites][6] behind n_weights (as trio_source's).
 std::string weight_source(const Model &m, int variant, bool site_prior = false);
 
+// The posterior characteristic function of an additive statistic (famseq_charfn_batch).  HIP source of
+// `extern "C" __global__ famseq_charfn(lk, flags, cf, loglik, status, n_sites, tc, lc, cw, n_tables)`: per site and table m
+// cf[m] = (Re Z_m / Z0, Im Z_m / Z0), Z_m the network's total weight with member p's likelihood entry g multiplied by the complex
+// number cw[m][p][g] = (re, im) — every member's, sequenced or not — and Z0 the total weight on the rows as they are (true
+// divisions, nothing clamped); and loglik, famseq_evidence's.  The real sum pass of famseq_evidence once, then a complex sum pass
+// per table on the same read of the site's rows: every message a pair of doubles, the transmission entries, priors and scales
+// real; a pass's weights are read through a wave-uniform pointer.  variant 0..3: the fence levels of famseq_elim's; every
+// variant gives the same bits.  Throws if the engine does not serve the pedigree.
+constexpr int kCharfnVariants = 4;
+// site_prior: famseq_charfn_prior, with a trailing `prior` [n_sites][6] behind n_tables (as trio_source's).
+std::string charfn_source(const Model &m, int variant, bool site_prior = false);
+
 // Phase by transmission (famseq_origin_batch).  HIP source of
 // `extern "C" __global__ famseq_origin(lk, flags, origin, hettx, status, n_sites, tc, lc, al)`: per site and child k
 // (trio_children's order) origin[k][2 a + b], the posterior that the child received allele a (0 ref, 1 alt) from its mother and b

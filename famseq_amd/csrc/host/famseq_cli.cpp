@@ -7,6 +7,7 @@
 //              [-seg dominant|recessive|both -affected ID[,ID...] [-unaffected ID[,ID...]]] [-sample K [-seed S]]
 //              [-afEM T [-afStart X]] [-swapCheck FILE] [-mRateScan FILE [-mRateGrid r1,r2,...]] [-phase] [-mapQ]
 //              [-segPen F0,F1,F2[/F0,F1,F2...] -affected ID[,ID...] [-unaffected ID[,ID...]]]
+//              [-countDist carriers|alleles|homalt [-countOf ID[,ID...]]]
 //   FamSeq LK -lkFile f -pedFile p -output o [-lkType n|log10|ln|PS] [...]
 // Reference behaviour being reproduced (all cites /root/reference/src):
 //   flag parsing + defaults + messages   checkInput.cpp:149-578, 671-1067; FamSeq.cpp:28-156
@@ -225,6 +226,10 @@ struct Options {
   bool rate_scan_given = false, rate_grid_given = false, rate_grid_is_bad = false;
   vector<double> rate_grid = {0, 1e-9, 1e-8, 1e-7, 1e-6, 1e-5, 1e-4, 1e-3};
   string rate_grid_bad;
+  // -countDist carriers|alleles|homalt [-countOf ID[,ID...]]: a PCD key in the INFO column (vcf mode), the exact posterior
+  // distribution of the number of carriers / alt alleles / hom-alt members among the members of -countOf (PED IDs; default all)
+  bool count_given = false, count_of_given = false;
+  string count_kind, count_of;
   string af_tag;     // -afTag KEY: the founders' prior of a line from the allele frequency KEY= of its INFO column (vcf mode)
   bool af_conflict = false;  // both -afTag and -afTagAll were given
   bool af_all = false;  // -afTagAll KEY: -afTag KEY, applied to every field a line prints (DNP, JGT and JP too: may go with -dnm / -map)
@@ -451,6 +456,10 @@ int parse_options(int argc, char **argv, Options &o) {
         for (; got < 3; ++got) o.pen.push_back(0.0);
         at = end + 1;
       }
+    } else if (opt == "countDist" || opt == "countOf") {  // (what may be wrong with either: check_count_dist, with the other side options' checks)
+      // (no value, or one that starts like an option: an empty one, which check_count_dist refuses)
+      (opt == "countDist" ? o.count_given : o.count_of_given) = true;
+      (opt == "countDist" ? o.count_kind : o.count_of) = missing(i + 1) ? "" : argv[++i];
     } else if (opt == "seg" || opt == "affected" || opt == "unaffected") {
       i++;
       if (missing(i)) {
@@ -925,6 +934,62 @@ bool penetrance_tables(const Options &o, const Ped &ped, vector<double> &tables)
     for (int i = 0; i < ped.n(); ++i)
       for (int g = 0; g < 3; ++g) tables.push_back(role[i] == 1 ? o.pen[3 * m + g] : (role[i] == 2 ? 1.0 - o.pen[3 * m + g] : 1.0));
   return true;
+}
+
+// -countDist: the score of each genotype of a counted member, by kind; null for a kind it does not know
+const int *count_kind_scores(const string &kind) {
+  static const int carriers[3] = {0, 1, 1}, alleles[3] = {0, 1, 2}, homalt[3] = {0, 0, 1};
+  return kind == "carriers" ? carriers : (kind == "alleles" ? alleles : (kind == "homalt" ? homalt : nullptr));
+}
+
+// -countDist: which members are counted (-countOf's PED IDs; without it everyone), counted[i] of member i (PED order).  false with
+// a message: an ID the PED file does not hold, an ID named twice.
+bool counted_members(const Options &o, const Ped &ped, vector<uint8_t> &counted) {
+  counted.assign(ped.n(), o.count_of_given ? 0 : 1);
+  if (!o.count_of_given) return true;
+  if (o.count_of.empty()) {
+    std::cout << "-countOf takes the members to count, ID[,ID...] (PED IDs): the list is empty." << std::endl;
+    return false;
+  }
+  std::istringstream in(o.count_of);
+  string tok;
+  while (std::getline(in, tok, ',')) {
+    char *end = nullptr;
+    const long id = std::strtol(tok.c_str(), &end, 10);
+    int at = -1;
+    for (int i = 0; i < ped.n() && !tok.empty() && *end == 0; ++i)
+      if (ped.id[i] == id) at = i;
+    if (at < 0) {
+      std::cout << "-countOf: \"" << tok << "\" is not an individual ID of the PED file." << std::endl;
+      return false;
+    }
+    if (counted[at]) {
+      std::cout << "-countOf: individual " << tok << " is named twice." << std::endl;
+      return false;
+    }
+    counted[at] = 1;
+  }
+  return true;
+}
+
+// -countDist: D, the largest value the count reaches, and the tables of its characteristic function at the frequencies
+// j = 0 .. (D + 1) / 2, [n_tables][N][3][2] in PED order: omega^(j * score), omega = exp(2 pi i / (D + 1)), the exponent reduced
+// mod D + 1 in integers.  (main has checked the options: kind and members are good here.)
+int count_tables(const Options &o, const Ped &ped, vector<double> &tables) {
+  vector<uint8_t> counted;
+  const int *score = count_kind_scores(o.count_kind);
+  if (!score || !counted_members(o, ped, counted)) return -1;
+  int D = 0;
+  for (int i = 0; i < ped.n(); ++i) D += counted[i] ? score[2] : 0;
+  const int M = D + 1;
+  tables.clear();
+  for (int j = 0; j <= M / 2; ++j)
+    for (int i = 0; i < ped.n(); ++i)
+      for (int g = 0; g < 3; ++g) {
+        const double x = 2.0 * M_PI * double((long(j) * (counted[i] ? score[g] : 0)) % M) / M;
+        tables.push_back(std::cos(x)), tables.push_back(std::sin(x));
+      }
+  return D;
 }
 
 // -afTag: the allele frequency of a line, the first value of KEY= in its INFO column; < 0 where there is none to use (no such
@@ -1483,11 +1548,11 @@ struct Part {
 // ---- side outputs: what -dnm, -map, -siteQ, -loo, -sample, -seg and -afEM add to a line, one row of kSide each; -swapCheck and
 // ---- -mRateScan, which add nothing to any line and write a report of their own behind the last site (SideRow::report), are rows too
 // The order is the one main checks them and prints its notices in; it is also the order of the fields in a sample column (DNP,
-// JGT:JP, LOP:LOF, SGT, PGT:PGP, JGQ) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL, then PSL, then JP2).  Header
+// JGT:JP, LOP:LOF, SGT, PGT:PGP, JGQ) and of the keys joined to the INFO column (FQ;FLL, then PSD;PSR, then FAF;FAL, then PSL, then JP2, then PCD).  Header
 // lines have their own order.
-enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap, kRateScan, kPhase, kSegPen, kMapQ };
-constexpr int kSides = kMapQ + 1;
-const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap, kRateScan, kPhase, kSegPen, kMapQ};
+enum SideId { kDnm, kMap, kSiteQ, kLoo, kSample, kSeg, kAfEm, kSwap, kRateScan, kPhase, kSegPen, kMapQ, kCountDist };
+constexpr int kSides = kCountDist + 1;
+const SideId kHeaderOrder[kSides] = {kDnm, kMap, kLoo, kSample, kSeg, kSiteQ, kAfEm, kSwap, kRateScan, kPhase, kSegPen, kMapQ, kCountDist};
 
 // One side output of a block: the two arrays its C entry fills ([site][...], read as the entry's own types) and its status per site.
 struct SideOut {
@@ -1555,6 +1620,10 @@ struct VcfRun {
   // -segPen: the models' weight tables [n_models][N][3], and the all-ones likelihood rows of the null call (grown to the largest
   // block: the phenotypes' probability under the pedigree and the founders' prior alone, by the block's flags and priors)
   vector<double> pen_tables, ones_lk;
+  // -countDist: the count's largest value D, the complex weight tables of its characteristic function at the frequencies
+  // 0 .. (D + 1) / 2 (count_tables) and the inverse transform's cos / sin of 2 pi r / (D + 1), r = 0 .. D
+  int count_D = 0;
+  vector<double> count_cw, count_cos, count_sin;
   // -swapCheck: the exchange of every two sequenced samples, in VCF column order, as assignment rows [pair][N] (PED order), and
   // what the sites so far add up to, in file order: per pair the sum of alt_loglik - loglik over the used sites where alt_loglik
   // is finite and the number of used sites where it is -inf; the used and the skipped (status != 0) sites, the used sites' loglik
@@ -1607,6 +1676,13 @@ struct VcfRun {
     // (main has checked -seg's options: this cannot fail here)
     if (!o.seg.empty() && !o.pack_mode && !segregation_masks(o, ped, seg_masks, seg_keys)) return false;
     if (o.pen_given && !o.pack_mode && !penetrance_tables(o, ped, pen_tables)) return false;
+    if (o.count_given && !o.pack_mode) {
+      if ((count_D = count_tables(o, ped, count_cw)) < 0) return false;
+      for (int r = 0; r <= count_D; ++r) {
+        const double x = 2.0 * M_PI * r / (count_D + 1);
+        count_cos.push_back(std::cos(x)), count_sin.push_back(std::sin(x));
+      }
+    }
     for (int k = 0; k < 3; ++k) {
       model_rows[0][k] = m.p.genoProbN[k], model_rows[0][3 + k] = m.p.genoProbXN[k];
       model_rows[1][k] = m.p.genoProbK[k], model_rows[1][3 + k] = m.p.genoProbXK[k];
@@ -1984,6 +2060,13 @@ struct VcfRun {
       case kSeg: rc = entry(famseq_pattern_batch, famseq_pattern_prior_batch, seg_masks.data(), (int32_t)seg_keys.size(), a, none, st); break;
       case kSwap: return call_swap(sl, so, lk, pl16);
       case kSegPen: rc = call_seg_pen(sl, so, lk, pl16); break;
+      case kCountDist: {
+        const int32_t T = (count_D + 1) / 2 + 1;
+        vector<double> cf(sl.n_sites * size_t(T) * 2);
+        rc = entry(famseq_charfn_batch, famseq_charfn_prior_batch, count_cw.data(), T, cf.data(), none, st);
+        if (rc == 0) count_distributions(sl, so, cf);
+        break;
+      }
       case kPhase:
         so.flags = sl.io.flags;
         rc = entry(famseq_origin_batch, famseq_origin_prior_batch, n_kids ? a : none, none, st);
@@ -2032,6 +2115,34 @@ struct VcfRun {
       st[s] = 0;
     }
     return 0;
+  }
+  // -countDist: the inverse DFT of a block's characteristic functions cf[site][j][2], j = 0 .. M / 2 with M = D + 1, the missing
+  // frequencies the conjugates of those given: so.a[s * M + k] = p_k = (1 / M) sum_j Re(phi_j omega^(-j k)), (D + 1)^2 operations
+  // per site.  A value in [-1e-12, 0) — rounding below an exact 0, within the entry's absolute bar — becomes 0.0; nothing is
+  // renormalised.  A failed site's row is NaN and, like -segPen's, leaves no status but 0: it prints "PCD=.".
+  void count_distributions(Slot &sl, SideOut &so, const vector<double> &cf) {
+    const size_t M = size_t(count_D) + 1, T = M / 2 + 1;
+    on_threads(sl.n_parts, [&](int t) {
+      for (size_t s = sl.n_sites * t / sl.n_parts; s < sl.n_sites * (t + 1) / sl.n_parts; ++s) {
+        double *p = so.a.data() + s * M;
+        if (so.status[s] != 0) {
+          std::fill(p, p + M, std::numeric_limits<double>::quiet_NaN());
+          so.status[s] = 0;
+          continue;
+        }
+        const double *phi = cf.data() + s * T * 2;
+        for (size_t k = 0; k < M; ++k) {
+          double sum = 0;
+          for (size_t j = 0; j < M; ++j) {
+            const size_t jj = j < T ? j : M - j, r = j * k % M;
+            const double re = phi[2 * jj], im = j < T ? phi[2 * jj + 1] : -phi[2 * jj + 1];
+            sum += re * count_cos[r] + im * count_sin[r];
+          }
+          const double v = sum / double(M);
+          p[k] = v < 0 && v >= -1e-12 ? 0.0 : v;
+        }
+      }
+    });
   }
   // -swapCheck: the pairs in groups of at most FAMSEQ_MAX_RELABEL per call, each group's columns summed up over the block's
   // sites in file order behind its call (a pair's sum is its own: the order of the pairs does not enter).  The first group also
@@ -2391,8 +2502,21 @@ inline void put_mapq(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s,
   out.num(second == 0 ? 99999.0 : std::fabs(-10.0 * std::log10(second / m[best])));
 }
 
+// -countDist: the D + 1 probabilities of the count, printed as FLL's value is; "." where the site failed
+// (VcfRun::count_distributions)
+inline void put_pcd(TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t) {
+  const size_t M = size_t(r.count_D) + 1;
+  out.put("PCD=", 4);
+  if (std::isnan(so.a[s * M])) return out.ch('.');
+  for (size_t k = 0; k < M; ++k) {
+    if (k) out.ch(',');
+    out.num(so.a[s * M + k]);
+  }
+}
+
 [[gnu::always_inline]] inline void put_side(SideId id, TextBuf &out, const VcfRun &r, const SideOut &so, size_t s, size_t j) {
   switch (id) {
+    case kCountDist: return put_pcd(out, r, so, s, j);
     case kMapQ: return put_mapq(out, r, so, s, j);
     case kSegPen: return put_psl(out, r, so, s, j);
     case kPhase: return put_phase(out, r, so, s, j);
@@ -2435,6 +2559,29 @@ bool check_seg_pen(const Options &o, const Ped &ped) {
   }
   vector<double> tables;
   return penetrance_tables(o, ped, tables);
+}
+
+// -countDist's own: -countOf without it, an unknown kind, an ID the PED file does not hold or names twice, a count whose
+// distribution needs more frequencies than one call takes
+bool check_count_dist(const Options &o, const Ped &ped) {
+  if (!o.count_given) {
+    std::cout << "-countOf belongs to -countDist carriers|alleles|homalt, which was not given." << std::endl;
+    return false;
+  }
+  const int *score = count_kind_scores(o.count_kind);
+  if (!score) {
+    std::cout << "-countDist takes carriers, alleles or homalt, not \"" << o.count_kind << "\"." << std::endl;
+    return false;
+  }
+  vector<uint8_t> counted;
+  if (!counted_members(o, ped, counted)) return false;
+  const int D = score[2] * int(std::count(counted.begin(), counted.end(), 1)), tables = (D + 1) / 2 + 1;
+  if (tables > FAMSEQ_MAX_CWEIGHTS) {
+    std::cout << "-countDist " << o.count_kind << ": the count reaches D = " << D << ", whose distribution needs " << tables
+              << " frequencies; one call takes at most " << FAMSEQ_MAX_CWEIGHTS << ". Count fewer members (-countOf)." << std::endl;
+    return false;
+  }
+  return true;
 }
 
 // -afEM's own options: -afStart without it, a step count or a start value out of range
@@ -2588,6 +2735,16 @@ const SideRow kSide[kSides] = {
               "configuration of the whole family\">" << std::endl;
      },
      ":JGQ", ":NA", [](const VcfRun &r) { return SideBytes{24 * size_t(r.ped.n()), 16}; }, /*report=*/false, /*info_too=*/true},
+    // (on: either of its options, so that main can say which one is missing; its first array: the distribution, D + 1 doubles)
+    {kCountDist, "-countDist", "famseq_charfn", true, [](const Options &o) { return o.count_given || o.count_of_given; },
+     [](Options &o) { o.count_given = o.count_of_given = false; }, check_count_dist,
+     [](std::ostream &out, const Options &o) {
+       out << "##INFO=<ID=PCD,Number=.,Type=Float,Description=\"Posterior distribution of the number of "
+           << (o.count_kind == "carriers" ? "carriers of the variant" : (o.count_kind == "alleles" ? "alternate alleles" : "homozygous-alternate members"))
+           << " among " << (o.count_of_given ? "the members " + o.count_of : string("all members")) << " of the family: the probabilities of 0, 1, ... "
+              "given the whole family's data, each to 1e-12 absolute (.: the site failed)\">" << std::endl;
+     },
+     nullptr, nullptr, [](const VcfRun &r) { return SideBytes{8 * (size_t(r.count_D) + 1), 0}; }},
 };
 
 // `FamSeq vcf` and `FamSeq pack`: the wiring of a VcfRun's stages
@@ -2832,6 +2989,11 @@ void help() {
             << "\t\tsample has another genotype (99999: none has any probability), to every sample column, and JP2, the posterior of the" << std::endl
             << "\t\tsecond most probable configuration, to the INFO column. With or without -map. Implies -method 2; may be combined with" << std::endl
             << "\t\tevery other option above, under -afTagAll with the line's prior; not with -afTag." << std::endl
+            << "-countDist KIND\t(vcf) KIND carriers, alleles or homalt, optionally with -countOf ID[,ID...] (PED IDs; default every member): add PCD," << std::endl
+            << "\t\tthe exact posterior distribution of the number of members who carry the variant / of alt alleles they hold between" << std::endl
+            << "\t\tthem / of hom-alt members, p0,p1,...,pD given the whole family's data, each to 1e-12 absolute (. where the site failed);" << std::endl
+            << "\t\tat most " << 2 * FAMSEQ_MAX_CWEIGHTS - 1 << " values. alleles sums the genotype indices as coded: a male's genotype 2 at a chrX site counts 2." << std::endl
+            << "\t\tImplies -method 2; may be combined with every other option above, under -afTagAll with the line's prior; not with -afTag." << std::endl
             << "pack\t\tFamSeq pack -vcfFile f -pedFile p -output f.fspl: write the computable sites as packed integer PLs." << std::endl
             << "PL\t\tFamSeq PL -plFile f.fspl -pedFile p -output o [-binOutput]: call variants from a packed PL file" << std::endl
             << "\t\t(-binOutput: write a packed result file instead of text)." << std::endl

@@ -67,6 +67,19 @@ int check_weights(famseq_ctx *c, const void *table, int32_t n_weights, int64_t) 
     }
   return 0;
 }
+int check_cweights(famseq_ctx *c, const void *table, int32_t n_tables, int64_t) {
+  const double *cw = static_cast<const double *>(table);
+  const size_t N = c->model.n_members;
+  for (size_t i = 0, n = size_t(n_tables) * 6 * N; i < n; ++i)
+    if (!(cw[i] >= -1.79769313486231570815e308 && cw[i] <= 1.79769313486231570815e308)) {
+      char v[40];
+      std::snprintf(v, sizeof v, "%g", cw[i]);
+      return fail(c, FAMSEQ_E_ARG, "a complex weight is a pair of finite numbers: weight table " + std::to_string(i / (6 * N)) + ", member " +
+                                       std::to_string(i / 6 % N) + ", genotype " + std::to_string(i / 2 % 3) + ", " +
+                                       (i % 2 ? "imaginary" : "real") + " part is " + v);
+    }
+  return 0;
+}
 
 #define FS_STR_(x) #x
 #define FS_STR(x) FS_STR_(x)
@@ -133,6 +146,11 @@ SideTable &side_table() {
       {"maxmarg", "max-marginals", "1", K_MAXMARG, K_MAXMARG_PRIOR, 1, kMaxmargVariants,
        [](const Model &m, int v, int, bool site_prior) { return maxmarg_source(m, v, site_prior); },
        [](const Model &m, int, size_t row[2]) { row[0] = 3 * size_t(m.n_members) * sizeof(double), row[1] = 2 * sizeof(double); }},  // maxmarg[N][3], top[2]
+      {"charfn", "count characteristic function", "1", K_CHARFN, K_CHARFN_PRIOR, 1, kCharfnVariants,
+       [](const Model &m, int v, int, bool site_prior) { return charfn_source(m, v, site_prior); },
+       [](const Model &, int n_tables, size_t row[2]) { row[0] = 2 * size_t(n_tables) * sizeof(double), row[1] = sizeof(double); },  // cf[M][2], loglik
+       {X_CALL, "tn", "n_tables", 1, FAMSEQ_MAX_CWEIGHTS, "cweights", "n_tables tables of three complex numbers per member", check_cweights,
+        [](const Model &m) { return 6 * size_t(m.n_members) * sizeof(double); }, nullptr, "d_cweights", nullptr, charfn_served}},
   };
   return table;
 }
@@ -310,6 +328,13 @@ int origin_model(famseq_ctx *c) {
   if (c->origin_state > 0) return 0;
   return fail(c, FAMSEQ_E_ARG, "phase by transmission: there is no allele-level model for custom transmission tables (the model's pcp2, pcp2Xf and "
                                "pcp2Xm are not famseq_transmission_tables of one mutation rate)");
+}
+
+int charfn_served(famseq_ctx *c) {
+  if (have(c, c->kern[K_CHARFN]) || have(c, c->kern[K_CHARFN_PRIOR])) return 0;  // (a kernel that exists was generated for it)
+  std::string why;
+  if (elim_supported(c->model, &why)) return 0;
+  return fail(c, FAMSEQ_E_ARG, std::string(side_table()[SIDE_CHARFN].what) + " (sum-product engine): " + why);
 }
 
 int load_or_fail(famseq_ctx *c, int kind) {

@@ -25,10 +25,23 @@ SIDE_PRODUCTS_SINCE = (("mutrate", 1, True), ("origin", 1, True), ("weight", 1, 
 # ... and since tests/_edge.py's matrix was drawn up over those two (its own GPU tests: tests/test_gpu_maxmarg.py); build()
 # pre-builds this list as it does the others
 SIDE_PRODUCTS_LATER = (("maxmarg", 1, True),)
+# ... and since tests/golden/generated_sources_later.json was written over that one (tests/test_generated_sources_later.py pins the
+# list with the manifest: a manifest that exists is a yardstick and is not rewritten): the characteristic-function kernel, whose
+# texts tests/golden/generated_sources_newer.json records (tools/source_digests.py --newer) and whose own GPU tests are
+# tests/test_gpu_charfn.py; build() pre-builds this list as it does the others
+SIDE_PRODUCTS_NEWER = (("charfn", 1, True),)
 # The pedigrees tests/test_gpu_maxmarg.py and tests/test_cli_mapq_gpu.py run beside the lists above (side_variant_pedigree's
 # names and wide<n>; random0 and random6 are test_gpu_map.py's loop0 and loop1): build() compiles the max-marginal kernel and its
 # site-prior sibling for each, so that no test waits for a compiler on the device
 MAXMARG_PEDIGREES = ("trio", "quad", "ped5", "ped10", "ped15", "random0", "random6", "wide24", "wide64")
+# The pedigrees tests/test_gpu_charfn.py and tests/test_cli_countdist_gpu.py run (side_variant_pedigree's names, an
+# EDGE_PEDIGREES name, or fam<k>: tests/golden/testdata/fam<k>.ped): build() compiles the characteristic-function kernel and its
+# site-prior sibling for each, and the evidence and pattern kernels the tests compare them with, so that no test waits for a
+# compiler on the device.  random0 / random99 have one and two conditioned members, loop20 three; wide24 / wide25 are the two
+# sides of the kernel's lean threshold (csrc/elim_codegen.cpp, kCharfnLeanFrom), edge39 / edge40 of every other side product's.
+CHARFN_PEDIGREES = ("trio", "quad", "ped10", "cousins", "random15", "random0", "random99", "wide24", "wide25", "edge39", "edge40", "loop20",
+                    "fam01")
+CHARFN_LEAN_FROM = 25
 
 
 # The pedigrees on which the lane kernel's variants 4-11 (csrc/enum_codegen.h: 4-7 the once-per-site form, 8-11 the outer-leaf
@@ -91,6 +104,21 @@ def edge_pedigree(name):
     ped = grow_pedigree(np.random.RandomState(seed), n, allow_loops=loops)
     ped.relations()
     return ped
+
+
+def charfn_pedigree(name):
+    """A pedigree of CHARFN_PEDIGREES."""
+    import os
+
+    from .pedigree import read_ped
+
+    if name in EDGE_PEDIGREES:
+        return edge_pedigree(name)
+    if name.startswith("fam"):
+        ped = read_ped(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "testdata", name + ".ped"))
+        ped.relations()
+        return ped
+    return side_variant_pedigree(name)
 
 
 def lane_form_pedigree(name):

@@ -851,6 +851,73 @@ int famseq_weight_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const dou
                                      const double *d_weights, int32_t n_weights, double *d_wt_loglik, double *d_loglik,
                                      uint8_t *d_status, void *stream);
 
+/* ---- complex per-member weights: the exact distribution of an additive statistic of the family -------------------------------
+ * cf[s][m] = E[ prod_p w_p(g_p) | data ] = Z(lk o w_m) / Z(lk), a complex number, for up to FAMSEQ_MAX_CWEIGHTS tables of complex
+ * weights at once.  With w_p(g) = exp(i theta c_p(g)) it is the posterior characteristic function of the count sum_p c_p(g_p) at
+ * theta; at the M = D + 1 roots of unity (D the count's largest value) an inverse DFT of length M gives the count's distribution,
+ * well conditioned where recovering it from famseq_weight_batch's real points t^count is not.  The table conjugate to another
+ * gives the conjugate result, so a caller runs the frequencies 0 .. M / 2 alone.
+ *   cweights [n_tables][N][3][2]   member p's weight of genotype g in table m is the complex number at
+ *              cweights[((m * N + p) * 3 + g) * 2 + {0 re, 1 im}], the same for every site of the call; every member has a row,
+ *              sequenced or not.  Finite numbers.
+ *   n_tables                1 .. FAMSEQ_MAX_CWEIGHTS.
+ *   cf [n_sites][n_tables][2]   (Re Z_m / Z0, Im Z_m / Z0): Z0 the network's total weight on the rows as they are, Z_m with
+ *              member p's likelihood entry g taken as the pair (l * w_re, l * w_im).  True divisions; nothing is clamped; a Z_m
+ *              of exactly 0 gives (0.0, 0.0), which is a result.
+ *   loglik [n_sites]        famseq_evidence_batch's bits on the rows as they are (the prior form: famseq_evidence_prior_batch's).
+ *   status [n_sites]        0 OK; 1 the single-posterior failure rule of famseq_bn_batch, applied to the rows as given; 2 Z0 is
+ *              <= 0 or not finite.  Wherever status != 0, both parts of every cf entry and loglik of the site are NaN.  There is
+ *              no -LRC shortcut.
+ * The contract.  Bit for bit: a column depends on neither n_tables nor the other tables; equal tables give equal bits; the table
+ * conjugate to another gives the conjugate result, as numbers (every operation of the pass is odd or even in the imaginary parts;
+ * an imaginary part of zero may be +0.0 in both: the sums over a looped pedigree's conditioned members start from +0.0); a table
+ * whose imaginary parts are all +0.0 and whose real parts are >= 0 gives imaginary parts of exactly +0.0; if its real parts are
+ * 0.0 or 1.0, cf.re is famseq_pattern_batch's pat_post of the masks with those bits, hence a table of (1, 0) entries gives
+ * exactly (1.0, +0.0); packed and fp64 input give the same bits; a site's result does not depend on the batch, its chunking or
+ * the launch; every variant of the kernel gives the same bits.
+ * To rounding, ABSOLUTE: |cf - exact| <= 1e-12 * A, A = Z(lk o |w|) / Z(lk), which is 1 for weights of unit modulus.  Every
+ * configuration's term is a product of at most about 6 N rounded factors and the terms' moduli add up to A * Z, which bounds
+ * the error by 6 N * 1.1e-16 * A (3e-14 at 48 members); the terms cancel, so no relative accuracy is promised: a count
+ * distribution recovered from cf is good to 1e-12 in each probability, not in each probability's digits.  For the relative
+ * accuracy of a tail event (nobody carries the variant; every affected member does) famseq_pattern_batch remains the entry.
+ * One kernel launch reads a site's rows once, runs the real sum pass on them and then the complex sum pass n_tables times (every
+ * message a pair of doubles; transmission entries, priors and scales real), a pass's weights arriving through a wave-uniform
+ * pointer.  Served by the sum-product engine's graph as famseq_evidence_batch is, whatever the context's engine: loop-free
+ * pedigrees of any size, loops up to three conditioned members.  Compiled on the first call or ahead through famseq_set_option
+ * "charfn_kernels" = 1 (a context without a device generates and cross-compiles it).  famseq_plan_json: "charfn_code_object",
+ * "charfn_variant".
+ * FAMSEQ_E_ARG, with a message and before the device is asked for: n_tables outside 1 .. FAMSEQ_MAX_CWEIGHTS, cweights /
+ * d_cweights NULL, (host entries) the first entry that is not finite ("... weight table 2, member 1, genotype 0, imaginary part
+ * is nan"), a pedigree the engine does not serve (the engine's message). */
+#define FAMSEQ_MAX_CWEIGHTS 64
+
+/* Host buffers, blocking, chunked and pipelined; inputs as famseq_evidence_batch.  cweights is a host array; the library checks
+ * it and stages it on the stream the chunks' kernels run on.  Any of cf / loglik / status may be NULL; without cf only the real
+ * pass runs. */
+int famseq_charfn_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                        int32_t n_seq, const uint8_t *flags, const double *cweights /*[n_tables][N][3][2]*/, int32_t n_tables,
+                        double *cf /*[n_sites][n_tables][2]*/, double *loglik /*[n_sites]*/, uint8_t *status);
+
+/* The same on device buffers resident on ctx's device (seq_members is a host array), d_cweights among them — it must stay valid
+ * and unchanged until the kernel has run, and nothing is checked of its contents: the kernel indexes nothing by them.  Enqueues
+ * on `stream` (a hipStream_t; NULL = the default stream) and returns without synchronising (the stream rule at
+ * famseq_bn_batch_device: with d_lk no context state, no event and no wait; with d_pl16 through the kept scratch rows, like every
+ * side entry). */
+int famseq_charfn_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                               const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_cweights,
+                               int32_t n_tables, double *d_cf, double *d_loglik, uint8_t *d_status, void *stream);
+
+/* With the founders' genotype prior given per site: prior[n_sites][6], as for famseq_evidence_prior_batch.  Given rows that equal
+ * the model's constants the outputs are, bit for bit, famseq_charfn_batch's.  "charfn_prior_kernels" = 1 builds the kernel
+ * (famseq_charfn_prior) ahead; famseq_plan_json: "charfn_prior_code_object", "charfn_prior_variant". */
+int famseq_charfn_prior_batch(famseq_ctx *ctx, int64_t n_sites, const double *lk, const uint16_t *pl16, const int32_t *seq_members,
+                              int32_t n_seq, const uint8_t *flags, const double *prior, const double *cweights, int32_t n_tables,
+                              double *cf, double *loglik, uint8_t *status);
+int famseq_charfn_prior_batch_device(famseq_ctx *ctx, int64_t n_sites, const double *d_lk, const uint16_t *d_pl16,
+                                     const int32_t *seq_members, int32_t n_seq, const uint8_t *d_flags, const double *d_prior,
+                                     const double *d_cweights, int32_t n_tables, double *d_cf, double *d_loglik,
+                                     uint8_t *d_status, void *stream);
+
 /* ---- max-marginals and the runner-up: the quality of the joint MAP call -----------------------------------------------------
  * famseq_map_batch gives the most probable configuration g* and its posterior; this entry says what holds the rest.  With w as
  * for famseq_map_batch and Z = sum_g w(g), by max-product message passing in both directions (no back-pointers) on the

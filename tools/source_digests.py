@@ -11,6 +11,7 @@ regenerates the matrix and compares.
     python tools/source_digests.py OUT.json --dump DIR   # ... and every source text, one file per case: run it on two commits
                                                          # and `diff -r` the directories to see what changed
     python tools/source_digests.py --later OUT.json      # the manifest of the products added since (LATER_STEMS, below)
+    python tools/source_digests.py --newer OUT.json      # ... and of those added since that one was written (NEWER_STEMS)
 
 The sources are obtained the way the host tests obtain them: a plan-only context with FAMSEQ_JIT_SOURCE_ONLY,
 FAMSEQ_KEEP_SRC and a scratch FAMSEQ_KERNEL_CACHE; FAMSEQ_VARIANT_ONLY forces the variant; the .hip file is read next to
@@ -29,7 +30,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import famseq_amd as fs  # noqa: E402
-from famseq_amd.prebuild_sets import (EDGE_PEDIGREES, SIDE_PRODUCTS, SIDE_PRODUCTS_LATER, SIDE_PRODUCTS_SINCE, SIDE_VARIANTS,  # noqa: E402
+from famseq_amd.prebuild_sets import (EDGE_PEDIGREES, SIDE_PRODUCTS, SIDE_PRODUCTS_LATER, SIDE_PRODUCTS_NEWER, SIDE_PRODUCTS_SINCE,  # noqa: E402
+                                      SIDE_VARIANTS,
                                       edge_pedigree, random_pedigree, wide_pedigree)
 
 TWO_CUT_SEED = 99  # the first random_pedigree seed whose loops need exactly two conditioned members (seeds 0..117 searched)
@@ -73,6 +75,10 @@ SIDE_STEMS = tuple((stem, has_prior) for stem, _, has_prior in SIDE_PRODUCTS + S
 # SIDE_PEDIGREES, cases "<stem>/<v>" and "<stem>_prior/<v>" as in the side layer and nothing else (later_digests(name)).
 # tests/golden/generated_sources_later.json holds it; tests/test_generated_sources_later.py compares.
 LATER_STEMS = tuple((stem, has_prior) for stem, _, has_prior in SIDE_PRODUCTS_LATER)
+# A fourth layer, for the same reason in a manifest of its own: the rows gained since the third layer's manifest was written
+# (prebuild_sets.SIDE_PRODUCTS_NEWER), the same cases on the same pedigrees (later_digests(name, NEWER_STEMS)).
+# tests/golden/generated_sources_newer.json holds it; tests/test_generated_sources_newer.py compares.
+NEWER_STEMS = tuple((stem, has_prior) for stem, _, has_prior in SIDE_PRODUCTS_NEWER)
 REFUSED = "refused"  # recorded in the digest's place where the generator declines the pedigree (sample_source: LDS rows)
 
 # One case per tuning switch at a value that is not its default, in a kernel family that reads it: (switch, value, pedigree,
@@ -145,9 +151,9 @@ def _side_digest(ctx, key):
     return _digest(ctx.plan(), key + "_code_object")
 
 
-def _one_variant(ped, v, env, side=False, later=False):
+def _one_variant(ped, v, env, side=False, later=None):
     """Every kernel family's source in variant v (the families that have that many variants), under `env`; side: the side
-    layer's families too; later: the third layer's families and no others."""
+    layer's families too; later: the families of that layer (LATER_STEMS or NEWER_STEMS) and no others."""
     out = {}
     cache = tempfile.mkdtemp(prefix="famseq_digests_")
     base = dict(FAMSEQ_KERNEL_CACHE=cache, FAMSEQ_JIT_SOURCE_ONLY="1", FAMSEQ_KEEP_SRC="1", FAMSEQ_QUIET="1", FAMSEQ_VARIANT_ONLY=str(v))
@@ -156,7 +162,7 @@ def _one_variant(ped, v, env, side=False, later=False):
             model = fs.make_model(ped)
             if later:
                 ctx = fs.Context(model, device=-1)
-                for stem, has_prior in LATER_STEMS:
+                for stem, has_prior in later:
                     for key in [stem] + ([stem + "_prior"] if has_prior else []):
                         out["%s/%d" % (key, v)] = _side_digest(ctx, key)
                 ctx.close()
@@ -219,19 +225,20 @@ def digests(name, side=False):
     return out
 
 
-def later_digests(name):
-    """{case: sha256} of pedigree `name` in the third layer: LATER_STEMS' families in every fence level."""
+def later_digests(name, stems=LATER_STEMS):
+    """{case: sha256} of pedigree `name` in the third layer (stems = NEWER_STEMS: the fourth): the families of `stems` in every
+    fence level."""
     ped = _named(name)
     ped.relations()
-    return {"%s %s" % (name, k): d for v in range(SIDE_VARIANTS) for k, d in _one_variant(ped, v, {}, later=True).items()}
+    return {"%s %s" % (name, k): d for v in range(SIDE_VARIANTS) for k, d in _one_variant(ped, v, {}, later=stems).items()}
 
 
 def main():
     global TEXTS
-    if len(sys.argv) == 3 and sys.argv[1] == "--later":
+    if len(sys.argv) == 3 and sys.argv[1] in ("--later", "--newer"):
         out = {}
         for name in SIDE_PEDIGREES:
-            out.update(later_digests(name))
+            out.update(later_digests(name, LATER_STEMS if sys.argv[1] == "--later" else NEWER_STEMS))
         with open(sys.argv[2], "w") as f:
             f.write(json.dumps(out, indent=0, sort_keys=True) + "\n")
         print("%s: %d cases over %d pedigrees" % (sys.argv[2], len(out), len(SIDE_PEDIGREES)))
